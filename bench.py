@@ -10,11 +10,13 @@ rocprofv3 --pmc passes (profiles/traffic.json), scaled to this launch.  Workload
 '((.*.))', x0 with lambda = (1,1) so the energy terms are exercised; the 10 000 sequences are sharded
 over the N ranks (strong scaling, as the metric is quoted).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself (a child `torch.distributed.run`,
 started before this process touches the GPU); under a launcher WORLD_SIZE must equal --gpus or the run is refused.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` then writes what the last timed step returned to its caller -- fn, gr,
+sum_eff, n_skipped of ShardedTrainer -- as DIR/<name>.npy (float64); the inputs are seeded, so two builds can be compared array
+by array.
 """
 import argparse
 import json
@@ -83,6 +85,15 @@ def cpu_baseline(seqs, quals, x, n_theta):
             "sample": "%d of the %d sequences, 1 eval, %d threads (%s, BPP filter included)" % (s_all, len(seqs), cores, what),
             "one_thread": {"value": v_one, "unit": "seq/s", "cores": 1,
                            "sample": "%d of the %d sequences, 1 eval, 1 thread (%s, BPP filter included)" % (s_one, len(seqs), what)}}
+
+
+def dump_outputs(path, fn, gr, sum_eff, n_skipped):
+    """--dump-outputs: the four results of one evaluation as path/<name>.npy, float64 (a few hundred bytes in all)."""
+    os.makedirs(path, exist_ok=True)
+    out = {"fn": fn, "gr": gr, "sum_eff": sum_eff, "n_skipped": n_skipped}
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
+    return sorted(out)
 
 
 def scan_algorithmic_bytes_per_seq(L, S, W=MAX_SPAN):
@@ -286,7 +297,11 @@ def main():
     ap.add_argument("--serial-passes", action="store_true",
                     help="everything on one stream (for kernel traces: with concurrent streams kernels overlap and their durations no "
                          "longer add up to the pipeline time)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write fn, gr, sum_eff, n_skipped of the last one as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # launch the ranks as a CHILD; this parent never touches torch or HIP (the GPUs are counted from the kernel driver's
@@ -392,6 +407,9 @@ def main():
                      "log_space_fallback_sequences": int(eng.last_timing()[2]),
                      "kernel_ms": k_s * 1e3, "algorithmic_bytes_per_launch": alg},
     }
+    if args.dump_outputs:
+        line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs),
+                                "arrays": dump_outputs(args.dump_outputs, fn, gr, eff, nsk)}
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(seqs, quals, x, eng.n_param - 2)
     if secondary:

@@ -249,3 +249,19 @@ def test_bench_launcher_builds_the_torchrun_command_and_refuses_a_wrong_world():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "GPU" in (r.stderr + r.stdout) and "{" not in r.stdout
+
+
+def test_bench_dumps_the_outputs_of_a_step_and_refuses_zero_steps(tmp_path):
+    """--dump-outputs DIR: fn, gr, sum_eff, n_skipped of one evaluation as DIR/<name>.npy in float64, values unchanged;
+    --steps 0 is refused before any GPU work (ms_per_step would be undefined)."""
+    sys.path.insert(0, REPO)
+    import bench
+    gr = np.linspace(-1.0, 1.0, 22)
+    names = bench.dump_outputs(str(tmp_path / "out"), 77.5, gr, 9999.25, 3)
+    assert names == ["fn", "gr", "n_skipped", "sum_eff"]
+    got = {n: np.load(str(tmp_path / "out" / (n + ".npy"))) for n in names}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["fn"] == 77.5 and got["sum_eff"] == 9999.25 and got["n_skipped"] == 3 and np.array_equal(got["gr"], gr)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0", "--dump-outputs", str(tmp_path / "z")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr and "{" not in r.stdout and not os.path.exists(str(tmp_path / "z"))
