@@ -184,6 +184,19 @@ typedef struct {
 } elemdp_scan_out;
 int elemdp_scan(elemdp_handle* h, const double* x, int32_t n_param, elemdp_scan_out* out);
 
+/* Base-pair probabilities of the resident batch under the motif model x: for every kept pair (i, j = i + d) of the BPP filter,
+ * P(i, j) = sum over the interval states s of inside(i, j, P, s) * outside(i, j, P, s) / Z(ari, nasi) over the tables of the
+ * scan's first sum pass (the motif-model counterpart of EnergyModel::lnBPP, energy_model.hpp:195-201, over
+ * motif_scanner.hpp:186-192); bases i and j-1 (0-based) pair.  Keeps on the device the pairs with P >= min_prob (min_prob >= 0;
+ * 0 = every kept pair) in (sequence, i, j) order and returns their number in *n_pairs; unpaired: NULL or seq_off indexing
+ * (L values per sequence), unpaired(p) = 1 - the P of the pairs base p takes part in.  elemdp_last_timing afterwards:
+ * [whole call, sum passes + pair kernels, sequences handed to the log-space form]. */
+int elemdp_pair_posteriors(elemdp_handle* h, const double* x, int32_t n_param, double min_prob,
+                           int64_t* n_pairs, double* unpaired);
+/* Copies the list of the last elemdp_pair_posteriors: seq (batch index), i, j (cell, j = i + d), p; any may be NULL.
+ * cap < n_pairs is ELEMDP_EINVAL; before any elemdp_pair_posteriors (of the resident batch) ELEMDP_ESTATE. */
+int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap);
+
 /* timing of the last train evaluation, measured with HIP events on the engine's stream:
  * ms[0] = whole evaluation, ms[1] = the DP pipeline only (all kernels of the inside/outside sweeps),
  * ms[2] = number of sequences the scaled-linear pipeline handed to the log-space pipeline (range check) */

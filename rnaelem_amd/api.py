@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -81,6 +81,8 @@ def load_library():
         L.elemdp_train_seq_stats.argtypes = [hp, dp, C.c_int32]
         L.elemdp_debug_tables.argtypes = [hp] + [dp] * 7
         L.elemdp_scan.argtypes = [hp, dp, C.c_int32, C.POINTER(ScanOut)]
+        L.elemdp_pair_posteriors.argtypes = [hp, dp, C.c_int32, C.c_double, C.POINTER(C.c_int64), dp]
+        L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
         L.elemdp_last_timing.argtypes = [hp, dp, C.c_int32]
         L.elemdp_epoch_permutation.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
         L.elemdp_kmer_shuffle.argtypes = [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
@@ -283,6 +285,23 @@ class Engine:
             recs.append(dict(start=start[a:b], inner=inner[a:b], end=end[int(qoff[k]):int(qoff[k + 1])], psihat=psi[a:b],
                              rss=raw[a:b], Ys=int(ys[k]), Ye=int(ye[k]), exist_prob=float(ex[k])))
         return recs, en
+
+    # ---- base-pair posteriors under the motif model
+    def pair_posteriors(self, x, min_prob=0.0):
+        """One entry per sequence: (i, j, p, unpaired) -- the cells (i, j = i + d) whose bases i and j-1 (0-based) pair with
+        probability p >= min_prob, in (i, j) order, and the probability that each base is unpaired."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        unp = np.zeros(max(int(off[-1]), 1))
+        m = C.c_int64()
+        self._check(self._lib.elemdp_pair_posteriors(self._h, _dp(x), self.n_param, float(min_prob), C.byref(m), _dp(unp)))
+        n = m.value
+        seq, ii, jj = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
+        p = np.zeros(max(n, 1))
+        self._check(self._lib.elemdp_pair_list(self._h, _i32(seq), _i32(ii), _i32(jj), _dp(p), max(n, 1)))
+        bounds = np.searchsorted(seq[:n], np.arange(self.n_seq + 1))
+        return [(ii[a:b].copy(), jj[a:b].copy(), p[a:b].copy(), unp[int(off[k]):int(off[k + 1])].copy())
+                for k, (a, b) in enumerate(zip(bounds[:-1], bounds[1:]))]
 
     def last_timing(self):
         """[ms whole evaluation, ms DP pipeline, sequences re-evaluated in log space]"""

@@ -3,6 +3,8 @@
 
     python -m rnaelem_amd.cli train --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --no-shuffle [-i 300]
     python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw
+    python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-pairs pairs.txt
+                                    # + base-pair posteriors under the motif model (--pair-min-prob, default 1e-3)
     python -m rnaelem_amd.cli       --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --out2 scan.raw
                                     # no sub-command = what script/elem spawns: train, write the model, scan (main.cpp:47-84)
     python -m rnaelem_amd.cli eval  --fastq pos.fq --motif-model model.txt --out1 fn.txt --out2 gr.txt     (motif_eval.hpp:23-54)
@@ -42,6 +44,9 @@ def build_parser():
         sub.choices[name].add_argument("--chunk", type=int, default=20000,
                                        help="sequences resident on the GPU at a time (plan + tables; BASELINE config E = 100 k x L=300 "
                                             "does not fit at once)")
+    sub.choices["scan"].add_argument("--out-pairs", default=None,
+                                     help="base-pair posteriors under the motif model: one record per sequence (io.pair_record)")
+    sub.choices["scan"].add_argument("--pair-min-prob", type=float, default=1e-3, help="pairs below this probability are left out")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -165,32 +170,49 @@ def cmd_train(a):
         dist.destroy_process_group()
 
 
-def sharded_scan(recs, out1, rank, world, scan_part, barrier):
-    """Scan needs no collective (SURVEY.md section 8e): rank k scans the contiguous range assigned_range(n, world, k) and writes
-    `<out1>.<k>`; after a barrier rank 0 joins the parts in rank order = input order into `out1` (the reference's writer
-    emits records as its threads finish, motif_scanner.hpp:237-252; here the order is the input's).  `scan_part(records)`
-    yields the record texts of a list of (id, codes, quals)."""
+def sharded_write(recs, outs, rank, world, part, barrier):
+    """Rank k handles the contiguous range assigned_range(n, world, k): `part(records)` yields one tuple of texts per record, one
+    text per file of `outs`, written to `<out>.<k>`; after a barrier rank 0 joins the parts of every file in rank order = input
+    order."""
     from .distributed import assigned_range
     lo, hi = assigned_range(len(recs), world, rank)
-    out = out1 if world == 1 else "%s.%d" % (out1, rank)
-    with open(out, "w") as f:
-        for text in scan_part(recs[lo:hi]):
-            f.write(text)
+    names = list(outs) if world == 1 else ["%s.%d" % (o, rank) for o in outs]
+    files = [open(nm, "w") for nm in names]
+    try:
+        for texts in part(recs[lo:hi]):
+            for f, t in zip(files, texts):
+                f.write(t)
+    finally:
+        for f in files:
+            f.close()
     if world == 1:
         return
     barrier()
     if rank == 0:
-        with open(out1, "w") as f:
-            for k in range(world):
-                part = "%s.%d" % (out1, k)
-                with open(part) as g:
-                    for line in g:
-                        f.write(line)
-                os.remove(part)
+        for o in outs:
+            with open(o, "w") as f:
+                for k in range(world):
+                    name = "%s.%d" % (o, k)
+                    with open(name) as g:
+                        for line in g:
+                            f.write(line)
+                    os.remove(name)
     barrier()
 
 
-def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier):
+def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
+    """Scan needs no collective (SURVEY.md section 8e): rank k scans the contiguous range assigned_range(n, world, k) and writes
+    `<out1>.<k>`; after a barrier rank 0 joins the parts in rank order = input order into `out1` (the reference's writer
+    emits records as its threads finish, motif_scanner.hpp:237-252; here the order is the input's).  `scan_part(records)`
+    yields the record texts of a list of (id, codes, quals); with `out_pairs` it yields (scan record, pair record) tuples and
+    the pair records are joined into `out_pairs` the same way."""
+    if out_pairs is None:
+        sharded_write(recs, [out1], rank, world, lambda mine: ((t,) for t in scan_part(mine)), barrier)
+    else:
+        sharded_write(recs, [out1, out_pairs], rank, world, scan_part, barrier)
+
+
+def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3):
     nodes = eng.describe()["node"]
     step = max(1, chunk)
 
@@ -199,10 +221,15 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier):
             part = mine[c0:c0 + step]
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
-            for (rid, codes, _), r in zip(part, res):
-                yield io.scan_record(rid, codes, r, nodes)
+            if out_pairs is None:
+                for (rid, codes, _), r in zip(part, res):
+                    yield io.scan_record(rid, codes, r, nodes)
+                continue
+            prs = eng.pair_posteriors(m["x"], pair_min_prob)   # (the same loaded batch)
+            for (rid, codes, _), r, (ii, jj, pp, unp) in zip(part, res, prs):
+                yield io.scan_record(rid, codes, r, nodes), io.pair_record(rid, len(codes), (ii, jj, pp), unp)
 
-    sharded_scan(recs, out1, rank, world, scan_part, barrier)
+    sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
 
 
 def cmd_scan(a):
@@ -215,7 +242,7 @@ def cmd_scan(a):
         barrier = dist.barrier
     m = io.read_model(a.motif_model)
     eng = io.engine_from_model(m, a.device if a.device is not None else local_rank)
-    _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier)
+    _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob)
     if world > 1:
         dist.destroy_process_group()
 

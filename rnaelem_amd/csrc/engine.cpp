@@ -238,6 +238,9 @@ class Engine {
   void train_partial(const double* x, int n_param, void* partial, bool device_ptr, bool reduce = false);
   void train_finish(const double* reduced, double* fn, double* gr, double* sum_eff, int32_t* n_skipped);
   void scan(const double* x, int n_param, elemdp_scan_out* out);
+  // base-pair posteriors of the batch under the motif model (pair_rules.h); the list stays on the device for pair_list
+  void pair_posteriors(const double* x, int n_param, double min_prob, int64_t* n_pairs, double* unpaired);
+  void pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap);
   int partial_len() const { return 4 + 2 * au_.n_theta() + 4; }
   void set_option(const std::string& key, double v);
   void comm_init(int rank, int world, const void* id);
@@ -345,6 +348,12 @@ class Engine {
   template <class Work> void stream_chunks(Work work);
   void stream_train(const double* x, int n_param, void* partial, bool device_ptr, bool reduce);
   void stream_scan(const double* x, int n_param, elemdp_scan_out* out);
+  void stream_pairs(const double* x, int n_param, double min_prob, double* unpaired);
+  // pair posteriors: kept pairs per sequence and their prefix (staging ranges), pairs kept by min_prob and their prefix, the
+  // P(i, d) scratch of the table slots, the staging list, the final list of the last call (n_pairs_ < 0: none)
+  DevBuf d_pr_kept_, d_pr_koff_, d_pr_cnt_, d_pr_off_, d_pr_P_, d_pr_unp_, d_pr_si_, d_pr_sj_, d_pr_sp_;
+  DevBuf d_pl_seq_, d_pl_i_, d_pl_j_, d_pl_p_;
+  int64_t n_pairs_ = -1;
 
   Automaton au_;
   EnergyTables et_;
@@ -831,6 +840,7 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   // a rejected batch leaves the handle without a batch (ELEMDP_ESTATE for what follows) instead of the new sizes over the old
   // device buffers
   n_seq_ = 0;
+  n_pairs_ = -1;
   streaming_ = false;
   if (n > 0 && seq && off && qual && qoff && should_stream(off, n)) { stream_setup(seq, off, qual, qoff, fix, n); return; }
   if (n <= 0 || !seq || !off || !qual || !qoff) throw ArgError("load_batch: empty batch or null pointer");
@@ -1979,6 +1989,213 @@ void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
 }
 
 
+// ---- base-pair posteriors under the motif model (pair_rules.h).  The scan's first sum pass per group, the pair
+// reduction on the group's table slots right behind it (before the next group of the stream reuses them), the log-space form --
+// the fused scan kernel up to its first outside pass -- for the sequences that leave the double range and under pipeline 3, then
+// the batch list in (sequence, i, j) order: prefix over the per-sequence counts, scatter out of the staging ranges.
+void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, int64_t* n_pairs, double* unpaired) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (!n_pairs) throw ArgError("pair_posteriors: null n_pairs");
+  if (!(min_prob >= 0.)) throw ArgError("pair_posteriors: min_prob must be >= 0");
+  n_pairs_ = -1;
+  if (streaming_) { stream_pairs(x, n_param_in, min_prob, unpaired); *n_pairs = n_pairs_; return; }
+  if (n_seq_ <= 0) throw StateError("pair_posteriors before load_batch");
+  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+  upload_params(x, lay_, false);
+  const int n = n_seq_, S = au_.S();
+  const size_t n_seqpos = (size_t)h_seq_off_[n], n_pos = n_seqpos + n;
+  const size_t pcells = (size_t)(Lmax_ + 1) * (Wmax_ + 1);   // P(i, d) of one table slot
+  DevBuf d_start, d_inner, d_end, d_ys, d_ye, d_exist;        // what the first sum pass writes besides its tables
+  d_start.alloc(8 * n_seqpos); d_inner.alloc(8 * n_seqpos); d_end.alloc(8 * n_pos);
+  d_ys.alloc(4 * n); d_ye.alloc(4 * n); d_exist.alloc(8 * n);
+  d_pr_kept_.alloc(8 * (size_t)n); d_pr_koff_.alloc(8 * ((size_t)n + 1));
+  d_pr_cnt_.alloc(8 * (size_t)n); d_pr_off_.alloc(8 * ((size_t)n + 1));
+  d_pr_unp_.alloc(8 * n_seqpos);
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  // staging ranges: a sequence's list holds at most its kept pairs
+  HIP_OK(launch_pair_kept(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, d_pr_kept_.as<int64_t>(), st_));
+  HIP_OK(launch_pair_prefix(d_pr_kept_.as<int64_t>(), n, d_pr_koff_.as<int64_t>(), st_));
+  int64_t n_kept = 0;
+  HIP_OK(hipMemcpyAsync(&n_kept, d_pr_koff_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  d_pr_si_.alloc(4 * (size_t)n_kept); d_pr_sj_.alloc(4 * (size_t)n_kept); d_pr_sp_.alloc(8 * (size_t)n_kept);
+  HIP_OK(hipMemsetAsync(d_pr_cnt_.as<void>(), 0, 8 * (size_t)n, st_));
+  PairArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.plans = plan_.d_plans.as<SeqPlan>();
+  pa.okbits = d_okbits1_.as<uint32_t>();
+  pa.seq_out = d_seq_out_.as<double>(); pa.out_stride = out_stride_;
+  pa.p_stride = pcells;
+  pa.min_prob = min_prob;
+  pa.unpaired = d_pr_unp_.as<double>();
+  pa.koff = d_pr_koff_.as<int64_t>(); pa.cnt = d_pr_cnt_.as<int64_t>();
+  pa.st_i = d_pr_si_.as<int32_t>(); pa.st_j = d_pr_sj_.as<int32_t>(); pa.st_p = d_pr_sp_.as<double>();
+  std::vector<int32_t> flagged;
+  const bool sums_on_batch = opt_pipeline_ == 4;
+  if (sums_on_batch) {
+    // the scan's first sum pass on the same groups, slots and streams as Engine::scan
+    LinArgs a;
+    group_cap_ = std::max(1024, n_slots_);
+    const int gsz = prepare_lin(a, false, true);
+    group_cap_ = 8192;
+    a.scan = 1;
+    a.ys = d_ys.as<int32_t>(); a.ye = d_ye.as<int32_t>();
+    a.pos_start = d_start.as<double>(); a.pos_inner = d_inner.as<double>(); a.pos_end = d_end.as<double>();
+    a.exist = d_exist.as<double>();
+    HIP_OK(hipMemsetAsync(d_start.as<void>(), 0, 8 * n_seqpos, st_));
+    HIP_OK(hipMemsetAsync(d_inner.as<void>(), 0, 8 * n_seqpos, st_));
+    HIP_OK(hipMemsetAsync(d_seq_out_.as<void>(), 0, sizeof(double) * (size_t)out_stride_ * n, st_));
+    HIP_OK(hipMemsetAsync(d_flagged_.as<void>(), 0, sizeof(int32_t), st_));
+    lin_weights();
+    poison_tables();
+    d_pr_P_.alloc(8 * pcells * (size_t)n_slots_);
+    // the P plane's columns of the real states are 0 .. ncol-1: Automaton::flatten numbers a plane's columns in state order, and
+    // a shadow state comes last
+    int ncol = 0;
+    for (int s = 0; s < a.lay.S; ++s) {
+      const int c = ints_[a.lay.tab_cmap + ST_P * a.lay.S + s];
+      if (s == a.lay.shadow || c < 0) continue;
+      if (c != ncol) throw std::logic_error("pair_posteriors: the P plane's columns are not in state order");
+      ++ncol;
+    }
+    pa.tab_cell = a.lay.tab_cell; pa.p_cs = a.lay.tab_cs[ST_P]; pa.p_rs = a.lay.tab_cell ? a.lay.tab_row : a.lay.tab_rs[ST_P];
+    pa.ncol = ncol;
+    pa.band_stride = a.band_stride;
+    pa.skip_flagged = 1;
+    const int ns = (opt_group_streams_ >= 2 && n >= 128 && n_slots_ >= 128) ? std::min(opt_group_streams_, kMaxGroupStreams) : 1;
+    const int slots_each = n_slots_ / ns;
+    int n_groups = (n + slots_each - 1) / slots_each;
+    if (ns > 1) n_groups = ((n_groups + ns - 1) / ns) * ns;
+    const int gsz2 = (ns == 1) ? gsz : (n + n_groups - 1) / n_groups;
+    need_group_streams(ns);
+    if (ns > 1) {
+      HIP_OK(hipEventRecord(gstart_, st_));
+      for (int k = 1; k < ns; ++k) HIP_OK(hipStreamWaitEvent(gs_[k], gstart_, 0));
+    }
+    int gi = 0;
+    for (int g0 = 0; g0 < n; g0 += gsz2, ++gi) {
+      const int G = std::min(gsz2, n - g0);
+      const int k = gi % ns;
+      hipStream_t st = gs_[k];
+      const size_t k0 = (size_t)k * slots_each;
+      LinArgs ak = a;
+      ak.band_in += k0 * a.band_stride; ak.band_out += k0 * a.band_stride;
+      ak.ext_in += k0 * a.ext_stride; ak.ext_out += k0 * a.ext_stride;
+      ak.zs += 4 * k0;
+      ak.a_in += k0 * a.a_stride; ak.a_out += k0 * a.a_stride;
+      ak.grp = d_order_.as<int32_t>() + g0;
+      ak.plans_slot = d_plans_sorted_.as<SeqPlan>() + g0;
+      const int Lg = h_plans_[h_order_[g0]].L, Wg = std::min(Lg, max_span_);
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, 0, st));
+      PairArgs pk = pa;
+      pk.idx = ak.grp;
+      pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+      pk.P = d_pr_P_.as<double>() + k0 * pcells;
+      HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
+      HIP_OK(launch_pair_seq(pk, G, st));
+    }
+    for (int k = 1; k < ns; ++k) {
+      HIP_OK(hipEventRecord(gdone_[k], gs_[k]));
+      HIP_OK(hipStreamWaitEvent(st_, gdone_[k], 0));
+    }
+    int32_t n_flagged = 0;
+    HIP_OK(hipMemcpyAsync(&n_flagged, d_flagged_.as<void>(), sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipStreamSynchronize(st_));
+    flagged.resize(n_flagged);
+    n_flagged_last_ = n_flagged;
+    tables_linear_ = false;
+  }
+  // ---- the log-space form: the sequences the range check flagged, or every sequence under pipeline 3, in chunks of at most as
+  // many sequences as the table slots hold (the P scratch is bounded by the chunk)
+  const int n_log = sums_on_batch ? (int)flagged.size() : n;
+  if (n_log > 0) {
+    int n_blocks, chunk;
+    if (sums_on_batch) {
+      n_blocks = std::min(std::min(n_slots_, 2 * n_cu_), n);
+      chunk = std::min(n_log, n_slots_);
+    } else {
+      ensure_slots(S, true, n);
+      lin_slots_ = 0;
+      n_blocks = std::min(n_slots_, n);
+      chunk = std::min(n_log, std::max(n_blocks, 1024));
+      d_pr_P_.alloc(8 * pcells * (size_t)chunk);
+    }
+    DpArgs d = base_args(lay_, d_ints_.as<int32_t>(), d_params_.as<double>(), plan_, d_okbits1_.as<uint32_t>(), S);
+    d.lds = lds_layout(lay_, Lmax_, nword_max_, true);
+    d.pair_p = d_pr_P_.as<double>();
+    d.pair_stride = pcells;
+    const int32_t* list = sums_on_batch ? d_flagged_.as<int32_t>() + 1 : d_order_.as<int32_t>();
+    for (int c0 = 0; c0 < n_log; c0 += chunk) {
+      const int C = std::min(chunk, n_log - c0);
+      d.order = list + c0;
+      d.n_seq = C;
+      HIP_OK(hipMemsetAsync(d_counter_.as<void>(), 0, sizeof(int32_t), st_));
+      HIP_OK(launch_dp(DP_SCAN, d, std::min(n_blocks, C), st_));
+      PairArgs pk = pa;
+      pk.idx = list + c0;
+      pk.P = d_pr_P_.as<double>();
+      pk.skip_flagged = 0;
+      HIP_OK(launch_pair_seq(pk, C, st_));
+    }
+  }
+  if (!sums_on_batch) n_slots_ = 0;   // (as after a scan: these slots are not reused by the train pipelines)
+  HIP_OK(hipEventRecord(ev_[3], st_));
+  // ---- the list in (sequence, i, j) order
+  HIP_OK(launch_pair_prefix(d_pr_cnt_.as<int64_t>(), n, d_pr_off_.as<int64_t>(), st_));
+  int64_t total = 0;
+  HIP_OK(hipMemcpyAsync(&total, d_pr_off_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  d_pl_seq_.alloc(4 * (size_t)total); d_pl_i_.alloc(4 * (size_t)total); d_pl_j_.alloc(4 * (size_t)total); d_pl_p_.alloc(8 * (size_t)total);
+  HIP_OK(launch_pair_scatter(d_pr_koff_.as<int64_t>(), d_pr_cnt_.as<int64_t>(), d_pr_off_.as<int64_t>(), d_pr_si_.as<int32_t>(),
+                             d_pr_sj_.as<int32_t>(), d_pr_sp_.as<double>(), n, d_pl_seq_.as<int32_t>(), d_pl_i_.as<int32_t>(),
+                             d_pl_j_.as<int32_t>(), d_pl_p_.as<double>(), st_));
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms_all = 0, ms_dp = 0;
+  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
+  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
+  last_ms[0] = ms_all;
+  last_ms[1] = ms_dp;
+  last_ms[2] = (double)flagged.size();
+  if (unpaired) HIP_OK(hipMemcpy(unpaired, d_pr_unp_.as<void>(), 8 * n_seqpos, hipMemcpyDeviceToHost));
+  n_pairs_ = total;
+  *n_pairs = total;
+}
+
+void Engine::stream_pairs(const double* x, int n_param_in, double min_prob, double* unpaired) {
+  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+  std::vector<int32_t> hs, hi, hj;
+  std::vector<double> hp;
+  last_ms[0] = last_ms[1] = last_ms[2] = 0.;
+  stream_chunks([&](int, int c0, int, Engine& e) {
+    int64_t m = 0;
+    e.pair_posteriors(x, n_param_in, min_prob, &m, unpaired ? unpaired + (h_seq_off_[c0] - h_seq_off_[0]) : nullptr);
+    const size_t b = hs.size();
+    hs.resize(b + m); hi.resize(b + m); hj.resize(b + m); hp.resize(b + m);
+    e.pair_list(hs.data() + b, hi.data() + b, hj.data() + b, hp.data() + b, m);
+    for (size_t t = b; t < hs.size(); ++t) hs[t] += c0;   // (batch-global sequence indices)
+    for (int t = 0; t < 3; ++t) last_ms[t] += e.last_ms[t];
+  });
+  d_pl_seq_.upload(hs, st_); d_pl_i_.upload(hi, st_); d_pl_j_.upload(hj, st_); d_pl_p_.upload(hp, st_);
+  HIP_OK(hipStreamSynchronize(st_));
+  n_pairs_ = (int64_t)hs.size();
+}
+
+void Engine::pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (n_pairs_ < 0) throw StateError("pair_list before pair_posteriors");
+  if (cap < n_pairs_) throw ArgError("pair_list: buffer too small");
+  const size_t m = (size_t)n_pairs_;
+  if (m == 0) return;
+  if (seq) HIP_OK(hipMemcpy(seq, d_pl_seq_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (i) HIP_OK(hipMemcpy(i, d_pl_i_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (j) HIP_OK(hipMemcpy(j, d_pl_j_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (p) HIP_OK(hipMemcpy(p, d_pl_p_.as<void>(), 8 * m, hipMemcpyDeviceToHost));
+}
+
+
 // ---- shuffled negatives (host) ------------------------------------------------------------------------------------
 // k-let preserving shuffle by a random Euler tour (uShuffle): vertices = distinct (k-1)-lets in order of first
 // appearance, edges = consecutive lets; a random arborescence towards the last let (Wilson), the remaining out-edges of
@@ -2214,6 +2431,18 @@ int elemdp_scan(elemdp_handle* h, const double* x, int32_t n_param, elemdp_scan_
   ELEMDP_TRY
   if (!h || !x) throw elemdp::ArgError("elemdp_scan: null argument");
   h->e->scan(x, n_param, out);
+  ELEMDP_CATCH
+}
+int elemdp_pair_posteriors(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, int64_t* n_pairs, double* unpaired) {
+  ELEMDP_TRY
+  if (!h || !x || !n_pairs) throw elemdp::ArgError("elemdp_pair_posteriors: null argument");
+  h->e->pair_posteriors(x, n_param, min_prob, n_pairs, unpaired);
+  ELEMDP_CATCH
+}
+int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {
+  ELEMDP_TRY
+  if (!h) throw elemdp::ArgError("elemdp_pair_list: null handle");
+  h->e->pair_list(seq, i, j, p, cap);
   ELEMDP_CATCH
 }
 int elemdp_last_timing(elemdp_handle* h, double* ms, int32_t n) {

@@ -90,6 +90,9 @@ struct DpArgs {
   int32_t* trace_stack; int32_t trace_stack_stride;
   long long* prof;  // optional [n_blocks][8] cycle counters: stage, in-band, in-ext, out-ext, out-band, other
   LdsLayout lds;
+  // SCAN, base-pair posteriors (pair_rules.h): non-null = stop after inside + the first outside pass and write P(i, d) of the
+  // sequence order[w] to pair_p + w * pair_stride ([i][d], rows of W+1; 0 where the cell is not kept)
+  double* pair_p; size_t pair_stride;
 };
 
 // arguments of the diagonal-synchronous train pipeline (train_kernels.hip)
@@ -238,5 +241,35 @@ bool plan_copies_fused(const PlanKernelArgs& a);   // launch_plan_items has writ
 hipError_t launch_dp(int kind, const DpArgs& a, int n_blocks, hipStream_t st);
 hipError_t launch_reduce(const double* seq_out, int out_stride, int n_seq, int n_theta, double* partial, hipStream_t st);
 const char* dp_kernel_name(int kind);
+
+// ---- base-pair posteriors (pair_rules.h, pair_kernels.hip).  A launch covers the G sequences idx[0 .. G) of one group or chunk;
+// slot g of the launch owns P + g * p_stride ([i][d], rows of W+1).
+struct PairArgs {
+  const SeqPlan* plans;           // batch plans (batch index)
+  const int32_t* idx;             // idx[g] = batch index of the sequence in slot g
+  const uint32_t* okbits;         // pair mask after the filter (bits_base indexing)
+  // launch_pair_cells: the compact tables of the group's slots, P plane (AutomatonLayout::tab_*): rows start at
+  // p_base + (d * (L+1) + i) * p_rs with p_base = tab_cs[P] (cell-major) or tab_cs[P] * cells; the real states' columns are 0 .. ncol-1
+  const double* band_in; const double* band_out; size_t band_stride;
+  int32_t tab_cell, p_cs, p_rs, ncol;
+  const double* zs;               // per slot: Z(ari, nasi) mantissa at zs[4 g]
+  const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
+  int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)
+  double* P; size_t p_stride;
+  // launch_pair_seq
+  double min_prob;
+  double* unpaired;               // seq_base indexing, L values per sequence
+  const int64_t* koff;            // per batch index: first staging entry (prefix of the kept pairs)
+  int32_t* st_i; int32_t* st_j; double* st_p;   // staging list, (i, j) in row order per sequence
+  int64_t* cnt;                   // per batch index: pairs with P >= min_prob
+};
+hipError_t launch_pair_cells(const PairArgs& a, int G, int cells_max, hipStream_t st);   // k4_pairs
+hipError_t launch_pair_seq(const PairArgs& a, int G, hipStream_t st);
+// kept pairs of every sequence of the batch (the staging capacity), off[0..n] = exclusive prefix of cnt[0..n) with off[n] the total,
+// and the scatter of the staging list into the final list ordered by (sequence, i, j)
+hipError_t launch_pair_kept(const SeqPlan* plans, const uint32_t* okbits, int n, int64_t* kept, hipStream_t st);
+hipError_t launch_pair_prefix(const int64_t* cnt, int n, int64_t* off, hipStream_t st);
+hipError_t launch_pair_scatter(const int64_t* koff, const int64_t* cnt, const int64_t* off, const int32_t* st_i, const int32_t* st_j,
+                               const double* st_p, int n, int32_t* seq, int32_t* i, int32_t* j, double* p, hipStream_t st);
 
 }  // namespace elemdp

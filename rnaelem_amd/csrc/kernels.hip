@@ -19,6 +19,7 @@
 #include "dp_rules.h"
 #include "energy_rules.h"
 #include "kernels.h"
+#include "pair_rules.h"
 #include "plan_rules.h"
 #include "scan_rules.h"
 #include "wave_gather.h"
@@ -709,6 +710,20 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
         const double ZL = l_zs[0];
         sink.post_[0] = Pys; sink.post_[1] = Pyi;
         sweep_outside<OUT_SCAN>(m, q, Tin, Tout, ZL, c0, true, true, sink, l_eh, no_rss, sc, pf);
+        if (a.pair_p) {   // base-pair posteriors (pair_rules.h): the tables of this first pass are all they need
+          double* P = a.pair_p + (size_t)w * a.pair_stride;
+          const PairLog r{ZL};
+          const bool live = ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL;
+          for (int t = tid; t < ncell; t += kThreads) {
+            const int i = t / (W + 1), d = t - i * (W + 1);
+            double acc = 0.;
+            if (live && i + d <= L && q.pair_ok(i, d))
+              for (int s = 0; s < S; ++s)
+                if (s != m.lay.shadow) acc += r.term(Tin.at(ST_P, d, i, s), Tout.at(ST_P, d, i, s));
+            P[t] = r.finish(acc);
+          }
+          continue;
+        }
         if (tid == 0) l_zs[4] = (double)last_argmax(Pys, L);
         __syncthreads();
         Ys = (int)l_zs[4];

@@ -4,6 +4,7 @@
     character '!' <=> the sequence carries the motif        RNAelem/fastq_io.hpp:64-108
   * model text file                                          RNAelem/motif_io.hpp:29-57 (write), :118-262 (read)
   * 10-line scan record                                      RNAelem/motif_scanner.hpp:240-251
+  * base-pair posterior record (`scan --out-pairs`; the reference has no such output)
 """
 import json
 import math
@@ -140,3 +141,28 @@ def scan_record(rid, codes, rec, nodes):
         "id: " + rid, "start: " + fmt_vec(rec["start"]), "end: " + fmt_vec(rec["end"]), "inner: " + fmt_vec(rec["inner"]),
         "psihat: " + fmt_vec([int(v) for v in rec["psihat"]]), "motif region: %d - %d" % (rec["Ys"], rec["Ye"]),
         "exist prob: " + fmt(rec["exist_prob"]), "seq: " + decode_seq(codes), "rss: " + rec["rss"], "mot: " + mot]) + "\n"
+
+
+def pair_record(rid, L, pairs, unpaired):
+    """Record of one sequence in the `scan --out-pairs` file: its id, the L unpaired probabilities, the number of pairs, then one
+    line `i j p` per pair -- 1-based base positions i < j (cell (i0, j0) -> i0+1, j0), ordered by i then j, p as %.6g."""
+    ii, jj, pp = pairs
+    assert len(unpaired) == L
+    lines = ["id: " + rid, "unpaired: " + fmt_vec(unpaired), "pairs: %d" % len(pp)]
+    lines += ["%d %d %.6g" % (int(a) + 1, int(b), float(v)) for a, b, v in zip(ii, jj, pp)]
+    return "\n".join(lines) + "\n"
+
+
+def read_pair_records(path):
+    """-> list of (id, unpaired array, [(i, j, p), ...] with 1-based i < j) from a `scan --out-pairs` file."""
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+    while k + 2 < len(lines) and lines[k].startswith("id: "):
+        rid = lines[k][4:]
+        body = lines[k + 1][len("unpaired: "):].strip("[]")
+        unp = np.array([float(v) for v in body.split(",")] if body else [])
+        n = int(lines[k + 2][len("pairs: "):])
+        prs = [(int(a), int(b), float(v)) for a, b, v in (lines[k + 3 + t].split() for t in range(n))]
+        out.append((rid, unp, prs))
+        k += 3 + n
+    return out
