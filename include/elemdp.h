@@ -81,7 +81,7 @@ int elemdp_initial_params(const elemdp_handle* h, double lambda_init, double* x,
 /* JSON description of the automaton (states, transition lists) for inspection / host-logic tests. */
 int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
 
-/* Engine knobs (not part of the reference interface).  Unknown keys are ELEMDP_EARG.
+/* Engine knobs (not part of the reference interface).  Unknown keys are ELEMDP_EINVAL.
  *   evaluation
  *     "pipeline"        4 (default): scaled-linear batch pipeline, which hands sequences outside the double range to the log-space
  *                       one; 3: log-space batch pipeline for everything.  (2, the fused kernel of round 1, is retired.)
@@ -91,7 +91,7 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *     "nblk"            blocks of cells a band-kernel workgroup owns: 0 (default) = chosen per launch, n = n wherever they fit
  *     "deterministic"   1: bit-identical repeats of elemdp_train_eval (fixed summation order, as the reference at --thread 1); slower
  *     "eval_first", "eval_count"   a train evaluation covers the records [first, first + count) of the resident batch only
- *                       (count 0 = all; reset by elemdp_load_batch).  Refused (ELEMDP_EARG) for a streamed batch and for pipeline 3
+ *                       (count 0 = all; reset by elemdp_load_batch).  Refused (ELEMDP_EINVAL) for a streamed batch and for pipeline 3
  *     "prune"           1 (default): transition lists without what cannot occur in a complete parse; 0: the reference's complete lists
  *     "first_pass_only" debug: stop a train evaluation after the first outside pass
  *   batches
@@ -100,7 +100,7 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *                       second inner engine and host thread while chunk k is evaluated, partial sums added in chunk order; set
  *                       before elemdp_load_batch
  *     "group"           sequences swept in lockstep (0 = as many as fit); "group_streams": groups evaluated concurrently (default 2);
- *                       "two_streams": second outside pass of schedule 0 on a second stream (default 1); "slots": table slots
+ *                       "slots": table slots; "two_streams": retired with pipeline 2, accepted and ignored
  *     "keep_lnbpp"      keep ln BPP of the filter for elemdp_batch_pairs; "bpp_log": 1 = log-space BPP filter for every band
  *     "sorted_plan"     1: role lists of the plan sorted per cell (reproducible summation order of the log-space pipeline)
  *     "row_pad"         padding of the compact table rows in doubles (default 1 = none; 8 = rows start on 64-byte lines)

@@ -272,12 +272,24 @@ class Engine {
   // row: doubles per cell of a band table slot (0: the dense layout, 7 * S; the compact tables of the scaled-linear pipeline
   // pass AutomatonLayout::tab_row)
   void ensure_slots(int S, bool scan, int n_want, int row = 0);
-  void run_train(bool first_pass_only);
+  void run_train();
   void run_train_batch();
   void run_lin_batch();
-  int prepare_lin(LinArgs& a, bool sched1, bool dense_too = false, int n_eval = 0);
-  int balanced_group(size_t per_slot_bytes, int n = 0);
-  int group_cap_ = 8192;   // most sequences swept in lockstep (a first scan uses fewer: fresh table memory costs ~20 ms / GB)
+  // group_cap: most sequences swept in lockstep (a scan uses fewer: fresh table memory costs ~20 ms / GB)
+  int prepare_lin(LinArgs& a, bool sched1, bool dense_too = false, int n_eval = 0, int group_cap = 8192);
+  int balanced_group(size_t per_slot_bytes, int n, int group_cap);
+  template <class Work> void sweep_groups(const LinArgs& a, int n, const int32_t* h_ord, const int32_t* d_ord, const SeqPlan* d_sorted,
+                                          int gsz, int ns, Work work);
+  struct ScanPos {   // what a scan's first sum pass writes besides its tables: per position, then per sequence
+    DevBuf start, inner, end, ys, ye, exist;
+    ScanPos(size_t n_seqpos, int n) {
+      start.alloc(8 * n_seqpos); inner.alloc(8 * n_seqpos); end.alloc(8 * (n_seqpos + n));
+      ys.alloc(4 * (size_t)n); ye.alloc(4 * (size_t)n); exist.alloc(8 * (size_t)n);
+    }
+  };
+  int prepare_scan(LinArgs& a, const ScanPos& pos);
+  int read_flagged(std::vector<int32_t>* list = nullptr);
+  DpArgs log_scan_args(bool sums_on_batch, int* n_blocks);
   TrArgs log_pipeline_args();
   void init_device();
   void flatten_automaton();
@@ -367,9 +379,7 @@ class Engine {
   int device_ = -1, n_cu_ = 256;   // device_ < 0: no HIP device (host-only handle)
   hipStream_t st_ = nullptr;
   hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev2_[2] = {nullptr, nullptr};
-  bool opt_two_streams_ = true;
-  // groups evaluated concurrently (run_lin_batch, scan): stream k of gs_ (gs_[0] = st_) with its second-pass stream gs2_[k]
+  // groups evaluated concurrently (sweep_groups): stream k of gs_ (gs_[0] = st_)
   static constexpr int kMaxGroupStreams = 4;
   hipStream_t gs_[kMaxGroupStreams] = {nullptr, nullptr, nullptr, nullptr};
   // (created when first used: the runtime deals its few hardware queues to streams in the order they are made, and two
@@ -378,8 +388,12 @@ class Engine {
     for (int k = 1; k < ns && k < kMaxGroupStreams; ++k)
       if (!gs_[k]) HIP_OK(hipStreamCreateWithFlags(&gs_[k], hipStreamNonBlocking));
   }
-  hipEvent_t gev_[kMaxGroupStreams][2] = {}, gdone_[kMaxGroupStreams] = {}, gstart_ = nullptr;
+  hipEvent_t gdone_[kMaxGroupStreams] = {}, gstart_ = nullptr;
   int opt_group_streams_ = 2;
+  // streams for a sweep whose schedule allows concurrent groups
+  int group_streams(bool concurrent) const {
+    return (concurrent && opt_group_streams_ >= 2) ? std::min(opt_group_streams_, kMaxGroupStreams) : 1;
+  }
   DevBuf d_et_, d_xet_, d_ints_, d_ints0_, d_params_, d_params0_, d_counter_, d_lay_, d_lay0_, d_layr_, d_intsr_;
   std::vector<double> theta_;  // log-probabilities of the last evaluation (softmax Jacobian)
 
@@ -508,14 +522,9 @@ void Engine::init_device() {
   n_cu_ = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   HIP_OK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
   gs_[0] = st_;
-  for (int k = 0; k < kMaxGroupStreams; ++k) {
-    if (k) for (auto& e : gev_[k]) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&gdone_[k], hipEventDisableTiming));
-  }
+  for (auto& e : gdone_) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIP_OK(hipEventCreateWithFlags(&gstart_, hipEventDisableTiming));
   for (auto& e : ev_) HIP_OK(hipEventCreate(&e));
-  for (auto& e : ev2_) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  gev_[0][0] = ev2_[0]; gev_[0][1] = ev2_[1];
   d_et_.alloc(sizeof(EnergyTables));
   HIP_OK(hipMemcpyAsync(d_et_.as<void>(), &et_, sizeof(EnergyTables), hipMemcpyHostToDevice, st_));
   loops_finite_ = loop_tables_finite(et_);
@@ -573,9 +582,7 @@ Engine::~Engine() {
   comm_destroy();
   if (st_) (void)hipStreamSynchronize(st_);
   for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ev2_) if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < kMaxGroupStreams; ++k) {
-    if (k) for (auto& e : gev_[k]) if (e) (void)hipEventDestroy(e);
     if (gdone_[k]) (void)hipEventDestroy(gdone_[k]);
     if (k && gs_[k]) (void)hipStreamDestroy(gs_[k]);
   }
@@ -589,7 +596,7 @@ void Engine::set_option(const std::string& key, double v) {
   else if (key == "keep_lnbpp") opt_keep_lnbpp_ = v != 0;
   else if (key == "first_pass_only") opt_first_pass_only_ = v != 0;
   else if (key == "profile") opt_profile_ = v != 0;
-  else if (key == "two_streams") opt_two_streams_ = v != 0;
+  else if (key == "two_streams") {}   // (retired with pipeline 2: accepted and ignored, as bench.py --serial-passes still sets it)
   else if (key == "group_streams") opt_group_streams_ = (int)v;
   else if (key == "pipeline") {
     if ((int)v != 3 && (int)v != 4) throw ArgError("option pipeline: 4 (scaled linear, default) or 3 (log space); the fused kernel (2) is retired");
@@ -1341,10 +1348,9 @@ void Engine::stream_scan(const double* x, int n_param_in, elemdp_scan_out* out) 
   if (out->en) std::copy(en.begin(), en.end(), out->en);
 }
 
-// Sequences swept in lockstep: as many as fit in ~55 % of the free device memory (at most 8192), then balanced so that all
+// Sequences swept in lockstep: as many as fit in ~55 % of the free device memory (at most group_cap), then balanced so that all
 // groups of the batch have the same size (a small last group runs at lower efficiency).
-int Engine::balanced_group(size_t per_slot_bytes, int n) {
-  if (n <= 0) n = n_seq_;
+int Engine::balanced_group(size_t per_slot_bytes, int n, int group_cap) {
   if (opt_group_ > 0) return opt_group_;
   size_t free_b = 0, total_b = 0;
   HIP_OK(hipMemGetInfo(&free_b, &total_b));
@@ -1352,7 +1358,7 @@ int Engine::balanced_group(size_t per_slot_bytes, int n) {
   size_t budget = (size_t)((double)(free_b + held) * 0.68);
   if (slot_budget_ > 0) budget = std::min(budget, slot_budget_);
   long cap = (long)(budget / std::max<size_t>(per_slot_bytes, 1));
-  cap = std::max(1L, std::min(cap, (long)group_cap_));
+  cap = std::max(1L, std::min(cap, (long)group_cap));
   const long n_groups = (n + cap - 1) / cap;
   return (int)((n + n_groups - 1) / n_groups);
 }
@@ -1435,7 +1441,7 @@ void Engine::lin_weights(int first, int count) {
   HIP_OK(launch_lin_weights(w, st_));
 }
 
-int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval) {
+int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int group_cap) {
   // schedule 1 sweeps the automaton with the shadow copy of (0,0) (one state more per table row); the scan and schedule 0
   // the plain one.  The slots are sized for the wider row.
   const bool shadow = sched1 && lays_.shadow >= 0;
@@ -1449,7 +1455,7 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval) {
   {
     const size_t cells = (size_t)(Wmax_ + 1) * (Lmax_ + 1), ext = (size_t)(Lmax_ + 1);
     slot_override_ = balanced_group((cells * row + ext * Sa) * 2 * sizeof(double) + ext * Sa * 3 * sizeof(double) +
-                                    cells * nap * 2 * sizeof(double), n_need);
+                                    cells * nap * 2 * sizeof(double), n_need, group_cap);
   }
   ensure_slots(Sa, false, n_need, row);
   slot_override_ = 0;
@@ -1511,6 +1517,60 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval) {
   return gsz;
 }
 
+// One sweep of the scaled-linear pipeline over n sequences in processing order (h_ord / d_ord, plan records d_sorted), cut into
+// groups of equal size and dealt round-robin to ns streams, each with its own share of the table slots: the serial parts of a
+// group (exterior chains, launch tails) run under the band kernels of another.  work(ak, slot0, G, Lg, Wg, stream) queues one
+// group of G sequences (the longest of length Lg, spans up to Wg) with the arguments ak of its slots, the first of which is slot0.
+template <class Work>
+void Engine::sweep_groups(const LinArgs& a, int n, const int32_t* h_ord, const int32_t* d_ord, const SeqPlan* d_sorted, int gsz,
+                          int ns, Work work) {
+  const int slots_each = n_slots_ / ns;
+  if (ns > 1) {   // every stream the same number of groups
+    int n_groups = (n + slots_each - 1) / slots_each;
+    n_groups = ((n_groups + ns - 1) / ns) * ns;
+    gsz = (n + n_groups - 1) / n_groups;
+  }
+  need_group_streams(ns);
+  if (ns > 1) {   // the other streams start behind what st_ has queued so far ...
+    HIP_OK(hipEventRecord(gstart_, st_));
+    for (int k = 1; k < ns; ++k) HIP_OK(hipStreamWaitEvent(gs_[k], gstart_, 0));
+  }
+  int gi = 0;
+  for (int g0 = 0; g0 < n; g0 += gsz, ++gi) {
+    const int k = gi % ns;
+    const size_t k0 = (size_t)k * slots_each;
+    LinArgs ak = a;
+    ak.band_in += k0 * a.band_stride; ak.band_out += k0 * a.band_stride;
+    ak.ext_in += k0 * a.ext_stride; ak.ext_out += k0 * a.ext_stride;
+    ak.zs += 4 * k0;
+    ak.a_in += k0 * a.a_stride; ak.a_out += k0 * a.a_stride;
+    if (a.tr_ext) ak.tr_ext += k0 * a.ext_stride;   // (the scan's trace slots; null elsewhere)
+    if (a.trace_stack) ak.trace_stack += k0 * a.trace_stack_stride;
+    ak.grp = d_ord + g0;
+    ak.plans_slot = d_sorted + g0;
+    const int Lg = h_plans_[h_ord[g0]].L;
+    work(ak, k0, std::min(gsz, n - g0), Lg, std::min(Lg, max_span_), gs_[k]);
+  }
+  for (int k = 1; k < ns; ++k) {   // ... and st_ continues behind them
+    HIP_OK(hipEventRecord(gdone_[k], gs_[k]));
+    HIP_OK(hipStreamWaitEvent(st_, gdone_[k], 0));
+  }
+}
+
+// Waits for st_ and returns the number of sequences the range check of the scaled-linear pipeline flagged (their indices into
+// *list when given).
+int Engine::read_flagged(std::vector<int32_t>* list) {
+  int32_t n_flagged = 0;
+  HIP_OK(hipMemcpyAsync(&n_flagged, d_flagged_.as<void>(), sizeof(int32_t), hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  if (list) {
+    list->resize(n_flagged);
+    if (n_flagged) HIP_OK(hipMemcpy(list->data(), d_flagged_.as<int32_t>() + 1, sizeof(int32_t) * n_flagged, hipMemcpyDeviceToHost));
+  }
+  n_flagged_last_ = n_flagged;
+  return n_flagged;
+}
+
 void Engine::run_lin_batch() {
   const bool sched1 = opt_schedule_ == 1 && linear_ok_ && !opt_first_pass_only_ && lay_.s00 == 0 && lays_.shadow >= 0;
   LinArgs a;
@@ -1553,44 +1613,12 @@ void Engine::run_lin_batch() {
   HIP_OK(hipEventRecord(ev_[1], st_));
   lin_weights(r0, n_ev);
   poison_tables();
-  // Two groups at a time, each on its own stream and its own half of the table slots: the serial parts of a
-  // group (exterior chains, launch tails) run under the band kernels of the other.  (Not for a handful of sequences,
-  // whose tables debug_tables reads, nor under the phase profile.)
-  const int ns = (opt_group_streams_ >= 2 && n_ev >= 64 && n_slots_ >= 64 && !opt_profile_) ? std::min(opt_group_streams_, kMaxGroupStreams) : 1;
-  const int slots_each = n_slots_ / ns;
-  int n_groups = (n_ev + slots_each - 1) / slots_each;
-  if (ns > 1) n_groups = ((n_groups + ns - 1) / ns) * ns;      // (every stream the same number of groups)
-  const int gsz2 = (ns == 1) ? gsz : (n_ev + n_groups - 1) / n_groups;
-  auto shifted = [&](LinArgs x, size_t k) {   // the arguments of a group that uses the slots from k on
-    x.band_in += k * x.band_stride; x.band_out += k * x.band_stride;
-    x.ext_in += k * x.ext_stride; x.ext_out += k * x.ext_stride;
-    x.zs += 4 * k;
-    x.a_in += k * x.a_stride; x.a_out += k * x.a_stride;
-    return x;
-  };
-  need_group_streams(ns);
-  if (ns > 1) {   // the other streams start behind the weights
-    HIP_OK(hipEventRecord(gstart_, st_));
-    for (int k = 1; k < ns; ++k) HIP_OK(hipStreamWaitEvent(gs_[k], gstart_, 0));
-  }
-  int gi = 0;
-  for (int g0 = 0; g0 < n_ev; g0 += gsz2, ++gi) {
-    const int G = std::min(gsz2, n_ev - g0);
-    const int k = gi % ns;
-    LinArgs ak = shifted(a, (size_t)k * slots_each);
-    ak.grp = d_ord + g0;
-    ak.plans_slot = d_sorted + g0;
-    const int Lg = h_plans_[h_ord[g0]].L;
-    HIP_OK(launch_lin_group(ak, G, Lg, std::min(Lg, max_span_), opt_first_pass_only_, gs_[k]));
-  }
-  for (int k = 1; k < ns; ++k) {   // ... and the main stream continues behind them
-    HIP_OK(hipEventRecord(gdone_[k], gs_[k]));
-    HIP_OK(hipStreamWaitEvent(st_, gdone_[k], 0));
-  }
-  int32_t n_flagged = 0;
-  HIP_OK(hipMemcpyAsync(&n_flagged, d_flagged_.as<void>(), sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  n_flagged_last_ = n_flagged;
+  // (concurrent groups: not for a handful of sequences, whose tables debug_tables reads, nor under the phase profile)
+  const int ns = group_streams(n_ev >= 64 && n_slots_ >= 64 && !opt_profile_);
+  sweep_groups(a, n_ev, h_ord, d_ord, d_sorted, gsz, ns, [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
+    HIP_OK(launch_lin_group(ak, G, Lg, Wg, opt_first_pass_only_, st));
+  });
+  const int n_flagged = read_flagged();
   if (opt_profile_) {
     std::vector<long long> hp(16 * 64);
     HIP_OK(hipMemcpy(hp.data(), d_prof_.as<void>(), sizeof(long long) * 16 * 64, hipMemcpyDeviceToHost));
@@ -1613,7 +1641,7 @@ void Engine::run_lin_batch() {
   HIP_OK(launch_reduce(d_seq_out_.as<double>() + (size_t)r0 * out_stride_, out_stride_, n_ev, au_.n_theta(), d_partial_.as<double>(), st_));
 }
 
-void Engine::run_train(bool) {
+void Engine::run_train() {
   // pipeline 4 (default): the scaled-linear batch pipeline (lin_kernels.hip), which hands sequences outside the double range to
   // pipeline 3, the log-space batch pipeline (train_kernels.hip).  (Pipeline 2, the fused per-sequence kernel of round 1, is
   // retired for training; its scan schedule stays as the scan's range fallback.)
@@ -1632,7 +1660,7 @@ void Engine::train_partial(const double* x, int n_param_in, void* partial, bool 
   last_x_.assign(x, x + n_param_in);
   upload_params(x, lay_, false);
   if (n_seq_ > 0) {
-    run_train(false);
+    run_train();
   } else {   // a rank without a share of the batch: zeros into the all-reduce
     HIP_OK(hipMemsetAsync(d_partial_.as<void>(), 0, sizeof(double) * partial_len(), st_));
     HIP_OK(hipEventRecord(ev_[1], st_));
@@ -1825,6 +1853,46 @@ void Engine::batch_pairs(int idx, uint8_t* kept, double* lnbpp, int cap) {
   }
 }
 
+// The scaled-linear sum passes of a scan (and the first one of pair_posteriors): table slots, cleared outputs, weights.  A scan
+// is one pass: 1 024 sequences per group run within 4 % of the largest groups and need a third of the table memory (an
+// evaluation loop that already holds larger groups keeps them).  Returns the balanced group size.
+int Engine::prepare_scan(LinArgs& a, const ScanPos& pos) {
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  const int gsz = prepare_lin(a, false, true, 0, std::max(1024, n_slots_));
+  a.scan = 1;
+  a.ys = pos.ys.as<int32_t>(); a.ye = pos.ye.as<int32_t>();
+  a.pos_start = pos.start.as<double>(); a.pos_inner = pos.inner.as<double>(); a.pos_end = pos.end.as<double>();
+  a.exist = pos.exist.as<double>();
+  HIP_OK(hipMemsetAsync(pos.start.as<void>(), 0, 8 * n_seqpos, st_));
+  HIP_OK(hipMemsetAsync(pos.inner.as<void>(), 0, 8 * n_seqpos, st_));
+  HIP_OK(hipMemsetAsync(pos.end.as<void>(), 0, 8 * (n_seqpos + n), st_));
+  HIP_OK(hipMemsetAsync(pos.ys.as<void>(), 0, 4 * (size_t)n, st_));
+  HIP_OK(hipMemsetAsync(pos.ye.as<void>(), 0, 4 * (size_t)n, st_));
+  HIP_OK(hipMemsetAsync(d_seq_out_.as<void>(), 0, sizeof(double) * (size_t)out_stride_ * n, st_));
+  HIP_OK(hipMemsetAsync(d_flagged_.as<void>(), 0, sizeof(int32_t), st_));
+  lin_weights();
+  poison_tables();
+  return gsz;
+}
+
+// The fused scan kernel (the log-space form) and its block count.  After the scaled-linear sum passes it reuses their table and
+// trace slots; otherwise (pipeline 3) it gets table slots with trace tables, which the train pipelines do not reuse: the caller
+// drops them (n_slots_ = 0) when done.
+DpArgs Engine::log_scan_args(bool sums_on_batch, int* n_blocks) {
+  const int n = n_seq_, S = au_.S();
+  if (sums_on_batch) {
+    *n_blocks = std::min(std::min(n_slots_, 2 * n_cu_), n);
+  } else {
+    ensure_slots(S, true, n);
+    lin_slots_ = 0;   // (the table slots were re-allocated with trace tables)
+    *n_blocks = std::min(n_slots_, n);
+  }
+  DpArgs d = base_args(lay_, d_ints_.as<int32_t>(), d_params_.as<double>(), plan_, d_okbits1_.as<uint32_t>(), S);
+  d.lds = lds_layout(lay_, Lmax_, nword_max_, true);
+  return d;
+}
+
 void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
   require_device();
   DeviceGuard dg(device_);
@@ -1837,10 +1905,9 @@ void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
   upload_params(x, lay_, false);
   const int nt = au_.n_theta(), n = n_seq_, S = au_.S();
   const size_t n_seqpos = (size_t)h_seq_off_[n], n_pos = n_seqpos + n;
-  DevBuf d_start, d_end, d_inner, d_psi, d_rss, d_ys, d_ye, d_exist, d_en;
-  d_start.alloc(8 * n_seqpos); d_inner.alloc(8 * n_seqpos); d_end.alloc(8 * n_pos);
-  d_psi.alloc(4 * n_seqpos); d_rss.alloc(n_seqpos);
-  d_ys.alloc(4 * n); d_ye.alloc(4 * n); d_exist.alloc(8 * n); d_en.alloc(8 * (size_t)n * (nt + 1));
+  ScanPos pos(n_seqpos, n);
+  DevBuf d_psi, d_rss, d_en;
+  d_psi.alloc(4 * n_seqpos); d_rss.alloc(n_seqpos); d_en.alloc(8 * (size_t)n * (nt + 1));
   HIP_OK(hipEventRecord(ev_[1], st_));
   // ---- K4 / K5 (the four sum passes, motif_scanner.hpp:186-202) on the scaled-linear batch pipeline
   std::vector<int32_t> flagged;
@@ -1849,101 +1916,43 @@ void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
   if (sums_on_batch) {
     LinArgs a;
     dbg_lap("scan: start");
-    // a scan is one pass: 1 024 sequences per group run within 4 % of the largest groups and need a third of the table
-    // memory (an evaluation loop that already holds larger groups keeps them)
-    group_cap_ = std::max(1024, n_slots_);
-    const int gsz = prepare_lin(a, false, true);
-    group_cap_ = 8192;
-    dbg_lap("scan: prepare_lin (table slots)");
-    a.scan = 1;
-    a.ys = d_ys.as<int32_t>(); a.ye = d_ye.as<int32_t>();
-    a.pos_start = d_start.as<double>(); a.pos_inner = d_inner.as<double>(); a.pos_end = d_end.as<double>();
-    a.exist = d_exist.as<double>();
-    HIP_OK(hipMemsetAsync(d_start.as<void>(), 0, 8 * n_seqpos, st_));
-    HIP_OK(hipMemsetAsync(d_inner.as<void>(), 0, 8 * n_seqpos, st_));
-    HIP_OK(hipMemsetAsync(d_end.as<void>(), 0, 8 * n_pos, st_));
-    HIP_OK(hipMemsetAsync(d_ys.as<void>(), 0, 4 * n, st_));
-    HIP_OK(hipMemsetAsync(d_ye.as<void>(), 0, 4 * n, st_));
-    HIP_OK(hipMemsetAsync(d_seq_out_.as<void>(), 0, sizeof(double) * (size_t)out_stride_ * n, st_));
-    HIP_OK(hipMemsetAsync(d_flagged_.as<void>(), 0, sizeof(int32_t), st_));
-    lin_weights();
-    poison_tables();
+    const int gsz = prepare_scan(a, pos);
+    dbg_lap("scan: table slots + weights");
     // trace records of the Viterbi pass: the exterior chain's rows and the traceback stack per table slot (the band targets keep
     // none: scan_rules.h, cyk_retrace)
     const size_t ext = (size_t)(Lmax_ + 1) * S;
     const int stack_stride = 4 * (4 * (Lmax_ + 2));
     d_tr_ext_.alloc(ext * n_slots_ * sizeof(TraceRec));
     d_tr_stack_.alloc((size_t)n_slots_ * stack_stride * sizeof(int32_t));
-    dbg_lap("scan: weights + trace slots");
+    dbg_lap("scan: trace slots");
     a.tr_ext = d_tr_ext_.as<TraceRec>();
     a.trace_stack = d_tr_stack_.as<int32_t>(); a.trace_stack_stride = stack_stride;
     a.sc_psihat = d_psi.as<int32_t>(); a.sc_rss = d_rss.as<char>();
     const bool cyk_on_batch = !(opt_dbg_ & 64);
-    // two groups at a time (as in run_lin_batch): each on its own stream, with its half of the table slots -- the five exterior
-    // chains of a group run under the band kernels of the other
-    const int ns = (opt_group_streams_ >= 2 && n >= 128 && n_slots_ >= 128) ? std::min(opt_group_streams_, kMaxGroupStreams) : 1;
-    const int slots_each = n_slots_ / ns;
-    int n_groups = (n + slots_each - 1) / slots_each;
-    if (ns > 1) n_groups = ((n_groups + ns - 1) / ns) * ns;    // (every stream the same number of groups)
-    const int gsz2 = (ns == 1) ? gsz : (n + n_groups - 1) / n_groups;
-    need_group_streams(ns);
-    if (ns > 1) {
-      HIP_OK(hipEventRecord(gstart_, st_));
-      for (int k = 1; k < ns; ++k) HIP_OK(hipStreamWaitEvent(gs_[k], gstart_, 0));
-    }
-    int gi = 0;
-    for (int g0 = 0; g0 < n; g0 += gsz2, ++gi) {
-      const int G = std::min(gsz2, n - g0);
-      const int k = gi % ns;
-      hipStream_t st = gs_[k];
-      LinArgs ak = a;
-      ak.band_in += (size_t)k * slots_each * a.band_stride; ak.band_out += (size_t)k * slots_each * a.band_stride;
-      ak.ext_in += (size_t)k * slots_each * a.ext_stride; ak.ext_out += (size_t)k * slots_each * a.ext_stride;
-      ak.zs += 4 * (size_t)k * slots_each;
-      ak.a_in += (size_t)k * slots_each * a.a_stride; ak.a_out += (size_t)k * slots_each * a.a_stride;
-      ak.tr_ext += (size_t)k * slots_each * a.ext_stride;
-      ak.trace_stack += (size_t)k * slots_each * stack_stride;
-      ak.grp = d_order_.as<int32_t>() + g0;
-      ak.plans_slot = d_plans_sorted_.as<SeqPlan>() + g0;
-      const int Lg = h_plans_[h_order_[g0]].L;
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, std::min(Lg, max_span_), 0, st));
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, std::min(Lg, max_span_), 1, st));
-      if (cyk_on_batch) HIP_OK(launch_cyk_group(ak, G, Lg, std::min(Lg, max_span_), st));   // K6 on the same table slots
-    }
-    for (int k = 1; k < ns; ++k) {
-      HIP_OK(hipEventRecord(gdone_[k], gs_[k]));
-      HIP_OK(hipStreamWaitEvent(st_, gdone_[k], 0));
-    }
+    const int ns = group_streams(n >= 128 && n_slots_ >= 128);
+    sweep_groups(a, n, h_order_.data(), d_order_.as<int32_t>(), d_plans_sorted_.as<SeqPlan>(), gsz, ns,
+                 [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, 0, st));
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, 1, st));
+      if (cyk_on_batch) HIP_OK(launch_cyk_group(ak, G, Lg, Wg, st));   // K6 on the same table slots
+    });
     cyk_done = cyk_on_batch;
     dbg_lap("scan: launches queued");
-    int32_t n_flagged = 0;
-    HIP_OK(hipMemcpyAsync(&n_flagged, d_flagged_.as<void>(), sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-    HIP_OK(hipStreamSynchronize(st_));
+    read_flagged(&flagged);
     dbg_lap("scan: device done");
-    flagged.resize(n_flagged);
-    if (n_flagged) HIP_OK(hipMemcpy(flagged.data(), d_flagged_.as<int32_t>() + 1, sizeof(int32_t) * n_flagged, hipMemcpyDeviceToHost));
-    n_flagged_last_ = n_flagged;
     tables_linear_ = false;
   }
   // ---- K6 (Viterbi parse + traceback) on the fused kernel; it also runs the whole schedule for the sequences the
   // linear passes flagged (range check) and for pipeline != 4
   int n_blocks;
-  if (sums_on_batch) {   // reuse the table and trace slots of the batch pipeline
-    n_blocks = std::min(std::min(n_slots_, 2 * n_cu_), n);
-  } else {
-    ensure_slots(S, true, n);
-    lin_slots_ = 0;   // (the table slots were re-allocated with trace tables)
-    n_blocks = std::min(n_slots_, n);
-  }
-  DpArgs d = base_args(lay_, d_ints_.as<int32_t>(), d_params_.as<double>(), plan_, d_okbits1_.as<uint32_t>(), S);
+  DpArgs d = log_scan_args(sums_on_batch, &n_blocks);
   d.order = d_order_.as<int32_t>();
   d.tr_ext = d_tr_ext_.as<TraceRec>();
   d.trace_stack = d_tr_stack_.as<int32_t>();
   d.trace_stack_stride = 4 * (4 * (Lmax_ + 2));
-  d.sc_start = d_start.as<double>(); d.sc_end = d_end.as<double>(); d.sc_inner = d_inner.as<double>();
+  d.sc_start = pos.start.as<double>(); d.sc_end = pos.end.as<double>(); d.sc_inner = pos.inner.as<double>();
   d.sc_psihat = d_psi.as<int32_t>(); d.sc_rss = d_rss.as<char>();
-  d.sc_ys = d_ys.as<int32_t>(); d.sc_ye = d_ye.as<int32_t>(); d.sc_exist = d_exist.as<double>(); d.sc_en = d_en.as<double>();
-  d.lds = lds_layout(lay_, Lmax_, nword_max_, true);
+  d.sc_ys = pos.ys.as<int32_t>(); d.sc_ye = pos.ye.as<int32_t>(); d.sc_exist = pos.exist.as<double>(); d.sc_en = d_en.as<double>();
   d.cyk_only = sums_on_batch ? 1 : 0;
   if (!cyk_done) {
     HIP_OK(hipMemsetAsync(d_counter_.as<void>(), 0, sizeof(int32_t), st_));
@@ -1964,14 +1973,14 @@ void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
   last_ms[0] = last_ms[1] = ms;
   last_ms[2] = (double)flagged.size();
   auto get = [&](void* dst, const DevBuf& src, size_t bytes) { if (dst) HIP_OK(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost)); };
-  get(out->start, d_start, 8 * n_seqpos);
-  get(out->inner, d_inner, 8 * n_seqpos);
-  get(out->end, d_end, 8 * n_pos);
+  get(out->start, pos.start, 8 * n_seqpos);
+  get(out->inner, pos.inner, 8 * n_seqpos);
+  get(out->end, pos.end, 8 * n_pos);
   get(out->psihat, d_psi, 4 * n_seqpos);
   get(out->rss, d_rss, n_seqpos);
-  get(out->ys, d_ys, 4 * n);
-  get(out->ye, d_ye, 4 * n);
-  get(out->exist_prob, d_exist, 8 * n);
+  get(out->ys, pos.ys, 4 * n);
+  get(out->ye, pos.ye, 4 * n);
+  get(out->exist_prob, pos.exist, 8 * n);
   if (out->en) {  // E[N] summed over the batch in input order (motif_scanner.hpp:253-259)
     for (int t = 0; t < nt; ++t) out->en[t] = 0.;
     std::vector<char> is_flagged(n, 0);
@@ -2003,12 +2012,10 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   if (n_seq_ <= 0) throw StateError("pair_posteriors before load_batch");
   if (n_param_in != n_param()) throw ArgError("n_param mismatch");
   upload_params(x, lay_, false);
-  const int n = n_seq_, S = au_.S();
-  const size_t n_seqpos = (size_t)h_seq_off_[n], n_pos = n_seqpos + n;
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
   const size_t pcells = (size_t)(Lmax_ + 1) * (Wmax_ + 1);   // P(i, d) of one table slot
-  DevBuf d_start, d_inner, d_end, d_ys, d_ye, d_exist;        // what the first sum pass writes besides its tables
-  d_start.alloc(8 * n_seqpos); d_inner.alloc(8 * n_seqpos); d_end.alloc(8 * n_pos);
-  d_ys.alloc(4 * n); d_ye.alloc(4 * n); d_exist.alloc(8 * n);
+  ScanPos pos(n_seqpos, n);
   d_pr_kept_.alloc(8 * (size_t)n); d_pr_koff_.alloc(8 * ((size_t)n + 1));
   d_pr_cnt_.alloc(8 * (size_t)n); d_pr_off_.alloc(8 * ((size_t)n + 1));
   d_pr_unp_.alloc(8 * n_seqpos);
@@ -2031,24 +2038,12 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   pa.unpaired = d_pr_unp_.as<double>();
   pa.koff = d_pr_koff_.as<int64_t>(); pa.cnt = d_pr_cnt_.as<int64_t>();
   pa.st_i = d_pr_si_.as<int32_t>(); pa.st_j = d_pr_sj_.as<int32_t>(); pa.st_p = d_pr_sp_.as<double>();
-  std::vector<int32_t> flagged;
+  int n_flagged = 0;
   const bool sums_on_batch = opt_pipeline_ == 4;
   if (sums_on_batch) {
     // the scan's first sum pass on the same groups, slots and streams as Engine::scan
     LinArgs a;
-    group_cap_ = std::max(1024, n_slots_);
-    const int gsz = prepare_lin(a, false, true);
-    group_cap_ = 8192;
-    a.scan = 1;
-    a.ys = d_ys.as<int32_t>(); a.ye = d_ye.as<int32_t>();
-    a.pos_start = d_start.as<double>(); a.pos_inner = d_inner.as<double>(); a.pos_end = d_end.as<double>();
-    a.exist = d_exist.as<double>();
-    HIP_OK(hipMemsetAsync(d_start.as<void>(), 0, 8 * n_seqpos, st_));
-    HIP_OK(hipMemsetAsync(d_inner.as<void>(), 0, 8 * n_seqpos, st_));
-    HIP_OK(hipMemsetAsync(d_seq_out_.as<void>(), 0, sizeof(double) * (size_t)out_stride_ * n, st_));
-    HIP_OK(hipMemsetAsync(d_flagged_.as<void>(), 0, sizeof(int32_t), st_));
-    lin_weights();
-    poison_tables();
+    const int gsz = prepare_scan(a, pos);
     d_pr_P_.alloc(8 * pcells * (size_t)n_slots_);
     // the P plane's columns of the real states are 0 .. ncol-1: Automaton::flatten numbers a plane's columns in state order, and
     // a shadow state comes last
@@ -2063,66 +2058,28 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
     pa.ncol = ncol;
     pa.band_stride = a.band_stride;
     pa.skip_flagged = 1;
-    const int ns = (opt_group_streams_ >= 2 && n >= 128 && n_slots_ >= 128) ? std::min(opt_group_streams_, kMaxGroupStreams) : 1;
-    const int slots_each = n_slots_ / ns;
-    int n_groups = (n + slots_each - 1) / slots_each;
-    if (ns > 1) n_groups = ((n_groups + ns - 1) / ns) * ns;
-    const int gsz2 = (ns == 1) ? gsz : (n + n_groups - 1) / n_groups;
-    need_group_streams(ns);
-    if (ns > 1) {
-      HIP_OK(hipEventRecord(gstart_, st_));
-      for (int k = 1; k < ns; ++k) HIP_OK(hipStreamWaitEvent(gs_[k], gstart_, 0));
-    }
-    int gi = 0;
-    for (int g0 = 0; g0 < n; g0 += gsz2, ++gi) {
-      const int G = std::min(gsz2, n - g0);
-      const int k = gi % ns;
-      hipStream_t st = gs_[k];
-      const size_t k0 = (size_t)k * slots_each;
-      LinArgs ak = a;
-      ak.band_in += k0 * a.band_stride; ak.band_out += k0 * a.band_stride;
-      ak.ext_in += k0 * a.ext_stride; ak.ext_out += k0 * a.ext_stride;
-      ak.zs += 4 * k0;
-      ak.a_in += k0 * a.a_stride; ak.a_out += k0 * a.a_stride;
-      ak.grp = d_order_.as<int32_t>() + g0;
-      ak.plans_slot = d_plans_sorted_.as<SeqPlan>() + g0;
-      const int Lg = h_plans_[h_order_[g0]].L, Wg = std::min(Lg, max_span_);
+    const int ns = group_streams(n >= 128 && n_slots_ >= 128);
+    sweep_groups(a, n, h_order_.data(), d_order_.as<int32_t>(), d_plans_sorted_.as<SeqPlan>(), gsz, ns,
+                 [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
       HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, 0, st));
       PairArgs pk = pa;
       pk.idx = ak.grp;
       pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
-      pk.P = d_pr_P_.as<double>() + k0 * pcells;
+      pk.P = d_pr_P_.as<double>() + slot0 * pcells;
       HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
       HIP_OK(launch_pair_seq(pk, G, st));
-    }
-    for (int k = 1; k < ns; ++k) {
-      HIP_OK(hipEventRecord(gdone_[k], gs_[k]));
-      HIP_OK(hipStreamWaitEvent(st_, gdone_[k], 0));
-    }
-    int32_t n_flagged = 0;
-    HIP_OK(hipMemcpyAsync(&n_flagged, d_flagged_.as<void>(), sizeof(int32_t), hipMemcpyDeviceToHost, st_));
-    HIP_OK(hipStreamSynchronize(st_));
-    flagged.resize(n_flagged);
-    n_flagged_last_ = n_flagged;
+    });
+    n_flagged = read_flagged();
     tables_linear_ = false;
   }
   // ---- the log-space form: the sequences the range check flagged, or every sequence under pipeline 3, in chunks of at most as
   // many sequences as the table slots hold (the P scratch is bounded by the chunk)
-  const int n_log = sums_on_batch ? (int)flagged.size() : n;
+  const int n_log = sums_on_batch ? n_flagged : n;
   if (n_log > 0) {
-    int n_blocks, chunk;
-    if (sums_on_batch) {
-      n_blocks = std::min(std::min(n_slots_, 2 * n_cu_), n);
-      chunk = std::min(n_log, n_slots_);
-    } else {
-      ensure_slots(S, true, n);
-      lin_slots_ = 0;
-      n_blocks = std::min(n_slots_, n);
-      chunk = std::min(n_log, std::max(n_blocks, 1024));
-      d_pr_P_.alloc(8 * pcells * (size_t)chunk);
-    }
-    DpArgs d = base_args(lay_, d_ints_.as<int32_t>(), d_params_.as<double>(), plan_, d_okbits1_.as<uint32_t>(), S);
-    d.lds = lds_layout(lay_, Lmax_, nword_max_, true);
+    int n_blocks;
+    DpArgs d = log_scan_args(sums_on_batch, &n_blocks);
+    const int chunk = std::min(n_log, sums_on_batch ? n_slots_ : std::max(n_blocks, 1024));
+    if (!sums_on_batch) d_pr_P_.alloc(8 * pcells * (size_t)chunk);
     d.pair_p = d_pr_P_.as<double>();
     d.pair_stride = pcells;
     const int32_t* list = sums_on_batch ? d_flagged_.as<int32_t>() + 1 : d_order_.as<int32_t>();
@@ -2157,7 +2114,7 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
   last_ms[0] = ms_all;
   last_ms[1] = ms_dp;
-  last_ms[2] = (double)flagged.size();
+  last_ms[2] = (double)n_flagged;
   if (unpaired) HIP_OK(hipMemcpy(unpaired, d_pr_unp_.as<void>(), 8 * n_seqpos, hipMemcpyDeviceToHost));
   n_pairs_ = total;
   *n_pairs = total;

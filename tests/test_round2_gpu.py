@@ -196,7 +196,7 @@ def test_engine_binds_its_device_in_every_entry_point():
 
 def test_gradient_of_a_medium_batch_against_the_oracle_on_the_concurrent_stream_path():
     """192 x L=200: large enough for the concurrent groups / second outside stream (n >= 64), small enough for the oracle.
-    gr against the oracle (1e-7), and the serial-stream evaluation (group_streams = 1, two_streams = 0) to 1e-10."""
+    gr against the oracle (1e-7), and the serial-stream evaluation (group_streams = 1) to 1e-10."""
     m = io.read_model(gpath("syn_b.model"))
     eng = io.engine_from_model(m)
     seqs, quals = synth.synth_batch(192, 200, seed=4242)
@@ -210,10 +210,40 @@ def test_gradient_of_a_medium_batch_against_the_oracle_on_the_concurrent_stream_
     assert nsk == no and fn == pytest.approx(fo, rel=1e-9) and eff == pytest.approx(eo, rel=1e-12)
     np.testing.assert_allclose(gr, go, rtol=1e-7, atol=1e-7)
     eng.set_option("group_streams", 1)
-    eng.set_option("two_streams", 0)
     fn1, gr1, _, _ = eng.train_eval(x)
     assert fn1 == pytest.approx(fn, rel=1e-12)
     np.testing.assert_allclose(gr1, gr, rtol=1e-10, atol=1e-10)
+
+
+def test_scan_and_pair_posteriors_of_a_medium_batch_on_the_concurrent_stream_path():
+    """256 x L=200: enough sequences and table slots for the scan's concurrent groups (n >= 128).  The scan records and the
+    pair lists of the concurrent default equal those of the serial-stream sweep (group_streams = 1); values to the last bits
+    (1e-12 and 1e-13), as the sums gather through atomics."""
+    m = io.read_model(gpath("syn_b.model"))
+    eng = io.engine_from_model(m)
+    seqs, quals = synth.synth_batch(256, 200, seed=4243)
+    for k in range(0, 256, 5):
+        quals[k][-1] = 5
+    eng.load_batch(seqs, quals)
+    x = m["x"]
+    res = {}
+    for ns in (2, 1):
+        eng.set_option("group_streams", ns)
+        res[ns] = eng.scan(x), eng.pair_posteriors(x, 0.0)
+    (r2, en2), p2 = res[2]
+    (r1, en1), p1 = res[1]
+    np.testing.assert_allclose(en1, en2, rtol=1e-12, atol=1e-300)
+    for a, b in zip(r2, r1):
+        assert (a["Ys"], a["Ye"], a["rss"]) == (b["Ys"], b["Ye"], b["rss"]) and np.array_equal(a["psihat"], b["psihat"])
+        assert b["exist_prob"] == pytest.approx(a["exist_prob"], rel=1e-12)
+        for key in ("start", "inner", "end"):
+            assert np.array_equal(np.isfinite(a[key]), np.isfinite(b[key])), key
+            np.testing.assert_allclose(b[key], a[key], rtol=1e-12, atol=1e-12, err_msg=key)
+    assert len(p1) == len(p2) == 256 and sum(len(p[2]) for p in p2) > 0
+    for (ia, ja, pa, ua), (ib, jb, pb, ub) in zip(p2, p1):
+        assert np.array_equal(ia, ib) and np.array_equal(ja, jb)
+        np.testing.assert_allclose(pb, pa, rtol=1e-13, atol=1e-300)
+        np.testing.assert_allclose(ub, ua, rtol=1e-13, atol=1e-15)
 
 
 def test_full_size_gradient_subsample_against_the_oracle():
@@ -231,12 +261,10 @@ def test_full_size_gradient_subsample_against_the_oracle():
     assert eng.last_timing()[2] == 0
     # serial streams give the same full-size numbers as the concurrent default
     eng.set_option("group_streams", 1)
-    eng.set_option("two_streams", 0)
     fs, gs, _, _ = eng.train_eval(x)
     assert fs == pytest.approx(fa, rel=1e-12)
     np.testing.assert_allclose(gs, ga, rtol=1e-9, atol=1e-8)
     eng.set_option("group_streams", 2)
-    eng.set_option("two_streams", 1)
     eng.load_batch([seqs[k] for k in rest], [quals[k] for k in rest])
     fr, gr, er, nr = eng.train_eval(x)
     sub = io.engine_from_model(m)
