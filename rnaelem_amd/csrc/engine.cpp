@@ -129,12 +129,14 @@ class DevBuf {
   // slack: allocate an eighth more than asked for -- buffers whose size depends on the data (interior-loop items of a batch):
   // the next batch of the same shape then fits without a re-allocation
   // (such a buffer is also never given up for a smaller one: the last chunk of a load is smaller than the others)
-  void alloc(size_t bytes, bool slack = false) {
+  // returns true when the memory is fresh (its contents undefined), false when the buffer was kept
+  bool alloc(size_t bytes, bool slack = false) {
     bytes = bytes ? bytes : 8;
-    if (p_ && bytes <= bytes_ && (slack || bytes_ <= 2 * bytes + (size_t(1) << 20))) return;
+    if (p_ && bytes <= bytes_ && (slack || bytes_ <= 2 * bytes + (size_t(1) << 20))) return false;
     reset();
     bytes_ = slack ? bytes + bytes / 8 : bytes;
     HIP_OK(hipMalloc(&p_, bytes_));
+    return true;
   }
   void reset() { if (p_) { (void)hipFree(p_); p_ = nullptr; bytes_ = 0; } }
   template <class T> T* as() const { return static_cast<T*>(p_); }
@@ -150,7 +152,7 @@ class DevBuf {
 };
 
 // pinned host staging buffer, kept from load to load (a fresh std::vector of 24 MB costs its page faults -- 30 ms per
-// 10 000 x L=300 for the four arrays of load_batch -- and a pageable upload goes through the runtime's own staging copies)
+// 10 000 x L=300 for the staging arrays of load_batch -- and a pageable upload goes through the runtime's own staging copies)
 class HostBuf {
  public:
   HostBuf() = default;
@@ -161,9 +163,10 @@ class HostBuf {
     const size_t bytes = std::max<size_t>(n * sizeof(T), 8);
     if (bytes > bytes_) {
       if (p_) (void)hipHostFree(p_);
-      p_ = nullptr;
-      bytes_ = bytes + bytes / 8;
-      HIP_OK(hipHostMalloc(&p_, bytes_, hipHostMallocDefault));
+      p_ = nullptr; bytes_ = 0;
+      void* p = nullptr;   // (p_ and bytes_ are set once the allocation has succeeded)
+      HIP_OK(hipHostMalloc(&p, bytes + bytes / 8, hipHostMallocDefault));
+      p_ = p; bytes_ = bytes + bytes / 8;
     }
     return static_cast<T*>(p_);
   }
@@ -264,6 +267,20 @@ class Engine {
  public:
   void set_theta_from(const double* x);  // host: theta (log-softmax of x when theta-softmax)
  private:
+  // ---- the stages of load_batch
+  struct BatchShape {   // a checked batch: the records' plans (L, W, C, positive, offsets into the batch arrays), its extent
+    std::vector<SeqPlan> plans;
+    int Lmax = 0, Wmax = 0, nword_max = 0;
+    int64_t n_bases = 0, n_pos = 0, n_words = 0, n_cells = 0;
+  };
+  BatchShape check_batch(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix, int n) const;
+  void stage_batch(BatchShape&& b, const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix,
+                   std::vector<uint8_t>& h_seq, std::vector<uint32_t>& fix_bits);
+  const uint32_t* bpp_filter(const std::vector<uint32_t>& fix_bits);
+  void bpp_chunks(bool lin);
+  void bpp_lin_chunk(int first, int count, int64_t cells, double* lnbpp);
+  void bpp_log_chunk(int first, int count, int64_t cells, double* lnbpp);
+  void resident_plan(const uint32_t* mask);
   void build_planset(PlanSet& ps, int first, int count, const uint32_t* d_okbits);
   void ensure_sorted_plan();
   LdsLayout lds_layout(const AutomatonLayout& lay, int Lmax, int nword_max, bool scan) const;
@@ -335,8 +352,9 @@ class Engine {
   elemdp_model_desc desc_;
   std::string desc_pattern_, desc_par_;
   bool desc_has_par_ = false;
-  bool should_stream(const int32_t* off, int n);
-  void stream_setup(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix, int n);
+  bool should_stream(const BatchShape& b);
+  void stream_setup(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix,
+                    BatchShape&& b);
   void stream_load_chunk(int k, Engine& e);
   // The BPP filter does not depend on the parameters: a streamed batch keeps the filtered pair mask (1.3 KB per sequence of
   // L = 200) and the kept fractions of every chunk on the host after its first load; later loads of the chunk hand them
@@ -374,8 +392,10 @@ class Engine {
   bool linear_ok_ = true;
   int flags_, max_span_, max_iloop_;
   bool loops_finite_ = false;   // loop_tables_finite(et_)
-  bool bpp_planes_finite_ = false;   // the linear filter's planes hold nothing but finite values (cleared at allocation)
   double min_bpp_, tau_;
+  // shortest hairpin: m_min of the DP rules, min_span of the pair masks (ELEMDP_DBG_NO_TURN drops the turn)
+  int m_min() const { return (flags_ & ELEMDP_DBG_NO_TURN) ? 4 : 10; }
+  int min_span() const { return (flags_ & ELEMDP_DBG_NO_TURN) ? 1 : 5; }
   int device_ = -1, n_cu_ = 256;   // device_ < 0: no HIP device (host-only handle)
   hipStream_t st_ = nullptr;
   hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -401,7 +421,7 @@ class Engine {
   int n_seq_ = 0, Lmax_ = 0, Wmax_ = 0, nword_max_ = 0;
   std::vector<SeqPlan> h_plans_;
   std::vector<int32_t> h_order_, h_seq_off_, h_qual_off_;
-  DevBuf d_seq_, d_ws_, d_unp_, d_ndot_, d_okbits0_, d_okbits1_, d_order_, d_ncanon_, d_zero_ws_;
+  DevBuf d_seq_, d_ws_, d_unp_, d_ndot_, d_okbits0_, d_okbits1_, d_order_, d_ncanon_;
   std::vector<double> h_lnbpp_;          // optional (keep_lnbpp)
   std::vector<int64_t> h_lnbpp_base_;
   PlanSet plan_;
@@ -440,10 +460,16 @@ class Engine {
   int opt_dbg_ = 0;        // timing experiments (LinArgs::dbg); results are wrong when set
   int opt_group_ = 0;      // sequences swept in lockstep by the batch pipeline (0 = auto)
   DevBuf d_prof_;
-  DevBuf d_bpp_band_in_, d_bpp_band_out_, d_bpp_ext_in_, d_bpp_ext_out_, d_bpp_tmp_;   // S = 1 tables of the BPP filter
-  PlanSet bpp_plan_;   // plan over the unfiltered mask, chunk by chunk (only the filter reads it)
-  DevBuf d_bpp_order_, d_bpp_rows_, d_bpp_kept_, d_okbits_end_, d_nitems_, d_plans_all_;   // scratch kept across loads
-  DevBuf d_bpp_plans_, d_bpp_xw_, d_bpp_dmin_, d_bpp_cand_, d_bpp_plist_, d_bpp_poff_;   // linear-semiring filter (bpp_kernels.hip)
+  DevBuf d_okbits_end_, d_nitems_, d_plans_all_;   // scratch of build_planset and of the canonical mask, kept across loads
+  // scratch of the BPP filter, which nothing else reads; kept across loads (the mini-batch trainer loads before every evaluation)
+  struct BppScratch {
+    DevBuf band_in, band_out, ext_in, ext_out, tmp;   // planes of the linear form / S = 1 table slots of the log-space form
+    DevBuf kept;                                      // pairs kept per sequence of the chunk
+    DevBuf plans, xw, dmin, cand, plist, poff;        // linear form (bpp_kernels.hip)
+    bool planes_finite = false;                       // ... its planes hold nothing but finite values (cleared at allocation)
+    PlanSet plan;                                     // log-space form: plan over the unfiltered mask, chunk by chunk
+    DevBuf order, rows, zero_ws;                      // ... its sweep order, output rows and weights (all 0)
+  } bpp_;
   bool opt_bpp_log_ = false;                      // option "bpp_log": the log-space filter over the unfiltered plan
  public:
   std::vector<long long> last_prof;
@@ -535,8 +561,8 @@ void Engine::init_device() {
     HIP_OK(hipMemcpy(d_xet_.as<void>(), x.get(), sizeof(EnergyTables), hipMemcpyHostToDevice));
     std::unique_ptr<BppCandTable> ct(new BppCandTable);
     build_bpp_cand(*x, ct.get());
-    d_bpp_cand_.alloc(sizeof(BppCandTable));
-    HIP_OK(hipMemcpy(d_bpp_cand_.as<void>(), ct.get(), sizeof(BppCandTable), hipMemcpyHostToDevice));
+    bpp_.cand.alloc(sizeof(BppCandTable));
+    HIP_OK(hipMemcpy(bpp_.cand.as<void>(), ct.get(), sizeof(BppCandTable), hipMemcpyHostToDevice));
   }
   d_ints0_.upload(ints0_, st_);
   upload_automaton();
@@ -715,21 +741,19 @@ void Engine::build_planset(PlanSet& ps, int first, int count, const uint32_t* d_
     lmax = std::max(lmax, (int)p.L);
     wmax1 = std::max(wmax1, (int)p.W + 1);
   }
-  DevBuf& d_okbits_end = d_okbits_end_;   // the pair mask by (end, span): scratch of the item enumeration (kept across loads)
-  d_okbits_end.alloc(sizeof(uint32_t) * (size_t)bits_end);
+  d_okbits_end_.alloc(sizeof(uint32_t) * (size_t)bits_end);   // the pair mask by (end, span): scratch of the item enumeration
   ps.d_plans.upload(ps.h, st_);
   const bool chunked = ps.inner_only;   // the plan of the unfiltered mask is rebuilt chunk after chunk: its buffers only grow
   ps.dmin.alloc(sizeof(int16_t) * dmin_b, chunked);
   for (DevBuf* b : {&ps.e_stack, &ps.e_ext, &ps.e_ml, &ps.e_close, &ps.e_hp}) b->alloc(sizeof(double) * cell_b, chunked);
   for (DevBuf* b : {&ps.off_outer, &ps.off_inner, &ps.off_left, &ps.off_right, &ps.cursor}) b->alloc(sizeof(int32_t) * off_b, chunked);
-  DevBuf& d_nitems = d_nitems_;
-  d_nitems.alloc(sizeof(int32_t) * count);
+  d_nitems_.alloc(sizeof(int32_t) * count);
   PlanKernelArgs a;
   a.et = d_et_.as<EnergyTables>();
   a.b.seq = d_seq_.as<uint8_t>(); a.b.ws = d_ws_.as<double>(); a.b.unp = d_unp_.as<uint8_t>();
   a.b.ndot = (flags_ & ELEMDP_DBG_FIX_RSS) ? d_ndot_.as<int32_t>() : nullptr;
   a.okbits = d_okbits;
-  a.okbits_end = d_okbits_end.as<uint32_t>();
+  a.okbits_end = d_okbits_end_.as<uint32_t>();
   a.ncell_max = (int32_t)ncell_max;
   a.n_roles = ps.inner_only ? 1 : 3;
   a.lmax = lmax;
@@ -739,12 +763,12 @@ void Engine::build_planset(PlanSet& ps, int first, int count, const uint32_t* d_
   a.first = 0; a.count = count;
   a.p = ps.arrays();
   a.no_ene = (flags_ & ELEMDP_NO_ENERGY) ? 1 : 0;
-  a.min_span = (flags_ & ELEMDP_DBG_NO_TURN) ? 1 : 5;
+  a.min_span = min_span();
   a.fix_rss = (flags_ & ELEMDP_DBG_FIX_RSS) ? 1 : 0;
   a.count_fast = (loops_finite_ && !a.fix_rss && !getenv("ELEMDP_PLAN_ENUM_COUNT")) ? 1 : 0;
-  HIP_OK(launch_plan_cells(a, d_nitems.as<int32_t>(), st_));
+  HIP_OK(launch_plan_cells(a, d_nitems_.as<int32_t>(), st_));
   std::vector<int32_t> n_items(count);
-  HIP_OK(hipMemcpyAsync(n_items.data(), d_nitems.as<void>(), sizeof(int32_t) * count, hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipMemcpyAsync(n_items.data(), d_nitems_.as<void>(), sizeof(int32_t) * count, hipMemcpyDeviceToHost, st_));
   HIP_OK(hipStreamSynchronize(st_));
   int64_t ib = 0;
   for (int k = 0; k < count; ++k) {
@@ -822,7 +846,7 @@ DpArgs Engine::base_args(const AutomatonLayout& lay, const int32_t* d_ints, cons
   a.ints = d_ints;
   a.params = d_params;
   a.no_prf = (flags_ & ELEMDP_NO_PROFILE) ? 1 : 0;
-  a.m_min = (flags_ & ELEMDP_DBG_NO_TURN) ? 4 : 10;
+  a.m_min = m_min();
   a.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
   a.plans = ps.d_plans.as<SeqPlan>();
   a.n_seq = ps.count;
@@ -840,336 +864,330 @@ DpArgs Engine::base_args(const AutomatonLayout& lay, const int32_t* d_ints, cons
   return a;
 }
 
+// load_batch: check; stream, or stage and upload; canonical mask; BPP filter; resident plan; commit.  A rejected batch leaves the
+// handle without a batch (ELEMDP_ESTATE for what follows) instead of the new sizes over the old device buffers.
 void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix,
                         int n) {
   require_device();
   DeviceGuard dg(device_);
-  // a rejected batch leaves the handle without a batch (ELEMDP_ESTATE for what follows) instead of the new sizes over the old
-  // device buffers
   n_seq_ = 0;
   n_pairs_ = -1;
   streaming_ = false;
-  if (n > 0 && seq && off && qual && qoff && should_stream(off, n)) { stream_setup(seq, off, qual, qoff, fix, n); return; }
-  if (n <= 0 || !seq || !off || !qual || !qoff) throw ArgError("load_batch: empty batch or null pointer");
-  const bool fixmode = flags_ & ELEMDP_DBG_FIX_RSS;
-  if (fixmode && !fix) throw ArgError("load_batch: ELEMDP_DBG_FIX_RSS needs fix_rss strings");
-  const bool no_rss = flags_ & ELEMDP_NO_RSS;
-  h_plans_.assign(n, SeqPlan());
+  BatchShape shape = check_batch(seq, off, qual, qoff, fix, n);
   h_seq_off_.assign(off, off + n + 1);
   h_qual_off_.assign(qoff, qoff + n + 1);
-  int64_t seq_b = 0, pos_b = 0, bits_b = 0;
-  Lmax_ = Wmax_ = nword_max_ = 0;
-  for (int k = 0; k < n; ++k) {
-    const int L = off[k + 1] - off[k];
-    if (L <= 0) throw ArgError("load_batch: empty sequence");
-    if (L > 32000) throw ArgError("load_batch: sequence longer than 32000");
-    if (qoff[k + 1] - qoff[k] != L + 1) throw ArgError("bad seq format. (quality must have L+1 entries)");  // motif_trainer.hpp:139
-    SeqPlan& p = h_plans_[k];
-    p.L = L;
-    p.W = std::min(L, max_span_);
-    p.C = std::min(p.W - 2 - ((flags_ & ELEMDP_DBG_NO_TURN) ? 2 : 5), max_iloop_);  // energy_model.hpp:271-273
-    p.positive = qual[qoff[k + 1] - 1] == 0;
-    p.seq_base = seq_b; p.pos_base = pos_b; p.bits_base = bits_b;
-    const int nword = (int)(((int64_t)(L + 1) * (p.W + 1) + 31) / 32);
-    seq_b += L; pos_b += L + 1; bits_b += nword;
-    Lmax_ = std::max(Lmax_, L); Wmax_ = std::max(Wmax_, p.W); nword_max_ = std::max(nword_max_, nword);
-    p.bpp_eff = 0.;
-  }
-  if ((double)kNumBandStates * (Wmax_ + 1) * (Lmax_ + 1) * au_.S() >= 2147483648.0)
-    throw ArgError("load_batch: sequence too long for this pattern (band table exceeds 2^31 entries)");
-  // static arrays
-  h_seq_.resize((size_t)seq_b);
-  std::vector<uint8_t>& h_seq = h_seq_;
-  uint8_t* h_unp = hb_unp_.get<uint8_t>((size_t)pos_b);
-  double* h_ws = hb_ws_.get<double>((size_t)pos_b);
-  double* h_ews = hb_ews_.get<double>((size_t)pos_b);
-  std::memset(h_unp, 1, (size_t)pos_b);
-  std::vector<int32_t> h_ndot;
-  std::vector<uint32_t> h_bits;
-  if (fixmode) { h_ndot.assign((size_t)pos_b, 0); h_bits.assign((size_t)bits_b, 0u); }
-  for (int k = 0; k < n; ++k) {
-    const SeqPlan& p = h_plans_[k];
-    for (int t = 0; t < p.L; ++t) {
-      const uint8_t c = seq[off[k] + t];
-      if (c > 4) throw ArgError("load_batch: base code out of range");
-      h_seq[p.seq_base + t] = c;
-    }
-    position_weights(qual + qoff[k], p.L + 1, &h_ws[p.pos_base], &h_ews[p.pos_base]);
-    if (fixmode) {
-      const char* f = fix + off[k];
-      nondot_prefix(f, p.L, &h_ndot[p.pos_base]);
-      std::vector<int> open;
-      for (int t = 0; t < p.L; ++t) {
-        h_unp[p.pos_base + t] = f[t] == '.';
-        if (f[t] == '(') open.push_back(t);
-        else if (f[t] == ')') {
-          if (open.empty()) throw ArgError("bad rss: unbalanced");
-          const int o = open.back();
-          open.pop_back();
-          const int d = t + 1 - o;
-          if (d > p.W) throw ArgError("bad rss: pair wider than max_span");
-          const int64_t c = (int64_t)o * (p.W + 1) + d;
-          h_bits[p.bits_base + (c >> 5)] |= 1u << (c & 31);
-        } else if (f[t] != '.') throw ArgError(std::string("bad rss char: ") + f[t]);
-      }
-      if (!open.empty()) throw ArgError("bad rss: unbalanced");
-    }
-  }
-  dbg_lap("load: host arrays");
-  h_order_.resize(n);
-  std::iota(h_order_.begin(), h_order_.end(), 0);
-  std::stable_sort(h_order_.begin(), h_order_.end(), [&](int a, int b) { return h_plans_[a].L > h_plans_[b].L; });
-  d_seq_.upload(h_seq, st_);
-  d_ws_.alloc(sizeof(double) * pos_b);
-  HIP_OK(hipMemcpyAsync(d_ws_.as<void>(), h_ws, sizeof(double) * pos_b, hipMemcpyHostToDevice, st_));
-  d_ews_.alloc(sizeof(double) * pos_b);
-  HIP_OK(hipMemcpyAsync(d_ews_.as<void>(), h_ews, sizeof(double) * pos_b, hipMemcpyHostToDevice, st_));
-  d_zero_ws_.alloc(sizeof(double) * pos_b);
-  HIP_OK(hipMemsetAsync(d_zero_ws_.as<void>(), 0, sizeof(double) * pos_b, st_));
-  d_unp_.alloc((size_t)pos_b);
-  HIP_OK(hipMemcpyAsync(d_unp_.as<void>(), h_unp, (size_t)pos_b, hipMemcpyHostToDevice, st_));
-  if (fixmode) d_ndot_.upload(h_ndot, st_);
-  d_okbits0_.alloc(sizeof(uint32_t) * bits_b);
-  d_okbits1_.alloc(sizeof(uint32_t) * bits_b);
+  if (should_stream(shape)) { stream_setup(seq, off, qual, qoff, fix, std::move(shape)); return; }
+  std::vector<uint8_t> h_seq;      // (becomes h_seq_ at the commit)
+  std::vector<uint32_t> fix_bits;  // (ELEMDP_DBG_FIX_RSS: the pairs of the fixed structures)
+  stage_batch(std::move(shape), seq, off, qual, qoff, fix, h_seq, fix_bits);
+  // ---- canonical mask (d_okbits0_); it also counts the possible pairs = the denominator of bpp_eff
+  const bool rss = !(flags_ & ELEMDP_DBG_FIX_RSS) && !(flags_ & ELEMDP_NO_RSS);
   d_ncanon_.alloc(sizeof(int32_t) * n);
-  DevBuf& d_plans_all = d_plans_all_;
-  d_plans_all.upload(h_plans_, st_);
+  d_plans_all_.upload(h_plans_, st_);
   BatchArrays b;
   b.seq = d_seq_.as<uint8_t>(); b.ws = d_ws_.as<double>(); b.unp = d_unp_.as<uint8_t>(); b.ndot = nullptr;
-  const int min_span = (flags_ & ELEMDP_DBG_NO_TURN) ? 1 : 5;
-  // ---- canonical mask (also counts the possible pairs = denominator of bpp_eff)
-  HIP_OK(launch_mask(b, d_plans_all.as<SeqPlan>(), n, min_span, !fixmode && !no_rss, d_okbits0_.as<uint32_t>(),
-                     d_ncanon_.as<int32_t>(), st_));
+  HIP_OK(launch_mask(b, d_plans_all_.as<SeqPlan>(), n, min_span(), rss, d_okbits0_.as<uint32_t>(), d_ncanon_.as<int32_t>(), st_));
   std::vector<int32_t> ncanon(n);
   HIP_OK(hipMemcpyAsync(ncanon.data(), d_ncanon_.as<void>(), sizeof(int32_t) * n, hipMemcpyDeviceToHost, st_));
   HIP_OK(hipStreamSynchronize(st_));
   for (int k = 0; k < n; ++k) h_plans_[k].n_canonical = ncanon[k];
   dbg_lap("load: uploads + canonical mask");
-  h_lnbpp_.clear();
-  h_lnbpp_base_.clear();
+  resident_plan(bpp_filter(fix_bits));
+  h_seq_.swap(h_seq);
+  n_seq_ = n;   // committed: everything above succeeded
+  opt_eval_first_ = opt_eval_count_ = 0;   // (an evaluation range belongs to the batch it was set for)
+  range_key_[0] = range_key_[1] = -1;
+}
 
-  const uint32_t* final_bits = d_okbits0_.as<uint32_t>();
-  const uint32_t* preset_bits = preset_bits_;
+// the one check of a batch, resident or streamed (writes no member)
+Engine::BatchShape Engine::check_batch(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff,
+                                       const char* fix, int n) const {
+  if (n <= 0 || !seq || !off || !qual || !qoff) throw ArgError("load_batch: empty batch or null pointer");
+  if ((flags_ & ELEMDP_DBG_FIX_RSS) && !fix) throw ArgError("load_batch: ELEMDP_DBG_FIX_RSS needs fix_rss strings");
+  BatchShape b;
+  b.plans.assign(n, SeqPlan());
+  for (int k = 0; k < n; ++k) {
+    const int L = off[k + 1] - off[k];
+    if (L <= 0) throw ArgError("load_batch: empty sequence");
+    if (L > 32000) throw ArgError("load_batch: sequence longer than 32000");
+    if (qoff[k + 1] - qoff[k] != L + 1) throw ArgError("bad seq format. (quality must have L+1 entries)");  // motif_trainer.hpp:139
+    uint8_t cmax = 0;   // (a max, not a search: it vectorises)
+    for (int t = 0; t < L; ++t) cmax = std::max(cmax, seq[off[k] + t]);
+    if (cmax > 4) throw ArgError("load_batch: base code out of range");
+    SeqPlan& p = b.plans[k];
+    p.L = L;
+    p.W = std::min(L, max_span_);
+    p.C = std::min(p.W - 2 - ((flags_ & ELEMDP_DBG_NO_TURN) ? 2 : 5), max_iloop_);  // energy_model.hpp:271-273
+    p.positive = qual[qoff[k + 1] - 1] == 0;
+    p.seq_base = b.n_bases; p.pos_base = b.n_pos; p.bits_base = b.n_words;
+    const int64_t nc = (int64_t)(L + 1) * (p.W + 1);
+    const int nword = (int)((nc + 31) / 32);
+    b.n_bases += L; b.n_pos += L + 1; b.n_words += nword; b.n_cells += nc;
+    b.Lmax = std::max(b.Lmax, L); b.Wmax = std::max(b.Wmax, p.W); b.nword_max = std::max(b.nword_max, nword);
+  }
+  if ((double)kNumBandStates * (b.Wmax + 1) * (b.Lmax + 1) * au_.S() >= 2147483648.0)
+    throw ArgError("load_batch: sequence too long for this pattern (band table exceeds 2^31 entries)");
+  return b;
+}
+
+// the batch arrays on the host (base codes into h_seq, the rest through the pinned staging) and their uploads on st_
+void Engine::stage_batch(BatchShape&& b, const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff,
+                         const char* fix, std::vector<uint8_t>& h_seq, std::vector<uint32_t>& fix_bits) {
+  const int n = (int)b.plans.size();
+  const bool fixmode = flags_ & ELEMDP_DBG_FIX_RSS;
+  h_plans_ = std::move(b.plans);
+  Lmax_ = b.Lmax; Wmax_ = b.Wmax; nword_max_ = b.nword_max;
+  bits_words_ = (size_t)b.n_words;
+  n_cells_total_ = b.n_cells;
+  const size_t pos_b = (size_t)b.n_pos;
+  h_seq.resize((size_t)b.n_bases);
+  uint8_t* h_unp = hb_unp_.get<uint8_t>(pos_b);
+  double* h_ws = hb_ws_.get<double>(pos_b);
+  double* h_ews = hb_ews_.get<double>(pos_b);
+  std::memset(h_unp, 1, pos_b);
+  std::vector<int32_t> h_ndot;
+  if (fixmode) { h_ndot.assign(pos_b, 0); fix_bits.assign(bits_words_, 0u); }
+  for (int k = 0; k < n; ++k) {
+    const SeqPlan& p = h_plans_[k];
+    std::memcpy(&h_seq[p.seq_base], seq + off[k], p.L);
+    position_weights(qual + qoff[k], p.L + 1, &h_ws[p.pos_base], &h_ews[p.pos_base]);
+    if (!fixmode) continue;
+    const char* f = fix + off[k];
+    nondot_prefix(f, p.L, &h_ndot[p.pos_base]);
+    std::vector<int> open;
+    for (int t = 0; t < p.L; ++t) {
+      h_unp[p.pos_base + t] = f[t] == '.';
+      if (f[t] == '(') open.push_back(t);
+      else if (f[t] == ')') {
+        if (open.empty()) throw ArgError("bad rss: unbalanced");
+        const int o = open.back();
+        open.pop_back();
+        const int d = t + 1 - o;
+        if (d > p.W) throw ArgError("bad rss: pair wider than max_span");
+        const int64_t c = (int64_t)o * (p.W + 1) + d;
+        fix_bits[p.bits_base + (c >> 5)] |= 1u << (c & 31);
+      } else if (f[t] != '.') throw ArgError(std::string("bad rss char: ") + f[t]);
+    }
+    if (!open.empty()) throw ArgError("bad rss: unbalanced");
+  }
+  dbg_lap("load: host arrays");
+  h_order_.resize(n);
+  std::iota(h_order_.begin(), h_order_.end(), 0);
+  std::stable_sort(h_order_.begin(), h_order_.end(), [&](int a, int c) { return h_plans_[a].L > h_plans_[c].L; });
+  d_seq_.upload(h_seq, st_);
+  d_ws_.alloc(sizeof(double) * pos_b);
+  HIP_OK(hipMemcpyAsync(d_ws_.as<void>(), h_ws, sizeof(double) * pos_b, hipMemcpyHostToDevice, st_));
+  d_ews_.alloc(sizeof(double) * pos_b);
+  HIP_OK(hipMemcpyAsync(d_ews_.as<void>(), h_ews, sizeof(double) * pos_b, hipMemcpyHostToDevice, st_));
+  d_unp_.alloc(pos_b);
+  HIP_OK(hipMemcpyAsync(d_unp_.as<void>(), h_unp, pos_b, hipMemcpyHostToDevice, st_));
+  if (fixmode) d_ndot_.upload(h_ndot, st_);
+  d_okbits0_.alloc(sizeof(uint32_t) * bits_words_);
+  d_okbits1_.alloc(sizeof(uint32_t) * bits_words_);
+}
+
+// The BPP filter (energy_model.hpp:249-265): bpp_eff of every sequence, and the pair mask the resident plan is built over --
+// d_okbits1_ where the filter ran (or a streamed batch's cache stood in for it), else the canonical / fixed / empty d_okbits0_.
+const uint32_t* Engine::bpp_filter(const std::vector<uint32_t>& fix_bits) {
+  const bool no_rss = flags_ & ELEMDP_NO_RSS, fixmode = flags_ & ELEMDP_DBG_FIX_RSS;
+  const uint32_t* preset_bits = preset_words_ == bits_words_ ? preset_bits_ : nullptr;
   const double* preset_eff = preset_eff_;
-  const bool preset = preset_bits && preset_words_ == (size_t)bits_b && !no_rss && !fixmode && min_bpp_ > 0 && !opt_keep_lnbpp_;
   preset_bits_ = nullptr; preset_eff_ = nullptr; preset_words_ = 0;
-  bits_words_ = (size_t)bits_b;
-  if (preset) {          // the filter's result from an earlier load of the same records (streamed batch)
-    final_bits = d_okbits1_.as<uint32_t>();
-    HIP_OK(hipMemcpyAsync(d_okbits1_.as<void>(), preset_bits, sizeof(uint32_t) * bits_b, hipMemcpyHostToDevice, st_));
+  h_lnbpp_.clear(); h_lnbpp_base_.clear();
+  // the filter's result from an earlier load of the same records (streamed batch)
+  if (preset_bits && !no_rss && !fixmode && min_bpp_ > 0 && !opt_keep_lnbpp_) {
+    HIP_OK(hipMemcpyAsync(d_okbits1_.as<void>(), preset_bits, sizeof(uint32_t) * bits_words_, hipMemcpyHostToDevice, st_));
     HIP_OK(hipStreamSynchronize(st_));
-    for (int k = 0; k < n; ++k) h_plans_[k].bpp_eff = preset_eff[k];
+    for (size_t k = 0; k < h_plans_.size(); ++k) h_plans_[k].bpp_eff = preset_eff[k];
     dbg_lap("load: filtered mask from the cache");
-  } else if (no_rss) {
-    HIP_OK(hipMemsetAsync(d_okbits0_.as<void>(), 0, sizeof(uint32_t) * bits_b, st_));
+    return d_okbits1_.as<uint32_t>();
+  }
+  if (no_rss) {
+    HIP_OK(hipMemsetAsync(d_okbits0_.as<void>(), 0, sizeof(uint32_t) * bits_words_, st_));
     for (auto& p : h_plans_) p.bpp_eff = 0.;  // em.set_seq is never called in --no-rss mode (motif_model.hpp:57)
   } else if (fixmode) {
-    HIP_OK(hipMemcpyAsync(d_okbits0_.as<void>(), h_bits.data(), sizeof(uint32_t) * bits_b, hipMemcpyHostToDevice, st_));
+    HIP_OK(hipMemcpyAsync(d_okbits0_.as<void>(), fix_bits.data(), sizeof(uint32_t) * bits_words_, hipMemcpyHostToDevice, st_));
     HIP_OK(hipStreamSynchronize(st_));
-    for (int k = 0; k < n; ++k) {
+    for (auto& p : h_plans_) {
       int nbp = 0;
-      const SeqPlan& p = h_plans_[k];
       const int nword = (int)(((int64_t)(p.L + 1) * (p.W + 1) + 31) / 32);
-      for (int w = 0; w < nword; ++w) nbp += __builtin_popcount(h_bits[p.bits_base + w]);
-      h_plans_[k].bpp_eff = (double)nbp / (double)ncanon[k];
+      for (int w = 0; w < nword; ++w) nbp += __builtin_popcount(fix_bits[p.bits_base + w]);
+      p.bpp_eff = (double)nbp / (double)p.n_canonical;
     }
   } else if (min_bpp_ > 0) {
-    final_bits = d_okbits1_.as<uint32_t>();
-    if (opt_keep_lnbpp_) h_lnbpp_base_.assign(n + 1, 0);
-    if (Wmax_ <= kBppLinMaxSpan && !opt_bpp_log_) {
-      // ---- K1: BPP filter in the linear semiring (bpp_kernels.hip): no plan of the unfiltered mask; chunks by table memory
-      const int64_t cells_cap = 64LL * 1000 * 1000;     // 23 doubles per cell: ~12 GB per chunk
-      int first = 0;
-      while (first < n) {
-        int count = 0;
-        int64_t cells = 0, pos = 0;
-        int lmax = 0, wmax = 0;
-        std::vector<SeqPlan> hp;
-        while (first + count < n) {
-          SeqPlan p = h_plans_[first + count];
-          const int64_t nc = (int64_t)(p.L + 1) * (p.W + 1);
-          if (count > 0 && cells + nc > cells_cap) break;
-          p.cell_base = cells; p.dmin_base = pos;
-          cells += nc; pos += p.L + 1;
-          lmax = std::max(lmax, (int)p.L); wmax = std::max(wmax, (int)p.W);
-          hp.push_back(p);
-          ++count;
-        }
-        d_bpp_plans_.upload(hp, st_);
-        d_bpp_xw_.alloc(sizeof(double) * 5 * (size_t)cells, true);
-        // (the per-sequence sweeps read plane entries outside a sequence's triangle with coefficient 0: they must be finite, so a
-        // fresh allocation is cleared once; later loads leave finite values of theirs)
-        for (auto pb : {std::make_pair(&d_bpp_band_in_, sizeof(double) * kBppInPlanes * (size_t)cells),
-                        std::make_pair(&d_bpp_band_out_, sizeof(double) * kBppOutPlanes * (size_t)cells)}) {
-          const void* before = pb.first->as<void>();
-          const size_t before_b = pb.first->bytes();
-          pb.first->alloc(pb.second, true);
-          if (pb.first->as<void>() != before || pb.first->bytes() != before_b || !bpp_planes_finite_)
-            HIP_OK(hipMemsetAsync(pb.first->as<void>(), 0, pb.first->bytes(), st_));
-        }
-        bpp_planes_finite_ = true;
-        d_bpp_ext_in_.alloc(sizeof(double) * (size_t)pos, true);
-        d_bpp_ext_out_.alloc(sizeof(double) * (size_t)pos, true);
-        d_bpp_dmin_.alloc(sizeof(int16_t) * (size_t)pos, true);
-        d_bpp_kept_.alloc(sizeof(int32_t) * count, true);
-        DevBuf d_lnbpp;
-        BppLinArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.et = d_et_.as<EnergyTables>();
-        a.xet = d_xet_.as<EnergyTables>();
-        a.cand = d_bpp_cand_.as<BppCandTable>();
-        d_bpp_plist_.alloc(sizeof(int16_t) * (size_t)cells, true);
-        d_bpp_poff_.alloc(sizeof(int32_t) * (size_t)count * (wmax + 2), true);
-        a.plist = d_bpp_plist_.as<int16_t>(); a.poff = d_bpp_poff_.as<int32_t>(); a.poff_stride = wmax + 2;
-        for (int k = 0; k < count; ++k) a.pmax = std::max(a.pmax, ncanon[first + k]);
-        a.plans = d_bpp_plans_.as<SeqPlan>();
-        a.seq = d_seq_.as<uint8_t>();
-        a.okbits = d_okbits0_.as<uint32_t>();
-        a.dmin = d_bpp_dmin_.as<int16_t>();
-        a.xw = d_bpp_xw_.as<double>(); a.xw_stride = (size_t)cells;
-        a.tin = d_bpp_band_in_.as<double>(); a.tout = d_bpp_band_out_.as<double>(); a.t_stride = (size_t)cells;
-        a.lo_in = d_bpp_ext_in_.as<double>(); a.lo_out = d_bpp_ext_out_.as<double>();
-        a.no_ene = (flags_ & ELEMDP_NO_ENERGY) ? 1 : 0;
-        a.min_span = min_span;
-        a.m_min = (flags_ & ELEMDP_DBG_NO_TURN) ? 4 : 10;
-        a.okbits_out = d_okbits1_.as<uint32_t>();
-        a.kept = d_bpp_kept_.as<int32_t>();
-        a.log_min_bpp = std::log(min_bpp_);
-        DevBuf d_prof;
-        if (getenv("ELEMDP_BPP_PROF")) {
-          d_prof.alloc(sizeof(unsigned long long) * 16);
-          HIP_OK(hipMemsetAsync(d_prof.as<void>(), 0, sizeof(unsigned long long) * 16, st_));
-          a.prof = d_prof.as<unsigned long long>();
-        }
-        if (opt_keep_lnbpp_) { d_lnbpp.alloc(sizeof(double) * cells); a.lnbpp = d_lnbpp.as<double>(); }
-        HIP_OK(launch_bpp_lin(a, count, lmax, wmax, st_));
-        std::vector<int32_t> kept(count);
-        HIP_OK(hipMemcpyAsync(kept.data(), d_bpp_kept_.as<void>(), sizeof(int32_t) * count, hipMemcpyDeviceToHost, st_));
-        HIP_OK(hipStreamSynchronize(st_));
-        for (int k = 0; k < count; ++k) h_plans_[first + k].bpp_eff = (double)kept[k] / (double)ncanon[first + k];
-        dbg_lap("load: BPP filter, linear (chunk)");
-        if (a.prof) {
-          unsigned long long h[16];
-          HIP_OK(hipMemcpy(h, a.prof, sizeof(h), hipMemcpyDeviceToHost));
-          static const char* nm[8] = {"stage", "stems", "loops generic", "loops 1xn / bulge", "special shapes", "barrier 1", "unary", "barrier 2"};
-          for (int dir = 0; dir < 2; ++dir) {
-            unsigned long long tot = 0;
-            for (int k = 0; k < 8; ++k) tot += h[dir * 8 + k];
-            for (int k = 0; k < 8; ++k)
-              fprintf(stderr, "[elemdp bpp prof] %s %-18s %6.2f %%  %.3g cycles per sequence\n", dir ? "out" : "in ", nm[k],
-                      tot ? 100. * (double)h[dir * 8 + k] / (double)tot : 0., (double)h[dir * 8 + k] / count);
-          }
-        }
-        if (opt_keep_lnbpp_) {
-          const size_t base = h_lnbpp_.size();
-          h_lnbpp_.resize(base + cells);
-          HIP_OK(hipMemcpy(h_lnbpp_.data() + base, d_lnbpp.as<void>(), sizeof(double) * cells, hipMemcpyDeviceToHost));
-          for (int k = 0; k < count; ++k) h_lnbpp_base_[first + k] = (int64_t)base + hp[k].cell_base;
-        }
-        first += count;
-      }
-    } else {
-    // ---- K1 in log space over a plan of the unfiltered mask (bands wider than the linear range; option "bpp_log")
-    // ---- K1: BPP filter, in chunks (the plan of the unfiltered mask is large and only needed here)
-    int64_t cells_cap = 24LL * 1000 * 1000;
-    int first = 0;
-    PlanSet& tmp = bpp_plan_;   // (one set of buffers for all chunks and loads: DevBuf::alloc keeps what is large enough;
-    tmp.inner_only = true;      //  bounded by cells_cap: a few GB)
-    while (first < n) {
-      int count = 0;
-      int64_t cells = 0;
-      while (first + count < n && (count == 0 || cells + (int64_t)(h_plans_[first + count].L + 1) * (h_plans_[first + count].W + 1) <= cells_cap)) {
-        cells += (int64_t)(h_plans_[first + count].L + 1) * (h_plans_[first + count].W + 1);
-        ++count;
-      }
-      build_planset(tmp, first, count, d_okbits0_.as<uint32_t>());
-      dbg_lap("load: plan of the unfiltered mask (chunk)");
-      // table slots for S = 1, one per sequence of the chunk: buffers of their own, so that the (much larger) slots of the
-      // evaluation pipelines survive a load_batch -- the mini-batch training mode loads before every evaluation
-      {
-        const size_t band1 = (size_t)kNumBandStates * (Wmax_ + 1) * (Lmax_ + 1), ext1 = (size_t)(Lmax_ + 1);
-        bpp_planes_finite_ = false;   // (log-space values: log 0 = -inf)
-        d_bpp_band_in_.alloc(band1 * count * sizeof(double), true);
-        d_bpp_band_out_.alloc(band1 * count * sizeof(double), true);
-        d_bpp_ext_in_.alloc(ext1 * count * sizeof(double), true);
-        d_bpp_ext_out_.alloc(ext1 * count * sizeof(double), true);
-        d_bpp_tmp_.alloc(ext1 * 3 * count * sizeof(double), true);
-      }
-      std::vector<int32_t> order(count);
-      std::iota(order.begin(), order.end(), 0);
-      std::stable_sort(order.begin(), order.end(), [&](int a2, int b2) { return tmp.h[a2].L > tmp.h[b2].L; });
-      DevBuf& d_order = d_bpp_order_; DevBuf& d_rows = d_bpp_rows_; DevBuf& d_kept = d_bpp_kept_;
-      DevBuf d_lnbpp;
-      d_order.upload(order, st_);
-      const int stride = 10;
-      d_rows.alloc(sizeof(double) * stride * count);
-      d_kept.alloc(sizeof(int32_t) * count);
-      TrArgs a;
-      std::memset(&a, 0, sizeof(a));
-      a.lay = lay0_;
-      a.layp = d_lay0_.as<AutomatonLayout>();
-      a.ints = d_ints0_.as<int32_t>();
-      a.layp_r = a.layp; a.ints_r = a.ints;
-      a.params = d_params0_.as<double>();
-      a.no_prf = 1;
-      a.m_min = (flags_ & ELEMDP_DBG_NO_TURN) ? 4 : 10;
-      a.plans = tmp.d_plans.as<SeqPlan>();
-      a.grp = d_order.as<int32_t>();
-      a.b.seq = d_seq_.as<uint8_t>(); a.b.ws = d_zero_ws_.as<double>(); a.b.unp = d_unp_.as<uint8_t>(); a.b.ndot = nullptr;
-      a.okbits = d_okbits0_.as<uint32_t>();
-      a.p = tmp.arrays();
-      a.band_in = d_bpp_band_in_.as<double>(); a.band_out = d_bpp_band_out_.as<double>();
-      a.ext_in = d_bpp_ext_in_.as<double>(); a.ext_out = d_bpp_ext_out_.as<double>();
-      a.band_stride = (size_t)kNumBandStates * (Wmax_ + 1) * (Lmax_ + 1);
-      a.ext_stride = (size_t)(Lmax_ + 1);
-      a.tmp = d_bpp_tmp_.as<double>();
-      a.tmp_stride = a.ext_stride;
-      a.seq_out = d_rows.as<double>();
-      a.out_stride = stride;
-      BppOut o;
-      o.okbits_out = d_okbits1_.as<uint32_t>();
-      o.kept = d_kept.as<int32_t>();
-      o.log_min_bpp = std::log(min_bpp_);
-      o.lnbpp = nullptr;
-      if (opt_keep_lnbpp_) { d_lnbpp.alloc(sizeof(double) * cells); o.lnbpp = d_lnbpp.as<double>(); }
-      HIP_OK(hipMemsetAsync(d_rows.as<void>(), 0, sizeof(double) * stride * count, st_));
-      const int Lg = tmp.h[order[0]].L;
-      HIP_OK(launch_bpp_group(a, o, count, Lg, std::min(Lg, max_span_), st_));
-      std::vector<int32_t> kept(count);
-      HIP_OK(hipMemcpyAsync(kept.data(), d_kept.as<void>(), sizeof(int32_t) * count, hipMemcpyDeviceToHost, st_));
-      HIP_OK(hipStreamSynchronize(st_));
-      for (int k = 0; k < count; ++k) h_plans_[first + k].bpp_eff = (double)kept[k] / (double)ncanon[first + k];
-      dbg_lap("load: BPP filter (chunk)");
-      if (opt_keep_lnbpp_) {
-        const size_t base = h_lnbpp_.size();
-        h_lnbpp_.resize(base + cells);
-        HIP_OK(hipMemcpy(h_lnbpp_.data() + base, d_lnbpp.as<void>(), sizeof(double) * cells, hipMemcpyDeviceToHost));
-        for (int k = 0; k < count; ++k) h_lnbpp_base_[first + k] = (int64_t)base + tmp.h[k].cell_base;
-      }
-      first += count;
-    }
-    }
+    bpp_chunks(Wmax_ <= kBppLinMaxSpan && !opt_bpp_log_);   // the linear form, or log space (bands too wide; option "bpp_log")
+    return d_okbits1_.as<uint32_t>();
   } else {
     for (auto& p : h_plans_) p.bpp_eff = 1.;  // 0 == min_BPP: nbp = total (energy_model.hpp:249-251)
   }
-  // ---- resident plan of the filtered mask
-  if (final_bits != d_okbits1_.as<uint32_t>())
-    HIP_OK(hipMemcpyAsync(d_okbits1_.as<void>(), d_okbits0_.as<void>(), sizeof(uint32_t) * bits_b, hipMemcpyDeviceToDevice, st_));
+  return d_okbits0_.as<uint32_t>();
+}
+
+// K1 chunk after chunk: the form writes the kept pairs to d_okbits1_, their count to bpp_.kept, ln BPP per cell to lnbpp
+void Engine::bpp_chunks(bool lin) {
+  const int n = (int)h_plans_.size();
+  // cells per chunk, bounded by the filter's memory: the linear form holds 23 doubles per cell (~12 GB per chunk), the log-space
+  // form a plan of the unfiltered mask (a few GB)
+  const int64_t cells_cap = (lin ? 64LL : 24LL) * 1000 * 1000;
+  if (opt_keep_lnbpp_) h_lnbpp_base_.assign(n + 1, 0);
+  for (int first = 0, count = 0; first < n; first += count) {
+    int64_t cells = 0;
+    for (count = 0; first + count < n; ++count) {
+      const int64_t nc = (int64_t)(h_plans_[first + count].L + 1) * (h_plans_[first + count].W + 1);
+      if (count > 0 && cells + nc > cells_cap) break;
+      cells += nc;
+    }
+    bpp_.kept.alloc(sizeof(int32_t) * count, true);
+    DevBuf d_lnbpp;
+    if (opt_keep_lnbpp_) d_lnbpp.alloc(sizeof(double) * cells);
+    if (lin) bpp_lin_chunk(first, count, cells, d_lnbpp.as<double>());
+    else bpp_log_chunk(first, count, cells, d_lnbpp.as<double>());
+    std::vector<int32_t> kept(count);
+    HIP_OK(hipMemcpyAsync(kept.data(), bpp_.kept.as<void>(), sizeof(int32_t) * count, hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipStreamSynchronize(st_));
+    for (int k = 0; k < count; ++k) h_plans_[first + k].bpp_eff = (double)kept[k] / (double)h_plans_[first + k].n_canonical;
+    dbg_lap(lin ? "load: BPP filter, linear (chunk)" : "load: BPP filter (chunk)");
+    if (opt_keep_lnbpp_) {   // (cells of a chunk in sequence order)
+      const size_t base = h_lnbpp_.size();
+      h_lnbpp_.resize(base + cells);
+      HIP_OK(hipMemcpy(h_lnbpp_.data() + base, d_lnbpp.as<void>(), sizeof(double) * cells, hipMemcpyDeviceToHost));
+      int64_t c = (int64_t)base;
+      for (int k = first; k < first + count; ++k) { h_lnbpp_base_[k] = c; c += (int64_t)(h_plans_[k].L + 1) * (h_plans_[k].W + 1); }
+    }
+  }
+}
+
+// the linear form of K1 (bpp_kernels.hip) on the sequences [first, first + count): no plan of the unfiltered mask
+void Engine::bpp_lin_chunk(int first, int count, int64_t cells, double* lnbpp) {
+  BppScratch& f = bpp_;
+  std::vector<SeqPlan> hp(h_plans_.begin() + first, h_plans_.begin() + first + count);
+  int64_t cell_b = 0, pos_b = 0;
+  int lmax = 0, wmax = 0, pmax = 0;
+  for (SeqPlan& p : hp) {
+    p.cell_base = cell_b; p.dmin_base = pos_b;
+    cell_b += (int64_t)(p.L + 1) * (p.W + 1); pos_b += p.L + 1;
+    lmax = std::max(lmax, (int)p.L); wmax = std::max(wmax, (int)p.W); pmax = std::max(pmax, (int)p.n_canonical);
+  }
+  f.plans.upload(hp, st_);
+  f.xw.alloc(sizeof(double) * 5 * (size_t)cells, true);
+  // (the per-sequence sweeps read plane entries outside a sequence's triangle with coefficient 0: they must be finite, so a
+  // fresh allocation is cleared once; later loads leave finite values of theirs)
+  if (f.band_in.alloc(sizeof(double) * kBppInPlanes * (size_t)cells, true) || !f.planes_finite)
+    HIP_OK(hipMemsetAsync(f.band_in.as<void>(), 0, f.band_in.bytes(), st_));
+  if (f.band_out.alloc(sizeof(double) * kBppOutPlanes * (size_t)cells, true) || !f.planes_finite)
+    HIP_OK(hipMemsetAsync(f.band_out.as<void>(), 0, f.band_out.bytes(), st_));
+  f.planes_finite = true;
+  for (DevBuf* b : {&f.ext_in, &f.ext_out}) b->alloc(sizeof(double) * (size_t)pos_b, true);
+  f.dmin.alloc(sizeof(int16_t) * (size_t)pos_b, true);
+  f.plist.alloc(sizeof(int16_t) * (size_t)cells, true);
+  f.poff.alloc(sizeof(int32_t) * (size_t)count * (wmax + 2), true);
+  BppLinArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.et = d_et_.as<EnergyTables>(); a.xet = d_xet_.as<EnergyTables>(); a.cand = f.cand.as<BppCandTable>();
+  a.plist = f.plist.as<int16_t>(); a.poff = f.poff.as<int32_t>(); a.poff_stride = wmax + 2;
+  a.pmax = pmax;
+  a.plans = f.plans.as<SeqPlan>();
+  a.seq = d_seq_.as<uint8_t>();
+  a.okbits = d_okbits0_.as<uint32_t>();
+  a.dmin = f.dmin.as<int16_t>();
+  a.xw = f.xw.as<double>(); a.xw_stride = (size_t)cells;
+  a.tin = f.band_in.as<double>(); a.tout = f.band_out.as<double>(); a.t_stride = (size_t)cells;
+  a.lo_in = f.ext_in.as<double>(); a.lo_out = f.ext_out.as<double>();
+  a.no_ene = (flags_ & ELEMDP_NO_ENERGY) ? 1 : 0; a.min_span = min_span(); a.m_min = m_min();
+  a.okbits_out = d_okbits1_.as<uint32_t>();
+  a.kept = f.kept.as<int32_t>();
+  a.log_min_bpp = std::log(min_bpp_);
+  a.lnbpp = lnbpp;
+  DevBuf d_prof;
+  if (getenv("ELEMDP_BPP_PROF")) {
+    d_prof.alloc(sizeof(unsigned long long) * 16);
+    HIP_OK(hipMemsetAsync(d_prof.as<void>(), 0, sizeof(unsigned long long) * 16, st_));
+    a.prof = d_prof.as<unsigned long long>();
+  }
+  HIP_OK(launch_bpp_lin(a, count, lmax, wmax, st_));
+  if (a.prof) {
+    unsigned long long h[16];
+    HIP_OK(hipMemcpyAsync(h, a.prof, sizeof(h), hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipStreamSynchronize(st_));
+    static const char* nm[8] = {"stage", "stems", "loops generic", "loops 1xn / bulge", "special shapes", "barrier 1", "unary", "barrier 2"};
+    for (int dir = 0; dir < 2; ++dir) {
+      unsigned long long tot = 0;
+      for (int k = 0; k < 8; ++k) tot += h[dir * 8 + k];
+      for (int k = 0; k < 8; ++k)
+        fprintf(stderr, "[elemdp bpp prof] %s %-18s %6.2f %%  %.3g cycles per sequence\n", dir ? "out" : "in ", nm[k],
+                tot ? 100. * (double)h[dir * 8 + k] / (double)tot : 0., (double)h[dir * 8 + k] / count);
+    }
+  }
+}
+
+// the log-space form of K1 on [first, first + count): the one-state automaton over a plan of the unfiltered mask
+void Engine::bpp_log_chunk(int first, int count, int64_t cells, double* lnbpp) {
+  BppScratch& f = bpp_;
+  PlanSet& tmp = f.plan;   // (one set of buffers for all chunks and loads: DevBuf::alloc keeps what is large enough)
+  tmp.inner_only = true;
+  build_planset(tmp, first, count, d_okbits0_.as<uint32_t>());
+  dbg_lap("load: plan of the unfiltered mask (chunk)");
+  // table slots for S = 1: buffers of their own, so that the (much larger) slots of the evaluation pipelines survive a
+  // load_batch -- the mini-batch training mode loads before every evaluation
+  const size_t band1 = (size_t)kNumBandStates * (Wmax_ + 1) * (Lmax_ + 1), ext1 = (size_t)(Lmax_ + 1);
+  f.planes_finite = false;   // (log-space values: log 0 = -inf)
+  for (DevBuf* b : {&f.band_in, &f.band_out}) b->alloc(band1 * count * sizeof(double), true);
+  for (DevBuf* b : {&f.ext_in, &f.ext_out}) b->alloc(ext1 * count * sizeof(double), true);
+  f.tmp.alloc(ext1 * 3 * count * sizeof(double), true);
+  const SeqPlan& last = h_plans_.back();   // (nothing writes the weights: cleared when fresh)
+  if (f.zero_ws.alloc(sizeof(double) * (size_t)(last.pos_base + last.L + 1)))
+    HIP_OK(hipMemsetAsync(f.zero_ws.as<void>(), 0, f.zero_ws.bytes(), st_));
+  std::vector<int32_t> order(count);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a2, int b2) { return tmp.h[a2].L > tmp.h[b2].L; });
+  f.order.upload(order, st_);
+  const int stride = 10;
+  f.rows.alloc(sizeof(double) * stride * count);
+  TrArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.lay = lay0_;
+  a.layp = d_lay0_.as<AutomatonLayout>();
+  a.ints = d_ints0_.as<int32_t>();
+  a.layp_r = a.layp; a.ints_r = a.ints;
+  a.params = d_params0_.as<double>();
+  a.no_prf = 1;
+  a.m_min = m_min();
+  a.plans = tmp.d_plans.as<SeqPlan>();
+  a.grp = f.order.as<int32_t>();
+  a.b.seq = d_seq_.as<uint8_t>(); a.b.ws = f.zero_ws.as<double>(); a.b.unp = d_unp_.as<uint8_t>(); a.b.ndot = nullptr;
+  a.okbits = d_okbits0_.as<uint32_t>();
+  a.p = tmp.arrays();
+  a.band_in = f.band_in.as<double>(); a.band_out = f.band_out.as<double>();
+  a.ext_in = f.ext_in.as<double>(); a.ext_out = f.ext_out.as<double>();
+  a.band_stride = band1; a.ext_stride = ext1;
+  a.tmp = f.tmp.as<double>(); a.tmp_stride = ext1;
+  a.seq_out = f.rows.as<double>(); a.out_stride = stride;
+  BppOut o;
+  o.okbits_out = d_okbits1_.as<uint32_t>();
+  o.kept = f.kept.as<int32_t>();
+  o.log_min_bpp = std::log(min_bpp_);
+  o.lnbpp = lnbpp;
+  HIP_OK(hipMemsetAsync(f.rows.as<void>(), 0, sizeof(double) * stride * count, st_));
+  const int Lg = tmp.h[order[0]].L;
+  HIP_OK(launch_bpp_group(a, o, count, Lg, std::min(Lg, max_span_), st_));
+}
+
+// the resident plan of the filtered mask (in d_okbits1_) and the buffers the evaluations size by the batch
+void Engine::resident_plan(const uint32_t* mask) {
+  const int n = (int)h_plans_.size();
+  if (mask != d_okbits1_.as<uint32_t>())
+    HIP_OK(hipMemcpyAsync(d_okbits1_.as<void>(), mask, sizeof(uint32_t) * bits_words_, hipMemcpyDeviceToDevice, st_));
   plan_.permuted = true;
   build_planset(plan_, 0, n, d_okbits1_.as<uint32_t>());
   dbg_lap("load: plan of the filtered mask");
   for (int k = 0; k < n; ++k) { plan_.h[k].bpp_eff = h_plans_[k].bpp_eff; plan_.h[k].n_canonical = h_plans_[k].n_canonical; }
   plan_.d_plans.upload(plan_.h, st_);
-  for (int k = 0; k < n; ++k) h_plans_[k] = plan_.h[k];
+  h_plans_ = plan_.h;
   d_order_.upload(h_order_, st_);
-  {
-    std::vector<SeqPlan> sorted(n);
-    for (int k = 0; k < n; ++k) { sorted[k] = h_plans_[h_order_[k]]; sorted[k].index = h_order_[k]; }
-    d_plans_sorted_.upload(sorted, st_);
-    HIP_OK(hipStreamSynchronize(st_));
-  }
-  n_cells_total_ = 0;
-  for (auto const& pl : h_plans_) n_cells_total_ += (int64_t)(pl.L + 1) * (pl.W + 1);
+  std::vector<SeqPlan> sorted(n);
+  for (int k = 0; k < n; ++k) { sorted[k] = h_plans_[h_order_[k]]; sorted[k].index = h_order_[k]; }
+  d_plans_sorted_.upload(sorted, st_);
+  HIP_OK(hipStreamSynchronize(st_));
   d_xwc_.alloc(sizeof(double) * 10 * (size_t)n_cells_total_);
   d_flagged_.alloc(sizeof(int32_t) * ((size_t)n + 1));
   lin_slots_ = 0;
@@ -1178,43 +1196,24 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   n_slots_ = 0;
   HIP_OK(hipStreamSynchronize(st_));
   dbg_lap("load: weights / output buffers");
-  n_seq_ = n;   // committed: everything above succeeded
-  opt_eval_first_ = opt_eval_count_ = 0;   // (an evaluation range belongs to the batch it was set for)
-  range_key_[0] = range_key_[1] = -1;
 }
 
 // ---- streaming --------------------------------------------------------------------------------------------------------
-bool Engine::should_stream(const int32_t* off, int n) {
+bool Engine::should_stream(const BatchShape& b) {
   if (inner_) return false;
-  if (opt_max_resident_ > 0) return n > opt_max_resident_;
+  if (opt_max_resident_ > 0) return (int)b.plans.size() > opt_max_resident_;
   // resident needs per sequence: plan (terms, CSR offsets, items in four orders, their weights) + its share of the table
   // slots; a batch whose plan alone would take more than half of the free device memory is streamed
-  double cells = 0;
-  for (int k = 0; k < n; ++k) {
-    const double L = off[k + 1] - off[k], W = std::min<double>(L, max_span_);
-    cells += (L + 1) * (W + 1);
-  }
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
   const size_t held = d_band_in_.bytes() + d_band_out_.bytes() + d_xwc_.bytes() + d_xwi_.bytes();
-  return cells * 600.0 > 0.5 * (double)(free_b + held);
+  return (double)b.n_cells * 600.0 > 0.5 * (double)(free_b + held);
 }
 
-void Engine::stream_setup(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix, int n) {
-  if ((flags_ & ELEMDP_DBG_FIX_RSS) && !fix) throw ArgError("load_batch: ELEMDP_DBG_FIX_RSS needs fix_rss strings");
-  h_seq_off_.assign(off, off + n + 1);
-  h_qual_off_.assign(qoff, qoff + n + 1);
-  h_plans_.assign(n, SeqPlan());
-  double cells = 0;
-  for (int k = 0; k < n; ++k) {
-    const int L = off[k + 1] - off[k];
-    if (L <= 0) throw ArgError("load_batch: empty sequence");
-    if (qoff[k + 1] - qoff[k] != L + 1) throw ArgError("bad seq format. (quality must have L+1 entries)");
-    h_plans_[k].L = L;
-    h_plans_[k].W = std::min(L, max_span_);
-    h_plans_[k].positive = qual[qoff[k + 1] - 1] == 0;
-    cells += (double)(L + 1) * (h_plans_[k].W + 1);
-  }
+void Engine::stream_setup(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix,
+                          BatchShape&& b) {
+  const int n = (int)b.plans.size();
+  h_plans_ = std::move(b.plans);
   st_seq_.assign(seq + off[0], seq + off[n]);
   st_qual_.assign(qual + qoff[0], qual + qoff[n]);
   if (fix) st_fix_.assign(fix + off[0], fix + off[n]); else st_fix_.clear();
@@ -1223,7 +1222,7 @@ void Engine::stream_setup(const uint8_t* seq, const int32_t* off, const uint8_t*
   else {   // two inner engines, each with a fifth of the free memory for its plan
     size_t free_b = 0, total_b = 0;
     HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    const double per_seq = cells / n * 600.0;
+    const double per_seq = (double)b.n_cells / n * 600.0;
     st_chunk_ = (int)std::max(256.0, std::min((double)n, 0.2 * (double)free_b / per_seq));
     st_slot_budget_ = (size_t)(0.2 * (double)free_b);
   }
@@ -1235,8 +1234,8 @@ void Engine::stream_setup(const uint8_t* seq, const int32_t* off, const uint8_t*
     st_have_eff_.assign(nchunks, 0);
   }
   // (the buffers of an earlier resident batch would only stand in the way of the inner engines)
-  for (DevBuf* b : {&d_band_in_, &d_band_out_, &d_ext_in_, &d_ext_out_, &d_tmp_, &d_xwc_, &d_xwi_, &d_a_in_, &d_a_out_, &d_tr_ext_})
-    b->reset();
+  for (DevBuf* d : {&d_band_in_, &d_band_out_, &d_ext_in_, &d_ext_out_, &d_tmp_, &d_xwc_, &d_xwi_, &d_a_in_, &d_a_out_, &d_tr_ext_})
+    d->reset();
   n_slots_ = 0; lin_slots_ = 0;
   streaming_ = true;
   n_seq_ = n;
@@ -1372,7 +1371,7 @@ TrArgs Engine::log_pipeline_args() {
   a.ints = d_ints_.as<int32_t>();
   a.params = d_params_.as<double>();
   a.no_prf = (flags_ & ELEMDP_NO_PROFILE) ? 1 : 0;
-  a.m_min = (flags_ & ELEMDP_DBG_NO_TURN) ? 4 : 10;
+  a.m_min = m_min();
   a.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
   a.first_pass_only = opt_first_pass_only_ ? 1 : 0;
   a.lik_ratio = (flags_ & ELEMDP_LIK_RATIO) ? 1 : 0;
@@ -1480,7 +1479,7 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int
   a.fast = (opt_fast_ && !(flags_ & ELEMDP_DBG_FIX_RSS)) ? 1 : 0;
   a.nblk = opt_nblk_;
   a.no_prf = (flags_ & ELEMDP_NO_PROFILE) ? 1 : 0;
-  a.m_min = (flags_ & ELEMDP_DBG_NO_TURN) ? 4 : 10;
+  a.m_min = m_min();
   a.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
   a.lik_ratio = (flags_ & ELEMDP_LIK_RATIO) ? 1 : 0;
   a.ext_block = (flags_ & (ELEMDP_DBG_NO_TURN | ELEMDP_DBG_FIX_RSS)) ? 1 : 4;   // (pairs span >= 5 positions unless one of these)
@@ -1768,7 +1767,6 @@ void Engine::debug_tables(double* inside, double* outside, double* inside_o, dou
     HIP_OK(hipMemcpy(bits.data(), d_okbits1_.as<uint32_t>() + p.bits_base, sizeof(uint32_t) * ((cells + 31) / 32), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(dmin.data(), plan_.arrays().dmin + p.dmin_base, sizeof(int16_t) * (L + 1), hipMemcpyDeviceToHost));
   }
-  const int m_min = (flags_ & ELEMDP_DBG_NO_TURN) ? 4 : 10;
   auto pair_ok = [&](int i, int d) {
     if (i < 0 || d < 0 || d > W || i + d > L) return false;
     const size_t c = (size_t)i * (W + 1) + d;
@@ -1779,7 +1777,7 @@ void Engine::debug_tables(double* inside, double* outside, double* inside_o, dou
     switch (e) {
       case ST_P: return pair_ok(i, d);
       case ST_E: return i > 0 && d + 2 <= W && pair_ok(i - 1, d + 2);
-      case ST_M: return 0 < i && i + d < L && d <= W && m_min <= d;
+      case ST_M: return 0 < i && i + d < L && d <= W && m_min() <= d;
       case ST_B: case ST_1: case ST_2: return left_ok(i, d);
       default: return true;
     }

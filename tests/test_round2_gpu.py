@@ -163,6 +163,35 @@ def test_rejected_batch_leaves_the_handle_without_a_batch():
     assert again[0] == pytest.approx(ref[0], rel=1e-12)
 
 
+def test_rejected_streamed_batch_leaves_the_handle_without_a_batch():
+    """A batch that streams (option max_resident) gets the same check as a resident one: a record with base code 5 is refused
+    by load_batch itself, with the resident batch's message, and not at the first evaluation of its chunk."""
+    seqs, quals = synth.synth_batch(40, 60)
+    bad = [s.copy() for s in seqs]
+    bad[27][10] = 5                                  # in the second chunk
+    resident = api.Engine("((.*.))")
+    with pytest.raises(api.ElemdpError) as e_res:
+        resident.load_batch(bad, quals)
+    eng = api.Engine("((.*.))")
+    eng.set_option("max_resident", 16)
+    x = eng.initial_params(1.0)
+    eng.load_batch(seqs, quals)
+    ref = eng.train_eval(x)
+    with pytest.raises(api.ElemdpError) as e:
+        eng.load_batch(bad, quals)
+    assert e.value.code == e_res.value.code and str(e.value) == str(e_res.value)
+    assert "base code out of range" in str(e.value)
+    with pytest.raises(api.ElemdpError) as e:
+        eng.train_eval(x)
+    assert e.value.code == -4
+    with pytest.raises(api.ElemdpError) as e:
+        eng.scan(x)
+    assert e.value.code == -4
+    eng.load_batch(seqs, quals)                      # and the handle is still usable
+    again = eng.train_eval(x)
+    assert again[0] == pytest.approx(ref[0], rel=1e-12)
+
+
 def test_engine_binds_its_device_in_every_entry_point():
     """A handle used from another host thread (MiniBatches' prefetch thread) must run on ITS device: every entry point sets
     it.  With one GPU the thread case is exercised on device 0; with two, an engine on device 1 is driven from a thread whose
