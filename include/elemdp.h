@@ -193,7 +193,14 @@ int elemdp_scan(elemdp_handle* h, const double* x, int32_t n_param, elemdp_scan_
  * [whole call, sum passes + pair kernels, sequences handed to the log-space form]. */
 int elemdp_pair_posteriors(elemdp_handle* h, const double* x, int32_t n_param, double min_prob,
                            int64_t* n_pairs, double* unpaired);
-/* Copies the list of the last elemdp_pair_posteriors: seq (batch index), i, j (cell, j = i + d), p; any may be NULL.
+/* elemdp_pair_posteriors (the same list for elemdp_pair_list, the same unpaired and elemdp_last_timing) and, over the same P, the
+ * maximum expected accuracy structure of every sequence: with w(i, j) = 2 gamma P(i, j), the nested structure of
+ * kept pairs, spans <= max_span, that maximises the sum of w over its pairs plus the sum of unpaired over its unpaired bases.
+ * structure: NULL or seq_off indexing, L bytes '(' ')' '.' per sequence (no terminator); score: NULL or one value per sequence.
+ * gamma must be finite and > 0 (else ELEMDP_EINVAL); min_prob = +inf keeps no list. */
+int elemdp_pair_mea(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double gamma, int64_t* n_pairs,
+                    double* unpaired, char* structure, double* score);
+/* Copies the list of the last elemdp_pair_posteriors / elemdp_pair_mea: seq (batch index), i, j (cell, j = i + d), p; any may be NULL.
  * cap < n_pairs is ELEMDP_EINVAL; before any elemdp_pair_posteriors (of the resident batch) ELEMDP_ESTATE. */
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap);
 

@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -82,6 +82,7 @@ def load_library():
         L.elemdp_debug_tables.argtypes = [hp] + [dp] * 7
         L.elemdp_scan.argtypes = [hp, dp, C.c_int32, C.POINTER(ScanOut)]
         L.elemdp_pair_posteriors.argtypes = [hp, dp, C.c_int32, C.c_double, C.POINTER(C.c_int64), dp]
+        L.elemdp_pair_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int64), dp, C.c_char_p, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
         L.elemdp_last_timing.argtypes = [hp, dp, C.c_int32]
         L.elemdp_epoch_permutation.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
@@ -295,13 +296,33 @@ class Engine:
         unp = np.zeros(max(int(off[-1]), 1))
         m = C.c_int64()
         self._check(self._lib.elemdp_pair_posteriors(self._h, _dp(x), self.n_param, float(min_prob), C.byref(m), _dp(unp)))
-        n = m.value
+        return self._pair_lists(m.value, unp)
+
+    def _pair_lists(self, n, unp):
+        off = self._off
         seq, ii, jj = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
         p = np.zeros(max(n, 1))
         self._check(self._lib.elemdp_pair_list(self._h, _i32(seq), _i32(ii), _i32(jj), _dp(p), max(n, 1)))
         bounds = np.searchsorted(seq[:n], np.arange(self.n_seq + 1))
         return [(ii[a:b].copy(), jj[a:b].copy(), p[a:b].copy(), unp[int(off[k]):int(off[k + 1])].copy())
                 for k, (a, b) in enumerate(zip(bounds[:-1], bounds[1:]))]
+
+    # ---- maximum expected accuracy structures under the motif model
+    def mea_structures(self, x, gamma=1.0, min_prob=None):
+        """(structures, scores, pairs): per sequence the nested structure of kept pairs ('(', ')', '.') that maximises the sum of
+        2 gamma P over its pairs plus the sum of the unpaired probabilities over its unpaired bases, and that sum.  pairs: what
+        pair_posteriors(x, min_prob) gives, from the same call, or None when min_prob is None (then no list is built)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        unp = np.zeros(max(int(off[-1]), 1))
+        s = C.create_string_buffer(max(int(off[-1]), 1))
+        sc = np.zeros(max(self.n_seq, 1))
+        m = C.c_int64()
+        mp = float("inf") if min_prob is None else float(min_prob)
+        self._check(self._lib.elemdp_pair_mea(self._h, _dp(x), self.n_param, mp, float(gamma), C.byref(m), _dp(unp), s, _dp(sc)))
+        raw = s.raw.decode("ascii")
+        structs = [raw[int(off[k]):int(off[k + 1])] for k in range(self.n_seq)]
+        return structs, sc[:self.n_seq].copy(), None if min_prob is None else self._pair_lists(m.value, unp)
 
     def last_timing(self):
         """[ms whole evaluation, ms DP pipeline, sequences re-evaluated in log space]"""

@@ -5,6 +5,8 @@
     python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw
     python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-pairs pairs.txt
                                     # + base-pair posteriors under the motif model (--pair-min-prob, default 1e-3)
+    python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-mea mea.txt
+                                    # + maximum expected accuracy structures over those posteriors (--mea-gamma, default 1)
     python -m rnaelem_amd.cli       --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --out2 scan.raw
                                     # no sub-command = what script/elem spawns: train, write the model, scan (main.cpp:47-84)
     python -m rnaelem_amd.cli eval  --fastq pos.fq --motif-model model.txt --out1 fn.txt --out2 gr.txt     (motif_eval.hpp:23-54)
@@ -47,6 +49,11 @@ def build_parser():
     sub.choices["scan"].add_argument("--out-pairs", default=None,
                                      help="base-pair posteriors under the motif model: one record per sequence (io.pair_record)")
     sub.choices["scan"].add_argument("--pair-min-prob", type=float, default=1e-3, help="pairs below this probability are left out")
+    sub.choices["scan"].add_argument("--out-mea", default=None,
+                                     help="maximum expected accuracy structures under the motif model: one record per sequence "
+                                          "(io.mea_record)")
+    sub.choices["scan"].add_argument("--mea-gamma", type=float, default=1.0,
+                                     help="weight of the pairs: a pair scores 2 gamma P, an unpaired base its unpaired probability")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -212,7 +219,7 @@ def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
         sharded_write(recs, [out1, out_pairs], rank, world, scan_part, barrier)
 
 
-def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3):
+def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0):
     nodes = eng.describe()["node"]
     step = max(1, chunk)
 
@@ -221,15 +228,29 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             part = mine[c0:c0 + step]
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
-            if out_pairs is None:
+            if out_pairs is None and out_mea is None:
                 for (rid, codes, _), r in zip(part, res):
                     yield io.scan_record(rid, codes, r, nodes)
                 continue
-            prs = eng.pair_posteriors(m["x"], pair_min_prob)   # (the same loaded batch)
-            for (rid, codes, _), r, (ii, jj, pp, unp) in zip(part, res, prs):
-                yield io.scan_record(rid, codes, r, nodes), io.pair_record(rid, len(codes), (ii, jj, pp), unp)
+            # (the same loaded batch; with both files one device call gives the pairs and the structures)
+            if out_mea is None:
+                prs = eng.pair_posteriors(m["x"], pair_min_prob)
+            else:
+                structs, scores, prs = eng.mea_structures(m["x"], mea_gamma, pair_min_prob if out_pairs is not None else None)
+            for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
+                texts = [io.scan_record(rid, codes, r, nodes)]
+                if out_pairs is not None:
+                    ii, jj, pp, unp = prs[k]
+                    texts.append(io.pair_record(rid, len(codes), (ii, jj, pp), unp))
+                if out_mea is not None:
+                    texts.append(io.mea_record(rid, structs[k], scores[k]))
+                yield tuple(texts)
 
-    sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
+    if out_mea is None:
+        sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
+    else:
+        outs = [out1] + ([out_pairs] if out_pairs is not None else []) + [out_mea]
+        sharded_write(recs, outs, rank, world, scan_part, barrier)
 
 
 def cmd_scan(a):
@@ -242,7 +263,8 @@ def cmd_scan(a):
         barrier = dist.barrier
     m = io.read_model(a.motif_model)
     eng = io.engine_from_model(m, a.device if a.device is not None else local_rank)
-    _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob)
+    _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
+                  a.mea_gamma)
     if world > 1:
         dist.destroy_process_group()
 

@@ -242,7 +242,9 @@ class Engine {
   void train_finish(const double* reduced, double* fn, double* gr, double* sum_eff, int32_t* n_skipped);
   void scan(const double* x, int n_param, elemdp_scan_out* out);
   // base-pair posteriors of the batch under the motif model (pair_rules.h); the list stays on the device for pair_list
-  void pair_posteriors(const double* x, int n_param, double min_prob, int64_t* n_pairs, double* unpaired);
+  // mea (optional): also the maximum expected accuracy structures over the same P (mea_rules.h)
+  struct MeaOut { double gamma; char* structure; double* score; };
+  void pair_posteriors(const double* x, int n_param, double min_prob, int64_t* n_pairs, double* unpaired, const MeaOut* mea = nullptr);
   void pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap);
   int partial_len() const { return 4 + 2 * au_.n_theta() + 4; }
   void set_option(const std::string& key, double v);
@@ -378,12 +380,14 @@ class Engine {
   template <class Work> void stream_chunks(Work work);
   void stream_train(const double* x, int n_param, void* partial, bool device_ptr, bool reduce);
   void stream_scan(const double* x, int n_param, elemdp_scan_out* out);
-  void stream_pairs(const double* x, int n_param, double min_prob, double* unpaired);
+  void stream_pairs(const double* x, int n_param, double min_prob, double* unpaired, const MeaOut* mea);
   // pair posteriors: kept pairs per sequence and their prefix (staging ranges), pairs kept by min_prob and their prefix, the
   // P(i, d) scratch of the table slots, the staging list, the final list of the last call (n_pairs_ < 0: none)
   DevBuf d_pr_kept_, d_pr_koff_, d_pr_cnt_, d_pr_off_, d_pr_P_, d_pr_unp_, d_pr_si_, d_pr_sj_, d_pr_sp_;
   DevBuf d_pl_seq_, d_pl_i_, d_pl_j_, d_pl_p_;
   int64_t n_pairs_ = -1;
+  // MEA structures: the M table and choice scratch of the table slots (as d_pr_P_), the structures and the scores of the call
+  DevBuf d_mea_M_, d_mea_ch_, d_mea_s_, d_mea_sc_;
 
   Automaton au_;
   EnergyTables et_;
@@ -2000,13 +2004,15 @@ void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
 // reduction on the group's table slots right behind it (before the next group of the stream reuses them), the log-space form --
 // the fused scan kernel up to its first outside pass -- for the sequences that leave the double range and under pipeline 3, then
 // the batch list in (sequence, i, j) order: prefix over the per-sequence counts, scatter out of the staging ranges.
-void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, int64_t* n_pairs, double* unpaired) {
+void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, int64_t* n_pairs, double* unpaired,
+                             const MeaOut* mea) {
   require_device();
   DeviceGuard dg(device_);
   if (!n_pairs) throw ArgError("pair_posteriors: null n_pairs");
   if (!(min_prob >= 0.)) throw ArgError("pair_posteriors: min_prob must be >= 0");
+  if (mea && !(std::isfinite(mea->gamma) && mea->gamma > 0.)) throw ArgError("pair_mea: gamma must be finite and > 0");
   n_pairs_ = -1;
-  if (streaming_) { stream_pairs(x, n_param_in, min_prob, unpaired); *n_pairs = n_pairs_; return; }
+  if (streaming_) { stream_pairs(x, n_param_in, min_prob, unpaired, mea); *n_pairs = n_pairs_; return; }
   if (n_seq_ <= 0) throw StateError("pair_posteriors before load_batch");
   if (n_param_in != n_param()) throw ArgError("n_param mismatch");
   upload_params(x, lay_, false);
@@ -2036,6 +2042,25 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   pa.unpaired = d_pr_unp_.as<double>();
   pa.koff = d_pr_koff_.as<int64_t>(); pa.cnt = d_pr_cnt_.as<int64_t>();
   pa.st_i = d_pr_si_.as<int32_t>(); pa.st_j = d_pr_sj_.as<int32_t>(); pa.st_p = d_pr_sp_.as<double>();
+  // MEA: the M table and the choices of a slot next to its P(i, d); the chain's choices after the table's (L+1)(W+1)
+  const size_t mea_ch_stride = pcells + (size_t)Lmax_ + 1;
+  auto mea_scratch = [&](size_t slots) {
+    if (!mea) return;
+    d_mea_M_.alloc(8 * pcells * slots);
+    d_mea_ch_.alloc(4 * mea_ch_stride * slots);
+  };
+  auto launch_mea = [&](PairArgs pk, size_t slot0, int G, hipStream_t st) {
+    if (!mea) return;
+    pk.mea_M = d_mea_M_.as<double>() + slot0 * pcells;
+    pk.mea_ch = d_mea_ch_.as<int32_t>() + slot0 * mea_ch_stride;
+    HIP_OK(launch_pair_mea(pk, G, Wmax_, st));
+  };
+  if (mea) {
+    d_mea_s_.alloc(n_seqpos); d_mea_sc_.alloc(8 * (size_t)n);
+    pa.mea_gamma2 = 2. * mea->gamma;
+    pa.mea_ch_stride = mea_ch_stride;
+    pa.mea_s = d_mea_s_.as<char>(); pa.mea_score = d_mea_sc_.as<double>();
+  }
   int n_flagged = 0;
   const bool sums_on_batch = opt_pipeline_ == 4;
   if (sums_on_batch) {
@@ -2043,6 +2068,7 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
     LinArgs a;
     const int gsz = prepare_scan(a, pos);
     d_pr_P_.alloc(8 * pcells * (size_t)n_slots_);
+    mea_scratch((size_t)n_slots_);
     // the P plane's columns of the real states are 0 .. ncol-1: Automaton::flatten numbers a plane's columns in state order, and
     // a shadow state comes last
     int ncol = 0;
@@ -2066,6 +2092,7 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
       pk.P = d_pr_P_.as<double>() + slot0 * pcells;
       HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
       HIP_OK(launch_pair_seq(pk, G, st));
+      launch_mea(pk, slot0, G, st);
     });
     n_flagged = read_flagged();
     tables_linear_ = false;
@@ -2077,7 +2104,7 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
     int n_blocks;
     DpArgs d = log_scan_args(sums_on_batch, &n_blocks);
     const int chunk = std::min(n_log, sums_on_batch ? n_slots_ : std::max(n_blocks, 1024));
-    if (!sums_on_batch) d_pr_P_.alloc(8 * pcells * (size_t)chunk);
+    if (!sums_on_batch) { d_pr_P_.alloc(8 * pcells * (size_t)chunk); mea_scratch((size_t)chunk); }
     d.pair_p = d_pr_P_.as<double>();
     d.pair_stride = pcells;
     const int32_t* list = sums_on_batch ? d_flagged_.as<int32_t>() + 1 : d_order_.as<int32_t>();
@@ -2092,6 +2119,7 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
       pk.P = d_pr_P_.as<double>();
       pk.skip_flagged = 0;
       HIP_OK(launch_pair_seq(pk, C, st_));
+      launch_mea(pk, 0, C, st_);
     }
   }
   if (!sums_on_batch) n_slots_ = 0;   // (as after a scan: these slots are not reused by the train pipelines)
@@ -2114,18 +2142,23 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   last_ms[1] = ms_dp;
   last_ms[2] = (double)n_flagged;
   if (unpaired) HIP_OK(hipMemcpy(unpaired, d_pr_unp_.as<void>(), 8 * n_seqpos, hipMemcpyDeviceToHost));
+  if (mea && mea->structure) HIP_OK(hipMemcpy(mea->structure, d_mea_s_.as<void>(), n_seqpos, hipMemcpyDeviceToHost));
+  if (mea && mea->score) HIP_OK(hipMemcpy(mea->score, d_mea_sc_.as<void>(), 8 * (size_t)n, hipMemcpyDeviceToHost));
   n_pairs_ = total;
   *n_pairs = total;
 }
 
-void Engine::stream_pairs(const double* x, int n_param_in, double min_prob, double* unpaired) {
+void Engine::stream_pairs(const double* x, int n_param_in, double min_prob, double* unpaired, const MeaOut* mea) {
   if (n_param_in != n_param()) throw ArgError("n_param mismatch");
   std::vector<int32_t> hs, hi, hj;
   std::vector<double> hp;
   last_ms[0] = last_ms[1] = last_ms[2] = 0.;
   stream_chunks([&](int, int c0, int, Engine& e) {
     int64_t m = 0;
-    e.pair_posteriors(x, n_param_in, min_prob, &m, unpaired ? unpaired + (h_seq_off_[c0] - h_seq_off_[0]) : nullptr);
+    const int64_t at = h_seq_off_[c0] - h_seq_off_[0];   // (the chunk's first position)
+    MeaOut mc;
+    if (mea) mc = MeaOut{mea->gamma, mea->structure ? mea->structure + at : nullptr, mea->score ? mea->score + c0 : nullptr};
+    e.pair_posteriors(x, n_param_in, min_prob, &m, unpaired ? unpaired + at : nullptr, mea ? &mc : nullptr);
     const size_t b = hs.size();
     hs.resize(b + m); hi.resize(b + m); hj.resize(b + m); hp.resize(b + m);
     e.pair_list(hs.data() + b, hi.data() + b, hj.data() + b, hp.data() + b, m);
@@ -2392,6 +2425,14 @@ int elemdp_pair_posteriors(elemdp_handle* h, const double* x, int32_t n_param, d
   ELEMDP_TRY
   if (!h || !x || !n_pairs) throw elemdp::ArgError("elemdp_pair_posteriors: null argument");
   h->e->pair_posteriors(x, n_param, min_prob, n_pairs, unpaired);
+  ELEMDP_CATCH
+}
+int elemdp_pair_mea(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double gamma, int64_t* n_pairs,
+                    double* unpaired, char* structure, double* score) {
+  ELEMDP_TRY
+  if (!h || !x || !n_pairs) throw elemdp::ArgError("elemdp_pair_mea: null argument");
+  const elemdp::Engine::MeaOut mea{gamma, structure, score};
+  h->e->pair_posteriors(x, n_param, min_prob, n_pairs, unpaired, &mea);
   ELEMDP_CATCH
 }
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {

@@ -262,9 +262,16 @@ struct PairArgs {
   const int64_t* koff;            // per batch index: first staging entry (prefix of the kept pairs)
   int32_t* st_i; int32_t* st_j; double* st_p;   // staging list, (i, j) in row order per sequence
   int64_t* cnt;                   // per batch index: pairs with P >= min_prob
+  // launch_pair_mea (mea_rules.h): w = RN(mea_gamma2 * P), mea_gamma2 = 2 gamma; slot g owns mea_M + g * p_stride ([i][d], as P)
+  // and mea_ch + g * mea_ch_stride (the choices of M, then those of the exterior chain); the structure at seq_base, the score at n
+  double mea_gamma2;
+  double* mea_M; int32_t* mea_ch; size_t mea_ch_stride;
+  char* mea_s; double* mea_score;
 };
 hipError_t launch_pair_cells(const PairArgs& a, int G, int cells_max, hipStream_t st);   // k4_pairs
 hipError_t launch_pair_seq(const PairArgs& a, int G, hipStream_t st);
+// k_pair_mea, behind launch_pair_seq on the same slots and stream; Wmax >= the W of every sequence of the launch (LDS size)
+hipError_t launch_pair_mea(const PairArgs& a, int G, int Wmax, hipStream_t st);
 // kept pairs of every sequence of the batch (the staging capacity), off[0..n] = exclusive prefix of cnt[0..n) with off[n] the total,
 // and the scatter of the staging list into the final list ordered by (sequence, i, j)
 hipError_t launch_pair_kept(const SeqPlan* plans, const uint32_t* okbits, int n, int64_t* kept, hipStream_t st);

@@ -166,3 +166,19 @@ def read_pair_records(path):
         out.append((rid, unp, prs))
         k += 3 + n
     return out
+
+
+def mea_record(rid, structure, score):
+    """Record of one sequence in the `scan --out-mea` file: its id, the maximum expected accuracy structure under the motif model
+    ('(', ')', '.'; one character per base) and its score as %.17g."""
+    return "id: %s\nmea: %s\nscore: %.17g\n" % (rid, structure, float(score))
+
+
+def read_mea_records(path):
+    """-> list of (id, structure, score) from a `scan --out-mea` file."""
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+    while k + 2 < len(lines) and lines[k].startswith("id: "):
+        out.append((lines[k][4:], lines[k + 1][len("mea: "):], float(lines[k + 2][len("score: "):])))
+        k += 3
+    return out
