@@ -1448,7 +1448,19 @@ static int train_seq_impl(Model& m, const vector<int>& seq, const vector<int>& q
   res->bpp_eff = m.no_rss() ? 0. : q.bpp_eff; res->f = 0; res->skipped = 0;
   if (inside_o) std::copy(d.in_o.begin(), d.in_o.end(), inside_o);
   if (inside) std::copy(d.in_.begin(), d.in_.end(), inside);
-  if (!(std::isfinite(Zo) && std::isfinite(Za))) { res->skipped = 1; return 0; }
+  if (!(std::isfinite(Zo) && std::isfinite(Za))) {
+    res->skipped = 1;
+    if (outside && std::isfinite(Zo)) {
+      /* (not the reference's schedule: the first outside pass of a sequence the trainer skips, for the pair posteriors of the
+         scan's first pass, which it runs whenever Z(ari, nasi) is finite; the counts of this pass are discarded) */
+      VV en; V eh{0., 0.};
+      m.clear_counts(en);
+      TrainOut fo{d, Zo, eh, en};
+      run_outside(d, fo);
+      std::copy(d.out_.begin(), d.out_.end(), outside);
+    }
+    return 0;
+  }
   if (m.lik_ratio() && NINF < q.ws.back()) {
     /* --lik-ratio, sequence without motif (motif_trainer.hpp:163-171): the roles are swapped,
        "x" = Z(ari,nasi) with the full terminals, "o" = Z(ari only) */

@@ -16,9 +16,13 @@
 
 namespace elemdp {
 
-// a pair candidate: (w(i, e) + M(i+1, e-2)) + rest, rest = M(i+e, d-e) or F(i+e)
+// a pair candidate: (w(i, e) + M(i+1, e-2)) + rest, rest = M(i+e, d-e) or F(i+e).  HIP's __dmul_rn is a plain product, which
+// the default -ffp-contract=fast fuses with the sum behind it (one rounding instead of two, visible whenever 2 gamma P is not
+// exact, e.g. gamma = 1e3): contraction is off here, so that w is rounded before any sum.
 ELEMDP_HD double mea_pair(double gamma2, double p, double inner, double rest) {
-  return (ELEMDP_MUL_RN(gamma2, p) + inner) + rest;
+#pragma clang fp contract(off)
+  const double w = gamma2 * p;
+  return (w + inner) + rest;
 }
 
 // the first strictly greatest of two partial maxima of one candidate list, e = their first candidates (0 = none)

@@ -94,3 +94,24 @@ def test_mea_symbol_is_declared_and_exported():
     declared = set(re.findall(r"\b(elemdp_[a-z_0-9]+)\s*\(", open(HEADER).read()))
     assert "elemdp_pair_mea" in declared and "elemdp_pair_mea" in api.SYMBOLS
     assert hasattr(api.load_library(), "elemdp_pair_mea")
+
+
+def test_pair_weight_is_rounded_before_the_sum():
+    """mea_rules.h: a pair candidate is (RN(2 gamma P) + inner) + rest, two roundings where a fused multiply-add would make one.
+    At gamma = 1e3 the two differ for most P (at gamma = 0.5, 1, 4 the product is exact and they cannot): the bit-for-bit GPU
+    checks at gamma = 1e3 tell a contracted kernel from the rule.  The mirror's score of one pair follows the rule."""
+    from fractions import Fraction
+    rng = np.random.default_rng(7)
+    p, inner = rng.random(200), rng.random(200) * 50.0
+    for gamma, differ in ((1e3, True), (0.5, False), (1.0, False), (4.0, False)):
+        g2 = 2.0 * gamma
+        n = sum((g2 * a + b) != float(Fraction(g2) * Fraction(a) + Fraction(b)) for a, b in zip(p, inner))   # (exact, rounded once)
+        assert (n > 20) if differ else (n == 0), (gamma, n)
+    L, gamma, pv = 5, 1e3, 0.123456789
+    P = np.zeros((L + 1, L + 1))
+    kept = np.zeros((L + 1, L + 1), dtype=bool)
+    P[0, 5], kept[0, 5] = pv, True
+    q = np.full(L, 0.1)
+    s, sc = mea_fold(P, kept, q, gamma)
+    assert s == "(...)"
+    assert sc == ((2.0 * gamma) * pv + ((0.1 + 0.1) + 0.1)) + 0.0

@@ -7,7 +7,8 @@ import pytest
 from oracle import pyoracle as po
 from rnaelem_amd import api, cli, io, synth
 from tests.mea_mirror import expected_accuracy, mea_fold, pair_matrix, pairs_of
-from tests.test_pair_posterior_gpu import PATTERNS, perturbed, ragged_batch, same, same_scan_text, unpaired_of
+from tests.pair_check import check_against_mirror, oracle_pairs, unpaired_of
+from tests.test_pair_posterior_gpu import PATTERNS, perturbed, ragged_batch, same, same_scan_text
 from tests.util import gpath
 
 pytestmark = pytest.mark.gpu
@@ -16,40 +17,11 @@ PAR = "~T2004~"
 GAMMAS = (0.5, 1.0, 4.0)
 
 
-def oracle_pairs(o, seq, qual):
-    """P[i, d] = sum_s exp(inside + outside - Z) over plane P of the train schedule's first (full-terminal) pass, or None for a
-    sequence the train schedule skips (a Z that is not finite: it runs no outside pass)"""
-    t = o.train_seq(seq, qual, tables=True)
-    if t["skipped"]:
-        return None
-    Zo = t["Zo"]
-    with np.errstate(invalid="ignore"):
-        P = np.exp(t["inside"][:, :, 0, :] + t["outside"][:, :, 0, :] - Zo).sum(axis=2)
-    return np.nan_to_num(P, nan=0.0)
-
-
 def engine(pattern="((.*.))", **opts):
     eng = api.Engine(pattern, PAR, 50, 30, 1e-4, 0.1, 0, 0)
     for k, v in opts.items():
         eng.set_option(k, v)
     return eng
-
-
-def check_against_mirror(eng, seqs, x, gammas=GAMMAS):
-    """every structure and score equal to the mirror's over the same call's P (min_prob 0: every kept cell) and unpaired"""
-    out = {}
-    for gamma in gammas:
-        structs, scores, prs = eng.mea_structures(x, gamma, 0.0)
-        assert len(structs) == len(seqs) == len(scores) == len(prs)
-        for k, seq in enumerate(seqs):
-            L, W = len(seq), min(len(seq), eng.max_span)
-            ii, jj, pp, unp = prs[k]
-            P, kept = pair_matrix(L, W, ii, jj, pp)
-            s, sc = mea_fold(P, kept, unp, gamma)
-            assert structs[k] == s, (gamma, k)
-            assert scores[k] == sc, (gamma, k, scores[k], sc)
-        out[gamma] = structs, scores, prs
-    return out
 
 
 @pytest.mark.parametrize("pattern", PATTERNS)

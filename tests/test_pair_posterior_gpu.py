@@ -8,6 +8,7 @@ import pytest
 
 from oracle import pyoracle as po
 from rnaelem_amd import api, cli, io, synth
+from tests.pair_check import check_against_oracle
 from tests.util import gpath
 
 pytestmark = pytest.mark.gpu
@@ -33,57 +34,6 @@ def perturbed(eng, lam=0.7):
     x[:-2] += np.linspace(-0.3, 0.3, len(x) - 2)
     x[-1] += 0.2
     return x
-
-
-def oracle_pairs(o, seq, qual):
-    """P[i, d] = sum_s exp(inside + outside - Z) over plane P of the train schedule's first (full-terminal) pass, or None for a
-    sequence the train schedule skips (a Z that is not finite, motif_trainer.hpp:211-215: it runs no outside pass)"""
-    t = o.train_seq(seq, qual, tables=True)
-    if t["skipped"]:
-        return None
-    Zo = t["Zo"]
-    assert Zo == pytest.approx(o.scan_seq(seq, qual)["ZL"], rel=1e-12)
-    with np.errstate(invalid="ignore"):
-        P = np.exp(t["inside"][:, :, 0, :] + t["outside"][:, :, 0, :] - Zo).sum(axis=2)
-    return np.nan_to_num(P, nan=0.0)
-
-
-def unpaired_of(P, L):
-    u = np.ones(L)
-    W = P.shape[1] - 1
-    for i in range(L + 1):
-        for d in range(1, W + 1):
-            if i + d <= L and P[i, d] != 0.0:
-                u[i] -= P[i, d]
-                u[i + d - 1] -= P[i, d]
-    return u
-
-
-def check_against_oracle(eng, o, seqs, quals, x):
-    res = eng.pair_posteriors(x, 0.0)
-    assert len(res) == len(seqs)
-    n_checked = 0
-    for k, (seq, qual) in enumerate(zip(seqs, quals)):
-        L = len(seq)
-        ii, jj, pp, unp = res[k]
-        kept, _ = eng.pairs(k)
-        d = jj - ii
-        # the list holds exactly the kept pairs, in (i, j) order
-        ki, kd = np.nonzero(kept)
-        sel = (kd >= 1) & (ki + kd <= L)
-        assert list(zip(ii, d)) == list(zip(ki[sel], kd[sel])), k
-        P = oracle_pairs(o, seq, qual)
-        if P is None:
-            continue
-        n_checked += 1
-        ref = P[ii, d]
-        np.testing.assert_allclose(pp, ref, rtol=1e-8, atol=1e-12, err_msg="sequence %d" % k)
-        mask = np.zeros_like(P, dtype=bool)
-        mask[ii, d] = True
-        assert np.all(P[~mask] == 0.0), k          # nothing outside the filter's pairs
-        np.testing.assert_allclose(unp, unpaired_of(P, L), rtol=1e-8, atol=1e-10, err_msg="unpaired %d" % k)
-    assert n_checked >= min(3, len(seqs))
-    return res
 
 
 @pytest.mark.parametrize("pattern", PATTERNS)
