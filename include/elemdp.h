@@ -88,7 +88,6 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *     "schedule"        1 (default): ONE outside sweep for both passes of motif_trainer.hpp:209-225 -- "has motif" terminals on
  *                       the pattern's states, "no motif" terminal on a shadow copy of state (0,0); 0: the reference's two sweeps
  *     "fast"            1 (default): table-driven band kernels (per-state programs, weight tables, cell records); 0: generic rule code
- *     "nblk"            blocks of cells a band-kernel workgroup owns: 0 (default) = chosen per launch, n = n wherever they fit
  *     "deterministic"   1: bit-identical repeats of elemdp_train_eval (fixed summation order, as the reference at --thread 1); slower
  *     "eval_first", "eval_count"   a train evaluation covers the records [first, first + count) of the resident batch only
  *                       (count 0 = all; reset by elemdp_load_batch).  Refused (ELEMDP_EINVAL) for a streamed batch and for pipeline 3
@@ -103,8 +102,6 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *                       "slots": table slots; "two_streams": retired with pipeline 2, accepted and ignored
  *     "keep_lnbpp"      keep ln BPP of the filter for elemdp_batch_pairs; "bpp_log": 1 = log-space BPP filter for every band
  *     "sorted_plan"     1: role lists of the plan sorted per cell (reproducible summation order of the log-space pipeline)
- *     "row_pad"         padding of the compact table rows in doubles (default 1 = none; 8 = rows start on 64-byte lines)
- *     "cell_major"      1 = the seven rows of a cell side by side in one record instead of plane after plane (default 0)
  *   measurement / tests
  *     "profile"         in-kernel phase clocks for elemdp_debug_profile; "dbg": switch phases off (results invalid);
  *     "poison"          1: every table is filled with NaN before an evaluation (an unmasked read of an entry nobody stored shows) */

@@ -26,7 +26,7 @@ def needs_build():
 
 
 # per-file flags.  lin_kernels.hip: machine LICM hoists the constants of exp() (two dozen vector registers) out of the inner loops
-# of the band kernels to the top of their block loop, where they stay live across every phase -- a workgroup per CU of k4_out.
+# of the band kernels to the top of the kernel, where they stay live across every phase -- a workgroup per CU of k4_out.
 EXTRA = {"lin_kernels.hip": ["-mllvm", "-disable-machine-licm"]}
 OBJ_DIR = os.path.join(HERE, "_build")
 

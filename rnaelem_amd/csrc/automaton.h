@@ -56,12 +56,11 @@ class Automaton {
   // shadow: append a copy of state 0 = (0,0) as state S, closed under the same transitions but isolated from every other
   // state (requires that state 0 is closed, Engine::linear_ok_).  One outside sweep with the "has motif" terminals on the
   // states of the pattern and the "no motif" terminal on the shadow then yields both outside passes of the train schedule.
-  // row_pad: the rows of the compact tables of the scaled-linear pipeline (AutomatonLayout::tab_*) are padded to a multiple of
-  // row_pad doubles (8 = every row starts on a 64-byte line; 1, the default since round 4 = no padding: 70 instead of 104 doubles
-  // per cell for ((.*.)), and 4.7 % off the train evaluation -- the memory system is bound by requests).  cell_major: the seven rows of a cell lie side by side (one record of
-  // tab_row doubles per cell, padded to a multiple of 8) instead of one plane after the other (AutomatonLayout::tab_cell).
+  // The compact tables of the scaled-linear pipeline (AutomatonLayout::tab_*) lie plane after plane, their rows unpadded (70
+  // doubles per cell for ((.*.)) instead of 104 on 64-byte lines: 4.7 % off the train evaluation -- the memory system is bound
+  // by requests).
   void flatten(AutomatonLayout* lay, std::vector<int32_t>* ints, bool only_state0 = false, bool prune = false,
-               bool shadow = false, int row_pad = 1, bool cell_major = false) const;
+               bool shadow = false) const;
 
   // Static liveness of the (structural state, interval state) pairs, from the rule table alone in the
   // boolean semiring: inside_live[e][s] = some sequence gives inside(., ., e, s) a non-zero weight; useful[e][s] = inside-live

@@ -75,13 +75,11 @@ struct AutomatonLayout {
   // one column per interval state that is USEFUL in that plane (Automaton::liveness; every state without pruning):
   // ints[tab_cmap + e * S + s] = column of state s in plane e, or -1 (the entry is 0 in every complete parse and is neither
   // stored nor read).  tab_cs[e] = sum of the strides of the planes before e, tab_row = sum of all seven; the plane of a
-  // sequence starts at tab_cs[e] * (W+1) * (L+1).  Strides are padded (multiples of 8 doubles) so that rows start on 64-byte
-  // lines.  ap_rs: row stride of the pair tables of the factorised rule 2 (>= n_ap).
+  // sequence starts at tab_cs[e] * (W+1) * (L+1), entry = tab_cs[e] * cells + cell * tab_rs[e] + column (TableView::set_compact).
+  // Strides are not padded: tab_rs[e] = the plane's columns (at least 1; B as wide as P).  ap_rs: row stride of the pair tables
+  // of the factorised rule 2 (= n_ap, at least 1).
   int32_t tab_cmap;
   int32_t tab_rs[7], tab_cs[7], tab_row;
-  // tab_cell: the seven rows of a cell lie side by side in one record of tab_row doubles (entry = cell * tab_row + tab_cs[e] + column)
-  // instead of plane after plane (entry = tab_cs[e] * cells + cell * tab_rs[e] + column): TableView::set_compact
-  int32_t tab_cell;
   int32_t ap_rs;
   // ---- Table-driven train kernels (lin_fast.h, k4_in / k4_out with FAST).  They stage only their own FAST BLOB -- ints
   // [fb_in, fb_in + fb_in_n) resp. [fb_out, fb_out + fb_out_n) behind n_ints -- instead of the generic lists:

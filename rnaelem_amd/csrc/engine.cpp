@@ -316,8 +316,6 @@ class Engine {
   void lin_weights(int first = 0, int count = 0);
   void upload_automaton();
   bool opt_prune_ = true;   // transition lists pruned to the transitions of complete parses (Automaton::flatten)
-  int opt_row_pad_ = 1;     // rows of the compact tables padded to a multiple of this many doubles (8 = 64-byte lines; 1 = none)
-  bool opt_cell_major_ = false;   // compact tables cell by cell (the seven rows of a cell side by side) instead of plane by plane
   // a train evaluation covers the records [eval_first, eval_first + eval_count) of the resident batch only (count 0: all): the
   // mini-batch trainer loads the records + negatives of several coming evaluations as ONE batch -- the filter and the plan do not
   // depend on x, and a load of 128 sequences costs as much as one of 1024 (launch-bound) -- and evaluates them range by range
@@ -327,7 +325,6 @@ class Engine {
   int range_key_[2] = {-1, -1};
   bool opt_det_ = false;    // deterministic reductions of the scaled-linear train evaluation (LinArgs::det): bit-identical repeats
   bool opt_fast_ = true;    // table-driven unary phases of the train kernels (lin_fast.h); 0 = the generic rule code
-  int opt_nblk_ = 0;        // blocks of cells per band-kernel workgroup (LinArgs::nblk): 0 = chosen per launch, n = n wherever they fit
   bool opt_poison_ = false; // tests: the table slots are filled with NaN before every evaluation of the scaled-linear pipeline, so
                             // that a read of an entry nobody stored shows up in the results (the compact tables hold garbage there)
   void require_device() const;
@@ -520,9 +517,9 @@ Engine::Engine(const elemdp_model_desc& d)
 // the flat transition lists of the pattern automaton (pruned to the transitions that can occur in a complete parse unless
 // option "prune" = 0) and of its restriction to state (0,0)
 void Engine::flatten_automaton() {
-  au_.flatten(&lay_, &ints_, false, opt_prune_, false, opt_row_pad_, opt_cell_major_);
-  au_.flatten(&layr_, &intsr_, true, opt_prune_, false, opt_row_pad_, opt_cell_major_);
-  if (linear_ok_ && au_.S() < 127) au_.flatten(&lays_, &intss_, false, opt_prune_, true, opt_row_pad_, opt_cell_major_);
+  au_.flatten(&lay_, &ints_, false, opt_prune_, false);
+  au_.flatten(&layr_, &intsr_, true, opt_prune_, false);
+  if (linear_ok_ && au_.S() < 127) au_.flatten(&lays_, &intss_, false, opt_prune_, true);
   else { lays_ = lay_; lays_.shadow = -1; intss_ = ints_; }
   lin_slots_ = 0;   // (the pair tables of the linear pipeline are sized by the automaton's pair list)
 }
@@ -638,15 +635,12 @@ void Engine::set_option(const std::string& key, double v) {
   else if (key == "bpp_log") opt_bpp_log_ = v != 0;
   else if (key == "poison") opt_poison_ = v != 0;
   else if (key == "fast") opt_fast_ = v != 0;
-  else if (key == "nblk") opt_nblk_ = std::max(0, std::min(64, (int)v));
   else if (key == "deterministic") opt_det_ = v != 0;
   else if (key == "sorted_plan") opt_sorted_plan_ = v != 0;
   else if (key == "eval_first") opt_eval_first_ = (int)v;
   else if (key == "eval_count") opt_eval_count_ = (int)v;
-  else if (key == "prune" || key == "row_pad" || key == "cell_major") {
-    if (key == "prune") opt_prune_ = v != 0;
-    else if (key == "cell_major") opt_cell_major_ = v != 0;
-    else opt_row_pad_ = std::max(1, (int)v);
+  else if (key == "prune") {
+    opt_prune_ = v != 0;
     n_slots_ = 0;
     flatten_automaton();
     if (has_device_) { DeviceGuard dg(device_); HIP_OK(hipStreamSynchronize(st_)); upload_automaton(); }
@@ -1481,7 +1475,6 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int
   // (table-driven unary phases: not under FIX_RSS, whose fixed pairs need not be canonical -- the weight tables are indexed
   // by the pair type)
   a.fast = (opt_fast_ && !(flags_ & ELEMDP_DBG_FIX_RSS)) ? 1 : 0;
-  a.nblk = opt_nblk_;
   a.no_prf = (flags_ & ELEMDP_NO_PROFILE) ? 1 : 0;
   a.m_min = m_min();
   a.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
@@ -1791,7 +1784,6 @@ void Engine::debug_tables(double* inside, double* outside, double* inside_o, dou
     if (!lin) return t[(((size_t)e * (W + 1) + d) * (L + 1) + i) * S + s2];
     const int c = TI[TL.tab_cmap + e * S + s2];
     if (c < 0 || !cell_live(e, d, i)) return 0.;
-    if (TL.tab_cell) return t[((size_t)d * (L + 1) + i) * TL.tab_row + TL.tab_cs[e] + c];
     return t[(size_t)TL.tab_cs[e] * cells + ((size_t)d * (L + 1) + i) * TL.tab_rs[e] + c];
   };
   auto reorder = [&](const std::vector<double>& t, const std::vector<double>* plus2, double* dst, bool outside_tab) {  // -> [i][d][e][s]
@@ -2078,7 +2070,7 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
       if (c != ncol) throw std::logic_error("pair_posteriors: the P plane's columns are not in state order");
       ++ncol;
     }
-    pa.tab_cell = a.lay.tab_cell; pa.p_cs = a.lay.tab_cs[ST_P]; pa.p_rs = a.lay.tab_cell ? a.lay.tab_row : a.lay.tab_rs[ST_P];
+    pa.p_cs = a.lay.tab_cs[ST_P]; pa.p_rs = a.lay.tab_rs[ST_P];
     pa.ncol = ncol;
     pa.band_stride = a.band_stride;
     pa.skip_flagged = 1;

@@ -175,10 +175,8 @@ struct LinArgs {
   double* seq_out; int32_t out_stride;
   int32_t schedule, pass, d;
   int32_t cpb;                    // cells of one block = lanes of a workgroup / lanes per cell of the unary phase
-  float rcp_nap, rcp_lane, rcp_cpb, rcp_3cpb;   // 1 / n_ap, 1 / lanes per cell, 1 / cpb, 1 / (3 cpb) for the lane -> (cell, item) splits of the band
+  float rcp_nap, rcp_lane, rcp_cpb;   // 1 / n_ap, 1 / lanes per cell, 1 / cpb for the lane -> (cell, item) splits of the band
                                   // kernels (div_rcp: a reciprocal formed per lane costs ten instructions and a register for the whole kernel)
-  int32_t nblk;                   // blocks of cpb consecutive cells a band-kernel workgroup owns (k4_in / k4_out): the context of all
-                                  // of them is staged once, the phases then run block by block (set per launch; 0 means 1)
   int32_t* flagged;               // [0] = number of flagged sequences, [1..] = their batch indices
   // scan (sum passes K4 / K5 on this pipeline): start constraint and position-posterior accumulators (batch offsets)
   int32_t lik_ratio;              // --lik-ratio objective (ELEMDP_LIK_RATIO)
@@ -249,9 +247,9 @@ struct PairArgs {
   const int32_t* idx;             // idx[g] = batch index of the sequence in slot g
   const uint32_t* okbits;         // pair mask after the filter (bits_base indexing)
   // launch_pair_cells: the compact tables of the group's slots, P plane (AutomatonLayout::tab_*): rows start at
-  // p_base + (d * (L+1) + i) * p_rs with p_base = tab_cs[P] (cell-major) or tab_cs[P] * cells; the real states' columns are 0 .. ncol-1
+  // tab_cs[P] * cells + (d * (L+1) + i) * p_rs; the real states' columns are 0 .. ncol-1
   const double* band_in; const double* band_out; size_t band_stride;
-  int32_t tab_cell, p_cs, p_rs, ncol;
+  int32_t p_cs, p_rs, ncol;
   const double* zs;               // per slot: Z(ari, nasi) mantissa at zs[4 g]
   const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
   int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)

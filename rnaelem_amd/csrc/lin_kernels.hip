@@ -3,12 +3,12 @@
 // Same diagonal-synchronous batch pipeline as train_kernels.hip (a group of G sequences swept in
 // lockstep, kernel boundaries = dependencies), but a term of the O(L W^2) rules is one FMA on two
 // table loads instead of an exp.  The band kernels are bound by instruction issue and by the dependent round trips of a
-// workgroup (HBM traffic is at 1.3 x the algorithmic bytes and 40 % of the peak), hence table-driven phases,
-// several blocks of cells per workgroup and as many resident workgroups as registers and LDS allow:
+// workgroup (HBM traffic is at 1.3 x the algorithmic bytes and 40 % of the peak), hence table-driven phases
+// and as many resident workgroups as registers and LDS allow:
 //   k4_weights   once per evaluation: exp(lambda_k * structural term) of every cell (the loop items' terms are
 //                exponentiated where their records are staged)
-//   k4_in(d)     ONE launch per diagonal: workgroup = nblk blocks of cpb = 256/lanes-per-cell consecutive cells of one sequence;
-//                set-up once (context of all its cells staged in LDS), then per block: pair phase (rule 2 factorised: lane = (cell, pair)), item sums (rule 6c: lane =
+//   k4_in(d)     ONE launch per diagonal: workgroup = cpb = 256/lanes-per-cell consecutive cells of one sequence;
+//                context of its cells staged in LDS, then pair phase (rule 2 factorised: lane = (cell, pair)), item sums (rule 6c: lane =
 //                (record, tuple), records staged in LDS), then one lane per (cell, state) finishes P,E,M,B,1,2,L -- the heavy
 //                sums never touch HBM
 //   k4_in_ext    exterior chain, partition functions, objective, range check (flags the sequence)
@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #ifndef ELEMDP_KCI
 #define ELEMDP_KCI 2
@@ -119,8 +120,8 @@ struct LinSink {
 // phase timer (option "profile"): thread 0 of a workgroup sums the shader clocks between marks per slot and adds
 // them to one of 64 copies of the counter row when the workgroup ends (host adds the copies)
 struct PhaseClock {
-  // (the sums go straight to the counter row: accumulators in registers -- thirteen 64-bit values -- would stay live around the
-  // whole block loop of a band kernel, profiled or not; the last clock is read by every lane, outside divergent control flow,
+  // (the sums go straight to the counter row: accumulators in registers -- thirteen 64-bit values -- would stay live across
+  // every phase of a band kernel, profiled or not; the last clock is read by every lane, outside divergent control flow,
   // and so stays in scalar registers)
   long long* row;
   long long t0;
@@ -685,9 +686,7 @@ __device__ __forceinline__ void outer_stage(const LViews& v, const OuterRecs& r,
 }
 
 // FAST: table-driven phases (lin_fast.h; train schedule, the fast blob staged); FP: longest pair list of a state (2 or 3)
-// MB: the workgroup owns several blocks of cells (LinArgs::nblk > 1) -- a loop around the phases that costs registers (values that
-// are the same in every block stay live around it), so the one-block form is a kernel of its own: small groups and the scan
-template <bool BIG, bool CON, bool FAST = false, int FP = kFastP, bool W8 = false, bool MB = false>
+template <bool BIG, bool CON, bool FAST = false, int FP = kFastP, bool W8 = false>
 __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4_in(LinArgs a) {
   extern __shared__ double lds[];
   // (the automaton layout is read from the kernel arguments: constant offsets, scalar registers)
@@ -700,21 +699,17 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
   make_lviews(a, by, v);
   const AutomatonLayout& A = a.lay;
   const int S = a.lay.S, NA = a.lay.n_active, d = a.d, cpb = a.cpb, tid = threadIdx.x;
-  // The workgroup owns nblk blocks of cpb consecutive cells of the diagonal (cpbT cells from i0T on): everything that does not
-  // depend on the block -- plan record, automaton blob, parameters and weight tables, the window of positions, the cell records
-  // and CSR ranges of all its cells -- is fetched and staged ONCE; the phases then run block by block on the per-block heavy
-  // sums.  (One block per workgroup paid the launch, two dependent round trips and the staging for 12 cells of work.)
-  const int nblk = (MB && a.nblk > 1) ? a.nblk : 1, cpbT = cpb * nblk;
+  // The workgroup owns cpb consecutive cells of the diagonal (nc cells from i0 on)
   if (d > v.q.W) return;
-  const int ncell = v.q.L - d + 1, i0T = bx * cpbT;
-  if (i0T >= ncell) return;
-  const int ncT = (cpbT < ncell - i0T) ? cpbT : ncell - i0T;
+  const int ncell = v.q.L - d + 1, i0 = bx * cpb;
+  if (i0 >= ncell) return;
+  const int nc = (cpb < ncell - i0) ? cpb : ncell - i0;
   if (CON) {
     // The start constraint touches the emissions of position Ys only: a cell whose span does not cover Ys -- and everything below
     // it -- has the value of the unconstrained pass, which is still in the table (same slot, same layout; the scan runs
     // k4_in<false> first).  Only the cells i <= Ys < i + d are swept again: ~d of the L - d + 1 cells of the diagonal.
     const int ys = a.ys[v.n];
-    if (ys < i0T || ys - d + 1 > i0T + ncT - 1) return;
+    if (ys < i0 || ys - d + 1 > i0 + nc - 1) return;
   }
   const int HD = FAST ? A.n_lane : S;   // stride of the heavy sums per cell: the live states (table-driven: their index among them), or all
   const int CS = cpb * HD;
@@ -724,7 +719,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
   double* hbA = hb;
   double* heA = he;
   double* st1 = lds + NW * 2 * CS;           // item records (kRecIn doubles)
-  const BlockLds BL = block_lds(NW * 2 * CS + kRecIn, cpbT, a.n_lin, cpbT + a.wmax + 3, FAST ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, FAST ? kCellInD : 0);
+  const BlockLds BL = block_lds(NW * 2 * CS + kRecIn, cpb, a.n_lin, cpb + a.wmax + 3, FAST ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, FAST ? kCellInD : 0);
   // cell records of the table-driven unary phase: the exponentiated structural terms of the cells are fetched with the context
   // (lane = (cell, value); the addresses depend on the plan record only), the flags follow once the context is in LDS
   constexpr int kCRin = (ELEMDP_CPB_MAX * 8 + kBT - 1) / kBT;
@@ -733,18 +728,18 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
 #pragma unroll
     for (int r = 0; r < kCRin; ++r) {
       crx[r] = 0.;
-      if (r * kBT < cpbT * 8) {   // (uniform: most automata need the first round only)
-        const int t = tid + r * kBT, c = (t >> 3) < ncT ? (t >> 3) : 0;
-        crx[r] = cell_in_fetch(v.q, d, i0T + c, t & 7);
+      if (r * kBT < cpb * 8) {   // (uniform: most automata need the first round only)
+        const int t = tid + r * kBT, c = (t >> 3) < nc ? (t >> 3) : 0;
+        crx[r] = cell_in_fetch(v.q, d, i0 + c, t & 7);
       }
     }
   }
-  if (a.dbg & 1024) { if (ncT == 12345) lds[tid] = crx[0]; return; }   // (timing experiments: the workgroup up to its plan record ...
-  const BlockCtx cx = stage_context<BIG, 0, FAST>(a, v, reinterpret_cast<unsigned char*>(lds), BL, i0T, ncT, d, cpbT);
-  int* dmT = cx.dm; int* cntsT = cx.cnts; int* pre = cx.pre; int* baseT = cx.base;
+  if (a.dbg & 1024) { if (nc == 12345) lds[tid] = crx[0]; return; }   // (timing experiments: the workgroup up to its plan record ...
+  const BlockCtx cx = stage_context<BIG, 0, FAST>(a, v, reinterpret_cast<unsigned char*>(lds), BL, i0, nc, d, cpb);
+  int* dm = cx.dm; int* cnts = cx.cnts; int* pre = cx.pre; int* base = cx.base;
   const int32_t* G = v.m.big;
-  double* crecT = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(lds) + BL.crec);
-  int* crflT = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(lds) + BL.crfl);
+  double* crec = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(lds) + BL.crec);
+  int* crfl = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(lds) + BL.crfl);
   for (int t = tid; t < NW * 2 * CS; t += kBT) lds[t] = 0.;
   __syncthreads();
   if (a.dbg & 2048) return;                                             //  ... and up to its staged context)
@@ -753,41 +748,25 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
 #pragma unroll
     for (int r = 0; r < kCRin; ++r) {
       const int t = tid + r * kBT, c = t >> 3, k = t & 7;
-      if (c < ncT) {
-        const bool on = k < 4 ? v.q.pair_ok(i0T + c, d) : v.q.e_ok(i0T + c, d);
-        crecT[c * kCellInD + 2 + k] = on ? crx[r] : 0.;
+      if (c < nc) {
+        const bool on = k < 4 ? v.q.pair_ok(i0 + c, d) : v.q.e_ok(i0 + c, d);
+        crec[c * kCellInD + 2 + k] = on ? crx[r] : 0.;
       }
     }
-    for (int c = tid; c < ncT; c += kBT) {
-      const int i = i0T + c, j = i + d;
+    for (int c = tid; c < nc; c += kBT) {
+      const int i = i0 + c, j = i + d;
       int fl = cell_in_flags(v.m, v.q, d, i);
       if (CON) { const int ys = a.ys[v.n]; fl |= (i == ys ? CF_YL : 0) | (j - 1 == ys ? CF_YR : 0); }
-      crflT[c] = fl;
-      crecT[c * kCellInD] = v.q.ews[i];
-      crecT[c * kCellInD + 1] = v.q.ews[j > 0 ? j - 1 : 0];
+      crfl[c] = fl;
+      crec[c * kCellInD] = v.q.ews[i];
+      crec[c * kCellInD + 1] = v.q.ews[j > 0 ? j - 1 : 0];
     }
   }
   const double* B = v.in.band;
   const int nq = ((a.dbg & 2) || (ELEMDP_KO & 2)) ? 0 : A.n_quad;
   // CSR ranges of the item sums of all cells of the workgroup (consumed behind the first pair phase, whose loads they travel with)
-  outer_ranges_load(v, i0T, ncT, d, nq > 0, tid, cntsT, baseT);
+  outer_ranges_load(v, i0, nc, d, nq > 0, tid, cnts, base);
   const RecAhead ahead{LoopItem{0., 0, 0, 0, 0}, 0, false};   // (records fetched ahead of the pair phase: two barriers more than the round trip saved, measured)
-  const int tid_wg = tid;
-  for (int blk = 0; MB ? blk * cpb < ncT : blk < 1; ++blk) {
-  // (the lane id behind an empty asm: what a lane derives from it -- its cell, pair record, program, tuple records -- is the same in
-  // every block, and the compiler would keep all of it in registers across the whole loop: 98 instead of 65 VGPRs)
-  int tid = tid_wg;
-  if (MB) asm volatile("" : "+v"(tid));
-  const int i0 = i0T + blk * cpb, nc = (cpb < ncT - blk * cpb) ? cpb : ncT - blk * cpb;
-  if (CON) {   // (uniform: blocks without a cell that covers Ys keep the values of the unconstrained pass)
-    const int ys = a.ys[v.n];
-    if (ys < i0 || ys - d + 1 > i0 + nc - 1) continue;
-  }
-  const int* dm = dmT + blk * cpb;
-  int* cnts = cntsT + blk * cpb;
-  int* base = baseT + blk * cpb;
-  const double* crec = crecT + blk * cpb * kCellInD;
-  const int* crfl = crflT + blk * cpb;
   // rule 2, factorised (lin_rules.h, lin_inside_apair): lane = (cell, pair p = (s1, t)).  A(i,j,p) = the tail step from
   // A(i,j-1,.) plus one term per stem (k, j) that ends at j and starts behind i; B(i,j,tgt(p)) += A(i,j,p).  The stems are
   // walked four at a time: their operand loads (1(i,k,s1), P(k,j,t), exp(lambda e_ml)) are in flight together.
@@ -973,23 +952,12 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
     if (FAST) {
       fast_inside_unary<kFastR, FP, kFastL, CON>(A, G + A.fp_in + s * kFastW, v.m.lin, v.in, crec + c * kCellInD, crfl[c], d, i, hb + c * HD + (tid - c * NL),
                                                  he + c * HD + (tid - c * NL), NW, 2 * CS, G + A.fs_in);
-      // (the lane owns these two sums: it clears them for the next block of the workgroup -- HD = NL here, and cells past nc take no adds)
-      if (nblk > 1)
-        for (int r = 0; r < NW; ++r) { hb[r * 2 * CS + tid] = 0.; he[r * 2 * CS + tid] = 0.; }
     } else {
       const Constraint con{CON ? a.ys[v.n] : -1, -1, 0};
       lin_inside_target_u<CON>(v.m, v.q, v.in, d, i, s, rep_sum(hb + c * HD + s, NW, 2 * CS), rep_sum(he + c * HD + s, NW, 2 * CS), con);
     }
   }
   pc.mark<4>();
-  if (MB && (blk + 1) * cpb < ncT) {   // the next block's pair phase adds to the heavy sums this unary phase has read
-    if (!FAST || (a.dbg & 4) || (ELEMDP_KO & 4)) {
-      __syncthreads();
-      for (int t = tid; t < NW * 2 * CS; t += kBT) lds[t] = 0.;
-    }
-    __syncthreads();
-  }
-  }   // blocks of the workgroup
   pc.finish();
 }
 
@@ -1433,7 +1401,7 @@ __global__ __launch_bounds__(kThreads) void k4_r7(LinArgs a) {
 
 // ---- outside, diagonal d: dynamic LDS = 4 * cpb * S + n_theta + 2 doubles
 // W6: asked for six waves per SIMD (80 registers, a few spilled dwords) -- taken by the launcher where six workgroups fit the LDS
-template <int MODE, bool BIG, bool FAST = false, int FP = kFastP, bool W6 = false, bool MB = false>
+template <int MODE, bool BIG, bool FAST = false, int FP = kFastP, bool W6 = false>
 __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_out(LinArgs a) {
   extern __shared__ double lds[];
   // (the automaton layout is read from the kernel arguments: constant offsets, scalar registers)
@@ -1447,19 +1415,17 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   const LPass pi = lpass(a, v);
   const AutomatonLayout& A = a.lay;
   const int S = a.lay.S, NA = a.lay.n_active, d = a.d, cpb = a.cpb, tid = threadIdx.x, nt = a.lay.n_theta;
-  // (nblk blocks of cpb cells per workgroup, context staged once: see k4_in)
-  const int nblk = (MB && a.nblk > 1) ? a.nblk : 1, cpbT = cpb * nblk;
   if (d > v.q.W) return;
   const int L = v.q.L, W = v.q.W;
-  const int ncell = L - d + 1, i0T = bx * cpbT;
-  if (i0T >= ncell) return;
-  const int ncT = (cpbT < ncell - i0T) ? cpbT : ncell - i0T;
+  const int ncell = L - d + 1, i0 = bx * cpb;
+  if (i0 >= ncell) return;
+  const int nc = (cpb < ncell - i0) ? cpb : ncell - i0;
   if (MODE == OUT_END) {
     // Under the start constraint the motif begins at Ys: a cell that ends at or before Ys holds no part of it, so no transition in
     // it can be an end of the motif (its posterior is an exact 0: a derivation whose motif began earlier emits Ys with weight 0),
     // and nothing that is swept reads its outside value -- parents, item sums and pair entries all look at cells that contain the
     // reader.  Workgroups whose cells all satisfy j <= Ys return: on average half of the sweep.
-    if (!(a.dbg & 4096) && i0T + ncT - 1 + d <= a.ys[v.n]) return;
+    if (!(a.dbg & 4096) && i0 + nc - 1 + d <= a.ys[v.n]) return;
   }
   const int HD = FAST ? A.n_lane : S;   // (as in k4_in)
   const int CS = cpb * HD;
@@ -1479,10 +1445,10 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   double* l_en = l_en0 + wvd * ES;             // ... this lane's copy
   double* l_eh = l_en + 2 * nt;
   double* l_pos = l_en0 + NWS * ES;            // scan: [2][win] position posteriors of the window (start, inner | end, -)
-  const int win = cpbT + a.wmax + 3;
+  const int win = cpb + a.wmax + 3;
   constexpr bool kScanMode = MODE == OUT_SCAN || MODE == OUT_END;
   double* sOB1 = l_pos + (kScanMode ? 2 * win : 0);   // item records of the three roles (kRecOut doubles; no position window in training)
-  const BlockLds BL = block_lds(out_doubles(CS, nt, win, NWS, kScanMode), cpbT, a.n_lin, win, FAST ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * cpbT, FAST ? kCellOutD : 0);
+  const BlockLds BL = block_lds(out_doubles(CS, nt, win, NWS, kScanMode), cpb, a.n_lin, win, FAST ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * cpb, FAST ? kCellOutD : 0);
   // cell records of the table-driven unary phase (see k4_in): twelve global values per cell, fetched with the context
   constexpr int kCRout = (ELEMDP_CPB_MAX * 12 + kBT - 1) / kBT;
   double crx[kCRout];
@@ -1490,19 +1456,19 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
 #pragma unroll
     for (int r = 0; r < kCRout; ++r) {
       crx[r] = 0.;
-      if (r * kBT < cpbT * 12) {   // (uniform: most automata need the first round only)
-        const int t = tid + r * kBT, c0 = t / 12, c = c0 < ncT ? c0 : 0;
-        crx[r] = cell_out_fetch(v.q, d, i0T + c, t - c0 * 12);
+      if (r * kBT < cpb * 12) {   // (uniform: most automata need the first round only)
+        const int t = tid + r * kBT, c0 = t / 12, c = c0 < nc ? c0 : 0;
+        crx[r] = cell_out_fetch(v.q, d, i0 + c, t - c0 * 12);
       }
     }
   }
-  if (a.dbg & 1024) { if (ncT == 12345) lds[tid] = crx[0] + pi.invZ; return; }   // (timing experiments, as in k4_in)
-  const BlockCtx cx = stage_context<BIG, 1, FAST>(a, v, reinterpret_cast<unsigned char*>(lds), BL, i0T, ncT, d, cpbT);
+  if (a.dbg & 1024) { if (nc == 12345) lds[tid] = crx[0] + pi.invZ; return; }   // (timing experiments, as in k4_in)
+  const BlockCtx cx = stage_context<BIG, 1, FAST>(a, v, reinterpret_cast<unsigned char*>(lds), BL, i0, nc, d, cpb);
   if (pi.skip) return;   // (tested here: the loads behind `pi` travel with those of the context instead of before them)
-  int* dmT = cx.dm; int* cntsT = cx.cnts; int* pre = cx.pre; int* baseT = cx.base;
+  int* dm = cx.dm; int* cnts = cx.cnts; int* pre = cx.pre; int* base = cx.base;
   const int32_t* G = v.m.big;
-  double* crecT = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(lds) + BL.crec);
-  int* crflT = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(lds) + BL.crfl);
+  double* crec = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(lds) + BL.crec);
+  int* crfl = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(lds) + BL.crfl);
   const int n_zero = HS + NWS * ES + ((MODE == OUT_SCAN || MODE == OUT_END) ? 2 * win : 0);
   for (int t = tid; t < n_zero; t += kBT) lds[t] = 0.;
   __syncthreads();
@@ -1512,19 +1478,19 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
 #pragma unroll
     for (int r = 0; r < kCRout; ++r) {
       const int t = tid + r * kBT, c = t / 12, k = t - c * 12;
-      if (c < ncT) {
-        const int i = i0T + c;
+      if (c < nc) {
+        const int i = i0 + c;
         const bool on = k < 4 ? v.q.e_ok(i, d) : k < 6 ? v.q.pair_ok(i, d) : k < 8 ? (v.q.pair_ok(i - 1, d + 2) && v.q.pair_ok(i, d)) : true;
-        crecT[c * kCellOutD + 2 + k] = on ? crx[r] : 0.;
+        crec[c * kCellOutD + 2 + k] = on ? crx[r] : 0.;
       }
     }
-    for (int c = tid; c < ncT; c += kBT) {
-      const int i = i0T + c, j = i + d;
+    for (int c = tid; c < nc; c += kBT) {
+      const int i = i0 + c, j = i + d;
       int fl = cell_out_flags(v.m, v.q, d, i);
       if (MODE == OUT_END) { const int ys = a.ys[v.n]; fl |= (i - 1 == ys ? CF_YL : 0) | (j == ys ? CF_YR : 0) | (L == j + 1 ? CF_JLAST : 0); }
-      crflT[c] = fl;
-      crecT[c * kCellOutD] = v.q.ews[i > 0 ? i - 1 : 0];
-      crecT[c * kCellOutD + 1] = v.q.ews[j < L ? j : L];
+      crfl[c] = fl;
+      crec[c * kCellOutD] = v.q.ews[i > 0 ? i - 1 : 0];
+      crec[c * kCellOutD + 1] = v.q.ews[j < L ? j : L];
     }
   }
   LinSink sink;
@@ -1532,7 +1498,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   sink.eh0 = sink.eh1 = 0.;
   // scan: the position posteriors of this workgroup-diagonal are summed in LDS over the window of positions it touches
   // ([p0, p0 + win): i0-1 .. i0+nc+d, the window of the staged context) and added to the sequence's arrays once at the end
-  const int pos_p0 = (i0T > 0) ? i0T - 1 : 0;
+  const int pos_p0 = (i0 > 0) ? i0 - 1 : 0;
   if (MODE == OUT_SCAN) { sink.pos0 = l_pos - pos_p0; sink.pos1 = l_pos + win - pos_p0; }
   if (MODE == OUT_END) sink.pos2 = l_pos - pos_p0;
   const TableView& in = v.in;
@@ -1540,13 +1506,12 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   const int nq = ((a.dbg & 2) || (ELEMDP_KO & 2)) ? 0 : A.n_quad;
   const double* IB = in.band;
   const double* OB = out.band;
-  // CSR ranges of the item sums of the three roles of all cells of the workgroup, [block][role][cpb] (consumed behind the first
+  // CSR ranges of the item sums of the three roles of all cells of the workgroup, [role][cpb] (consumed behind the first
   // pair phase, whose loads they travel with; the ranges of cells past the end are empty)
-  for (int vc = tid; vc < 3 * cpbT; vc += kBT) {
-    const int kb = div_rcp(vc, a.rcp_3cpb), vr = vc - kb * 3 * cpb;
-    const int role = div_rcp(vr, a.rcp_cpb), cT = kb * cpb + (vr - role * cpb);
-    const bool have = cT < ncT;
-    const int i = i0T + (have ? cT : 0);
+  for (int vc = tid; vc < 3 * cpb; vc += kBT) {
+    const int role = div_rcp(vc, a.rcp_cpb), c = vc - role * cpb;
+    const bool have = c < nc;
+    const int i = i0 + (have ? c : 0);
     const int cell = v.q.cell(i, d);
     const int32_t* off = role == 0 ? v.q.by_inner_off : role == 1 ? v.q.by_left_off : v.q.by_right_off;
     int n0 = 0, n1 = 0;
@@ -1554,21 +1519,10 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     // no children, and the statistics of the emissions into it use the parent's value.  Those cells own the records of every
     // stack and bulge of the sequence.  The generic kernels, whose tables debug_tables exports, keep them.)
     if (have && nq > 0 && (role != 0 || v.q.pair_ok(i, d)) && !(FAST && role != 0 && d == 0)) { n0 = off[cell]; n1 = off[cell + 1]; }
-    baseT[vc] = n0;
-    cntsT[vc] = (n1 > n0) ? n1 - n0 : 0;
+    base[vc] = n0;
+    cnts[vc] = (n1 > n0) ? n1 - n0 : 0;
   }
   const int nv = 3 * cpb;
-  const int tid_wg = tid;
-  for (int blk = 0; MB ? blk * cpb < ncT : blk < 1; ++blk) {
-  int tid = tid_wg;   // (behind an empty asm: see k4_in)
-  if (MB) asm volatile("" : "+v"(tid));
-  const int i0 = i0T + blk * cpb, nc = (cpb < ncT - blk * cpb) ? cpb : ncT - blk * cpb;
-  if (MODE == OUT_END && !(a.dbg & 4096) && i0 + nc - 1 + d <= a.ys[v.n]) continue;   // (uniform; see the workgroup test above)
-  const int* dm = dmT + blk * cpb;
-  const int* cnts = cntsT + blk * 3 * cpb;
-  const int* base = baseT + blk * 3 * cpb;
-  const double* crec = crecT + blk * cpb * kCellOutD;
-  const int* crfl = crflT + blk * cpb;
   // rule 2, factorised, outside direction (lin_rules.h: lheavy_o1 / lheavy_o2):
   //   h1[c][s1] = H1 = sum over the stems (j, l) that start at the cell's end j = i + d:  outA(i,l,p) * P(j,l,t) * xml(j,l)
   //   h2[c][t]  = HA = sum_{ii < i} outA(ii,j,p) * 1(ii,i,s1), only where the cell itself is a stem P(i,j)
@@ -1627,8 +1581,8 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
         if (term != 0.) atomicAdd(&h2A[ha_idx[u]], term);
       }
     };
-    // (unconditional, like the add below: a value that is defined under a condition inside the block loop counts as live around
-    // the whole loop -- 16 registers here)
+    // (unconditional, like the add below: a value that is defined under a condition here counts as live across the phases
+    // around it -- 16 registers)
     ha_load(a.det ? total : tid);      // (deterministic mode: HA follows the H1 sums, a stem cell per wave)
     // (deterministic mode: a cell's pairs in one wave, as in k4_in)
     const int pad = (a.det && a.det_sh >= 0) ? (1 << a.det_sh) : nA;
@@ -1707,8 +1661,6 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   // their weights are staged into the (now free) operand staging area by all lanes with one round of loads; a work item
   // then needs a single round of table loads, selected by role without branches.
   {
-    // (the unary phase of the previous block left out B of its targets in `hp`, which the pair entries behind it have read)
-    if (MB && blk > 0) for (int t = tid; t < CS; t += kBT) hp[t] = 0.;
     lds_prefix(nv, tid, cnts, pre);
     __syncthreads();
     const int n_rec = pre[nv];
@@ -1721,7 +1673,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     // the workgroup's before the unary phase (four accumulators less across it)
     double ew[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { ew[k] = 0.; asm volatile("" : "+v"(ew[k])); }   // (pinned here: the zeros would be set up at the top of the block loop)
+    for (int k = 0; k < 4; ++k) { ew[k] = 0.; asm volatile("" : "+v"(ew[k])); }   // (pinned here: the zeros would be set up at the top of the kernel)
     for (int p0 = 0; p0 < n_rec; p0 += cap) {
       const int np = (cap < n_rec - p0) ? cap : n_rec - p0;
       for (int x = tid; x < np; x += kBT) {
@@ -1846,8 +1798,6 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
         oB = lin_outside_target_u<MODE>(x, d, i0 + c, s, H);     // out B(i,d,s)
       }
     }
-    if (nblk > 1)
-      for (int r = 0; r < NW; ++r) { h1[r * HS + slot] = 0.; h2[r * HS + slot] = 0.; hl[r * HS + slot] = 0.; if (r) hp[r * HS + slot] = 0.; }
     hp[slot] = oB;
   }
   __syncthreads();
@@ -1909,15 +1859,9 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     sink.en_ = en_keep;
   }
   pc.mark<11>();
-  if (MB && (blk + 1) * cpb < ncT && (!FAST || (a.dbg & 4) || (ELEMDP_KO & 4))) {   // (generic rule code: the lanes do not cover every slot)
-    __syncthreads();
-    for (int t = tid; t < NW * HS; t += kBT) lds[t] = 0.;
-    __syncthreads();
-  }
-  }   // blocks of the workgroup
   if (MODE == OUT_SCAN || MODE == OUT_END) {
     __syncthreads();
-    const int p1 = (i0T + ncT + d < L) ? i0T + ncT + d : L;   // inclusive
+    const int p1 = (i0 + nc + d < L) ? i0 + nc + d : L;   // inclusive
     for (int t = tid; t <= p1 - pos_p0; t += kBT) {
       const double v0 = l_pos[t], v1 = l_pos[win + t];
       if (MODE == OUT_SCAN) {
@@ -2279,44 +2223,34 @@ hipError_t launch_cyk_group(const LinArgs& full, int G, int Lmax, int Wmax, hipS
   return hipGetLastError();
 }
 
-// Blocks of cpb cells per band-kernel workgroup (LinArgs::nblk) for a diagonal of `nb` blocks: at most `nmax` (<= ELEMDP_CPB_MAX
-// cells: the cell records and the stem mask of a workgroup), spread evenly over the fewest workgroups; one block per workgroup
-// where the whole launch is resident at once anyway (small groups: there the lifetime of ONE workgroup is the launch's duration).
-// DEFAULT: ONE block.  Three blocks per workgroup stage the context a third as often and measured the same on the bench
-// (257.9 against 258.0 ms per step of 10 000 x L=200 on one box, 107.3 against 105.7 ms per 4096): the set-up they save is not
-// what bounds the kernels, and they cost a resident workgroup per CU (LDS) -- DESIGN.md 4.2d.  Option "nblk" / ELEMDP_NBLK keep
-// the form reachable (tests/test_round4_gpu.py runs it against the one-block kernels and the oracle).
-static int env_nblk(int part) {   // experiments: ELEMDP_NBLK, or ELEMDP_NBLK_IN / ELEMDP_NBLK_OUT for one direction
-  static const int v[3] = {[] { const char* e = getenv("ELEMDP_NBLK"); return e ? atoi(e) : 0; }(),
-                           [] { const char* e = getenv("ELEMDP_NBLK_IN"); return e ? atoi(e) : 0; }(),
-                           [] { const char* e = getenv("ELEMDP_NBLK_OUT"); return e ? atoi(e) : 0; }()};
-  return v[1 + part] > 0 ? v[1 + part] : v[0];
-}
-#ifndef ELEMDP_NBLK_DEFAULT
-#define ELEMDP_NBLK_DEFAULT 1
-#endif
-// req: LinArgs::nblk as the host engine passes it (option "nblk"): 0 = the policy above, n = n blocks wherever they fit;
-// part 0: k4_in, 1: k4_out
-static int nblk_max(int cpb, bool fast, bool det, int req, int part) {
-  if (!fast || det) return 1;
-  // default: up to ELEMDP_NBLK_DEFAULT blocks and ~40 cells per workgroup -- an automaton with few live states has large blocks
-  // already (cpb = 32 for (.....): a second block there costs two of six resident workgroups and the scan got 15 % slower)
-  const int want = req > 0 ? req : env_nblk(part) > 0 ? env_nblk(part) : std::min(ELEMDP_NBLK_DEFAULT, 40 / std::max(cpb, 1));
-  return std::max(1, std::min(want, ELEMDP_CPB_MAX / std::max(cpb, 1)));
-}
 static void set_rcps(LinArgs& a, bool fast) {
   a.rcp_nap = 1.0f / (float)std::max(a.lay.n_ap, 1);
   a.rcp_lane = 1.0f / (float)std::max(fast ? a.lay.n_lane : a.lay.n_active, 1);
   a.rcp_cpb = 1.0f / (float)std::max(a.cpb, 1);
-  a.rcp_3cpb = 1.0f / (float)std::max(3 * a.cpb, 1);
   // deterministic mode: lanes per cell in the pair phases = the power of two >= n_ap (no cell then straddles two waves)
   a.det_sh = -1;
   if (a.lay.n_ap <= 64) { a.det_sh = 0; while ((1 << a.det_sh) < a.lay.n_ap) ++a.det_sh; }
 }
-static int nblk_for(int nb, int G, int nmax, int req) {
-  if (nmax <= 1 || (req <= 0 && (long long)nb * G <= 6144)) return 1;
-  const int nsuper = (nb + nmax - 1) / nmax;
-  return (nb + nsuper - 1) / nsuper;
+// One band-kernel launch per diagonal, the variant chosen the same way by the scan and the train: table-driven with the longest
+// pair list at most 2 -- asking for eight k4_in / six k4_out waves per SIMD where that many workgroups fit a CU's LDS (the
+// 64-register k4_in, the 80-register k4_out) --, table-driven, the blob staged, generic.
+template <bool CON>
+static void launch_k4_in(const LinArgs& a, dim3 grid, size_t lds, bool fast, bool big, hipStream_t st) {
+  const bool fp2 = a.lay.fp_max_p <= 2;
+  if (fast && fp2 && lds * 8 <= 160 * 1024) hipLaunchKernelGGL((k4_in<true, CON, true, 2, true>), grid, dim3(kBT), lds, st, a);
+  else if (fast && fp2) hipLaunchKernelGGL((k4_in<true, CON, true, 2>), grid, dim3(kBT), lds, st, a);
+  else if (fast) hipLaunchKernelGGL((k4_in<true, CON, true>), grid, dim3(kBT), lds, st, a);
+  else if (big) hipLaunchKernelGGL((k4_in<true, CON>), grid, dim3(kBT), lds, st, a);
+  else hipLaunchKernelGGL((k4_in<false, CON>), grid, dim3(kBT), lds, st, a);
+}
+template <int MODE>
+static void launch_k4_out(const LinArgs& a, dim3 grid, size_t lds, bool fast, bool big, hipStream_t st) {
+  const bool fp2 = a.lay.fp_max_p <= 2;
+  if (fast && fp2 && lds * 6 <= 160 * 1024) hipLaunchKernelGGL((k4_out<MODE, true, true, 2, true>), grid, dim3(kBT), lds, st, a);
+  else if (fast && fp2) hipLaunchKernelGGL((k4_out<MODE, true, true, 2>), grid, dim3(kBT), lds, st, a);
+  else if (fast) hipLaunchKernelGGL((k4_out<MODE, true, true>), grid, dim3(kBT), lds, st, a);
+  else if (big) hipLaunchKernelGGL((k4_out<MODE, true>), grid, dim3(kBT), lds, st, a);
+  else hipLaunchKernelGGL((k4_out<MODE, false>), grid, dim3(kBT), lds, st, a);
 }
 
 hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax, int phase, hipStream_t st) {
@@ -2338,72 +2272,45 @@ hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax,
   a.fast = fast ? 1 : 0;
   if (fast) a.cpb = std::min(kBT / std::max(a.lay.n_lane, 1), ELEMDP_CPB_MAX);
   a.n_lin = fast ? a.lay.lin_total : kLinEth + nt;
-  const bool fp2 = a.lay.fp_max_p <= 2;
   const int hd = fast ? a.lay.n_lane : S;   // stride of the heavy sums per cell (k4_in / k4_out: HD)
   set_rcps(a, fast);
-  // (the scan's sum passes keep one block per workgroup unless option "nblk" asks: with (.....) -- few live states, 18 cells per
-  // block already -- a second block costs a resident workgroup per CU and measured 10 % slower, profiles/r04_*)
-  const bool mb_scan = full.nblk > 0 || env_nblk(0) > 0 || env_nblk(1) > 0;
-  const int nbmax_in = mb_scan ? nblk_max(a.cpb, fast, false, full.nblk, 0) : 1, nbmax_out = mb_scan ? nblk_max(a.cpb, fast, false, full.nblk, 1) : 1;
-  auto lds_in_of = [&](int nblk) { const int ct = a.cpb * nblk; return (size_t)block_lds(2 * a.cpb * hd + kRecIn, ct, a.n_lin, ct + Wmax + 3, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0).total; };
-  auto lds_out_of = [&](int nblk) { const int ct = a.cpb * nblk; return (size_t)block_lds(out_doubles(a.cpb * hd, nt, ct + Wmax + 3), ct, a.n_lin, ct + Wmax + 3, fast ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * ct, fast ? kCellOutD : 0).total; };
-  const size_t lds_in = lds_in_of(1), lds_out = lds_out_of(1);
-  // (the eighth k4_in workgroup of a CU fits the LDS: the 64-register variant; the sixth k4_out workgroup: the 80-register variant)
-  auto w8_of = [&](int nblk) { return lds_in_of(nblk) * 8 <= 160 * 1024; };
-  auto w6_of = [&](int nblk) { return lds_out_of(nblk) * 6 <= 160 * 1024; };
-  if (getenv("ELEMDP_LDS_DEBUG") && phase == 0) fprintf(stderr, "scan group: G %d cpb %d S %d nt %d fast %d n_lin %d fast blob in/out %d/%d ints win %d lds k4_in %zu k4_out %zu; with %d / %d blocks per workgroup %zu / %zu\n", G, a.cpb, S, nt, (int)fast, a.n_lin, a.lay.fb_in_n, a.lay.fb_out_n, a.cpb + Wmax + 3, lds_in, lds_out, nbmax_in, nbmax_out, lds_in_of(nbmax_in), lds_out_of(nbmax_out));
+  const int win = a.cpb + Wmax + 3;
+  const size_t lds_in = block_lds(2 * a.cpb * hd + kRecIn, a.cpb, a.n_lin, win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0).total;
+  const size_t lds_out = block_lds(out_doubles(a.cpb * hd, nt, win), a.cpb, a.n_lin, win, fast ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * a.cpb, fast ? kCellOutD : 0).total;
+  if (getenv("ELEMDP_LDS_DEBUG") && phase == 0) fprintf(stderr, "scan group: G %d cpb %d S %d nt %d fast %d n_lin %d fast blob in/out %d/%d ints win %d lds k4_in %zu k4_out %zu\n", G, a.cpb, S, nt, (int)fast, a.n_lin, a.lay.fb_in_n, a.lay.fb_out_n, win, lds_in, lds_out);
   const bool stage_ext = Lmax <= 2048 && a.nword_max <= 8192;
   const size_t lds_ext_in = stage_ext ? (size_t)ext_lds((a.ext_ring ? ext_ring_doubles(0, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : 0;
   const size_t lds_ext_out = stage_ext ? (size_t)ext_lds(2 * nt + 4 + (a.ext_ring ? ext_ring_doubles(2 * nt + 4, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : sizeof(double) * (2 * nt + 4);
   const int ext_nt = (a.ext_block == kExtBlock && a.ext_ring && a.lay.n_active <= 128 && !(a.dbg & 8192)) ? 128 * kExtBlock : 128;   // (small groups: there the chain is exposed; in a large one its four-fold footprint only takes CUs from the band kernels)
-#define ELEMDP_SCAN_PASS(CON, MODE)                                                                                              \
-  do {                                                                                                                           \
-    for (int d = 0; d <= Wmax; ++d) {                                                                                            \
-      const int ncell = Lmax - d + 1;                                                                                            \
-      if (ncell <= 0) break;                                                                                                     \
-      a.d = d;                                                                                                                   \
-      const int nb = (ncell + a.cpb - 1) / a.cpb;                                                                                \
-      a.nblk = nblk_for(nb, G, nbmax_in, full.nblk);                                                                                           \
-      const dim3 grid((nb + a.nblk - 1) / a.nblk, G);                                                                            \
-      const size_t lds_i = lds_in_of(a.nblk);                                                                                    \
-      if (a.nblk > 1 && fp2) hipLaunchKernelGGL((k4_in<true, CON, true, 2, false, true>), grid, dim3(kBT), lds_i, st, a);        \
-      else if (a.nblk > 1) hipLaunchKernelGGL((k4_in<true, CON, true, kFastP, false, true>), grid, dim3(kBT), lds_i, st, a);     \
-      else if (fast && fp2 && w8_of(a.nblk)) hipLaunchKernelGGL((k4_in<true, CON, true, 2, true>), grid, dim3(kBT), lds_i, st, a); \
-      else if (fast && fp2) hipLaunchKernelGGL((k4_in<true, CON, true, 2>), grid, dim3(kBT), lds_i, st, a);                      \
-      else if (fast) hipLaunchKernelGGL((k4_in<true, CON, true>), grid, dim3(kBT), lds_i, st, a);                                \
-      else if (big) hipLaunchKernelGGL((k4_in<true, CON>), grid, dim3(kBT), lds_i, st, a);                                       \
-      else hipLaunchKernelGGL((k4_in<false, CON>), grid, dim3(kBT), lds_i, st, a);                                               \
-    }                                                                                                                            \
-    if (stage_ext) hipLaunchKernelGGL((k4_in_ext<true, CON>), dim3(G), dim3(ext_nt), lds_ext_in, st, a);                         \
-    else hipLaunchKernelGGL((k4_in_ext<false, CON>), dim3(G), dim3(128), 0, st, a);                                              \
-    if (stage_ext) hipLaunchKernelGGL((k4_out_ext<MODE, true>), dim3(G), dim3(ext_nt), lds_ext_out, st, a);                      \
-    else hipLaunchKernelGGL((k4_out_ext<MODE, false>), dim3(G), dim3(128), lds_ext_out, st, a);                                  \
-    hipLaunchKernelGGL(k4_r7, dim3(((Lmax + 1) * (Wmax + 1) + kThreads - 1) / kThreads, G), dim3(kThreads), 0, st, a);           \
-    for (int d = Wmax; d >= 0; --d) {                                                                                            \
-      const int ncell = Lmax - d + 1;                                                                                            \
-      if (ncell <= 0) continue;                                                                                                  \
-      a.d = d;                                                                                                                   \
-      const int nb = (ncell + a.cpb - 1) / a.cpb;                                                                                \
-      a.nblk = nblk_for(nb, G, nbmax_out, full.nblk);                                                                                           \
-      const dim3 grid((nb + a.nblk - 1) / a.nblk, G);                                                                            \
-      const size_t lds_o = lds_out_of(a.nblk);                                                                                   \
-      if (a.nblk > 1 && fp2) hipLaunchKernelGGL((k4_out<MODE, true, true, 2, false, true>), grid, dim3(kBT), lds_o, st, a);      \
-      else if (a.nblk > 1) hipLaunchKernelGGL((k4_out<MODE, true, true, kFastP, false, true>), grid, dim3(kBT), lds_o, st, a);   \
-      else if (fast && fp2 && w6_of(a.nblk)) hipLaunchKernelGGL((k4_out<MODE, true, true, 2, true>), grid, dim3(kBT), lds_o, st, a); \
-      else if (fast && fp2) hipLaunchKernelGGL((k4_out<MODE, true, true, 2>), grid, dim3(kBT), lds_o, st, a);                    \
-      else if (fast) hipLaunchKernelGGL((k4_out<MODE, true, true>), grid, dim3(kBT), lds_o, st, a);                              \
-      else if (big) hipLaunchKernelGGL((k4_out<MODE, true>), grid, dim3(kBT), lds_o, st, a);                                     \
-      else hipLaunchKernelGGL((k4_out<MODE, false>), grid, dim3(kBT), lds_o, st, a);                                             \
-    }                                                                                                                            \
-  } while (0)
+  // pass 0: unconstrained sweeps, the statistics of the scan; pass 1: the start constraint at Ys, the end posteriors
+  auto sweeps = [&](auto con, auto mode) {
+    constexpr bool CON = decltype(con)::value;
+    constexpr int MODE = decltype(mode)::value;
+    for (int d = 0; d <= Wmax; ++d) {
+      const int ncell = Lmax - d + 1;
+      if (ncell <= 0) break;
+      a.d = d;
+      launch_k4_in<CON>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), lds_in, fast, big, st);
+    }
+    if (stage_ext) hipLaunchKernelGGL((k4_in_ext<true, CON>), dim3(G), dim3(ext_nt), lds_ext_in, st, a);
+    else hipLaunchKernelGGL((k4_in_ext<false, CON>), dim3(G), dim3(128), 0, st, a);
+    if (stage_ext) hipLaunchKernelGGL((k4_out_ext<MODE, true>), dim3(G), dim3(ext_nt), lds_ext_out, st, a);
+    else hipLaunchKernelGGL((k4_out_ext<MODE, false>), dim3(G), dim3(128), lds_ext_out, st, a);
+    hipLaunchKernelGGL(k4_r7, dim3(((Lmax + 1) * (Wmax + 1) + kThreads - 1) / kThreads, G), dim3(kThreads), 0, st, a);
+    for (int d = Wmax; d >= 0; --d) {
+      const int ncell = Lmax - d + 1;
+      if (ncell <= 0) continue;
+      a.d = d;
+      launch_k4_out<MODE>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), lds_out, fast, big, st);
+    }
+  };
   if (phase == 0) {
-    ELEMDP_SCAN_PASS(false, OUT_SCAN);
+    sweeps(std::false_type{}, std::integral_constant<int, OUT_SCAN>{});
     hipLaunchKernelGGL(k5_pick<0>, dim3((G + 63) / 64), dim3(64), 0, st, a, G);
   } else {
-    ELEMDP_SCAN_PASS(true, OUT_END);
+    sweeps(std::true_type{}, std::integral_constant<int, OUT_END>{});
     hipLaunchKernelGGL(k5_pick<1>, dim3((G + 63) / 64), dim3(64), 0, st, a, G);
   }
-#undef ELEMDP_SCAN_PASS
   return hipGetLastError();
 }
 
@@ -2425,29 +2332,17 @@ hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool
   const int NW = a.det ? kBT / 64 : 1;   // (copies of the statistics of k4_out: one per wave in the deterministic mode)
   const int hd = fast ? a.lay.n_lane : S;   // stride of the heavy sums per cell (k4_in / k4_out: HD)
   set_rcps(a, fast);
-  const int nbmax_in = nblk_max(a.cpb, fast, a.det != 0, full.nblk, 0), nbmax_out = nblk_max(a.cpb, fast, a.det != 0, full.nblk, 1);
-  auto lds_in_of = [&](int nblk) { const int ct = a.cpb * nblk; return (size_t)block_lds(2 * a.cpb * hd + kRecIn, ct, a.n_lin, ct + Wmax + 3, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0).total; };
-  auto lds_out_of = [&](int nblk) { const int ct = a.cpb * nblk; return (size_t)block_lds(out_doubles(a.cpb * hd, nt, ct + Wmax + 3, NW, false), ct, a.n_lin, ct + Wmax + 3, fast ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * ct, fast ? kCellOutD : 0).total; };
-  const size_t lds_in = lds_in_of(1);
+  const int win = a.cpb + Wmax + 3;
+  const size_t lds_in = block_lds(2 * a.cpb * hd + kRecIn, a.cpb, a.n_lin, win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0).total;
+  const size_t lds_out = block_lds(out_doubles(a.cpb * hd, nt, win, NW, false), a.cpb, a.n_lin, win, fast ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * a.cpb, fast ? kCellOutD : 0).total;
   const size_t lds_stat = sizeof(double) * (2 * nt + 4);
   if (!a.no_rss)
     for (int d = 0; d <= Wmax; ++d) {
       const int ncell = Lmax - d + 1;
       if (ncell <= 0) break;
       a.d = d;
-      const int nb = (ncell + a.cpb - 1) / a.cpb;
-      a.nblk = nblk_for(nb, G, nbmax_in, full.nblk);
-      const dim3 grid((nb + a.nblk - 1) / a.nblk, G);
-      const size_t lds_i = lds_in_of(a.nblk);
-      if (a.nblk > 1 && a.lay.fp_max_p <= 2) hipLaunchKernelGGL((k4_in<true, false, true, 2, false, true>), grid, dim3(kBT), lds_i, st, a);
-      else if (a.nblk > 1) hipLaunchKernelGGL((k4_in<true, false, true, kFastP, false, true>), grid, dim3(kBT), lds_i, st, a);
-      else if (fast && a.lay.fp_max_p <= 2 && lds_i * 8 <= 160 * 1024) hipLaunchKernelGGL((k4_in<true, false, true, 2, true>), grid, dim3(kBT), lds_i, st, a);
-      else if (fast && a.lay.fp_max_p <= 2) hipLaunchKernelGGL((k4_in<true, false, true, 2>), grid, dim3(kBT), lds_i, st, a);
-      else if (fast) hipLaunchKernelGGL((k4_in<true, false, true>), grid, dim3(kBT), lds_i, st, a);
-      else if (big) hipLaunchKernelGGL((k4_in<true, false>), grid, dim3(kBT), lds_i, st, a);
-      else hipLaunchKernelGGL((k4_in<false, false>), grid, dim3(kBT), lds_i, st, a);
+      launch_k4_in<false>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), lds_in, fast, big, st);
     }
-  a.nblk = 1;
   a.lmax = Lmax;
   const bool stage_ext = Lmax <= 2048 && a.nword_max <= 8192;
   const size_t lds_ext_in = stage_ext ? (size_t)ext_lds((a.ext_ring ? ext_ring_doubles(0, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : 0;
@@ -2458,8 +2353,7 @@ hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool
   // pattern's states, the "no motif" terminal on the shadow of (0,0), each with its own Z and statistics (lpass).
   // schedule 0: the reference's two sweeps, (ari, nasi) then the label's mask.
   const int n_pass = (a.schedule == 1 || first_pass_only) ? 1 : 2;
-  const size_t lds_b = lds_out_of(1);
-  if (getenv("ELEMDP_LDS_DEBUG")) fprintf(stderr, "lin group: G %d cpb %d fast %d n_lin %d staged ints in/out %d/%d lds k4_in %zu k4_out %zu; with %d / %d blocks per workgroup %zu / %zu\n", G, a.cpb, (int)fast, a.n_lin, staged_ints(a.lay, a.n_stage, 0), staged_ints(a.lay, a.n_stage, 1), lds_in, lds_b, nbmax_in, nbmax_out, lds_in_of(nbmax_in), lds_out_of(nbmax_out));
+  if (getenv("ELEMDP_LDS_DEBUG")) fprintf(stderr, "lin group: G %d cpb %d fast %d n_lin %d staged ints in/out %d/%d lds k4_in %zu k4_out %zu\n", G, a.cpb, (int)fast, a.n_lin, staged_ints(a.lay, a.n_stage, 0), staged_ints(a.lay, a.n_stage, 1), lds_in, lds_out);
   for (int pass = 0; pass < n_pass; ++pass) {
     LinArgs b = a;
     b.pass = pass;
@@ -2472,18 +2366,9 @@ hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool
         const int ncell = Lmax - d + 1;
         if (ncell <= 0) continue;
         b.d = d;
-        const int nb = (ncell + b.cpb - 1) / b.cpb;
-        b.nblk = nblk_for(nb, G, nbmax_out, full.nblk);
-        const dim3 grid((nb + b.nblk - 1) / b.nblk, G);
-        const size_t lds_o = lds_out_of(b.nblk);
-        if (big && (b.dbg & 16)) hipLaunchKernelGGL((k4_out<OUT_NONE, true>), grid, dim3(kBT), lds_o, st, b);   // (timing experiment: no statistics)
-        else if (b.nblk > 1 && b.lay.fp_max_p <= 2) hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2, false, true>), grid, dim3(kBT), lds_o, st, b);
-        else if (b.nblk > 1) hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, kFastP, false, true>), grid, dim3(kBT), lds_o, st, b);
-        else if (fast && b.lay.fp_max_p <= 2 && lds_o * 6 <= 160 * 1024) hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2, true>), grid, dim3(kBT), lds_o, st, b);
-        else if (fast && b.lay.fp_max_p <= 2) hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2>), grid, dim3(kBT), lds_o, st, b);
-        else if (fast) hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true>), grid, dim3(kBT), lds_o, st, b);
-        else if (big) hipLaunchKernelGGL((k4_out<OUT_TRAIN, true>), grid, dim3(kBT), lds_o, st, b);
-        else hipLaunchKernelGGL((k4_out<OUT_TRAIN, false>), grid, dim3(kBT), lds_o, st, b);
+        const dim3 grid((ncell + b.cpb - 1) / b.cpb, G);
+        if (big && (b.dbg & 16)) hipLaunchKernelGGL((k4_out<OUT_NONE, true>), grid, dim3(kBT), lds_out, st, b);   // (timing experiment: no statistics)
+        else launch_k4_out<OUT_TRAIN>(b, grid, lds_out, fast, big, st);
       }
     }
   }

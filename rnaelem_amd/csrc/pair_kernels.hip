@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kThreads) void k4_pairs(PairArgs a) {
   double v = 0.;
   if (i + d <= L && pair_kept(a.okbits + p.bits_base, i, d, W)) {
     const uint32_t cells = (uint32_t)(W + 1) * (uint32_t)(L + 1);
-    const uint32_t row = (a.tab_cell ? (uint32_t)a.p_cs : (uint32_t)a.p_cs * cells) + ((uint32_t)d * (uint32_t)(L + 1) + (uint32_t)i) * (uint32_t)a.p_rs;
+    const uint32_t row = (uint32_t)a.p_cs * cells + ((uint32_t)d * (uint32_t)(L + 1) + (uint32_t)i) * (uint32_t)a.p_rs;
     const double* in = a.band_in + (size_t)g * a.band_stride + row;
     const double* out = a.band_out + (size_t)g * a.band_stride + row;
     const PairLin r{1. / a.zs[4 * g]};

@@ -106,12 +106,7 @@ def test_band_widths(W, C):
 
 C_LENS = (13, 40, 97, 131, 200, 257, 300)
 C_OPTS = {
-    "row_pad8": (("row_pad", 8),),
-    "cell_major": (("cell_major", 1),),
-    "cell_major_row_pad8": (("cell_major", 1), ("row_pad", 8)),
-    "nblk2": (("nblk", 2),),
-    "nblk3": (("nblk", 3),),
-    "nblk5": (("nblk", 5),),
+    "default": (),
     "fast0": (("fast", 0),),
     "prune0": (("prune", 0),),
     "deterministic": (("deterministic", 1),),
@@ -128,12 +123,12 @@ def layout_refs():
 
 @pytest.mark.parametrize("name", list(C_OPTS))
 def test_layouts_and_kernel_forms(name, layout_refs):
-    """k4_pairs builds the row address of a cell from tab_cell / p_cs / p_rs: row_pad widens the rows, cell_major puts the seven
-    rows of a cell side by side, and pair_posteriors requires the P plane's columns in state order under every layout; nblk,
-    fast 0 and prune 0 change the band kernels that fill the tables k4_pairs reads, deterministic their sum order.  Each option
-    set on a fresh engine against the oracle directly (a wrong row stride or column reads another plane's values)."""
+    """k4_pairs builds the row address of a cell from p_cs / p_rs, and pair_posteriors requires the P plane's columns in state
+    order; fast 0 and prune 0 change the band kernels that fill the tables k4_pairs reads and prune 0 the columns, deterministic
+    their sum order.  Each option set on a fresh engine against the oracle directly (a wrong row stride or column reads another
+    plane's values); the default layout with the scan as well."""
     seqs, quals, x, refs = layout_refs
-    run(P1, seqs, quals, opts=C_OPTS[name], x=x, refs=refs, scan=(name in ("row_pad8", "cell_major_row_pad8")))
+    run(P1, seqs, quals, opts=C_OPTS[name], x=x, refs=refs, scan=(name == "default"))
 
 
 # ---- D. groups and slot reuse

@@ -1,4 +1,4 @@
-"""Round 4, GPU: band-kernel workgroups that own several blocks of cells (option "nblk"), ranged evaluations, streamed scans."""
+"""Round 4, GPU: the band kernels on ragged batches, ranged evaluations, streamed scans."""
 import numpy as np
 import pytest
 
@@ -17,92 +17,48 @@ def ragged(seed, shapes):
 
 
 @pytest.mark.parametrize("pattern", ["((.*.))", "(.....)", "(.(.).)"])
-def test_workgroups_of_several_blocks_train(pattern):
-    """k4_in / k4_out with nblk blocks of cells per workgroup (context staged once, phases block by block; the heavy sums of
-    a block are cleared by the lanes that own them) against one block per workgroup and against the oracle: fn, gr, kept
-    fractions on a ragged batch with negatives, both schedules.  Lengths are chosen so that diagonals end in partial blocks and
-    in workgroups with fewer blocks than nblk (RNAelemTrainDP::operator(), motif_trainer.hpp:124-272)."""
+def test_band_kernels_train_repeat_schedules_oracle(pattern):
+    """k4_in / k4_out on a ragged batch with negatives (lengths chosen so that diagonals end in partial workgroups): a second
+    evaluation on the same slots repeats the first (nothing left behind in the tables), schedule 1 (one outside sweep for
+    both passes) agrees with schedule 0 (the reference's two sweeps) in fn, gr and kept fractions, and the first eight
+    sequences agree with the oracle (RNAelemTrainDP::operator(), motif_trainer.hpp:124-272)."""
     from oracle import pyoracle as po
     seqs, quals = ragged(1100, ((40, 5), (200, 7), (97, 6), (131, 6), (13, 3)))
     for k in range(0, len(quals), 2):
         quals[k][-1] = 5
     res = {}
     x = None
-    for nblk in (1, 2, 3, 5):
-        for sched in (0, 1):
-            eng = api.Engine(pattern, "~T2004~", 50, 30, 1e-4, 0.1, 0, 0)
-            eng.set_option("nblk", nblk)
-            eng.set_option("schedule", sched)
-            eng.load_batch(seqs, quals)
-            if x is None:
-                x = eng.initial_params(0.7)
-                x[:-2] += np.linspace(-0.3, 0.3, len(x) - 2)
-            res[(nblk, sched)] = eng.train_eval(x)
-            again = eng.train_eval(x)      # (the same slots once more: nothing left behind in the tables)
-            assert again[0] == pytest.approx(res[(nblk, sched)][0], rel=1e-12)
-    ref = res[(1, 0)]
-    for key, r in res.items():
-        assert r[0] == pytest.approx(ref[0], rel=1e-10), key
-        np.testing.assert_allclose(r[1], ref[1], rtol=1e-8, atol=1e-9, err_msg=str(key))
-        assert r[2] == ref[2] and r[3] == ref[3]
+    for sched in (0, 1):
+        eng = api.Engine(pattern, "~T2004~", 50, 30, 1e-4, 0.1, 0, 0)
+        eng.set_option("schedule", sched)
+        eng.load_batch(seqs, quals)
+        if x is None:
+            x = eng.initial_params(0.7)
+            x[:-2] += np.linspace(-0.3, 0.3, len(x) - 2)
+        res[sched] = eng.train_eval(x)
+        again = eng.train_eval(x)      # (the same slots once more: nothing left behind in the tables)
+        assert again[0] == pytest.approx(res[sched][0], rel=1e-12)
+    r, ref = res[1], res[0]
+    assert r[0] == pytest.approx(ref[0], rel=1e-10)
+    np.testing.assert_allclose(r[1], ref[1], rtol=1e-8, atol=1e-9)
+    assert r[2] == ref[2] and r[3] == ref[3]
     o = po.make_oracle(pattern, 50, 30, min_bpp=1e-4, tau=0.1)
     fo, go, eo, no = o.train_eval(x, seqs[:8], quals[:8])
     eng = api.Engine(pattern, "~T2004~", 50, 30, 1e-4, 0.1, 0, 0)
-    eng.set_option("nblk", 3)
     eng.load_batch(seqs[:8], quals[:8])
     fn, gr, eff, nsk = eng.train_eval(x)
     assert fn == pytest.approx(fo, rel=1e-9)
     np.testing.assert_allclose(gr, go, rtol=1e-7, atol=1e-7)
 
 
-@pytest.mark.parametrize("pattern", ["((.*.))", "(.....)"])
-def test_workgroups_of_several_blocks_scan(pattern):
-    """The scan's sum passes (start / inner posteriors, the constrained passes with their skipped blocks, end posteriors) with
-    several blocks per workgroup against one (motif_scanner.hpp:186-252)."""
-    seqs, quals = ragged(1300, ((35, 4), (180, 6), (97, 5), (300, 3), (64, 5)))
-    for k in range(0, len(quals), 3):
-        quals[k][len(quals[k]) // 2] = 5
-    out = {}
-    x = None
-    for nblk in (1, 2, 4):
-        eng = api.Engine(pattern, "~T2004~", 50, 30, 1e-4, 0.1, 0, 0)
-        eng.set_option("nblk", nblk)
-        eng.load_batch(seqs, quals)
-        if x is None:
-            x = eng.initial_params(0.7)
-            x[:-2] += np.linspace(-0.4, 0.4, len(x) - 2)
-        out[nblk] = eng.scan(x)
-    r0, en0 = out[1]
-    for nblk in (2, 4):
-        r1, en1 = out[nblk]
-        np.testing.assert_allclose(en1, en0, rtol=1e-9, atol=1e-12)
-        for a_, b_ in zip(r0, r1):
-            assert (a_["Ys"], a_["Ye"]) == (b_["Ys"], b_["Ye"])
-            assert a_["rss"] == b_["rss"] and np.array_equal(a_["psihat"], b_["psihat"])
-            assert b_["exist_prob"] == pytest.approx(a_["exist_prob"], rel=1e-9)
-            for key in ("start", "inner", "end"):
-                fa, fb = np.isfinite(a_[key]), np.isfinite(b_[key])
-                assert np.array_equal(fa, fb), key
-                np.testing.assert_allclose(b_[key][fb], a_[key][fa], rtol=1e-8, atol=1e-9, err_msg=key)
-
-
-def test_three_blocks_per_workgroup_at_size():
-    """At a size where a launch has many more workgroups than the chip keeps resident: three blocks per workgroup against the
-    default (one), results and rate of both (the rates are equal within the noise: DESIGN.md 4.2d)."""
-    seqs, quals = synth.synth_batch(1024, 200, seed=77)
+def test_retired_layout_and_workgroup_options_are_refused():
+    """The band kernels have one form (one block of cells per workgroup) and the compact tables one layout (plane after plane,
+    rows unpadded): the options that selected the retired ones are unknown keys."""
     eng = api.Engine("((.*.))", "~T2004~", 50, 30, 1e-4, 0.1, 0, 0)
-    eng.load_batch(seqs, quals)
-    x = eng.initial_params(1.0)
-    a = eng.train_eval(x)
-    a = eng.train_eval(x)
-    ms_one = eng.last_timing()[1]
-    eng.set_option("nblk", 3)
-    b = eng.train_eval(x)
-    b = eng.train_eval(x)
-    ms_three = eng.last_timing()[1]
-    print("1024 x L=200: %.1f ms with one block per workgroup, %.1f ms with three" % (ms_one, ms_three))
-    assert a[0] == pytest.approx(b[0], rel=1e-10)
-    np.testing.assert_allclose(a[1], b[1], rtol=1e-8, atol=1e-9)
+    for key in ("nblk", "row_pad", "cell_major"):
+        with pytest.raises(api.ElemdpError) as err:
+            eng.set_option(key, 1)
+        assert err.value.code == -1, key      # ELEMDP_EINVAL
 
 
 def test_ranged_evaluation_equals_loading_the_range_alone():
@@ -347,40 +303,6 @@ def test_plan_builder_forms_agree(monkeypatch):
         else:
             np.testing.assert_allclose(got[2], ref[2], rtol=1e-10, atol=1e-11)
         np.testing.assert_array_equal(got[3], ref[3])
-
-
-@pytest.mark.parametrize("pattern", ["((.*.))", "(.....)"])
-def test_table_layouts_agree(pattern):
-    """The compact tables without row padding (the default since round 4), with rows padded to 64-byte lines (row_pad = 8, the
-    layout of round 3) and cell by cell (cell_major: the seven rows of a cell side by side) hold the same values: a deterministic
-    train evaluation is bit-identical, a default one agrees to 1e-11, and the scan's records are the same."""
-    seqs, quals = ragged(500, ((70, 4), (200, 5), (33, 3), (121, 4)))
-    res = {}
-    for name, opts in (("plain", {}), ("pad8", {"row_pad": 8}), ("cell", {"cell_major": 1}), ("cell8", {"cell_major": 1, "row_pad": 8})):
-        for det in (0, 1):
-            eng = api.Engine(pattern, "~T2004~", 50, 30, 1e-4, 0.1, 0, 0)
-            for k, v in opts.items():
-                eng.set_option(k, v)
-            if det:
-                eng.set_option("deterministic", 1)
-            eng.load_batch(seqs, quals)
-            x = eng.initial_params(1.0)
-            res[(name, det)] = eng.train_eval(x)[:2] + (eng.seq_stats().copy(),)
-            if det:
-                res[(name, "scan")] = eng.scan(x)
-    for name in ("pad8", "cell", "cell8"):
-        a, b = res[(name, 1)], res[("plain", 1)]
-        assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), name
-        a, b = res[(name, 0)], res[("plain", 0)]
-        assert a[0] == pytest.approx(b[0], rel=1e-11)
-        np.testing.assert_allclose(a[1], b[1], rtol=1e-10, atol=1e-11)
-        (ra, ea), (rb, eb) = res[(name, "scan")], res[("plain", "scan")]
-        for p, q in zip(ra, rb):
-            assert (p["Ys"], p["Ye"], p["rss"]) == (q["Ys"], q["Ye"], q["rss"]) and list(p["psihat"]) == list(q["psihat"])
-            np.testing.assert_allclose(p["start"], q["start"], rtol=1e-10, atol=1e-300)
-            np.testing.assert_allclose(p["end"], q["end"], rtol=1e-10, atol=1e-300)
-            assert p["exist_prob"] == pytest.approx(q["exist_prob"], rel=1e-10)
-        np.testing.assert_allclose(ea, eb, rtol=1e-10, atol=1e-12)
 
 
 def test_filter_forms_on_random_lengths(monkeypatch):
