@@ -10,13 +10,18 @@ rocprofv3 --pmc passes (profiles/traffic.json), scaled to this launch.  Workload
 '((.*.))', x0 with lambda = (1,1) so the energy terms are exercised; the 10 000 sequences are sharded
 over the N ranks (strong scaling, as the metric is quoted).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself (a child `torch.distributed.run`,
 started before this process touches the GPU); under a launcher WORLD_SIZE must equal --gpus or the run is refused.
 Prints ONE JSON line on rank 0.  `--dump-outputs DIR` then writes what the last timed step returned to its caller -- fn, gr,
 sum_eff, n_skipped of ShardedTrainer -- as DIR/<name>.npy (float64); the inputs are seeded, so two builds can be compared array
 by array.
+
+A plain run sets up, warms up, times the K steps and reports them (the roofline from the kernel times of those steps).
+`--full` adds what takes runs of its own (a few minutes): `second_point` (x0 with lambda = (0,0)), `cpu_baseline` and, on one
+GPU, the secondary measurements (`secondary*`, `per_gpu_at_shard`); `--no-cpu-baseline`, `--no-secondary` and `--no-streamed`
+leave parts of it out.
 """
 import argparse
 import json
@@ -284,24 +289,33 @@ def launcher_command(n, argv, port=None):
             "--master-port", str(port), os.path.join(REPO, "bench.py")] + list(argv)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--n-seq", type=int, default=N_SEQ)
     ap.add_argument("--seq-len", type=int, default=SEQ_LEN)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the scan measurement (BASELINE's secondary metric)")
-    ap.add_argument("--no-streamed", action="store_true", help="skip the streamed evaluation of 60 000 sequences (secondary_streamed)")
+    ap.add_argument("--full", action="store_true",
+                    help="also second_point, cpu_baseline and (one GPU) the secondary measurements and per_gpu_at_shard")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the secondary measurements (scan: BASELINE's secondary metric, and the others)")
+    ap.add_argument("--no-streamed", action="store_true",
+                    help="with --full: skip the streamed evaluations (secondary_streamed, secondary_scan_streamed)")
     ap.add_argument("--serial-passes", action="store_true",
                     help="everything on one stream (for kernel traces: with concurrent streams kernels overlap and their durations no "
                          "longer add up to the pipeline time)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write fn, gr, sum_eff, n_skipped of the last one as DIR/<name>.npy (float64)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def main():
+    args = parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # launch the ranks as a CHILD; this parent never touches torch or HIP (the GPUs are counted from the kernel driver's
@@ -329,7 +343,7 @@ def main():
 
     from rnaelem_amd import api, synth
     from rnaelem_amd.distributed import ShardedTrainer
-    secondary = world == 1 and not args.no_secondary
+    secondary = args.full and world == 1 and not args.no_secondary
     eng = api.Engine(PATTERN, "~T2004~", MAX_SPAN, MAX_ILOOP, 1e-4, 0.1, 0, local_rank)
     if args.serial_passes:
         eng.set_option("two_streams", 0)
@@ -357,15 +371,17 @@ def main():
         kern_ms.append(eng.last_timing()[1])
     barrier()
     dt = time.perf_counter() - t0
-    # second timed point of SURVEY section 8(d): x0 as the CLI builds it, lambda = (0,0)
-    x00 = eng.initial_params(0.0)
-    trainer(x00)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(3):
+    dt00 = 0.0
+    if args.full:
+        # second timed point of SURVEY section 8(d): x0 as the CLI builds it, lambda = (0,0)
+        x00 = eng.initial_params(0.0)
         trainer(x00)
-    barrier()
-    dt00 = (time.perf_counter() - t0) / 3
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            trainer(x00)
+        barrier()
+        dt00 = (time.perf_counter() - t0) / 3
     shard_sizes = [n_local]
     if world > 1:
         t = torch.tensor([dt, dt00], dtype=torch.float64, device="cuda")
@@ -395,8 +411,6 @@ def main():
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "rccl_ranks": dist.get_world_size() if world > 1 else 1, "shard_sizes": shard_sizes,
-        "second_point": {"x": "x0 of the CLI defaults, lambda = (0,0)", "value": args.n_seq / dt00, "unit": "seq/s", "ms_per_step": dt00 * 1e3,
-                         "steps": 3},
         "config": {"workload": "%d synthetic RNAs L=%d, pattern %s, W=%d C=%d min_bpp=1e-4 T2004, x0 lambda=(1,1), one (fn,gr) eval per step" % (
             args.n_seq, args.seq_len, PATTERN, MAX_SPAN, MAX_ILOOP), "n_seq": args.n_seq, "seq_len": args.seq_len, "pattern": PATTERN,
             "sharding": "contiguous ranges per rank, 1 all-reduce of %d doubles per step" % eng.partial_len(),
@@ -407,10 +421,13 @@ def main():
                      "log_space_fallback_sequences": int(eng.last_timing()[2]),
                      "kernel_ms": k_s * 1e3, "algorithmic_bytes_per_launch": alg},
     }
+    if args.full:
+        line["second_point"] = {"x": "x0 of the CLI defaults, lambda = (0,0)", "value": args.n_seq / dt00, "unit": "seq/s",
+                                "ms_per_step": dt00 * 1e3, "steps": 3}
     if args.dump_outputs:
         line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs),
                                 "arrays": dump_outputs(args.dump_outputs, fn, gr, eff, nsk)}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(seqs, quals, x, eng.n_param - 2)
     if secondary:
         del trainer, eng

@@ -265,3 +265,15 @@ def test_bench_dumps_the_outputs_of_a_step_and_refuses_zero_steps(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0", "--dump-outputs", str(tmp_path / "z")],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "--steps" in r.stderr and "{" not in r.stdout and not os.path.exists(str(tmp_path / "z"))
+
+
+def test_bench_full_is_off_by_default_and_passed_on_to_the_ranks():
+    """A plain run times the steps and nothing else; --full (second point, CPU baseline, secondary measurements) is asked for,
+    and a --gpus N launch hands it to every rank with the rest of the command line."""
+    sys.path.insert(0, REPO)
+    import bench
+    assert not bench.parse_args([]).full
+    a = bench.parse_args(["--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"])
+    assert a.full and a.no_cpu_baseline and (a.steps, a.warmup) == (3, 2)
+    cmd = bench.launcher_command(2, ["--gpus", "2", "--full"], port=29998)
+    assert cmd[-3:] == ["--gpus", "2", "--full"]

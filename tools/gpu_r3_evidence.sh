@@ -5,9 +5,10 @@
 O=$GRAFT_REPO_ROOT/gpurun_out/r3ev
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-400 $O/bench.json
+R=$(pwd)
+timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-400 $O/bench.json
 cd /tmp && export TMPDIR=/tmp
-B="python3 $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
+B="python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-secondary"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o run -- $B --serial-passes > $O/kt.log 2>&1; tail -1 $O/kt.log | cut -c1-200
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $O/fetch -o run -- $B > $O/fetch.log 2>&1; tail -1 $O/fetch.log | cut -c1-120
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE -d $O/write -o run -- $B > $O/write.log 2>&1; tail -1 $O/write.log | cut -c1-120

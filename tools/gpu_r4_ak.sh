@@ -4,7 +4,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r4ak; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -3 $O/tests.log
-timeout -k 10 1000 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-330 $O/bench.json
+timeout -k 10 1000 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-330 $O/bench.json
 python - <<'PY'
 import json,os
 b=json.load(open(os.path.join(os.environ["GRAFT_REPO_ROOT"],"gpurun_out/r4ak/bench.json")))

@@ -6,7 +6,7 @@
 O=$GRAFT_REPO_ROOT/gpurun_out/r4ev3
 mkdir -p $O
 cd $GRAFT_REPO_ROOT
-timeout -k 10 1000 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-400 $O/bench.json
+timeout -k 10 1000 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-400 $O/bench.json
 cd /tmp && export TMPDIR=/tmp
 B="python3 $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o run -- $B --serial-passes > $O/kt.log 2>&1; tail -1 $O/kt.log | cut -c1-200
