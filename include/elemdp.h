@@ -197,6 +197,19 @@ int elemdp_pair_posteriors(elemdp_handle* h, const double* x, int32_t n_param, d
  * gamma must be finite and > 0 (else ELEMDP_EINVAL); min_prob = +inf keeps no list. */
 int elemdp_pair_mea(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double gamma, int64_t* n_pairs,
                     double* unpaired, char* structure, double* score);
+/* Stochastic samples of whole derivations of the motif x energy grammar: n_samples (> 0, else ELEMDP_EINVAL) draws
+ * per sequence, each a structure together with its motif alignment, with its exact probability under the model.  The draws are a
+ * pure function of (seed, batch index + index_base, sample index, draw index): a sharded or chunked run that passes the batch
+ * offset of its first sequence as index_base draws what one whole run draws.  Sample k of a sequence with seq_off offset b and
+ * length L: rss + n_samples * b + k * L, L structure letters O L R H B I M (as elemdp_scan's rss); node, at the same offset, L motif
+ * nodes (psihat, one byte each: a model with more than 255 nodes is ELEMDP_EINVAL); logp[seq * n_samples + k], the log of the
+ * derivation's probability.  status[seq]: 0 sampled, 1 no parse (Z = 0), 2 refused (a walk found no candidate with a positive
+ * weight or exceeded its stack bound; that sample has blank letters, node 0 and a NaN log-probability, the others stay).  Sequences
+ * that leave the double range of the scaled-linear tables, and every sequence under option pipeline 3, are sampled on the
+ * log-space tables of the fused scan kernel.  Any output may be NULL.  elemdp_last_timing afterwards: [whole call, the same,
+ * sequences handed to the log-space form].  elemdp_scan, the pair calls and the train calls are unaffected. */
+int elemdp_sample(elemdp_handle* h, const double* x, int32_t n_param, int32_t n_samples, uint64_t seed, int64_t index_base,
+                  char* rss, uint8_t* node, double* logp, int32_t* status);
 /* Copies the list of the last elemdp_pair_posteriors / elemdp_pair_mea: seq (batch index), i, j (cell, j = i + d), p; any may be NULL.
  * cap < n_pairs is ELEMDP_EINVAL; before any elemdp_pair_posteriors (of the resident batch) ELEMDP_ESTATE. */
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap);

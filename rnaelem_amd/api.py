@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -83,6 +83,7 @@ def load_library():
         L.elemdp_scan.argtypes = [hp, dp, C.c_int32, C.POINTER(ScanOut)]
         L.elemdp_pair_posteriors.argtypes = [hp, dp, C.c_int32, C.c_double, C.POINTER(C.c_int64), dp]
         L.elemdp_pair_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int64), dp, C.c_char_p, dp]
+        L.elemdp_sample.argtypes = [hp, dp, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(C.c_uint8), dp, i32]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
         L.elemdp_last_timing.argtypes = [hp, dp, C.c_int32]
         L.elemdp_epoch_permutation.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
@@ -323,6 +324,32 @@ class Engine:
         raw = s.raw.decode("ascii")
         structs = [raw[int(off[k]):int(off[k + 1])] for k in range(self.n_seq)]
         return structs, sc[:self.n_seq].copy(), None if min_prob is None else self._pair_lists(m.value, unp)
+
+    # ---- stochastic samples of derivations
+    SAMPLED, NO_PARSE, REFUSED = 0, 1, 2
+
+    def sample_structures(self, x, n_samples, seed=0, index_base=0):
+        """One entry per sequence: (rss, nodes, logp, status) -- n_samples derivations drawn with their probabilities under the
+        model: rss the structure letters (O L R H B I M) of each sample, nodes an (n_samples, L) uint8 array of motif nodes
+        (psihat), logp the log-probability of each derivation, status SAMPLED, NO_PARSE or REFUSED (a failed walk: its sample has blank
+        rss, nodes 0 and logp NaN).  The draws depend on (seed, index_base + batch index, sample index) only."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        n_samples = int(n_samples)
+        nb = max(int(off[-1]) * max(n_samples, 0), 1)
+        rss = C.create_string_buffer(nb)
+        node = np.zeros(nb, dtype=np.uint8)
+        logp = np.zeros(max(self.n_seq * max(n_samples, 0), 1))
+        status = np.zeros(max(self.n_seq, 1), dtype=np.int32)
+        self._check(self._lib.elemdp_sample(self._h, _dp(x), self.n_param, n_samples, int(seed) & (2 ** 64 - 1), int(index_base),
+                                            rss, node.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(logp), _i32(status)))
+        raw = rss.raw.decode("ascii")
+        out = []
+        for k in range(self.n_seq):
+            L, b = int(off[k + 1] - off[k]), int(off[k]) * n_samples
+            out.append(([raw[b + t * L:b + (t + 1) * L] for t in range(n_samples)], node[b:b + n_samples * L].reshape(n_samples, L).copy(),
+                        logp[k * n_samples:(k + 1) * n_samples].copy(), int(status[k])))
+        return out
 
     def last_timing(self):
         """[ms whole evaluation, ms DP pipeline, sequences re-evaluated in log space]"""

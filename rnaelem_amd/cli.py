@@ -7,6 +7,8 @@
                                     # + base-pair posteriors under the motif model (--pair-min-prob, default 1e-3)
     python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-mea mea.txt
                                     # + maximum expected accuracy structures over those posteriors (--mea-gamma, default 1)
+    python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-samples samples.txt
+                                    # + sampled structures with their motif alignments (--n-samples 100, --sample-seed 0)
     python -m rnaelem_amd.cli       --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --out2 scan.raw
                                     # no sub-command = what script/elem spawns: train, write the model, scan (main.cpp:47-84)
     python -m rnaelem_amd.cli eval  --fastq pos.fq --motif-model model.txt --out1 fn.txt --out2 gr.txt     (motif_eval.hpp:23-54)
@@ -54,6 +56,12 @@ def build_parser():
                                           "(io.mea_record)")
     sub.choices["scan"].add_argument("--mea-gamma", type=float, default=1.0,
                                      help="weight of the pairs: a pair scores 2 gamma P, an unpaired base its unpaired probability")
+    sub.choices["scan"].add_argument("--out-samples", default=None,
+                                     help="stochastic samples of structures with their motif alignments: one record per sequence "
+                                          "(io.sample_record).  Host memory per chunk: n-samples x bases of the chunk x 2 bytes")
+    sub.choices["scan"].add_argument("--n-samples", type=int, default=100, help="samples per sequence")
+    sub.choices["scan"].add_argument("--sample-seed", type=int, default=0,
+                                     help="seed of the draws (with the sequence's input index: a torchrun run writes what one GPU writes)")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -219,24 +227,28 @@ def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
         sharded_write(recs, [out1, out_pairs], rank, world, scan_part, barrier)
 
 
-def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0):
+def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0,
+                  out_samples=None, n_samples=100, sample_seed=0):
+    from .distributed import assigned_range
     nodes = eng.describe()["node"]
     step = max(1, chunk)
+    lo = assigned_range(len(recs), world, rank)[0]     # (batch-global sequence index of this rank's first record: the samples' key)
 
     def scan_part(mine):
         for c0 in range(0, len(mine), step):        # records are independent: chunks in input order
             part = mine[c0:c0 + step]
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
-            if out_pairs is None and out_mea is None:
+            if out_pairs is None and out_mea is None and out_samples is None:
                 for (rid, codes, _), r in zip(part, res):
                     yield io.scan_record(rid, codes, r, nodes)
                 continue
             # (the same loaded batch; with both files one device call gives the pairs and the structures)
             if out_mea is None:
-                prs = eng.pair_posteriors(m["x"], pair_min_prob)
+                prs = eng.pair_posteriors(m["x"], pair_min_prob) if out_pairs is not None else None
             else:
                 structs, scores, prs = eng.mea_structures(m["x"], mea_gamma, pair_min_prob if out_pairs is not None else None)
+            smp = eng.sample_structures(m["x"], n_samples, sample_seed, lo + c0) if out_samples is not None else None
             for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
                 texts = [io.scan_record(rid, codes, r, nodes)]
                 if out_pairs is not None:
@@ -244,12 +256,15 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                     texts.append(io.pair_record(rid, len(codes), (ii, jj, pp), unp))
                 if out_mea is not None:
                     texts.append(io.mea_record(rid, structs[k], scores[k]))
+                if out_samples is not None:
+                    rss, node, logp, status = smp[k]
+                    texts.append(io.sample_record(rid, (rss, node, logp) if status == eng.SAMPLED else None, nodes, status))
                 yield tuple(texts)
 
-    if out_mea is None:
+    if out_mea is None and out_samples is None:
         sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
     else:
-        outs = [out1] + ([out_pairs] if out_pairs is not None else []) + [out_mea]
+        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples) if o is not None]
         sharded_write(recs, outs, rank, world, scan_part, barrier)
 
 
@@ -264,7 +279,7 @@ def cmd_scan(a):
     m = io.read_model(a.motif_model)
     eng = io.engine_from_model(m, a.device if a.device is not None else local_rank)
     _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
-                  a.mea_gamma)
+                  a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed)
     if world > 1:
         dist.destroy_process_group()
 

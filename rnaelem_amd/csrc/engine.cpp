@@ -35,6 +35,7 @@
 #include "host_prep.h"
 #include "kernels.h"
 #include "lin_params.h"
+#include "sample_rules.h"
 
 namespace elemdp {
 namespace {
@@ -246,6 +247,9 @@ class Engine {
   struct MeaOut { double gamma; char* structure; double* score; };
   void pair_posteriors(const double* x, int n_param, double min_prob, int64_t* n_pairs, double* unpaired, const MeaOut* mea = nullptr);
   void pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap);
+  // stochastic samples of derivations (sample_rules.h); outputs as elemdp_sample
+  struct SampleOut { char* rss; uint8_t* node; double* logp; int32_t* status; };
+  void sample_structures(const double* x, int n_param, int n_samples, uint64_t seed, int64_t index_base, const SampleOut& out);
   int partial_len() const { return 4 + 2 * au_.n_theta() + 4; }
   void set_option(const std::string& key, double v);
   void comm_init(int rank, int world, const void* id);
@@ -378,6 +382,7 @@ class Engine {
   void stream_train(const double* x, int n_param, void* partial, bool device_ptr, bool reduce);
   void stream_scan(const double* x, int n_param, elemdp_scan_out* out);
   void stream_pairs(const double* x, int n_param, double min_prob, double* unpaired, const MeaOut* mea);
+  void stream_samples(const double* x, int n_param, int n_samples, uint64_t seed, int64_t index_base, const SampleOut& out);
   // pair posteriors: kept pairs per sequence and their prefix (staging ranges), pairs kept by min_prob and their prefix, the
   // P(i, d) scratch of the table slots, the staging list, the final list of the last call (n_pairs_ < 0: none)
   DevBuf d_pr_kept_, d_pr_koff_, d_pr_cnt_, d_pr_off_, d_pr_P_, d_pr_unp_, d_pr_si_, d_pr_sj_, d_pr_sp_;
@@ -385,6 +390,7 @@ class Engine {
   int64_t n_pairs_ = -1;
   // MEA structures: the M table and choice scratch of the table slots (as d_pr_P_), the structures and the scores of the call
   DevBuf d_mea_M_, d_mea_ch_, d_mea_s_, d_mea_sc_;
+  DevBuf d_sm_rss_, d_sm_node_, d_sm_logp_, d_sm_status_, d_sm_stack_;   // sample_structures
 
   Automaton au_;
   EnergyTables et_;
@@ -2176,6 +2182,94 @@ void Engine::pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t 
 }
 
 
+// ---- stochastic samples of derivations (sample_rules.h).  The inside sweeps of the scan's first sum pass per group
+// (launch_lin_scan_group phase 2: no outside pass) and k_sample on the group's slots right behind them, before the next group of the
+// stream reuses them; the log-space form in the fused scan kernel for the sequences the range check flags.
+void Engine::sample_structures(const double* x, int n_param_in, int n_samples, uint64_t seed, int64_t index_base,
+                               const SampleOut& out) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (n_samples <= 0) throw ArgError("sample: n_samples must be > 0");
+  if (n_node() > 255) throw ArgError("sample: more than 255 motif nodes do not fit the node bytes");
+  if (streaming_) { stream_samples(x, n_param_in, n_samples, seed, index_base, out); return; }
+  if (n_seq_ <= 0) throw StateError("sample before load_batch");
+  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+  upload_params(x, lay_, false);
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  const size_t n_bytes = (size_t)n_samples * n_seqpos;
+  const int cap = sample_stack_cap(Lmax_);
+  d_sm_rss_.alloc(std::max<size_t>(n_bytes, 1)); d_sm_node_.alloc(std::max<size_t>(n_bytes, 1));
+  d_sm_logp_.alloc(8 * (size_t)n * n_samples); d_sm_status_.alloc(4 * (size_t)n);
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  SampleArgs sa;
+  std::memset(&sa, 0, sizeof(sa));
+  sa.n_samples = n_samples; sa.seed = seed; sa.index_base = index_base;
+  sa.rss = d_sm_rss_.as<char>(); sa.node = d_sm_node_.as<uint8_t>(); sa.logp = d_sm_logp_.as<double>();
+  sa.status = d_sm_status_.as<int32_t>();
+  sa.stack_cap = cap;
+  int n_flagged = 0;
+  const bool sums_on_batch = opt_pipeline_ == 4;
+  if (sums_on_batch) {
+    ScanPos pos(n_seqpos, n);
+    LinArgs a;
+    const int gsz = prepare_scan(a, pos);
+    sa.stack_lanes = std::min(n_samples, kSampleLanes);
+    d_sm_stack_.alloc(sizeof(TraceFrame) * (size_t)n_slots_ * sa.stack_lanes * cap);
+    const int ns = group_streams(n >= 128 && n_slots_ >= 128);
+    sweep_groups(a, n, h_order_.data(), d_order_.as<int32_t>(), d_plans_sorted_.as<SeqPlan>(), gsz, ns,
+                 [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, 2, st));
+      SampleArgs sk = sa;
+      sk.stack = d_sm_stack_.as<TraceFrame>() + slot0 * sa.stack_lanes * (size_t)cap;
+      HIP_OK(launch_sample(ak, sk, G, st));
+    });
+    n_flagged = read_flagged();
+    tables_linear_ = false;
+  }
+  // ---- the log-space form: the sequences the range check flagged, or every sequence under pipeline 3.  The fused scan kernel
+  // stops after its inside pass and draws the samples on its own slot before it takes the next sequence.
+  const int n_log = sums_on_batch ? n_flagged : n;
+  if (n_log > 0) {
+    int n_blocks;
+    DpArgs d = log_scan_args(sums_on_batch, &n_blocks);
+    const int lanes = std::min(n_samples, kThreads);
+    d_sm_stack_.alloc(sizeof(TraceFrame) * (size_t)n_blocks * lanes * cap);
+    d.order = sums_on_batch ? d_flagged_.as<int32_t>() + 1 : d_order_.as<int32_t>();
+    d.n_seq = n_log;
+    d.smp = sa;
+    d.smp.stack = d_sm_stack_.as<TraceFrame>();
+    d.smp.stack_lanes = lanes;
+    HIP_OK(hipMemsetAsync(d_counter_.as<void>(), 0, sizeof(int32_t), st_));
+    HIP_OK(launch_dp(DP_SCAN, d, std::min(n_blocks, n_log), st_));
+  }
+  if (!sums_on_batch) n_slots_ = 0;   // (as after a scan: these slots are not reused by the train pipelines)
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms = 0;
+  HIP_OK(hipEventElapsedTime(&ms, ev_[1], ev_[2]));
+  last_ms[0] = last_ms[1] = ms;
+  last_ms[2] = (double)n_flagged;
+  if (out.rss && n_bytes) HIP_OK(hipMemcpy(out.rss, d_sm_rss_.as<void>(), n_bytes, hipMemcpyDeviceToHost));
+  if (out.node && n_bytes) HIP_OK(hipMemcpy(out.node, d_sm_node_.as<void>(), n_bytes, hipMemcpyDeviceToHost));
+  if (out.logp) HIP_OK(hipMemcpy(out.logp, d_sm_logp_.as<void>(), 8 * (size_t)n * n_samples, hipMemcpyDeviceToHost));
+  if (out.status) HIP_OK(hipMemcpy(out.status, d_sm_status_.as<void>(), 4 * (size_t)n, hipMemcpyDeviceToHost));
+}
+
+void Engine::stream_samples(const double* x, int n_param_in, int n_samples, uint64_t seed, int64_t index_base,
+                            const SampleOut& out) {
+  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+  last_ms[0] = last_ms[1] = last_ms[2] = 0.;
+  stream_chunks([&](int, int c0, int, Engine& e) {
+    const int64_t at = (h_seq_off_[c0] - h_seq_off_[0]) * (int64_t)n_samples;   // (the chunk's first sample byte)
+    const SampleOut oc{out.rss ? out.rss + at : nullptr, out.node ? out.node + at : nullptr,
+                       out.logp ? out.logp + (size_t)c0 * n_samples : nullptr, out.status ? out.status + c0 : nullptr};
+    e.sample_structures(x, n_param_in, n_samples, seed, index_base + c0, oc);
+    for (int t = 0; t < 3; ++t) last_ms[t] += e.last_ms[t];
+  });
+}
+
+
 // ---- shuffled negatives (host) ------------------------------------------------------------------------------------
 // k-let preserving shuffle by a random Euler tour (uShuffle): vertices = distinct (k-1)-lets in order of first
 // appearance, edges = consecutive lets; a random arborescence towards the last let (Wilson), the remaining out-edges of
@@ -2425,6 +2519,13 @@ int elemdp_pair_mea(elemdp_handle* h, const double* x, int32_t n_param, double m
   if (!h || !x || !n_pairs) throw elemdp::ArgError("elemdp_pair_mea: null argument");
   const elemdp::Engine::MeaOut mea{gamma, structure, score};
   h->e->pair_posteriors(x, n_param, min_prob, n_pairs, unpaired, &mea);
+  ELEMDP_CATCH
+}
+int elemdp_sample(elemdp_handle* h, const double* x, int32_t n_param, int32_t n_samples, uint64_t seed, int64_t index_base,
+                  char* rss, uint8_t* node, double* logp, int32_t* status) {
+  ELEMDP_TRY
+  if (!h || !x) throw elemdp::ArgError("elemdp_sample: null argument");
+  h->e->sample_structures(x, n_param, n_samples, seed, index_base, elemdp::Engine::SampleOut{rss, node, logp, status});
   ELEMDP_CATCH
 }
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {

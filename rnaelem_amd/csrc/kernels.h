@@ -57,6 +57,21 @@ struct LdsLayout {
 
 enum DpKind : int { DP_TRAIN = 0, DP_BPP = 1, DP_SCAN = 2 };
 
+// ---- stochastic samples of derivations (sample_rules.h, sample_kernels.hip), on the inside tables of launch_lin_scan_group phase
+// 2, right behind it on the same slots and stream
+// (launch_sample), and -- the log-space form -- in the fused scan kernel right after its inside pass (DpArgs::smp).  Batch index n (= grp[g]) with seq_base b and length L writes sample k at
+// rss / node + n_samples * b + k * L (L bytes each) and logp[n * n_samples + k]; status[n] is a SampleStatus.
+struct TraceFrame;   // (scan_rules.h)
+struct SampleArgs {
+  int32_t n_samples;
+  uint64_t seed;
+  int64_t index_base;        // added to the batch index in the generator key
+  char* rss; uint8_t* node; double* logp; int32_t* status;
+  TraceFrame* stack;         // per slot of the launch: stack_lanes stacks of stack_cap frames, one per walking lane
+  int32_t stack_cap, stack_lanes;   // stack_lanes = min(n_samples, lanes of a workgroup)
+};
+constexpr int kSampleLanes = 64;   // one wave per sequence, one lane per sample
+
 struct DpArgs {
   AutomatonLayout lay;            // host-visible copy (launch geometry, LDS sizes)
   const AutomatonLayout* layp;    // the same record in device memory: kernels read it through this pointer
@@ -93,6 +108,9 @@ struct DpArgs {
   // SCAN, base-pair posteriors (pair_rules.h): non-null = stop after inside + the first outside pass and write P(i, d) of the
   // sequence order[w] to pair_p + w * pair_stride ([i][d], rows of W+1; 0 where the cell is not kept)
   double* pair_p; size_t pair_stride;
+  // SCAN, samples (sample_rules.h, log-space form): n_samples > 0 = stop after the inside pass and draw the samples of sequence
+  // order[w] on the slot's dense log tables, the workgroup's lanes over the samples
+  SampleArgs smp;
 };
 
 // arguments of the diagonal-synchronous train pipeline (train_kernels.hip)
@@ -221,7 +239,8 @@ hipError_t launch_lin_weights(const LinWeightArgs& a, hipStream_t st);
 // one whole train evaluation of a group; `full` sweeps the pattern automaton, `compact` (schedule 1) the one-state
 // automaton of the no-motif pass over the compact tables
 // scan: phase 0 = inside + outside with start / inner posteriors and argmax start; phase 1 = the same constrained to that
-// start with end posteriors and argmax end (RNAelemScanDP::operator(), motif_scanner.hpp:186-202)
+// start with end posteriors and argmax end (RNAelemScanDP::operator(), motif_scanner.hpp:186-202); phase 2 = the inside sweeps
+// and the exterior chain of phase 0 only (Z and the range check, no outside pass: the tables of the sampler, sample_rules.h)
 hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax, int phase, hipStream_t st);
 // scan: Viterbi parse (max-plus CYK with trace records, then traceback) of a group; uses band_in / ext_in as the CYK table
 hipError_t launch_cyk_group(const LinArgs& full, int G, int Lmax, int Wmax, hipStream_t st);
@@ -270,6 +289,8 @@ hipError_t launch_pair_cells(const PairArgs& a, int G, int cells_max, hipStream_
 hipError_t launch_pair_seq(const PairArgs& a, int G, hipStream_t st);
 // k_pair_mea, behind launch_pair_seq on the same slots and stream; Wmax >= the W of every sequence of the launch (LDS size)
 hipError_t launch_pair_mea(const PairArgs& a, int G, int Wmax, hipStream_t st);
+
+hipError_t launch_sample(const LinArgs& a, const SampleArgs& s, int G, hipStream_t st);
 // kept pairs of every sequence of the batch (the staging capacity), off[0..n] = exclusive prefix of cnt[0..n) with off[n] the total,
 // and the scatter of the staging list into the final list ordered by (sequence, i, j)
 hipError_t launch_pair_kept(const SeqPlan* plans, const uint32_t* okbits, int n, int64_t* kept, hipStream_t st);

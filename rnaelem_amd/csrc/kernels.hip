@@ -21,6 +21,8 @@
 #include "kernels.h"
 #include "pair_rules.h"
 #include "plan_rules.h"
+#include "sample_lane.h"
+#include "sample_rules.h"
 #include "scan_rules.h"
 #include "wave_gather.h"
 
@@ -707,6 +709,20 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
         sweep_inside<false>(m, q, Tin, c0, no_rss, sc, pf);
         if (tid == 0) { l_zs[0] = part_func(m, Tin, true, true); l_zs[1] = Tin.o(L, m.lay.s00); }
         __syncthreads();
+        if (a.smp.n_samples > 0) {   // samples (sample_rules.h): the inside tables are all they need
+          __shared__ int l_status;
+          if (tid == 0) l_status = SAMPLE_OK;
+          __syncthreads();
+          const LogSampleTab T{Tin};
+          TraceFrame* stack = a.smp.stack + ((size_t)blockIdx.x * a.smp.stack_lanes + min(tid, a.smp.stack_lanes - 1)) * (size_t)a.smp.stack_cap;
+          const int64_t base = (int64_t)a.smp.n_samples * p.seq_base;
+          int status = SAMPLE_OK;
+          for (int k = tid; k < a.smp.n_samples; k += kThreads) status = max(status, sample_one(m, q, T, a.smp, n, base, L, k, stack));
+          if (status != SAMPLE_OK) atomicMax(&l_status, status);
+          __syncthreads();
+          if (tid == 0) a.smp.status[n] = l_status;
+          continue;
+        }
         const double ZL = l_zs[0];
         sink.post_[0] = Pys; sink.post_[1] = Pyi;
         sweep_outside<OUT_SCAN>(m, q, Tin, Tout, ZL, c0, true, true, sink, l_eh, no_rss, sc, pf);

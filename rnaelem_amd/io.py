@@ -182,3 +182,48 @@ def read_mea_records(path):
         out.append((lines[k][4:], lines[k + 1][len("mea: "):], float(lines[k + 2][len("score: "):])))
         k += 3
     return out
+
+
+def sample_motif_span(nodes, M):
+    """(start, end) of the motif in one sample, half-open: the span of the positions whose node is neither 0 nor M-1 (the non-blank
+    part of `mot`), or (-1, -1) when the sample has no motif."""
+    inside = [p for p, h in enumerate(nodes) if h != 0 and h != M - 1]
+    return (inside[0], inside[-1] + 1) if inside else (-1, -1)
+
+
+SAMPLE_STATUS = ("sampled", "no parse", "refused")
+
+
+def sample_record(rid, samples, nodes, status=0):
+    """Record of one sequence in the `scan --out-samples` file: `id: <id>`, `samples: N`, then one line per sample with the
+    tab-separated fields index, log-probability (%.17g), motif start and end (half-open, 0-based; -1 -1 without a motif),
+    dot-bracket (L -> '(', R -> ')', else '.'), the structure letters, and the `mot` string of scan_record (the node name per
+    position, blank outside the motif).  samples: (rss strings, node rows, logps) as Engine.sample_structures gives them for a
+    sampled sequence, or None (N = 0: not sampled); nodes: the pattern's node names.  A line `status: <sampled | no parse |
+    refused>` (Engine.sample_structures' status) follows the count."""
+    rss, node, logp = samples if samples is not None else ([], [], [])
+    M = len(nodes)
+    lines = ["id: " + rid, "samples: %d" % len(rss), "status: " + SAMPLE_STATUS[status]]
+    for t, (r, h, lp) in enumerate(zip(rss, node, logp)):
+        a, b = sample_motif_span(h, M)
+        db = "".join("(" if c == "L" else ")" if c == "R" else "." for c in r)
+        mot = "".join(" " if (v == 0 or v == M - 1) else nodes[v] for v in h)
+        lines.append("\t".join([str(t), "%.17g" % float(lp), str(a), str(b), db, r, mot]))
+    return "\n".join(lines) + "\n"
+
+
+def read_sample_records(path):
+    """-> list of (id, status, [(index, logp, start, end, dot-bracket, rss, mot), ...]) from a `scan --out-samples` file."""
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+    while k + 1 < len(lines) and lines[k].startswith("id: "):
+        rid = lines[k][4:]
+        n = int(lines[k + 1][len("samples: "):])
+        status = lines[k + 2][len("status: "):]
+        rows = []
+        for t in range(n):
+            f = lines[k + 3 + t].split("\t")
+            rows.append((int(f[0]), float(f[1]), int(f[2]), int(f[3]), f[4], f[5], f[6]))
+        out.append((rid, status, rows))
+        k += 3 + n
+    return out
