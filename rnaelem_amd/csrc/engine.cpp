@@ -313,6 +313,9 @@ class Engine {
   int prepare_scan(LinArgs& a, const ScanPos& pos);
   int read_flagged(std::vector<int32_t>* list = nullptr);
   DpArgs log_scan_args(bool sums_on_batch, int* n_blocks);
+  void require_resident(const char* what, int n_param_in);
+  template <class Fill, class Group> int scan_sums(const ScanPos& pos, Fill fill, Group group, std::vector<int32_t>* flagged = nullptr);
+  template <class Fill, class Behind> void scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind behind);
   TrArgs log_pipeline_args();
   void init_device();
   void flatten_automaton();
@@ -378,7 +381,7 @@ class Engine {
     for (size_t k = 0; k < h_plans_.size(); ++k) eff[k] = h_plans_[k].bpp_eff;
   }
   void stream_subs();
-  template <class Work> void stream_chunks(Work work);
+  template <class Checked, class Work> void stream_call(int n_param_in, Checked checked, Work work);
   void stream_train(const double* x, int n_param, void* partial, bool device_ptr, bool reduce);
   void stream_scan(const double* x, int n_param, elemdp_scan_out* out);
   void stream_pairs(const double* x, int n_param, double min_prob, double* unpaired, const MeaOut* mea);
@@ -1273,8 +1276,13 @@ void Engine::stream_load_chunk(int k, Engine& e) {
   if (k < (int)st_have_eff_.size()) st_have_eff_[k] = 1;
 }
 
-// work(k, c0, c1, engine): chunk k = sequences [c0, c1) is resident on `engine`; the next chunk loads meanwhile
-template <class Work> void Engine::stream_chunks(Work work) {
+// The streamed form of a call.  checked(): the call's own argument checks and set-up, which come behind the n_param check;
+// work(c0, c1, engine): the call on the sequences [c0, c1), the chunk resident on `engine` (the next chunk loads meanwhile),
+// and the merge of its results.  last_ms adds up over the chunks.
+template <class Checked, class Work> void Engine::stream_call(int n_param_in, Checked checked, Work work) {
+  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+  checked();
+  last_ms[0] = last_ms[1] = last_ms[2] = 0.;
   stream_subs();
   const int nchunks = (n_seq_ + st_chunk_ - 1) / st_chunk_;
   stream_load_chunk(0, *sub_[0]);
@@ -1287,7 +1295,8 @@ template <class Work> void Engine::stream_chunks(Work work) {
         try { stream_load_chunk(k + 1, *sub_[(k + 1) & 1]); } catch (...) { err = std::current_exception(); }
       });
     try {
-      work(k, k * st_chunk_, std::min(n_seq_, (k + 1) * st_chunk_), cur);
+      work(k * st_chunk_, std::min(n_seq_, (k + 1) * st_chunk_), cur);
+      for (int t = 0; t < 3; ++t) last_ms[t] += cur.last_ms[t];
     } catch (...) {
       if (th.joinable()) th.join();
       throw;
@@ -1298,22 +1307,20 @@ template <class Work> void Engine::stream_chunks(Work work) {
 }
 
 void Engine::stream_train(const double* x, int n_param_in, void* partial, bool device_ptr, bool reduce) {
-  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
-  // (a range of the batch is evaluated by the resident scaled-linear pipeline only: run_lin_batch; anything else would return
-  // sums over the whole batch for it)
-  if (opt_eval_count_ > 0 && !(opt_eval_first_ == 0 && opt_eval_count_ == n_seq_))
-    throw ArgError("eval_first / eval_count: a streamed batch is evaluated as a whole (load fewer sequences, or raise max_resident)");
-  set_theta_from(x);
   const int np = partial_len();
   std::vector<double> total(np, 0.), part(np);
-  st_rows_.assign((size_t)5 * n_seq_, 0.);
-  last_ms[0] = last_ms[1] = last_ms[2] = 0.;
-  stream_chunks([&](int, int c0, int c1, Engine& e) {
+  stream_call(n_param_in, [&] {
+    // (a range of the batch is evaluated by the resident scaled-linear pipeline only: run_lin_batch; anything else would return
+    // sums over the whole batch for it)
+    if (opt_eval_count_ > 0 && !(opt_eval_first_ == 0 && opt_eval_count_ == n_seq_))
+      throw ArgError("eval_first / eval_count: a streamed batch is evaluated as a whole (load fewer sequences, or raise max_resident)");
+    set_theta_from(x);
+    st_rows_.assign((size_t)5 * n_seq_, 0.);
+  }, [&](int c0, int c1, Engine& e) {
     e.train_partial(x, n_param_in, part.data(), false, false);
     for (int t = 0; t < np; ++t) total[t] += part[t];
     e.seq_stats(st_rows_.data() + (size_t)5 * c0, c1 - c0);
     for (int t = c0; t < c1; ++t) h_plans_[t].bpp_eff = e.plans()[t - c0].bpp_eff;
-    for (int t = 0; t < 3; ++t) last_ms[t] += e.last_ms[t];
   });
   if (comm_ && reduce) {
     HIP_OK(hipMemcpyAsync(d_partial_.as<void>(), total.data(), sizeof(double) * np, hipMemcpyHostToDevice, st_));
@@ -1326,13 +1333,9 @@ void Engine::stream_train(const double* x, int n_param_in, void* partial, bool d
 }
 
 void Engine::stream_scan(const double* x, int n_param_in, elemdp_scan_out* out) {
-  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
-  if (!out) throw ArgError("scan: null output");
   const int nt = au_.n_theta();
   std::vector<double> en(nt, 0.), en_k(nt);
-  last_ms[0] = last_ms[1] = last_ms[2] = 0.;
-  stream_chunks([&](int, int c0, int c1, Engine& e) {
-    (void)c1;
+  stream_call(n_param_in, [&] { if (!out) throw ArgError("scan: null output"); }, [&](int c0, int, Engine& e) {
     const size_t so = (size_t)(h_seq_off_[c0] - h_seq_off_[0]), qo = (size_t)(h_qual_off_[c0] - h_qual_off_[0]);
     elemdp_scan_out o = *out;   // the chunk's slices of the caller's arrays (batch offsets)
     if (o.start) o.start += so;
@@ -1346,7 +1349,6 @@ void Engine::stream_scan(const double* x, int n_param_in, elemdp_scan_out* out) 
     o.en = out->en ? en_k.data() : nullptr;
     e.scan(x, n_param_in, &o);
     if (out->en) for (int t = 0; t < nt; ++t) en[t] += en_k[t];
-    for (int t = 0; t < 3; ++t) last_ms[t] += e.last_ms[t];
   });
   if (out->en) std::copy(en.begin(), en.end(), out->en);
 }
@@ -1877,8 +1879,8 @@ int Engine::prepare_scan(LinArgs& a, const ScanPos& pos) {
 }
 
 // The fused scan kernel (the log-space form) and its block count.  After the scaled-linear sum passes it reuses their table and
-// trace slots; otherwise (pipeline 3) it gets table slots with trace tables, which the train pipelines do not reuse: the caller
-// drops them (n_slots_ = 0) when done.
+// trace slots; otherwise (pipeline 3) it gets table slots with trace tables, which the train pipelines do not reuse:
+// scan_log_form drops them (n_slots_ = 0) when done.
 DpArgs Engine::log_scan_args(bool sums_on_batch, int* n_blocks) {
   const int n = n_seq_, S = au_.S();
   if (sums_on_batch) {
@@ -1893,12 +1895,59 @@ DpArgs Engine::log_scan_args(bool sums_on_batch, int* n_blocks) {
   return d;
 }
 
+void Engine::require_resident(const char* what, int n_param_in) {
+  if (n_seq_ <= 0) throw StateError(std::string(what) + " before load_batch");
+  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+}
+
+// The scaled-linear form of a scan-family call (pipeline 4): the scan's first sum pass on the groups, slots and streams of
+// Engine::scan.  fill(a) adds the call's fields to the argument record and sizes the call's per-slot scratch (n_slots_ is known
+// only behind prepare_scan); group(ak, slot0, G, Lg, Wg, stream) queues a group's work as for sweep_groups.  Waits for the device
+// and returns the number of sequences the range check flagged (their indices into *flagged when given): those are left to
+// scan_log_form.
+template <class Fill, class Group>
+int Engine::scan_sums(const ScanPos& pos, Fill fill, Group group, std::vector<int32_t>* flagged) {
+  LinArgs a;
+  const int gsz = prepare_scan(a, pos);
+  fill(a);
+  const int ns = group_streams(n_seq_ >= 128 && n_slots_ >= 128);
+  sweep_groups(a, n_seq_, h_order_.data(), d_order_.as<int32_t>(), d_plans_sorted_.as<SeqPlan>(), gsz, ns, group);
+  dbg_lap("scan sums: launches queued");
+  const int n_flagged = read_flagged(flagged);
+  dbg_lap("scan sums: device done");
+  tables_linear_ = false;
+  return n_flagged;
+}
+
+// The log-space form of a scan-family call: the fused scan kernel on the n_flagged sequences the range check of scan_sums flagged
+// (listed behind the count in d_flagged_), or -- pipeline 3, no sum passes on the batch -- on every sequence in processing order.
+// fill(d, n_blocks, n_log) sets the call's fields of the kernel's arguments, sizes the call's scratch and returns the most
+// sequences one launch may take; behind(idx, C) queues the call's work on the C sequences idx[0 .. C) of a launch behind it.
+template <class Fill, class Behind>
+void Engine::scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind behind) {
+  const int n_log = sums_on_batch ? n_flagged : n_seq_;
+  if (n_log > 0) {
+    int n_blocks;
+    DpArgs d = log_scan_args(sums_on_batch, &n_blocks);
+    const int chunk = fill(d, n_blocks, n_log);
+    const int32_t* list = sums_on_batch ? d_flagged_.as<int32_t>() + 1 : d_order_.as<int32_t>();
+    for (int c0 = 0; c0 < n_log; c0 += chunk) {
+      const int C = std::min(chunk, n_log - c0);
+      d.order = list + c0;
+      d.n_seq = C;
+      HIP_OK(hipMemsetAsync(d_counter_.as<void>(), 0, sizeof(int32_t), st_));
+      HIP_OK(launch_dp(DP_SCAN, d, std::min(n_blocks, C), st_));
+      behind(list + c0, C);
+    }
+  }
+  if (!sums_on_batch) n_slots_ = 0;   // the slots of log_scan_args are not reused by the train pipelines
+}
+
 void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
   require_device();
   DeviceGuard dg(device_);
   if (streaming_) { stream_scan(x, n_param_in, out); return; }
-  if (n_seq_ <= 0) throw StateError("scan before load_batch");
-  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+  require_resident("scan", n_param_in);
   // (--no-rss: load_batch cleared the pair mask, so every sweep reduces to the exterior chain = the profile-HMM
   // forward / backward / Viterbi of motif_model.hpp:171-206 under the scanner functors, motif_scanner.hpp:186-214)
   if (!out) throw ArgError("scan: null output");
@@ -1909,63 +1958,49 @@ void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
   DevBuf d_psi, d_rss, d_en;
   d_psi.alloc(4 * n_seqpos); d_rss.alloc(n_seqpos); d_en.alloc(8 * (size_t)n * (nt + 1));
   HIP_OK(hipEventRecord(ev_[1], st_));
+  const int stack_stride = 4 * (4 * (Lmax_ + 2));
+  auto scan_fields = [&](DpArgs& d) {   // what the fused kernel reads and writes of a scan
+    d.tr_ext = d_tr_ext_.as<TraceRec>();
+    d.trace_stack = d_tr_stack_.as<int32_t>();
+    d.trace_stack_stride = stack_stride;
+    d.sc_start = pos.start.as<double>(); d.sc_end = pos.end.as<double>(); d.sc_inner = pos.inner.as<double>();
+    d.sc_psihat = d_psi.as<int32_t>(); d.sc_rss = d_rss.as<char>();
+    d.sc_ys = pos.ys.as<int32_t>(); d.sc_ye = pos.ye.as<int32_t>(); d.sc_exist = pos.exist.as<double>(); d.sc_en = d_en.as<double>();
+  };
   // ---- K4 / K5 (the four sum passes, motif_scanner.hpp:186-202) on the scaled-linear batch pipeline
   std::vector<int32_t> flagged;
-  bool cyk_done = false;
   const bool sums_on_batch = opt_pipeline_ == 4;
   if (sums_on_batch) {
-    LinArgs a;
     dbg_lap("scan: start");
-    const int gsz = prepare_scan(a, pos);
-    dbg_lap("scan: table slots + weights");
-    // trace records of the Viterbi pass: the exterior chain's rows and the traceback stack per table slot (the band targets keep
-    // none: scan_rules.h, cyk_retrace)
-    const size_t ext = (size_t)(Lmax_ + 1) * S;
-    const int stack_stride = 4 * (4 * (Lmax_ + 2));
-    d_tr_ext_.alloc(ext * n_slots_ * sizeof(TraceRec));
-    d_tr_stack_.alloc((size_t)n_slots_ * stack_stride * sizeof(int32_t));
-    dbg_lap("scan: trace slots");
-    a.tr_ext = d_tr_ext_.as<TraceRec>();
-    a.trace_stack = d_tr_stack_.as<int32_t>(); a.trace_stack_stride = stack_stride;
-    a.sc_psihat = d_psi.as<int32_t>(); a.sc_rss = d_rss.as<char>();
     const bool cyk_on_batch = !(opt_dbg_ & 64);
-    const int ns = group_streams(n >= 128 && n_slots_ >= 128);
-    sweep_groups(a, n, h_order_.data(), d_order_.as<int32_t>(), d_plans_sorted_.as<SeqPlan>(), gsz, ns,
-                 [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, 0, st));
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, 1, st));
+    scan_sums(pos, [&](LinArgs& a) {
+      // trace records of the Viterbi pass: the exterior chain's rows and the traceback stack per table slot (the band targets keep
+      // none: scan_rules.h, cyk_retrace)
+      d_tr_ext_.alloc((size_t)(Lmax_ + 1) * S * n_slots_ * sizeof(TraceRec));
+      d_tr_stack_.alloc((size_t)n_slots_ * stack_stride * sizeof(int32_t));
+      dbg_lap("scan: trace slots");
+      a.tr_ext = d_tr_ext_.as<TraceRec>();
+      a.trace_stack = d_tr_stack_.as<int32_t>(); a.trace_stack_stride = stack_stride;
+      a.sc_psihat = d_psi.as<int32_t>(); a.sc_rss = d_rss.as<char>();
+    }, [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_END, st));
       if (cyk_on_batch) HIP_OK(launch_cyk_group(ak, G, Lg, Wg, st));   // K6 on the same table slots
-    });
-    cyk_done = cyk_on_batch;
-    dbg_lap("scan: launches queued");
-    read_flagged(&flagged);
-    dbg_lap("scan: device done");
-    tables_linear_ = false;
+    }, &flagged);
+    if (!cyk_on_batch) {   // K6 (Viterbi parse + traceback) of the whole batch on the fused kernel
+      int n_blocks;
+      DpArgs d = log_scan_args(true, &n_blocks);
+      scan_fields(d);
+      d.order = d_order_.as<int32_t>();
+      d.cyk_only = 1;
+      HIP_OK(hipMemsetAsync(d_counter_.as<void>(), 0, sizeof(int32_t), st_));
+      HIP_OK(launch_dp(DP_SCAN, d, n_blocks, st_));
+    }
   }
-  // ---- K6 (Viterbi parse + traceback) on the fused kernel; it also runs the whole schedule for the sequences the
-  // linear passes flagged (range check) and for pipeline != 4
-  int n_blocks;
-  DpArgs d = log_scan_args(sums_on_batch, &n_blocks);
-  d.order = d_order_.as<int32_t>();
-  d.tr_ext = d_tr_ext_.as<TraceRec>();
-  d.trace_stack = d_tr_stack_.as<int32_t>();
-  d.trace_stack_stride = 4 * (4 * (Lmax_ + 2));
-  d.sc_start = pos.start.as<double>(); d.sc_end = pos.end.as<double>(); d.sc_inner = pos.inner.as<double>();
-  d.sc_psihat = d_psi.as<int32_t>(); d.sc_rss = d_rss.as<char>();
-  d.sc_ys = pos.ys.as<int32_t>(); d.sc_ye = pos.ye.as<int32_t>(); d.sc_exist = pos.exist.as<double>(); d.sc_en = d_en.as<double>();
-  d.cyk_only = sums_on_batch ? 1 : 0;
-  if (!cyk_done) {
-    HIP_OK(hipMemsetAsync(d_counter_.as<void>(), 0, sizeof(int32_t), st_));
-    HIP_OK(launch_dp(DP_SCAN, d, n_blocks, st_));
-  }
-  if (!flagged.empty()) {
-    d.cyk_only = 0;
-    d.order = d_flagged_.as<int32_t>() + 1;
-    d.n_seq = (int32_t)flagged.size();
-    HIP_OK(hipMemsetAsync(d_counter_.as<void>(), 0, sizeof(int32_t), st_));
-    HIP_OK(launch_dp(DP_SCAN, d, std::min(n_blocks, (int)flagged.size()), st_));
-  }
-  if (!sums_on_batch) n_slots_ = 0;   // scan slots are not reused by the train pipelines
+  // ---- the fused kernel runs the whole schedule, K6 included, for the sequences the linear passes flagged (range check) and
+  // for pipeline != 4
+  scan_log_form(sums_on_batch, (int)flagged.size(), [&](DpArgs& d, int, int n_log) { scan_fields(d); return n_log; },
+                [](const int32_t*, int) {});
   HIP_OK(hipEventRecord(ev_[2], st_));
   HIP_OK(hipStreamSynchronize(st_));
   float ms = 0;
@@ -2011,8 +2046,7 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   if (mea && !(std::isfinite(mea->gamma) && mea->gamma > 0.)) throw ArgError("pair_mea: gamma must be finite and > 0");
   n_pairs_ = -1;
   if (streaming_) { stream_pairs(x, n_param_in, min_prob, unpaired, mea); *n_pairs = n_pairs_; return; }
-  if (n_seq_ <= 0) throw StateError("pair_posteriors before load_batch");
-  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+  require_resident("pair_posteriors", n_param_in);
   upload_params(x, lay_, false);
   const int n = n_seq_;
   const size_t n_seqpos = (size_t)h_seq_off_[n];
@@ -2061,29 +2095,25 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   }
   int n_flagged = 0;
   const bool sums_on_batch = opt_pipeline_ == 4;
-  if (sums_on_batch) {
-    // the scan's first sum pass on the same groups, slots and streams as Engine::scan
-    LinArgs a;
-    const int gsz = prepare_scan(a, pos);
-    d_pr_P_.alloc(8 * pcells * (size_t)n_slots_);
-    mea_scratch((size_t)n_slots_);
-    // the P plane's columns of the real states are 0 .. ncol-1: Automaton::flatten numbers a plane's columns in state order, and
-    // a shadow state comes last
-    int ncol = 0;
-    for (int s = 0; s < a.lay.S; ++s) {
-      const int c = ints_[a.lay.tab_cmap + ST_P * a.lay.S + s];
-      if (s == a.lay.shadow || c < 0) continue;
-      if (c != ncol) throw std::logic_error("pair_posteriors: the P plane's columns are not in state order");
-      ++ncol;
-    }
-    pa.p_cs = a.lay.tab_cs[ST_P]; pa.p_rs = a.lay.tab_rs[ST_P];
-    pa.ncol = ncol;
-    pa.band_stride = a.band_stride;
-    pa.skip_flagged = 1;
-    const int ns = group_streams(n >= 128 && n_slots_ >= 128);
-    sweep_groups(a, n, h_order_.data(), d_order_.as<int32_t>(), d_plans_sorted_.as<SeqPlan>(), gsz, ns,
-                 [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, 0, st));
+  if (sums_on_batch)
+    n_flagged = scan_sums(pos, [&](LinArgs& a) {
+      d_pr_P_.alloc(8 * pcells * (size_t)n_slots_);
+      mea_scratch((size_t)n_slots_);
+      // the P plane's columns of the real states are 0 .. ncol-1: Automaton::flatten numbers a plane's columns in state order,
+      // and a shadow state comes last
+      int ncol = 0;
+      for (int s = 0; s < a.lay.S; ++s) {
+        const int c = ints_[a.lay.tab_cmap + ST_P * a.lay.S + s];
+        if (s == a.lay.shadow || c < 0) continue;
+        if (c != ncol) throw std::logic_error("pair_posteriors: the P plane's columns are not in state order");
+        ++ncol;
+      }
+      pa.p_cs = a.lay.tab_cs[ST_P]; pa.p_rs = a.lay.tab_rs[ST_P];
+      pa.ncol = ncol;
+      pa.band_stride = a.band_stride;
+      pa.skip_flagged = 1;
+    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
       PairArgs pk = pa;
       pk.idx = ak.grp;
       pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
@@ -2092,35 +2122,21 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
       HIP_OK(launch_pair_seq(pk, G, st));
       launch_mea(pk, slot0, G, st);
     });
-    n_flagged = read_flagged();
-    tables_linear_ = false;
-  }
-  // ---- the log-space form: the sequences the range check flagged, or every sequence under pipeline 3, in chunks of at most as
-  // many sequences as the table slots hold (the P scratch is bounded by the chunk)
-  const int n_log = sums_on_batch ? n_flagged : n;
-  if (n_log > 0) {
-    int n_blocks;
-    DpArgs d = log_scan_args(sums_on_batch, &n_blocks);
+  // ---- the log-space form, in chunks of at most as many sequences as the table slots hold (the P scratch is bounded by the chunk)
+  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
     const int chunk = std::min(n_log, sums_on_batch ? n_slots_ : std::max(n_blocks, 1024));
     if (!sums_on_batch) { d_pr_P_.alloc(8 * pcells * (size_t)chunk); mea_scratch((size_t)chunk); }
     d.pair_p = d_pr_P_.as<double>();
     d.pair_stride = pcells;
-    const int32_t* list = sums_on_batch ? d_flagged_.as<int32_t>() + 1 : d_order_.as<int32_t>();
-    for (int c0 = 0; c0 < n_log; c0 += chunk) {
-      const int C = std::min(chunk, n_log - c0);
-      d.order = list + c0;
-      d.n_seq = C;
-      HIP_OK(hipMemsetAsync(d_counter_.as<void>(), 0, sizeof(int32_t), st_));
-      HIP_OK(launch_dp(DP_SCAN, d, std::min(n_blocks, C), st_));
-      PairArgs pk = pa;
-      pk.idx = list + c0;
-      pk.P = d_pr_P_.as<double>();
-      pk.skip_flagged = 0;
-      HIP_OK(launch_pair_seq(pk, C, st_));
-      launch_mea(pk, 0, C, st_);
-    }
-  }
-  if (!sums_on_batch) n_slots_ = 0;   // (as after a scan: these slots are not reused by the train pipelines)
+    return chunk;
+  }, [&](const int32_t* idx, int C) {
+    PairArgs pk = pa;
+    pk.idx = idx;
+    pk.P = d_pr_P_.as<double>();
+    pk.skip_flagged = 0;
+    HIP_OK(launch_pair_seq(pk, C, st_));
+    launch_mea(pk, 0, C, st_);
+  });
   HIP_OK(hipEventRecord(ev_[3], st_));
   // ---- the list in (sequence, i, j) order
   HIP_OK(launch_pair_prefix(d_pr_cnt_.as<int64_t>(), n, d_pr_off_.as<int64_t>(), st_));
@@ -2147,11 +2163,9 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
 }
 
 void Engine::stream_pairs(const double* x, int n_param_in, double min_prob, double* unpaired, const MeaOut* mea) {
-  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
   std::vector<int32_t> hs, hi, hj;
   std::vector<double> hp;
-  last_ms[0] = last_ms[1] = last_ms[2] = 0.;
-  stream_chunks([&](int, int c0, int, Engine& e) {
+  stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
     int64_t m = 0;
     const int64_t at = h_seq_off_[c0] - h_seq_off_[0];   // (the chunk's first position)
     MeaOut mc;
@@ -2161,7 +2175,6 @@ void Engine::stream_pairs(const double* x, int n_param_in, double min_prob, doub
     hs.resize(b + m); hi.resize(b + m); hj.resize(b + m); hp.resize(b + m);
     e.pair_list(hs.data() + b, hi.data() + b, hj.data() + b, hp.data() + b, m);
     for (size_t t = b; t < hs.size(); ++t) hs[t] += c0;   // (batch-global sequence indices)
-    for (int t = 0; t < 3; ++t) last_ms[t] += e.last_ms[t];
   });
   d_pl_seq_.upload(hs, st_); d_pl_i_.upload(hi, st_); d_pl_j_.upload(hj, st_); d_pl_p_.upload(hp, st_);
   HIP_OK(hipStreamSynchronize(st_));
@@ -2183,7 +2196,7 @@ void Engine::pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t 
 
 
 // ---- stochastic samples of derivations (sample_rules.h).  The inside sweeps of the scan's first sum pass per group
-// (launch_lin_scan_group phase 2: no outside pass) and k_sample on the group's slots right behind them, before the next group of the
+// (launch_lin_scan_group, SCAN_PASS_INSIDE: no outside pass) and k_sample on the group's slots right behind them, before the next group of the
 // stream reuses them; the log-space form in the fused scan kernel for the sequences the range check flags.
 void Engine::sample_structures(const double* x, int n_param_in, int n_samples, uint64_t seed, int64_t index_base,
                                const SampleOut& out) {
@@ -2192,8 +2205,7 @@ void Engine::sample_structures(const double* x, int n_param_in, int n_samples, u
   if (n_samples <= 0) throw ArgError("sample: n_samples must be > 0");
   if (n_node() > 255) throw ArgError("sample: more than 255 motif nodes do not fit the node bytes");
   if (streaming_) { stream_samples(x, n_param_in, n_samples, seed, index_base, out); return; }
-  if (n_seq_ <= 0) throw StateError("sample before load_batch");
-  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+  require_resident("sample", n_param_in);
   upload_params(x, lay_, false);
   const int n = n_seq_;
   const size_t n_seqpos = (size_t)h_seq_off_[n];
@@ -2212,38 +2224,26 @@ void Engine::sample_structures(const double* x, int n_param_in, int n_samples, u
   const bool sums_on_batch = opt_pipeline_ == 4;
   if (sums_on_batch) {
     ScanPos pos(n_seqpos, n);
-    LinArgs a;
-    const int gsz = prepare_scan(a, pos);
-    sa.stack_lanes = std::min(n_samples, kSampleLanes);
-    d_sm_stack_.alloc(sizeof(TraceFrame) * (size_t)n_slots_ * sa.stack_lanes * cap);
-    const int ns = group_streams(n >= 128 && n_slots_ >= 128);
-    sweep_groups(a, n, h_order_.data(), d_order_.as<int32_t>(), d_plans_sorted_.as<SeqPlan>(), gsz, ns,
-                 [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, 2, st));
+    n_flagged = scan_sums(pos, [&](LinArgs&) {
+      sa.stack_lanes = std::min(n_samples, kSampleLanes);
+      d_sm_stack_.alloc(sizeof(TraceFrame) * (size_t)n_slots_ * sa.stack_lanes * cap);
+    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_INSIDE, st));
       SampleArgs sk = sa;
       sk.stack = d_sm_stack_.as<TraceFrame>() + slot0 * sa.stack_lanes * (size_t)cap;
       HIP_OK(launch_sample(ak, sk, G, st));
     });
-    n_flagged = read_flagged();
-    tables_linear_ = false;
   }
-  // ---- the log-space form: the sequences the range check flagged, or every sequence under pipeline 3.  The fused scan kernel
-  // stops after its inside pass and draws the samples on its own slot before it takes the next sequence.
-  const int n_log = sums_on_batch ? n_flagged : n;
-  if (n_log > 0) {
-    int n_blocks;
-    DpArgs d = log_scan_args(sums_on_batch, &n_blocks);
+  // ---- the log-space form: the fused scan kernel stops after its inside pass and draws the samples on its own slot before it
+  // takes the next sequence
+  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
     const int lanes = std::min(n_samples, kThreads);
     d_sm_stack_.alloc(sizeof(TraceFrame) * (size_t)n_blocks * lanes * cap);
-    d.order = sums_on_batch ? d_flagged_.as<int32_t>() + 1 : d_order_.as<int32_t>();
-    d.n_seq = n_log;
     d.smp = sa;
     d.smp.stack = d_sm_stack_.as<TraceFrame>();
     d.smp.stack_lanes = lanes;
-    HIP_OK(hipMemsetAsync(d_counter_.as<void>(), 0, sizeof(int32_t), st_));
-    HIP_OK(launch_dp(DP_SCAN, d, std::min(n_blocks, n_log), st_));
-  }
-  if (!sums_on_batch) n_slots_ = 0;   // (as after a scan: these slots are not reused by the train pipelines)
+    return n_log;
+  }, [](const int32_t*, int) {});
   HIP_OK(hipEventRecord(ev_[2], st_));
   HIP_OK(hipStreamSynchronize(st_));
   float ms = 0;
@@ -2258,14 +2258,11 @@ void Engine::sample_structures(const double* x, int n_param_in, int n_samples, u
 
 void Engine::stream_samples(const double* x, int n_param_in, int n_samples, uint64_t seed, int64_t index_base,
                             const SampleOut& out) {
-  if (n_param_in != n_param()) throw ArgError("n_param mismatch");
-  last_ms[0] = last_ms[1] = last_ms[2] = 0.;
-  stream_chunks([&](int, int c0, int, Engine& e) {
+  stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
     const int64_t at = (h_seq_off_[c0] - h_seq_off_[0]) * (int64_t)n_samples;   // (the chunk's first sample byte)
     const SampleOut oc{out.rss ? out.rss + at : nullptr, out.node ? out.node + at : nullptr,
                        out.logp ? out.logp + (size_t)c0 * n_samples : nullptr, out.status ? out.status + c0 : nullptr};
     e.sample_structures(x, n_param_in, n_samples, seed, index_base + c0, oc);
-    for (int t = 0; t < 3; ++t) last_ms[t] += e.last_ms[t];
   });
 }
 

@@ -57,8 +57,8 @@ struct LdsLayout {
 
 enum DpKind : int { DP_TRAIN = 0, DP_BPP = 1, DP_SCAN = 2 };
 
-// ---- stochastic samples of derivations (sample_rules.h, sample_kernels.hip), on the inside tables of launch_lin_scan_group phase
-// 2, right behind it on the same slots and stream
+// ---- stochastic samples of derivations (sample_rules.h, sample_kernels.hip), on the inside tables of launch_lin_scan_group
+// (SCAN_PASS_INSIDE), right behind it on the same slots and stream
 // (launch_sample), and -- the log-space form -- in the fused scan kernel right after its inside pass (DpArgs::smp).  Batch index n (= grp[g]) with seq_base b and length L writes sample k at
 // rss / node + n_samples * b + k * L (L bytes each) and logp[n * n_samples + k]; status[n] is a SampleStatus.
 struct TraceFrame;   // (scan_rules.h)
@@ -238,10 +238,12 @@ struct LinWeightArgs {
 hipError_t launch_lin_weights(const LinWeightArgs& a, hipStream_t st);
 // one whole train evaluation of a group; `full` sweeps the pattern automaton, `compact` (schedule 1) the one-state
 // automaton of the no-motif pass over the compact tables
-// scan: phase 0 = inside + outside with start / inner posteriors and argmax start; phase 1 = the same constrained to that
-// start with end posteriors and argmax end (RNAelemScanDP::operator(), motif_scanner.hpp:186-202); phase 2 = the inside sweeps
-// and the exterior chain of phase 0 only (Z and the range check, no outside pass: the tables of the sampler, sample_rules.h)
-hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax, int phase, hipStream_t st);
+// scan: SCAN_PASS_START = inside + outside with start / inner posteriors and argmax start; SCAN_PASS_END = the same constrained
+// to that start with end posteriors and argmax end (RNAelemScanDP::operator(), motif_scanner.hpp:186-202); SCAN_PASS_INSIDE = the
+// inside sweeps and the exterior chain of SCAN_PASS_START only (Z and the range check, no outside pass: the tables of the sampler,
+// sample_rules.h)
+enum ScanPass { SCAN_PASS_START = 0, SCAN_PASS_END = 1, SCAN_PASS_INSIDE = 2 };
+hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax, ScanPass pass, hipStream_t st);
 // scan: Viterbi parse (max-plus CYK with trace records, then traceback) of a group; uses band_in / ext_in as the CYK table
 hipError_t launch_cyk_group(const LinArgs& full, int G, int Lmax, int Wmax, hipStream_t st);
 hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool first_pass_only, hipStream_t st);

@@ -2100,8 +2100,6 @@ hipError_t launch_cyk_group(const LinArgs& full, int G, int Lmax, int Wmax, hipS
   if (G <= 0) return hipSuccess;
   LinArgs a = full;
   const int S = a.lay.S, nt = a.lay.n_theta;
-  a.cpb = kBT / S;
-  if (a.cpb > ELEMDP_CPB_MAX) a.cpb = ELEMDP_CPB_MAX;
   a.wmax = Wmax;
   a.ext_ring = G <= 1024 ? 1 : 0;
   a.lmax = Lmax;
@@ -2170,72 +2168,104 @@ static void launch_k4_out(const LinArgs& a, dim3 grid, size_t lds, bool fast, bo
   else if (big) hipLaunchKernelGGL((k4_out<MODE, true>), grid, dim3(kBT), lds, st, a);
   else hipLaunchKernelGGL((k4_out<MODE, false>), grid, dim3(kBT), lds, st, a);
 }
+// (no statistics -- a timing experiment of the train, which asks for it with the blob staged only: that one variant)
+template <>
+void launch_k4_out<OUT_NONE>(const LinArgs& a, dim3 grid, size_t lds, bool, bool, hipStream_t st) {
+  hipLaunchKernelGGL((k4_out<OUT_NONE, true>), grid, dim3(kBT), lds, st, a);
+}
 
-hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax, int phase, hipStream_t st) {
-  if (G <= 0) return hipSuccess;
-  LinArgs a = full;
+// The geometry of a group's band and chain launches: the group's argument record with the launch-wide fields filled in (cpb, wmax,
+// ext_ring, lmax, fast, n_lin, the reciprocals), and the workgroup sizes and LDS bytes its kernels are launched with.
+struct GroupGeom {
+  LinArgs a;
+  bool big, fast;           // the whole blob is staged; table-driven unary phases (lin_fast.h)
+  int hd, win;              // stride of the heavy sums per cell (k4_in / k4_out: HD); cells of a workgroup's window
+  size_t lds_in, lds_out;   // k4_in, k4_out
+  bool stage_ext;           // the exterior-chain kernels stage their context
+  size_t lds_ext_in;
+  int ext_nt;               // threads of a staged exterior-chain workgroup
+};
+// scan: terminals (ari, nasi), Z = Z(ari,nasi) -- pass 0 of the reference schedule --, never the deterministic mode, and k4_out's
+// LDS with the scan's window rows; else the train's (one copy of the statistics per wave in the deterministic mode)
+static GroupGeom group_geometry(const LinArgs& full, int G, int Lmax, int Wmax, bool scan) {
+  GroupGeom g;
+  LinArgs& a = g.a;
+  a = full;
   const int S = a.lay.S, nt = a.lay.n_theta;
-  a.cpb = kBT / S;
-  if (a.cpb > ELEMDP_CPB_MAX) a.cpb = ELEMDP_CPB_MAX;
+  a.cpb = std::min(kBT / S, ELEMDP_CPB_MAX);
   a.wmax = Wmax;
   a.ext_ring = G <= 1024 ? 1 : 0;
-  a.lmax = Lmax;
-  a.schedule = 0;   // terminals (ari, nasi), Z = Z(ari,nasi): pass 0 of the reference schedule
-  a.pass = 0;
-  a.scan = 1;
-  a.det = 0;
-  const bool big = a.n_stage >= a.lay.n_ints;
-  // table-driven unary phases as in launch_lin_group (the scanner's node tests are flag words of the fast blobs)
-  const bool fast = a.fast && big && a.lay.fp_ok && !(a.dbg & 16) && a.lay.lin_total <= 2048;
+  a.lmax = Lmax;   // (read by the exterior-chain kernels only)
+  if (scan) { a.schedule = 0; a.pass = 0; a.scan = 1; a.det = 0; }
+  g.big = a.n_stage >= a.lay.n_ints;
+  // table-driven unary phases (lin_fast.h): an automaton whose lists fit the programs, the whole blob and the weight tables staged
+  // (the scanner's node tests are flag words of the fast blobs)
+  const bool fast = g.fast = a.fast && g.big && a.lay.fp_ok && !(a.dbg & 16) && a.lay.lin_total <= 2048;
   a.fast = fast ? 1 : 0;
-  if (fast) a.cpb = std::min(kBT / std::max(a.lay.n_lane, 1), ELEMDP_CPB_MAX);
+  if (fast) a.cpb = std::min(kBT / std::max(a.lay.n_lane, 1), ELEMDP_CPB_MAX);   // (states without any column take no lane)
   a.n_lin = fast ? a.lay.lin_total : kLinEth + nt;
-  const int hd = fast ? a.lay.n_lane : S;   // stride of the heavy sums per cell (k4_in / k4_out: HD)
+  const int NW = a.det ? kBT / 64 : 1;   // (copies of the statistics of k4_out: one per wave in the deterministic mode)
+  g.hd = fast ? a.lay.n_lane : S;
   set_rcps(a, fast);
-  const int win = a.cpb + Wmax + 3;
-  const size_t lds_in = block_lds(2 * a.cpb * hd + kRecIn, a.cpb, a.n_lin, win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0).total;
-  const size_t lds_out = block_lds(out_doubles(a.cpb * hd, nt, win), a.cpb, a.n_lin, win, fast ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * a.cpb, fast ? kCellOutD : 0).total;
-  if (getenv("ELEMDP_LDS_DEBUG") && phase == 0) fprintf(stderr, "scan group: G %d cpb %d S %d nt %d fast %d n_lin %d fast blob in/out %d/%d ints win %d lds k4_in %zu k4_out %zu\n", G, a.cpb, S, nt, (int)fast, a.n_lin, a.lay.fb_in_n, a.lay.fb_out_n, win, lds_in, lds_out);
-  const bool stage_ext = Lmax <= 2048 && a.nword_max <= 8192;
-  const size_t lds_ext_in = stage_ext ? (size_t)ext_lds((a.ext_ring ? ext_ring_doubles(0, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : 0;
-  const size_t lds_ext_out = stage_ext ? (size_t)ext_lds(2 * nt + 4 + (a.ext_ring ? ext_ring_doubles(2 * nt + 4, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : sizeof(double) * (2 * nt + 4);
-  const int ext_nt = (a.ext_block == kExtBlock && a.ext_ring && a.lay.n_active <= 128 && !(a.dbg & 8192)) ? 128 * kExtBlock : 128;   // (small groups: there the chain is exposed; in a large one its four-fold footprint only takes CUs from the band kernels)
-  // pass 0: unconstrained sweeps, the statistics of the scan; pass 1: the start constraint at Ys, the end posteriors
-  auto sweeps = [&](auto con, auto mode) {
-    constexpr bool CON = decltype(con)::value;
-    constexpr int MODE = decltype(mode)::value;
+  g.win = a.cpb + Wmax + 3;
+  g.lds_in = block_lds(2 * a.cpb * g.hd + kRecIn, a.cpb, a.n_lin, g.win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0).total;
+  g.lds_out = block_lds(out_doubles(a.cpb * g.hd, nt, g.win, NW, scan), a.cpb, a.n_lin, g.win, fast ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * a.cpb, fast ? kCellOutD : 0).total;
+  g.stage_ext = Lmax <= 2048 && a.nword_max <= 8192;
+  g.lds_ext_in = g.stage_ext ? (size_t)ext_lds((a.ext_ring ? ext_ring_doubles(0, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : 0;
+  g.ext_nt = (a.ext_block == kExtBlock && a.ext_ring && a.lay.n_active <= 128 && !(a.dbg & 8192)) ? 128 * kExtBlock : 128;   // (small groups: there the chain is exposed; in a large one its four-fold footprint only takes CUs from the band kernels)
+  return g;
+}
+// The inside sweep of a group: the band diagonals 0 .. Wmax (`bands`: the train has none without pairs, no_rss), then the
+// exterior chain.
+template <bool CON>
+static void inside_sweeps(GroupGeom& g, int G, int Lmax, int Wmax, bool bands, hipStream_t st) {
+  LinArgs& a = g.a;
+  if (bands)
     for (int d = 0; d <= Wmax; ++d) {
       const int ncell = Lmax - d + 1;
       if (ncell <= 0) break;
       a.d = d;
-      launch_k4_in<CON>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), lds_in, fast, big, st);
+      launch_k4_in<CON>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), g.lds_in, g.fast, g.big, st);
     }
-    if (stage_ext) hipLaunchKernelGGL((k4_in_ext<true, CON>), dim3(G), dim3(ext_nt), lds_ext_in, st, a);
-    else hipLaunchKernelGGL((k4_in_ext<false, CON>), dim3(G), dim3(128), 0, st, a);
-    if (stage_ext) hipLaunchKernelGGL((k4_out_ext<MODE, true>), dim3(G), dim3(ext_nt), lds_ext_out, st, a);
-    else hipLaunchKernelGGL((k4_out_ext<MODE, false>), dim3(G), dim3(128), lds_ext_out, st, a);
-    hipLaunchKernelGGL(k4_r7, dim3(((Lmax + 1) * (Wmax + 1) + kThreads - 1) / kThreads, G), dim3(kThreads), 0, st, a);
-    for (int d = Wmax; d >= 0; --d) {
-      const int ncell = Lmax - d + 1;
-      if (ncell <= 0) continue;
-      a.d = d;
-      launch_k4_out<MODE>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), lds_out, fast, big, st);
-    }
-  };
-  if (phase == 2) {   // inside sweeps and the exterior chain only (the sampler's tables: no outside pass, no pick)
-    for (int d = 0; d <= Wmax; ++d) {
-      const int ncell = Lmax - d + 1;
-      if (ncell <= 0) break;
-      a.d = d;
-      launch_k4_in<false>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), lds_in, fast, big, st);
-    }
-    if (stage_ext) hipLaunchKernelGGL((k4_in_ext<true, false>), dim3(G), dim3(ext_nt), lds_ext_in, st, a);
-    else hipLaunchKernelGGL((k4_in_ext<false, false>), dim3(G), dim3(128), 0, st, a);
-  } else if (phase == 0) {
-    sweeps(std::false_type{}, std::integral_constant<int, OUT_SCAN>{});
+  if (g.stage_ext) hipLaunchKernelGGL((k4_in_ext<true, CON>), dim3(G), dim3(g.ext_nt), g.lds_ext_in, st, a);
+  else hipLaunchKernelGGL((k4_in_ext<false, CON>), dim3(G), dim3(128), 0, st, a);
+}
+// The outside band sweep of a group, behind its exterior chain: rule 7, then the diagonals Wmax .. 0.
+template <int MODE>
+static void outside_bands(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t st) {
+  LinArgs& a = g.a;
+  hipLaunchKernelGGL(k4_r7, dim3(((Lmax + 1) * (Wmax + 1) + kThreads - 1) / kThreads, G), dim3(kThreads), 0, st, a);
+  for (int d = Wmax; d >= 0; --d) {
+    const int ncell = Lmax - d + 1;
+    if (ncell <= 0) continue;
+    a.d = d;
+    launch_k4_out<MODE>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), g.lds_out, g.fast, g.big, st);
+  }
+}
+// an unconstrained or constrained sum pass of the scan: inside sweep, exterior chain outwards, outside band sweep
+template <bool CON, int MODE>
+static void scan_sweeps(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t st) {
+  const LinArgs& a = g.a;
+  const int S = a.lay.S, nt = a.lay.n_theta;
+  const size_t lds_ext_out = g.stage_ext ? (size_t)ext_lds(2 * nt + 4 + (a.ext_ring ? ext_ring_doubles(2 * nt + 4, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : sizeof(double) * (2 * nt + 4);
+  inside_sweeps<CON>(g, G, Lmax, Wmax, true, st);
+  if (g.stage_ext) hipLaunchKernelGGL((k4_out_ext<MODE, true>), dim3(G), dim3(g.ext_nt), lds_ext_out, st, a);
+  else hipLaunchKernelGGL((k4_out_ext<MODE, false>), dim3(G), dim3(128), lds_ext_out, st, a);
+  outside_bands<MODE>(g, G, Lmax, Wmax, st);
+}
+
+hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax, ScanPass pass, hipStream_t st) {
+  if (G <= 0) return hipSuccess;
+  GroupGeom g = group_geometry(full, G, Lmax, Wmax, true);
+  const LinArgs& a = g.a;
+  if (getenv("ELEMDP_LDS_DEBUG") && pass == SCAN_PASS_START) fprintf(stderr, "scan group: G %d cpb %d S %d nt %d fast %d n_lin %d fast blob in/out %d/%d ints win %d lds k4_in %zu k4_out %zu\n", G, a.cpb, a.lay.S, a.lay.n_theta, (int)g.fast, a.n_lin, a.lay.fb_in_n, a.lay.fb_out_n, g.win, g.lds_in, g.lds_out);
+  if (pass == SCAN_PASS_INSIDE) {   // inside sweeps and the exterior chain only (the sampler's tables: no outside pass, no pick)
+    inside_sweeps<false>(g, G, Lmax, Wmax, true, st);
+  } else if (pass == SCAN_PASS_START) {   // unconstrained sweeps, the statistics of the scan
+    scan_sweeps<false, OUT_SCAN>(g, G, Lmax, Wmax, st);
     hipLaunchKernelGGL(k5_pick<0>, dim3((G + 63) / 64), dim3(64), 0, st, a, G);
-  } else {
-    sweeps(std::true_type{}, std::integral_constant<int, OUT_END>{});
+  } else {   // the start constraint at Ys, the end posteriors
+    scan_sweeps<true, OUT_END>(g, G, Lmax, Wmax, st);
     hipLaunchKernelGGL(k5_pick<1>, dim3((G + 63) / 64), dim3(64), 0, st, a, G);
   }
   return hipGetLastError();
@@ -2243,61 +2273,25 @@ hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax,
 
 hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool first_pass_only, hipStream_t st) {
   if (G <= 0) return hipSuccess;
-  LinArgs a = full;
+  GroupGeom g = group_geometry(full, G, Lmax, Wmax, false);
+  const LinArgs& a = g.a;
   const int S = a.lay.S, nt = a.lay.n_theta;
-  a.cpb = kBT / S;
-  if (a.cpb > ELEMDP_CPB_MAX) a.cpb = ELEMDP_CPB_MAX;
-  a.wmax = Wmax;
-  a.ext_ring = G <= 1024 ? 1 : 0;
-  const bool big = a.n_stage >= a.lay.n_ints;
-  // table-driven unary phases (lin_fast.h): the train schedule on an automaton whose lists fit the programs, the whole blob
-  // and the weight tables staged
-  const bool fast = a.fast && big && a.lay.fp_ok && !(a.dbg & 16) && a.lay.lin_total <= 2048;
-  a.fast = fast ? 1 : 0;
-  if (fast) a.cpb = std::min(kBT / std::max(a.lay.n_lane, 1), ELEMDP_CPB_MAX);   // (states without any column take no lane)
-  a.n_lin = fast ? a.lay.lin_total : kLinEth + nt;
-  const int NW = a.det ? kBT / 64 : 1;   // (copies of the statistics of k4_out: one per wave in the deterministic mode)
-  const int hd = fast ? a.lay.n_lane : S;   // stride of the heavy sums per cell (k4_in / k4_out: HD)
-  set_rcps(a, fast);
-  const int win = a.cpb + Wmax + 3;
-  const size_t lds_in = block_lds(2 * a.cpb * hd + kRecIn, a.cpb, a.n_lin, win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0).total;
-  const size_t lds_out = block_lds(out_doubles(a.cpb * hd, nt, win, NW, false), a.cpb, a.n_lin, win, fast ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * a.cpb, fast ? kCellOutD : 0).total;
-  const size_t lds_stat = sizeof(double) * (2 * nt + 4);
-  if (!a.no_rss)
-    for (int d = 0; d <= Wmax; ++d) {
-      const int ncell = Lmax - d + 1;
-      if (ncell <= 0) break;
-      a.d = d;
-      launch_k4_in<false>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), lds_in, fast, big, st);
-    }
-  a.lmax = Lmax;
-  const bool stage_ext = Lmax <= 2048 && a.nword_max <= 8192;
-  const size_t lds_ext_in = stage_ext ? (size_t)ext_lds((a.ext_ring ? ext_ring_doubles(0, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : 0;
-  const int ext_nt = (a.ext_block == kExtBlock && a.ext_ring && a.lay.n_active <= 128 && !(a.dbg & 8192)) ? 128 * kExtBlock : 128;   // (small groups: there the chain is exposed; in a large one its four-fold footprint only takes CUs from the band kernels)
-  if (stage_ext) hipLaunchKernelGGL((k4_in_ext<true, false>), dim3(G), dim3(ext_nt), lds_ext_in, st, a);
-  else hipLaunchKernelGGL((k4_in_ext<false, false>), dim3(G), dim3(128), 0, st, a);
+  inside_sweeps<false>(g, G, Lmax, Wmax, !a.no_rss, st);
   // schedule 1 (automaton with the shadow state): ONE outside sweep carries both passes -- the "has motif" terminals on the
   // pattern's states, the "no motif" terminal on the shadow of (0,0), each with its own Z and statistics (lpass).
   // schedule 0: the reference's two sweeps, (ari, nasi) then the label's mask.
   const int n_pass = (a.schedule == 1 || first_pass_only) ? 1 : 2;
-  if (getenv("ELEMDP_LDS_DEBUG")) fprintf(stderr, "lin group: G %d cpb %d fast %d n_lin %d staged ints in/out %d/%d lds k4_in %zu k4_out %zu\n", G, a.cpb, (int)fast, a.n_lin, staged_ints(a.lay, a.n_stage, 0), staged_ints(a.lay, a.n_stage, 1), lds_in, lds_out);
+  if (getenv("ELEMDP_LDS_DEBUG")) fprintf(stderr, "lin group: G %d cpb %d fast %d n_lin %d staged ints in/out %d/%d lds k4_in %zu k4_out %zu\n", G, a.cpb, (int)g.fast, a.n_lin, staged_ints(a.lay, a.n_stage, 0), staged_ints(a.lay, a.n_stage, 1), g.lds_in, g.lds_out);
   for (int pass = 0; pass < n_pass; ++pass) {
-    LinArgs b = a;
+    GroupGeom gp = g;
+    LinArgs& b = gp.a;
     b.pass = pass;
     const int n_stat = ext_stat_doubles(nt, b.det);
-    if (stage_ext) hipLaunchKernelGGL((k4_out_ext<OUT_TRAIN, true>), dim3(G), dim3(b.det ? 128 : ext_nt), (size_t)ext_lds(n_stat + (b.ext_ring ? ext_ring_doubles(n_stat, Wmax, S, kLinEth + nt, Lmax, b.nword_max, b.n_stage) : 0), kLinEth + nt, Lmax, b.nword_max, b.n_stage).total, st, b);
+    if (g.stage_ext) hipLaunchKernelGGL((k4_out_ext<OUT_TRAIN, true>), dim3(G), dim3(b.det ? 128 : g.ext_nt), (size_t)ext_lds(n_stat + (b.ext_ring ? ext_ring_doubles(n_stat, Wmax, S, kLinEth + nt, Lmax, b.nword_max, b.n_stage) : 0), kLinEth + nt, Lmax, b.nword_max, b.n_stage).total, st, b);
     else hipLaunchKernelGGL((k4_out_ext<OUT_TRAIN, false>), dim3(G), dim3(128), sizeof(double) * n_stat, st, b);
-    if (!b.no_rss) {
-      hipLaunchKernelGGL(k4_r7, dim3(((Lmax + 1) * (Wmax + 1) + kThreads - 1) / kThreads, G), dim3(kThreads), 0, st, b);
-      for (int d = Wmax; d >= 0; --d) {
-        const int ncell = Lmax - d + 1;
-        if (ncell <= 0) continue;
-        b.d = d;
-        const dim3 grid((ncell + b.cpb - 1) / b.cpb, G);
-        if (big && (b.dbg & 16)) hipLaunchKernelGGL((k4_out<OUT_NONE, true>), grid, dim3(kBT), lds_out, st, b);   // (timing experiment: no statistics)
-        else launch_k4_out<OUT_TRAIN>(b, grid, lds_out, fast, big, st);
-      }
-    }
+    if (b.no_rss) continue;
+    if (g.big && (b.dbg & 16)) outside_bands<OUT_NONE>(gp, G, Lmax, Wmax, st);   // (timing experiment: no statistics)
+    else outside_bands<OUT_TRAIN>(gp, G, Lmax, Wmax, st);
   }
   if ((a.schedule == 1 || a.lik_ratio || a.det) && !first_pass_only) hipLaunchKernelGGL(k4_combine, dim3(G), dim3(kThreads), 0, st, a, G);
   return hipGetLastError();

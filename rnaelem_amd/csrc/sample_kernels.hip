@@ -1,6 +1,6 @@
 // sample_kernels.hip -- stochastic samples of derivations under the motif model (rule in sample_rules.h).
-// k_sample runs on the inside tables of launch_lin_scan_group phase 2, right behind it on the same slots and stream (before the
-// next group of the stream reuses them): one wave per sequence, one lane per sample (samples k = lane, lane + 64, ..), each lane
+// k_sample runs on the inside tables of launch_lin_scan_group (SCAN_PASS_INSIDE), right behind it on the same slots and stream
+// (before the next group of the stream reuses them): one wave per sequence, one lane per sample (samples k = lane, lane + 64, ..), each lane
 // walking its own derivation with its stack in the slot's scratch (min(n_samples, 64) x stack_cap frames, sample_stack_cap).  A
 // sequence the range check flagged is left to the fused scan kernel (DpArgs::smp).
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
-"""Stochastic samples of derivations on the GPU: the inside-only sweep (launch_lin_scan_group phase 2) and
-k_sample, against the oracle's posteriors, the CPU driver of the same rule, other forms and runs of the same draws, and
+"""Stochastic samples of derivations on the GPU: the inside-only sweep (launch_lin_scan_group,
+SCAN_PASS_INSIDE) and k_sample, against the oracle's posteriors, the CPU driver of the same rule, other forms and runs of the same draws, and
 `scan --out-samples`."""
 import numpy as np
 import pytest
