@@ -490,6 +490,7 @@ struct Model {
   bool no_theta() const { return flags & ORC_DBG_NO_THETA; }
   bool fix_rss() const { return flags & ORC_DBG_FIX_RSS; }
   bool no_turn() const { return flags & ORC_DBG_NO_TURN; }
+  bool out_inside_loops() const { return flags & ORC_OUT_INSIDE_LOOPS; }
   int S() const { return mm.S(); }
   int M() const { return mm.M; }
   int n_theta() const { int n = 0; for (auto const& r : mm.theta) n += (int)r.size(); return n; }
@@ -535,6 +536,12 @@ struct Seq {
   vector<char> bp_ok, left_ok;
   double bpp_eff = 0;
   string fix_s;
+  /* orc_derivation_logz only: the structure constraint of fix_rss whatever the model's flags, and the node every emission at a
+     position has to carry (empty: any node) */
+  bool force_fix = false;
+  vector<int> want_node;
+  bool fixed() const { return force_fix || m->fix_rss(); }
+  bool node_ok(int pos, int h) const { return want_node.empty() || want_node[pos] == h; }
   /* plain McCaskill tables for the BPP filter */
   V pin_o, pout_o, pin, pout;
 
@@ -573,7 +580,7 @@ struct Seq {
   }
 
   template <class F> void sweep_inside(F& f);
-  template <class F> void sweep_outside(F& f);
+  template <class F> void sweep_outside(F& f, bool filter = false);
   void calc_bpp();
   double lnBPP(int i, int j) { /* :195-201 */
     if (0 <= i && j <= L && j - i <= W && (m->no_turn() ? true : (5 <= j - i)))
@@ -591,7 +598,7 @@ struct Seq {
     int total = 0, nbp = 0;
     for (int i = 0; i <= L; ++i) for (int j = model.no_turn() ? i + 1 : i + 5; j <= std::min(L, i + W); ++j)
       if ((bp_ok[i * (W + 1) + j - i] = 0 < BP[seq[i]][seq[j - 1]])) ++total;
-    if (model.fix_rss()) {
+    if (fixed()) {
       vector<int> stk;
       if ((int)fix_s.size() != L) die("fix_rss length");
       bp_ok.assign((L + 1) * (W + 1), 0);
@@ -618,7 +625,7 @@ struct Seq {
 // ---- structural sweeps (energy_model.hpp:340-547)
 template <class F> void Seq::sweep_inside(F& f) {
   const EnergyTables& ep = m->ep;
-  const bool ne = m->no_ene(), fx = m->fix_rss();
+  const bool ne = m->no_ene(), fx = fixed();
   for (int j = 0; j <= L; ++j) {
     int i0 = std::max(0, j - W);
     f.before(i0, j);
@@ -677,9 +684,9 @@ template <class F> void Seq::sweep_inside(F& f) {
   }
 }
 
-template <class F> void Seq::sweep_outside(F& f) {
+template <class F> void Seq::sweep_outside(F& f, bool filter) {   /* filter: the plain pass of the BPP filter */
   const EnergyTables& ep = m->ep;
-  const bool ne = m->no_ene(), fx = m->fix_rss();
+  const bool ne = m->no_ene(), fx = fixed();
   for (int j = L; 0 <= j; --j) {
     int i0 = std::max(0, j - W);
     if (1 <= j) f.before(i0, j - 1);
@@ -725,6 +732,7 @@ template <class F> void Seq::sweep_outside(F& f) {
              C-(k-i) >= 0 inside this loop it never terminates the scan early, i.e. l >= k+2 */
           for (int l = j; l >= k + 2; --l) {
             if (i == k && l == j) continue;
+            if (!filter && m->out_inside_loops() && (k - i) + (j - l) > C) continue;   /* (the inside sweep's loops only) */
             if (parsable(ST_P, k, l)) {
               tsc = ne ? 0. : ep.loop_energy(i - 1, j, k, l - 1, seq);
               if (fx && (string(k - i, '.') != fix_s.substr(i, k - i) || string(j - l, '.') != fix_s.substr(l, j - l))) {}
@@ -778,7 +786,7 @@ void Seq::calc_bpp() { /* :180-193 */
   pout.assign((size_t)(L + 1) * (W + 1) * 7, NINF);
   pin_o[0] = 0; pout_o[L] = 0;
   PlainInside fi{*this}; sweep_inside(fi);
-  PlainOutside fo{*this}; sweep_outside(fo);
+  PlainOutside fo{*this}; sweep_outside(fo, true);
 }
 
 // ================================================================= motif DP
@@ -833,6 +841,7 @@ template <class G> struct MotifInside {
     for (int i = j - 1; i0 <= i; --i)
       for (int sid : mm.loop_state) {
         const IS& s = mm.st(sid);
+        if (!q.node_ok(j - 1, s.r)) continue;
         double lam = m.lam(s);
         for (int s1id : mm.right[sid]) {
           const IS& s1 = mm.st(s1id);
@@ -856,6 +865,7 @@ template <class G> struct MotifInside {
             const IS& s1 = mm.st(s1id);
             int rb = (tt == TT_P_E) ? seq[j - 1] : seq[l];
             int rp = (tt == TT_P_E) ? j - 1 : l;
+            if (!q.node_ok(i, s1.l) || !q.node_ok(rp, s.r)) continue;
             double w = m.no_prf() ? 0. : m.theta2(s1.l, s.r, seq[i], rb);
             double ws = q.weight(s1.l, i) + q.weight(s.r, rp);
             double t = (s.r == s1.r && ')' == mm.node[s1.r]) ? tauL() : 0.;
@@ -865,6 +875,7 @@ template <class G> struct MotifInside {
         break;
       case TT_O_O: case TT_2_2:
         for (const IS& s : mm.state) {
+          if (!q.node_ok(l, s.r)) continue;
           double lam = m.lam(s);
           for (int s1id : mm.right[s.id]) {
             const IS& s1 = mm.st(s1id);
@@ -899,6 +910,7 @@ template <class G> struct MotifInside {
           double lam = m.lam(s);
           for (int s1id : mm.left[s.id]) {
             const IS& s1 = mm.st(s1id);
+            if (!q.node_ok(i, s1.l)) continue;
             double w = m.no_prf() ? 0. : m.theta1(s1.l, seq[i]);
             double ws = q.weight(s1.l, i);
             double t = (s.l == s1.l && '.' == mm.node[s.l]) ? tauL() : 0.;
@@ -1029,6 +1041,7 @@ template <class G> void norss_forward(DP& d, G& g) {
   for (int i = 1; i <= d.L; ++i)
     for (const IS& s : mm.state) for (int s1id : mm.right[s.id]) {
       const IS& s1 = mm.st(s1id);
+      if (!q.node_ok(i - 1, s.r)) continue;
       double w = m.theta1(s.r, q.seq[i - 1]);
       double ws = q.weight(s.r, i - 1);
       double t = (s.r == s1.r && '.' == mm.node[s.r]) ? m.log_tau : 0.;
@@ -1500,6 +1513,34 @@ int orc_train_seq(orc_model* h, const uint8_t* seq, int L, const uint8_t* qual, 
     if (ENx) flatten(enx, ENx);
     if (EHo) { EHo[0] = eho[0]; EHo[1] = eho[1]; }
     if (EHx) { EHx[0] = ehx[0]; EHx[1] = ehx[1]; }
+    return 0;
+  } catch (std::exception& e) { g_err = e.what(); return 1; }
+}
+
+int orc_derivation_logz(orc_model* h, const uint8_t* seq, int L, const uint8_t* qual, const char* dot_bracket,
+                        const uint8_t* nodes, double* logz) {
+  try {
+    const Model& m = h->m;   /* (read only: one handle per thread is enough) */
+    Seq q;
+    q.force_fix = dot_bracket != nullptr;
+    if (nodes) q.want_node.assign(nodes, nodes + L);
+    vector<int> open;
+    for (int i = 0; dot_bracket && i < L; ++i) {
+      if (dot_bracket[i] == '(') open.push_back(i);
+      else if (dot_bracket[i] == ')') {
+        if (open.empty()) die("unbalanced dot-bracket");
+        if (i + 1 - open.back() > std::min(L, m.max_pair)) die("pair wider than max_span");
+        open.pop_back();
+      } else if (dot_bracket[i] != '.') die("bad rss char");
+    }
+    if (!open.empty()) die("unbalanced dot-bracket");
+    q.prepare(m, to_vec(seq, L), dot_bracket ? string(dot_bracket, dot_bracket + L) : string());
+    q.set_ws(vector<int>(qual, qual + L + 1));
+    DP d(m, q);
+    d.init_inside(d.in_, d.in_o);
+    TrainIn fi{d};
+    run_inside(d, fi);
+    *logz = d.part_func(true, true);
     return 0;
   } catch (std::exception& e) { g_err = e.what(); return 1; }
 }

@@ -27,6 +27,11 @@ enum {
   ORC_DBG_NO_THETA = 1 << 8,
   ORC_DBG_FIX_RSS = 1 << 9,
   ORC_DBG_NO_TURN = 1 << 10,
+  /* not the reference's: the outside sweep of the motif DP (not the BPP filter's) visits the interior loops of the inside sweep only, (k-i) + (j-l) <= C.  The
+   * reference's outside bound (energy_model.hpp:529) admits every l >= k + 2, so where max_iloop binds, its outside values,
+   * and every posterior formed from them, hold loops that Z does not (a pair posterior can exceed 1).  With this flag the
+   * posteriors are the marginals of the distribution that the inside pass defines: the one the sampler draws from. */
+  ORC_OUT_INSIDE_LOOPS = 1 << 11,
 };
 
 typedef struct orc_model orc_model;
@@ -72,6 +77,22 @@ typedef struct {
 int orc_train_seq(orc_model*, const uint8_t* seq, int L, const uint8_t* qual, const char* fix_rss,
                   orc_seq_result* res, double* ENo, double* EHo, double* ENx, double* EHx,
                   double* inside_o, double* inside, double* outside, double* outside_o);
+
+/* The weight of one derivation: log Z(ari, nasi) of the inside pass of orc_train_seq restricted to one structure and one
+ * motif node per position.  dot_bracket[L] ('(' ')' '.') constrains the structure as fix_rss does under ORC_DBG_FIX_RSS,
+ * whatever the model's flags (a pair wider than max_span is an error; under ORC_NO_RSS it is ignored).  nodes[L] names the node
+ * that the emission at each position has to carry, in the numbering of psihat: 0 = 'z' (before the motif), 1 .. M-2 the
+ * pattern's nodes, M-1 = 'o' (after it); every emission with another node is left out of the sums:
+ *   L -> L        node s.r at j-1                     O -> O, 2 -> 2   node s.r at l
+ *   P -> E, P     node s1.l at i, s.r at the closing base            M -> M   node s1.l at i
+ *   --no-rss      node s.r at i-1
+ * These are the positions and nodes the sampler writes (sample_walk), so (dot_bracket, nodes) of a sample select its own
+ * derivation and *logz - Zo is the log of its probability.  nodes = NULL: no node constraint (the structure's whole weight);
+ * dot_bracket = NULL: no structure constraint (with both NULL, Zo of orc_train_seq itself from one inside pass).
+ * -inf where nothing satisfies the constraints.  Reads the model only: calls on one handle may run side by side as long as
+ * nobody sets its parameters; no other entry changes (the constraints live in the per-call sequence context). */
+int orc_derivation_logz(orc_model*, const uint8_t* seq, int L, const uint8_t* qual, const char* dot_bracket,
+                        const uint8_t* nodes, double* logz);
 
 /* Whole-batch fn / gr evaluation == RNAelemTrainer::operator() (motif_trainer.hpp:595-633) with
  * --no-shuffle, batch = everything.  Sequences concatenated; off[n_seq+1]; qual_off likewise. */

@@ -17,6 +17,7 @@ DEFAULT_PAR = os.path.join(REPO, "rnaelem_amd", "data", "turner2004.elempar")
 
 NO_RSS, NO_PRF, NO_ENE, THETA_SOFTMAX, LIK_RATIO = 1, 2, 4, 8, 16
 DBG_NO_THETA, DBG_FIX_RSS, DBG_NO_TURN = 1 << 8, 1 << 9, 1 << 10
+OUT_INSIDE_LOOPS = 1 << 11     # (not the reference's: see elem_oracle.h)
 
 _CODE = np.zeros(256, dtype=np.uint8)
 for _c, _v in (("A", 1), ("a", 1), ("C", 2), ("c", 2), ("G", 3), ("g", 3), ("U", 4), ("u", 4), ("T", 4), ("t", 4)):
@@ -75,6 +76,7 @@ def lib():
         L.orc_sum_ext_m.argtypes = [C.c_void_p, u8, C.c_int, C.c_int, C.c_int, C.c_int]
         L.orc_bpp.argtypes = [C.c_void_p, u8, C.c_int, dp, u8, dp, dp]
         L.orc_train_seq.argtypes = [C.c_void_p, u8, C.c_int, u8, C.c_char_p, C.POINTER(SeqResult)] + [dp] * 8
+        L.orc_derivation_logz.argtypes = [C.c_void_p, u8, C.c_int, u8, C.c_char_p, u8, dp]
         L.orc_train_eval.argtypes = [C.c_void_p, dp, u8, i32, u8, i32, C.c_int, C.c_int, dp, dp, dp, i32]
         L.orc_scan_seq.argtypes = [C.c_void_p, u8, C.c_int, u8, C.POINTER(ScanResult), dp, dp, dp, i32, C.c_char_p, dp]
         _lib = L
@@ -190,6 +192,23 @@ class Oracle:
             out["inside"] = ins.reshape(L + 1, res.W + 1, 7, self.S)
             out["outside"] = outs.reshape(L + 1, res.W + 1, 7, self.S)
         return out
+
+    def derivation_logz(self, seq, qual, dot_bracket, nodes=None):
+        """log Z(ari, nasi) restricted to the structure dot_bracket and, with nodes (one motif node per position, 0 = z,
+        M-1 = o, as psihat), to the emissions that carry these nodes: the weight of one derivation.  nodes None: of the
+        whole structure; dot_bracket None: no structure constraint (both None: Zo of train_seq from one inside pass)."""
+        L = len(seq)
+        assert (dot_bracket is None or len(dot_bracket) == L) and (nodes is None or len(nodes) == L)
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        qual = np.ascontiguousarray(qual, dtype=np.uint8)
+        if nodes is not None:
+            nodes = np.ascontiguousarray(nodes, dtype=np.uint8)
+        z = C.c_double()
+        rc = lib().orc_derivation_logz(self.h, _u8(seq), L, _u8(qual), None if dot_bracket is None else dot_bracket.encode(),
+                                       None if nodes is None else _u8(nodes), C.byref(z))
+        if rc:
+            raise RuntimeError(lib().orc_last_error().decode())
+        return z.value
 
     def train_eval(self, x, seqs, quals, n_threads=1):
         """fn, gr, sum_eff, n_skipped over a batch (lists of uint8 arrays)."""

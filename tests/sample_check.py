@@ -1,8 +1,12 @@
 """Shared checks of the sampler: the test-only CPU driver (tests/sample_emul.cpp), a Python mirror of the
-generator, the validity of a sample, and the sample frequencies against the oracle's posteriors."""
+generator, the validity of a sample, the sample frequencies against the oracle's posteriors, the exact log-probability of a
+sample against the oracle's weight of that one derivation (Oracle.derivation_logz), and check_sample_path, the whole check of
+one sample call of an engine."""
 import ctypes as C
 import os
 import subprocess
+import threading
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -33,16 +37,17 @@ def driver():
         L.emu_sample_uniform.argtypes = [C.c_uint64] * 4
         L.emu_set_fast.argtypes = [C.c_void_p, C.c_int]
         L.emu_sample_seq_lin.argtypes = [C.c_void_p, dp, u8, C.c_int, u8, C.c_int, C.c_uint64, C.c_uint64, C.c_char_p, u8, dp]
+        L.emu_sample_seq_lin_cap.argtypes = L.emu_sample_seq_lin.argtypes + [C.c_int]
         _lib = L
     return _lib
 
 
 class Driver:
-    def __init__(self, pattern, par="~T2004~", max_span=50, max_iloop=30, min_bpp=1e-4, tau=0.1):
-        if par == "~T2004~":      # (the engine's name of the default parameter set; the driver reads the text)
+    def __init__(self, pattern, par="~T2004~", max_span=50, max_iloop=30, min_bpp=1e-4, tau=0.1, flags=0):
+        if par in ("~T2004~", "~A2007~"):      # (the engine's names of the built-in parameter sets; the driver reads the text)
             from oracle import pyoracle as po
-            par = open(po.DEFAULT_PAR).read()
-        self.h = driver().emu_create(pattern.encode(), par.encode(), max_span, max_iloop, min_bpp, tau, 0)
+            par = po.energy_param_text(par)
+        self.h = driver().emu_create(pattern.encode(), par.encode(), max_span, max_iloop, min_bpp, tau, flags)
         if not self.h:
             raise RuntimeError(driver().emu_last_error().decode())
 
@@ -56,8 +61,9 @@ class Driver:
         except Exception:
             pass
 
-    def sample(self, x, seq, qual, n_samples, seed, index):
-        """(rss strings, node rows, logp, status) of one sequence, as Engine.sample_structures gives them"""
+    def sample(self, x, seq, qual, n_samples, seed, index, cap=None):
+        """(rss strings, node rows, logp, status) of one sequence, as Engine.sample_structures gives them; cap: walk stacks of
+        cap frames in place of sample_stack_cap(L)"""
         x = np.ascontiguousarray(x, dtype=np.float64)
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         qual = np.ascontiguousarray(qual, dtype=np.uint8)
@@ -65,13 +71,24 @@ class Driver:
         rss = C.create_string_buffer(max(L * n_samples, 1))
         node = np.zeros(max(L * n_samples, 1), dtype=np.uint8)
         logp = np.zeros(n_samples)
-        st = driver().emu_sample_seq_lin(self.h, x.ctypes.data_as(C.POINTER(C.c_double)), seq.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                         L, qual.ctypes.data_as(C.POINTER(C.c_uint8)), n_samples, seed, index, rss,
-                                         node.ctypes.data_as(C.POINTER(C.c_uint8)), logp.ctypes.data_as(C.POINTER(C.c_double)))
+        st = driver().emu_sample_seq_lin_cap(self.h, x.ctypes.data_as(C.POINTER(C.c_double)), seq.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             L, qual.ctypes.data_as(C.POINTER(C.c_uint8)), n_samples, seed, index, rss,
+                                             node.ctypes.data_as(C.POINTER(C.c_uint8)), logp.ctypes.data_as(C.POINTER(C.c_double)),
+                                             stack_cap(L) if cap is None else cap)
         if st < 0:
             raise RuntimeError(driver().emu_last_error().decode())
         raw = rss.raw.decode("ascii")
         return [raw[t * L:(t + 1) * L] for t in range(n_samples)], node[:L * n_samples].reshape(n_samples, L), logp, st
+
+
+def stack_cap(L):
+    """sample_stack_cap of sample_rules.h"""
+    return L + 4
+
+
+def driver_from_model(m):
+    """the CPU driver of a model read by io.read_model (its flags have the oracle's and the driver's bit values)"""
+    return Driver(m["pattern"], m["ene_param"], m["max_span"], m["max_iloop"], m["min_bpp"], m["tau"], m["flags"])
 
 
 M64 = (1 << 64) - 1
@@ -154,3 +171,154 @@ def check_valid(rss, nodes, kept, W, M, node_names, what=""):
                     assert r[p] in "LR", (what, t, p)
         else:
             assert np.all((h == 0) | (h == M - 1)), (what, t)
+
+
+# ---- the exact log-probability of a sample ---------------------------------------------------------------------------------------
+
+LOGZ_RTOL = 1e-10     # the project's tolerance of a log partition function (test_tables_of_single_sequences)
+
+
+def logp_atol(Zo):
+    """logp = derivation_logz - Zo: LOGZ_RTOL on both terms, each at most |Zo| in size (or 1)"""
+    return 2 * LOGZ_RTOL * max(1.0, abs(Zo))
+
+
+def dot_bracket(rss):
+    return "".join("(" if c == "L" else ")" if c == "R" else "." for c in rss)
+
+
+def oracle_map(make_oracle, fn, jobs):
+    """[fn(o, job) for job in jobs] over pair_check.n_workers() threads, one oracle handle of make_oracle() per thread (the
+    oracle's C calls release the GIL)"""
+    from tests.pair_check import n_workers
+    local = threading.local()
+
+    def one(job):
+        if not hasattr(local, "o"):
+            local.o = make_oracle()
+        return fn(local.o, job)
+
+    with ThreadPoolExecutor(max_workers=n_workers()) as ex:
+        return list(ex.map(one, jobs))
+
+
+def oracle_zo(make_oracle, seqs, quals):
+    """Zo = log Z(ari, nasi) per sequence (-inf: no parse), from one unconstrained inside pass"""
+    order = sorted(range(len(seqs)), key=lambda k: -len(seqs[k]))
+    z = oracle_map(make_oracle, lambda o, k: o.derivation_logz(seqs[k], quals[k], None, None), order)
+    out = [None] * len(seqs)
+    for k, v in zip(order, z):
+        out[k] = v
+    return out
+
+
+def pick_samples(n_samples, n_check, rng):
+    """sample indices to check: 0, 63, 64 and the last one where they exist (both lane rounds of k_sample and the seam between
+    them), the rest drawn by rng, n_check in all (or every sample)"""
+    must = sorted({t for t in (0, 63, 64, n_samples - 1) if 0 <= t < n_samples})
+    rest = [t for t in range(n_samples) if t not in must]
+    more = max(0, min(n_check - len(must), len(rest)))
+    return sorted(must + [int(t) for t in rng.choice(rest, size=more, replace=False)]) if more else must
+
+
+def check_exact_logp(make_oracle, seqs, quals, Zo, samples, picks, what=""):
+    """logp == derivation_logz(rss, nodes) - Zo within logp_atol(Zo) for the samples picks[k] of every sequence k (samples[k] =
+    (rss, nodes, logp, status); a derivation picked twice is computed once).  Returns the largest |logp - oracle| / max(1, |Zo|)."""
+    jobs, seen = [], set()
+    for k, ts in enumerate(picks):
+        rss, nodes, logp, _ = samples[k]
+        for t in ts:
+            key = (k, rss[t], nodes[t].tobytes())
+            if key not in seen:
+                seen.add(key)
+                jobs.append((k, t))
+    jobs.sort(key=lambda kt: -len(seqs[kt[0]]))
+    z = oracle_map(make_oracle, lambda o, kt: o.derivation_logz(seqs[kt[0]], quals[kt[0]], dot_bracket(samples[kt[0]][0][kt[1]]),
+                                                               samples[kt[0]][1][kt[1]]), jobs)
+    worst = 0.0
+    for (k, t), zd in zip(jobs, z):
+        lp = samples[k][2][t]
+        err = abs(lp - (zd - Zo[k]))
+        assert np.isfinite(zd) and err <= logp_atol(Zo[k]), (what, "logp", k, t, lp, zd - Zo[k], err, Zo[k])
+        worst = max(worst, err / max(1.0, abs(Zo[k])))
+    return worst
+
+
+def distinct(rss, nodes):
+    """{(rss, node bytes): [sample indices]} in order of first appearance"""
+    out = {}
+    for t, (r, h) in enumerate(zip(rss, nodes)):
+        out.setdefault((r, h.tobytes()), []).append(t)
+    return out
+
+
+def check_sample_path(eng, seqs, quals, x, make_oracle, n_samples, seed, drv=None, index_base=0, mask_eng=None, refs=None,
+                      n_check=16, log_all=False, count_flagged=True, dist="all", what=""):
+    """The whole check of one sample call of an engine with the batch loaded.
+    (a) status SAMPLED, or NO_PARSE exactly where the oracle's Zo is not finite; no NaN logp in a sampled sequence
+    (b) check_valid on every sample (each distinct one once) on the kept cells of mask_eng (default: eng)
+    (c) the CPU driver drv (the engine's model and x) draws the same samples with index index_base + k: at least 99.9 % of the
+        case's samples identical in (rss, nodes).  Left out only for sequences in the log-space form, which the driver does
+        not have: all of them with log_all (pipeline 3), else those whose scaled-linear Z leaves the double range in the driver
+        as well (NO_PARSE or a NaN logp there although the oracle has a parse); with count_flagged their number must be the
+        engine's own count, last_timing()[2]
+    (d) logp == derivation_logz - Zo within logp_atol for n_check samples per sequence (4 for L > 1000), pick_samples
+    (e) with refs (pair_check.oracle_refs): check_distribution of every sampled sequence (dist "log": of those in the log-space
+        form only)
+    Returns dict(res, Zo, same, total, share, worst, n_log)."""
+    mask_eng = mask_eng or eng
+    names = eng.describe()["node"]
+    M = len(names)
+    res = eng.sample_structures(x, n_samples, seed=seed, index_base=index_base)
+    n_flagged = int(eng.last_timing()[2])
+    assert len(res) == len(seqs)
+    Zo = [r["scan"]["ZL"] for r in refs] if refs is not None else oracle_zo(make_oracle, seqs, quals)
+    for k, (rss, nodes, logp, st) in enumerate(res):          # (a), (b)
+        L = len(seqs[k])
+        assert len(rss) == n_samples and nodes.shape == (n_samples, L) and len(logp) == n_samples, (what, k)
+        if not np.isfinite(Zo[k]):
+            assert st == eng.NO_PARSE, (what, "status", k, st)
+            continue
+        assert st == eng.SAMPLED, (what, "status", k, st, Zo[k])
+        assert np.all(np.isfinite(logp)) and np.all(logp <= logp_atol(Zo[k])), (what, "logp", k)
+        first = [ts[0] for ts in distinct(rss, nodes).values()]
+        check_valid([rss[t] for t in first], nodes[first], mask_eng.pairs(k)[0], min(L, eng.max_span), M, names, what=(what, k))
+    same = total = n_log = 0
+    differ = [[] for _ in seqs]
+    log_form = [log_all] * len(seqs)
+    if not log_all:                                           # (c)
+        assert drv is not None
+        for k, (rss, nodes, logp, st) in enumerate(res):
+            d_rss, d_nodes, d_logp, d_st = drv.sample(x, seqs[k], quals[k], n_samples, seed, index_base + k)
+            if d_st != 0 or not np.all(np.isfinite(d_logp)):
+                assert d_st in (0, 1), (what, "driver refused", k)
+                n_log += 1                                    # (the scaled-linear tables left the double range, or no parse)
+                log_form[k] = True
+                continue
+            assert st == eng.SAMPLED, (what, k)
+            total += n_samples
+            for t in range(n_samples):
+                if rss[t] == d_rss[t] and np.array_equal(nodes[t], d_nodes[t]):
+                    same += 1
+                else:
+                    differ[k].append(t)
+        if count_flagged:
+            assert n_log == n_flagged, (what, "sequences in the log-space form", n_log, n_flagged)
+        assert same >= 0.999 * total, (what, "draws against the CPU driver", same, total)
+    rng = np.random.default_rng(seed + 1000003 * n_samples)   # (d)
+    picks = []
+    for k, (rss, nodes, logp, st) in enumerate(res):
+        if st != eng.SAMPLED:
+            picks.append([])
+            continue
+        ts = pick_samples(n_samples, 4 if len(seqs[k]) > 1000 else n_check, rng)
+        picks.append(sorted(set(ts) | set(differ[k])))        # (every sample that differs from the driver's has to be exact)
+    worst = check_exact_logp(make_oracle, seqs, quals, Zo, res, picks, what=what)
+    if refs is not None:                                      # (e)
+        for k, ((rss, nodes, logp, st), ref) in enumerate(zip(res, refs)):
+            if st == eng.SAMPLED and (dist == "all" or log_form[k]):
+                check_distribution(rss, nodes, ref["P"], ref["scan"], M, what=(what, k))
+    share = same / total if total else float("nan")
+    print("sample case %s: %d sequences, driver share %s (%d of %d), log form %d, max |logp - oracle| / max(1, |Zo|) = %.3g"
+          % (what, len(seqs), "%.5f" % share if total else "n/a", same, total, n_log, worst))
+    return dict(res=res, Zo=Zo, same=same, total=total, share=share, worst=worst, n_log=n_log)

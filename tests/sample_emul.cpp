@@ -10,10 +10,11 @@ double emu_sample_uniform(uint64_t seed, uint64_t index, uint64_t sample, uint64
   return elemdp::sample_uniform(seed, index, sample, draw);
 }
 
-// n_samples derivations of one sequence: rss / node n_samples x L bytes, logp n_samples values; returns the SampleStatus, or -1
-// with emu_last_error on a failure of the driver itself
-int emu_sample_seq_lin(void* h, const double* x, const uint8_t* seq, int L, const uint8_t* qual, int n_samples, uint64_t seed,
-                       uint64_t index, char* rss, uint8_t* node, double* logp) {
+// n_samples derivations of one sequence with walk stacks of cap frames: rss / node n_samples x L bytes, logp n_samples values;
+// a failed walk leaves its sample blank with node 0 and a NaN log-probability, as sample_one does on the device.  Returns the
+// SampleStatus, or -1 with emu_last_error on a failure of the driver itself
+int emu_sample_seq_lin_cap(void* h, const double* x, const uint8_t* seq, int L, const uint8_t* qual, int n_samples, uint64_t seed,
+                           uint64_t index, char* rss, uint8_t* node, double* logp, int cap) {
   try {
     Emu& E = *(Emu*)h;
     const int nt = E.au->n_theta();
@@ -56,7 +57,8 @@ int emu_sample_seq_lin(void* h, const double* x, const uint8_t* seq, int L, cons
     for (int j = 1; j <= L; ++j)
       for (int s = 0; s < S; ++s) lin_inside_ext_target<false>(m, q, in.v, j, s, c0);
     const LinSampleTab T{in.v};
-    std::vector<TraceFrame> stack(sample_stack_cap(L));
+    if (cap < 1) throw std::runtime_error("cap < 1");
+    std::vector<TraceFrame> stack(cap + 3);   // (a step pushes up to three frames past a bound it has checked)
     int status = SAMPLE_OK;
     for (int k = 0; k < n_samples; ++k) {
       char* r = rss + (size_t)k * L;
@@ -64,12 +66,23 @@ int emu_sample_seq_lin(void* h, const double* x, const uint8_t* seq, int L, cons
       std::fill(r, r + L, ' ');
       std::fill(nd, nd + L, (uint8_t)0);
       double lp = std::numeric_limits<double>::quiet_NaN();
-      const int st = sample_walk(m, q, T, seed, index, (uint64_t)k, nd, r, &lp, stack.data(), (int)stack.size());
-      logp[k] = st == SAMPLE_OK ? lp : std::numeric_limits<double>::quiet_NaN();
+      const int st = sample_walk(m, q, T, seed, index, (uint64_t)k, nd, r, &lp, stack.data(), cap);
+      if (st != SAMPLE_OK) {
+        lp = std::numeric_limits<double>::quiet_NaN();
+        std::fill(r, r + L, ' ');
+        std::fill(nd, nd + L, (uint8_t)0);
+      }
+      logp[k] = lp;
       status = std::max(status, st);
     }
     return status;
   } catch (std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// the same with the stack bound of the product, sample_stack_cap(L)
+int emu_sample_seq_lin(void* h, const double* x, const uint8_t* seq, int L, const uint8_t* qual, int n_samples, uint64_t seed,
+                       uint64_t index, char* rss, uint8_t* node, double* logp) {
+  return emu_sample_seq_lin_cap(h, x, seq, L, qual, n_samples, seed, index, rss, node, logp, elemdp::sample_stack_cap(L));
 }
 
 }  // extern "C"
