@@ -158,6 +158,12 @@ int elemdp_comm_destroy(elemdp_handle* h);
 /* per-sequence diagnostics of the last train evaluation: 5 doubles per sequence
  * [Z(ari,nasi), Z(ari), Z(nasi), f_n, skipped] (motif_trainer.hpp:108-112, 204-227) */
 int elemdp_train_seq_stats(elemdp_handle* h, double* out, int32_t n_seq);
+/* per-sequence expected counts of the last train evaluation: 2 * n_theta + 4 doubles per sequence
+ * [ENo[n_theta], ENx[n_theta], EHo[2], EHx[2]] (the terms of the reference's gradient, motif_trainer.hpp:229-249); all 0
+ * for a skipped sequence, and for the sequences outside a ranged evaluation whatever the evaluation before left.  A resident
+ * batch only: ELEMDP_ESTATE while the handle streams its batch, before any train evaluation of the loaded batch, and after
+ * a scan-family call (which writes rows of its own). */
+int elemdp_train_seq_counts(elemdp_handle* h, double* out, int32_t n_seq);
 /* debug: tables of ONE sequence after a train evaluation of a batch holding only that sequence:
  * inside_o/outside_o [(L+1)*S]; inside/outside [(L+1)*(W+1)*7*S] in the reference's index order
  * [i][d][e][s] (motif_trainer.hpp:62-65); outside = the first (full-terminal) pass.  Any may be NULL.

@@ -23,7 +23,7 @@ DBG_FIX_RSS, DBG_NO_TURN = 1 << 9, 1 << 10
 SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "elemdp_create", "elemdp_destroy",
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_train_eval",
-           "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats",
+           "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
            "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
@@ -79,6 +79,7 @@ def load_library():
         L.elemdp_train_finish.argtypes = [hp, dp, dp, dp, dp, i32]
         L.elemdp_set_finish_params.argtypes = [hp, dp, C.c_int32]
         L.elemdp_train_seq_stats.argtypes = [hp, dp, C.c_int32]
+        L.elemdp_train_seq_counts.argtypes = [hp, dp, C.c_int32]
         L.elemdp_debug_tables.argtypes = [hp] + [dp] * 7
         L.elemdp_scan.argtypes = [hp, dp, C.c_int32, C.POINTER(ScanOut)]
         L.elemdp_pair_posteriors.argtypes = [hp, dp, C.c_int32, C.c_double, C.POINTER(C.c_int64), dp]
@@ -255,6 +256,15 @@ class Engine:
         out = np.zeros((self.n_seq, 5))
         self._check(self._lib.elemdp_train_seq_stats(self._h, _dp(out), self.n_seq))
         return out
+
+    def seq_counts(self):
+        """Per sequence the expected counts of the last train_eval / train_partial: dict of ENo, ENx (n_seq, n_theta) and
+        EHo, EHx (n_seq, 2), the reference's (o, x) terms in every mode (schedule 0 / 1, LIK_RATIO, deterministic, log space).
+        Resident batches only (ESTATE while streaming, before an evaluation and after a scan-family call)."""
+        nt = self.n_param - 2
+        out = np.zeros((self.n_seq, 2 * nt + 4))
+        self._check(self._lib.elemdp_train_seq_counts(self._h, _dp(out), self.n_seq))
+        return dict(ENo=out[:, :nt], ENx=out[:, nt:2 * nt], EHo=out[:, 2 * nt:2 * nt + 2], EHx=out[:, 2 * nt + 2:])
 
     def debug_tables(self):
         assert self.n_seq == 1

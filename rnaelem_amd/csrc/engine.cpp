@@ -259,6 +259,7 @@ class Engine {
   int n_seq() const { return n_seq_; }
   const std::vector<SeqPlan>& plans() const { return h_plans_; }
   void seq_stats(double* out, int n);
+  void seq_counts(double* out, int n);
   bool bpp_eff_known() const {
     if (!streaming_) return true;
     for (char c : st_have_eff_) if (!c) return false;
@@ -460,6 +461,7 @@ class Engine {
   std::vector<uint8_t> h_seq_;           // base codes of the batch (table export)
   HostBuf hb_ws_, hb_ews_, hb_unp_;      // staging of load_batch
   int64_t n_cells_total_ = 0;
+  bool train_rows_ = false;              // d_seq_out_ holds the rows of a train evaluation (seq_counts)
   bool tables_linear_ = false;           // the resident tables hold scaled linear values (debug_tables converts)
   int n_flagged_last_ = 0;
   DevBuf d_a_in_, d_a_out_;   // pair tables of the factorised rule 2 (lin_rules.h), per slot [W+1][Lmax+1][n_ap]
@@ -880,6 +882,7 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   n_seq_ = 0;
   n_pairs_ = -1;
   streaming_ = false;
+  train_rows_ = false;
   BatchShape shape = check_batch(seq, off, qual, qoff, fix, n);
   h_seq_off_.assign(off, off + n + 1);
   h_qual_off_.assign(qoff, qoff + n + 1);
@@ -1664,7 +1667,9 @@ void Engine::train_partial(const double* x, int n_param_in, void* partial, bool 
   last_x_.assign(x, x + n_param_in);
   upload_params(x, lay_, false);
   if (n_seq_ > 0) {
+    train_rows_ = false;
     run_train();
+    train_rows_ = true;
   } else {   // a rank without a share of the batch: zeros into the all-reduce
     HIP_OK(hipMemsetAsync(d_partial_.as<void>(), 0, sizeof(double) * partial_len(), st_));
     HIP_OK(hipEventRecord(ev_[1], st_));
@@ -1727,6 +1732,19 @@ void Engine::seq_stats(double* out, int n) {
   HIP_OK(hipMemcpy(h.data(), d_seq_out_.as<void>(), sizeof(double) * h.size(), hipMemcpyDeviceToHost));
   for (int k = 0; k < n; ++k)
     for (int c = 0; c < 5; ++c) out[5 * k + c] = h[(size_t)k * out_stride_ + c];
+}
+
+// The count columns of the rows as the last train evaluation left them: ENo, ENx [n_theta each], EHo, EHx [2 each].
+void Engine::seq_counts(double* out, int n) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (streaming_) throw StateError("seq_counts needs a resident batch (the handle streams this one in chunks)");
+  if (n_seq_ <= 0 || !train_rows_) throw StateError("seq_counts before train_eval");
+  if (n != n_seq_) throw ArgError("seq_counts: n_seq mismatch");
+  const size_t nc = (size_t)out_stride_ - 6;
+  std::vector<double> h((size_t)out_stride_ * n);
+  HIP_OK(hipMemcpy(h.data(), d_seq_out_.as<void>(), sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+  for (int k = 0; k < n; ++k) std::copy(h.begin() + (size_t)k * out_stride_ + 6, h.begin() + (size_t)(k + 1) * out_stride_, out + (size_t)k * nc);
 }
 
 void Engine::debug_tables(double* inside, double* outside, double* inside_o, double* outside_o, double* ENo, double* ENx,
@@ -1898,6 +1916,7 @@ DpArgs Engine::log_scan_args(bool sums_on_batch, int* n_blocks) {
 void Engine::require_resident(const char* what, int n_param_in) {
   if (n_seq_ <= 0) throw StateError(std::string(what) + " before load_batch");
   if (n_param_in != n_param()) throw ArgError("n_param mismatch");
+  train_rows_ = false;   // (the scan family writes rows of its own into d_seq_out_)
 }
 
 // The scaled-linear form of a scan-family call (pipeline 4): the scan's first sum pass on the groups, slots and streams of
@@ -2489,6 +2508,12 @@ int elemdp_train_seq_stats(elemdp_handle* h, double* out, int32_t n_seq) {
   ELEMDP_TRY
   if (!h || !out) throw elemdp::ArgError("elemdp_train_seq_stats: null argument");
   h->e->seq_stats(out, n_seq);
+  ELEMDP_CATCH
+}
+int elemdp_train_seq_counts(elemdp_handle* h, double* out, int32_t n_seq) {
+  ELEMDP_TRY
+  if (!h || !out) throw elemdp::ArgError("elemdp_train_seq_counts: null argument");
+  h->e->seq_counts(out, n_seq);
   ELEMDP_CATCH
 }
 int elemdp_debug_tables(elemdp_handle* h, double* inside, double* outside, double* inside_o, double* outside_o,

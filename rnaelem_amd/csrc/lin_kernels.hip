@@ -2150,23 +2150,35 @@ static void set_rcps(LinArgs& a, bool fast) {
 // One band-kernel launch per diagonal, the variant chosen the same way by the scan and the train: table-driven with the longest
 // pair list at most 2 -- asking for eight k4_in / six k4_out waves per SIMD where that many workgroups fit a CU's LDS (the
 // 64-register k4_in, the 80-register k4_out) --, table-driven, the blob staged, generic.
+enum K4Form { K4_FP2_WAVES, K4_FP2, K4_FAST, K4_STAGED, K4_GENERIC };
+static const char* const kK4FormName[] = {"fp2-waves", "fp2", "fast", "staged", "generic"};   // (the ELEMDP_LDS_DEBUG line)
+// waves: the workgroups per CU the first variant asks for (8: k4_in, 6: k4_out)
+static K4Form k4_form(const LinArgs& a, size_t lds, int waves, bool fast, bool big) {
+  const bool fp2 = a.lay.fp_max_p <= 2;
+  if (fast && fp2 && lds * waves <= 160 * 1024) return K4_FP2_WAVES;
+  if (fast && fp2) return K4_FP2;
+  if (fast) return K4_FAST;
+  return big ? K4_STAGED : K4_GENERIC;
+}
 template <bool CON>
 static void launch_k4_in(const LinArgs& a, dim3 grid, size_t lds, bool fast, bool big, hipStream_t st) {
-  const bool fp2 = a.lay.fp_max_p <= 2;
-  if (fast && fp2 && lds * 8 <= 160 * 1024) hipLaunchKernelGGL((k4_in<true, CON, true, 2, true>), grid, dim3(kBT), lds, st, a);
-  else if (fast && fp2) hipLaunchKernelGGL((k4_in<true, CON, true, 2>), grid, dim3(kBT), lds, st, a);
-  else if (fast) hipLaunchKernelGGL((k4_in<true, CON, true>), grid, dim3(kBT), lds, st, a);
-  else if (big) hipLaunchKernelGGL((k4_in<true, CON>), grid, dim3(kBT), lds, st, a);
-  else hipLaunchKernelGGL((k4_in<false, CON>), grid, dim3(kBT), lds, st, a);
+  switch (k4_form(a, lds, 8, fast, big)) {
+    case K4_FP2_WAVES: hipLaunchKernelGGL((k4_in<true, CON, true, 2, true>), grid, dim3(kBT), lds, st, a); break;
+    case K4_FP2: hipLaunchKernelGGL((k4_in<true, CON, true, 2>), grid, dim3(kBT), lds, st, a); break;
+    case K4_FAST: hipLaunchKernelGGL((k4_in<true, CON, true>), grid, dim3(kBT), lds, st, a); break;
+    case K4_STAGED: hipLaunchKernelGGL((k4_in<true, CON>), grid, dim3(kBT), lds, st, a); break;
+    case K4_GENERIC: hipLaunchKernelGGL((k4_in<false, CON>), grid, dim3(kBT), lds, st, a); break;
+  }
 }
 template <int MODE>
 static void launch_k4_out(const LinArgs& a, dim3 grid, size_t lds, bool fast, bool big, hipStream_t st) {
-  const bool fp2 = a.lay.fp_max_p <= 2;
-  if (fast && fp2 && lds * 6 <= 160 * 1024) hipLaunchKernelGGL((k4_out<MODE, true, true, 2, true>), grid, dim3(kBT), lds, st, a);
-  else if (fast && fp2) hipLaunchKernelGGL((k4_out<MODE, true, true, 2>), grid, dim3(kBT), lds, st, a);
-  else if (fast) hipLaunchKernelGGL((k4_out<MODE, true, true>), grid, dim3(kBT), lds, st, a);
-  else if (big) hipLaunchKernelGGL((k4_out<MODE, true>), grid, dim3(kBT), lds, st, a);
-  else hipLaunchKernelGGL((k4_out<MODE, false>), grid, dim3(kBT), lds, st, a);
+  switch (k4_form(a, lds, 6, fast, big)) {
+    case K4_FP2_WAVES: hipLaunchKernelGGL((k4_out<MODE, true, true, 2, true>), grid, dim3(kBT), lds, st, a); break;
+    case K4_FP2: hipLaunchKernelGGL((k4_out<MODE, true, true, 2>), grid, dim3(kBT), lds, st, a); break;
+    case K4_FAST: hipLaunchKernelGGL((k4_out<MODE, true, true>), grid, dim3(kBT), lds, st, a); break;
+    case K4_STAGED: hipLaunchKernelGGL((k4_out<MODE, true>), grid, dim3(kBT), lds, st, a); break;
+    case K4_GENERIC: hipLaunchKernelGGL((k4_out<MODE, false>), grid, dim3(kBT), lds, st, a); break;
+  }
 }
 // (no statistics -- a timing experiment of the train, which asks for it with the blob staged only: that one variant)
 template <>
@@ -2281,7 +2293,13 @@ hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool
   // pattern's states, the "no motif" terminal on the shadow of (0,0), each with its own Z and statistics (lpass).
   // schedule 0: the reference's two sweeps, (ari, nasi) then the label's mask.
   const int n_pass = (a.schedule == 1 || first_pass_only) ? 1 : 2;
-  if (getenv("ELEMDP_LDS_DEBUG")) fprintf(stderr, "lin group: G %d cpb %d fast %d n_lin %d staged ints in/out %d/%d lds k4_in %zu k4_out %zu\n", G, a.cpb, (int)g.fast, a.n_lin, staged_ints(a.lay, a.n_stage, 0), staged_ints(a.lay, a.n_stage, 1), g.lds_in, g.lds_out);
+  const bool combine = (a.schedule == 1 || a.lik_ratio || a.det) && !first_pass_only;
+  if (getenv("ELEMDP_LDS_DEBUG")) {
+    const bool stats = !(g.big && (a.dbg & 16));   // (else the timing experiment's OUT_NONE variant)
+    fprintf(stderr, "lin group: G %d cpb %d fast %d n_lin %d staged ints in/out %d/%d lds k4_in %zu k4_out %zu fp_max_p %d forms k4_in %s k4_out %s stage_ext %d ext_nt %d ext_ring %d n_pass %d combine %d\n", G, a.cpb, (int)g.fast, a.n_lin, staged_ints(a.lay, a.n_stage, 0), staged_ints(a.lay, a.n_stage, 1), g.lds_in, g.lds_out, a.lay.fp_max_p,
+            a.no_rss ? "none" : kK4FormName[k4_form(a, g.lds_in, 8, g.fast, g.big)], a.no_rss ? "none" : !stats ? "nostat" : kK4FormName[k4_form(a, g.lds_out, 6, g.fast, g.big)],
+            (int)g.stage_ext, g.stage_ext ? g.ext_nt : 128, a.ext_ring, n_pass, (int)combine);
+  }
   for (int pass = 0; pass < n_pass; ++pass) {
     GroupGeom gp = g;
     LinArgs& b = gp.a;
@@ -2293,7 +2311,7 @@ hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool
     if (g.big && (b.dbg & 16)) outside_bands<OUT_NONE>(gp, G, Lmax, Wmax, st);   // (timing experiment: no statistics)
     else outside_bands<OUT_TRAIN>(gp, G, Lmax, Wmax, st);
   }
-  if ((a.schedule == 1 || a.lik_ratio || a.det) && !first_pass_only) hipLaunchKernelGGL(k4_combine, dim3(G), dim3(kThreads), 0, st, a, G);
+  if (combine) hipLaunchKernelGGL(k4_combine, dim3(G), dim3(kThreads), 0, st, a, G);
   return hipGetLastError();
 }
 

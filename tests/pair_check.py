@@ -130,14 +130,17 @@ def check_against_mirror(eng, seqs, x, gammas=(0.5, 1.0, 4.0), mask_eng=None):
 
 
 def check_scan(eng, x, seqs, refs):
-    """scan records against the oracle's scan: start in log space and exist_prob; where the oracle has a parse with the motif
-    (exist_prob > 0) also end in log space and Ys, Ye, rss and psihat exact (where it has none, every start posterior is -inf,
-    the argmax is a tie and the oracle's end posteriors are 0 / 0)"""
-    recs, _ = eng.scan(x)
+    """scan records against the oracle's scan: start and inner in log space and exist_prob; where the oracle has a parse with the
+    motif (exist_prob > 0) also end in log space and Ys, Ye, rss and psihat exact (where it has none, every start and inner
+    posterior is -inf, the argmax is a tie and the oracle's end posteriors are 0 / 0); the batch's expected counts E[N] against
+    the sum of the oracle's per sequence"""
+    recs, en = eng.scan(x)
     assert len(recs) == len(seqs)
+    np.testing.assert_allclose(en, np.sum([ref["scan"]["EN"] for ref in refs], axis=0), rtol=1e-8, atol=1e-10, err_msg="E[N] of the scan")
     for k, (r, ref) in enumerate(zip(recs, refs)):
         a = ref["scan"]
         assert_log_close(r["start"], a["start"], rtol=1e-8, atol=1e-6, what="start %d" % k)
+        assert_log_close(r["inner"], a["inner"], rtol=1e-8, atol=1e-6, what="inner %d" % k)
         assert r["exist_prob"] == pytest.approx(a["exist_prob"], rel=1e-8), k
         if a["exist_prob"] == 0.0:
             continue
