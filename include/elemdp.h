@@ -102,6 +102,8 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *                       "slots": table slots; "two_streams": retired with pipeline 2, accepted and ignored
  *     "keep_lnbpp"      keep ln BPP of the filter for elemdp_batch_pairs; "bpp_log": 1 = log-space BPP filter for every band
  *     "sorted_plan"     1: role lists of the plan sorted per cell (reproducible summation order of the log-space pipeline)
+ *     "useful_mask"     1 (default): the train sweeps skip the table entries no complete parse reaches (elemdp_useful_mask);
+ *                       0: they compute every entry -- kept as the A/B switch and as the tests' reference
  *   measurement / tests
  *     "profile"         in-kernel phase clocks for elemdp_debug_profile; "dbg": switch phases off (results invalid);
  *     "poison"          1: every table is filled with NaN before an evaluation (an unmasked read of an entry nobody stored shows) */
@@ -120,6 +122,15 @@ int elemdp_load_batch(elemdp_handle* h, const uint8_t* seq_codes, const int32_t*
 int elemdp_batch_bpp_eff(elemdp_handle* h, double* bpp_eff, int32_t n_seq);
 /* kept[(L+1)*(W+1)] (index i*(W+1)+d) of one sequence after the filter; lnbpp may be NULL */
 int elemdp_batch_pairs(elemdp_handle* h, int32_t seq_index, uint8_t* kept, double* lnbpp, int32_t cap);
+/* Debug: the usefulness mask of one sequence of the resident plan, mask[(W+1)*(L+1)] (index d*(L+1)+i, like the tables).  Bits:
+ * 1 P, 2 E, 4 M, 8 B, 16 A (pair entries of the factorised rule 2), 32 plane 1, 64 plane 2, 128 L -- set where a complete parse
+ * can pass through the entry with every weight taken as positive (a superset of that set). */
+int elemdp_useful_mask(elemdp_handle* h, int32_t seq_index, uint8_t* mask, int32_t cap);
+/* Host only: the same mask by the same rules on the CPU from the kept pairs of one sequence, kept[(L+1)*(W+1)] (index
+ * i*(W+1)+d, as elemdp_batch_pairs gives them); W = min(L, max_span); unp: L flags "may be unpaired" or NULL (all may);
+ * flags: ELEMDP_NO_ENERGY and ELEMDP_DBG_NO_TURN are looked at. */
+int elemdp_useful_mask_host(const uint8_t* kept, const uint8_t* unp, int32_t L, int32_t W, int32_t max_iloop, int32_t flags,
+                            uint8_t* mask);
 
 /* == RNAelemTrainer::operator()(x, fn, gr) over the whole resident batch with --no-shuffle
  * (motif_trainer.hpp:595-633 + RNAelemTrainDP::operator() :124-272).  fn/gr are the UNREGULARISED

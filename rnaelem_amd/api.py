@@ -22,7 +22,7 @@ DBG_FIX_RSS, DBG_NO_TURN = 1 << 9, 1 << 10
 # every symbol include/elemdp.h declares
 SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "elemdp_create", "elemdp_destroy",
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
-           "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_train_eval",
+           "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
            "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
@@ -74,6 +74,8 @@ def load_library():
         L.elemdp_load_batch.argtypes = [hp, u8, i32, u8, i32, C.c_char_p, C.c_int32]
         L.elemdp_batch_bpp_eff.argtypes = [hp, dp, C.c_int32]
         L.elemdp_batch_pairs.argtypes = [hp, C.c_int32, u8, dp, C.c_int32]
+        L.elemdp_useful_mask.argtypes = [hp, C.c_int32, u8, C.c_int32]
+        L.elemdp_useful_mask_host.argtypes = [u8, u8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, u8]
         L.elemdp_train_eval.argtypes = [hp, dp, C.c_int32, dp, dp, dp, i32]
         L.elemdp_train_partial.argtypes = [hp, dp, C.c_int32, C.c_void_p, C.c_int32]
         L.elemdp_train_finish.argtypes = [hp, dp, dp, dp, dp, i32]
@@ -125,6 +127,23 @@ def kmer_shuffle(codes, k, iter_cnt):
     rc = load_library().elemdp_kmer_shuffle(_u8(codes), len(codes), int(k), int(iter_cnt), _u8(out))
     if rc:
         raise ElemdpError(rc, "kmer_shuffle")
+    return out
+
+
+# planes of the usefulness mask (elemdp_useful_mask): bit of each plane
+USEFUL_BITS = dict(P=1, E=2, M=4, B=8, A=16, S1=32, S2=64, L=128)
+
+
+def useful_mask_host(kept, max_iloop=30, flags=0, unp=None):
+    """Usefulness mask of one sequence on the CPU from its kept pairs, kept[(L+1), (W+1)] -> uint8 [(W+1), (L+1)] of
+    USEFUL_BITS (host; elemdp_useful_mask_host)."""
+    kept = np.ascontiguousarray(kept, dtype=np.uint8)
+    L, W = kept.shape[0] - 1, kept.shape[1] - 1
+    out = np.zeros((W + 1, L + 1), dtype=np.uint8)
+    u = None if unp is None else _u8(np.ascontiguousarray(unp, dtype=np.uint8))
+    rc = load_library().elemdp_useful_mask_host(_u8(kept), u, L, W, int(max_iloop), int(flags), _u8(out))
+    if rc:
+        raise ElemdpError(rc, "useful_mask_host")
     return out
 
 
@@ -202,6 +221,14 @@ class Engine:
         ln = np.full((L + 1, W + 1), -np.inf) if with_lnbpp else None
         self._check(self._lib.elemdp_batch_pairs(self._h, index, _u8(kept), _dp(ln), kept.size))
         return kept, ln
+
+    def useful_mask(self, index):
+        """uint8 [(W+1), (L+1)] of USEFUL_BITS: the entries of sequence `index` the train sweeps compute."""
+        L = int(self._off[index + 1] - self._off[index])
+        W = min(L, self.max_span)
+        out = np.zeros((W + 1, L + 1), dtype=np.uint8)
+        self._check(self._lib.elemdp_useful_mask(self._h, index, _u8(out), out.size))
+        return out
 
     # ---- training: == RNAelemTrainer::operator()
     def train_eval(self, x):

@@ -163,6 +163,9 @@ struct SeqView {
   const LoopItem* items_inner = nullptr; const LoopItem* items_left = nullptr; const LoopItem* items_right = nullptr;
   // the pair mask indexed by (end j, span): bit j * (W+1) + span <=> pair cell (j - span, span)  (k_mask_by_end)
   const uint32_t* okbits_end = nullptr;
+  // usefulness mask of the train sweeps (plan_rules.h: UB_* bits per cell, [d][i] like the tables); null: every entry is useful
+  const uint8_t* useful = nullptr;
+  ELEMDP_HD int ubits(int i, int d) const { return useful ? (int)useful[d * (L + 1) + i] : 0xff; }
 
   ELEMDP_HD int cell(int i, int d) const { return i * (W + 1) + d; }
   ELEMDP_HD bool pair_ok(int i, int d) const {  // is_parsable<ST_P>

@@ -203,6 +203,11 @@ struct PlanSet {
   std::vector<SeqPlan> h;
   DevBuf d_plans, dmin, e_stack, e_ext, e_ml, e_close, e_hp, off_outer, off_inner, off_left, off_right, cursor, items,
       item_in, idx_inner, idx_left, idx_right, items_inner, items_left, items_right;
+  // usefulness mask of the train sweeps (PlanArrays::useful), built by the first train evaluation that wants it
+  // (Engine::ensure_useful_mask): a batch that is only scanned never pays for it
+  DevBuf useful;
+  bool useful_built = false;
+  int64_t n_cells = 0;
   bool permuted = false;   // keep item copies in the secondary orders (resident plan of the train pipeline)
   bool inner_only = false; // build only the by_inner order (the BPP filter needs no outside values of loop cells)
   bool sorted = true;      // the segments of the role lists are sorted by item index (Engine::ensure_sorted_plan)
@@ -230,6 +235,7 @@ class Engine {
   explicit Engine(const elemdp_model_desc& d);
   ~Engine();
 
+  void useful_mask(int idx, uint8_t* mask, int cap);
   int n_param() const { return au_.n_theta() + 2; }
   int n_state() const { return au_.S(); }
   int n_node() const { return au_.M(); }
@@ -290,6 +296,7 @@ class Engine {
   void resident_plan(const uint32_t* mask);
   void build_planset(PlanSet& ps, int first, int count, const uint32_t* d_okbits);
   void ensure_sorted_plan();
+  void ensure_useful_mask();
   LdsLayout lds_layout(const AutomatonLayout& lay, int Lmax, int nword_max, bool scan) const;
   DpArgs base_args(const AutomatonLayout& lay, const int32_t* d_ints, const double* d_params, const PlanSet& ps,
                    const uint32_t* d_okbits, int S);
@@ -450,6 +457,8 @@ class Engine {
   bool opt_profile_ = false;
   // 4 = scaled-linear batch pipeline (lin_kernels.hip), 3 = log-space batch pipeline, 2 = fused one-workgroup-per-sequence kernel
   int opt_pipeline_ = 4;
+  bool opt_useful_mask_ = true;    // option "useful_mask": the train sweeps skip the entries no complete parse reaches
+  int opt_useful_lds_kb_ = 150;    // option "useful_mask_lds_kb": k_useful_mask's LDS budget; a larger sequence gets the all-ones mask
   bool opt_sorted_plan_ = false;   // option "sorted_plan": sort the role lists at load_batch whatever the pipeline
   // scaled-linear pipeline
   AutomatonLayout lays_;                 // the automaton with the shadow copy of (0,0): both outside passes in one sweep
@@ -648,6 +657,11 @@ void Engine::set_option(const std::string& key, double v) {
   else if (key == "fast") opt_fast_ = v != 0;
   else if (key == "deterministic") opt_det_ = v != 0;
   else if (key == "sorted_plan") opt_sorted_plan_ = v != 0;
+  else if (key == "useful_mask") opt_useful_mask_ = v != 0;
+  else if (key == "useful_mask_lds_kb") {   // (at most what a workgroup can have; takes effect for the masks built after it)
+    if (v < 0 || v > 150) throw ArgError("useful_mask_lds_kb: 0 .. 150");
+    opt_useful_lds_kb_ = (int)v;
+  }
   else if (key == "eval_first") opt_eval_first_ = (int)v;
   else if (key == "eval_count") opt_eval_count_ = (int)v;
   else if (key == "prune") {
@@ -750,6 +764,8 @@ void Engine::build_planset(PlanSet& ps, int first, int count, const uint32_t* d_
     lmax = std::max(lmax, (int)p.L);
     wmax1 = std::max(wmax1, (int)p.W + 1);
   }
+  ps.n_cells = cell_b;
+  ps.useful_built = false;   // (the mask follows the pair mask: ensure_useful_mask builds it again)
   d_okbits_end_.alloc(sizeof(uint32_t) * (size_t)bits_end);   // the pair mask by (end, span): scratch of the item enumeration
   ps.d_plans.upload(ps.h, st_);
   const bool chunked = ps.inner_only;   // the plan of the unfiltered mask is rebuilt chunk after chunk: its buffers only grow
@@ -802,6 +818,16 @@ void Engine::build_planset(PlanSet& ps, int first, int count, const uint32_t* d_
   HIP_OK(hipStreamSynchronize(st_));
   ps.sorted = a.sort_roles != 0;
   ps.ka = a;
+}
+
+// The usefulness mask of the resident plan, from its pair masks and dmin (still in place: the band kernels read them too).
+void Engine::ensure_useful_mask() {
+  if (plan_.useful_built || plan_.count <= 0) return;
+  plan_.useful.alloc((size_t)plan_.n_cells);
+  plan_.ka.p.useful = plan_.useful.as<uint8_t>();
+  plan_.ka.m_min = m_min();
+  HIP_OK(launch_useful_mask(plan_.ka, (size_t)plan_.n_cells, (size_t)opt_useful_lds_kb_ * 1024, st_));
+  plan_.useful_built = true;
 }
 
 void Engine::ensure_sorted_plan() {
@@ -1586,6 +1612,8 @@ void Engine::run_lin_batch() {
   const int r0 = ranged ? opt_eval_first_ : 0, n_ev = ranged ? opt_eval_count_ : n_seq_;
   if (r0 < 0 || n_ev <= 0 || r0 + n_ev > n_seq_) throw ArgError("eval_first / eval_count outside the resident batch");
   int gsz = prepare_lin(a, sched1, false, n_ev);
+  if (opt_useful_mask_) ensure_useful_mask();
+  a.p.useful = opt_useful_mask_ ? plan_.useful.as<uint8_t>() : nullptr;   // (the train sweeps only: the scan family sees null)
   const int32_t* h_ord = h_order_.data();
   const int32_t* d_ord = d_order_.as<int32_t>();
   const SeqPlan* d_sorted = d_plans_sorted_.as<SeqPlan>();
@@ -1871,6 +1899,19 @@ void Engine::batch_pairs(int idx, uint8_t* kept, double* lnbpp, int cap) {
     for (int c = 0; c < nc; ++c)
       lnbpp[c] = ((w0[c >> 5] >> (c & 31)) & 1u) ? h_lnbpp_[h_lnbpp_base_[idx] + c] : -std::numeric_limits<double>::infinity();
   }
+}
+
+void Engine::useful_mask(int idx, uint8_t* mask, int cap) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (streaming_) throw StateError("useful_mask needs a resident batch (the handle streams this one in chunks)");
+  if (idx < 0 || idx >= n_seq_) throw ArgError("useful_mask: bad sequence index");
+  const SeqPlan& p = h_plans_[idx];
+  const int nc = (p.L + 1) * (p.W + 1);
+  if (cap < nc) throw ArgError("useful_mask: buffer too small");
+  ensure_useful_mask();
+  HIP_OK(hipStreamSynchronize(st_));
+  HIP_OK(hipMemcpy(mask, plan_.useful.as<uint8_t>() + p.cell_base, nc, hipMemcpyDeviceToHost));
 }
 
 // The scaled-linear sum passes of a scan (and the first one of pair_posteriors): table slots, cleared outputs, weights.  A scan
@@ -2451,6 +2492,19 @@ int elemdp_batch_pairs(elemdp_handle* h, int32_t seq_index, uint8_t* kept, doubl
   if (!h || !kept) throw elemdp::ArgError("elemdp_batch_pairs: null argument");
   h->e->batch_pairs(seq_index, kept, lnbpp, cap);
   ELEMDP_CATCH
+}
+
+int elemdp_useful_mask(elemdp_handle* h, int32_t seq_index, uint8_t* mask, int32_t cap) {
+  ELEMDP_TRY
+  if (!h || !mask) throw elemdp::ArgError("elemdp_useful_mask: null argument");
+  h->e->useful_mask(seq_index, mask, cap);
+  ELEMDP_CATCH
+}
+int elemdp_useful_mask_host(const uint8_t* kept, const uint8_t* unp, int32_t L, int32_t W, int32_t max_iloop, int32_t flags,
+                            uint8_t* mask) {
+  if (!kept || !mask || L < 0 || W < 0 || W > L || max_iloop < 0) return ELEMDP_EINVAL;
+  elemdp::useful_mask_host(kept, unp, L, W, max_iloop, (flags & ELEMDP_DBG_NO_TURN) ? 4 : 10, (flags & ELEMDP_NO_ENERGY) != 0, mask);
+  return ELEMDP_OK;
 }
 
 int elemdp_partial_len(const elemdp_handle* h) { return h ? h->e->partial_len() : ELEMDP_EINVAL; }

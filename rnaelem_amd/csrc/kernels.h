@@ -24,6 +24,9 @@ struct PlanArrays {
   int32_t* by_inner_idx = nullptr; int32_t* by_left_idx = nullptr; int32_t* by_right_idx = nullptr;
   // copies of the items in the three secondary orders (one dependent load less per term in the outside sweeps)
   LoopItem* items_inner = nullptr; LoopItem* items_left = nullptr; LoopItem* items_right = nullptr;
+  // usefulness mask of the train sweeps (plan_rules.h: UB_* bits), one byte per cell at cell_base + d * (L+1) + i; null: every
+  // entry counts as useful
+  uint8_t* useful = nullptr;
 };
 
 // static per-batch arrays
@@ -43,6 +46,7 @@ struct PlanKernelArgs {
   int32_t first, count;
   PlanArrays p;
   int32_t no_ene, min_span, fix_rss;
+  int32_t m_min = 0;     // smallest span of a multiloop cell (the usefulness mask)
   int32_t ncell_max = 0, nword_max = 0, nitems_max = 0, lmax = 0;   // largest sequence of the set (grid sizes)
   int32_t wmax1 = 0;     // largest W + 1 of the set
   int32_t n_roles = 3;   // 1: only the by_inner order (plan of the BPP filter)
@@ -254,6 +258,8 @@ hipError_t launch_mask(const BatchArrays& b, const SeqPlan* plans, int n_seq, in
                        int32_t* n_canonical, hipStream_t st);
 hipError_t launch_plan_cells(const PlanKernelArgs& a, int32_t* n_items_out, hipStream_t st);
 hipError_t launch_plan_items(const PlanKernelArgs& a, hipStream_t st);
+hipError_t launch_useful_mask(const PlanKernelArgs& a, size_t n_cells, size_t lds_cap, hipStream_t st);   // needs dmin (launch_plan_cells)
+void useful_mask_host(const uint8_t* kept, const uint8_t* unp, int L, int W, int C, int m_min, bool no_ene, uint8_t* out);
 hipError_t launch_plan_sort(const PlanKernelArgs& a, hipStream_t st);   // the sort of launch_plan_items alone (sort_roles = 0 before)
 hipError_t launch_permute_items(const PlanKernelArgs& a, hipStream_t st);
 bool plan_copies_fused(const PlanKernelArgs& a);   // launch_plan_items has written the item copies already (no launch_permute_items)

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <vector>
 
 #include "dp_rules.h"
 #include "energy_rules.h"
@@ -818,6 +819,59 @@ __global__ __launch_bounds__(kThreads) void k_reduce(const double* seq_out, int 
   if (threadIdx.x == 0) partial[col] = part[0];
 }
 
+// K-plan 5: usefulness mask of the train sweeps (plan_rules.h: useful_inside_cell / useful_loop_operands /
+// useful_outside_cell), one workgroup per sequence with the byte rows, the pair mask, dmin and the unpaired flags in LDS; the
+// cells of a diagonal are dealt to the lanes, one barrier per diagonal and sweep.
+struct UsefulLds { int m, lm, bits, bits_end, dmin, unp, total; };
+__host__ __device__ inline UsefulLds useful_lds(int L, int W) {
+  const int n = (L + 1) * (W + 1);
+  UsefulLds u;
+  int o = 0;
+  auto take = [&](int bytes) { const int at = o; o += (bytes + 15) & ~15; return at; };
+  u.m = take(n); u.lm = take(n); u.bits = take(4 * ((n + 31) / 32 + 1)); u.bits_end = take(4 * ((n + 31) / 32 + 1)); u.dmin = take(2 * (L + 1)); u.unp = take(L + 1);
+  u.total = o;
+  return u;
+}
+__global__ __launch_bounds__(kThreads) void k_useful_mask(PlanKernelArgs a) {
+  extern __shared__ unsigned char u_lds[];
+  const SeqPlan p = a.plans[a.first + blockIdx.x];
+  const int L = p.L, W = p.W, n = (L + 1) * (W + 1), nword = (n + 31) / 32, tid = threadIdx.x;
+  const UsefulLds u = useful_lds(L, W);
+  uint8_t* m = u_lds + u.m;
+  uint8_t* lm = u_lds + u.lm;
+  uint32_t* bits = reinterpret_cast<uint32_t*>(u_lds + u.bits);
+  uint32_t* bits_end = reinterpret_cast<uint32_t*>(u_lds + u.bits_end);
+  int16_t* dm = reinterpret_cast<int16_t*>(u_lds + u.dmin);
+  uint8_t* un = u_lds + u.unp;
+  for (int t = tid; t <= nword; t += kThreads) {
+    bits[t] = t < nword ? a.okbits[p.bits_base + t] : 0u;
+    bits_end[t] = t < nword ? a.okbits_end[p.bits_base + t] : 0u;
+  }
+  for (int t = tid; t <= L; t += kThreads) {
+    dm[t] = a.p.dmin[p.dmin_base + t];
+    un[t] = t < L ? a.b.unp[p.pos_base + t] : 0;
+  }
+  for (int c = tid; c < n; c += kThreads) { m[c] = 0; lm[c] = 0; }
+  __syncthreads();
+  const UsefulCtx q{L, W, p.C, a.m_min, a.no_ene ? (1 << 20) : kMaxLoop, bits, bits_end, dm, un};
+  const int dtop = W < L ? W : L;
+  for (int d = 0; d <= dtop; ++d) {
+    for (int i = tid; i + d <= L; i += kThreads) m[q.at(i, d)] = (uint8_t)useful_inside_cell(q, m, i, d);
+    __syncthreads();
+  }
+  for (int c = tid; c < n; c += kThreads) {
+    const int d = c / (L + 1), i = c - d * (L + 1);
+    if (i + d <= L) useful_loop_operands(q, i, d, [&](int x) { lm[x] = 1; });   // (every writer stores the same byte)
+  }
+  __syncthreads();
+  for (int d = dtop; d >= 0; --d) {
+    for (int i = tid; i + d <= L; i += kThreads) m[q.at(i, d)] = (uint8_t)useful_outside_cell(q, m, lm, i, d);
+    __syncthreads();
+  }
+  uint8_t* out = a.p.useful + p.cell_base;
+  for (int c = tid; c < n; c += kThreads) out[c] = m[c];
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -916,6 +970,37 @@ hipError_t launch_reduce(const double* seq_out, int out_stride, int n_seq, int n
   const int ncol = 4 + 2 * n_theta + 4;
   hipLaunchKernelGGL(k_reduce, dim3(ncol), dim3(kThreads), 0, st, seq_out, out_stride, n_seq, n_theta, partial);
   return hipGetLastError();
+}
+// the usefulness mask of every sequence of the set into a.p.useful (cell_base indexing, [d][i]); a set whose largest sequence
+// does not fit lds_cap bytes of a workgroup's LDS gets the mask of all ones (every entry useful: the sweeps then skip nothing)
+hipError_t launch_useful_mask(const PlanKernelArgs& a, size_t n_cells, size_t lds_cap, hipStream_t st) {
+  if (a.count <= 0 || !a.p.useful) return hipSuccess;
+  const size_t lds = (size_t)useful_lds(a.lmax, a.wmax1 - 1).total;
+  if (lds > lds_cap) return hipMemsetAsync(a.p.useful, UB_ALL, n_cells, st);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_useful_mask), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_useful_mask, dim3(a.count), dim3(kThreads), lds, st, a);
+  return hipGetLastError();
+}
+// the same sweep on the host from a kept-pair matrix kept[(L+1)][(W+1)] (no GPU needed); unp: L flags or null (all unpaired
+// positions allowed); out: (W+1) * (L+1) bytes, [d][i]
+void useful_mask_host(const uint8_t* kept, const uint8_t* unp, int L, int W, int C, int m_min, bool no_ene, uint8_t* out) {
+  const int n = (L + 1) * (W + 1);
+  std::vector<uint32_t> bits((n + 31) / 32 + 1, 0u), bits_end((n + 31) / 32 + 1, 0u);
+  std::vector<int16_t> dmin(L + 1, 0);
+  std::vector<uint8_t> un(L + 1, 1), lm(n, 0);
+  for (int i = 0; i <= L; ++i)
+    for (int d = 0; d <= W; ++d)
+      if (i + d <= L && kept[i * (W + 1) + d]) {
+        const int c = i * (W + 1) + d;
+        bits[c >> 5] |= 1u << (c & 31);
+        const int ce = (i + d) * (W + 1) + d;
+        bits_end[ce >> 5] |= 1u << (ce & 31);
+        if (d > 0 && dmin[i] == 0) dmin[i] = (int16_t)d;
+      }
+  if (unp) for (int i = 0; i < L; ++i) un[i] = unp[i];
+  const UsefulCtx q{L, W, C, m_min, no_ene ? (1 << 20) : kMaxLoop, bits.data(), bits_end.data(), dmin.data(), un.data()};
+  useful_mask_serial(q, out, lm.data());
 }
 const char* dp_kernel_name(int kind) {
   return kind == DP_TRAIN ? "k_dp<0>" : kind == DP_BPP ? "k_dp<1>" : "k_dp<2>";

@@ -18,6 +18,7 @@
 // transition (AutomatonLayout::fs_in / fs_out), the comparisons of the emitted positions with the chosen start are cell flags.
 #pragma once
 #include "lin_rules.h"
+#include "plan_rules.h"
 
 namespace elemdp {
 
@@ -35,7 +36,11 @@ enum : int { CF_POK = 1, CF_LOK = 2, CF_MOK = 4, CF_EOK = 8, CF_DO2 = 16, CF_DOM
              CF_UP = 64, CF_DOL = 128,                                                                              // outside reuse
              // scan passes under the start constraint Ys: the position the cell's left / right emission covers is Ys (inside: i,
              // j - 1; outside: i - 1, j); outside: j is the last position of the sequence
-             CF_YL = 1 << 17, CF_YR = 1 << 18, CF_JLAST = 1 << 19 };
+             CF_YL = 1 << 17, CF_YR = 1 << 18, CF_JLAST = 1 << 19,
+             // train sweeps: the cell's byte of the usefulness mask (plan_rules.h: UB_* << CF_USH; all ones without a mask).  A
+             // plane whose bit is off loads no operand and takes the value 0, which is stored like any other: an entry that is
+             // parsable but useless has readers (they multiply it by an exact 0 of their own, or are useless themselves).
+             CF_USH = 20 };
 ELEMDP_HD int fcol(int packed, int byte) { const int c = (packed >> (8 * byte)) & 0xff; return c == 0xff ? -1 : c; }
 
 // which global value lane k (0..7) of a cell fetches for the inside record, and from which cell
@@ -52,7 +57,7 @@ ELEMDP_HD int cell_in_flags(const ModelView& m, const SeqView& q, int d, int i) 
   const bool doM = mok && m_ok(m, q, i + 1, d - 1) && q.unp[i];
   const bool inner = d >= 2 && q.pair_ok(i + 1, d - 2);
   const int bi = i < q.L ? q.seq[i] : 0, bj = j > 0 ? q.seq[j - 1] : 0;
-  return (pok ? CF_POK : 0) | (lok ? CF_LOK : 0) | (mok ? CF_MOK : 0) | (eok ? CF_EOK : 0) | (do2 ? CF_DO2 : 0) | (doM ? CF_DOM : 0) |
+  return (q.ubits(i, d) << CF_USH) | (pok ? CF_POK : 0) | (lok ? CF_LOK : 0) | (mok ? CF_MOK : 0) | (eok ? CF_EOK : 0) | (do2 ? CF_DO2 : 0) | (doM ? CF_DOM : 0) |
          ((pok && d >= 2) ? CF_CE : 0) | ((pok && inner) ? CF_CP : 0) | (bi << 8) | (bj << 11) | (bp_type(bi, bj) << 14);
 }
 
@@ -66,9 +71,11 @@ ELEMDP_HD void fast_inside_unary(const AutomatonLayout& A, const int32_t* P, con
   const int w0 = P[0], w1 = P[1], w2 = P[2];
   const bool isloop = w0 & 1, wr_pos = w0 & 8;
   const int kl = (w0 >> 2) & 1, nR = (w0 >> 8) & 15, nP = (w0 >> 12) & 15, nL = (w0 >> 16) & 15;
-  const bool pok = fl & CF_POK, lok = fl & CF_LOK, mok = fl & CF_MOK, eok = fl & CF_EOK, do2 = fl & CF_DO2, doM = fl & CF_DOM;
+  const int ub = fl >> CF_USH;
+  const bool uL = ub & UB_L, u2 = ub & UB_2, u1 = ub & UB_1, uM = ub & UB_M, uB = ub & UB_B;
+  const bool pok = fl & CF_POK, lok = fl & CF_LOK, mok = fl & CF_MOK, eok = fl & CF_EOK, do2 = (fl & CF_DO2) && u2, doM = (fl & CF_DOM) && uM;
   const bool cE = fl & CF_CE, cP = fl & CF_CP;
-  const bool doL = isloop && d > 0;
+  const bool doL = isloop && d > 0 && uL;
   const bool yl = CON && (fl & CF_YL), yr = CON && (fl & CF_YR);
   const int bi = (fl >> 8) & 7, bj = (fl >> 11) & 7, ty = (fl >> 14) & 7;
   const int d1 = d > 0 ? d - 1 : 0, d2 = d > 1 ? d - 2 : 0, i1 = i + 1;
@@ -126,12 +133,12 @@ ELEMDP_HD void fast_inside_unary(const AutomatonLayout& A, const int32_t* P, con
     }
   double HB = *pHB, HE = *pHE;
   for (int r = 1; r < nrep; ++r) { HB += pHB[r * rstride]; HE += pHE[r * rstride]; }   // (deterministic mode: one copy per wave)
-  const double vL = isloop ? (d == 0 ? ((w0 & 2) ? 1. : 0.) : sL) : 0.;   // motif_trainer.hpp:89-95
+  const double vL = (isloop && uL) ? (d == 0 ? ((w0 & 2) ? 1. : 0.) : sL) : 0.;   // motif_trainer.hpp:89-95
   const double vP = pok ? sP : 0.;                                          // rules 1a, 1b
-  const double vB = lok ? HB : 0.;                                          // rule 2
-  const double v2 = lok ? fma(vP, xml, s2) : 0.;                            // rules 3a, 3b
-  const double v1 = lok ? v2 + vB : 0.;                                     // rules 4a, 4b
-  const double vM = mok ? sM + vB : 0.;                                     // rules 5a, 5b
+  const double vB = (lok && uB) ? HB : 0.;                                  // rule 2
+  const double v2 = (lok && u2) ? fma(vP, xml, s2) : 0.;                    // rules 3a, 3b
+  const double v1 = (lok && u1) ? v2 + vB : 0.;                             // rules 4a, 4b
+  const double vM = (mok && uM) ? sM + vB : 0.;                             // rules 5a, 5b
   const double vE = eok ? fma(vM, xcl, fma(vL, xhp, HE)) : 0.;              // rules 6a, 6b, 6c
   // (the B plane is not stored: nothing reads it -- the outside pass of the train kernels decides liveness from the pair entries)
   const int cLo = fcol(w2, 2), cPo = fcol(w1, 0), c2o = fcol(w2, 1), c1o = fcol(w2, 0), cMo = fcol(w1, 2), cEo = fcol(w1, 1);
@@ -171,7 +178,7 @@ ELEMDP_HD int cell_out_flags(const ModelView& m, const SeqView& q, int d, int i)
   const bool do2 = lok && q.left_ok(i, d + 1) && q.unp[j];
   const bool doLc = j < q.L && d + 1 <= q.W;
   const int bl = i > 0 ? q.seq[i - 1] : 0, br = j < q.L ? q.seq[j] : 0;
-  return (pok ? CF_POK : 0) | (lok ? CF_LOK : 0) | (mok ? CF_MOK : 0) | (eok ? CF_EOK : 0) | (do2 ? CF_DO2 : 0) | (doM ? CF_DOM : 0) |
+  return (q.ubits(i, d) << CF_USH) | (pok ? CF_POK : 0) | (lok ? CF_LOK : 0) | (mok ? CF_MOK : 0) | (eok ? CF_EOK : 0) | (do2 ? CF_DO2 : 0) | (doM ? CF_DOM : 0) |
          (up_ok ? CF_UP : 0) | (doLc ? CF_DOL : 0) | (bl << 8) | (br << 11) | (bp_type(bl, br) << 14);
 }
 // which flag masks value k of the outside record (a value that is not masked is only used under a non-zero posterior)
@@ -219,8 +226,12 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
   const int w0 = P[0], w1 = P[1], w2 = P[2], enl = P[3];
   const bool isloop = w0 & 1, wl_s = w0 & 16;
   const int kl = (w0 >> 2) & 1, nRR = (w0 >> 8) & 15, nRP = (w0 >> 12) & 15, nRL = (w0 >> 16) & 15;
-  const bool pok = fl & CF_POK, lok = fl & CF_LOK, mok = fl & CF_MOK, eok = fl & CF_EOK, do2 = fl & CF_DO2, doM = fl & CF_DOM;
-  const bool up_ok = fl & CF_UP, doL = isloop && (fl & CF_DOL);
+  // (usefulness bits: a target whose bit is off has outside value 0 -- its inside value, and with it every parent operand, is
+  // not loaded; the selects on `in.. != 0.` below then leave the 0 that is stored)
+  const int ub = fl >> CF_USH;
+  const bool uL = ub & UB_L, u2 = ub & UB_2, u1 = ub & UB_1, uM = ub & UB_M;
+  const bool pok = fl & CF_POK, lok = fl & CF_LOK, mok = fl & CF_MOK, eok = fl & CF_EOK, do2 = (fl & CF_DO2) && u2, doM = (fl & CF_DOM) && uM;
+  const bool up_ok = fl & CF_UP, doL = isloop && (fl & CF_DOL) && uL;
   const int bl = (fl >> 8) & 7, br = (fl >> 11) & 7, ty = (fl >> 14) & 7;
   const int cLo = fcol(w2, 2), cPo = fcol(w1, 0), c2o = fcol(w2, 1), c1o = fcol(w2, 0), cMo = fcol(w1, 2), cEo = fcol(w1, 1);
   const int dp1 = d + 1, dp2 = d + 2, im1 = i - 1;   // (only dereferenced where the parent cell exists: do2 / doL / up_ok / doM)
@@ -230,7 +241,7 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
   // here: nothing reads them (the generic kernels, which debug_tables uses, store every plane).
   const double ews_l = cr[0], ews_r = cr[1];
   const int ehs = lam_same ? 0 : kl;
-  const double inE = in.ldc(ST_E, d, i, cEo, eok), inM = in.ldc(ST_M, d, i, cMo, mok), inP = in.ldc(ST_P, d, i, cPo, pok);
+  const double inE = in.ldc(ST_E, d, i, cEo, eok), inM = in.ldc(ST_M, d, i, cMo, mok && uM), inP = in.ldc(ST_P, d, i, cPo, pok);
   double opP[kFP], opM[kFL];
   int eP[kFP], eL[kFL];
 #pragma unroll
@@ -244,7 +255,7 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
     opM[u] = out.ldc(ST_M, dp1, im1, fcol(eL[u], 0), u < nRL && doM);
   }
 #if !ELEMDP_UNARY2
-  const double in1 = in.ldc(ST_1, d, i, c1o, lok), in2 = in.ldc(ST_2, d, i, c2o, lok), inL = in.ldc(ST_L, d, i, cLo, isloop);
+  const double in1 = in.ldc(ST_1, d, i, c1o, lok && u1), in2 = in.ldc(ST_2, d, i, c2o, lok && u2), inL = in.ldc(ST_L, d, i, cLo, isloop && uL);
   const double r7 = out.ldc(ST_P, d, i, cPo, pok);
   double op2[kFR], opL[kFR];
   int eR[kFR];
@@ -303,7 +314,7 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
 #if defined(__HIP_DEVICE_COMPILE__)
   __builtin_amdgcn_sched_barrier(0);
 #endif
-  const double in1 = in.ldc(ST_1, d, i, c1o, lok), in2 = in.ldc(ST_2, d, i, c2o, lok), inL = in.ldc(ST_L, d, i, cLo, isloop);
+  const double in1 = in.ldc(ST_1, d, i, c1o, lok && u1), in2 = in.ldc(ST_2, d, i, c2o, lok && u2), inL = in.ldc(ST_L, d, i, cLo, isloop && uL);
   const double r7 = out.ldc(ST_P, d, i, cPo, pok);
   double op2[kFR], opL[kFR];
   int eR[kFR];

@@ -603,6 +603,29 @@ __device__ __forceinline__ void outer_stage(const LViews& v, const OuterRecs& r,
   __syncthreads();
 }
 
+// Train sweeps under the usefulness mask (plan_rules.h; SeqView::useful): true when no cell of the workgroup has a useful entry
+// in any plane (uniform over the workgroup).  Such a workgroup computes nothing: fill_dead_rows stores the zeros that the
+// readers of its cells' entries expect (an entry that is parsable but useless still has readers) and the kernel returns.
+__device__ __forceinline__ bool block_is_dead(const SeqView& q, int d, int i0, int nc, int tid) {
+  if (!q.useful) return false;
+  const int b = tid < nc ? (int)q.useful[d * (q.L + 1) + i0 + tid] : 0;
+  return !__syncthreads_or(b);
+}
+// zeros into the rows of planes e0, e1, e2, e3 (negative: none) and the pair entries of cells i0 .. i0 + nc - 1 of diagonal d
+__device__ __forceinline__ void fill_dead_rows(const TableView& T, int d, int i0, int nc, int tid, int e0, int e1, int e2, int e3) {
+  const int pl[4] = {e0, e1, e2, e3};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (pl[k] < 0) continue;
+    double* row = T.band + T.cidx(pl[k], d, i0, 0);
+    for (int t = tid; t < nc * T.rs[pl[k]]; t += kBT) row[t] = 0.;
+  }
+  if (T.ap) {
+    double* row = T.ap + T.aidx(d, i0, 0);
+    for (int t = tid; t < nc * T.nAs; t += kBT) row[t] = 0.;
+  }
+}
+
 // FAST: table-driven phases (lin_fast.h; train schedule, the fast blob staged); FP: longest pair list of a state (2 or 3)
 template <bool BIG, bool CON, bool FAST = false, int FP = kFastP, bool W8 = false>
 __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4_in(LinArgs a) {
@@ -629,6 +652,8 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
     const int ys = a.ys[v.n];
     if (ys < i0 || ys - d + 1 > i0 + nc - 1) return;
   }
+  constexpr bool MASK = FAST && !CON;   // the train form honours the usefulness mask (the scan passes get none)
+  if (MASK && block_is_dead(v.q, d, i0, nc, tid)) { fill_dead_rows(v.in, d, i0, nc, tid, ST_L, ST_2, ST_1, ST_M); return; }
   const int HD = FAST ? A.n_lane : S;   // stride of the heavy sums per cell: the live states (table-driven: their index among them), or all
   const int CS = cpb * HD;
   constexpr int NW = 1;                      // (one copy of the heavy sums in either mode: see the deterministic mode above)
@@ -707,7 +732,13 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
         const int c1 = fcol(r0, 0), cP = fcol(r0, 1), tg = (r0 >> 16) & 0xff;
         const int dmi = dm[c];
         double av = 0.;
-        if (dmi > 0 && dmi < d) {
+        const bool exists = dmi > 0 && dmi < d;
+        // (a useless entry: 0, no stem walk.  The byte comes from the plan: the cell flags in LDS are written without a barrier
+        // before this phase)
+        const bool dead = MASK && exists && !(v.q.ubits(i, d) & UB_A);
+        if (dead) {
+          v.in.a(d, i, p) = 0.;
+        } else if (exists) {
           BitIter it;
           it.init(v.q.okbits_end, j * W1, 1, d - dmi);
           const int nch = (dmi < d - 1 && v.q.unp[j - 1]) ? (r1 >> 16) & 15 : 0;   // (the entries of (i, d-1) exist iff dmin[i] < d - 1)
@@ -1345,6 +1376,8 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     // reader.  Workgroups whose cells all satisfy j <= Ys return: on average half of the sweep.
     if (!(a.dbg & 4096) && i0 + nc - 1 + d <= a.ys[v.n]) return;
   }
+  constexpr bool MASK = FAST && MODE == OUT_TRAIN;   // (as in k4_in; the B plane and plane 1 are not stored on this side)
+  if (MASK && block_is_dead(v.q, d, i0, nc, tid)) { fill_dead_rows(v.out, d, i0, nc, tid, ST_L, ST_2, ST_M, -1); return; }
   const int HD = FAST ? A.n_lane : S;   // (as in k4_in)
   const int CS = cpb * HD;
   // ONE copy of the heavy sums (deterministic mode: each gets its adds from one wave, see the top of the file); the statistics,
@@ -1513,7 +1546,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
       const int s1 = pr_s1(p);
       const int cP = pr_cP(p);
       const int dmi = dm[c];
-      if (dmi > 0 && dmi <= d) {     // left_ok(i, d)  (a dead child 1(i,j,s1) drops the sum in the unary phase)
+      if (dmi > 0 && dmi <= d && !(MASK && !(v.q.ubits(i, d) & UB_1))) {     // left_ok(i, d)  (a dead child 1(i,j,s1) drops the sum in the unary phase; a useless one is not summed)
         const int hi = (W - d < L - j) ? W - d : L - j;
         const double* xml = v.q.xwc + (size_t)(pr_kl(p) * 5 + XT_ML) * v.q.xwc_stride;
         double acc = 0.;
@@ -1733,7 +1766,11 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
         const int tg = (r0 >> 16) & 0xff;
         const bool w1 = pi.merged && (r0 & (4 << 24));
         const int i = i0 + c, j = i + d, dmi = dm[c];
-        if (dmi > 0 && dmi < d) {      // (otherwise the entry does not exist)
+        const bool exists = dmi > 0 && dmi < d;      // (otherwise the entry does not exist)
+        const bool dead = MASK && exists && !((crfl[c] >> CF_USH) & UB_A);
+        if (dead) {                    // a useless entry: 0, nothing loaded
+          out.a(d, i, p) = 0.;
+        } else if (exists) {
           const bool step = d + 1 <= W && j < L && v.q.unp[j];
           const int nr = step ? (r1 >> 20) & 15 : 0;
           const double a_in = in.a(d, i, p);

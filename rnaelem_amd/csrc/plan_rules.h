@@ -131,4 +131,143 @@ ELEMDP_HD int count_interior_by_end(bool no_ene, int L, int W, int C, const Word
   return n;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Usefulness mask: one byte per band cell, [d][i] like the tables.  Bit (cell, plane) is set when a complete parse
+// can pass through that entry in the structure grammar with every weight taken as positive; an entry whose bit is clear has
+// inside value 0 or outside value 0 for every theta / lambda.  The mask may be a superset of that set, never miss an entry.
+// Two boolean sweeps with the conditions the band kernels test (lin_fast.h: cell_in_flags / cell_out_flags, the pair phases of
+// k4_in / k4_out): inside liveness bottom-up (useful_inside_cell: reads rows of smaller span), then outside reachability
+// top-down through the inside-live entries only (useful_outside_cell: reads rows of larger span, and the cell's own inside
+// bits, which it replaces -- the sweep works in place).  All cells of one diagonal are independent in either sweep.
+// ---------------------------------------------------------------------------------------------
+// (these run on the host too -- the host entry of the C ABI -- where the recurrences of dp_rules.h are device code only)
+#if defined(__HIPCC__)
+#define ELEMDP_HOSTDEV __host__ __device__ __forceinline__
+#else
+#define ELEMDP_HOSTDEV inline
+#endif
+enum : int { UB_P = 1, UB_E = 2, UB_M = 4, UB_B = 8, UB_A = 16, UB_1 = 32, UB_2 = 64, UB_L = 128, UB_ALL = 255 };
+
+struct UsefulCtx {
+  int32_t L, W, C, m_min;
+  int32_t loop_cap;          // an interior loop holds at most this many unpaired bases (kMaxLoop; no bound under --no-energy)
+  const uint32_t* okbits;    // kept pairs, bit i * (W+1) + d (one word of slack behind the last: the bit walks read ahead)
+  const uint32_t* okbits_end;   // the same pairs by (end, span): bit j * (W+1) + d <=> pair cell (j - d, d)  (k_mask_by_end)
+  const int16_t* dmin;       // L+1
+  const uint8_t* unp;        // L
+  ELEMDP_HOSTDEV bool pair_ok(int i, int d) const {
+    if (i < 0 || d < 0 || d > W || i + d > L) return false;
+    const int c = i * (W + 1) + d;
+    return (okbits[c >> 5] >> (c & 31)) & 1u;
+  }
+  ELEMDP_HOSTDEV bool left_ok(int i, int d) const {
+    if (d > W || d < 0 || i + d > L) return false;
+    const int dm = dmin[i];
+    return dm > 0 && d >= dm;
+  }
+  ELEMDP_HOSTDEV bool e_ok(int i, int d) const { return i > 0 && d + 2 <= W && pair_ok(i - 1, d + 2); }
+  ELEMDP_HOSTDEV bool m_ok(int i, int d) const { return 0 < i && i + d < L && d <= W && m_min <= d; }
+  ELEMDP_HOSTDEV int at(int i, int d) const { return d * (L + 1) + i; }
+};
+
+// pred(n) for the set bits bit0 + n of a pair mask with n in [lo, hi], ascending, until one holds (-> true).  The kept pairs are
+// ~7 % of the cells: a walk over the set bits of a run visits a few of them where a loop over its positions tests up to W.
+template <class F>
+ELEMDP_HOSTDEV bool any_mask_bit(const uint32_t* m, int bit0, int lo, int hi, F&& pred) {
+  if (hi < lo) return false;
+  const int b = bit0 + lo, e = bit0 + hi;
+  int w = b >> 5;
+  uint32_t word = m[w] & (~0u << (b & 31));
+  for (;;) {
+    while (word) {
+      const int bit = (w << 5) + __builtin_ctz(word);
+      if (bit > e) return false;
+      if (pred(bit - bit0)) return true;
+      word &= word - 1;
+    }
+    if (((w + 1) << 5) > e) return false;
+    word = m[++w];
+  }
+}
+
+// inside-liveness bits of cell (i, d) from the rows below it (UB_L: the loop chain exists everywhere)
+ELEMDP_HOSTDEV int useful_inside_cell(const UsefulCtx& q, const uint8_t* m, int i, int d) {
+  const int j = i + d;
+  const bool pok = q.pair_ok(i, d), lok = q.left_ok(i, d), mok = q.m_ok(i, d), eok = q.e_ok(i, d);
+  const int dmi = q.dmin[i];
+  int r = UB_L | (pok ? UB_P : 0) | (eok ? UB_E : 0);
+  bool iA = false;
+  if (dmi > 0 && dmi < d) {           // (the pair entries of the factorised rule 2 exist)
+    if (dmi < d - 1 && q.unp[j - 1] && (m[q.at(i, d - 1)] & UB_A)) iA = true;             // tail step
+    if (!iA)                                                                              // stems (j - sp, j), sp <= d - dmin[i]
+      iA = any_mask_bit(q.okbits_end, j * (q.W + 1), 1, d - dmi, [&](int sp) { return (m[q.at(i, d - sp)] & UB_1) != 0; });
+  }
+  const bool iB = lok && iA;
+  const bool do2 = lok && d > 0 && q.left_ok(i, d - 1) && q.unp[j - 1];
+  const bool i2 = lok && (pok || (do2 && (m[q.at(i, d - 1)] & UB_2)));
+  const bool doM = mok && q.m_ok(i + 1, d - 1) && q.unp[i];
+  const bool iM = mok && (iB || (doM && (m[q.at(i + 1, d - 1)] & UB_M)));
+  return r | (iA ? UB_A : 0) | (iB ? UB_B : 0) | (i2 ? UB_2 : 0) | ((i2 || iB) ? UB_1 : 0) | (iM ? UB_M : 0);
+}
+
+// The loops L(i, k) and L(l, j) that an interior loop of the E cell (i, d) reads, over the OUTSIDE enumeration (enum_interior:
+// k - i <= C, whatever j - l) bounded by the loop size alone -- the superset of the plan's items that needs neither the energy
+// tables nor the bases: calls f(cell index) for both operands of every candidate.
+template <class F>
+ELEMDP_HOSTDEV void useful_loop_operands(const UsefulCtx& q, int i, int d, F&& f) {
+  if (!q.e_ok(i, d)) return;
+  const int j = i + d;
+  for (int l = j; l >= i + 2; --l) {
+    int kmax = (l - 2 < i + q.C) ? l - 2 : i + q.C;
+    const int kcap = i + q.loop_cap - (j - l);
+    if (kcap < kmax) kmax = kcap;
+    if (kmax < i) break;
+    const int shi = (l - i < q.W) ? l - i : q.W;       // spans l - k of the candidates k = i .. kmax: one run of bits at end l
+    any_mask_bit(q.okbits_end, l * (q.W + 1), l - kmax, shi, [&](int sp) {
+      const int k = l - sp;
+      if (k == i && l == j) return false;
+      f(q.at(i, k - i));
+      f(q.at(l, j - l));
+      return false;
+    });
+  }
+}
+
+// final bits of cell (i, d): m holds the final bits of the rows above and the inside bits of this row; lm[cell] != 0 where
+// useful_loop_operands marked the cell
+ELEMDP_HOSTDEV int useful_outside_cell(const UsefulCtx& q, const uint8_t* m, const uint8_t* lm, int i, int d) {
+  const int j = i + d, W = q.W, L = q.L;
+  const int in = m[q.at(i, d)];
+  const bool lok = q.left_ok(i, d), mok = q.m_ok(i, d), eok = q.e_ok(i, d);
+  const int dmi = q.dmin[i];
+  const bool doM = mok && q.m_ok(i - 1, d + 1) && q.unp[i > 0 ? i - 1 : 0];
+  const bool uM = (in & UB_M) && (eok || (doM && (m[q.at(i - 1, d + 1)] & UB_M)));         // rules 6a, 5a
+  bool u1 = false;
+  if ((in & UB_1) && lok) {                                                                 // rule 2: stems (j, j + sp)
+    const int hi = (W - d < L - j) ? W - d : L - j;
+    u1 = any_mask_bit(q.okbits, j * (W + 1), 1, hi, [&](int sp) { return (m[q.at(i, d + sp)] & UB_A) != 0; });
+  }
+  const bool uB = (in & UB_B) && (uM || u1);                                                // rules 5b, 4b
+  const bool step = d + 1 <= W && j < L && q.unp[j];
+  const bool uA = (in & UB_A) && dmi > 0 && dmi < d && (uB || (step && (m[q.at(i, d + 1)] & UB_A)));
+  const bool do2 = lok && q.left_ok(i, d + 1) && q.unp[j];
+  const bool u2 = (in & UB_2) && (u1 || (do2 && (m[q.at(i, d + 1)] & UB_2)));               // rules 4a, 3a
+  const bool doL = j < L && d + 1 <= W;
+  const bool uL = eok || lm[q.at(i, d)] != 0 || (doL && (m[q.at(i, d + 1)] & UB_L));        // rules 6b, 6c, L <- L
+  return (in & (UB_P | UB_E)) | (uM ? UB_M : 0) | (uB ? UB_B : 0) | (uA ? UB_A : 0) | (u1 ? UB_1 : 0) | (u2 ? UB_2 : 0) | (uL ? UB_L : 0);
+}
+
+// the whole mask of one sequence, serially (the host entry elemdp_useful_mask_host; the GPU runs the same cell functions with
+// the cells of a diagonal dealt to the lanes of a workgroup: k_useful_mask, kernels.hip).  m, lm: (W+1) * (L+1) bytes each.
+ELEMDP_HOSTDEV void useful_mask_serial(const UsefulCtx& q, uint8_t* m, uint8_t* lm) {
+  const int L = q.L, W = q.W, n = (W + 1) * (L + 1);
+  for (int c = 0; c < n; ++c) { m[c] = 0; lm[c] = 0; }
+  for (int d = 0; d <= W && d <= L; ++d)
+    for (int i = 0; i + d <= L; ++i) m[q.at(i, d)] = (uint8_t)useful_inside_cell(q, m, i, d);
+  for (int d = 0; d <= W && d <= L; ++d)
+    for (int i = 0; i + d <= L; ++i) useful_loop_operands(q, i, d, [&](int c) { lm[c] = 1; });
+  for (int d = (W < L ? W : L); d >= 0; --d)
+    for (int i = 0; i + d <= L; ++i) m[q.at(i, d)] = (uint8_t)useful_outside_cell(q, m, lm, i, d);
+}
+
 }  // namespace elemdp
