@@ -102,6 +102,12 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *                       "slots": table slots; "two_streams": retired with pipeline 2, accepted and ignored
  *     "keep_lnbpp"      keep ln BPP of the filter for elemdp_batch_pairs; "bpp_log": 1 = log-space BPP filter for every band
  *     "sorted_plan"     1: role lists of the plan sorted per cell (reproducible summation order of the log-space pipeline)
+ *     "live_blocks"     1 (default): a workgroup of the train sweeps takes its cells from the plan's lists of LIVE cells (non-zero
+ *                       mask byte) of the diagonal instead of consecutive ones (elemdp_live_blocks) on the diagonals where that leaves fewer workgroups;
+ *                       2: on every diagonal; 0: consecutive cells.  Needs
+ *                       "useful_mask"; the deterministic mode keeps consecutive cells whatever the value;
+ *     "live_span"       the cells the live cells of one block may span, up to 64 (a model with more cells per block than
+ *                       the value takes its cells per block); 0 (default): 32;
  *     "useful_mask"     1 (default): the train sweeps skip the table entries no complete parse reaches (elemdp_useful_mask);
  *                       0: they compute every entry -- kept as the A/B switch and as the tests' reference
  *   measurement / tests
@@ -131,6 +137,19 @@ int elemdp_useful_mask(elemdp_handle* h, int32_t seq_index, uint8_t* mask, int32
  * flags: ELEMDP_NO_ENERGY and ELEMDP_DBG_NO_TURN are looked at. */
 int elemdp_useful_mask_host(const uint8_t* kept, const uint8_t* unp, int32_t L, int32_t W, int32_t max_iloop, int32_t flags,
                             uint8_t* mask);
+/* Debug: the live-block lists of one sequence of the resident plan for the cells per block of the model and the span of the
+ * current options (built by the call if no evaluation has built them): counts[d], d = 0 .. W, blocks of
+ * diagonal d in records + 16 * (d * stride + b).  A record is 16 bytes: uint64 live (bit k: cell first + k is live), int16 first,
+ * int16 own_lo, int16 own_end (the block owns the cells [own_lo, own_end)), int16 count.  stride >= (L + 8) / 8.  cpb_cap[2]
+ * receives the cells per block and the span a block may cover.  taken[W+1] (may be NULL) receives 1 where a train evaluation of
+ * the current options ("live_blocks", "useful_mask", "deterministic") sweeps diagonal d from
+ * its list, 0 where it takes consecutive cells. */
+int elemdp_live_blocks(elemdp_handle* h, int32_t seq_index, int32_t* counts, void* records, int32_t stride, int32_t* cpb_cap,
+                       int32_t* taken);
+/* Host only: the same lists by the same rule on the CPU from a mask[(W+1)*(L+1)] (any non-zero byte is a live cell) for blocks
+ * of cpb live cells that span at most cap cells, cpb <= cap <= 64 (else ELEMDP_EINVAL); stride >= ceil((L + 1) / cpb). */
+int elemdp_live_blocks_host(const uint8_t* mask, int32_t L, int32_t W, int32_t cpb, int32_t cap, int32_t* counts, void* records,
+                            int32_t stride);
 
 /* == RNAelemTrainer::operator()(x, fn, gr) over the whole resident batch with --no-shuffle
  * (motif_trainer.hpp:595-633 + RNAelemTrainDP::operator() :124-272).  fn/gr are the UNREGULARISED

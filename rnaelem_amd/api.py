@@ -22,7 +22,7 @@ DBG_FIX_RSS, DBG_NO_TURN = 1 << 9, 1 << 10
 # every symbol include/elemdp.h declares
 SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "elemdp_create", "elemdp_destroy",
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
-           "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_train_eval",
+           "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
            "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
@@ -76,6 +76,8 @@ def load_library():
         L.elemdp_batch_pairs.argtypes = [hp, C.c_int32, u8, dp, C.c_int32]
         L.elemdp_useful_mask.argtypes = [hp, C.c_int32, u8, C.c_int32]
         L.elemdp_useful_mask_host.argtypes = [u8, u8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, u8]
+        L.elemdp_live_blocks.argtypes = [hp, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.elemdp_live_blocks_host.argtypes = [u8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]
         L.elemdp_train_eval.argtypes = [hp, dp, C.c_int32, dp, dp, dp, i32]
         L.elemdp_train_partial.argtypes = [hp, dp, C.c_int32, C.c_void_p, C.c_int32]
         L.elemdp_train_finish.argtypes = [hp, dp, dp, dp, dp, i32]
@@ -145,6 +147,40 @@ def useful_mask_host(kept, max_iloop=30, flags=0, unp=None):
     if rc:
         raise ElemdpError(rc, "useful_mask_host")
     return out
+
+
+# a record of the live-block lists (elemdp_live_blocks): 16 bytes
+LIVE_BLOCK = np.dtype([("live", "<u8"), ("first", "<i2"), ("own_lo", "<i2"), ("own_end", "<i2"), ("count", "<i2")])
+
+
+def _live_block_lists(counts, recs):
+    """[d] -> list of blocks (first cell, [live cells], (own_lo, own_end)) from the records of elemdp_live_blocks*."""
+    out = []
+    for d in range(len(counts)):
+        row = []
+        for r in recs[d, :counts[d]]:
+            first, live = int(r["first"]), int(r["live"])
+            cells = [first + k for k in range(64) if (live >> k) & 1]
+            assert len(cells) == int(r["count"])
+            row.append((first, cells, (int(r["own_lo"]), int(r["own_end"]))))
+        out.append(row)
+    return out
+
+
+def live_blocks_host(mask, cpb, cap):
+    """Live-block lists of one sequence on the CPU from a mask [(W+1), (L+1)] (any non-zero byte is a live cell): per diagonal d
+    the blocks (first cell, [live cells], (own_lo, own_end)) of at most `cpb` live cells that span at most `cap` cells (host;
+    elemdp_live_blocks_host).  cap < cpb is refused."""
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    W, L = mask.shape[0] - 1, mask.shape[1] - 1
+    stride = (L + cpb) // max(int(cpb), 1) if cpb >= 1 else 1
+    counts = np.zeros(W + 1, dtype=np.int32)
+    recs = np.zeros((W + 1, max(stride, 1)), dtype=LIVE_BLOCK)
+    rc = load_library().elemdp_live_blocks_host(_u8(mask), L, W, int(cpb), int(cap), counts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                recs.ctypes.data_as(C.c_void_p), recs.shape[1])
+    if rc:
+        raise ElemdpError(rc, "live_blocks_host")
+    return _live_block_lists(counts, recs)
 
 
 class Engine:
@@ -229,6 +265,23 @@ class Engine:
         out = np.zeros((W + 1, L + 1), dtype=np.uint8)
         self._check(self._lib.elemdp_useful_mask(self._h, index, _u8(out), out.size))
         return out
+
+    def live_blocks(self, index, with_taken=False):
+        """The live-block lists of sequence `index` for the model's cells per block and the span of the current options:
+        (lists, cpb, cap), lists as live_blocks_host gives them; with_taken: also a bool array [W+1], True where a train
+        evaluation of the current options sweeps that diagonal from its list (False: consecutive cells)."""
+        L = int(self._off[index + 1] - self._off[index])
+        W = min(L, self.max_span)
+        stride = (L + 8) // 8
+        counts = np.zeros(W + 1, dtype=np.int32)
+        recs = np.zeros((W + 1, stride), dtype=LIVE_BLOCK)
+        cc = np.zeros(2, dtype=np.int32)
+        taken = np.zeros(W + 1, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self._lib.elemdp_live_blocks(self._h, index, counts.ctypes.data_as(ip), recs.ctypes.data_as(C.c_void_p),
+                                                 stride, cc.ctypes.data_as(ip), taken.ctypes.data_as(ip)))
+        out = (_live_block_lists(counts, recs), int(cc[0]), int(cc[1]))
+        return out + (taken != 0,) if with_taken else out
 
     # ---- training: == RNAelemTrainer::operator()
     def train_eval(self, x):

@@ -134,6 +134,7 @@ struct ModelView {
   ELEMDP_HD int param_index(int row, int col) const { return ints[lay.row_off + row] + col; }
 };
 
+struct LiveBlock;   // (live_blocks.h)
 struct SeqView {
   int32_t L, W, C;
   const uint8_t* seq;        // L base codes 0..4
@@ -166,6 +167,8 @@ struct SeqView {
   // usefulness mask of the train sweeps (plan_rules.h: UB_* bits per cell, [d][i] like the tables); null: every entry is useful
   const uint8_t* useful = nullptr;
   ELEMDP_HD int ubits(int i, int d) const { return useful ? (int)useful[d * (L + 1) + i] : 0xff; }
+  // live-block lists of the train sweeps (live_blocks.h); null: a workgroup takes consecutive cells
+  const LiveBlock* blocks = nullptr;
 
   ELEMDP_HD int cell(int i, int d) const { return i * (W + 1) + d; }
   ELEMDP_HD bool pair_ok(int i, int d) const {  // is_parsable<ST_P>

@@ -35,6 +35,7 @@
 #include "host_prep.h"
 #include "kernels.h"
 #include "lin_params.h"
+#include "live_blocks.h"
 #include "sample_rules.h"
 
 namespace elemdp {
@@ -207,6 +208,13 @@ struct PlanSet {
   // (Engine::ensure_useful_mask): a batch that is only scanned never pays for it
   DevBuf useful;
   bool useful_built = false;
+  // live-block lists of the train sweeps (PlanArrays::blocks; Engine::ensure_live_blocks) for `blk_cpb` cells per block that span
+  // at most `blk_cap` cells, and the largest block count of every diagonal over the set (host copy: the grids)
+  DevBuf blocks, blk_max;
+  int64_t n_blocks = 0;
+  int blk_cpb = 0, blk_cap = 0;
+  std::vector<int32_t> h_blk_max, h_blk_grid;
+  bool blk_all = false;            // built under live_blocks 2 (lists on every diagonal)
   int64_t n_cells = 0;
   bool permuted = false;   // keep item copies in the secondary orders (resident plan of the train pipeline)
   bool inner_only = false; // build only the by_inner order (the BPP filter needs no outside values of loop cells)
@@ -236,6 +244,7 @@ class Engine {
   ~Engine();
 
   void useful_mask(int idx, uint8_t* mask, int cap);
+  void live_blocks(int idx, int32_t* counts, void* records, int stride, int32_t* cpb_cap, int32_t* taken);
   int n_param() const { return au_.n_theta() + 2; }
   int n_state() const { return au_.S(); }
   int n_node() const { return au_.M(); }
@@ -297,6 +306,9 @@ class Engine {
   void build_planset(PlanSet& ps, int first, int count, const uint32_t* d_okbits);
   void ensure_sorted_plan();
   void ensure_useful_mask();
+  bool ensure_live_blocks(int cpb, int cap);
+  int live_span_for(int cpb) const;
+  bool lists_wanted() const;
   LdsLayout lds_layout(const AutomatonLayout& lay, int Lmax, int nword_max, bool scan) const;
   DpArgs base_args(const AutomatonLayout& lay, const int32_t* d_ints, const double* d_params, const PlanSet& ps,
                    const uint32_t* d_okbits, int S);
@@ -458,6 +470,9 @@ class Engine {
   // 4 = scaled-linear batch pipeline (lin_kernels.hip), 3 = log-space batch pipeline, 2 = fused one-workgroup-per-sequence kernel
   int opt_pipeline_ = 4;
   bool opt_useful_mask_ = true;    // option "useful_mask": the train sweeps skip the entries no complete parse reaches
+  int opt_live_blocks_ = 1;        // option "live_blocks": a workgroup of the train sweeps takes cpb LIVE cells of its diagonal;
+                                   // 2: on every diagonal, also where the lists save no workgroups
+  int opt_live_span_ = 0;          // option "live_span": the cells a block may span (0: kLiveSpanDefault, at least cpb)
   int opt_useful_lds_kb_ = 150;    // option "useful_mask_lds_kb": k_useful_mask's LDS budget; a larger sequence gets the all-ones mask
   bool opt_sorted_plan_ = false;   // option "sorted_plan": sort the role lists at load_batch whatever the pipeline
   // scaled-linear pipeline
@@ -658,6 +673,14 @@ void Engine::set_option(const std::string& key, double v) {
   else if (key == "deterministic") opt_det_ = v != 0;
   else if (key == "sorted_plan") opt_sorted_plan_ = v != 0;
   else if (key == "useful_mask") opt_useful_mask_ = v != 0;
+  else if (key == "live_blocks") {
+    if (v < 0 || v > 2) throw ArgError("live_blocks: 0, 1 or 2");
+    opt_live_blocks_ = (int)v;
+  }
+  else if (key == "live_span") {   // (0: the default; a model with more cells per block than the value takes its cells per block)
+    if (v < 0 || v > lin_live_span_max()) throw ArgError("live_span: 0 (default) or cells per block .. " + std::to_string(lin_live_span_max()));
+    opt_live_span_ = (int)v;
+  }
   else if (key == "useful_mask_lds_kb") {   // (at most what a workgroup can have; takes effect for the masks built after it)
     if (v < 0 || v > 150) throw ArgError("useful_mask_lds_kb: 0 .. 150");
     opt_useful_lds_kb_ = (int)v;
@@ -753,11 +776,14 @@ void Engine::build_planset(PlanSet& ps, int first, int count, const uint32_t* d_
   ps.first = first;
   ps.count = count;
   ps.h.assign(h_plans_.begin() + first, h_plans_.begin() + first + count);
-  int64_t dmin_b = 0, cell_b = 0, off_b = 0, bits_end = 0, ncell_max = 0;
+  int64_t dmin_b = 0, cell_b = 0, off_b = 0, bits_end = 0, ncell_max = 0, blk_b = 0;
   int lmax = 0, wmax1 = 0;
   for (auto& p : ps.h) {
     const int64_t nc = (int64_t)(p.L + 1) * (p.W + 1);
     p.dmin_base = dmin_b; p.cell_base = cell_b; p.off_base = off_b; p.item_base = 0; p.n_items = 0;
+    // (the lists are addressed by an int: a set too large for that gets none)
+    p.blk_base = blk_b >= 0 ? (int32_t)blk_b : 0;
+    if (blk_b >= 0) { blk_b += live_blocks_records(p.L, p.W); if (blk_b > 0x7fffffffll) blk_b = -1; }
     dmin_b += p.L + 1; cell_b += nc; off_b += nc + 1;
     bits_end = std::max<int64_t>(bits_end, p.bits_base + (nc + 31) / 32);
     ncell_max = std::max(ncell_max, nc);
@@ -765,7 +791,9 @@ void Engine::build_planset(PlanSet& ps, int first, int count, const uint32_t* d_
     wmax1 = std::max(wmax1, (int)p.W + 1);
   }
   ps.n_cells = cell_b;
+  ps.n_blocks = blk_b;
   ps.useful_built = false;   // (the mask follows the pair mask: ensure_useful_mask builds it again)
+  ps.blk_cpb = ps.blk_cap = 0;   // (and the lists follow the mask)
   d_okbits_end_.alloc(sizeof(uint32_t) * (size_t)bits_end);   // the pair mask by (end, span): scratch of the item enumeration
   ps.d_plans.upload(ps.h, st_);
   const bool chunked = ps.inner_only;   // the plan of the unfiltered mask is rebuilt chunk after chunk: its buffers only grow
@@ -828,6 +856,36 @@ void Engine::ensure_useful_mask() {
   plan_.ka.m_min = m_min();
   HIP_OK(launch_useful_mask(plan_.ka, (size_t)plan_.n_cells, (size_t)opt_useful_lds_kb_ * 1024, st_));
   plan_.useful_built = true;
+  plan_.blk_cpb = plan_.blk_cap = 0;
+}
+
+// The live-block lists of the resident plan for blocks of `cpb` cells that span at most `cap`, from its mask; the largest block
+// count per diagonal is read back once (W + 1 ints: the grids of the train sweeps).  False: no lists for this plan / geometry.
+bool Engine::ensure_live_blocks(int cpb, int cap) {
+  if (plan_.count <= 0 || plan_.n_blocks <= 0 || cpb < kLiveCpbMin || cap < cpb || cap > kLiveSpanMax) return false;
+  ensure_useful_mask();
+  if (plan_.blk_cpb == cpb && plan_.blk_cap == cap && plan_.blk_all == (opt_live_blocks_ >= 2)) return true;
+  plan_.blocks.alloc(sizeof(LiveBlock) * (size_t)plan_.n_blocks);
+  plan_.blk_max.alloc(sizeof(int32_t) * 3 * (size_t)plan_.ka.wmax1);
+  PlanKernelArgs a = plan_.ka;
+  a.p.useful = plan_.useful.as<uint8_t>();
+  a.p.blocks = plan_.blocks.as<LiveBlock>();
+  a.blk_max = plan_.blk_max.as<int32_t>();
+  a.live_cpb = cpb; a.live_cap = cap;
+  HIP_OK(launch_live_blocks(a, (size_t)plan_.n_blocks, st_));
+  plan_.h_blk_max.assign(3 * (size_t)a.wmax1, 0);
+  HIP_OK(hipMemcpyAsync(plan_.h_blk_max.data(), a.blk_max, sizeof(int32_t) * 3 * (size_t)a.wmax1, hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  // the grid of every diagonal: its largest block count, or -1 where the lists leave too many of the workgroups (kLiveKeepPct)
+  plan_.h_blk_grid.assign((size_t)a.wmax1, 0);
+  for (int d = 0; d < a.wmax1; ++d) {
+    const long long nb = plan_.h_blk_max[a.wmax1 + d], nw = plan_.h_blk_max[2 * a.wmax1 + d];
+    plan_.h_blk_grid[d] = (opt_live_blocks_ >= 2 || nb * 100 <= nw * kLiveKeepPct) ? plan_.h_blk_max[d] : -1;
+    if (getenv("ELEMDP_PLAN_DEBUG")) fprintf(stderr, "live blocks d %d: most %d, blocks %lld, working without lists %lld%s\n", d, plan_.h_blk_max[d], nb, nw, plan_.h_blk_grid[d] < 0 ? " (consecutive)" : "");
+  }
+  plan_.blk_all = opt_live_blocks_ >= 2;
+  plan_.blk_cpb = cpb; plan_.blk_cap = cap;
+  return true;
 }
 
 void Engine::ensure_sorted_plan() {
@@ -1229,6 +1287,8 @@ void Engine::resident_plan(const uint32_t* mask) {
   lin_slots_ = 0;
   out_stride_ = 6 + 2 * au_.n_theta() + 4;
   d_seq_out_.alloc(sizeof(double) * (size_t)out_stride_ * n);
+  // (a ranged evaluation writes the rows of its range only: the rows of a new batch start as zeros, not as what the memory held)
+  HIP_OK(hipMemsetAsync(d_seq_out_.as<void>(), 0, sizeof(double) * (size_t)out_stride_ * n, st_));
   n_slots_ = 0;
   HIP_OK(hipStreamSynchronize(st_));
   dbg_lap("load: weights / output buffers");
@@ -1614,6 +1674,15 @@ void Engine::run_lin_batch() {
   int gsz = prepare_lin(a, sched1, false, n_ev);
   if (opt_useful_mask_) ensure_useful_mask();
   a.p.useful = opt_useful_mask_ ? plan_.useful.as<uint8_t>() : nullptr;   // (the train sweeps only: the scan family sees null)
+  // ... and with it the live-block lists (not in the deterministic mode, whose sums follow the grouping of consecutive cells)
+  if (lists_wanted()) {
+    const int cpb = lin_train_cpb(a), cap = live_span_for(cpb);
+    if (cpb > 0 && ensure_live_blocks(cpb, cap)) {
+      a.p.blocks = plan_.blocks.as<LiveBlock>();
+      a.live_span = cap;
+      a.blk_grid = plan_.h_blk_grid.data();
+    }
+  }
   const int32_t* h_ord = h_order_.data();
   const int32_t* d_ord = d_order_.as<int32_t>();
   const SeqPlan* d_sorted = d_plans_sorted_.as<SeqPlan>();
@@ -1899,6 +1968,48 @@ void Engine::batch_pairs(int idx, uint8_t* kept, double* lnbpp, int cap) {
     for (int c = 0; c < nc; ++c)
       lnbpp[c] = ((w0[c >> 5] >> (c & 31)) & 1u) ? h_lnbpp_[h_lnbpp_base_[idx] + c] : -std::numeric_limits<double>::infinity();
   }
+}
+
+// Does a train evaluation take the plan's lists (where the model's kernels take any)?  Not without the mask, and not in the
+// deterministic mode, whose sums follow the grouping of consecutive cells.
+bool Engine::lists_wanted() const { return opt_useful_mask_ && opt_live_blocks_ && !opt_det_; }
+
+// the span a block of `cpb` live cells may cover: option live_span, or the default
+int Engine::live_span_for(int cpb) const {
+  // (never below cpb: a block of cpb consecutive live cells must fit, and only then is ceil(ncell / cpb) blocks enough -- a model
+  // with more cells per block than the option asks for takes cpb)
+  return std::max(cpb, opt_live_span_ > 0 ? opt_live_span_ : std::min(kLiveSpanDefault, lin_live_span_max()));
+}
+
+// The lists of sequence idx for the cells per block and the span of the current options (built here if no evaluation has):
+// counts[d] blocks of diagonal d at records + d * stride (16-byte LiveBlock records); cpb_cap = {cells per block, span};
+// taken[d] (may be null) = 1 where a train evaluation of the current options sweeps diagonal d from its list.
+void Engine::live_blocks(int idx, int32_t* counts, void* records, int stride, int32_t* cpb_cap, int32_t* taken) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (streaming_) throw StateError("live_blocks needs a resident batch (the handle streams this one in chunks)");
+  if (idx < 0 || idx >= n_seq_) throw ArgError("live_blocks: bad sequence index");
+  const SeqPlan& p = h_plans_[idx];
+  const bool sched1 = opt_schedule_ == 1 && linear_ok_ && !opt_first_pass_only_ && lay_.s00 == 0 && lays_.shadow >= 0;
+  LinArgs a;
+  prepare_lin(a, sched1, false, n_seq_);
+  const int cpb = lin_train_cpb(a);
+  if (cpb <= 0) throw StateError("live_blocks: the train sweeps of this model do not take lists");
+  const int cap = live_span_for(cpb);
+  if (stride < live_blocks_slots(p.L)) throw ArgError("live_blocks: stride too small");
+  if (!ensure_live_blocks(cpb, cap)) throw StateError("live_blocks: no lists for this batch");
+  HIP_OK(hipStreamSynchronize(st_));
+  std::vector<LiveBlock> h((size_t)live_blocks_records(p.L, p.W));
+  HIP_OK(hipMemcpy(h.data(), plan_.blocks.as<LiveBlock>() + p.blk_base, sizeof(LiveBlock) * h.size(), hipMemcpyDeviceToHost));
+  LiveBlock* out = static_cast<LiveBlock*>(records);
+  for (int d = 0; d <= p.W; ++d) {
+    counts[d] = h[d].count;
+    for (int b = 0; b < counts[d]; ++b) out[(size_t)d * stride + b] = h[(size_t)live_blocks_at(p.L, p.W, d) + b];
+  }
+  cpb_cap[0] = cpb; cpb_cap[1] = cap;
+  // which diagonals a train evaluation of the current options sweeps from these lists
+  const bool want = lists_wanted();
+  if (taken) for (int d = 0; d <= p.W; ++d) taken[d] = (want && plan_.h_blk_grid[d] >= 0) ? 1 : 0;
 }
 
 void Engine::useful_mask(int idx, uint8_t* mask, int cap) {
@@ -2499,6 +2610,21 @@ int elemdp_useful_mask(elemdp_handle* h, int32_t seq_index, uint8_t* mask, int32
   if (!h || !mask) throw elemdp::ArgError("elemdp_useful_mask: null argument");
   h->e->useful_mask(seq_index, mask, cap);
   ELEMDP_CATCH
+}
+int elemdp_live_blocks(elemdp_handle* h, int32_t seq_index, int32_t* counts, void* records, int32_t stride, int32_t* cpb_cap,
+                       int32_t* taken) {
+  ELEMDP_TRY
+  if (!h || !counts || !records || !cpb_cap) throw elemdp::ArgError("elemdp_live_blocks: null argument");
+  h->e->live_blocks(seq_index, counts, records, stride, cpb_cap, taken);
+  ELEMDP_CATCH
+}
+int elemdp_live_blocks_host(const uint8_t* mask, int32_t L, int32_t W, int32_t cpb, int32_t cap, int32_t* counts, void* records,
+                            int32_t stride) {
+  if (!mask || !counts || !records || L < 0 || W < 0 || W > L || cpb < 1 || cap < cpb || cap > elemdp::kLiveSpanMax ||
+      stride < (L + cpb) / cpb)
+    return ELEMDP_EINVAL;
+  elemdp::live_blocks_host(mask, L, W, cpb, cap, counts, static_cast<elemdp::LiveBlock*>(records), stride);
+  return ELEMDP_OK;
 }
 int elemdp_useful_mask_host(const uint8_t* kept, const uint8_t* unp, int32_t L, int32_t W, int32_t max_iloop, int32_t flags,
                             uint8_t* mask) {

@@ -8,6 +8,7 @@
 #include "device_layout.h"
 #include "energy_tables.h"
 #include "bpp_cand.h"
+#include "live_blocks.h"
 
 namespace elemdp {
 
@@ -27,6 +28,9 @@ struct PlanArrays {
   // usefulness mask of the train sweeps (plan_rules.h: UB_* bits), one byte per cell at cell_base + d * (L+1) + i; null: every
   // entry counts as useful
   uint8_t* useful = nullptr;
+  // live-block lists of the train sweeps (live_blocks.h: LiveBlock, W + 1 headers and the records of every diagonal from
+  // SeqPlan::blk_base on); null: a workgroup takes cpb consecutive cells
+  LiveBlock* blocks = nullptr;
 };
 
 // static per-batch arrays
@@ -52,6 +56,11 @@ struct PlanKernelArgs {
   int32_t n_roles = 3;   // 1: only the by_inner order (plan of the BPP filter)
   int32_t sort_roles = 1;   // sort every segment of the role lists by item index (reproducible summation order of the gathers)
   int32_t count_fast = 0;   // loop_tables_finite and no imposed structure: the count pass takes popcounts (count_interior_by_end)
+  // live-block lists (launch_live_blocks): cells per block and the span a block may cover; blk_max: three rows of wmax1 ints over
+  // the sequences of the set (cleared by the launcher) -- the most blocks of diagonal d, the sum of its blocks, and the sum of
+  // the workgroups of cpb consecutive cells that hold a live cell
+  int32_t live_cpb = 0, live_cap = 0;
+  int32_t* blk_max = nullptr;
 };
 
 // byte offsets of the dynamic LDS regions of the DP kernels
@@ -229,6 +238,11 @@ struct LinArgs {
   int32_t det_sh;                 // log2 of the lanes a cell's pairs take in the pair phases of the deterministic mode (a power of two
                                   // >= n_ap, so that no cell straddles two waves); -1: more than 64 pairs, one wave does the phase
   double* det_rows; int32_t det_nslot;
+  // train sweeps from the live-block lists of the plan (p.blocks non-null): the cells a block may span (the window of positions a
+  // workgroup stages; 0 without lists: cpb) and, for the launcher alone, the HOST array of the largest block count per diagonal
+  // (negative: this diagonal keeps consecutive cells)
+  int32_t live_span;
+  const int32_t* blk_grid;
 };
 struct LinWeightArgs {
   const LoopItem* items_inner; const LoopItem* items_left; const LoopItem* items_right;   // (may be null)
@@ -260,6 +274,16 @@ hipError_t launch_plan_cells(const PlanKernelArgs& a, int32_t* n_items_out, hipS
 hipError_t launch_plan_items(const PlanKernelArgs& a, hipStream_t st);
 hipError_t launch_useful_mask(const PlanKernelArgs& a, size_t n_cells, size_t lds_cap, hipStream_t st);   // needs dmin (launch_plan_cells)
 void useful_mask_host(const uint8_t* kept, const uint8_t* unp, int L, int W, int C, int m_min, bool no_ene, uint8_t* out);
+// the live-block lists of every sequence of the set from its mask (a.p.useful -> a.p.blocks of n_records records, a.blk_max),
+// cells per block a.live_cpb
+hipError_t launch_live_blocks(const PlanKernelArgs& a, size_t n_records, hipStream_t st);
+// the same lists on the host from a mask [d][i] of (W+1) * (L+1) bytes: counts[d] blocks of diagonal d at records + d * stride
+// (stride >= ceil((L + 1) / cpb) records of 16 bytes)
+void live_blocks_host(const uint8_t* mask, int L, int W, int cpb, int cap, int32_t* counts, LiveBlock* records, int stride);
+// cells per block of the table-driven train sweeps of these arguments, 0 where they run another form (no lists then); the
+// largest span a block's live cells may cover in this build
+int lin_train_cpb(const LinArgs& full);
+int lin_live_span_max();
 hipError_t launch_plan_sort(const PlanKernelArgs& a, hipStream_t st);   // the sort of launch_plan_items alone (sort_roles = 0 before)
 hipError_t launch_permute_items(const PlanKernelArgs& a, hipStream_t st);
 bool plan_copies_fused(const PlanKernelArgs& a);   // launch_plan_items has written the item copies already (no launch_permute_items)

@@ -872,6 +872,27 @@ __global__ __launch_bounds__(kThreads) void k_useful_mask(PlanKernelArgs a) {
   for (int c = tid; c < n; c += kThreads) out[c] = m[c];
 }
 
+// K-plan 6: the live-block lists of the train sweeps from the finished mask (plan_rules.h: live_blocks_row), lane = (sequence,
+// diagonal): the header of the diagonal gets its block count, blk_max[d] the largest count of the set.  A sequence with the mask
+// of all ones gets consecutive blocks by the same rule.
+__global__ __launch_bounds__(kThreads) void k_live_blocks(PlanKernelArgs a) {
+  const int t = blockIdx.x * kThreads + threadIdx.x;
+  const int n = t / a.wmax1, d = t - n * a.wmax1;
+  if (n >= a.count) return;
+  const SeqPlan p = a.plans[a.first + n];
+  if (d > p.W) return;
+  LiveBlock* base = a.p.blocks + p.blk_base;
+  const int ncell = p.L - d + 1;
+  const int nb = ncell > 0 ? live_blocks_row(a.p.useful + p.cell_base + (size_t)d * (p.L + 1), ncell, a.live_cpb, a.live_cap,
+                                             base + live_blocks_at(p.L, p.W, d)) : 0;
+  base[d] = LiveBlock{0ull, 0, 0, 0, (int16_t)nb};
+  if (nb > 0) {      // [largest count | blocks | workgroups of consecutive cells with a live one] of the diagonal over the set
+    atomicMax(&a.blk_max[d], nb);
+    atomicAdd(&a.blk_max[a.wmax1 + d], nb);
+    atomicAdd(&a.blk_max[2 * a.wmax1 + d], working_blocks_row(a.p.useful + p.cell_base + (size_t)d * (p.L + 1), ncell, a.live_cpb));
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -981,6 +1002,24 @@ hipError_t launch_useful_mask(const PlanKernelArgs& a, size_t n_cells, size_t ld
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_useful_mask, dim3(a.count), dim3(kThreads), lds, st, a);
   return hipGetLastError();
+}
+hipError_t launch_live_blocks(const PlanKernelArgs& a, size_t n_records, hipStream_t st) {
+  if (a.count <= 0 || !a.p.useful || !a.p.blocks || !a.blk_max) return hipSuccess;
+  if (a.live_cpb < kLiveCpbMin || a.live_cap < a.live_cpb || a.live_cap > kLiveSpanMax) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(a.blk_max, 0, sizeof(int32_t) * 3 * a.wmax1, st);
+  if (e != hipSuccess) return e;
+  // (the slots behind the last block of a diagonal read as "no block": the band kernels load their slot without a count)
+  e = hipMemsetAsync(a.p.blocks, 0, n_records * sizeof(LiveBlock), st);
+  if (e != hipSuccess) return e;
+  const long long lanes = (long long)a.count * a.wmax1;
+  hipLaunchKernelGGL(k_live_blocks, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a);
+  return hipGetLastError();
+}
+void live_blocks_host(const uint8_t* mask, int L, int W, int cpb, int cap, int32_t* counts, LiveBlock* records, int stride) {
+  for (int d = 0; d <= W; ++d) {
+    const int ncell = L - d + 1;
+    counts[d] = ncell > 0 ? live_blocks_row(mask + (size_t)d * (L + 1), ncell, cpb, cap, records + (size_t)d * stride) : 0;
+  }
 }
 // the same sweep on the host from a kept-pair matrix kept[(L+1)][(W+1)] (no GPU needed); unp: L flags or null (all unpaired
 // positions allowed); out: (W+1) * (L+1) bytes, [d][i]

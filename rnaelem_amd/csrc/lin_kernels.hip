@@ -193,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void k4_weights(LinWeightArgs a) {
 // window of positions the workgroup touches, small int arrays, the automaton blob, and the dmin / base / unpaired
 // windows.  With the context in LDS the unary phase has a single level of global loads (the tables themselves).
 struct BlockLds {
-  int lin, ews, ints, dm, cnts, pre, base, blob, bits, bits2, dmin16, seq8, unp8, crec, crfl, total;   // byte offsets
+  int lin, ews, ints, dm, lof, cnts, pre, base, blob, bits, bits2, dmin16, seq8, unp8, crec, crfl, total;   // byte offsets
 };
 // LDS doubles of the item-record area of k4_in / k5_cyk (one role) and of k4_out (three roles)
 constexpr int kRecIn = ELEMDP_RECIN, kRecOut = ELEMDP_RECOUT;
@@ -223,8 +223,11 @@ struct BitIter {
   }
 };
 // crd: doubles per cell record of the table-driven unary phase (lin_fast.h), 0 = none
-__host__ __device__ inline BlockLds block_lds(int nd, int cpb, int n_lin, int win, int n_stage, int nv = 0, int crd = 0) {
+// sp: the cells the workgroup's window spans -- cpb (0), or the cap of the live-block lists (train sweeps: the cells of a block
+// lie up to `sp` apart); win = sp + W + 3 positions
+__host__ __device__ inline BlockLds block_lds(int nd, int cpb, int n_lin, int win, int n_stage, int nv = 0, int crd = 0, int sp = 0) {
   BlockLds b;
+  if (sp < cpb) sp = cpb;
   if (nv < cpb) nv = cpb;   // CSR ranges of the item sums: one per cell, or one per (role, cell) in k4_out
   int o = nd * 8;
   b.lin = o; o += n_lin * 8;
@@ -233,13 +236,14 @@ __host__ __device__ inline BlockLds block_lds(int nd, int cpb, int n_lin, int wi
   b.crfl = o; o += crd ? ((cpb + 1) / 2) * 8 : 0;
   b.ints = o;
   b.dm = o; o += cpb * 4;
+  b.lof = o; o += cpb * 4;      // offsets of the workgroup's cells from its first one (train sweeps)
   b.cnts = o; o += nv * 4;
   b.pre = o; o += (nv + 1) * 4;
   b.base = o; o += nv * 4;
   b.blob = o; o += n_stage * 4;
-  // pair-mask words of the rows i0-1 .. i0+cpb+W (k4_out also reads the stems that start at the cells' ends); win = cpb + W + 3
-  b.bits = o; o += ((win * (win - cpb - 2) + 31) / 32 + 3) * 4;
-  b.bits2 = o; o += (((cpb + 1) * (win - cpb - 2) + 31) / 32 + 3) * 4;   // end-indexed mask, rows i0+d .. i0+d+cpb (k4_in)
+  // pair-mask words of the rows i0-1 .. i0+sp+W (k4_out also reads the stems that start at the cells' ends); win = sp + W + 3
+  b.bits = o; o += ((win * (win - sp - 2) + 31) / 32 + 3) * 4;
+  b.bits2 = o; o += (((sp + 1) * (win - sp - 2) + 31) / 32 + 3) * 4;   // end-indexed mask, rows i0+d .. i0+d+sp (k4_in)
   b.dmin16 = o; o += ((win + 1) / 2) * 4;
   b.seq8 = o; o += ((win + 3) / 4) * 4;
   b.unp8 = o; o += ((win + 3) / 4) * 4;
@@ -260,9 +264,11 @@ __host__ __device__ inline int staged_ints(const AutomatonLayout& L, int n_stage
 
 // stages the context and redirects the views to it; positions [p0, p0+len) = [i0-1, i0+nc+d] clipped to [0, L].
 // FAST: only the fast blob of the direction is staged (AutomatonLayout::fb_*); the generic lists stay in global memory.
+// The workgroup's cells are i0 .. i0 + nc - 1; a block of live cells (train sweeps) passes the cells it spans as `nc` and the
+// cell of lane `tid` (tid < cells of the block) as i_lane.
 template <bool BIG, int PART, bool FAST = false>
 __device__ __forceinline__ BlockCtx stage_context(const LinArgs& a, LViews& v, unsigned char* raw, const BlockLds& B, int i0, int nc,
-                                                  int d, int cpb) {
+                                                  int d, int cpb, int i_lane = -1) {
   const int tid = threadIdx.x;
   const int L = v.q.L;
   // (the outside kernel also needs dmin of the rows i - b, b <= W - d, whose pair entries feed HA: lheavy_o2)
@@ -311,7 +317,7 @@ __device__ __forceinline__ BlockCtx stage_context(const LinArgs& a, LViews& v, u
   const int16_t r_dmin = v.q.dmin[pw];
   const uint8_t r_unp = v.q.unp[pw];
   const uint8_t r_seq = v.q.seq[pw < L ? pw : (L > 0 ? L - 1 : 0)];
-  const int16_t r_dm = v.q.dmin[i0 + (tid < nc ? tid : 0)];
+  const int16_t r_dm = v.q.dmin[i_lane >= 0 ? i_lane : i0 + (tid < nc ? tid : 0)];
 #pragma unroll
   for (int u = 0; u < kU; ++u) {
     const int t = tid + u * kBT;
@@ -345,7 +351,7 @@ __device__ __forceinline__ BlockCtx stage_context(const LinArgs& a, LViews& v, u
   c.cnts = reinterpret_cast<int*>(raw + B.cnts);
   c.pre = reinterpret_cast<int*>(raw + B.pre);
   c.base = reinterpret_cast<int*>(raw + B.base);
-  if (tid < cpb) c.dm[tid] = (tid < nc) ? (int)r_dm : 0;
+  if (tid < cpb) c.dm[tid] = (tid < nc || i_lane >= 0) ? (int)r_dm : 0;
   if (!FAST) {
     v.m.ints = blob;
     v.in.cm = v.out.cm = blob + a.lay.tab_cmap;
@@ -508,9 +514,11 @@ __device__ __forceinline__ OuterRecs outer_recs(double* area, int n_doubles) {
 // ranges + prefix; returns the number of records of the workgroup
 // (two halves: the CSR loads are issued before the pair phase of the kernel, whose own loads they travel with; the prefix
 // follows behind the barrier that ends the pair phase)
-__device__ __forceinline__ void outer_ranges_load(const LViews& v, int i0, int nc, int d, bool on, int tid, int* cnts, int* base) {
+// (lof: the offsets of the cells from i0 -- a block of live cells --, or null: consecutive)
+__device__ __forceinline__ void outer_ranges_load(const LViews& v, int i0, int nc, int d, bool on, int tid, int* cnts, int* base,
+                                                  const int* lof = nullptr) {
   for (int c = tid; c < nc; c += kBT) {
-    const int i = i0 + c;
+    const int i = i0 + (lof ? lof[c] : c);
     int n0 = 0, n1 = 0;
     if (on && v.q.e_ok(i, d)) { const int cell = v.q.cell(i, d); n0 = v.q.by_outer_off[cell]; n1 = v.q.by_outer_off[cell + 1]; }
     base[c] = n0;
@@ -626,8 +634,50 @@ __device__ __forceinline__ void fill_dead_rows(const TableView& T, int d, int i0
   }
 }
 
+// the same zeros for the DEAD cells among lo .. hi - 1 only: what a block of live cells owes the cells it owns.  The live ones are
+// the set bits of `live` from cell `first` on (no load: the record is in scalar registers)
+__device__ __forceinline__ void fill_dead_cells(const TableView& T, unsigned long long live, int first, int d, int lo, int hi, int tid,
+                                                int e0, int e1, int e2, int e3) {
+  auto dead = [&](int i) { const int k = i - first; return k < 0 || k > 63 || !((live >> k) & 1ull); };
+  auto plane = [&](int e) {
+    if (e < 0) return;
+    const int rs = T.rs[e];
+    double* row = T.band + T.cidx(e, d, lo, 0);
+    for (int t = tid; t < (hi - lo) * rs; t += kBT) if (dead(lo + t / rs)) row[t] = 0.;
+  };
+  plane(e0); plane(e1); plane(e2); plane(e3);
+  if (T.ap) {
+    double* row = T.ap + T.aidx(d, lo, 0);
+    for (int t = tid; t < (hi - lo) * T.nAs; t += kBT) if (dead(lo + t / T.nAs)) row[t] = 0.;
+  }
+}
+// The cells of a workgroup of the train sweeps that take lists: block bx of the diagonal's live-block list (plan_rules.h).
+// sweep: false = nothing to sweep (beyond the list; workgroup 0 of a diagonal without a live cell still owns its zeros)
+struct LiveCells { int i0, nc, span, own_lo, own_end; unsigned long long live; bool sweep; };
+__device__ __forceinline__ LiveCells live_cells(const SeqView& q, int d, int bx, int ncell) {
+  LiveCells r;
+  // ONE load behind the plan record: the slots behind a diagonal's last block hold zeros (count 0), so the workgroup needs no count
+  const int nslot = live_blocks_slots(q.L), slot = bx < nslot ? bx : nslot - 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const LiveBlock __attribute__((address_space(4))) * ConstBlock;   // (uniform, read-only: scalar loads)
+  const LiveBlock b = *reinterpret_cast<ConstBlock>(reinterpret_cast<uintptr_t>(q.blocks + live_blocks_at(q.L, q.W, d) + slot));
+#else
+  const LiveBlock b = q.blocks[live_blocks_at(q.L, q.W, d) + slot];
+#endif
+  r.sweep = slot == bx && b.count > 0;
+  r.i0 = r.sweep ? b.first : 0;
+  r.nc = r.sweep ? b.count : 0;
+  r.live = r.sweep ? b.live : 0ull;
+  r.span = r.sweep ? 64 - __builtin_clzll(b.live | 1ull) : 0;
+  r.own_lo = r.sweep ? b.own_lo : 0;
+  r.own_end = r.sweep ? b.own_end : (bx == 0 ? ncell : 0);   // (no block 0: the diagonal has no live cell)
+  return r;
+}
+
 // FAST: table-driven phases (lin_fast.h; train schedule, the fast blob staged); FP: longest pair list of a state (2 or 3)
-template <bool BIG, bool CON, bool FAST = false, int FP = kFastP, bool W8 = false>
+// LISTS: the train form whose workgroups take the live cells of a block of the plan's lists (live_blocks.h) -- a form of its own, so
+// that the one of consecutive cells stays the code it was
+template <bool BIG, bool CON, bool FAST = false, int FP = kFastP, bool W8 = false, bool LISTS = false>
 __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4_in(LinArgs a) {
   extern __shared__ double lds[];
   // (the automaton layout is read from the kernel arguments: constant offsets, scalar registers)
@@ -640,11 +690,25 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
   make_lviews(a, by, v);
   const AutomatonLayout& A = a.lay;
   const int S = a.lay.S, NA = a.lay.n_active, d = a.d, cpb = a.cpb, tid = threadIdx.x;
-  // The workgroup owns cpb consecutive cells of the diagonal (nc cells from i0 on)
+  // The workgroup owns cpb consecutive cells of the diagonal (nc cells from i0 on), or -- the train form with the live-block
+  // lists of the plan -- the nc live cells i0 + lof[c] of block bx, which span `span` cells
   if (d > v.q.W) return;
-  const int ncell = v.q.L - d + 1, i0 = bx * cpb;
-  if (i0 >= ncell) return;
-  const int nc = (cpb < ncell - i0) ? cpb : ncell - i0;
+  constexpr bool MASK = FAST && !CON;   // the train form honours the usefulness mask (the scan passes get none)
+  const int ncell = v.q.L - d + 1;
+  static_assert(!LISTS || (FAST && !CON), "lists: the table-driven train form only");
+  constexpr bool lists = LISTS;
+  int i0 = bx * cpb, nc = 0, span = 0;
+  unsigned long long live = 0ull;
+  if (lists) {
+    const LiveCells lc = live_cells(v.q, d, (int)bx, ncell);
+    // (the zeros of the dead cells the block owns: an entry that is parsable but useless still has readers)
+    if (lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.in, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, ST_L, ST_2, ST_1, ST_M);
+    if (!lc.sweep) return;
+    i0 = lc.i0; nc = lc.nc; span = lc.span; live = lc.live;
+  } else {
+    if (i0 >= ncell) return;
+    nc = span = (cpb < ncell - i0) ? cpb : ncell - i0;
+  }
   if (CON) {
     // The start constraint touches the emissions of position Ys only: a cell whose span does not cover Ys -- and everything below
     // it -- has the value of the unconstrained pass, which is still in the table (same slot, same layout; the scan runs
@@ -652,8 +716,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
     const int ys = a.ys[v.n];
     if (ys < i0 || ys - d + 1 > i0 + nc - 1) return;
   }
-  constexpr bool MASK = FAST && !CON;   // the train form honours the usefulness mask (the scan passes get none)
-  if (MASK && block_is_dead(v.q, d, i0, nc, tid)) { fill_dead_rows(v.in, d, i0, nc, tid, ST_L, ST_2, ST_1, ST_M); return; }
+  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid)) { fill_dead_rows(v.in, d, i0, nc, tid, ST_L, ST_2, ST_1, ST_M); return; }
   const int HD = FAST ? A.n_lane : S;   // stride of the heavy sums per cell: the live states (table-driven: their index among them), or all
   const int CS = cpb * HD;
   constexpr int NW = 1;                      // (one copy of the heavy sums in either mode: see the deterministic mode above)
@@ -662,7 +725,17 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
   double* hbA = hb;
   double* heA = he;
   double* st1 = lds + NW * 2 * CS;           // item records (kRecIn doubles)
-  const BlockLds BL = block_lds(NW * 2 * CS + kRecIn, cpb, a.n_lin, cpb + a.wmax + 3, FAST ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, FAST ? kCellInD : 0);
+  const int SP = (MASK && a.live_span > cpb) ? a.live_span : cpb;   // cells the staged window spans
+  const BlockLds BL = block_lds(NW * 2 * CS + kRecIn, cpb, a.n_lin, SP + a.wmax + 3, FAST ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, FAST ? kCellInD : 0, SP);
+  // cell c of the workgroup: i0 + c, or the c-th live cell of the block (its offset in LDS; the non-train forms keep i0 + c at no cost)
+  int* lof = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(lds) + BL.lof);
+  // (a block whose live cells are consecutive -- most blocks of the short diagonals -- needs no offsets: no LDS, no barrier)
+  const bool gaps = lists && (live & (live + 1ull)) != 0ull;
+  if (gaps) {
+    if (tid < 64 && ((live >> tid) & 1ull)) lof[__popcll(live & ((1ull << tid) - 1ull))] = tid;
+    __syncthreads();
+  }
+  auto ci = [&](int c) -> int { return (LISTS && gaps) ? i0 + lof[c] : i0 + c; };
   // cell records of the table-driven unary phase: the exponentiated structural terms of the cells are fetched with the context
   // (lane = (cell, value); the addresses depend on the plan record only), the flags follow once the context is in LDS
   constexpr int kCRin = (ELEMDP_CPB_MAX * 8 + kBT - 1) / kBT;
@@ -673,12 +746,12 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
       crx[r] = 0.;
       if (r * kBT < cpb * 8) {   // (uniform: most automata need the first round only)
         const int t = tid + r * kBT, c = (t >> 3) < nc ? (t >> 3) : 0;
-        crx[r] = cell_in_fetch(v.q, d, i0 + c, t & 7);
+        crx[r] = cell_in_fetch(v.q, d, ci(c), t & 7);
       }
     }
   }
   if (a.dbg & 1024) { if (nc == 12345) lds[tid] = crx[0]; return; }   // (timing experiments: the workgroup up to its plan record ...
-  const BlockCtx cx = stage_context<BIG, 0, FAST>(a, v, reinterpret_cast<unsigned char*>(lds), BL, i0, nc, d, cpb);
+  const BlockCtx cx = stage_context<BIG, 0, FAST>(a, v, reinterpret_cast<unsigned char*>(lds), BL, i0, span, d, cpb, gaps ? ci(tid < nc ? tid : 0) : -1);
   int* dm = cx.dm; int* cnts = cx.cnts; int* pre = cx.pre; int* base = cx.base;
   const int32_t* G = v.m.big;
   double* crec = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(lds) + BL.crec);
@@ -692,12 +765,12 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
     for (int r = 0; r < kCRin; ++r) {
       const int t = tid + r * kBT, c = t >> 3, k = t & 7;
       if (c < nc) {
-        const bool on = k < 4 ? v.q.pair_ok(i0 + c, d) : v.q.e_ok(i0 + c, d);
+        const bool on = k < 4 ? v.q.pair_ok(ci(c), d) : v.q.e_ok(ci(c), d);
         crec[c * kCellInD + 2 + k] = on ? crx[r] : 0.;
       }
     }
     for (int c = tid; c < nc; c += kBT) {
-      const int i = i0 + c, j = i + d;
+      const int i = ci(c), j = i + d;
       int fl = cell_in_flags(v.m, v.q, d, i);
       if (CON) { const int ys = a.ys[v.n]; fl |= (i == ys ? CF_YL : 0) | (j - 1 == ys ? CF_YR : 0); }
       crfl[c] = fl;
@@ -708,7 +781,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
   const double* B = v.in.band;
   const int nq = ((a.dbg & 2) || (ELEMDP_KO & 2)) ? 0 : A.n_quad;
   // CSR ranges of the item sums of all cells of the workgroup (consumed behind the first pair phase, whose loads they travel with)
-  outer_ranges_load(v, i0, nc, d, nq > 0, tid, cnts, base);
+  outer_ranges_load(v, i0, nc, d, nq > 0, tid, cnts, base, gaps ? lof : nullptr);
   const RecAhead ahead{LoopItem{0., 0, 0, 0, 0}, 0, false};   // (records fetched ahead of the pair phase: two barriers more than the round trip saved, measured)
   // rule 2, factorised (lin_rules.h, lin_inside_apair): lane = (cell, pair p = (s1, t)).  A(i,j,p) = the tail step from
   // A(i,j-1,.) plus one term per stem (k, j) that ends at j and starts behind i; B(i,j,tgt(p)) += A(i,j,p).  The stems are
@@ -725,7 +798,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
     for (int w = one_wave ? ((tid < 64) ? tid : nwork) : tid; w < nwork; w += one_wave ? 64 : kBT) {
       const int c = (a.det && a.det_sh >= 0) ? (w >> a.det_sh) : div_rcp(w, a.rcp_nap), p = w - c * pad;
       if (p >= nA) continue;
-      const int i = i0 + c, j = i + d;
+      const int i = ci(c), j = i + d;
       if (FAST) {   // the same sums from the pair record (AutomatonLayout::fpr_in): columns, chain entries with their weight ids
         const int32_t* PR = G + A.fpr_in + 8 * p;
         const int r0 = PR[0], r1 = PR[1];
@@ -859,7 +932,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
         const LoopItem it = R.it[xc];
         const int meta = R.meta[xc];
         const int c = (meta >> 16) & 0x7fff;
-        const int i = i0 + c, j = i + d;
+        const int i = ci(c), j = i + d;
         const bool in_set = x < np && meta >= 0;   // (sign bit: not in the inside enumeration)
         // (the inner pair of an item is a kept pair, the loops L are stored everywhere)
         const uint32_t rP = v.in.cidx(ST_P, it.l - it.k, it.k, 0), rL1 = v.in.cidx(ST_L, it.k - i, i, 0), rL2 = v.in.cidx(ST_L, j - it.l, it.l, 0);
@@ -897,7 +970,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
   if (tid < nc * NL && !(a.dbg & 4) && !(ELEMDP_KO & 4)) {
     const int c = div_rcp(tid, a.rcp_lane);
     const int s = FAST ? G[A.f_live_in + tid - c * NL] : tid - c * NL;
-    const int i = i0 + c;
+    const int i = ci(c);
     if (FAST) {
       fast_inside_unary<kFastR, FP, kFastL, CON>(A, G + A.fp_in + s * kFastW, v.m.lin, v.in, crec + c * kCellInD, crfl[c], d, i, hb + c * HD + (tid - c * NL),
                                                  he + c * HD + (tid - c * NL), NW, 2 * CS, G + A.fs_in);
@@ -1350,7 +1423,7 @@ __global__ __launch_bounds__(kThreads) void k4_r7(LinArgs a) {
 
 // ---- outside, diagonal d: dynamic LDS = 4 * cpb * S + n_theta + 2 doubles
 // W6: asked for six waves per SIMD (80 registers, a few spilled dwords) -- taken by the launcher where six workgroups fit the LDS
-template <int MODE, bool BIG, bool FAST = false, int FP = kFastP, bool W6 = false>
+template <int MODE, bool BIG, bool FAST = false, int FP = kFastP, bool W6 = false, bool LISTS = false>
 __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_out(LinArgs a) {
   extern __shared__ double lds[];
   // (the automaton layout is read from the kernel arguments: constant offsets, scalar registers)
@@ -1366,9 +1439,21 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   const int S = a.lay.S, NA = a.lay.n_active, d = a.d, cpb = a.cpb, tid = threadIdx.x, nt = a.lay.n_theta;
   if (d > v.q.W) return;
   const int L = v.q.L, W = v.q.W;
-  const int ncell = L - d + 1, i0 = bx * cpb;
-  if (i0 >= ncell) return;
-  const int nc = (cpb < ncell - i0) ? cpb : ncell - i0;
+  constexpr bool MASK = FAST && MODE == OUT_TRAIN;   // (as in k4_in; the B plane and plane 1 are not stored on this side)
+  const int ncell = L - d + 1;
+  static_assert(!LISTS || (FAST && MODE == OUT_TRAIN), "lists: the table-driven train form only");
+  constexpr bool lists = LISTS;   // (as in k4_in: the live cells of block bx)
+  int i0 = bx * cpb, nc = 0, span = 0;
+  unsigned long long live = 0ull;
+  if (lists) {
+    const LiveCells lc = live_cells(v.q, d, (int)bx, ncell);
+    if (lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.out, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, ST_L, ST_2, ST_M, -1);
+    if (!lc.sweep) return;
+    i0 = lc.i0; nc = lc.nc; span = lc.span; live = lc.live;
+  } else {
+    if (i0 >= ncell) return;
+    nc = span = (cpb < ncell - i0) ? cpb : ncell - i0;
+  }
   if (MODE == OUT_END) {
     // Under the start constraint the motif begins at Ys: a cell that ends at or before Ys holds no part of it, so no transition in
     // it can be an end of the motif (its posterior is an exact 0: a derivation whose motif began earlier emits Ys with weight 0),
@@ -1376,8 +1461,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     // reader.  Workgroups whose cells all satisfy j <= Ys return: on average half of the sweep.
     if (!(a.dbg & 4096) && i0 + nc - 1 + d <= a.ys[v.n]) return;
   }
-  constexpr bool MASK = FAST && MODE == OUT_TRAIN;   // (as in k4_in; the B plane and plane 1 are not stored on this side)
-  if (MASK && block_is_dead(v.q, d, i0, nc, tid)) { fill_dead_rows(v.out, d, i0, nc, tid, ST_L, ST_2, ST_M, -1); return; }
+  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid)) { fill_dead_rows(v.out, d, i0, nc, tid, ST_L, ST_2, ST_M, -1); return; }
   const int HD = FAST ? A.n_lane : S;   // (as in k4_in)
   const int CS = cpb * HD;
   // ONE copy of the heavy sums (deterministic mode: each gets its adds from one wave, see the top of the file); the statistics,
@@ -1396,10 +1480,19 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   double* l_en = l_en0 + wvd * ES;             // ... this lane's copy
   double* l_eh = l_en + 2 * nt;
   double* l_pos = l_en0 + NWS * ES;            // scan: [2][win] position posteriors of the window (start, inner | end, -)
-  const int win = cpb + a.wmax + 3;
+  const int SP = (MASK && a.live_span > cpb) ? a.live_span : cpb;   // cells the staged window spans
+  const int win = SP + a.wmax + 3;
   constexpr bool kScanMode = MODE == OUT_SCAN || MODE == OUT_END;
   double* sOB1 = l_pos + (kScanMode ? 2 * win : 0);   // item records of the three roles (kRecOut doubles; no position window in training)
-  const BlockLds BL = block_lds(out_doubles(CS, nt, win, NWS, kScanMode), cpb, a.n_lin, win, FAST ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * cpb, FAST ? kCellOutD : 0);
+  const BlockLds BL = block_lds(out_doubles(CS, nt, win, NWS, kScanMode), cpb, a.n_lin, win, FAST ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * cpb, FAST ? kCellOutD : 0, SP);
+  int* lof = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(lds) + BL.lof);   // (as in k4_in)
+  // (a block whose live cells are consecutive -- most blocks of the short diagonals -- needs no offsets: no LDS, no barrier)
+  const bool gaps = lists && (live & (live + 1ull)) != 0ull;
+  if (gaps) {
+    if (tid < 64 && ((live >> tid) & 1ull)) lof[__popcll(live & ((1ull << tid) - 1ull))] = tid;
+    __syncthreads();
+  }
+  auto ci = [&](int c) -> int { return (LISTS && gaps) ? i0 + lof[c] : i0 + c; };
   // cell records of the table-driven unary phase (see k4_in): twelve global values per cell, fetched with the context
   constexpr int kCRout = (ELEMDP_CPB_MAX * 12 + kBT - 1) / kBT;
   double crx[kCRout];
@@ -1409,12 +1502,12 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
       crx[r] = 0.;
       if (r * kBT < cpb * 12) {   // (uniform: most automata need the first round only)
         const int t = tid + r * kBT, c0 = t / 12, c = c0 < nc ? c0 : 0;
-        crx[r] = cell_out_fetch(v.q, d, i0 + c, t - c0 * 12);
+        crx[r] = cell_out_fetch(v.q, d, ci(c), t - c0 * 12);
       }
     }
   }
   if (a.dbg & 1024) { if (nc == 12345) lds[tid] = crx[0] + pi.invZ; return; }   // (timing experiments, as in k4_in)
-  const BlockCtx cx = stage_context<BIG, 1, FAST>(a, v, reinterpret_cast<unsigned char*>(lds), BL, i0, nc, d, cpb);
+  const BlockCtx cx = stage_context<BIG, 1, FAST>(a, v, reinterpret_cast<unsigned char*>(lds), BL, i0, span, d, cpb, gaps ? ci(tid < nc ? tid : 0) : -1);
   if (pi.skip) return;   // (tested here: the loads behind `pi` travel with those of the context instead of before them)
   int* dm = cx.dm; int* cnts = cx.cnts; int* pre = cx.pre; int* base = cx.base;
   const int32_t* G = v.m.big;
@@ -1430,13 +1523,13 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     for (int r = 0; r < kCRout; ++r) {
       const int t = tid + r * kBT, c = t / 12, k = t - c * 12;
       if (c < nc) {
-        const int i = i0 + c;
+        const int i = ci(c);
         const bool on = k < 4 ? v.q.e_ok(i, d) : k < 6 ? v.q.pair_ok(i, d) : k < 8 ? (v.q.pair_ok(i - 1, d + 2) && v.q.pair_ok(i, d)) : true;
         crec[c * kCellOutD + 2 + k] = on ? crx[r] : 0.;
       }
     }
     for (int c = tid; c < nc; c += kBT) {
-      const int i = i0 + c, j = i + d;
+      const int i = ci(c), j = i + d;
       int fl = cell_out_flags(v.m, v.q, d, i);
       if (MODE == OUT_END) { const int ys = a.ys[v.n]; fl |= (i - 1 == ys ? CF_YL : 0) | (j == ys ? CF_YR : 0) | (L == j + 1 ? CF_JLAST : 0); }
       crfl[c] = fl;
@@ -1462,7 +1555,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   for (int vc = tid; vc < 3 * cpb; vc += kBT) {
     const int role = div_rcp(vc, a.rcp_cpb), c = vc - role * cpb;
     const bool have = c < nc;
-    const int i = i0 + (have ? c : 0);
+    const int i = ci(have ? c : 0);
     const int cell = v.q.cell(i, d);
     const int32_t* off = role == 0 ? v.q.by_inner_off : role == 1 ? v.q.by_left_off : v.q.by_right_off;
     int n0 = 0, n1 = 0;
@@ -1494,7 +1587,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     // sums: both read outA of larger spans only, so one round trip serves both.  (The rule-7 term of the stem cells' P states
     // is already in the table: k4_r7.)
     unsigned long long stems = 0;             // bit c: cell c of the workgroup is a pair (cpb <= 64)
-    for (int c = 0; c < nc; ++c) stems |= v.q.pair_ok(i0 + c, d) ? (1ull << c) : 0ull;
+    for (int c = 0; c < nc; ++c) stems |= v.q.pair_ok(ci(c), d) ? (1ull << c) : 0ull;
     if ((a.dbg & 1) || (ELEMDP_KO & 1)) stems = 0;
     const int nb = W - d;                     // b = 1 .. nb: parent span d + b <= W
     const int per = nb * nA, total = __popcll(stems) * per;
@@ -1508,7 +1601,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
         for (int k = 0; k < sc; ++k) m &= m - 1;          // the sc-th stem cell
         const int c = stems ? __builtin_ctzll(m) : 0;
         const int b = 1 + div_rcp(r, a.rcp_nap), p = r - (b - 1) * nA;
-        const int ii = i0 + c - b;
+        const int ii = ci(c) - b;
         const int dmii = (valid && ii >= 0) ? (int)v.q.dmin[ii] : 0;
         const bool ok = dmii > 0 && b >= dmii;              // 1(ii, i, .) is parsable (then the pair entries of (ii, d + b) exist)
         ha_oa[u] = out.lda(d + b, ii, p, ok);
@@ -1542,7 +1635,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     for (int w = one_wave ? ((tid < 64) ? tid : nwork_l) : tid; w < nwork_l; w += one_wave ? 64 : kBT) {
       const int c = (a.det && a.det_sh >= 0) ? (w >> a.det_sh) : div_rcp(w, a.rcp_nap), p = w - c * pad;
       if (p >= nA) continue;
-      const int i = i0 + c, j = i + d;
+      const int i = ci(c), j = i + d;
       const int s1 = pr_s1(p);
       const int cP = pr_cP(p);
       const int dmi = dm[c];
@@ -1653,7 +1746,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
         const int xc = valid ? x : np - 1;
         const LoopItem it = r_it[xc];
         const int role = r_meta[xc] >> 16, c = r_meta[xc] & 0xffff;
-        const int i = i0 + c, j = i + d;
+        const int i = ci(c), j = i + d;
         const uint32_t rE = out.cidx(ST_E, it.j - it.i, it.i, 0);
         const uint32_t rPi = in.cidx(ST_P, it.l - it.k, it.k, 0);
         const uint32_t r1 = role == 0 ? in.cidx(ST_L, i - it.i, it.i, 0) : rPi;
@@ -1731,13 +1824,13 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     const int s = FAST ? G[A.f_live_out + tid - c * NL] : tid - c * NL;
     const int slot = FAST ? tid : c * HD + s;
     double oB = 0.;
-    if (i0 + c + d > end_ys) {
+    if (ci(c) + d > end_ys) {
       const bool w1 = pi.merged && s == A.shadow;      // the shadow state: world 1 (its own Z, second set of statistics)
       sink.world = w1 ? 1 : 0;
       sink.en_ = l_en + (w1 ? nt : 0);
       if (FAST) {
         oB = fast_outside_unary<kFastR, FP, kFastL, MODE>(A, G + A.fp_out + s * kFastW, G, v.m.lin, in, out, crec + c * kCellOutD, crfl[c],
-                                                          d, i0 + c, w1 ? pi.invZs : pi.invZ, v.m.lam_same != 0, v.m.no_prf != 0, sink,
+                                                          d, ci(c), w1 ? pi.invZs : pi.invZ, v.m.lam_same != 0, v.m.no_prf != 0, sink,
                                                           h1 + slot, CS, NW, HS, G + A.fs_out);
       } else {
         LinOutCtx<LinSink> x{v.m, v.q, in, out, w1 ? pi.invZs : pi.invZ, sink, Constraint{MODE == OUT_END ? a.ys[v.n] : -1, -1, 0}};
@@ -1759,13 +1852,13 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     double* const en_keep = sink.en_;
     for (int w = tid; w < nc * nA; w += kBT) {
       const int c = div_rcp(w, a.rcp_nap), p = w - c * nA;
-      if (i0 + c + d <= end_ys) continue;
+      if (ci(c) + d <= end_ys) continue;
       if (FAST) {   // lin_outside_apair from the pair record (AutomatonLayout::fpr_out) and the weight tables
         const int32_t* PR = G + A.fpr_out + 8 * p;
         const int r0 = PR[0], r1 = PR[1];
         const int tg = (r0 >> 16) & 0xff;
         const bool w1 = pi.merged && (r0 & (4 << 24));
-        const int i = i0 + c, j = i + d, dmi = dm[c];
+        const int i = ci(c), j = i + d, dmi = dm[c];
         const bool exists = dmi > 0 && dmi < d;      // (otherwise the entry does not exist)
         const bool dead = MASK && exists && !((crfl[c] >> CF_USH) & UB_A);
         if (dead) {                    // a useless entry: 0, nothing loaded
@@ -2199,6 +2292,13 @@ static K4Form k4_form(const LinArgs& a, size_t lds, int waves, bool fast, bool b
 }
 template <bool CON>
 static void launch_k4_in(const LinArgs& a, dim3 grid, size_t lds, bool fast, bool big, hipStream_t st) {
+  if (!CON && fast && a.p.blocks) {   // the train forms that take the plan's lists
+    switch (k4_form(a, lds, 8, fast, big)) {
+      case K4_FP2_WAVES: hipLaunchKernelGGL((k4_in<true, false, true, 2, true, true>), grid, dim3(kBT), lds, st, a); return;
+      case K4_FP2: hipLaunchKernelGGL((k4_in<true, false, true, 2, false, true>), grid, dim3(kBT), lds, st, a); return;
+      default: hipLaunchKernelGGL((k4_in<true, false, true, kFastP, false, true>), grid, dim3(kBT), lds, st, a); return;
+    }
+  }
   switch (k4_form(a, lds, 8, fast, big)) {
     case K4_FP2_WAVES: hipLaunchKernelGGL((k4_in<true, CON, true, 2, true>), grid, dim3(kBT), lds, st, a); break;
     case K4_FP2: hipLaunchKernelGGL((k4_in<true, CON, true, 2>), grid, dim3(kBT), lds, st, a); break;
@@ -2209,6 +2309,13 @@ static void launch_k4_in(const LinArgs& a, dim3 grid, size_t lds, bool fast, boo
 }
 template <int MODE>
 static void launch_k4_out(const LinArgs& a, dim3 grid, size_t lds, bool fast, bool big, hipStream_t st) {
+  if (MODE == OUT_TRAIN && fast && a.p.blocks) {   // the train forms that take the plan's lists
+    switch (k4_form(a, lds, 6, fast, big)) {
+      case K4_FP2_WAVES: hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2, true, true>), grid, dim3(kBT), lds, st, a); return;
+      case K4_FP2: hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2, false, true>), grid, dim3(kBT), lds, st, a); return;
+      default: hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, kFastP, false, true>), grid, dim3(kBT), lds, st, a); return;
+    }
+  }
   switch (k4_form(a, lds, 6, fast, big)) {
     case K4_FP2_WAVES: hipLaunchKernelGGL((k4_out<MODE, true, true, 2, true>), grid, dim3(kBT), lds, st, a); break;
     case K4_FP2: hipLaunchKernelGGL((k4_out<MODE, true, true, 2>), grid, dim3(kBT), lds, st, a); break;
@@ -2236,6 +2343,15 @@ struct GroupGeom {
 };
 // scan: terminals (ari, nasi), Z = Z(ari,nasi) -- pass 0 of the reference schedule --, never the deterministic mode, and k4_out's
 // LDS with the scan's window rows; else the train's (one copy of the statistics per wave in the deterministic mode)
+// table-driven unary phases (lin_fast.h): an automaton whose lists fit the programs, the whole blob and the weight tables staged
+// (the scanner's node tests are flag words of the fast blobs)
+static bool geometry_fast(const LinArgs& a) {
+  return a.fast && a.n_stage >= a.lay.n_ints && a.lay.fp_ok && !(a.dbg & 16) && a.lay.lin_total <= 2048;
+}
+int lin_train_cpb(const LinArgs& full) {
+  return geometry_fast(full) ? std::min(kBT / std::max(full.lay.n_lane, 1), ELEMDP_CPB_MAX) : 0;
+}
+int lin_live_span_max() { return kLiveSpanMax; }
 static GroupGeom group_geometry(const LinArgs& full, int G, int Lmax, int Wmax, bool scan) {
   GroupGeom g;
   LinArgs& a = g.a;
@@ -2247,22 +2363,34 @@ static GroupGeom group_geometry(const LinArgs& full, int G, int Lmax, int Wmax, 
   a.lmax = Lmax;   // (read by the exterior-chain kernels only)
   if (scan) { a.schedule = 0; a.pass = 0; a.scan = 1; a.det = 0; }
   g.big = a.n_stage >= a.lay.n_ints;
-  // table-driven unary phases (lin_fast.h): an automaton whose lists fit the programs, the whole blob and the weight tables staged
-  // (the scanner's node tests are flag words of the fast blobs)
-  const bool fast = g.fast = a.fast && g.big && a.lay.fp_ok && !(a.dbg & 16) && a.lay.lin_total <= 2048;
+  const bool fast = g.fast = geometry_fast(a);
   a.fast = fast ? 1 : 0;
   if (fast) a.cpb = std::min(kBT / std::max(a.lay.n_lane, 1), ELEMDP_CPB_MAX);   // (states without any column take no lane)
   a.n_lin = fast ? a.lay.lin_total : kLinEth + nt;
   const int NW = a.det ? kBT / 64 : 1;   // (copies of the statistics of k4_out: one per wave in the deterministic mode)
   g.hd = fast ? a.lay.n_lane : S;
   set_rcps(a, fast);
-  g.win = a.cpb + Wmax + 3;
-  g.lds_in = block_lds(2 * a.cpb * g.hd + kRecIn, a.cpb, a.n_lin, g.win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0).total;
-  g.lds_out = block_lds(out_doubles(a.cpb * g.hd, nt, g.win, NW, scan), a.cpb, a.n_lin, g.win, fast ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * a.cpb, fast ? kCellOutD : 0).total;
+  // train sweeps from the live-block lists of the plan: only the table-driven forms, which honour the mask, and not the
+  // deterministic mode (its sums are single-writer in an order that follows the grouping of the cells)
+  if (scan || !fast || a.det || !a.p.useful || !a.p.blocks || !a.blk_grid || a.live_span < a.cpb) { a.p.blocks = nullptr; a.blk_grid = nullptr; a.live_span = 0; }
+  const int sp = a.live_span > a.cpb ? a.live_span : a.cpb;   // cells a workgroup's window spans
+  g.win = sp + Wmax + 3;
+  g.lds_in = block_lds(2 * a.cpb * g.hd + kRecIn, a.cpb, a.n_lin, g.win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0, sp).total;
+  g.lds_out = block_lds(out_doubles(a.cpb * g.hd, nt, g.win, NW, scan), a.cpb, a.n_lin, g.win, fast ? a.lay.fb_out_n : staged_ints(a.lay, a.n_stage, 1), 3 * a.cpb, fast ? kCellOutD : 0, sp).total;
   g.stage_ext = Lmax <= 2048 && a.nword_max <= 8192;
   g.lds_ext_in = g.stage_ext ? (size_t)ext_lds((a.ext_ring ? ext_ring_doubles(0, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : 0;
   g.ext_nt = (a.ext_block == kExtBlock && a.ext_ring && a.lay.n_active <= 128 && !(a.dbg & 8192)) ? 128 * kExtBlock : 128;   // (small groups: there the chain is exposed; in a large one its four-fold footprint only takes CUs from the band kernels)
   return g;
+}
+// workgroups per sequence of the band launch of diagonal a.d: its ncell cells cpb at a time, or (train sweeps with lists) the
+// largest block count of the diagonal in the plan -- at least one: workgroup 0 of a diagonal without a live cell stores its zeros
+// (blk_grid[d] < 0: the plan found that the lists of this diagonal save no workgroups worth their cost -- consecutive cells there:
+// either scheme stores every entry of the diagonal, so the choice is free per launch)
+static unsigned band_blocks(LinArgs& a, int ncell, bool train) {
+  const int n = (ncell + a.cpb - 1) / a.cpb;
+  if (!train || !a.blk_grid || !a.p.blocks) return (unsigned)n;
+  if (a.blk_grid[a.d] < 0) { a.p.blocks = nullptr; return (unsigned)n; }
+  return (unsigned)std::max(1, std::min(n, a.blk_grid[a.d]));
 }
 // The inside sweep of a group: the band diagonals 0 .. Wmax (`bands`: the train has none without pairs, no_rss), then the
 // exterior chain.
@@ -2273,8 +2401,10 @@ static void inside_sweeps(GroupGeom& g, int G, int Lmax, int Wmax, bool bands, h
     for (int d = 0; d <= Wmax; ++d) {
       const int ncell = Lmax - d + 1;
       if (ncell <= 0) break;
-      a.d = d;
-      launch_k4_in<CON>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), g.lds_in, g.fast, g.big, st);
+      LinArgs ad = a;
+      ad.d = d;
+      const unsigned gx = band_blocks(ad, ncell, !CON);
+      launch_k4_in<CON>(ad, dim3(gx, G), g.lds_in, g.fast, g.big, st);
     }
   if (g.stage_ext) hipLaunchKernelGGL((k4_in_ext<true, CON>), dim3(G), dim3(g.ext_nt), g.lds_ext_in, st, a);
   else hipLaunchKernelGGL((k4_in_ext<false, CON>), dim3(G), dim3(128), 0, st, a);
@@ -2287,8 +2417,10 @@ static void outside_bands(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t s
   for (int d = Wmax; d >= 0; --d) {
     const int ncell = Lmax - d + 1;
     if (ncell <= 0) continue;
-    a.d = d;
-    launch_k4_out<MODE>(a, dim3((ncell + a.cpb - 1) / a.cpb, G), g.lds_out, g.fast, g.big, st);
+    LinArgs ad = a;
+    ad.d = d;
+    const unsigned gx = band_blocks(ad, ncell, MODE == OUT_TRAIN);
+    launch_k4_out<MODE>(ad, dim3(gx, G), g.lds_out, g.fast, g.big, st);
   }
 }
 // an unconstrained or constrained sum pass of the scan: inside sweep, exterior chain outwards, outside band sweep

@@ -88,6 +88,7 @@ __device__ __forceinline__ void make_lviews(const LinArgs& a, int g, LViews& v) 
   v.in.cyk_compact = a.cyk_compact;      // (the Viterbi pass sweeps band_in: TableView::ldm / stm)
   q.okbits_end = a.okbits_end ? a.okbits_end + p.bits_base : nullptr;
   q.useful = a.p.useful ? a.p.useful + p.cell_base : nullptr;
+  q.blocks = a.p.blocks ? a.p.blocks + p.blk_base : nullptr;
   v.row = a.seq_out + (size_t)n * a.out_stride;
   v.zs = a.zs + (size_t)g * 4;
 }

@@ -9,6 +9,7 @@
 #pragma once
 #include "dp_rules.h"
 #include "energy_rules.h"
+#include "live_blocks.h"
 
 namespace elemdp {
 
@@ -141,11 +142,6 @@ ELEMDP_HD int count_interior_by_end(bool no_ene, int L, int W, int C, const Word
 // bits, which it replaces -- the sweep works in place).  All cells of one diagonal are independent in either sweep.
 // ---------------------------------------------------------------------------------------------
 // (these run on the host too -- the host entry of the C ABI -- where the recurrences of dp_rules.h are device code only)
-#if defined(__HIPCC__)
-#define ELEMDP_HOSTDEV __host__ __device__ __forceinline__
-#else
-#define ELEMDP_HOSTDEV inline
-#endif
 enum : int { UB_P = 1, UB_E = 2, UB_M = 4, UB_B = 8, UB_A = 16, UB_1 = 32, UB_2 = 64, UB_L = 128, UB_ALL = 255 };
 
 struct UsefulCtx {
