@@ -249,6 +249,26 @@ int elemdp_sample(elemdp_handle* h, const double* x, int32_t n_param, int32_t n_
 /* Copies the list of the last elemdp_pair_posteriors / elemdp_pair_mea: seq (batch index), i, j (cell, j = i + d), p; any may be NULL.
  * cap < n_pairs is ELEMDP_EINVAL; before any elemdp_pair_posteriors (of the resident batch) ELEMDP_ESTATE. */
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap);
+/* Structural context profile of every position under the motif model x: profile[7 * (seq_off[n] + p) + c] is the
+ * probability that base p (0-based) of sequence n has the rss letter c of "OLRHBIM" -- exterior, left or right base of a pair,
+ * unpaired in a hairpin, bulge, interior or multi-branch loop -- over the ensemble of the scan's first sum pass (terminals ari and
+ * nasi: the ensemble of elemdp_pair_posteriors, elemdp_pair_mea and elemdp_sample), from its inside / outside tables and Z(ari, nasi):
+ *   L(p) = sum_d P(p, d), R(p) = sum_i P(i, p+1-i), P the pair posterior of elemdp_pair_posteriors;
+ *   U(p) = sum_{i <= p} sum_s in(L, i, p+1, s) out(L, i, p+1, s) / Z: p is unpaired in a run of loop bases below a pair;
+ *   H(p) = the posterior of rule 6b (hairpin), summed over the runs [i, j) that hold p;
+ *   B(p) = the posterior of the rule-6c items of the inside pass with exactly one empty side, summed over the runs that hold p;
+ *   I(p) = max(0, U - H - B);   O(p) = the posterior of rule 8 (exterior emission) at p;   M(p) = max(0, 1 - L - R - U - O).
+ * The two remainders make a row sum to 1; they are exact wherever the tables' inside and outside agree.  With max_iloop < 30 the
+ * reference's outside pass enumerates interior loops its inside pass does not: the tables carry that, elemdp_pair_posteriors
+ * inherits it and so does this profile (U, hence I and M), which is why the remainders are clamped at 0.  A sequence without any
+ * parse (Z = 0) has O = 1 and 0 elsewhere, exactly (unpaired = 1 of the pair call); under ELEMDP_NO_RSS every position has O = 1.
+ * Sequences that leave the double range of the scaled-linear tables, and every sequence under option pipeline 3, go through the
+ * same rule on the log-space tables of the fused scan kernel.  profile NULL is ELEMDP_EINVAL, a call before elemdp_load_batch
+ * ELEMDP_ESTATE.  A row sums to 1 within 1e-12 for a sequence in the scaled-linear form; in the log-space form a term is
+ * exp(a + b - ln Z), whose exponent rounds at eps |ln Z|, and the sum holds to about 1e-15 |ln Z| per term (within 1e-10 at
+ * |ln Z| of a few thousand).  elemdp_last_timing afterwards: [whole call including the copy of the profile to the host, sum
+ * passes + context kernels, sequences handed to the log-space form].  elemdp_scan, the pair calls (the list of the last one stays valid), elemdp_sample and the train calls are unaffected. */
+int elemdp_context_profile(elemdp_handle* h, const double* x, int32_t n_param, double* profile);
 
 /* timing of the last train evaluation, measured with HIP events on the engine's stream:
  * ms[0] = whole evaluation, ms[1] = the DP pipeline only (all kernels of the inside/outside sweeps),

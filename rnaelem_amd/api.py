@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -89,6 +89,7 @@ def load_library():
         L.elemdp_pair_posteriors.argtypes = [hp, dp, C.c_int32, C.c_double, C.POINTER(C.c_int64), dp]
         L.elemdp_pair_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int64), dp, C.c_char_p, dp]
         L.elemdp_sample.argtypes = [hp, dp, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(C.c_uint8), dp, i32]
+        L.elemdp_context_profile.argtypes = [hp, dp, C.c_int32, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
         L.elemdp_last_timing.argtypes = [hp, dp, C.c_int32]
         L.elemdp_epoch_permutation.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
@@ -440,6 +441,20 @@ class Engine:
             out.append(([raw[b + t * L:b + (t + 1) * L] for t in range(n_samples)], node[b:b + n_samples * L].reshape(n_samples, L).copy(),
                         logp[k * n_samples:(k + 1) * n_samples].copy(), int(status[k])))
         return out
+
+    # ---- structural context profiles
+    CONTEXT_LETTERS = "OLRHBIM"
+
+    def context_profiles(self, x):
+        """One (L, 7) array per sequence: the probability that each base is exterior (O), the left (L) or right (R) base of a
+        pair, or unpaired in a hairpin (H), bulge (B), interior (I) or multi-branch (M) loop -- the marginals of the rss letters,
+        in the column order of CONTEXT_LETTERS, over the ensemble of pair_posteriors and sample_structures.  Rows sum to 1."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        n_pos = int(off[-1]) if off is not None else 0
+        prof = np.zeros(max(7 * n_pos, 1))
+        self._check(self._lib.elemdp_context_profile(self._h, _dp(x), self.n_param, _dp(prof)))
+        return [prof[7 * int(off[k]):7 * int(off[k + 1])].reshape(-1, 7).copy() for k in range(self.n_seq)]
 
     def last_timing(self):
         """[ms whole evaluation, ms DP pipeline, sequences re-evaluated in log space]"""

@@ -265,6 +265,8 @@ class Engine {
   // stochastic samples of derivations (sample_rules.h); outputs as elemdp_sample
   struct SampleOut { char* rss; uint8_t* node; double* logp; int32_t* status; };
   void sample_structures(const double* x, int n_param, int n_samples, uint64_t seed, int64_t index_base, const SampleOut& out);
+  // structural context profiles (ctx_rules.h): 7 doubles per position of the batch, O L R H B I M
+  void context_profile(const double* x, int n_param, double* profile);
   int partial_len() const { return 4 + 2 * au_.n_theta() + 4; }
   void set_option(const std::string& key, double v);
   void comm_init(int rank, int world, const void* id);
@@ -414,6 +416,8 @@ class Engine {
   // MEA structures: the M table and choice scratch of the table slots (as d_pr_P_), the structures and the scores of the call
   DevBuf d_mea_M_, d_mea_ch_, d_mea_s_, d_mea_sc_;
   DevBuf d_sm_rss_, d_sm_node_, d_sm_logp_, d_sm_status_, d_sm_stack_;   // sample_structures
+  // context profiles: P, u, h, b of the table slots (four [i][d] arrays per slot), their exterior columns, the profile of the call
+  DevBuf d_cx_cells_, d_cx_o_, d_cx_prof_;
 
   Automaton au_;
   EnergyTables et_;
@@ -2366,6 +2370,113 @@ void Engine::pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t 
 }
 
 
+// ---- structural context profiles under the motif model (ctx_rules.h).  The scan's first sum pass per group, then
+// on the group's table slots, before the next group of the stream reuses them: the pair reduction (k4_pairs), the per-run values
+// and the exterior column (k_ctx_cells), the seven columns per position (k_ctx_seq).  The log-space form -- the fused scan kernel
+// up to its first outside pass, then the same rule on its dense tables -- for the sequences that leave the double range and under
+// pipeline 3, with k_ctx_seq behind every launch.  Leaves the list of the last pair call alone.
+void Engine::context_profile(const double* x, int n_param_in, double* profile) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (!profile) throw ArgError("context_profile: null profile");
+  if (streaming_) {
+    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+      e.context_profile(x, n_param_in, profile + (size_t)kCtxCols * (size_t)(h_seq_off_[c0] - h_seq_off_[0]));
+    });
+    return;
+  }
+  require_resident("context_profile", n_param_in);
+  upload_params(x, lay_, false);
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  const size_t pcells = (size_t)(Lmax_ + 1) * (Wmax_ + 1);   // one [i][d] array of a table slot
+  const size_t ocol = (size_t)Lmax_ + 1;
+  ScanPos pos(n_seqpos, n);
+  d_cx_prof_.alloc(8 * kCtxCols * std::max<size_t>(n_seqpos, 1));
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  CtxArgs ca;
+  std::memset(&ca, 0, sizeof(ca));
+  ca.plans = plan_.d_plans.as<SeqPlan>();
+  ca.seq_out = d_seq_out_.as<double>(); ca.out_stride = out_stride_;
+  ca.c_stride = 4 * pcells;
+  ca.o_stride = ocol;
+  ca.profile = d_cx_prof_.as<double>();
+  ca.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
+  auto scratch = [&](size_t slots) {
+    d_cx_cells_.alloc(8 * 4 * pcells * slots);
+    d_cx_o_.alloc(8 * ocol * slots);
+  };
+  auto at_slot = [&](CtxArgs& ck, size_t slot0) {
+    ck.P = d_cx_cells_.as<double>() + slot0 * 4 * pcells;
+    ck.u = ck.P + pcells; ck.h = ck.P + 2 * pcells; ck.b = ck.P + 3 * pcells;
+    ck.o = d_cx_o_.as<double>() + slot0 * ocol;
+  };
+  PairArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.plans = ca.plans;
+  pa.okbits = d_okbits1_.as<uint32_t>();
+  pa.seq_out = ca.seq_out; pa.out_stride = out_stride_;
+  pa.p_stride = 4 * pcells;
+  int n_flagged = 0;
+  const bool sums_on_batch = opt_pipeline_ == 4;
+  if (sums_on_batch)
+    n_flagged = scan_sums(pos, [&](LinArgs& a) {
+      scratch((size_t)n_slots_);
+      int ncol = 0;   // (the P plane's columns of the real states are 0 .. ncol-1, as pair_posteriors requires)
+      for (int s = 0; s < a.lay.S; ++s) {
+        const int c = ints_[a.lay.tab_cmap + ST_P * a.lay.S + s];
+        if (s == a.lay.shadow || c < 0) continue;
+        if (c != ncol) throw std::logic_error("context_profile: the P plane's columns are not in state order");
+        ++ncol;
+      }
+      pa.p_cs = a.lay.tab_cs[ST_P]; pa.p_rs = a.lay.tab_rs[ST_P];
+      pa.ncol = ncol;
+      pa.band_stride = a.band_stride;
+      pa.skip_flagged = 1;
+      ca.skip_flagged = 1;
+    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      CtxArgs ck = ca;
+      ck.idx = ak.grp;
+      at_slot(ck, slot0);
+      if (!ca.no_rss) {
+        PairArgs pk = pa;
+        pk.idx = ak.grp;
+        pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+        pk.P = ck.P;
+        HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
+        HIP_OK(launch_ctx_cells(ak, ck, G, (Lg + 1) * (Wg + 1), st));
+      }
+      HIP_OK(launch_ctx_seq(ck, G, st));
+    });
+  // ---- the log-space form, in chunks of at most as many sequences as the scratch holds
+  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+    const int chunk = std::min(n_log, sums_on_batch ? n_slots_ : std::max(n_blocks, 1024));
+    if (!sums_on_batch) scratch((size_t)chunk);
+    d.ctx = ca;
+    at_slot(d.ctx, 0);
+    return chunk;
+  }, [&](const int32_t* idx, int C) {
+    CtxArgs ck = ca;
+    ck.idx = idx;
+    ck.skip_flagged = 0;
+    at_slot(ck, 0);
+    HIP_OK(launch_ctx_seq(ck, C, st_));
+  });
+  HIP_OK(hipEventRecord(ev_[3], st_));
+  // (the whole call includes the profile's way to the host: 7 doubles per position, 112 MB for 10 000 sequences of L = 200)
+  if (n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_cx_prof_.as<void>(), 8 * kCtxCols * n_seqpos, hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms_all = 0, ms_dp = 0;
+  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
+  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
+  last_ms[0] = ms_all;
+  last_ms[1] = ms_dp;
+  last_ms[2] = (double)n_flagged;
+}
+
+
 // ---- stochastic samples of derivations (sample_rules.h).  The inside sweeps of the scan's first sum pass per group
 // (launch_lin_scan_group, SCAN_PASS_INSIDE: no outside pass) and k_sample on the group's slots right behind them, before the next group of the
 // stream reuses them; the log-space form in the fused scan kernel for the sequences the range check flags.
@@ -2728,6 +2839,12 @@ int elemdp_sample(elemdp_handle* h, const double* x, int32_t n_param, int32_t n_
   ELEMDP_TRY
   if (!h || !x) throw elemdp::ArgError("elemdp_sample: null argument");
   h->e->sample_structures(x, n_param, n_samples, seed, index_base, elemdp::Engine::SampleOut{rss, node, logp, status});
+  ELEMDP_CATCH
+}
+int elemdp_context_profile(elemdp_handle* h, const double* x, int32_t n_param, double* profile) {
+  ELEMDP_TRY
+  if (!h || !x || !profile) throw elemdp::ArgError("elemdp_context_profile: null argument");
+  h->e->context_profile(x, n_param, profile);
   ELEMDP_CATCH
 }
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {

@@ -85,6 +85,22 @@ struct SampleArgs {
 };
 constexpr int kSampleLanes = 64;   // one wave per sequence, one lane per sample
 
+// ---- structural context profiles (ctx_rules.h, ctx_kernels.hip).  A launch covers the G sequences idx[0 .. G) of one group or
+// chunk; slot g of the launch owns P, u, h, b + g * c_stride (each [i][d], rows of W+1: the pair posteriors and the per-run
+// values of ctx_rules.h) and o + g * o_stride (the exterior column, L values).  The profile of batch index n goes to
+// profile + 7 * seq_base, 7 doubles per position in the order O L R H B I M.
+constexpr int kCtxCols = 7;
+struct CtxArgs {
+  const SeqPlan* plans;           // batch plans (batch index)
+  const int32_t* idx;             // idx[g] = batch index of the sequence in slot g (launch_ctx_seq)
+  const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
+  int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)
+  double* P; double* u; double* h; double* b; size_t c_stride;
+  double* o; size_t o_stride;
+  double* profile;
+  int32_t no_rss;                 // a model without secondary structure: every position is exterior
+};
+
 struct DpArgs {
   AutomatonLayout lay;            // host-visible copy (launch geometry, LDS sizes)
   const AutomatonLayout* layp;    // the same record in device memory: kernels read it through this pointer
@@ -124,6 +140,9 @@ struct DpArgs {
   // SCAN, samples (sample_rules.h, log-space form): n_samples > 0 = stop after the inside pass and draw the samples of sequence
   // order[w] on the slot's dense log tables, the workgroup's lanes over the samples
   SampleArgs smp;
+  // SCAN, structural context profiles (ctx_rules.h, log-space form): ctx.u non-null = stop after inside + the first outside pass
+  // and write P, u, h, b and o of the sequence order[w] to slot w of ctx (the rows k_ctx_seq reads behind the launch)
+  CtxArgs ctx;
 };
 
 // arguments of the diagonal-synchronous train pipeline (train_kernels.hip)
@@ -323,6 +342,10 @@ hipError_t launch_pair_seq(const PairArgs& a, int G, hipStream_t st);
 hipError_t launch_pair_mea(const PairArgs& a, int G, int Wmax, hipStream_t st);
 
 hipError_t launch_sample(const LinArgs& a, const SampleArgs& s, int G, hipStream_t st);
+// k_ctx_cells behind launch_lin_scan_group (SCAN_PASS_START) and launch_pair_cells on the same slots and stream; k_ctx_seq behind
+// it, or behind the fused scan kernel (DpArgs::ctx)
+hipError_t launch_ctx_cells(const LinArgs& a, const CtxArgs& c, int G, int cells_max, hipStream_t st);
+hipError_t launch_ctx_seq(const CtxArgs& c, int G, hipStream_t st);
 // kept pairs of every sequence of the batch (the staging capacity), off[0..n] = exclusive prefix of cnt[0..n) with off[n] the total,
 // and the scatter of the staging list into the final list ordered by (sequence, i, j)
 hipError_t launch_pair_kept(const SeqPlan* plans, const uint32_t* okbits, int n, int64_t* kept, hipStream_t st);

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "ctx_rules.h"
 #include "dp_rules.h"
 #include "energy_rules.h"
 #include "kernels.h"
@@ -739,6 +740,29 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
                 if (s != m.lay.shadow) acc += r.term(Tin.at(ST_P, d, i, s), Tout.at(ST_P, d, i, s));
             P[t] = r.finish(acc);
           }
+          continue;
+        }
+        if (a.ctx.u) {   // structural context profiles (ctx_rules.h): P and the per-run values of this first pass, the exterior column
+          const size_t cb = (size_t)w * a.ctx.c_stride;
+          const CtxLog f{ZL};
+          const PairLog r{ZL};
+          const bool live = ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL && !no_rss;
+          for (int t = tid; t < ncell; t += kThreads) {
+            const int i = t / (W + 1), d = t - i * (W + 1);
+            double acc = 0.;
+            CtxCell c{0., 0., 0.};
+            if (live && d >= 1 && i + d <= L) {
+              if (q.pair_ok(i, d))
+                for (int s = 0; s < S; ++s)
+                  if (s != m.lay.shadow) acc += r.term(Tin.at(ST_P, d, i, s), Tout.at(ST_P, d, i, s));
+              c = ctx_cell(f, m, q, Tin, Tout, d, i);
+            }
+            a.ctx.P[cb + t] = r.finish(acc);
+            a.ctx.u[cb + t] = c.u;
+            a.ctx.h[cb + t] = c.h;
+            a.ctx.b[cb + t] = c.b;
+          }
+          for (int t = tid; t < L; t += kThreads) a.ctx.o[(size_t)w * a.ctx.o_stride + t] = live ? ctx_exterior(f, m, q, Tin, Tout, t) : 1.;
           continue;
         }
         if (tid == 0) l_zs[4] = (double)last_argmax(Pys, L);

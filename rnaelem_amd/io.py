@@ -227,3 +227,33 @@ def read_sample_records(path):
         out.append((rid, status, rows))
         k += 3 + n
     return out
+
+
+CONTEXT_LETTERS = "OLRHBIM"
+
+
+def context_record(rid, profile):
+    """Record of one sequence in the `scan --out-context` file: `id: <id>`, then seven lines `O: [...]` to `M: [...]` with the
+    probability of that structure letter at every base (6 significant digits); profile: an (L, 7) array as
+    Engine.context_profiles gives it."""
+    profile = np.asarray(profile, dtype=np.float64).reshape(-1, len(CONTEXT_LETTERS))
+    lines = ["id: " + rid] + ["%s: %s" % (c, fmt_vec(profile[:, k])) for k, c in enumerate(CONTEXT_LETTERS)]
+    return "\n".join(lines) + "\n"
+
+
+def read_context_records(path):
+    """-> list of (id, (L, 7) array) from a `scan --out-context` file."""
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+    n = len(CONTEXT_LETTERS)
+    while k + n < len(lines) and lines[k].startswith("id: "):
+        cols = []
+        for t, c in enumerate(CONTEXT_LETTERS):
+            head, body = lines[k + 1 + t].split(": ", 1)
+            if head != c:
+                raise ValueError("context record %r: line %r where %r was expected" % (lines[k][4:], head, c))
+            body = body.strip("[]")
+            cols.append([float(v) for v in body.split(",")] if body else [])
+        out.append((lines[k][4:], np.array(cols, dtype=np.float64).T.reshape(-1, n)))
+        k += 1 + n
+    return out
