@@ -197,7 +197,8 @@ int elemdp_train_seq_counts(elemdp_handle* h, double* out, int32_t n_seq);
 /* debug: tables of ONE sequence after a train evaluation of a batch holding only that sequence:
  * inside_o/outside_o [(L+1)*S]; inside/outside [(L+1)*(W+1)*7*S] in the reference's index order
  * [i][d][e][s] (motif_trainer.hpp:62-65); outside = the first (full-terminal) pass.  Any may be NULL.
- * ENo/ENx [n_theta], EH [4] = EHo,EHx. */
+ * ENo/ENx [n_theta], EH [4] = EHo,EHx.  ELEMDP_ESTATE before any train evaluation of the loaded batch and, as
+ * elemdp_train_seq_counts, after a scan-family call (whose tables are not a train evaluation's). */
 int elemdp_debug_tables(elemdp_handle* h, double* inside, double* outside, double* inside_o, double* outside_o,
                         double* ENo, double* ENx, double* EH);
 

@@ -37,29 +37,13 @@
 #include "lin_params.h"
 #include "live_blocks.h"
 #include "sample_rules.h"
+#include "table_slots.h"
 
 namespace elemdp {
 namespace {
 
 thread_local std::string g_error;
 std::string g_data_dir;
-
-struct HipError : std::runtime_error {
-  explicit HipError(const std::string& m) : std::runtime_error(m) {}
-};
-struct ArgError : std::runtime_error {
-  explicit ArgError(const std::string& m) : std::runtime_error(m) {}
-};
-struct StateError : std::runtime_error {
-  explicit StateError(const std::string& m) : std::runtime_error(m) {}
-};
-
-#define HIP_OK(expr)                                                                                   \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess)                                                                              \
-      throw HipError(std::string(#expr) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-  } while (0)
 
 // Makes `device` the calling thread's current HIP device for the lifetime of the guard and restores the previous one.  Every
 // computing entry point of an Engine takes one: the current device is a per-thread setting, so a handle used from another
@@ -119,63 +103,17 @@ struct Rccl {
                              (elemdp::Rccl::get().GetErrorString ? elemdp::Rccl::get().GetErrorString(r_) : "rccl error")); \
   } while (0)
 
-// owning device buffer
-class DevBuf {
+// sets a variable for a scope: the old value comes back however the scope is left
+template <class T> class ScopedValue {
  public:
-  DevBuf() = default;
-  ~DevBuf() { reset(); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  // (an allocation that is large enough and at most twice too large is kept: fresh device memory costs ~20 ms / GB, and
-  // the plan sets of a load are rebuilt chunk after chunk with similar sizes; bytes() is the capacity)
-  // slack: allocate an eighth more than asked for -- buffers whose size depends on the data (interior-loop items of a batch):
-  // the next batch of the same shape then fits without a re-allocation
-  // (such a buffer is also never given up for a smaller one: the last chunk of a load is smaller than the others)
-  // returns true when the memory is fresh (its contents undefined), false when the buffer was kept
-  bool alloc(size_t bytes, bool slack = false) {
-    bytes = bytes ? bytes : 8;
-    if (p_ && bytes <= bytes_ && (slack || bytes_ <= 2 * bytes + (size_t(1) << 20))) return false;
-    reset();
-    bytes_ = slack ? bytes + bytes / 8 : bytes;
-    HIP_OK(hipMalloc(&p_, bytes_));
-    return true;
-  }
-  void reset() { if (p_) { (void)hipFree(p_); p_ = nullptr; bytes_ = 0; } }
-  template <class T> T* as() const { return static_cast<T*>(p_); }
-  size_t bytes() const { return bytes_; }
-  template <class T> void upload(const std::vector<T>& v, hipStream_t st) {
-    alloc(v.size() * sizeof(T));
-    if (!v.empty()) HIP_OK(hipMemcpyAsync(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  }
+  ScopedValue(T& ref, T v) : ref_(ref), old_(ref) { ref_ = v; }
+  ~ScopedValue() { ref_ = old_; }
+  ScopedValue(const ScopedValue&) = delete;
+  ScopedValue& operator=(const ScopedValue&) = delete;
 
  private:
-  void* p_ = nullptr;
-  size_t bytes_ = 0;
-};
-
-// pinned host staging buffer, kept from load to load (a fresh std::vector of 24 MB costs its page faults -- 30 ms per
-// 10 000 x L=300 for the staging arrays of load_batch -- and a pageable upload goes through the runtime's own staging copies)
-class HostBuf {
- public:
-  HostBuf() = default;
-  ~HostBuf() { if (p_) (void)hipHostFree(p_); }
-  HostBuf(const HostBuf&) = delete;
-  HostBuf& operator=(const HostBuf&) = delete;
-  template <class T> T* get(size_t n) {
-    const size_t bytes = std::max<size_t>(n * sizeof(T), 8);
-    if (bytes > bytes_) {
-      if (p_) (void)hipHostFree(p_);
-      p_ = nullptr; bytes_ = 0;
-      void* p = nullptr;   // (p_ and bytes_ are set once the allocation has succeeded)
-      HIP_OK(hipHostMalloc(&p, bytes + bytes / 8, hipHostMallocDefault));
-      p_ = p; bytes_ = bytes + bytes / 8;
-    }
-    return static_cast<T*>(p_);
-  }
-
- private:
-  void* p_ = nullptr;
-  size_t bytes_ = 0;
+  T& ref_;
+  T old_;
 };
 
 std::string default_data_dir() {
@@ -314,15 +252,13 @@ class Engine {
   LdsLayout lds_layout(const AutomatonLayout& lay, int Lmax, int nword_max, bool scan) const;
   DpArgs base_args(const AutomatonLayout& lay, const int32_t* d_ints, const double* d_params, const PlanSet& ps,
                    const uint32_t* d_okbits, int S);
-  // row: doubles per cell of a band table slot (0: the dense layout, 7 * S; the compact tables of the scaled-linear pipeline
-  // pass AutomatonLayout::tab_row)
-  void ensure_slots(int S, bool scan, int n_want, int row = 0);
+  // the request for table slots of the loaded batch under the handle's options (its fields: slot_sizing.h)
+  SlotRequest slot_request(int S, int row, bool scan, int n_want, int group = 0, int pair_row = 0) const;
   void run_train();
   void run_train_batch();
   void run_lin_batch();
   // group_cap: most sequences swept in lockstep (a scan uses fewer: fresh table memory costs ~20 ms / GB)
   int prepare_lin(LinArgs& a, bool sched1, bool dense_too = false, int n_eval = 0, int group_cap = 8192);
-  int balanced_group(size_t per_slot_bytes, int n, int group_cap);
   template <class Work> void sweep_groups(const LinArgs& a, int n, const int32_t* h_ord, const int32_t* d_ord, const SeqPlan* d_sorted,
                                           int gsz, int ns, Work work);
   struct ScanPos {   // what a scan's first sum pass writes besides its tables: per position, then per sequence
@@ -335,6 +271,9 @@ class Engine {
   int prepare_scan(LinArgs& a, const ScanPos& pos);
   int read_flagged(std::vector<int32_t>* list = nullptr);
   DpArgs log_scan_args(bool sums_on_batch, int* n_blocks);
+  int log_chunk(bool sums_on_batch, int n_blocks, int n_log) const;
+  PairArgs pair_batch_args() const;
+  void pair_plane_fields(PairArgs& pa, const LinArgs& a) const;
   void require_resident(const char* what, int n_param_in);
   template <class Fill, class Group> int scan_sums(const ScanPos& pos, Fill fill, Group group, std::vector<int32_t>* flagged = nullptr);
   template <class Fill, class Behind> void scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind behind);
@@ -459,11 +398,7 @@ class Engine {
   std::vector<double> h_lnbpp_;          // optional (keep_lnbpp)
   std::vector<int64_t> h_lnbpp_base_;
   PlanSet plan_;
-  // slots
-  int n_slots_ = 0, slots_S_ = 0, slot_override_ = 0;
-  bool slots_scan_ = false;
-  size_t band_stride_ = 0, ext_stride_ = 0;
-  DevBuf d_band_in_, d_band_out_, d_ext_in_, d_ext_out_, d_tr_ext_, d_tr_stack_, d_tmp_;
+  TableSlots slots_;
   DevBuf d_seq_out_, d_partial_;
   int out_stride_ = 0;
   // options
@@ -483,19 +418,15 @@ class Engine {
   AutomatonLayout lays_;                 // the automaton with the shadow copy of (0,0): both outside passes in one sweep
   std::vector<int32_t> intss_;
   DevBuf d_lays_, d_intss_;
-  int tables_S_ = 0;                     // state stride of the tables of the last linear evaluation (debug_tables)
   std::vector<double> last_x_;           // parameters of the last train evaluation (debug_tables repeats it with the generic kernels)
   std::vector<double> h_lin_, h_lins_;   // linear parameter block of the last evaluation (plain automaton / with the shadow state)
   std::vector<uint8_t> h_seq_;           // base codes of the batch (table export)
   HostBuf hb_ws_, hb_ews_, hb_unp_;      // staging of load_batch
   int64_t n_cells_total_ = 0;
   bool train_rows_ = false;              // d_seq_out_ holds the rows of a train evaluation (seq_counts)
-  bool tables_linear_ = false;           // the resident tables hold scaled linear values (debug_tables converts)
   int n_flagged_last_ = 0;
-  DevBuf d_a_in_, d_a_out_;   // pair tables of the factorised rule 2 (lin_rules.h), per slot [W+1][Lmax+1][n_ap]
   DevBuf d_plans_sorted_;   // plan records in processing (h_order_) order
-  DevBuf d_ews_, d_xwc_, d_xwi_, d_lin_, d_lins_, d_zs_, d_flagged_, d_det_;
-  int lin_slots_ = 0;
+  DevBuf d_ews_, d_xwc_, d_xwi_, d_lin_, d_lins_, d_flagged_, d_det_;
   int opt_schedule_ = 1;   // 1 = linear (ari pass + one-state nasi pass), 0 = the reference's two full passes
   int opt_dbg_ = 0;        // timing experiments (LinArgs::dbg); results are wrong when set
   int opt_group_ = 0;      // sequences swept in lockstep by the batch pipeline (0 = auto)
@@ -560,7 +491,6 @@ void Engine::flatten_automaton() {
   au_.flatten(&layr_, &intsr_, true, opt_prune_, false);
   if (linear_ok_ && au_.S() < 127) au_.flatten(&lays_, &intss_, false, opt_prune_, true);
   else { lays_ = lay_; lays_.shadow = -1; intss_ = ints_; }
-  lin_slots_ = 0;   // (the pair tables of the linear pipeline are sized by the automaton's pair list)
 }
 
 void Engine::upload_automaton() {
@@ -693,7 +623,7 @@ void Engine::set_option(const std::string& key, double v) {
   else if (key == "eval_count") opt_eval_count_ = (int)v;
   else if (key == "prune") {
     opt_prune_ = v != 0;
-    n_slots_ = 0;
+    slots_.invalidate();   // (row widths and the pair list follow the transition lists)
     flatten_automaton();
     if (has_device_) { DeviceGuard dg(device_); HIP_OK(hipStreamSynchronize(st_)); upload_automaton(); }
   }
@@ -900,38 +830,13 @@ void Engine::ensure_sorted_plan() {
   plan_.sorted = true;
 }
 
-void Engine::ensure_slots(int S, bool scan, int n_want, int row) {
-  if (row <= 0) row = kNumBandStates * S;
-  const size_t band = (size_t)(Wmax_ + 1) * (Lmax_ + 1) * row;
-  // (the log-space fallback of the scaled-linear pipeline sweeps dense tables over the same buffers: at least one fits)
-  const size_t dense1 = (size_t)kNumBandStates * (Wmax_ + 1) * (Lmax_ + 1) * au_.S();
-  const size_t ext = (size_t)(Lmax_ + 1) * S;
-  int want = opt_slots_ > 0 ? opt_slots_ : 2 * n_cu_;
-  if (slot_override_ > 0) want = slot_override_;
-  want = std::max(1, std::min(want, n_want));
-  size_t free_b = 0, total_b = 0;
-  HIP_OK(hipMemGetInfo(&free_b, &total_b));
-  const size_t per_slot = (band + ext) * 2 * sizeof(double) + (scan ? ext * sizeof(TraceRec) + 16 * (Lmax_ + 2) : 0);
-  if (n_slots_ >= want && slots_S_ == S && band_stride_ == band && (slots_scan_ || !scan)) return;
-  // (no reset: DevBuf::alloc keeps what is large enough -- a load_batch per evaluation must not re-allocate the tables)
-  HIP_OK(hipMemGetInfo(&free_b, &total_b));
-  const size_t held_t = d_band_in_.bytes() + d_band_out_.bytes() + d_ext_in_.bytes() + d_ext_out_.bytes() + d_tmp_.bytes();
-  const size_t held_tr = d_tr_ext_.bytes() + d_tr_stack_.bytes();
-  size_t budget = (size_t)((double)(free_b + held_t + held_tr) * 0.72);
-  if (slot_budget_ > 0) budget = std::min(budget, slot_budget_);
-  if (per_slot * (size_t)want > budget) want = (int)std::max<size_t>(1, budget / per_slot);
-  if (per_slot * want > free_b + held_t + held_tr) throw HipError("not enough device memory for one table slot");
-  n_slots_ = want; slots_S_ = S; slots_scan_ = scan;
-  band_stride_ = band; ext_stride_ = ext;
-  d_band_in_.alloc(std::max(band * want, dense1) * sizeof(double));
-  d_band_out_.alloc(std::max(band * want, dense1) * sizeof(double));
-  d_ext_in_.alloc(ext * want * sizeof(double));
-  d_ext_out_.alloc(ext * want * sizeof(double));
-  d_tmp_.alloc(ext * 3 * want * sizeof(double));
-  if (scan) {
-    d_tr_ext_.alloc(ext * want * sizeof(TraceRec));
-    d_tr_stack_.alloc((size_t)want * 4 * (4 * (Lmax_ + 2)) * sizeof(int32_t));
-  }
+SlotRequest Engine::slot_request(int S, int row, bool scan, int n_want, int group, int pair_row) const {
+  SlotRequest r;
+  r.S = S; r.row = row; r.scan = scan; r.n_want = n_want; r.group = group; r.pair_row = pair_row;
+  r.opt_slots = opt_slots_; r.n_cu = n_cu_;
+  r.Lmax = Lmax_; r.Wmax = Wmax_; r.S_dense = au_.S();
+  r.budget = slot_budget_;
+  return r;
 }
 
 DpArgs Engine::base_args(const AutomatonLayout& lay, const int32_t* d_ints, const double* d_params, const PlanSet& ps,
@@ -952,11 +857,11 @@ DpArgs Engine::base_args(const AutomatonLayout& lay, const int32_t* d_ints, cons
   a.b.ndot = nullptr;
   a.okbits = d_okbits;
   a.p = ps.arrays();
-  a.band_in = d_band_in_.as<double>(); a.band_out = d_band_out_.as<double>();
-  a.ext_in = d_ext_in_.as<double>(); a.ext_out = d_ext_out_.as<double>();
+  a.band_in = slots_.band_in.as<double>(); a.band_out = slots_.band_out.as<double>();
+  a.ext_in = slots_.ext_in.as<double>(); a.ext_out = slots_.ext_out.as<double>();
   a.band_stride = (size_t)kNumBandStates * (Wmax_ + 1) * (Lmax_ + 1) * S;
   a.ext_stride = (size_t)(Lmax_ + 1) * S;
-  a.tmp = d_tmp_.as<double>();
+  a.tmp = slots_.tmp.as<double>();
   a.tmp_stride = a.ext_stride;
   return a;
 }
@@ -1288,12 +1193,11 @@ void Engine::resident_plan(const uint32_t* mask) {
   HIP_OK(hipStreamSynchronize(st_));
   d_xwc_.alloc(sizeof(double) * 10 * (size_t)n_cells_total_);
   d_flagged_.alloc(sizeof(int32_t) * ((size_t)n + 1));
-  lin_slots_ = 0;
   out_stride_ = 6 + 2 * au_.n_theta() + 4;
   d_seq_out_.alloc(sizeof(double) * (size_t)out_stride_ * n);
   // (a ranged evaluation writes the rows of its range only: the rows of a new batch start as zeros, not as what the memory held)
   HIP_OK(hipMemsetAsync(d_seq_out_.as<void>(), 0, sizeof(double) * (size_t)out_stride_ * n, st_));
-  n_slots_ = 0;
+  slots_.invalidate();   // (a new batch: new Lmax, Wmax)
   HIP_OK(hipStreamSynchronize(st_));
   dbg_lap("load: weights / output buffers");
 }
@@ -1306,7 +1210,7 @@ bool Engine::should_stream(const BatchShape& b) {
   // slots; a batch whose plan alone would take more than half of the free device memory is streamed
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-  const size_t held = d_band_in_.bytes() + d_band_out_.bytes() + d_xwc_.bytes() + d_xwi_.bytes();
+  const size_t held = slots_.held_bytes(TableSlots::Held::Stream) + d_xwc_.bytes() + d_xwi_.bytes();
   return (double)b.n_cells * 600.0 > 0.5 * (double)(free_b + held);
 }
 
@@ -1334,9 +1238,8 @@ void Engine::stream_setup(const uint8_t* seq, const int32_t* off, const uint8_t*
     st_have_eff_.assign(nchunks, 0);
   }
   // (the buffers of an earlier resident batch would only stand in the way of the inner engines)
-  for (DevBuf* d : {&d_band_in_, &d_band_out_, &d_ext_in_, &d_ext_out_, &d_tmp_, &d_xwc_, &d_xwi_, &d_a_in_, &d_a_out_, &d_tr_ext_})
-    d->reset();
-  n_slots_ = 0; lin_slots_ = 0;
+  slots_.release();
+  d_xwc_.reset(); d_xwi_.reset();
   streaming_ = true;
   n_seq_ = n;
 }
@@ -1446,21 +1349,6 @@ void Engine::stream_scan(const double* x, int n_param_in, elemdp_scan_out* out) 
   if (out->en) std::copy(en.begin(), en.end(), out->en);
 }
 
-// Sequences swept in lockstep: as many as fit in ~55 % of the free device memory (at most group_cap), then balanced so that all
-// groups of the batch have the same size (a small last group runs at lower efficiency).
-int Engine::balanced_group(size_t per_slot_bytes, int n, int group_cap) {
-  if (opt_group_ > 0) return opt_group_;
-  size_t free_b = 0, total_b = 0;
-  HIP_OK(hipMemGetInfo(&free_b, &total_b));
-  const size_t held = d_band_in_.bytes() + d_band_out_.bytes() + d_ext_in_.bytes() + d_ext_out_.bytes();
-  size_t budget = (size_t)((double)(free_b + held) * 0.68);
-  if (slot_budget_ > 0) budget = std::min(budget, slot_budget_);
-  long cap = (long)(budget / std::max<size_t>(per_slot_bytes, 1));
-  cap = std::max(1L, std::min(cap, (long)group_cap));
-  const long n_groups = (n + cap - 1) / cap;
-  return (int)((n + n_groups - 1) / n_groups);
-}
-
 TrArgs Engine::log_pipeline_args() {
   const int S = au_.S();
   TrArgs a;
@@ -1481,11 +1369,11 @@ TrArgs Engine::log_pipeline_args() {
   a.b.seq = d_seq_.as<uint8_t>(); a.b.ws = d_ws_.as<double>(); a.b.unp = d_unp_.as<uint8_t>(); a.b.ndot = nullptr;
   a.okbits = d_okbits1_.as<uint32_t>();
   a.p = plan_.arrays();
-  a.band_in = d_band_in_.as<double>(); a.band_out = d_band_out_.as<double>();
-  a.ext_in = d_ext_in_.as<double>(); a.ext_out = d_ext_out_.as<double>();
+  a.band_in = slots_.band_in.as<double>(); a.band_out = slots_.band_out.as<double>();
+  a.ext_in = slots_.ext_in.as<double>(); a.ext_out = slots_.ext_out.as<double>();
   a.band_stride = (size_t)kNumBandStates * (Wmax_ + 1) * (Lmax_ + 1) * S;
   a.ext_stride = (size_t)(Lmax_ + 1) * S;
-  a.tmp = d_tmp_.as<double>();
+  a.tmp = slots_.tmp.as<double>();
   a.tmp_stride = a.ext_stride;
   a.seq_out = d_seq_out_.as<double>();
   a.out_stride = out_stride_;
@@ -1495,15 +1383,14 @@ TrArgs Engine::log_pipeline_args() {
 void Engine::run_train_batch() {
   if (opt_eval_count_ > 0 && !(opt_eval_first_ == 0 && opt_eval_count_ == n_seq_))
     throw ArgError("eval_first / eval_count: the log-space pipeline (pipeline 3) evaluates the whole batch");
-  slot_override_ = opt_group_ > 0 ? opt_group_ : 4096;
-  ensure_slots(au_.S(), false, n_seq_);
-  slot_override_ = 0;
+  slots_.ensure(slot_request(au_.S(), 0, false, n_seq_, opt_group_ > 0 ? opt_group_ : 4096), free_device_bytes());
   TrArgs a = log_pipeline_args();
-  tables_linear_ = false;
+  slots_.set_holds(TableSlots::Holds::DenseLog);
+  const int n_slots = slots_.n();
   HIP_OK(hipMemsetAsync(d_seq_out_.as<void>(), 0, sizeof(double) * (size_t)out_stride_ * n_seq_, st_));
   HIP_OK(hipEventRecord(ev_[1], st_));
-  for (int g0 = 0; g0 < n_seq_; g0 += n_slots_) {
-    const int G = std::min(n_slots_, n_seq_ - g0);
+  for (int g0 = 0; g0 < n_seq_; g0 += n_slots) {
+    const int G = std::min(n_slots, n_seq_ - g0);
     a.grp = d_order_.as<int32_t>() + g0;
     const int Lg = h_plans_[h_order_[g0]].L;
     HIP_OK(launch_train_group(a, G, Lg, std::min(Lg, max_span_), st_));
@@ -1517,7 +1404,7 @@ void Engine::run_train_batch() {
 // slots, side buffers and the argument record of the scaled-linear pipeline; returns the balanced group size
 void Engine::poison_tables() {
   if (!opt_poison_) return;
-  for (DevBuf* b : {&d_band_in_, &d_band_out_, &d_a_in_, &d_a_out_})
+  for (DevBuf* b : {&slots_.band_in, &slots_.band_out, &slots_.a_in, &slots_.a_out})
     if (b->bytes()) HIP_OK(hipMemsetAsync(b->as<void>(), 0xff, b->bytes(), st_));   // (all-ones bytes: NaN)
 }
 
@@ -1550,23 +1437,12 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int
   const int row = std::max(std::max(lay_.tab_row, lays_.tab_row), dense_too ? kNumBandStates * lay_.S : 0);
   // (an evaluation of a range of the resident batch -- options eval_first / eval_count -- needs slots for that range only)
   const int n_need = n_eval > 0 ? std::min(n_eval, n_seq_) : n_seq_;
-  {
-    const size_t cells = (size_t)(Wmax_ + 1) * (Lmax_ + 1), ext = (size_t)(Lmax_ + 1);
-    slot_override_ = balanced_group((cells * row + ext * Sa) * 2 * sizeof(double) + ext * Sa * 3 * sizeof(double) +
-                                    cells * nap * 2 * sizeof(double), n_need, group_cap);
-  }
-  ensure_slots(Sa, false, n_need, row);
-  slot_override_ = 0;
+  const size_t free_b = free_device_bytes();
+  const int group = balanced_group(lin_group_bytes(Lmax_, Wmax_, row, Sa, nap), n_need, group_cap, opt_group_, slot_budget_, free_b,
+                                   slots_.held_bytes(TableSlots::Held::Group));
+  slots_.ensure(slot_request(Sa, row, false, n_need, group, nap), free_b);
   // (if the allocation had to shrink, rebalance for the slots we got)
-  const int n_groups = (n_need + n_slots_ - 1) / n_slots_;
-  const int gsz = (n_need + n_groups - 1) / n_groups;
-  if (lin_slots_ != n_slots_) {
-    d_zs_.alloc(sizeof(double) * 4 * n_slots_);
-    const size_t acell = (size_t)(Wmax_ + 1) * (Lmax_ + 1);
-    d_a_in_.alloc(sizeof(double) * acell * nap * n_slots_);
-    d_a_out_.alloc(sizeof(double) * acell * nap * n_slots_);
-    lin_slots_ = n_slots_;
-  }
+  const int gsz = even_groups(n_need, slots_.n());
   std::memset(&a, 0, sizeof(a));
   a.lay = L;
   a.layp = shadow ? d_lays_.as<AutomatonLayout>() : d_lay_.as<AutomatonLayout>();
@@ -1588,12 +1464,12 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int
   a.p = plan_.arrays();
   a.xwc = d_xwc_.as<double>(); a.xwc_stride = (size_t)n_cells_total_;
   a.xwi = nullptr; a.xwi_stride = 0;
-  a.band_in = d_band_in_.as<double>(); a.band_out = d_band_out_.as<double>();
-  a.ext_in = d_ext_in_.as<double>(); a.ext_out = d_ext_out_.as<double>();
-  a.band_stride = band_stride_;
+  a.band_in = slots_.band_in.as<double>(); a.band_out = slots_.band_out.as<double>();
+  a.ext_in = slots_.ext_in.as<double>(); a.ext_out = slots_.ext_out.as<double>();
+  a.band_stride = slots_.band_stride();
   a.ext_stride = (size_t)(Lmax_ + 1) * S;
-  a.zs = d_zs_.as<double>();
-  a.a_in = d_a_in_.as<double>(); a.a_out = d_a_out_.as<double>();
+  a.zs = slots_.zs.as<double>();
+  a.a_in = slots_.a_in.as<double>(); a.a_out = slots_.a_out.as<double>();
   a.a_stride = (size_t)(Wmax_ + 1) * (Lmax_ + 1) * L.ap_rs;
   a.okbits_end = d_okbits_end_.as<uint32_t>();
   a.lmax = Lmax_;
@@ -1610,7 +1486,6 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int
     a.prof = d_prof_.as<long long>();
   }
   a.n_stage = (L.n_ints <= 4096 && !(opt_dbg_ & 8)) ? L.n_ints : L.n_small;
-  tables_S_ = S;
   return gsz;
 }
 
@@ -1621,7 +1496,7 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int
 template <class Work>
 void Engine::sweep_groups(const LinArgs& a, int n, const int32_t* h_ord, const int32_t* d_ord, const SeqPlan* d_sorted, int gsz,
                           int ns, Work work) {
-  const int slots_each = n_slots_ / ns;
+  const int slots_each = slots_.n() / ns;
   if (ns > 1) {   // every stream the same number of groups
     int n_groups = (n + slots_each - 1) / slots_each;
     n_groups = ((n_groups + ns - 1) / ns) * ns;
@@ -1705,8 +1580,7 @@ void Engine::run_lin_batch() {
     h_ord = h_order_r_.data();
     d_ord = d_order_r_.as<int32_t>();
     d_sorted = d_plans_sorted_r_.as<SeqPlan>();
-    const int n_groups = (n_ev + n_slots_ - 1) / n_slots_;
-    gsz = (n_ev + n_groups - 1) / n_groups;
+    gsz = even_groups(n_ev, slots_.n());
   }
   HIP_OK(hipMemsetAsync(d_seq_out_.as<double>() + (size_t)r0 * out_stride_, 0, sizeof(double) * (size_t)out_stride_ * n_ev, st_));
   HIP_OK(hipMemsetAsync(d_flagged_.as<void>(), 0, sizeof(int32_t), st_));
@@ -1722,7 +1596,7 @@ void Engine::run_lin_batch() {
   lin_weights(r0, n_ev);
   poison_tables();
   // (concurrent groups: not for a handful of sequences, whose tables debug_tables reads, nor under the phase profile)
-  const int ns = group_streams(n_ev >= 64 && n_slots_ >= 64 && !opt_profile_);
+  const int ns = group_streams(n_ev >= 64 && slots_.n() >= 64 && !opt_profile_);
   sweep_groups(a, n_ev, h_ord, d_ord, d_sorted, gsz, ns, [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
     HIP_OK(launch_lin_group(ak, G, Lg, Wg, opt_first_pass_only_, st));
   });
@@ -1733,12 +1607,13 @@ void Engine::run_lin_batch() {
     last_prof.assign(16, 0);
     for (size_t k = 0; k < hp.size(); ++k) last_prof[k % 16] += hp[k];
   }
-  tables_linear_ = n_flagged == 0;
+  if (n_flagged == 0) slots_.set_holds(TableSlots::Holds::Linear, a.lay.S);
+  else slots_.set_holds(TableSlots::Holds::DenseLog);
   if (n_flagged > 0) {
     ensure_sorted_plan();   // (the log-space kernels sum the role lists in list order: kernels.h)
     TrArgs t = log_pipeline_args();
-    // (dense tables over the buffers of the compact ones: as many slots as fit, at least one -- ensure_slots)
-    const int n_dense = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_slots_, (band_stride_ * (size_t)n_slots_) / t.band_stride));
+    // (dense tables over the buffers of the compact ones: as many slots as fit, at least one -- TableSlots::ensure)
+    const int n_dense = (int)std::max<size_t>(1, std::min<size_t>((size_t)slots_.n(), (slots_.band_stride() * (size_t)slots_.n()) / t.band_stride));
     for (int g0 = 0; g0 < n_flagged; g0 += n_dense) {
       const int G = std::min(n_dense, n_flagged - g0);
       t.grp = d_flagged_.as<int32_t>() + 1 + g0;
@@ -1853,26 +1728,27 @@ void Engine::debug_tables(double* inside, double* outside, double* inside_o, dou
   require_device();
   DeviceGuard dg(device_);
   if (n_seq_ != 1 || streaming_) throw StateError("debug_tables needs a resident batch of exactly one sequence");
-  if (n_slots_ < 1) throw StateError("debug_tables before train_eval");
-  if (tables_linear_ && opt_fast_ && !last_x_.empty()) {
+  auto linear = [&] { return slots_.holds() == TableSlots::Holds::Linear; };
+  // (only a train evaluation leaves tables the export can read: not a load, an option that invalidates the slots or a scan-family call)
+  if (slots_.n() < 1 || slots_.holds() == TableSlots::Holds::Nothing) throw StateError("debug_tables before train_eval");
+  if (linear() && opt_fast_ && !last_x_.empty()) {
     // the table-driven train kernels do not store the planes nothing reads (inside B, outside B and 1): the export repeats the
     // evaluation of the one sequence with the generic kernels, which store every plane
     std::vector<double> part(partial_len());
-    opt_fast_ = false;
-    try { train_partial(last_x_.data(), n_param(), part.data(), false, false); } catch (...) { opt_fast_ = true; throw; }
-    opt_fast_ = true;
+    ScopedValue<bool> generic(opt_fast_, false);
+    train_partial(last_x_.data(), n_param(), part.data(), false, false);
   }
   const SeqPlan& p = h_plans_[0];
   const int Sref = au_.S(), L = p.L, W = p.W;
   // (a schedule-1 evaluation of the linear pipeline leaves tables with one more state per row: the shadow of (0,0))
-  const int S = (tables_linear_ && tables_S_ > 0) ? tables_S_ : Sref;
+  const bool lin = linear();
+  const int S = lin ? slots_.linear_S() : Sref;
   const AutomatonLayout& TL = (S == lays_.S && lays_.shadow >= 0 && S != Sref) ? lays_ : lay_;
   const std::vector<int32_t>& TI = (&TL == &lays_) ? intss_ : ints_;
   const size_t cells = (size_t)(W + 1) * (L + 1);
   // the scaled-linear pipeline keeps Boltzmann weights times a power-of-two scale (lin_rules.h) in COMPACT tables
   // (TableView::ld / st, dp_rules.h): columns only for the states that are useful in a plane, nothing for cells that are not
   // parsable in it -- the export reads those as 0 -> log 0
-  const bool lin = tables_linear_;
   const size_t band = lin ? cells * TL.tab_row : (size_t)7 * cells * S, ext = (size_t)(L + 1) * S;
   auto fetch = [&](const DevBuf& src, size_t cnt) {
     std::vector<double> h(cnt);
@@ -1923,14 +1799,14 @@ void Engine::debug_tables(double* inside, double* outside, double* inside_o, dou
       dst[(((size_t)i * (W + 1) + d) * 7 + e) * Sref + ref_id(s)] = (i + d <= L) ? conv(v, sc) : NEGINF;
     }
   };
-  if (inside) reorder(fetch(d_band_in_, band), nullptr, inside, false);
+  if (inside) reorder(fetch(slots_.band_in, band), nullptr, inside, false);
   if (outside) {
-    std::vector<double> to = fetch(d_band_out_, band), ha;
-    if (lin && TL.n_ap > 0 && d_a_out_.bytes() >= sizeof(double) * cells * TL.ap_rs) {
+    std::vector<double> to = fetch(slots_.band_out, band), ha;
+    if (lin && TL.n_ap > 0 && slots_.a_out.bytes() >= sizeof(double) * cells * TL.ap_rs) {
       // the linear pipeline keeps only the direct part (rules 4a, 3a) of the plane-2 outside values; what arrives through
       // rule 2 is HA(k,l,t) = sum_i sum_{p=(s1,t)} outA(i,l,p) 1(i,k,s1) (lin_rules.h) -- added here for the export
       const int nA = TL.n_ap, nAs = TL.ap_rs;
-      const std::vector<double> ti = fetch(d_band_in_, band), ao = fetch(d_a_out_, cells * nAs);
+      const std::vector<double> ti = fetch(slots_.band_in, band), ao = fetch(slots_.a_out, cells * nAs);
       ha.assign(cells * S, 0.);
       for (int d = 0; d <= W; ++d) for (int i = 0; i + d <= L; ++i) for (int q = 0; q < nA; ++q) {
         const int s1 = TI[TL.ap_s1 + q], t = TI[TL.ap_t + q];
@@ -1944,8 +1820,8 @@ void Engine::debug_tables(double* inside, double* outside, double* inside_o, dou
     }
     reorder(to, ha.empty() ? nullptr : &ha, outside, true);
   }
-  if (inside_o) { auto h = fetch(d_ext_in_, ext); for (int j = 0; j <= L; ++j) for (int s = 0; s < S; ++s) if (s != TL.shadow) inside_o[(size_t)j * Sref + ref_id(s)] = conv(h[(size_t)j * S + s], cum[j]); }
-  if (outside_o) { auto h = fetch(d_ext_out_, ext); for (int j = 0; j <= L; ++j) for (int s = 0; s < S; ++s) if (s != TL.shadow) outside_o[(size_t)j * Sref + ref_id(s)] = conv(h[(size_t)j * S + s], cum[L] - cum[j]); }
+  if (inside_o) { auto h = fetch(slots_.ext_in, ext); for (int j = 0; j <= L; ++j) for (int s = 0; s < S; ++s) if (s != TL.shadow) inside_o[(size_t)j * Sref + ref_id(s)] = conv(h[(size_t)j * S + s], cum[j]); }
+  if (outside_o) { auto h = fetch(slots_.ext_out, ext); for (int j = 0; j <= L; ++j) for (int s = 0; s < S; ++s) if (s != TL.shadow) outside_o[(size_t)j * Sref + ref_id(s)] = conv(h[(size_t)j * S + s], cum[L] - cum[j]); }
   std::vector<double> o = fetch(d_seq_out_, out_stride_);
   const int nt = au_.n_theta();
   if (ENo) std::copy(o.begin() + 6, o.begin() + 6 + nt, ENo);
@@ -2035,7 +1911,7 @@ void Engine::useful_mask(int idx, uint8_t* mask, int cap) {
 int Engine::prepare_scan(LinArgs& a, const ScanPos& pos) {
   const int n = n_seq_;
   const size_t n_seqpos = (size_t)h_seq_off_[n];
-  const int gsz = prepare_lin(a, false, true, 0, std::max(1024, n_slots_));
+  const int gsz = prepare_lin(a, false, true, 0, std::max(1024, slots_.n()));
   a.scan = 1;
   a.ys = pos.ys.as<int32_t>(); a.ye = pos.ye.as<int32_t>();
   a.pos_start = pos.start.as<double>(); a.pos_inner = pos.inner.as<double>(); a.pos_end = pos.end.as<double>();
@@ -2054,15 +1930,14 @@ int Engine::prepare_scan(LinArgs& a, const ScanPos& pos) {
 
 // The fused scan kernel (the log-space form) and its block count.  After the scaled-linear sum passes it reuses their table and
 // trace slots; otherwise (pipeline 3) it gets table slots with trace tables, which the train pipelines do not reuse:
-// scan_log_form drops them (n_slots_ = 0) when done.
+// scan_log_form marks them (Holds::Trace) when done.
 DpArgs Engine::log_scan_args(bool sums_on_batch, int* n_blocks) {
   const int n = n_seq_, S = au_.S();
   if (sums_on_batch) {
-    *n_blocks = std::min(std::min(n_slots_, 2 * n_cu_), n);
+    *n_blocks = std::min(std::min(slots_.n(), 2 * n_cu_), n);
   } else {
-    ensure_slots(S, true, n);
-    lin_slots_ = 0;   // (the table slots were re-allocated with trace tables)
-    *n_blocks = std::min(n_slots_, n);
+    slots_.ensure(slot_request(S, 0, true, n), free_device_bytes());
+    *n_blocks = std::min(slots_.n(), n);
   }
   DpArgs d = base_args(lay_, d_ints_.as<int32_t>(), d_params_.as<double>(), plan_, d_okbits1_.as<uint32_t>(), S);
   d.lds = lds_layout(lay_, Lmax_, nword_max_, true);
@@ -2075,8 +1950,42 @@ void Engine::require_resident(const char* what, int n_param_in) {
   train_rows_ = false;   // (the scan family writes rows of its own into d_seq_out_)
 }
 
+// Sequences per launch of the log-space form of a call with per-slot scratch: what the table slots hold behind the sum passes,
+// else (pipeline 3) what the scratch of the call is sized for.
+int Engine::log_chunk(bool sums_on_batch, int n_blocks, int n_log) const {
+  return std::min(n_log, sums_on_batch ? slots_.n() : std::max(n_blocks, 1024));
+}
+
+// The pair reduction's arguments (pair_posteriors, context_profile).  pair_batch_args: its view of the batch -- plan, mask and rows --
+// which both forms of a call need.  pair_plane_fields: behind prepare_scan, with the arguments `a` of the sum pass, where the P plane
+// lies in a compact table slot (the scaled-linear form only).
+PairArgs Engine::pair_batch_args() const {
+  PairArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.plans = plan_.d_plans.as<SeqPlan>();
+  pa.okbits = d_okbits1_.as<uint32_t>();
+  pa.seq_out = d_seq_out_.as<double>(); pa.out_stride = out_stride_;
+  return pa;
+}
+
+void Engine::pair_plane_fields(PairArgs& pa, const LinArgs& a) const {
+  // the P plane's columns of the real states are 0 .. ncol-1: Automaton::flatten numbers a plane's columns in state order,
+  // and a shadow state comes last
+  int ncol = 0;
+  for (int s = 0; s < a.lay.S; ++s) {
+    const int c = ints_[a.lay.tab_cmap + ST_P * a.lay.S + s];
+    if (s == a.lay.shadow || c < 0) continue;
+    if (c != ncol) throw std::logic_error("pair reduction: the P plane's columns are not in state order");
+    ++ncol;
+  }
+  pa.p_cs = a.lay.tab_cs[ST_P]; pa.p_rs = a.lay.tab_rs[ST_P];
+  pa.ncol = ncol;
+  pa.band_stride = a.band_stride;
+  pa.skip_flagged = 1;
+}
+
 // The scaled-linear form of a scan-family call (pipeline 4): the scan's first sum pass on the groups, slots and streams of
-// Engine::scan.  fill(a) adds the call's fields to the argument record and sizes the call's per-slot scratch (n_slots_ is known
+// Engine::scan.  fill(a) adds the call's fields to the argument record and sizes the call's per-slot scratch (slots_.n() is known
 // only behind prepare_scan); group(ak, slot0, G, Lg, Wg, stream) queues a group's work as for sweep_groups.  Waits for the device
 // and returns the number of sequences the range check flagged (their indices into *flagged when given): those are left to
 // scan_log_form.
@@ -2085,12 +1994,12 @@ int Engine::scan_sums(const ScanPos& pos, Fill fill, Group group, std::vector<in
   LinArgs a;
   const int gsz = prepare_scan(a, pos);
   fill(a);
-  const int ns = group_streams(n_seq_ >= 128 && n_slots_ >= 128);
+  const int ns = group_streams(n_seq_ >= 128 && slots_.n() >= 128);
   sweep_groups(a, n_seq_, h_order_.data(), d_order_.as<int32_t>(), d_plans_sorted_.as<SeqPlan>(), gsz, ns, group);
   dbg_lap("scan sums: launches queued");
   const int n_flagged = read_flagged(flagged);
   dbg_lap("scan sums: device done");
-  tables_linear_ = false;
+  slots_.set_holds(TableSlots::Holds::Nothing);   // (not what a train evaluation leaves: debug_tables refuses)
   return n_flagged;
 }
 
@@ -2115,7 +2024,7 @@ void Engine::scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind 
       behind(list + c0, C);
     }
   }
-  if (!sums_on_batch) n_slots_ = 0;   // the slots of log_scan_args are not reused by the train pipelines
+  if (!sums_on_batch) slots_.set_holds(TableSlots::Holds::Trace);   // the slots of log_scan_args are not reused by the train pipelines
 }
 
 void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
@@ -2133,10 +2042,10 @@ void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
   DevBuf d_psi, d_rss, d_en;
   d_psi.alloc(4 * n_seqpos); d_rss.alloc(n_seqpos); d_en.alloc(8 * (size_t)n * (nt + 1));
   HIP_OK(hipEventRecord(ev_[1], st_));
-  const int stack_stride = 4 * (4 * (Lmax_ + 2));
+  const int stack_stride = trace_stack_stride(Lmax_);
   auto scan_fields = [&](DpArgs& d) {   // what the fused kernel reads and writes of a scan
-    d.tr_ext = d_tr_ext_.as<TraceRec>();
-    d.trace_stack = d_tr_stack_.as<int32_t>();
+    d.tr_ext = slots_.tr_ext.as<TraceRec>();
+    d.trace_stack = slots_.tr_stack.as<int32_t>();
     d.trace_stack_stride = stack_stride;
     d.sc_start = pos.start.as<double>(); d.sc_end = pos.end.as<double>(); d.sc_inner = pos.inner.as<double>();
     d.sc_psihat = d_psi.as<int32_t>(); d.sc_rss = d_rss.as<char>();
@@ -2151,11 +2060,10 @@ void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
     scan_sums(pos, [&](LinArgs& a) {
       // trace records of the Viterbi pass: the exterior chain's rows and the traceback stack per table slot (the band targets keep
       // none: scan_rules.h, cyk_retrace)
-      d_tr_ext_.alloc((size_t)(Lmax_ + 1) * S * n_slots_ * sizeof(TraceRec));
-      d_tr_stack_.alloc((size_t)n_slots_ * stack_stride * sizeof(int32_t));
+      slots_.ensure_trace();
       dbg_lap("scan: trace slots");
-      a.tr_ext = d_tr_ext_.as<TraceRec>();
-      a.trace_stack = d_tr_stack_.as<int32_t>(); a.trace_stack_stride = stack_stride;
+      a.tr_ext = slots_.tr_ext.as<TraceRec>();
+      a.trace_stack = slots_.tr_stack.as<int32_t>(); a.trace_stack_stride = stack_stride;
       a.sc_psihat = d_psi.as<int32_t>(); a.sc_rss = d_rss.as<char>();
     }, [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
       HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
@@ -2239,11 +2147,7 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   HIP_OK(hipStreamSynchronize(st_));
   d_pr_si_.alloc(4 * (size_t)n_kept); d_pr_sj_.alloc(4 * (size_t)n_kept); d_pr_sp_.alloc(8 * (size_t)n_kept);
   HIP_OK(hipMemsetAsync(d_pr_cnt_.as<void>(), 0, 8 * (size_t)n, st_));
-  PairArgs pa;
-  std::memset(&pa, 0, sizeof(pa));
-  pa.plans = plan_.d_plans.as<SeqPlan>();
-  pa.okbits = d_okbits1_.as<uint32_t>();
-  pa.seq_out = d_seq_out_.as<double>(); pa.out_stride = out_stride_;
+  PairArgs pa = pair_batch_args();
   pa.p_stride = pcells;
   pa.min_prob = min_prob;
   pa.unpaired = d_pr_unp_.as<double>();
@@ -2272,21 +2176,9 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   const bool sums_on_batch = opt_pipeline_ == 4;
   if (sums_on_batch)
     n_flagged = scan_sums(pos, [&](LinArgs& a) {
-      d_pr_P_.alloc(8 * pcells * (size_t)n_slots_);
-      mea_scratch((size_t)n_slots_);
-      // the P plane's columns of the real states are 0 .. ncol-1: Automaton::flatten numbers a plane's columns in state order,
-      // and a shadow state comes last
-      int ncol = 0;
-      for (int s = 0; s < a.lay.S; ++s) {
-        const int c = ints_[a.lay.tab_cmap + ST_P * a.lay.S + s];
-        if (s == a.lay.shadow || c < 0) continue;
-        if (c != ncol) throw std::logic_error("pair_posteriors: the P plane's columns are not in state order");
-        ++ncol;
-      }
-      pa.p_cs = a.lay.tab_cs[ST_P]; pa.p_rs = a.lay.tab_rs[ST_P];
-      pa.ncol = ncol;
-      pa.band_stride = a.band_stride;
-      pa.skip_flagged = 1;
+      d_pr_P_.alloc(8 * pcells * (size_t)slots_.n());
+      mea_scratch((size_t)slots_.n());
+      pair_plane_fields(pa, a);
     }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
       HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
       PairArgs pk = pa;
@@ -2299,7 +2191,7 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
     });
   // ---- the log-space form, in chunks of at most as many sequences as the table slots hold (the P scratch is bounded by the chunk)
   scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
-    const int chunk = std::min(n_log, sums_on_batch ? n_slots_ : std::max(n_blocks, 1024));
+    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
     if (!sums_on_batch) { d_pr_P_.alloc(8 * pcells * (size_t)chunk); mea_scratch((size_t)chunk); }
     d.pair_p = d_pr_P_.as<double>();
     d.pair_stride = pcells;
@@ -2411,28 +2303,14 @@ void Engine::context_profile(const double* x, int n_param_in, double* profile) {
     ck.u = ck.P + pcells; ck.h = ck.P + 2 * pcells; ck.b = ck.P + 3 * pcells;
     ck.o = d_cx_o_.as<double>() + slot0 * ocol;
   };
-  PairArgs pa;
-  std::memset(&pa, 0, sizeof(pa));
-  pa.plans = ca.plans;
-  pa.okbits = d_okbits1_.as<uint32_t>();
-  pa.seq_out = ca.seq_out; pa.out_stride = out_stride_;
+  PairArgs pa = pair_batch_args();
   pa.p_stride = 4 * pcells;
   int n_flagged = 0;
   const bool sums_on_batch = opt_pipeline_ == 4;
   if (sums_on_batch)
     n_flagged = scan_sums(pos, [&](LinArgs& a) {
-      scratch((size_t)n_slots_);
-      int ncol = 0;   // (the P plane's columns of the real states are 0 .. ncol-1, as pair_posteriors requires)
-      for (int s = 0; s < a.lay.S; ++s) {
-        const int c = ints_[a.lay.tab_cmap + ST_P * a.lay.S + s];
-        if (s == a.lay.shadow || c < 0) continue;
-        if (c != ncol) throw std::logic_error("context_profile: the P plane's columns are not in state order");
-        ++ncol;
-      }
-      pa.p_cs = a.lay.tab_cs[ST_P]; pa.p_rs = a.lay.tab_rs[ST_P];
-      pa.ncol = ncol;
-      pa.band_stride = a.band_stride;
-      pa.skip_flagged = 1;
+      scratch((size_t)slots_.n());
+      pair_plane_fields(pa, a);
       ca.skip_flagged = 1;
     }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
       HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
@@ -2451,7 +2329,7 @@ void Engine::context_profile(const double* x, int n_param_in, double* profile) {
     });
   // ---- the log-space form, in chunks of at most as many sequences as the scratch holds
   scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
-    const int chunk = std::min(n_log, sums_on_batch ? n_slots_ : std::max(n_blocks, 1024));
+    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
     if (!sums_on_batch) scratch((size_t)chunk);
     d.ctx = ca;
     at_slot(d.ctx, 0);
@@ -2508,7 +2386,7 @@ void Engine::sample_structures(const double* x, int n_param_in, int n_samples, u
     ScanPos pos(n_seqpos, n);
     n_flagged = scan_sums(pos, [&](LinArgs&) {
       sa.stack_lanes = std::min(n_samples, kSampleLanes);
-      d_sm_stack_.alloc(sizeof(TraceFrame) * (size_t)n_slots_ * sa.stack_lanes * cap);
+      d_sm_stack_.alloc(sizeof(TraceFrame) * (size_t)slots_.n() * sa.stack_lanes * cap);
     }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
       HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_INSIDE, st));
       SampleArgs sk = sa;
