@@ -270,6 +270,26 @@ int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, dou
  * |ln Z| of a few thousand).  elemdp_last_timing afterwards: [whole call including the copy of the profile to the host, sum
  * passes + context kernels, sequences handed to the log-space form].  elemdp_scan, the pair calls (the list of the last one stays valid), elemdp_sample and the train calls are unaffected. */
 int elemdp_context_profile(elemdp_handle* h, const double* x, int32_t n_param, double* profile);
+/* Posterior motif-node profile of every position under the motif model x: with M = elemdp_n_node,
+ * profile[M * (seq_off[n] + p) + m] is the probability that base p (0-based) of sequence n is emitted by pattern node m -- 0 is
+ * 'z', M-1 is 'o', the numbering of psihat and of the node bytes of elemdp_sample -- over the ensemble of the scan's first sum pass
+ * (terminals ari and nasi: the ensemble of elemdp_pair_posteriors, elemdp_sample and elemdp_context_profile), from its inside /
+ * outside tables and Z(ari, nasi).  Every base of a derivation is emitted once, by one of five rules, and the profile is the sum of
+ * their posteriors routed to the emitted node, clamped to [0, 1]:
+ *   L <- L  in(L, i, d, s) out(L, i, d, s): node r(s) at j-1;      3a  out(2, i, d, s) wr in(2, i, d-1, s1): node r(s) at j-1;
+ *   5a  out(M, i, d, s) wl in(M, i+1, d-1, sl): node l(sl) at i;   8   out_o(p+1, s) wt in_o(p, s1): node r(s) at p;
+ *   1a / 1b  out(P, i, d, s) wp (in(P, i+1, d-2, sp) xst + in(E, i+1, d-2, sp)): node l(sp) at i and node r(s) at j-1.
+ * There is no remainder column and no renormalisation: a row sums to 1 wherever the tables' inside and outside agree (within
+ * 1e-12 for a sequence in the scaled-linear form, about 1e-15 |ln Z| per term in the log-space form); with max_iloop < 30 the
+ * reference's outside pass enumerates interior loops its inside pass does not, and the sum follows the tables.  The sum over the
+ * nodes 1 .. M-2 is exp(inner) of elemdp_scan.  A sequence without any parse (Z = 0) has profile 1 at node 0 and 0 elsewhere,
+ * exactly; under ELEMDP_NO_RSS rule 8 alone carries the alignment.  Sequences that leave the double range of the scaled-linear
+ * tables, and every sequence under option pipeline 3, go through the same rule on the log-space tables of the fused scan kernel.
+ * profile NULL or more than 255 pattern nodes is ELEMDP_EINVAL, a call before elemdp_load_batch ELEMDP_ESTATE.
+ * elemdp_last_timing afterwards: [whole call including the copy of the profile to the host, sum passes + node kernels, sequences
+ * handed to the log-space form].  elemdp_scan, the pair calls (the list of the last one stays valid), elemdp_sample,
+ * elemdp_context_profile and the train calls are unaffected. */
+int elemdp_node_profile(elemdp_handle* h, const double* x, int32_t n_param, double* profile);
 
 /* timing of the last train evaluation, measured with HIP events on the engine's stream:
  * ms[0] = whole evaluation, ms[1] = the DP pipeline only (all kernels of the inside/outside sweeps),

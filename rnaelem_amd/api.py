@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -90,6 +90,7 @@ def load_library():
         L.elemdp_pair_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int64), dp, C.c_char_p, dp]
         L.elemdp_sample.argtypes = [hp, dp, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(C.c_uint8), dp, i32]
         L.elemdp_context_profile.argtypes = [hp, dp, C.c_int32, dp]
+        L.elemdp_node_profile.argtypes = [hp, dp, C.c_int32, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
         L.elemdp_last_timing.argtypes = [hp, dp, C.c_int32]
         L.elemdp_epoch_permutation.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
@@ -456,6 +457,19 @@ class Engine:
         self._check(self._lib.elemdp_context_profile(self._h, _dp(x), self.n_param, _dp(prof)))
         return [prof[7 * int(off[k]):7 * int(off[k + 1])].reshape(-1, 7).copy() for k in range(self.n_seq)]
 
+    # ---- posterior motif-node profiles
+    def node_profiles(self, x):
+        """One (L, M) array per sequence, M = n_node: the probability that each base is emitted by each pattern node, in the node
+        order of describe()["node"] (0 = 'z', M-1 = 'o': the numbering of psihat and of the sampler's node rows), over the
+        ensemble of pair_posteriors, context_profiles and sample_structures.  Rows sum to 1."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        M = self.n_node
+        n_pos = int(off[-1]) if off is not None else 0
+        prof = np.zeros(max(M * n_pos, 1))
+        self._check(self._lib.elemdp_node_profile(self._h, _dp(x), self.n_param, _dp(prof)))
+        return [prof[M * int(off[k]):M * int(off[k + 1])].reshape(-1, M).copy() for k in range(self.n_seq)]
+
     def last_timing(self):
         """[ms whole evaluation, ms DP pipeline, sequences re-evaluated in log space]"""
         ms = np.zeros(3)
@@ -469,3 +483,15 @@ class Engine:
 
     def kernel_name(self):
         return self._lib.elemdp_kernel_name().decode()
+
+
+def alignment_confidence(profile, psihat):
+    """Confidence of a CYK alignment: N(p, psihat[p]) for every position p, from the (L, M) node profile of the sequence
+    (Engine.node_profiles) and the node row the scan prints for it."""
+    profile = np.asarray(profile, dtype=np.float64)
+    psihat = np.asarray(psihat, dtype=np.int64)
+    if profile.ndim != 2 or psihat.shape != (profile.shape[0],):
+        raise ValueError("alignment_confidence: an (L, M) profile and L node indices are expected")
+    if psihat.size and (psihat.min() < 0 or psihat.max() >= profile.shape[1]):
+        raise ValueError("alignment_confidence: node index out of range")
+    return profile[np.arange(profile.shape[0]), psihat]

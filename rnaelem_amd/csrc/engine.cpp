@@ -36,6 +36,7 @@
 #include "kernels.h"
 #include "lin_params.h"
 #include "live_blocks.h"
+#include "node_rules.h"
 #include "sample_rules.h"
 #include "table_slots.h"
 
@@ -205,6 +206,8 @@ class Engine {
   void sample_structures(const double* x, int n_param, int n_samples, uint64_t seed, int64_t index_base, const SampleOut& out);
   // structural context profiles (ctx_rules.h): 7 doubles per position of the batch, O L R H B I M
   void context_profile(const double* x, int n_param, double* profile);
+  // posterior motif-node profiles (node_rules.h): n_node doubles per position of the batch
+  void node_profile(const double* x, int n_param, double* profile);
   int partial_len() const { return 4 + 2 * au_.n_theta() + 4; }
   void set_option(const std::string& key, double v);
   void comm_init(int rank, int world, const void* id);
@@ -357,6 +360,7 @@ class Engine {
   DevBuf d_sm_rss_, d_sm_node_, d_sm_logp_, d_sm_status_, d_sm_stack_;   // sample_structures
   // context profiles: P, u, h, b of the table slots (four [i][d] arrays per slot), their exterior columns, the profile of the call
   DevBuf d_cx_cells_, d_cx_o_, d_cx_prof_;
+  DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
 
   Automaton au_;
   EnergyTables et_;
@@ -430,6 +434,7 @@ class Engine {
   int opt_schedule_ = 1;   // 1 = linear (ari pass + one-state nasi pass), 0 = the reference's two full passes
   int opt_dbg_ = 0;        // timing experiments (LinArgs::dbg); results are wrong when set
   int opt_group_ = 0;      // sequences swept in lockstep by the batch pipeline (0 = auto)
+  int opt_node_rules_ = NR_ALL;   // node_profile: the emitting rules that take part (NodeRule bits)
   DevBuf d_prof_;
   DevBuf d_okbits_end_, d_nitems_, d_plans_all_;   // scratch of build_planset and of the canonical mask, kept across loads
   // scratch of the BPP filter, which nothing else reads; kept across loads (the mini-batch trainer loads before every evaluation)
@@ -599,6 +604,10 @@ void Engine::set_option(const std::string& key, double v) {
     opt_pipeline_ = (int)v;
   }
   else if (key == "group") opt_group_ = (int)v;
+  else if (key == "node_rules") {   // (node_profile: the emitting rules that take part, NodeRule bits; a subset gives that part of the profile)
+    if (v < 1 || v > NR_ALL) throw ArgError("node_rules: 1 .. 63 (bits: L <- L, rule 3a, rule 5a, left base of rules 1a / 1b, rule 8, right base of rules 1a / 1b)");
+    opt_node_rules_ = (int)v;
+  }
   else if (key == "schedule") opt_schedule_ = (int)v;
   else if (key == "dbg") opt_dbg_ = (int)v;
   else if (key == "bpp_log") opt_bpp_log_ = v != 0;
@@ -2355,6 +2364,67 @@ void Engine::context_profile(const double* x, int n_param_in, double* profile) {
 }
 
 
+// ---- posterior motif-node profiles under the motif model (node_rules.h).  The scan's first sum pass per group,
+// then k_node_pos on the group's table slots, before the next group of the stream reuses them; the log-space form -- the fused
+// scan kernel up to its first outside pass, then the same rule on its dense tables -- for the sequences that leave the double
+// range and under pipeline 3.  Both forms write the profile of the call directly: no scratch per slot.  Leaves the list of the
+// last pair call alone.
+void Engine::node_profile(const double* x, int n_param_in, double* profile) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (!profile) throw ArgError("node_profile: null profile");
+  const int M = au_.M();
+  if (M > 255) throw ArgError("node_profile: more than 255 pattern nodes");
+  if (streaming_) {
+    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+      e.node_profile(x, n_param_in, profile + (size_t)M * (size_t)(h_seq_off_[c0] - h_seq_off_[0]));
+    });
+    return;
+  }
+  require_resident("node_profile", n_param_in);
+  upload_params(x, lay_, false);
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  ScanPos pos(n_seqpos, n);
+  d_nd_prof_.alloc(8 * (size_t)M * std::max<size_t>(n_seqpos, 1));
+  std::vector<int32_t> lists;
+  node_lists_build(lay_, ints_.data(), &lists);
+  d_nd_lists_.upload(lists, st_);
+  HIP_OK(hipStreamSynchronize(st_));   // (the host vector goes out of use with the copy)
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  NodeArgs na;
+  std::memset(&na, 0, sizeof(na));
+  na.lists = d_nd_lists_.as<int32_t>();
+  na.M = M;
+  na.rules = opt_node_rules_;
+  na.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
+  na.profile = d_nd_prof_.as<double>();
+  int n_flagged = 0;
+  const bool sums_on_batch = opt_pipeline_ == 4;
+  if (sums_on_batch)
+    n_flagged = scan_sums(pos, [&](LinArgs& a) {
+      if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("node_profile: the scan sweeps another automaton than the lists name");
+    }, [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      HIP_OK(launch_node_pos(ak, na, G, Lg, st));
+    });
+  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+    d.node = na;
+    return std::max(n_log, 1);
+  }, [&](const int32_t*, int) {});
+  HIP_OK(hipEventRecord(ev_[3], st_));
+  if (n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_nd_prof_.as<void>(), 8 * (size_t)M * n_seqpos, hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms_all = 0, ms_dp = 0;
+  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
+  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
+  last_ms[0] = ms_all;
+  last_ms[1] = ms_dp;
+  last_ms[2] = (double)n_flagged;
+}
+
+
 // ---- stochastic samples of derivations (sample_rules.h).  The inside sweeps of the scan's first sum pass per group
 // (launch_lin_scan_group, SCAN_PASS_INSIDE: no outside pass) and k_sample on the group's slots right behind them, before the next group of the
 // stream reuses them; the log-space form in the fused scan kernel for the sequences the range check flags.
@@ -2723,6 +2793,12 @@ int elemdp_context_profile(elemdp_handle* h, const double* x, int32_t n_param, d
   ELEMDP_TRY
   if (!h || !x || !profile) throw elemdp::ArgError("elemdp_context_profile: null argument");
   h->e->context_profile(x, n_param, profile);
+  ELEMDP_CATCH
+}
+int elemdp_node_profile(elemdp_handle* h, const double* x, int32_t n_param, double* profile) {
+  ELEMDP_TRY
+  if (!h || !x || !profile) throw elemdp::ArgError("elemdp_node_profile: null argument");
+  h->e->node_profile(x, n_param, profile);
   ELEMDP_CATCH
 }
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {

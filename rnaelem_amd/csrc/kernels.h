@@ -101,6 +101,16 @@ struct CtxArgs {
   int32_t no_rss;                 // a model without secondary structure: every position is exterior
 };
 
+// ---- posterior motif-node profiles (node_rules.h, node_kernels.hip): the profile of batch index n goes to
+// profile + M * seq_base, M doubles per position in node order (0 = 'z' .. M-1 = 'o')
+struct NodeArgs {
+  const int32_t* lists;           // the transitions by emitted node (node_lists_build)
+  int32_t M;                      // pattern nodes
+  int32_t rules;                  // NodeRule bits: the rules that take part (all of them unless option node_rules says otherwise)
+  int32_t no_rss;                 // a model without secondary structure: rule 8 alone, the band tables are not read
+  double* profile;
+};
+
 struct DpArgs {
   AutomatonLayout lay;            // host-visible copy (launch geometry, LDS sizes)
   const AutomatonLayout* layp;    // the same record in device memory: kernels read it through this pointer
@@ -143,6 +153,9 @@ struct DpArgs {
   // SCAN, structural context profiles (ctx_rules.h, log-space form): ctx.u non-null = stop after inside + the first outside pass
   // and write P, u, h, b and o of the sequence order[w] to slot w of ctx (the rows k_ctx_seq reads behind the launch)
   CtxArgs ctx;
+  // SCAN, posterior motif-node profiles (node_rules.h, log-space form): node.profile non-null = stop after inside + the first
+  // outside pass and write the M columns of every position of the sequence order[w]
+  NodeArgs node;
 };
 
 // arguments of the diagonal-synchronous train pipeline (train_kernels.hip)
@@ -346,6 +359,8 @@ hipError_t launch_sample(const LinArgs& a, const SampleArgs& s, int G, hipStream
 // it, or behind the fused scan kernel (DpArgs::ctx)
 hipError_t launch_ctx_cells(const LinArgs& a, const CtxArgs& c, int G, int cells_max, hipStream_t st);
 hipError_t launch_ctx_seq(const CtxArgs& c, int G, hipStream_t st);
+// k_node_pos behind launch_lin_scan_group (SCAN_PASS_START) on the same slots and stream: one wave per (sequence, position)
+hipError_t launch_node_pos(const LinArgs& a, const NodeArgs& c, int G, int Lmax, hipStream_t st);
 // kept pairs of every sequence of the batch (the staging capacity), off[0..n] = exclusive prefix of cnt[0..n) with off[n] the total,
 // and the scatter of the staging list into the final list ordered by (sequence, i, j)
 hipError_t launch_pair_kept(const SeqPlan* plans, const uint32_t* okbits, int n, int64_t* kept, hipStream_t st);

@@ -21,6 +21,7 @@
 #include "dp_rules.h"
 #include "energy_rules.h"
 #include "kernels.h"
+#include "node_rules.h"
 #include "pair_rules.h"
 #include "plan_rules.h"
 #include "sample_lane.h"
@@ -763,6 +764,17 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
             a.ctx.b[cb + t] = c.b;
           }
           for (int t = tid; t < L; t += kThreads) a.ctx.o[(size_t)w * a.ctx.o_stride + t] = live ? ctx_exterior(f, m, q, Tin, Tout, t) : 1.;
+          continue;
+        }
+        if (a.node.profile) {   // posterior motif-node profiles (node_rules.h): one (position, node) per lane on this first pass
+          const NodeLog f(ZL);
+          const NodeLists nl{a.node.lists, a.node.M, a.node.rules};
+          const bool live = ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL;
+          double* prof = a.node.profile + (size_t)a.node.M * p.seq_base;
+          for (int t = tid; t < L * a.node.M; t += kThreads) {
+            const int pos = t / a.node.M, node = t - pos * a.node.M;
+            prof[t] = live ? node_value(f, nl, m, q, Tin, Tout, pos, node, !no_rss) : node_no_parse(node);
+          }
           continue;
         }
         if (tid == 0) l_zs[4] = (double)last_argmax(Pys, L);

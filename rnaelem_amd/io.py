@@ -257,3 +257,42 @@ def read_context_records(path):
         out.append((lines[k][4:], np.array(cols, dtype=np.float64).T.reshape(-1, n)))
         k += 1 + n
     return out
+
+
+def node_record(rid, profile, names, confidence=None):
+    """Record of one sequence in the `scan --out-nodes` file: `id: <id>`, then one line per pattern node `<index><name>: [...]`
+    with the probability that the node emits each base (6 significant digits); profile: an (L, M) array as Engine.node_profiles
+    gives it, names: describe()["node"].  confidence (api.alignment_confidence of the scan's psihat) adds a last line
+    `confidence: [...]`."""
+    M = len(names)
+    profile = np.asarray(profile, dtype=np.float64).reshape(-1, M)
+    lines = ["id: " + rid] + ["%d%s: %s" % (k, c, fmt_vec(profile[:, k])) for k, c in enumerate(names)]
+    if confidence is not None:
+        lines.append("confidence: " + fmt_vec(confidence))
+    return "\n".join(lines) + "\n"
+
+
+def read_node_records(path):
+    """-> list of (id, node names, (L, M) array, confidence or None) from a `scan --out-nodes` file."""
+    def vec(body):
+        body = body.strip("[]")
+        return [float(v) for v in body.split(",")] if body else []
+
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+    while k < len(lines) and lines[k].startswith("id: "):
+        rid = lines[k][4:]
+        k += 1
+        names, cols, conf = "", [], None
+        while k < len(lines) and lines[k] and not lines[k].startswith("id: "):
+            head, body = lines[k].split(": ", 1)
+            if head == "confidence":
+                conf = np.array(vec(body), dtype=np.float64)
+            else:
+                if not head[:-1].isdigit() or int(head[:-1]) != len(cols):
+                    raise ValueError("node record %r: line %r where node %d was expected" % (rid, head, len(cols)))
+                names += head[-1]
+                cols.append(vec(body))
+            k += 1
+        out.append((rid, names, np.array(cols, dtype=np.float64).T.reshape(-1, len(cols)), conf))
+    return out
