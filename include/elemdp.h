@@ -110,6 +110,11 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *                       the value takes its cells per block); 0 (default): 32;
  *     "useful_mask"     1 (default): the train sweeps skip the table entries no complete parse reaches (elemdp_useful_mask);
  *                       0: they compute every entry -- kept as the A/B switch and as the tests' reference
+ *     "loop_prepass"    1 (default): a row pre-pass fills the inside L plane before the table-driven train sweep, whose workgroups
+ *                       then compute no L, skip the cells that are useful in the L plane alone (lists of their own:
+ *                       elemdp_live_blocks_inside) and the diagonals below the first hairpin; active wherever "useful_mask" is,
+ *                       the deterministic mode included (every L entry is bit-identical to the sweep's own); 0: the sweep
+ *                       computes L itself, with one set of lists -- the A/B switch and the tests' reference
  *   measurement / tests
  *     "profile"         in-kernel phase clocks for elemdp_debug_profile; "dbg": switch phases off (results invalid);
  *     "poison"          1: every table is filled with NaN before an evaluation (an unmasked read of an entry nobody stored shows) */
@@ -143,13 +148,23 @@ int elemdp_useful_mask_host(const uint8_t* kept, const uint8_t* unp, int32_t L, 
  * int16 own_lo, int16 own_end (the block owns the cells [own_lo, own_end)), int16 count.  stride >= (L + 8) / 8.  cpb_cap[2]
  * receives the cells per block and the span a block may cover.  taken[W+1] (may be NULL) receives 1 where a train evaluation of
  * the current options ("live_blocks", "useful_mask", "deterministic") sweeps diagonal d from
- * its list, 0 where it takes consecutive cells. */
+ * its list, 0 where it takes consecutive cells -- the outside sweep, and the inside sweep without the loop pre-pass; behind the
+ * pre-pass ("loop_prepass" 1) the inside sweep takes the second set, elemdp_live_blocks_inside. */
 int elemdp_live_blocks(elemdp_handle* h, int32_t seq_index, int32_t* counts, void* records, int32_t stride, int32_t* cpb_cap,
                        int32_t* taken);
 /* Host only: the same lists by the same rule on the CPU from a mask[(W+1)*(L+1)] (any non-zero byte is a live cell) for blocks
  * of cpb live cells that span at most cap cells, cpb <= cap <= 64 (else ELEMDP_EINVAL); stride >= ceil((L + 1) / cpb). */
 int elemdp_live_blocks_host(const uint8_t* mask, int32_t L, int32_t W, int32_t cpb, int32_t cap, int32_t* counts, void* records,
                             int32_t stride);
+/* Debug: as elemdp_live_blocks, for the second set of lists of the plan -- the lists of the inside sweep behind the loop pre-pass
+ * (option "loop_prepass"), in which a cell is live where its mask byte has a bit other than 128 (L).  taken[d] = 1 where a train
+ * evaluation of the current options sweeps diagonal d of the inside pass from this list: never without the pre-pass, and never on
+ * a diagonal below the first one that can hold an entry outside the L plane (no inside launch there at all). */
+int elemdp_live_blocks_inside(elemdp_handle* h, int32_t seq_index, int32_t* counts, void* records, int32_t stride, int32_t* cpb_cap,
+                              int32_t* taken);
+/* Host only: elemdp_live_blocks_host with the bits that make a cell live (1 .. 255; 255 = any non-zero byte, 127 = the inside set). */
+int elemdp_live_blocks_host_bits(const uint8_t* mask, int32_t L, int32_t W, int32_t cpb, int32_t cap, int32_t bits, int32_t* counts,
+                                 void* records, int32_t stride);
 
 /* == RNAelemTrainer::operator()(x, fn, gr) over the whole resident batch with --no-shuffle
  * (motif_trainer.hpp:595-633 + RNAelemTrainDP::operator() :124-272).  fn/gr are the UNREGULARISED

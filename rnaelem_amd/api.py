@@ -22,7 +22,7 @@ DBG_FIX_RSS, DBG_NO_TURN = 1 << 9, 1 << 10
 # every symbol include/elemdp.h declares
 SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "elemdp_create", "elemdp_destroy",
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
-           "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_train_eval",
+           "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
            "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
@@ -78,6 +78,8 @@ def load_library():
         L.elemdp_useful_mask_host.argtypes = [u8, u8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, u8]
         L.elemdp_live_blocks.argtypes = [hp, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.elemdp_live_blocks_host.argtypes = [u8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]
+        L.elemdp_live_blocks_inside.argtypes = L.elemdp_live_blocks.argtypes
+        L.elemdp_live_blocks_host_bits.argtypes = [u8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]
         L.elemdp_train_eval.argtypes = [hp, dp, C.c_int32, dp, dp, dp, i32]
         L.elemdp_train_partial.argtypes = [hp, dp, C.c_int32, C.c_void_p, C.c_int32]
         L.elemdp_train_finish.argtypes = [hp, dp, dp, dp, dp, i32]
@@ -152,6 +154,7 @@ def useful_mask_host(kept, max_iloop=30, flags=0, unp=None):
 
 
 # a record of the live-block lists (elemdp_live_blocks): 16 bytes
+LIVE_INSIDE_BITS = 0x7f   # every mask bit but L (128): the cells the inside sweep behind the loop pre-pass computes
 LIVE_BLOCK = np.dtype([("live", "<u8"), ("first", "<i2"), ("own_lo", "<i2"), ("own_end", "<i2"), ("count", "<i2")])
 
 
@@ -169,17 +172,22 @@ def _live_block_lists(counts, recs):
     return out
 
 
-def live_blocks_host(mask, cpb, cap):
+def live_blocks_host(mask, cpb, cap, bits=None):
     """Live-block lists of one sequence on the CPU from a mask [(W+1), (L+1)] (any non-zero byte is a live cell): per diagonal d
     the blocks (first cell, [live cells], (own_lo, own_end)) of at most `cpb` live cells that span at most `cap` cells (host;
-    elemdp_live_blocks_host).  cap < cpb is refused."""
+    elemdp_live_blocks_host).  cap < cpb is refused.  bits: the mask bits that make a cell live (elemdp_live_blocks_host_bits;
+    LIVE_INSIDE_BITS = the lists of the inside sweep behind the loop pre-pass)."""
     mask = np.ascontiguousarray(mask, dtype=np.uint8)
     W, L = mask.shape[0] - 1, mask.shape[1] - 1
     stride = (L + cpb) // max(int(cpb), 1) if cpb >= 1 else 1
     counts = np.zeros(W + 1, dtype=np.int32)
     recs = np.zeros((W + 1, max(stride, 1)), dtype=LIVE_BLOCK)
-    rc = load_library().elemdp_live_blocks_host(_u8(mask), L, W, int(cpb), int(cap), counts.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                recs.ctypes.data_as(C.c_void_p), recs.shape[1])
+    if bits is None:
+        rc = load_library().elemdp_live_blocks_host(_u8(mask), L, W, int(cpb), int(cap), counts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    recs.ctypes.data_as(C.c_void_p), recs.shape[1])
+    else:
+        rc = load_library().elemdp_live_blocks_host_bits(_u8(mask), L, W, int(cpb), int(cap), int(bits),
+                                                         counts.ctypes.data_as(C.POINTER(C.c_int32)), recs.ctypes.data_as(C.c_void_p), recs.shape[1])
     if rc:
         raise ElemdpError(rc, "live_blocks_host")
     return _live_block_lists(counts, recs)
@@ -268,10 +276,11 @@ class Engine:
         self._check(self._lib.elemdp_useful_mask(self._h, index, _u8(out), out.size))
         return out
 
-    def live_blocks(self, index, with_taken=False):
+    def live_blocks(self, index, with_taken=False, inside=False):
         """The live-block lists of sequence `index` for the model's cells per block and the span of the current options:
         (lists, cpb, cap), lists as live_blocks_host gives them; with_taken: also a bool array [W+1], True where a train
-        evaluation of the current options sweeps that diagonal from its list (False: consecutive cells)."""
+        evaluation of the current options sweeps that diagonal from its list (False: consecutive cells).  inside: the second
+        set, the lists of the inside sweep behind the loop pre-pass (elemdp_live_blocks_inside)."""
         L = int(self._off[index + 1] - self._off[index])
         W = min(L, self.max_span)
         stride = (L + 8) // 8
@@ -280,8 +289,9 @@ class Engine:
         cc = np.zeros(2, dtype=np.int32)
         taken = np.zeros(W + 1, dtype=np.int32)
         ip = C.POINTER(C.c_int32)
-        self._check(self._lib.elemdp_live_blocks(self._h, index, counts.ctypes.data_as(ip), recs.ctypes.data_as(C.c_void_p),
-                                                 stride, cc.ctypes.data_as(ip), taken.ctypes.data_as(ip)))
+        entry = self._lib.elemdp_live_blocks_inside if inside else self._lib.elemdp_live_blocks
+        self._check(entry(self._h, index, counts.ctypes.data_as(ip), recs.ctypes.data_as(C.c_void_p),
+                          stride, cc.ctypes.data_as(ip), taken.ctypes.data_as(ip)))
         out = (_live_block_lists(counts, recs), int(cc[0]), int(cc[1]))
         return out + (taken != 0,) if with_taken else out
 

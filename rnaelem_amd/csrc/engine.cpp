@@ -153,7 +153,9 @@ struct PlanSet {
   int64_t n_blocks = 0;
   int blk_cpb = 0, blk_cap = 0;
   std::vector<int32_t> h_blk_max, h_blk_grid;
+  std::vector<int32_t> h_blk_grid_in;   // the same choice for the inside set (the lists of the bytes without UB_L: live_blocks.h)
   bool blk_all = false;            // built under live_blocks 2 (lists on every diagonal)
+  bool blk_two = false;            // the inside set (the bytes without UB_L) is built too: only where the loop pre-pass runs, or for its read-back
   int64_t n_cells = 0;
   bool permuted = false;   // keep item copies in the secondary orders (resident plan of the train pipeline)
   bool inner_only = false; // build only the by_inner order (the BPP filter needs no outside values of loop cells)
@@ -183,7 +185,7 @@ class Engine {
   ~Engine();
 
   void useful_mask(int idx, uint8_t* mask, int cap);
-  void live_blocks(int idx, int32_t* counts, void* records, int stride, int32_t* cpb_cap, int32_t* taken);
+  void live_blocks(int idx, int32_t* counts, void* records, int stride, int32_t* cpb_cap, int32_t* taken, bool inside = false);
   int n_param() const { return au_.n_theta() + 2; }
   int n_state() const { return au_.S(); }
   int n_node() const { return au_.M(); }
@@ -249,7 +251,8 @@ class Engine {
   void build_planset(PlanSet& ps, int first, int count, const uint32_t* d_okbits);
   void ensure_sorted_plan();
   void ensure_useful_mask();
-  bool ensure_live_blocks(int cpb, int cap);
+  bool ensure_live_blocks(int cpb, int cap, bool inside_too);
+  bool loop_prepass_ok(bool sched1) const;
   int live_span_for(int cpb) const;
   bool lists_wanted() const;
   LdsLayout lds_layout(const AutomatonLayout& lay, int Lmax, int nword_max, bool scan) const;
@@ -416,6 +419,8 @@ class Engine {
   int opt_live_blocks_ = 1;        // option "live_blocks": a workgroup of the train sweeps takes cpb LIVE cells of its diagonal;
                                    // 2: on every diagonal, also where the lists save no workgroups
   int opt_live_span_ = 0;          // option "live_span": the cells a block may span (0: kLiveSpanDefault, at least cpb)
+  bool opt_loop_prepass_ = true;   // option "loop_prepass": a row pre-pass fills the inside L plane of the table-driven train sweep, whose
+                                   // workgroups then skip the cells that are useful in L alone; 0 = the sweep computes L itself
   int opt_useful_lds_kb_ = 150;    // option "useful_mask_lds_kb": k_useful_mask's LDS budget; a larger sequence gets the all-ones mask
   bool opt_sorted_plan_ = false;   // option "sorted_plan": sort the role lists at load_batch whatever the pipeline
   // scaled-linear pipeline
@@ -620,6 +625,7 @@ void Engine::set_option(const std::string& key, double v) {
     if (v < 0 || v > 2) throw ArgError("live_blocks: 0, 1 or 2");
     opt_live_blocks_ = (int)v;
   }
+  else if (key == "loop_prepass") opt_loop_prepass_ = v != 0;
   else if (key == "live_span") {   // (0: the default; a model with more cells per block than the value takes its cells per block)
     if (v < 0 || v > lin_live_span_max()) throw ArgError("live_span: 0 (default) or cells per block .. " + std::to_string(lin_live_span_max()));
     opt_live_span_ = (int)v;
@@ -804,29 +810,39 @@ void Engine::ensure_useful_mask() {
 
 // The live-block lists of the resident plan for blocks of `cpb` cells that span at most `cap`, from its mask; the largest block
 // count per diagonal is read back once (W + 1 ints: the grids of the train sweeps).  False: no lists for this plan / geometry.
-bool Engine::ensure_live_blocks(int cpb, int cap) {
+// inside_too: also the second set, for the inside sweep behind the loop pre-pass (without it one set, as before the pre-pass).
+bool Engine::ensure_live_blocks(int cpb, int cap, bool inside_too) {
   if (plan_.count <= 0 || plan_.n_blocks <= 0 || cpb < kLiveCpbMin || cap < cpb || cap > kLiveSpanMax) return false;
   ensure_useful_mask();
-  if (plan_.blk_cpb == cpb && plan_.blk_cap == cap && plan_.blk_all == (opt_live_blocks_ >= 2)) return true;
-  plan_.blocks.alloc(sizeof(LiveBlock) * (size_t)plan_.n_blocks);
-  plan_.blk_max.alloc(sizeof(int32_t) * 3 * (size_t)plan_.ka.wmax1);
+  if (plan_.blk_cpb == cpb && plan_.blk_cap == cap && plan_.blk_all == (opt_live_blocks_ >= 2) && (plan_.blk_two || !inside_too)) return true;
+  plan_.blocks.alloc(sizeof(LiveBlock) * (inside_too ? 2 : 1) * (size_t)plan_.n_blocks);   // (one set or both: live_blocks.h)
+  plan_.blk_max.alloc(sizeof(int32_t) * 6 * (size_t)plan_.ka.wmax1);
   PlanKernelArgs a = plan_.ka;
   a.p.useful = plan_.useful.as<uint8_t>();
   a.p.blocks = plan_.blocks.as<LiveBlock>();
+  a.p.blocks_in = inside_too ? a.p.blocks + (size_t)plan_.n_blocks : nullptr;
   a.blk_max = plan_.blk_max.as<int32_t>();
   a.live_cpb = cpb; a.live_cap = cap;
   HIP_OK(launch_live_blocks(a, (size_t)plan_.n_blocks, st_));
-  plan_.h_blk_max.assign(3 * (size_t)a.wmax1, 0);
-  HIP_OK(hipMemcpyAsync(plan_.h_blk_max.data(), a.blk_max, sizeof(int32_t) * 3 * (size_t)a.wmax1, hipMemcpyDeviceToHost, st_));
+  plan_.h_blk_max.assign(6 * (size_t)a.wmax1, 0);
+  HIP_OK(hipMemcpyAsync(plan_.h_blk_max.data(), a.blk_max, sizeof(int32_t) * 6 * (size_t)a.wmax1, hipMemcpyDeviceToHost, st_));
   HIP_OK(hipStreamSynchronize(st_));
   // the grid of every diagonal: its largest block count, or -1 where the lists leave too many of the workgroups (kLiveKeepPct)
+  // (each direction its own: the inside sweep behind the loop pre-pass takes the second set)
   plan_.h_blk_grid.assign((size_t)a.wmax1, 0);
+  plan_.h_blk_grid_in.assign((size_t)a.wmax1, 0);
   for (int d = 0; d < a.wmax1; ++d) {
+    const int32_t* mi = plan_.h_blk_max.data() + 3 * (size_t)a.wmax1;
     const long long nb = plan_.h_blk_max[a.wmax1 + d], nw = plan_.h_blk_max[2 * a.wmax1 + d];
+    const long long nbi = mi[a.wmax1 + d], nwi = mi[2 * a.wmax1 + d];
     plan_.h_blk_grid[d] = (opt_live_blocks_ >= 2 || nb * 100 <= nw * kLiveKeepPct) ? plan_.h_blk_max[d] : -1;
-    if (getenv("ELEMDP_PLAN_DEBUG")) fprintf(stderr, "live blocks d %d: most %d, blocks %lld, working without lists %lld%s\n", d, plan_.h_blk_max[d], nb, nw, plan_.h_blk_grid[d] < 0 ? " (consecutive)" : "");
+    plan_.h_blk_grid_in[d] = (opt_live_blocks_ >= 2 || nbi * 100 <= nwi * kLiveKeepPct) ? mi[d] : -1;
+    if (getenv("ELEMDP_PLAN_DEBUG"))
+      fprintf(stderr, "live blocks d %d: most %d, blocks %lld, working without lists %lld%s; inside behind the loop pre-pass: most %d, blocks %lld, working without lists %lld%s\n",
+              d, plan_.h_blk_max[d], nb, nw, plan_.h_blk_grid[d] < 0 ? " (consecutive)" : "", mi[d], nbi, nwi, plan_.h_blk_grid_in[d] < 0 ? " (consecutive)" : "");
   }
   plan_.blk_all = opt_live_blocks_ >= 2;
+  plan_.blk_two = inside_too;
   plan_.blk_cpb = cpb; plan_.blk_cap = cap;
   return true;
 }
@@ -1562,13 +1578,18 @@ void Engine::run_lin_batch() {
   int gsz = prepare_lin(a, sched1, false, n_ev);
   if (opt_useful_mask_) ensure_useful_mask();
   a.p.useful = opt_useful_mask_ ? plan_.useful.as<uint8_t>() : nullptr;   // (the train sweeps only: the scan family sees null)
+  // the loop pre-pass goes with the mask (the launcher drops it where the table-driven form does not run)
+  a.loop_pre = (opt_loop_prepass_ && opt_useful_mask_ && loop_prepass_ok(sched1)) ? 1 : 0;
+  a.in_d0 = first_inside_diagonal(min_span(), m_min());
   // ... and with it the live-block lists (not in the deterministic mode, whose sums follow the grouping of consecutive cells)
   if (lists_wanted()) {
     const int cpb = lin_train_cpb(a), cap = live_span_for(cpb);
-    if (cpb > 0 && ensure_live_blocks(cpb, cap)) {
+    if (cpb > 0 && ensure_live_blocks(cpb, cap, a.loop_pre != 0)) {
       a.p.blocks = plan_.blocks.as<LiveBlock>();
+      a.p.blocks_in = plan_.blk_two ? a.p.blocks + (size_t)plan_.n_blocks : nullptr;
       a.live_span = cap;
       a.blk_grid = plan_.h_blk_grid.data();
+      a.blk_grid_in = plan_.h_blk_grid_in.data();
     }
   }
   const int32_t* h_ord = h_order_.data();
@@ -1862,6 +1883,11 @@ void Engine::batch_pairs(int idx, uint8_t* kept, double* lnbpp, int cap) {
 // Does a train evaluation take the plan's lists (where the model's kernels take any)?  Not without the mask, and not in the
 // deterministic mode, whose sums follow the grouping of consecutive cells.
 bool Engine::lists_wanted() const { return opt_useful_mask_ && opt_live_blocks_ && !opt_det_; }
+// can the loop pre-pass serve the automaton a train evaluation sweeps (the one with the shadow state under schedule 1)?
+bool Engine::loop_prepass_ok(bool sched1) const {
+  const bool shadow = sched1 && lays_.shadow >= 0;
+  return lin_loop_prepass_ok(shadow ? lays_ : lay_, shadow ? intss_.data() : ints_.data(), min_span());
+}
 
 // the span a block of `cpb` live cells may cover: option live_span, or the default
 int Engine::live_span_for(int cpb) const {
@@ -1873,7 +1899,8 @@ int Engine::live_span_for(int cpb) const {
 // The lists of sequence idx for the cells per block and the span of the current options (built here if no evaluation has):
 // counts[d] blocks of diagonal d at records + d * stride (16-byte LiveBlock records); cpb_cap = {cells per block, span};
 // taken[d] (may be null) = 1 where a train evaluation of the current options sweeps diagonal d from its list.
-void Engine::live_blocks(int idx, int32_t* counts, void* records, int stride, int32_t* cpb_cap, int32_t* taken) {
+// inside: the second set (the lists of the inside sweep behind the loop pre-pass, from the bytes without UB_L) and its own choice.
+void Engine::live_blocks(int idx, int32_t* counts, void* records, int stride, int32_t* cpb_cap, int32_t* taken, bool inside) {
   require_device();
   DeviceGuard dg(device_);
   if (streaming_) throw StateError("live_blocks needs a resident batch (the handle streams this one in chunks)");
@@ -1886,10 +1913,10 @@ void Engine::live_blocks(int idx, int32_t* counts, void* records, int stride, in
   if (cpb <= 0) throw StateError("live_blocks: the train sweeps of this model do not take lists");
   const int cap = live_span_for(cpb);
   if (stride < live_blocks_slots(p.L)) throw ArgError("live_blocks: stride too small");
-  if (!ensure_live_blocks(cpb, cap)) throw StateError("live_blocks: no lists for this batch");
+  if (!ensure_live_blocks(cpb, cap, inside)) throw StateError("live_blocks: no lists for this batch");
   HIP_OK(hipStreamSynchronize(st_));
   std::vector<LiveBlock> h((size_t)live_blocks_records(p.L, p.W));
-  HIP_OK(hipMemcpy(h.data(), plan_.blocks.as<LiveBlock>() + p.blk_base, sizeof(LiveBlock) * h.size(), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(h.data(), plan_.blocks.as<LiveBlock>() + (inside ? (size_t)plan_.n_blocks : 0) + p.blk_base, sizeof(LiveBlock) * h.size(), hipMemcpyDeviceToHost));
   LiveBlock* out = static_cast<LiveBlock*>(records);
   for (int d = 0; d <= p.W; ++d) {
     counts[d] = h[d].count;
@@ -1897,8 +1924,11 @@ void Engine::live_blocks(int idx, int32_t* counts, void* records, int stride, in
   }
   cpb_cap[0] = cpb; cpb_cap[1] = cap;
   // which diagonals a train evaluation of the current options sweeps from these lists
-  const bool want = lists_wanted();
-  if (taken) for (int d = 0; d <= p.W; ++d) taken[d] = (want && plan_.h_blk_grid[d] >= 0) ? 1 : 0;
+  // (the inside set: only behind the pre-pass, and not below the first diagonal that has an entry outside the L plane)
+  const bool want = lists_wanted() && (!inside || (opt_loop_prepass_ && loop_prepass_ok(sched1)));
+  const std::vector<int32_t>& grid = inside ? plan_.h_blk_grid_in : plan_.h_blk_grid;
+  const int d0 = inside ? first_inside_diagonal(min_span(), m_min()) : 0;
+  if (taken) for (int d = 0; d <= p.W; ++d) taken[d] = (want && d >= d0 && grid[d] >= 0) ? 1 : 0;
 }
 
 void Engine::useful_mask(int idx, uint8_t* mask, int cap) {
@@ -2676,6 +2706,21 @@ int elemdp_live_blocks(elemdp_handle* h, int32_t seq_index, int32_t* counts, voi
   if (!h || !counts || !records || !cpb_cap) throw elemdp::ArgError("elemdp_live_blocks: null argument");
   h->e->live_blocks(seq_index, counts, records, stride, cpb_cap, taken);
   ELEMDP_CATCH
+}
+int elemdp_live_blocks_inside(elemdp_handle* h, int32_t seq_index, int32_t* counts, void* records, int32_t stride, int32_t* cpb_cap,
+                              int32_t* taken) {
+  ELEMDP_TRY
+  if (!h || !counts || !records || !cpb_cap) throw elemdp::ArgError("elemdp_live_blocks_inside: null argument");
+  h->e->live_blocks(seq_index, counts, records, stride, cpb_cap, taken, true);
+  ELEMDP_CATCH
+}
+int elemdp_live_blocks_host_bits(const uint8_t* mask, int32_t L, int32_t W, int32_t cpb, int32_t cap, int32_t bits, int32_t* counts,
+                                 void* records, int32_t stride) {
+  if (!mask || !counts || !records || L < 0 || W < 0 || W > L || cpb < 1 || cap < cpb || cap > elemdp::kLiveSpanMax ||
+      stride < (L + cpb) / cpb || bits < 1 || bits > 255)
+    return ELEMDP_EINVAL;
+  elemdp::live_blocks_host(mask, L, W, cpb, cap, counts, static_cast<elemdp::LiveBlock*>(records), stride, bits);
+  return ELEMDP_OK;
 }
 int elemdp_live_blocks_host(const uint8_t* mask, int32_t L, int32_t W, int32_t cpb, int32_t cap, int32_t* counts, void* records,
                             int32_t stride) {

@@ -31,6 +31,8 @@ struct PlanArrays {
   // live-block lists of the train sweeps (live_blocks.h: LiveBlock, W + 1 headers and the records of every diagonal from
   // SeqPlan::blk_base on); null: a workgroup takes cpb consecutive cells
   LiveBlock* blocks = nullptr;
+  // the second set of lists, from the mask bytes without UB_L: the inside sweep behind the loop pre-pass (live_blocks.h)
+  LiveBlock* blocks_in = nullptr;
 };
 
 // static per-batch arrays
@@ -58,7 +60,7 @@ struct PlanKernelArgs {
   int32_t count_fast = 0;   // loop_tables_finite and no imposed structure: the count pass takes popcounts (count_interior_by_end)
   // live-block lists (launch_live_blocks): cells per block and the span a block may cover; blk_max: three rows of wmax1 ints over
   // the sequences of the set (cleared by the launcher) -- the most blocks of diagonal d, the sum of its blocks, and the sum of
-  // the workgroups of cpb consecutive cells that hold a live cell
+  // the workgroups of cpb consecutive cells that hold a live cell --, then the same three rows for the inside set (p.blocks_in)
   int32_t live_cpb = 0, live_cap = 0;
   int32_t* blk_max = nullptr;
 };
@@ -275,6 +277,11 @@ struct LinArgs {
   // (negative: this diagonal keeps consecutive cells)
   int32_t live_span;
   const int32_t* blk_grid;
+  // loop pre-pass (option loop_prepass; k4_in_loops): 1 = the inside sweep of the table-driven train form takes its L plane from
+  // the pre-pass (the engine sets it where the mask is on and the automaton's loop states all have an L column); in_d0 = the first
+  // diagonal with an entry outside the L plane (first_inside_diagonal); blk_grid_in = blk_grid of the inside set (p.blocks_in)
+  int32_t loop_pre = 0, in_d0 = 0;
+  const int32_t* blk_grid_in = nullptr;
 };
 struct LinWeightArgs {
   const LoopItem* items_inner; const LoopItem* items_left; const LoopItem* items_right;   // (may be null)
@@ -307,11 +314,16 @@ hipError_t launch_plan_items(const PlanKernelArgs& a, hipStream_t st);
 hipError_t launch_useful_mask(const PlanKernelArgs& a, size_t n_cells, size_t lds_cap, hipStream_t st);   // needs dmin (launch_plan_cells)
 void useful_mask_host(const uint8_t* kept, const uint8_t* unp, int L, int W, int C, int m_min, bool no_ene, uint8_t* out);
 // the live-block lists of every sequence of the set from its mask (a.p.useful -> a.p.blocks of n_records records, a.blk_max),
-// cells per block a.live_cpb
+// cells per block a.live_cpb;
+// with a.p.blocks_in non-null also the inside set; a.blk_max holds 6 rows of wmax1 ints either way
 hipError_t launch_live_blocks(const PlanKernelArgs& a, size_t n_records, hipStream_t st);
 // the same lists on the host from a mask [d][i] of (W+1) * (L+1) bytes: counts[d] blocks of diagonal d at records + d * stride
 // (stride >= ceil((L + 1) / cpb) records of 16 bytes)
-void live_blocks_host(const uint8_t* mask, int L, int W, int cpb, int cap, int32_t* counts, LiveBlock* records, int stride);
+// (bits: the planes that make a cell live, live_blocks.h)
+void live_blocks_host(const uint8_t* mask, int L, int W, int cpb, int cap, int32_t* counts, LiveBlock* records, int stride, int bits = 0xff);
+// can the loop pre-pass serve the automaton of this host blob?  (the L rows fit the pre-pass's staging, and a loop state without an
+// L column has the L value 0 in the sweep's own rule too; min_span: the smallest span of a kept pair)
+bool lin_loop_prepass_ok(const AutomatonLayout& lay, const int32_t* ints, int min_span);
 // cells per block of the table-driven train sweeps of these arguments, 0 where they run another form (no lists then); the
 // largest span a block's live cells may cover in this build
 int lin_train_cpb(const LinArgs& full);

@@ -927,6 +927,18 @@ __global__ __launch_bounds__(kThreads) void k_live_blocks(PlanKernelArgs a) {
     atomicAdd(&a.blk_max[a.wmax1 + d], nb);
     atomicAdd(&a.blk_max[2 * a.wmax1 + d], working_blocks_row(a.p.useful + p.cell_base + (size_t)d * (p.L + 1), ncell, a.live_cpb));
   }
+  if (!a.p.blocks_in) return;
+  // the inside set: the same rule over the bytes without their L bit
+  LiveBlock* base_in = a.p.blocks_in + p.blk_base;
+  const int nbi = ncell > 0 ? live_blocks_row(a.p.useful + p.cell_base + (size_t)d * (p.L + 1), ncell, a.live_cpb, a.live_cap,
+                                              base_in + live_blocks_at(p.L, p.W, d), kLiveInsideBits) : 0;
+  base_in[d] = LiveBlock{0ull, 0, 0, 0, (int16_t)nbi};
+  if (nbi > 0) {
+    int32_t* mx = a.blk_max + 3 * a.wmax1;
+    atomicMax(&mx[d], nbi);
+    atomicAdd(&mx[a.wmax1 + d], nbi);
+    atomicAdd(&mx[2 * a.wmax1 + d], working_blocks_row(a.p.useful + p.cell_base + (size_t)d * (p.L + 1), ncell, a.live_cpb, kLiveInsideBits));
+  }
 }
 
 }  // namespace
@@ -1042,19 +1054,21 @@ hipError_t launch_useful_mask(const PlanKernelArgs& a, size_t n_cells, size_t ld
 hipError_t launch_live_blocks(const PlanKernelArgs& a, size_t n_records, hipStream_t st) {
   if (a.count <= 0 || !a.p.useful || !a.p.blocks || !a.blk_max) return hipSuccess;
   if (a.live_cpb < kLiveCpbMin || a.live_cap < a.live_cpb || a.live_cap > kLiveSpanMax) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(a.blk_max, 0, sizeof(int32_t) * 3 * a.wmax1, st);
+  hipError_t e = hipMemsetAsync(a.blk_max, 0, sizeof(int32_t) * 6 * a.wmax1, st);   // (both sets' rows, built or not)
   if (e != hipSuccess) return e;
   // (the slots behind the last block of a diagonal read as "no block": the band kernels load their slot without a count)
   e = hipMemsetAsync(a.p.blocks, 0, n_records * sizeof(LiveBlock), st);
+  if (e != hipSuccess) return e;
+  if (a.p.blocks_in) e = hipMemsetAsync(a.p.blocks_in, 0, n_records * sizeof(LiveBlock), st);
   if (e != hipSuccess) return e;
   const long long lanes = (long long)a.count * a.wmax1;
   hipLaunchKernelGGL(k_live_blocks, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a);
   return hipGetLastError();
 }
-void live_blocks_host(const uint8_t* mask, int L, int W, int cpb, int cap, int32_t* counts, LiveBlock* records, int stride) {
+void live_blocks_host(const uint8_t* mask, int L, int W, int cpb, int cap, int32_t* counts, LiveBlock* records, int stride, int bits) {
   for (int d = 0; d <= W; ++d) {
     const int ncell = L - d + 1;
-    counts[d] = ncell > 0 ? live_blocks_row(mask + (size_t)d * (L + 1), ncell, cpb, cap, records + (size_t)d * stride) : 0;
+    counts[d] = ncell > 0 ? live_blocks_row(mask + (size_t)d * (L + 1), ncell, cpb, cap, records + (size_t)d * stride, bits) : 0;
   }
 }
 // the same sweep on the host from a kept-pair matrix kept[(L+1)][(W+1)] (no GPU needed); unp: L flags or null (all unpaired

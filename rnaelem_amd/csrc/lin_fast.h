@@ -64,7 +64,10 @@ ELEMDP_HD int cell_in_flags(const ModelView& m, const SeqView& q, int d, int i) 
 // P,E,M,B,1,2,L of target (i, d, state of program P) from the heavy sums *pHB (rule 2) and *pHE (rule 6c, both in LDS: read
 // where they are used); stores them
 // CON: the start constraint of the scan's second pass (FS = the ScanFlag words; CF_YL / CF_YR set in fl)
-template <int kFR, int kFP, int kFL, bool CON = false>
+// LPRE: the L plane of the sweep is there already (the row pre-pass k4_in_loops of the train form, loop_inside_row below): no
+// operand of the chain is loaded and no L is stored; the lane of an e_ok cell reads the stored L(i, d, own column) for rule 6b
+// with the other operands -- the chain value where the cell's UB_L bit is on, an exact 0 where it is off: the vL of this function
+template <int kFR, int kFP, int kFL, bool CON = false, bool LPRE = false>
 ELEMDP_HD void fast_inside_unary(const AutomatonLayout& A, const int32_t* P, const double* lin, const TableView& T,
                                                   const double* cr, int fl, int d, int i, const double* pHB, const double* pHE, int nrep,
                                                   int rstride, const int32_t* FS = nullptr) {
@@ -85,7 +88,7 @@ ELEMDP_HD void fast_inside_unary(const AutomatonLayout& A, const int32_t* P, con
 #pragma unroll
   for (int u = 0; u < kFR; ++u) {
     eR[u] = P[4 + u];
-    tL[u] = T.ldc(ST_L, d1, i, fcol(eR[u], 0), u < nR && doL);
+    tL[u] = LPRE ? 0. : T.ldc(ST_L, d1, i, fcol(eR[u], 0), u < nR && doL);
     t2[u] = T.ldc(ST_2, d1, i, fcol(eR[u], 1), u < nR && do2);
   }
 #pragma unroll
@@ -99,6 +102,7 @@ ELEMDP_HD void fast_inside_unary(const AutomatonLayout& A, const int32_t* P, con
     eL[u] = P[12 + u];
     tM[u] = T.ldc(ST_M, d1, i1, fcol(eL[u], 0), u < nL && doM);
   }
+  const double preL = LPRE ? T.ldc(ST_L, d, i, fcol(w2, 2), eok) : 0.;
   const double ews_i = cr[0], ews_j = cr[1];
   const double xst = cr[2 + kl], xml = cr[4 + kl], xcl = cr[6 + kl], xhp = cr[8 + kl];   // (0 where pok / eok is not set)
   const double pj = wr_pos ? ews_j : 1.;
@@ -109,7 +113,7 @@ ELEMDP_HD void fast_inside_unary(const AutomatonLayout& A, const int32_t* P, con
       const int id = (eR[u] >> 16) & 0x7fff;
       double w = lin[A.lin_wr + 5 * id + bj] * pj;
       if (CON && yr && !(FS[id] & SF_SR)) w = 0.;   // allow_right
-      sL = fma(tL[u], w, sL);
+      if (!LPRE) sL = fma(tL[u], w, sL);
       s2 = fma(t2[u], w, s2);
     }
 #pragma unroll
@@ -133,7 +137,7 @@ ELEMDP_HD void fast_inside_unary(const AutomatonLayout& A, const int32_t* P, con
     }
   double HB = *pHB, HE = *pHE;
   for (int r = 1; r < nrep; ++r) { HB += pHB[r * rstride]; HE += pHE[r * rstride]; }   // (deterministic mode: one copy per wave)
-  const double vL = (isloop && uL) ? (d == 0 ? ((w0 & 2) ? 1. : 0.) : sL) : 0.;   // motif_trainer.hpp:89-95
+  const double vL = LPRE ? preL : (isloop && uL) ? (d == 0 ? ((w0 & 2) ? 1. : 0.) : sL) : 0.;   // motif_trainer.hpp:89-95
   const double vP = pok ? sP : 0.;                                          // rules 1a, 1b
   const double vB = (lok && uB) ? HB : 0.;                                  // rule 2
   const double v2 = (lok && u2) ? fma(vP, xml, s2) : 0.;                    // rules 3a, 3b
@@ -142,7 +146,7 @@ ELEMDP_HD void fast_inside_unary(const AutomatonLayout& A, const int32_t* P, con
   const double vE = eok ? fma(vM, xcl, fma(vL, xhp, HE)) : 0.;              // rules 6a, 6b, 6c
   // (the B plane is not stored: nothing reads it -- the outside pass of the train kernels decides liveness from the pair entries)
   const int cLo = fcol(w2, 2), cPo = fcol(w1, 0), c2o = fcol(w2, 1), c1o = fcol(w2, 0), cMo = fcol(w1, 2), cEo = fcol(w1, 1);
-  if (cLo >= 0) T.band[T.cidx(ST_L, d, i, cLo)] = vL;
+  if (!LPRE && cLo >= 0) T.band[T.cidx(ST_L, d, i, cLo)] = vL;
   if (pok && cPo >= 0) {
     T.band[T.cidx(ST_P, d, i, cPo)] = vP;
     // X = P * exp(lambda e_ml): what rule 3b hands to the stems of the factorised rule 2 (pair phases of k4_in / k4_out).  It takes
@@ -153,6 +157,30 @@ ELEMDP_HD void fast_inside_unary(const AutomatonLayout& A, const int32_t* P, con
   if (lok && c1o >= 0) T.band[T.cidx(ST_1, d, i, c1o)] = v1;
   if (mok && cMo >= 0) T.band[T.cidx(ST_M, d, i, cMo)] = vM;
   if (eok && cEo >= 0) T.band[T.cidx(ST_E, d, i, cEo)] = vE;
+}
+
+// The L entry of one (cell, state) from the L row of cell (i, d - 1) alone -- the L part of fast_inside_unary, operation for
+// operation (the transitions u < nR in program order, fma(tL, w, sL), w = lin[lin_wr + 5 id + bj] * pj), so that the row pre-pass
+// stores the doubles the sweep would: P = the state's program, prev = the STORED L row of (i, d - 1) (indexed by column), ub = the
+// cell's mask byte, bj / ews_j = base and position weight of j - 1, wr = the weight table WR (lin + lin_wr).
+template <int kFR>
+ELEMDP_HD double loop_inside_entry(const int32_t* P, const double* wr, const double* prev, int ub, int d, int bj, double ews_j) {
+  const int w0 = P[0];
+  const bool isloop = w0 & 1, wr_pos = w0 & 8, uL = ub & UB_L;
+  const int nR = (w0 >> 8) & 15;
+  if (!(isloop && uL)) return 0.;
+  if (d == 0) return (w0 & 2) ? 1. : 0.;
+  const double pj = wr_pos ? ews_j : 1.;
+  double sL = 0.;
+#pragma unroll
+  for (int u = 0; u < kFR; ++u)
+    if (u < nR) {
+      const int e = P[4 + u], c = fcol(e, 0), id = (e >> 16) & 0x7fff;
+      const double tL = c >= 0 ? prev[c] : 0.;
+      const double w = wr[5 * id + bj] * pj;
+      sL = fma(tL, w, sL);
+    }
+  return sL;
 }
 
 // ---- outside --------------------------------------------------------------------------------------------------------------

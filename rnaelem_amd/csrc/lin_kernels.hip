@@ -614,9 +614,10 @@ __device__ __forceinline__ void outer_stage(const LViews& v, const OuterRecs& r,
 // Train sweeps under the usefulness mask (plan_rules.h; SeqView::useful): true when no cell of the workgroup has a useful entry
 // in any plane (uniform over the workgroup).  Such a workgroup computes nothing: fill_dead_rows stores the zeros that the
 // readers of its cells' entries expect (an entry that is parsable but useless still has readers) and the kernel returns.
-__device__ __forceinline__ bool block_is_dead(const SeqView& q, int d, int i0, int nc, int tid) {
+// bits: the planes that count (the inside sweep behind the loop pre-pass ignores UB_L)
+__device__ __forceinline__ bool block_is_dead(const SeqView& q, int d, int i0, int nc, int tid, int bits = UB_ALL) {
   if (!q.useful) return false;
-  const int b = tid < nc ? (int)q.useful[d * (q.L + 1) + i0 + tid] : 0;
+  const int b = tid < nc ? ((int)q.useful[d * (q.L + 1) + i0 + tid] & bits) : 0;
   return !__syncthreads_or(b);
 }
 // zeros into the rows of planes e0, e1, e2, e3 (negative: none) and the pair entries of cells i0 .. i0 + nc - 1 of diagonal d
@@ -677,7 +678,10 @@ __device__ __forceinline__ LiveCells live_cells(const SeqView& q, int d, int bx,
 // FAST: table-driven phases (lin_fast.h; train schedule, the fast blob staged); FP: longest pair list of a state (2 or 3)
 // LISTS: the train form whose workgroups take the live cells of a block of the plan's lists (live_blocks.h) -- a form of its own, so
 // that the one of consecutive cells stays the code it was
-template <bool BIG, bool CON, bool FAST = false, int FP = kFastP, bool W8 = false, bool LISTS = false>
+// LPRE: the train form behind the row pre-pass k4_in_loops (option loop_prepass), which has stored the L plane of the whole table:
+// no L is computed or stored here, the zeros of dead cells leave the L rows alone, and a cell is live by its bits other than UB_L
+// (LISTS: the plan's second set of lists, which the launcher hands over as SeqView::blocks)
+template <bool BIG, bool CON, bool FAST = false, int FP = kFastP, bool W8 = false, bool LISTS = false, bool LPRE = false>
 __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4_in(LinArgs a) {
   extern __shared__ double lds[];
   // (the automaton layout is read from the kernel arguments: constant offsets, scalar registers)
@@ -696,13 +700,15 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
   constexpr bool MASK = FAST && !CON;   // the train form honours the usefulness mask (the scan passes get none)
   const int ncell = v.q.L - d + 1;
   static_assert(!LISTS || (FAST && !CON), "lists: the table-driven train form only");
+  static_assert(!LPRE || (FAST && !CON), "loop pre-pass: the table-driven train form only");
+  constexpr int kDeadL = LPRE ? -1 : (int)ST_L;   // (the L rows of dead cells: the pre-pass has stored them)
   constexpr bool lists = LISTS;
   int i0 = bx * cpb, nc = 0, span = 0;
   unsigned long long live = 0ull;
   if (lists) {
     const LiveCells lc = live_cells(v.q, d, (int)bx, ncell);
     // (the zeros of the dead cells the block owns: an entry that is parsable but useless still has readers)
-    if (lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.in, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, ST_L, ST_2, ST_1, ST_M);
+    if (lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.in, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, kDeadL, ST_2, ST_1, ST_M);
     if (!lc.sweep) return;
     i0 = lc.i0; nc = lc.nc; span = lc.span; live = lc.live;
   } else {
@@ -716,7 +722,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
     const int ys = a.ys[v.n];
     if (ys < i0 || ys - d + 1 > i0 + nc - 1) return;
   }
-  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid)) { fill_dead_rows(v.in, d, i0, nc, tid, ST_L, ST_2, ST_1, ST_M); return; }
+  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid, LPRE ? (UB_ALL & ~UB_L) : UB_ALL)) { fill_dead_rows(v.in, d, i0, nc, tid, kDeadL, ST_2, ST_1, ST_M); return; }
   const int HD = FAST ? A.n_lane : S;   // stride of the heavy sums per cell: the live states (table-driven: their index among them), or all
   const int CS = cpb * HD;
   constexpr int NW = 1;                      // (one copy of the heavy sums in either mode: see the deterministic mode above)
@@ -972,7 +978,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
     const int s = FAST ? G[A.f_live_in + tid - c * NL] : tid - c * NL;
     const int i = ci(c);
     if (FAST) {
-      fast_inside_unary<kFastR, FP, kFastL, CON>(A, G + A.fp_in + s * kFastW, v.m.lin, v.in, crec + c * kCellInD, crfl[c], d, i, hb + c * HD + (tid - c * NL),
+      fast_inside_unary<kFastR, FP, kFastL, CON, LPRE>(A, G + A.fp_in + s * kFastW, v.m.lin, v.in, crec + c * kCellInD, crfl[c], d, i, hb + c * HD + (tid - c * NL),
                                                  he + c * HD + (tid - c * NL), NW, 2 * CS, G + A.fs_in);
     } else {
       const Constraint con{CON ? a.ys[v.n] : -1, -1, 0};
@@ -981,6 +987,64 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
   }
   pc.mark<4>();
   pc.finish();
+}
+
+// ---- row pre-pass of the inside L plane (option loop_prepass; the table-driven train form under the mask)
+// L(i, d, .) depends on L(i, d - 1, .) alone (fast_inside_unary: no other plane, no heavy sum), so the plane is a chain along d
+// per row i and needs no diagonal sweep.  One wave per 64 consecutive rows of a sequence, one lane per row: the lane keeps its
+// row of the previous step in LDS ([lane][column] = the memory image of the wave's rows of a diagonal, which are contiguous in
+// [d][i]) and the wave stores every diagonal's rows as whole lines.  Every entry k4_in stores is stored: the chain value where the
+// cell's UB_L bit is on, an exact 0 where it is off (loop_inside_entry: the operations of fast_inside_unary in their order).
+constexpr int kLoopLanes = 64;     // rows per workgroup = one wave
+constexpr int kLoopColsMax = 16;   // most columns of an L row the pre-pass takes (lin_loop_prepass_ok)
+constexpr int kLoopProgW = 8;      // program words staged per column: P[0 .. 4 + kFastR)
+static_assert(4 + kFastR <= kLoopProgW, "the staged program holds the right transitions");
+static size_t loop_prepass_lds(const AutomatonLayout& A) {
+  return sizeof(double) * (2 * (size_t)kLoopLanes * A.tab_rs[ST_L] + 5 * (size_t)A.n_wr) + sizeof(int32_t) * kLoopColsMax * kLoopProgW;
+}
+__global__ __launch_bounds__(kLoopLanes) void k4_in_loops(LinArgs a) {
+  extern __shared__ double lds[];
+  LViews v(a.lay);
+  make_lviews(a, blockIdx.y, v);
+  const AutomatonLayout& A = a.lay;
+  const int tid = threadIdx.x, L = v.q.L, W = v.q.W;
+  const int i0 = blockIdx.x * kLoopLanes;
+  if (i0 > L) return;
+  const int rs = v.in.rs[ST_L];
+  double* cur = lds;
+  double* prev = lds + kLoopLanes * rs;
+  double* wr = lds + 2 * kLoopLanes * rs;
+  int32_t* prog = reinterpret_cast<int32_t*>(wr + 5 * A.n_wr);
+  // the program of the state that owns column c (a column without a state: zeros, which read as "no loop state" -> 0)
+  for (int t = tid; t < kLoopColsMax * kLoopProgW; t += kLoopLanes) prog[t] = 0;
+  for (int t = tid; t < 5 * A.n_wr; t += kLoopLanes) wr[t] = a.lin[A.lin_wr + t];
+  __syncthreads();
+  for (int k = tid; k < A.n_lane; k += kLoopLanes) {
+    const int32_t* P = a.ints + A.fp_in + a.ints[A.f_live_in + k] * kFastW;
+    const int c = fcol(P[2], 2);
+    if (c >= 0 && c < kLoopColsMax)
+      for (int w = 0; w < kLoopProgW; ++w) prog[c * kLoopProgW + w] = P[w];
+  }
+  __syncthreads();
+  const int i = i0 + tid;
+  const int dmax = (W < L - i0) ? W : L - i0;   // (uniform: the first row of the wave is its longest)
+  for (int d = 0; d <= dmax; ++d) {
+    if (i + d <= L) {
+      const int j = i + d;
+      const int bj = d > 0 ? (int)v.q.seq[j - 1] : 0;
+      const double ews_j = d > 0 ? v.q.ews[j - 1] : 1.;
+      const int ub = v.q.ubits(i, d);
+      for (int c = 0; c < rs; ++c)
+        cur[tid * rs + c] = loop_inside_entry<kFastR>(prog + c * kLoopProgW, wr, prev + tid * rs, ub, d, bj, ews_j);
+    }
+    __syncthreads();
+    // the rows i0 .. min(i0 + 63, L - d) of diagonal d: one contiguous run of the table
+    const int nrows = (kLoopLanes < L - d - i0 + 1) ? kLoopLanes : L - d - i0 + 1;
+    double* dst = v.in.band + v.in.cidx(ST_L, d, i0, 0);
+    for (int t = tid; t < nrows * rs; t += kLoopLanes) dst[t] = cur[t];
+    // (one barrier per step: the next step writes the rows read two steps ago, and reads only the lane's own row of this one)
+    double* x = cur; cur = prev; prev = x;
+  }
 }
 
 // Exterior-chain kernels (one workgroup of 128 per sequence, L sequential steps): the per-sequence context of the whole
@@ -2292,6 +2356,23 @@ static K4Form k4_form(const LinArgs& a, size_t lds, int waves, bool fast, bool b
 }
 template <bool CON>
 static void launch_k4_in(const LinArgs& a, dim3 grid, size_t lds, bool fast, bool big, hipStream_t st) {
+  if (!CON && fast && a.loop_pre) {   // the train forms behind the loop pre-pass, with the plan's (inside) lists or without
+    const bool l = a.p.blocks != nullptr;
+    switch (k4_form(a, lds, 8, fast, big)) {
+      case K4_FP2_WAVES:
+        if (l) hipLaunchKernelGGL((k4_in<true, false, true, 2, true, true, true>), grid, dim3(kBT), lds, st, a);
+        else hipLaunchKernelGGL((k4_in<true, false, true, 2, true, false, true>), grid, dim3(kBT), lds, st, a);
+        return;
+      case K4_FP2:
+        if (l) hipLaunchKernelGGL((k4_in<true, false, true, 2, false, true, true>), grid, dim3(kBT), lds, st, a);
+        else hipLaunchKernelGGL((k4_in<true, false, true, 2, false, false, true>), grid, dim3(kBT), lds, st, a);
+        return;
+      default:
+        if (l) hipLaunchKernelGGL((k4_in<true, false, true, kFastP, false, true, true>), grid, dim3(kBT), lds, st, a);
+        else hipLaunchKernelGGL((k4_in<true, false, true, kFastP, false, false, true>), grid, dim3(kBT), lds, st, a);
+        return;
+    }
+  }
   if (!CON && fast && a.p.blocks) {   // the train forms that take the plan's lists
     switch (k4_form(a, lds, 8, fast, big)) {
       case K4_FP2_WAVES: hipLaunchKernelGGL((k4_in<true, false, true, 2, true, true>), grid, dim3(kBT), lds, st, a); return;
@@ -2352,6 +2433,33 @@ int lin_train_cpb(const LinArgs& full) {
   return geometry_fast(full) ? std::min(kBT / std::max(full.lay.n_lane, 1), ELEMDP_CPB_MAX) : 0;
 }
 int lin_live_span_max() { return kLiveSpanMax; }
+bool lin_loop_prepass_ok(const AutomatonLayout& A, const int32_t* ints, int min_span) {
+  const bool say = getenv("ELEMDP_PLAN_DEBUG") != nullptr;
+  if (!A.fp_ok || A.tab_rs[ST_L] < 1 || A.tab_rs[ST_L] > kLoopColsMax || loop_prepass_lds(A) > 64 * 1024) {
+    if (say) fprintf(stderr, "loop pre-pass: not for this automaton (fp_ok %d, L row of %d columns)\n", A.fp_ok, A.tab_rs[ST_L]);
+    return false;
+  }
+  auto col = [](int packed, int byte) { const int c = (packed >> (8 * byte)) & 0xff; return c == 0xff ? -1 : c; };   // (fcol: device code under hipcc)
+  unsigned seen = 0;
+  for (int k = 0; k < A.n_lane; ++k) {
+    const int32_t* P = ints + A.fp_in + ints[A.f_live_in + k] * kFastW;
+    const int c = col(P[2], 2);
+    if (c >= 0) {   // no two states share a column of the row
+      if (c >= A.tab_rs[ST_L] || ((seen >> c) & 1u)) { if (say) fprintf(stderr, "loop pre-pass: not for this automaton (column %d of lane %d)\n", c, k); return false; }
+      seen |= 1u << c;
+      continue;
+    }
+    // A loop state WITHOUT an L column (its L entries are in no complete parse): the sweep behind the pre-pass reads its vL as 0.
+    // That is what fast_inside_unary computes where the state has no E column (vL is then used nowhere), or where none of its
+    // operands has a column (sL = 0) and d = 0 is no E cell (a pair of span 2 is not kept) or gives 0 anyway.
+    if (!(P[0] & 1) || col(P[1], 1) < 0) continue;
+    const int nR = (P[0] >> 8) & 15;
+    bool zero = !(P[0] & 2) || min_span > 2;
+    for (int u = 0; u < nR && u < kFastR; ++u) zero = zero && col(P[4 + u], 0) < 0;
+    if (!zero) { if (say) fprintf(stderr, "loop pre-pass: not for this automaton (lane %d: a loop state with an E column, no L column and an L value)\n", k); return false; }
+  }
+  return true;
+}
 static GroupGeom group_geometry(const LinArgs& full, int G, int Lmax, int Wmax, bool scan) {
   GroupGeom g;
   LinArgs& a = g.a;
@@ -2373,6 +2481,9 @@ static GroupGeom group_geometry(const LinArgs& full, int G, int Lmax, int Wmax, 
   // train sweeps from the live-block lists of the plan: only the table-driven forms, which honour the mask, and not the
   // deterministic mode (its sums are single-writer in an order that follows the grouping of the cells)
   if (scan || !fast || a.det || !a.p.useful || !a.p.blocks || !a.blk_grid || a.live_span < a.cpb) { a.p.blocks = nullptr; a.blk_grid = nullptr; a.live_span = 0; }
+  // the loop pre-pass: where the table-driven train form runs with the mask (the deterministic mode included: L enters no heavy sum)
+  if (scan || !fast || !a.p.useful) a.loop_pre = 0;
+  if (a.loop_pre && a.p.blocks && (!a.p.blocks_in || !a.blk_grid_in)) a.loop_pre = 0;
   const int sp = a.live_span > a.cpb ? a.live_span : a.cpb;   // cells a workgroup's window spans
   g.win = sp + Wmax + 3;
   g.lds_in = block_lds(2 * a.cpb * g.hd + kRecIn, a.cpb, a.n_lin, g.win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0, sp).total;
@@ -2397,11 +2508,21 @@ static unsigned band_blocks(LinArgs& a, int ncell, bool train) {
 template <bool CON>
 static void inside_sweeps(GroupGeom& g, int G, int Lmax, int Wmax, bool bands, hipStream_t st) {
   LinArgs& a = g.a;
+  // behind the loop pre-pass (train, table-driven, mask): the L plane by rows first, then the diagonals from the first one that can
+  // hold an entry outside the L plane (below it nothing else is parsable: nothing to compute, nothing to store), each with the
+  // inside set of lists and its own choice per diagonal
+  const bool pre = !CON && bands && g.fast && a.loop_pre;
+  LinArgs ai = a;
+  if (!pre) ai.loop_pre = 0;
+  if (pre) {
+    if (a.p.blocks) { ai.p.blocks = a.p.blocks_in; ai.blk_grid = a.blk_grid_in; }
+    hipLaunchKernelGGL(k4_in_loops, dim3((Lmax + kLoopLanes) / kLoopLanes, G), dim3(kLoopLanes), loop_prepass_lds(a.lay), st, ai);
+  }
   if (bands)
-    for (int d = 0; d <= Wmax; ++d) {
+    for (int d = pre ? a.in_d0 : 0; d <= Wmax; ++d) {
       const int ncell = Lmax - d + 1;
       if (ncell <= 0) break;
-      LinArgs ad = a;
+      LinArgs ad = ai;
       ad.d = d;
       const unsigned gx = band_blocks(ad, ncell, !CON);
       launch_k4_in<CON>(ad, dim3(gx, G), g.lds_in, g.fast, g.big, st);

@@ -21,6 +21,8 @@ namespace elemdp {
 // A block OWNS the cells from its first live cell up to the next block's first (the first block also the dead cells in front,
 // the last one those behind): the owned ranges partition 0 .. ncell - 1, and a block stores the zeros of the dead cells it owns.
 // A diagonal without a live cell has no block.
+// `bits`: the planes that make a cell live (UB_* of plan_rules.h; default: any).  The inside sweep whose L plane a row pre-pass has
+// filled (option loop_prepass) takes the lists of `~UB_L`: a cell that is useful in the L plane alone has nothing left to compute.
 // ---------------------------------------------------------------------------------------------
 constexpr int kLiveSpanMax = 64;   // largest `cap`: the live cells of a block are the set bits of one 64-bit word
 constexpr int kLiveSpanDefault = 32;   // the default (option live_span): the largest at which the train kernels keep their workgroups per CU at W = 50
@@ -31,11 +33,11 @@ struct LiveBlock {
   int16_t count;                   // live cells, 1 .. cpb
 };
 // the blocks of one diagonal from its mask bytes row[0 .. ncell); out: room for ceil(ncell / cpb) records; returns their number
-ELEMDP_HOSTDEV int live_blocks_row(const uint8_t* row, int ncell, int cpb, int cap, LiveBlock* out) {
+ELEMDP_HOSTDEV int live_blocks_row(const uint8_t* row, int ncell, int cpb, int cap, LiveBlock* out, int bits = 0xff) {
   int nb = 0;
   LiveBlock b{0, 0, 0, 0, 0};
   for (int i = 0; i < ncell; ++i) {
-    if (!row[i]) continue;
+    if (!(row[i] & bits)) continue;
     if (b.count == 0 || b.count == cpb || i - b.first >= cap) {
       if (b.count) { b.own_end = (int16_t)i; out[nb++] = b; }
       b.live = 1ull; b.first = (int16_t)i; b.own_lo = (int16_t)(nb == 0 ? 0 : i); b.count = 1;
@@ -48,11 +50,11 @@ ELEMDP_HOSTDEV int live_blocks_row(const uint8_t* row, int ncell, int cpb, int c
   return nb;
 }
 // the workgroups of cpb CONSECUTIVE cells of the diagonal that hold a live cell (the ones that do work without lists)
-ELEMDP_HOSTDEV int working_blocks_row(const uint8_t* row, int ncell, int cpb) {
+ELEMDP_HOSTDEV int working_blocks_row(const uint8_t* row, int ncell, int cpb, int bits = 0xff) {
   int n = 0;
   for (int i0 = 0; i0 < ncell; i0 += cpb) {
     bool any = false;
-    for (int i = i0; i < ncell && i < i0 + cpb; ++i) any = any || row[i] != 0;
+    for (int i = i0; i < ncell && i < i0 + cpb; ++i) any = any || (row[i] & bits) != 0;
     n += any;
   }
   return n;
@@ -68,5 +70,16 @@ constexpr int kLiveCpbMin = 8;
 ELEMDP_HOSTDEV int live_blocks_slots(int L) { return (L + kLiveCpbMin) / kLiveCpbMin; }                 // ceil((L + 1) / kLiveCpbMin)
 ELEMDP_HOSTDEV long long live_blocks_records(int L, int W) { return (long long)(W + 1) * (1 + live_blocks_slots(L)); }
 ELEMDP_HOSTDEV long long live_blocks_at(int L, int W, int d) { return (W + 1) + (long long)d * live_blocks_slots(L); }
+// The plan holds TWO such sets per sequence, each of all its records: the lists of the whole byte (the outside sweep, and the
+// inside sweep without the pre-pass) at PlanArrays::blocks, the lists of the inside sweep behind the pre-pass (the byte without its
+// L bit) at PlanArrays::blocks_in = blocks + the records of the whole plan.
+constexpr int kLiveInsideBits = 0x7f;   // UB_ALL & ~UB_L (plan_rules.h asserts it)
+// The first diagonal on which an entry outside the L plane can be parsable at all: E(i, d) closes a pair of span d + 2 >= min_span
+// (e_ok), P, B, 1 and 2 need a pair of span d >= min_span (pair_ok, left_ok through dmin), M needs d >= m_min (m_ok).  Below it
+// the inside sweep behind the pre-pass has nothing to compute and nothing to store.
+ELEMDP_HOSTDEV int first_inside_diagonal(int min_span, int m_min) {
+  const int e = min_span - 2, d = e < m_min ? e : m_min;
+  return d > 0 ? d : 0;
+}
 
 }  // namespace elemdp

@@ -143,6 +143,7 @@ ELEMDP_HD int count_interior_by_end(bool no_ene, int L, int W, int C, const Word
 // ---------------------------------------------------------------------------------------------
 // (these run on the host too -- the host entry of the C ABI -- where the recurrences of dp_rules.h are device code only)
 enum : int { UB_P = 1, UB_E = 2, UB_M = 4, UB_B = 8, UB_A = 16, UB_1 = 32, UB_2 = 64, UB_L = 128, UB_ALL = 255 };
+static_assert(kLiveInsideBits == (UB_ALL & ~UB_L), "live_blocks.h: the bits of the inside lists behind the loop pre-pass");
 
 struct UsefulCtx {
   int32_t L, W, C, m_min;

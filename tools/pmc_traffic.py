@@ -29,11 +29,12 @@ PEAK = 8.0e12
 
 
 def short(name):
-    """kernel name without namespace and arguments; the two forms of k4_in / k4_out that differ only in their last template
-    argument (takes the plan's live-block lists or consecutive cells) count as ONE kernel, under the name without it"""
+    """kernel name without namespace and arguments; the forms of k4_in / k4_out that differ only in their last template
+    arguments (takes the plan's live-block lists or consecutive cells; k4_in: runs behind the loop pre-pass k4_in_loops, which is a
+    kernel of the pipeline of its own) count as ONE kernel, under the name with the first five arguments"""
     n = name.replace("elemdp::(anonymous namespace)::", "").replace("void ", "").split("(")[0]
-    if n.startswith(("k4_in<", "k4_out<")) and n.count(",") == 5:
-        n = n[:n.rindex(",")] + ">"
+    if n.startswith(("k4_in<", "k4_out<")) and n.count(",") >= 5:
+        n = ",".join(n.split(",")[:5]) + ">"
     return n
 
 
