@@ -305,6 +305,27 @@ int elemdp_context_profile(elemdp_handle* h, const double* x, int32_t n_param, d
  * handed to the log-space form].  elemdp_scan, the pair calls (the list of the last one stays valid), elemdp_sample,
  * elemdp_context_profile and the train calls are unaffected. */
 int elemdp_node_profile(elemdp_handle* h, const double* x, int32_t n_param, double* profile);
+/* Maximum expected accuracy motif alignments and site lists under the motif model x, decoded on the device from
+ * the profile N of elemdp_node_profile.  A node row (0 = 'z' .. M-1 = 'o') is valid if it is the row of some alignment: all 'z', or
+ * z^a n1^r1 .. nk^rk o^c over the pattern's nodes in order, r >= 1 (r >= 0 for a '*' node), the body not empty.  With g = gamma on
+ * the pattern's nodes and 1 on 'z' and 'o', score(row) = sum_p g(row[p]) N(p, row[p]).  Slot 0 of a sequence is the valid row of
+ * greatest score; the positions that carry its pattern nodes are one region [start, end), site 0.  Slot k is the best valid row that
+ * puts no pattern node on a position of the sites 0 .. k-1; the list ends at the first slot whose best row is all 'z', or at
+ * max_sites.  Sites of a sequence never overlap.  Ties go to the lower predecessor at every step and the lower final node: the
+ * result is a function of the profile's bits.  The row maximises a sum of marginals and need not be a derivation of positive
+ * probability (with self-loops in the model it may repeat nodes); site_conf shows it.
+ *   profile: NULL, or as for elemdp_node_profile (then the profile is copied to the host, else it stays on the device);
+ *   node: the row of slot k of sequence n (seq_off[n] = b, length L) at node + max_sites * b + k * L, the layout of elemdp_sample;
+ *   n_sites[n]: the sites found; site_start, site_end, site_score (of the whole row) and site_conf (the mean of N(p, row[p])
+ *   over the site) at [n * max_sites + k].  Unused slots hold start = end = -1, score = conf = NaN and a row of 'z'.
+ * Any output may be NULL.  A sequence without any parse has n_sites 0, exactly.  gamma not finite or <= 0, max_sites outside
+ * 1 .. 64, more than 255 pattern nodes or x NULL is ELEMDP_EINVAL, a call before elemdp_load_batch ELEMDP_ESTATE.
+ * elemdp_last_timing afterwards: [whole call including the copies to the host, sum passes + node kernels + decode, sequences
+ * handed to the log-space form].  elemdp_scan, the pair calls (the list of the last one stays valid), elemdp_sample,
+ * elemdp_context_profile, elemdp_node_profile and the train calls are unaffected. */
+int elemdp_node_mea(elemdp_handle* h, const double* x, int32_t n_param, double gamma, int32_t max_sites,
+                    double* profile, uint8_t* node, int32_t* n_sites, int32_t* site_start, int32_t* site_end,
+                    double* site_score, double* site_conf);
 
 /* timing of the last train evaluation, measured with HIP events on the engine's stream:
  * ms[0] = whole evaluation, ms[1] = the DP pipeline only (all kernels of the inside/outside sweeps),

@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_node_mea", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -93,6 +93,7 @@ def load_library():
         L.elemdp_sample.argtypes = [hp, dp, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(C.c_uint8), dp, i32]
         L.elemdp_context_profile.argtypes = [hp, dp, C.c_int32, dp]
         L.elemdp_node_profile.argtypes = [hp, dp, C.c_int32, dp]
+        L.elemdp_node_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_int32, dp, u8, i32, i32, i32, dp, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
         L.elemdp_last_timing.argtypes = [hp, dp, C.c_int32]
         L.elemdp_epoch_permutation.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
@@ -479,6 +480,36 @@ class Engine:
         prof = np.zeros(max(M * n_pos, 1))
         self._check(self._lib.elemdp_node_profile(self._h, _dp(x), self.n_param, _dp(prof)))
         return [prof[M * int(off[k]):M * int(off[k + 1])].reshape(-1, M).copy() for k in range(self.n_seq)]
+
+    # ---- maximum expected accuracy motif alignments and site lists
+    def mea_alignments(self, x, gamma=1.0, max_sites=1, profile=False):
+        """One dict per sequence, decoded on the device from the node profile: rows (n_sites, L) uint8 -- row k is the valid node
+        row of greatest score sum_p g N(p, row[p]), g = gamma on the pattern's nodes and 1 on 'z' and 'o', that puts no pattern
+        node on a position of the sites before it --, start, end (the region that carries the pattern's nodes), score (of the
+        whole row) and confidence (the mean of N(p, row[p]) over the site), n_sites entries each; with profile=True also
+        profile, the (L, M) array of node_profiles from the same call (else the profile stays on the device)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        M, K, n = self.n_node, int(max_sites), max(self.n_seq, 0)
+        n_pos = int(off[-1]) if off is not None else 0
+        kk = min(max(K, 1), 64)
+        prof = np.zeros(max(M * n_pos, 1)) if profile else None
+        node = np.zeros(max(kk * n_pos, 1), dtype=np.uint8)
+        ns = np.zeros(max(n, 1), dtype=np.int32)
+        s0, s1 = np.zeros(max(n * kk, 1), dtype=np.int32), np.zeros(max(n * kk, 1), dtype=np.int32)
+        sc, cf = np.zeros(max(n * kk, 1)), np.zeros(max(n * kk, 1))
+        self._check(self._lib.elemdp_node_mea(self._h, _dp(x), self.n_param, float(gamma), K, _dp(prof), _u8(node), _i32(ns),
+                                              _i32(s0), _i32(s1), _dp(sc), _dp(cf)))
+        out = []
+        for k in range(self.n_seq):
+            a, b, m = int(off[k]), int(off[k + 1]), int(ns[k])
+            L = b - a
+            rec = dict(rows=node[K * a:K * a + m * L].reshape(m, L).copy(), start=s0[k * K:k * K + m].copy(),
+                       end=s1[k * K:k * K + m].copy(), score=sc[k * K:k * K + m].copy(), confidence=cf[k * K:k * K + m].copy())
+            if profile:
+                rec["profile"] = prof[M * a:M * b].reshape(L, M).copy()
+            out.append(rec)
+        return out
 
     def last_timing(self):
         """[ms whole evaluation, ms DP pipeline, sequences re-evaluated in log space]"""

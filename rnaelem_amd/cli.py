@@ -14,6 +14,9 @@
     python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-nodes nodes.txt
                                     # + posterior motif-node profiles: P(node) of every base and the confidence of the printed
                                     #   alignment (io.node_record)
+    python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-sites sites.txt
+                                    # + maximum expected accuracy motif alignments and site lists decoded from those profiles
+                                    #   (--site-gamma 1.0, --max-sites 1; io.site_record)
     python -m rnaelem_amd.cli       --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --out2 scan.raw
                                     # no sub-command = what script/elem spawns: train, write the model, scan (main.cpp:47-84)
     python -m rnaelem_amd.cli eval  --fastq pos.fq --motif-model model.txt --out1 fn.txt --out2 gr.txt     (motif_eval.hpp:23-54)
@@ -73,6 +76,12 @@ def build_parser():
     sub.choices["scan"].add_argument("--out-nodes", default=None,
                                      help="posterior motif-node profiles under the motif model: one record per sequence "
                                           "(io.node_record), with the confidence of the psihat line of --out1")
+    sub.choices["scan"].add_argument("--out-sites", default=None,
+                                     help="maximum expected accuracy motif alignments and site lists decoded from the node "
+                                          "profile: one record per sequence (io.site_record)")
+    sub.choices["scan"].add_argument("--site-gamma", type=float, default=1.0,
+                                     help="weight of the pattern's nodes: a base on a pattern node scores gamma N, on z or o its N")
+    sub.choices["scan"].add_argument("--max-sites", type=int, default=1, help="most sites reported per sequence (1 .. 64)")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -239,7 +248,8 @@ def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
 
 
 def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0,
-                  out_samples=None, n_samples=100, sample_seed=0, out_context=None, out_nodes=None):
+                  out_samples=None, n_samples=100, sample_seed=0, out_context=None, out_nodes=None, out_sites=None, site_gamma=1.0,
+                  max_sites=1):
     from .distributed import assigned_range
     nodes = eng.describe()["node"]
     step = max(1, chunk)
@@ -250,7 +260,7 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             part = mine[c0:c0 + step]
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
-            if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None:
+            if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None:
                 for (rid, codes, _), r in zip(part, res):
                     yield io.scan_record(rid, codes, r, nodes)
                 continue
@@ -261,7 +271,12 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                 structs, scores, prs = eng.mea_structures(m["x"], mea_gamma, pair_min_prob if out_pairs is not None else None)
             smp = eng.sample_structures(m["x"], n_samples, sample_seed, lo + c0) if out_samples is not None else None
             ctx = eng.context_profiles(m["x"]) if out_context is not None else None
-            nod = eng.node_profiles(m["x"]) if out_nodes is not None else None
+            # (with both files one node pass gives the profiles and the sites)
+            if out_sites is not None:
+                sit = eng.mea_alignments(m["x"], site_gamma, max_sites, profile=out_nodes is not None)
+                nod = [r["profile"] for r in sit] if out_nodes is not None else None
+            else:
+                nod = eng.node_profiles(m["x"]) if out_nodes is not None else None
             for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
                 texts = [io.scan_record(rid, codes, r, nodes)]
                 if out_pairs is not None:
@@ -276,12 +291,14 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                     texts.append(io.context_record(rid, ctx[k]))
                 if out_nodes is not None:
                     texts.append(io.node_record(rid, nod[k], nodes, api.alignment_confidence(nod[k], r["psihat"])))
+                if out_sites is not None:
+                    texts.append(io.site_record(rid, sit[k], nodes))
                 yield tuple(texts)
 
-    if out_mea is None and out_samples is None and out_context is None and out_nodes is None:
+    if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None:
         sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
     else:
-        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes) if o is not None]
+        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites) if o is not None]
         sharded_write(recs, outs, rank, world, scan_part, barrier)
 
 
@@ -296,7 +313,7 @@ def cmd_scan(a):
     m = io.read_model(a.motif_model)
     eng = io.engine_from_model(m, a.device if a.device is not None else local_rank)
     _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
-                  a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes)
+                  a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites)
     if world > 1:
         dist.destroy_process_group()
 

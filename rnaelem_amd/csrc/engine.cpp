@@ -36,6 +36,7 @@
 #include "kernels.h"
 #include "lin_params.h"
 #include "live_blocks.h"
+#include "node_mea_rules.h"
 #include "node_rules.h"
 #include "sample_rules.h"
 #include "table_slots.h"
@@ -210,6 +211,10 @@ class Engine {
   void context_profile(const double* x, int n_param, double* profile);
   // posterior motif-node profiles (node_rules.h): n_node doubles per position of the batch
   void node_profile(const double* x, int n_param, double* profile);
+  // maximum expected accuracy motif alignments and site lists over that profile (node_mea_rules.h); outputs as
+  // elemdp_node_mea, any may be null
+  struct NodeMeaOut { double* profile; uint8_t* node; int32_t* n_sites; int32_t* start; int32_t* end; double* score; double* conf; };
+  void node_mea(const double* x, int n_param, double gamma, int max_sites, const NodeMeaOut& out);
   int partial_len() const { return 4 + 2 * au_.n_theta() + 4; }
   void set_option(const std::string& key, double v);
   void comm_init(int rank, int world, const void* id);
@@ -283,6 +288,7 @@ class Engine {
   void require_resident(const char* what, int n_param_in);
   template <class Fill, class Group> int scan_sums(const ScanPos& pos, Fill fill, Group group, std::vector<int32_t>* flagged = nullptr);
   template <class Fill, class Behind> void scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind behind);
+  int node_profile_device(const char* what, const double* x, int n_param_in);
   TrArgs log_pipeline_args();
   void init_device();
   void flatten_automaton();
@@ -364,6 +370,8 @@ class Engine {
   // context profiles: P, u, h, b of the table slots (four [i][d] arrays per slot), their exterior columns, the profile of the call
   DevBuf d_cx_cells_, d_cx_o_, d_cx_prof_;
   DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
+  // node MEA: the chain lists, the backpointer scratch (M bytes per position), the rows, sites per sequence, start / end / score / confidence per slot
+  DevBuf d_nm_lists_, d_nm_bp_, d_nm_node_, d_nm_ns_, d_nm_s0_, d_nm_s1_, d_nm_sc_, d_nm_cf_;
 
   Automaton au_;
   EnergyTables et_;
@@ -2411,7 +2419,25 @@ void Engine::node_profile(const double* x, int n_param_in, double* profile) {
     });
     return;
   }
-  require_resident("node_profile", n_param_in);
+  const int n_flagged = node_profile_device("node_profile", x, n_param_in);
+  const size_t n_seqpos = (size_t)h_seq_off_[n_seq_];
+  HIP_OK(hipEventRecord(ev_[3], st_));
+  if (n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_nd_prof_.as<void>(), 8 * (size_t)M * n_seqpos, hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms_all = 0, ms_dp = 0;
+  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
+  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
+  last_ms[0] = ms_all;
+  last_ms[1] = ms_dp;
+  last_ms[2] = (double)n_flagged;
+}
+
+// The profile of the resident batch on the device (d_nd_prof_), both forms, queued on the engine's stream behind ev_[1]; returns
+// the number of sequences handed to the log-space form.  The step node_profile and node_mea share.
+int Engine::node_profile_device(const char* what, const double* x, int n_param_in) {
+  const int M = au_.M();
+  require_resident(what, n_param_in);
   upload_params(x, lay_, false);
   const int n = n_seq_;
   const size_t n_seqpos = (size_t)h_seq_off_[n];
@@ -2442,10 +2468,67 @@ void Engine::node_profile(const double* x, int n_param_in, double* profile) {
     d.node = na;
     return std::max(n_log, 1);
   }, [&](const int32_t*, int) {});
+  return n_flagged;
+}
+
+
+// ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h).  The node pass of
+// node_profile, then k_node_mea once over the profile of the whole batch on the engine's stream, behind the last group and the
+// log-space form.  The profile goes to the host only where the caller gave a buffer.  Leaves the list of the last pair call alone.
+void Engine::node_mea(const double* x, int n_param_in, double gamma, int max_sites, const NodeMeaOut& out) {
+  require_device();
+  DeviceGuard dg(device_);
+  const int M = au_.M(), K = max_sites;
+  if (!(gamma > 0.) || !std::isfinite(gamma)) throw ArgError("node_mea: gamma must be finite and > 0");
+  if (K < 1 || K > kNodeMeaMaxSites) throw ArgError("node_mea: max_sites must lie in 1 .. 64");
+  if (M > kNodeMeaMaxNodes) throw ArgError("node_mea: more than 255 pattern nodes");
+  if (streaming_) {
+    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+      const size_t at = (size_t)(h_seq_off_[c0] - h_seq_off_[0]), s0 = (size_t)c0 * K;   // (the chunk's first position / first slot)
+      const NodeMeaOut oc{out.profile ? out.profile + (size_t)M * at : nullptr, out.node ? out.node + (size_t)K * at : nullptr,
+                          out.n_sites ? out.n_sites + c0 : nullptr, out.start ? out.start + s0 : nullptr,
+                          out.end ? out.end + s0 : nullptr, out.score ? out.score + s0 : nullptr, out.conf ? out.conf + s0 : nullptr};
+      e.node_mea(x, n_param_in, gamma, K, oc);
+    });
+    return;
+  }
+  const int n_flagged = node_profile_device("node_mea", x, n_param_in);
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n], n_slots = (size_t)n * K;
+  std::vector<int32_t> lists;
+  {
+    std::string names(M, ' ');
+    for (int m = 0; m < M; ++m) names[m] = au_.node(m);
+    node_mea_lists_build(names.data(), M, &lists);
+  }
+  d_nm_lists_.upload(lists, st_);
+  d_nm_bp_.alloc((size_t)M * std::max<size_t>(n_seqpos, 1));
+  d_nm_node_.alloc((size_t)K * std::max<size_t>(n_seqpos, 1));
+  d_nm_ns_.alloc(4 * (size_t)n);
+  d_nm_s0_.alloc(4 * n_slots); d_nm_s1_.alloc(4 * n_slots);
+  d_nm_sc_.alloc(8 * n_slots); d_nm_cf_.alloc(8 * n_slots);
+  NodeMeaArgs ma;
+  std::memset(&ma, 0, sizeof(ma));
+  ma.plans = plan_.d_plans.as<SeqPlan>();
+  ma.lists = d_nm_lists_.as<int32_t>();
+  ma.M = M; ma.max_sites = K; ma.gamma = gamma;
+  ma.profile = d_nd_prof_.as<double>();
+  ma.bp = d_nm_bp_.as<uint8_t>();
+  ma.node = d_nm_node_.as<uint8_t>(); ma.n_sites = d_nm_ns_.as<int32_t>();
+  ma.start = d_nm_s0_.as<int32_t>(); ma.end = d_nm_s1_.as<int32_t>();
+  ma.score = d_nm_sc_.as<double>(); ma.conf = d_nm_cf_.as<double>();
+  HIP_OK(launch_node_mea(ma, n, st_));
   HIP_OK(hipEventRecord(ev_[3], st_));
-  if (n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_nd_prof_.as<void>(), 8 * (size_t)M * n_seqpos, hipMemcpyDeviceToHost, st_));
+  auto fetch = [&](void* dst, const DevBuf& src, size_t bytes) {
+    if (dst && bytes) HIP_OK(hipMemcpyAsync(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost, st_));
+  };
+  fetch(out.profile, d_nd_prof_, 8 * (size_t)M * n_seqpos);
+  fetch(out.node, d_nm_node_, (size_t)K * n_seqpos);
+  fetch(out.n_sites, d_nm_ns_, 4 * (size_t)n);
+  fetch(out.start, d_nm_s0_, 4 * n_slots); fetch(out.end, d_nm_s1_, 4 * n_slots);
+  fetch(out.score, d_nm_sc_, 8 * n_slots); fetch(out.conf, d_nm_cf_, 8 * n_slots);
   HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
+  HIP_OK(hipStreamSynchronize(st_));   // (the host vector of the lists goes out of use here at the latest)
   float ms_all = 0, ms_dp = 0;
   HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
   HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
@@ -2844,6 +2927,13 @@ int elemdp_node_profile(elemdp_handle* h, const double* x, int32_t n_param, doub
   ELEMDP_TRY
   if (!h || !x || !profile) throw elemdp::ArgError("elemdp_node_profile: null argument");
   h->e->node_profile(x, n_param, profile);
+  ELEMDP_CATCH
+}
+int elemdp_node_mea(elemdp_handle* h, const double* x, int32_t n_param, double gamma, int32_t max_sites, double* profile,
+                    uint8_t* node, int32_t* n_sites, int32_t* site_start, int32_t* site_end, double* site_score, double* site_conf) {
+  ELEMDP_TRY
+  if (!h || !x) throw elemdp::ArgError("elemdp_node_mea: null argument");
+  h->e->node_mea(x, n_param, gamma, max_sites, elemdp::Engine::NodeMeaOut{profile, node, n_sites, site_start, site_end, site_score, site_conf});
   ELEMDP_CATCH
 }
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {

@@ -113,6 +113,19 @@ struct NodeArgs {
   double* profile;
 };
 
+// ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h, node_mea_kernels.hip) over the profile of the
+// whole batch: batch index n with seq_base b and length L writes the row of slot k at node + max_sites * b + k * L (the sampler's
+// layout), n_sites[n], and start / end / score / conf at [n * max_sites + k]
+struct NodeMeaArgs {
+  const SeqPlan* plans;           // batch plans (batch index)
+  const int32_t* lists;           // lo, first, last per node (node_mea_lists_build)
+  int32_t M, max_sites;
+  double gamma;
+  const double* profile;          // NodeArgs::profile of the same call
+  uint8_t* bp;                    // scratch: M bytes per position of the batch, the predecessor of every (position, node)
+  uint8_t* node; int32_t* n_sites; int32_t* start; int32_t* end; double* score; double* conf;
+};
+
 struct DpArgs {
   AutomatonLayout lay;            // host-visible copy (launch geometry, LDS sizes)
   const AutomatonLayout* layp;    // the same record in device memory: kernels read it through this pointer
@@ -373,6 +386,8 @@ hipError_t launch_ctx_cells(const LinArgs& a, const CtxArgs& c, int G, int cells
 hipError_t launch_ctx_seq(const CtxArgs& c, int G, hipStream_t st);
 // k_node_pos behind launch_lin_scan_group (SCAN_PASS_START) on the same slots and stream: one wave per (sequence, position)
 hipError_t launch_node_pos(const LinArgs& a, const NodeArgs& c, int G, int Lmax, hipStream_t st);
+// k_node_mea behind the node pass of the whole batch (both forms), on the engine's stream: one wave per sequence
+hipError_t launch_node_mea(const NodeMeaArgs& a, int n_seq, hipStream_t st);
 // kept pairs of every sequence of the batch (the staging capacity), off[0..n] = exclusive prefix of cnt[0..n) with off[n] the total,
 // and the scatter of the staging list into the final list ordered by (sequence, i, j)
 hipError_t launch_pair_kept(const SeqPlan* plans, const uint32_t* okbits, int n, int64_t* kept, hipStream_t st);

@@ -296,3 +296,36 @@ def read_node_records(path):
             k += 1
         out.append((rid, names, np.array(cols, dtype=np.float64).T.reshape(-1, len(cols)), conf))
     return out
+
+
+def site_record(rid, res, names):
+    """Record of one sequence in the `scan --out-sites` file: `id: <id>`, then per site k one line `site k: start end score
+    confidence` (the region [start, end) that carries the pattern's nodes, the score of the whole row, the mean of N(p, row[p])
+    over the site; 6 significant digits) and one line with the node name of every base; res: one entry of
+    Engine.mea_alignments, names: describe()["node"].  A sequence without a site has the id line alone."""
+    lines = ["id: " + rid]
+    for k in range(len(res["start"])):
+        lines.append("site %d: %d %d %s %s" % (k, res["start"][k], res["end"][k], fmt(float(res["score"][k])), fmt(float(res["confidence"][k]))))
+        lines.append("".join(names[int(m)] for m in res["rows"][k]))
+    return "\n".join(lines) + "\n"
+
+
+def read_sites(path):
+    """-> list of (id, dict(start, end, score, confidence, rows)) from a `scan --out-sites` file; rows: the lines of node names."""
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+    while k < len(lines) and lines[k].startswith("id: "):
+        rid = lines[k][4:]
+        k += 1
+        start, end, score, conf, rows = [], [], [], [], []
+        while k < len(lines) and lines[k].startswith("site "):
+            head, body = lines[k].split(": ", 1)
+            if int(head[5:]) != len(start):
+                raise ValueError("site record %r: line %r where site %d was expected" % (rid, head, len(start)))
+            a, b, sc, cf = body.split()
+            start.append(int(a)); end.append(int(b)); score.append(float(sc)); conf.append(float(cf))
+            rows.append(lines[k + 1])
+            k += 2
+        out.append((rid, dict(start=np.array(start, dtype=np.int32), end=np.array(end, dtype=np.int32), score=np.array(score),
+                              confidence=np.array(conf), rows=rows)))
+    return out
