@@ -115,6 +115,12 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *                       elemdp_live_blocks_inside) and the diagonals below the first hairpin; active wherever "useful_mask" is,
  *                       the deterministic mode included (every L entry is bit-identical to the sweep's own); 0: the sweep
  *                       computes L itself, with one set of lists -- the A/B switch and the tests' reference
+ *     "loop_outside"    1 (default): the outside L plane -- the rule-6c sums of the loops, the chain L <- L, the 6b energy statistic
+ *                       and the right-emission counts of the chain -- is made by two kernels behind the table-driven outside
+ *                       sweep, which then computes no L, sums the item records of the inner pairs alone, and takes the lists
+ *                       of elemdp_live_blocks_inside (built for it where "loop_prepass" is 0); active wherever "useful_mask" is,
+ *                       except in the deterministic mode, where it is ignored; 0: the sweep computes L itself -- the A/B
+ *                       switch and the tests' reference
  *   measurement / tests
  *     "profile"         in-kernel phase clocks for elemdp_debug_profile; "dbg": switch phases off (results invalid);
  *     "poison"          1: every table is filled with NaN before an evaluation (an unmasked read of an entry nobody stored shows) */

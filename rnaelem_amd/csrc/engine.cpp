@@ -258,6 +258,7 @@ class Engine {
   void ensure_useful_mask();
   bool ensure_live_blocks(int cpb, int cap, bool inside_too);
   bool loop_prepass_ok(bool sched1) const;
+  bool loop_outside_ok(bool sched1) const;
   int live_span_for(int cpb) const;
   bool lists_wanted() const;
   LdsLayout lds_layout(const AutomatonLayout& lay, int Lmax, int nword_max, bool scan) const;
@@ -429,6 +430,9 @@ class Engine {
   int opt_live_span_ = 0;          // option "live_span": the cells a block may span (0: kLiveSpanDefault, at least cpb)
   bool opt_loop_prepass_ = true;   // option "loop_prepass": a row pre-pass fills the inside L plane of the table-driven train sweep, whose
                                    // workgroups then skip the cells that are useful in L alone; 0 = the sweep computes L itself
+  bool opt_loop_outside_ = true;   // option "loop_outside": the outside L plane (heavy sum HL, chain, 6b statistic, chain counts) is made by
+                                   // two kernels behind the table-driven train sweep, which skips the cells that are useful in L alone
+                                   // (DESIGN §4.6); ignored in the deterministic mode; 0 = the sweep computes L itself
   int opt_useful_lds_kb_ = 150;    // option "useful_mask_lds_kb": k_useful_mask's LDS budget; a larger sequence gets the all-ones mask
   bool opt_sorted_plan_ = false;   // option "sorted_plan": sort the role lists at load_batch whatever the pipeline
   // scaled-linear pipeline
@@ -634,6 +638,7 @@ void Engine::set_option(const std::string& key, double v) {
     opt_live_blocks_ = (int)v;
   }
   else if (key == "loop_prepass") opt_loop_prepass_ = v != 0;
+  else if (key == "loop_outside") opt_loop_outside_ = v != 0;
   else if (key == "live_span") {   // (0: the default; a model with more cells per block than the value takes its cells per block)
     if (v < 0 || v > lin_live_span_max()) throw ArgError("live_span: 0 (default) or cells per block .. " + std::to_string(lin_live_span_max()));
     opt_live_span_ = (int)v;
@@ -1588,11 +1593,12 @@ void Engine::run_lin_batch() {
   a.p.useful = opt_useful_mask_ ? plan_.useful.as<uint8_t>() : nullptr;   // (the train sweeps only: the scan family sees null)
   // the loop pre-pass goes with the mask (the launcher drops it where the table-driven form does not run)
   a.loop_pre = (opt_loop_prepass_ && opt_useful_mask_ && loop_prepass_ok(sched1)) ? 1 : 0;
+  a.loop_post = (opt_loop_outside_ && opt_useful_mask_ && !opt_det_ && loop_prepass_ok(sched1) && loop_outside_ok(sched1)) ? 1 : 0;
   a.in_d0 = first_inside_diagonal(min_span(), m_min());
   // ... and with it the live-block lists (not in the deterministic mode, whose sums follow the grouping of consecutive cells)
   if (lists_wanted()) {
     const int cpb = lin_train_cpb(a), cap = live_span_for(cpb);
-    if (cpb > 0 && ensure_live_blocks(cpb, cap, a.loop_pre != 0)) {
+    if (cpb > 0 && ensure_live_blocks(cpb, cap, a.loop_pre != 0 || a.loop_post != 0)) {
       a.p.blocks = plan_.blocks.as<LiveBlock>();
       a.p.blocks_in = plan_.blk_two ? a.p.blocks + (size_t)plan_.n_blocks : nullptr;
       a.live_span = cap;
@@ -1892,6 +1898,10 @@ void Engine::batch_pairs(int idx, uint8_t* kept, double* lnbpp, int cap) {
 // deterministic mode, whose sums follow the grouping of consecutive cells.
 bool Engine::lists_wanted() const { return opt_useful_mask_ && opt_live_blocks_ && !opt_det_; }
 // can the loop pre-pass serve the automaton a train evaluation sweeps (the one with the shadow state under schedule 1)?
+bool Engine::loop_outside_ok(bool sched1) const {
+  const bool shadow = sched1 && lays_.shadow >= 0;
+  return lin_loop_outside_ok(shadow ? lays_ : lay_, shadow ? intss_.data() : ints_.data());
+}
 bool Engine::loop_prepass_ok(bool sched1) const {
   const bool shadow = sched1 && lays_.shadow >= 0;
   return lin_loop_prepass_ok(shadow ? lays_ : lay_, shadow ? intss_.data() : ints_.data(), min_span());

@@ -295,6 +295,10 @@ struct LinArgs {
   // diagonal with an entry outside the L plane (first_inside_diagonal); blk_grid_in = blk_grid of the inside set (p.blocks_in)
   int32_t loop_pre = 0, in_d0 = 0;
   const int32_t* blk_grid_in = nullptr;
+  // the outside L plane behind the sweep (option loop_outside; k4_out_seed / k4_out_loops): 1 = the outside sweep of the table-driven
+  // train form computes and stores no L, takes the inside set of lists and starts no diagonal below in_d0 (the engine sets it where
+  // loop_pre could be set and the mode is not the deterministic one)
+  int32_t loop_post = 0;
 };
 struct LinWeightArgs {
   const LoopItem* items_inner; const LoopItem* items_left; const LoopItem* items_right;   // (may be null)
@@ -337,6 +341,8 @@ void live_blocks_host(const uint8_t* mask, int L, int W, int cpb, int cap, int32
 // can the loop pre-pass serve the automaton of this host blob?  (the L rows fit the pre-pass's staging, and a loop state without an
 // L column has the L value 0 in the sweep's own rule too; min_span: the smallest span of a kept pair)
 bool lin_loop_prepass_ok(const AutomatonLayout& lay, const int32_t* ints, int min_span);
+// ... and the L kernels behind the outside sweep (option loop_outside), on top of lin_loop_prepass_ok
+bool lin_loop_outside_ok(const AutomatonLayout& lay, const int32_t* ints);
 // cells per block of the table-driven train sweeps of these arguments, 0 where they run another form (no lists then); the
 // largest span a block's live cells may cover in this build
 int lin_train_cpb(const LinArgs& full);

@@ -243,7 +243,10 @@ ELEMDP_HD bool fast_scan_stat(Sink& sink, int sf, int kl, int kr, bool yl, bool 
 // (heavy sums H1, H2, HP, HL of the target at ph[0], ph[CS], ph[2 CS], ph[3 CS] in LDS: read where they are used)
 // MODE: OUT_TRAIN (expected counts + energy statistics), OUT_SCAN (counts + start / inner posteriors), OUT_END (end posteriors
 // under the start constraint: CF_YL / CF_YR / CF_JLAST in fl); FS = the ScanFlag words of the scan modes.
-template <int kFR, int kFP, int kFL, int MODE, class Sink>
+// LPOST: the L plane of the outside table is made behind the sweep (option loop_outside: k4_out_seed / k4_out_loops with
+// loop_outside_entry below) -- nothing in the sweep reads an outside L entry but the L chain itself, so no inside L and no parent
+// L is loaded here, no L <- L count, no 6b statistic and no HL is taken, and no L is stored
+template <int kFR, int kFP, int kFL, int MODE, bool LPOST = false, class Sink>
 ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, const int32_t* G, const double* lin,
                                                      const TableView& in, const TableView& out, const double* cr, int fl, int d, int i,
                                                      double invZ, bool lam_same, bool no_prf, Sink& sink, const double* ph, int CS, int nrep,
@@ -283,7 +286,7 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
     opM[u] = out.ldc(ST_M, dp1, im1, fcol(eL[u], 0), u < nRL && doM);
   }
 #if !ELEMDP_UNARY2
-  const double in1 = in.ldc(ST_1, d, i, c1o, lok && u1), in2 = in.ldc(ST_2, d, i, c2o, lok && u2), inL = in.ldc(ST_L, d, i, cLo, isloop && uL);
+  const double in1 = in.ldc(ST_1, d, i, c1o, lok && u1), in2 = in.ldc(ST_2, d, i, c2o, lok && u2), inL = LPOST ? 0. : in.ldc(ST_L, d, i, cLo, isloop && uL);
   const double r7 = out.ldc(ST_P, d, i, cPo, pok);
   double op2[kFR], opL[kFR];
   int eR[kFR];
@@ -291,7 +294,7 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
   for (int u = 0; u < kFR; ++u) {
     eR[u] = P[4 + u];
     op2[u] = out.ldc(ST_2, dp1, i, fcol(eR[u], 0), u < nRR && do2);
-    opL[u] = out.ldc(ST_L, dp1, i, fcol(eR[u], 1), u < nRR && doL && eR[u] < 0);   // (sign bit: the parent is a loop state)
+    opL[u] = LPOST ? 0. : out.ldc(ST_L, dp1, i, fcol(eR[u], 1), u < nRR && doL && eR[u] < 0);   // (sign bit: the parent is a loop state)
   }
 #endif
   const double inEz = inE * invZ, inPz = inP * invZ, inMz = inM * invZ;
@@ -342,7 +345,7 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
 #if defined(__HIP_DEVICE_COMPILE__)
   __builtin_amdgcn_sched_barrier(0);
 #endif
-  const double in1 = in.ldc(ST_1, d, i, c1o, lok && u1), in2 = in.ldc(ST_2, d, i, c2o, lok && u2), inL = in.ldc(ST_L, d, i, cLo, isloop && uL);
+  const double in1 = in.ldc(ST_1, d, i, c1o, lok && u1), in2 = in.ldc(ST_2, d, i, c2o, lok && u2), inL = LPOST ? 0. : in.ldc(ST_L, d, i, cLo, isloop && uL);
   const double r7 = out.ldc(ST_P, d, i, cPo, pok);
   double op2[kFR], opL[kFR];
   int eR[kFR];
@@ -350,11 +353,11 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
   for (int u = 0; u < kFR; ++u) {
     eR[u] = P[4 + u];
     op2[u] = out.ldc(ST_2, dp1, i, fcol(eR[u], 0), u < nRR && do2);
-    opL[u] = out.ldc(ST_L, dp1, i, fcol(eR[u], 1), u < nRR && doL && eR[u] < 0);   // (sign bit: the parent is a loop state)
+    opL[u] = LPOST ? 0. : out.ldc(ST_L, dp1, i, fcol(eR[u], 1), u < nRR && doL && eR[u] < 0);   // (sign bit: the parent is a loop state)
   }
 #endif
   const double in2z = in2 * invZ, inLz = inL * invZ;
-  const bool a2 = do2 && in2 != 0., aL = doL && inL != 0.;
+  const bool a2 = do2 && in2 != 0., aL = !LPOST && doL && inL != 0.;
   // 2 and L as children of 2 / L (i,j+1,par) (rules 3a, L <- L): right emission by the parent's r-node
 #pragma unroll
   for (int u = 0; u < kFR; ++u)
@@ -371,9 +374,10 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
     }
   // 1 (heavy sum H1), B (child of M (5b) and of 1 (4b): its inside value is non-zero wherever a pair entry that takes it is),
   // 2 (child of 1 (4a), of 2(i,j+1,par) (3a); the rule-2 part reaches P as H2 = HA)
-  double H1 = ph[0], H2 = ph[CS], HP = ph[2 * CS], HL = ph[3 * CS];
+  double H1 = ph[0], H2 = ph[CS], HP = ph[2 * CS], HL = LPOST ? 0. : ph[3 * CS];
   for (int r = 1; r < nrep; ++r) {   // (deterministic mode: one copy per wave)
-    H1 += ph[r * rstride]; H2 += ph[r * rstride + CS]; HP += ph[r * rstride + 2 * CS]; HL += ph[r * rstride + 3 * CS];
+    H1 += ph[r * rstride]; H2 += ph[r * rstride + CS]; HP += ph[r * rstride + 2 * CS];
+    if (!LPOST) HL += ph[r * rstride + 3 * CS];
   }
   const double o1 = (in1 != 0.) ? H1 : 0.;
   const double oB = lok ? (mok ? oM : 0.) + o1 : 0.;
@@ -386,6 +390,7 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
     oP = oP1b + t3b + (HP + r7);
   }
   if (pok && cPo >= 0) out.band[out.cidx(ST_P, d, i, cPo)] = oP;
+  if (LPOST) return oB;
   double oL = 0.;
   if (inL != 0.) {   // child of E (6b), of L(i,j+1,par), loops of interior loops (6c: HL)
     const double t6b = oE * cr[4 + kl], z = t6b * inLz;
@@ -394,6 +399,46 @@ ELEMDP_HD double fast_outside_unary(const AutomatonLayout& A, const int32_t* P, 
   }
   if (cLo >= 0) out.band[out.cidx(ST_L, d, i, cLo)] = oL;
   return oB;
+}
+
+// ---- the outside L plane behind the sweep (option loop_outside) ------------------------------------------------------------
+// One term of the heavy sum HL of rule 6c (the item phase of k4_out, roles 1 and 2): out E of the item's outer cell, in P of its
+// inner pair, in L of the other loop, and the item's weight exp(lambda_k tsc) of the lambda class of the tuple's parent.
+ELEMDP_HD double loop_outside_seed_term(double oE, double inP, double inLo, double xw) { return oE * (inP * inLo) * xw; }
+
+// The outside L entry of one (cell, loop state) behind the sweep -- the L part of fast_outside_unary, operation for operation:
+//   oL = inL != 0 ? (t6b + sL) + HL : 0,  t6b = oE * xhp (6b),  sL = sum over the right transitions u < nRR whose parent is a loop
+//   state of  out L(i, d + 1, parent) * w,  w = WR[id][br] * (fr & 1 ? ews_r : 1)   (L <- L)
+// with the 6b energy statistic e_hp * t6b * inL * invZ and the right-emission counts tL * inL * invZ of the chain.
+// P = the state's outside program, G = the blob (fe_r), wr = the weight table WR (lin + lin_wr), parent = the outside L row of
+// (i, d + 1) indexed by column (read only where doL), inL = the cell's own inside L entry (0 where the state is no loop state or
+// the cell's UB_L bit is off), oE / xhp / e_hp = out E of the state's E column and the hairpin terms of the cell above (0 where the
+// cell is no E cell), doL = the cell's CF_DOL flag, br / ews_r = base and position weight of j, ehs = the lambda class of the
+// statistic (0 under lam_same).
+template <int kFR, class Sink>
+ELEMDP_HD double loop_outside_entry(const int32_t* P, const int32_t* G, int fe_r, const double* wr, const double* parent, double inL,
+                                    double HL, double oE, double xhp, double e_hp, bool doL, int br, double ews_r, double invZ, int ehs,
+                                    bool no_prf, Sink& sink) {
+  if (inL == 0.) return 0.;
+  const int nRR = (P[0] >> 8) & 15;
+  const double inLz = inL * invZ;
+  double sL = 0.;
+  if (doL) {
+#pragma unroll
+    for (int u = 0; u < kFR; ++u)
+      if (u < nRR) {
+        const int e = P[4 + u], c = fcol(e, 1), id = (e >> 16) & 0x7fff;
+        const int enr = G[fe_r + 2 * id], fr = G[fe_r + 2 * id + 1];
+        const double w = wr[5 * id + br] * ((fr & 1) ? ews_r : 1.);
+        const double tL = (e < 0 && c >= 0) ? parent[c] * w : 0.;   // (sign bit: the parent is a loop state)
+        const double z = tL * inLz;
+        if (!no_prf && z != 0. && br) sink.en(enr + br, z);
+        sL += tL;
+      }
+  }
+  const double t6b = oE * xhp, z = t6b * inLz;
+  if (z != 0.) sink.eh(ehs, e_hp * z);
+  return t6b + sL + HL;
 }
 
 }  // namespace elemdp

@@ -1487,7 +1487,10 @@ __global__ __launch_bounds__(kThreads) void k4_r7(LinArgs a) {
 
 // ---- outside, diagonal d: dynamic LDS = 4 * cpb * S + n_theta + 2 doubles
 // W6: asked for six waves per SIMD (80 registers, a few spilled dwords) -- taken by the launcher where six workgroups fit the LDS
-template <int MODE, bool BIG, bool FAST = false, int FP = kFastP, bool W6 = false, bool LISTS = false>
+// LPOST: the train form in front of k4_out_seed / k4_out_loops (option loop_outside), which make the L plane of the outside table
+// and its statistics behind the sweep: no L is computed or stored here, the item phase has role 0 alone, the zeros of dead cells
+// leave the L rows alone, and a cell is live by its bits other than UB_L (LISTS: the plan's second set of lists, as behind LPRE)
+template <int MODE, bool BIG, bool FAST = false, int FP = kFastP, bool W6 = false, bool LISTS = false, bool LPOST = false>
 __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_out(LinArgs a) {
   extern __shared__ double lds[];
   // (the automaton layout is read from the kernel arguments: constant offsets, scalar registers)
@@ -1506,12 +1509,14 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   constexpr bool MASK = FAST && MODE == OUT_TRAIN;   // (as in k4_in; the B plane and plane 1 are not stored on this side)
   const int ncell = L - d + 1;
   static_assert(!LISTS || (FAST && MODE == OUT_TRAIN), "lists: the table-driven train form only");
+  static_assert(!LPOST || (FAST && MODE == OUT_TRAIN), "the L plane behind the sweep: the table-driven train form only");
+  constexpr int kDeadL = LPOST ? -1 : ST_L;   // (the L rows belong to the kernels behind the sweep)
   constexpr bool lists = LISTS;   // (as in k4_in: the live cells of block bx)
   int i0 = bx * cpb, nc = 0, span = 0;
   unsigned long long live = 0ull;
   if (lists) {
     const LiveCells lc = live_cells(v.q, d, (int)bx, ncell);
-    if (lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.out, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, ST_L, ST_2, ST_M, -1);
+    if (lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.out, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, kDeadL, ST_2, ST_M, -1);
     if (!lc.sweep) return;
     i0 = lc.i0; nc = lc.nc; span = lc.span; live = lc.live;
   } else {
@@ -1525,7 +1530,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     // reader.  Workgroups whose cells all satisfy j <= Ys return: on average half of the sweep.
     if (!(a.dbg & 4096) && i0 + nc - 1 + d <= a.ys[v.n]) return;
   }
-  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid)) { fill_dead_rows(v.out, d, i0, nc, tid, ST_L, ST_2, ST_M, -1); return; }
+  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid, LPOST ? (UB_ALL & ~UB_L) : UB_ALL)) { fill_dead_rows(v.out, d, i0, nc, tid, kDeadL, ST_2, ST_M, -1); return; }
   const int HD = FAST ? A.n_lane : S;   // (as in k4_in)
   const int CS = cpb * HD;
   // ONE copy of the heavy sums (deterministic mode: each gets its adds from one wave, see the top of the file); the statistics,
@@ -1626,7 +1631,8 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     // (table-driven kernels: no loop sums on the diagonal d = 0 -- the outside value of an EMPTY loop L(i,i) has no reader: it has
     // no children, and the statistics of the emissions into it use the parent's value.  Those cells own the records of every
     // stack and bulge of the sequence.  The generic kernels, whose tables debug_tables exports, keep them.)
-    if (have && nq > 0 && (role != 0 || v.q.pair_ok(i, d)) && !(FAST && role != 0 && d == 0)) { n0 = off[cell]; n1 = off[cell + 1]; }
+    // (LPOST: roles 1 and 2 are the seed kernel's)
+    if (have && nq > 0 && (role != 0 || v.q.pair_ok(i, d)) && !(FAST && role != 0 && d == 0) && !(LPOST && role != 0)) { n0 = off[cell]; n1 = off[cell + 1]; }
     base[vc] = n0;
     cnts[vc] = (n1 > n0) ? n1 - n0 : 0;
   }
@@ -1788,7 +1794,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
         const int p = p0 + x;
         int lo, n;
         outer_locate(p, nv, pre, base, lo, n);   // the (role, cell) owning record p
-        const int role = (lo >= cpb) + (lo >= 2 * cpb);
+        const int role = LPOST ? 0 : (lo >= cpb) + (lo >= 2 * cpb);
         const LoopItem* src = role == 0 ? v.q.items_inner : role == 1 ? v.q.items_left : v.q.items_right;
         const LoopItem itv = src[n];
         const int meta = (role << 16) | (lo - role * cpb);
@@ -1809,7 +1815,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
         const bool valid = x < np;
         const int xc = valid ? x : np - 1;
         const LoopItem it = r_it[xc];
-        const int role = r_meta[xc] >> 16, c = r_meta[xc] & 0xffff;
+        const int role = LPOST ? 0 : r_meta[xc] >> 16, c = r_meta[xc] & 0xffff;
         const int i = ci(c), j = i + d;
         const uint32_t rE = out.cidx(ST_E, it.j - it.i, it.i, 0);
         const uint32_t rPi = in.cidx(ST_P, it.l - it.k, it.k, 0);
@@ -1893,7 +1899,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
       sink.world = w1 ? 1 : 0;
       sink.en_ = l_en + (w1 ? nt : 0);
       if (FAST) {
-        oB = fast_outside_unary<kFastR, FP, kFastL, MODE>(A, G + A.fp_out + s * kFastW, G, v.m.lin, in, out, crec + c * kCellOutD, crfl[c],
+        oB = fast_outside_unary<kFastR, FP, kFastL, MODE, LPOST>(A, G + A.fp_out + s * kFastW, G, v.m.lin, in, out, crec + c * kCellOutD, crfl[c],
                                                           d, ci(c), w1 ? pi.invZs : pi.invZ, v.m.lam_same != 0, v.m.no_prf != 0, sink,
                                                           h1 + slot, CS, NW, HS, G + A.fs_out);
       } else {
@@ -1987,6 +1993,194 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   if (MODE == OUT_TRAIN || MODE == OUT_SCAN) lflush(a, v, pi, sink, l_en0, kBT, (int)bx);
   pc.mark<12>();
   pc.finish();
+}
+
+// ---- the outside L plane behind the sweep (option loop_outside; the table-driven train form under the mask, not the deterministic
+// mode).  Nothing in the outside sweep reads an outside L entry except the L chain itself, so everything that consumes out L runs
+// behind the sweep, where out E, in P and in L are complete and no diagonal order binds it: k4_out_seed sums the heavy sum HL of
+// rule 6c (roles 1 and 2 of the item records) into the cells' out L rows, k4_out_loops runs the chain L <- L down the rows with the
+// 6b statistic and the right-emission counts (loop_outside_entry, lin_fast.h).
+// k4_out_seed: a workgroup takes kSeedRows rows x kSeedDiags diagonals.  The role records of a row's cells (cell index i * (W + 1)
+// + d) are one run of the CSR arrays.  kSeedCap records at a time are staged in LDS, one lane each (the rows of the three operands,
+// both weights, the slot of the cell's sums); then lane = (record, tuple): three gathers and one LDS add.  Every entry of the tile
+// has this one writer: sums in LDS, then plain stores of every entry of the L rows -- zeros where a cell has no record or no UB_L
+// bit.  The LDS (the tile's sums, n_lane doubles per cell, + the staged records) bounds the residency: 5 workgroups per CU on the
+// bench model.
+constexpr int kSeedRows = 8, kSeedDiags = 17, kSeedCap = 256;   // (kSeedCap: records staged at a time)
+static size_t loop_seed_lds(const AutomatonLayout& A) {
+  return sizeof(double) * ((size_t)kSeedRows * kSeedDiags * A.n_lane + 2 * kSeedCap) +
+         sizeof(int32_t) * (kSeedRows * (kSeedDiags + 1) + kSeedRows + 1 + kLoopColsMax + 4 * kSeedCap + 2 * (size_t)A.n_quad);
+}
+__global__ __launch_bounds__(kBT) void k4_out_seed(LinArgs a) {
+  extern __shared__ double lds[];
+  LViews v(a.lay);
+  make_lviews(a, blockIdx.y, v);
+  if (v.row[4] != 0.) return;   // (a skipped sequence: lpass)
+  const AutomatonLayout& A = a.lay;
+  const int tid = threadIdx.x, L = v.q.L, W = v.q.W;
+  const int i0 = blockIdx.x * kSeedRows, d0 = blockIdx.z * kSeedDiags;
+  if (d0 > W || i0 + d0 > L) return;
+  const int nrow = (kSeedRows < L - i0 + 1) ? kSeedRows : L - i0 + 1, nd = (kSeedDiags < W - d0 + 1) ? kSeedDiags : W - d0 + 1;
+  const int HD = A.n_lane, nq = A.n_quad, rs = v.out.rs[ST_L];
+  double* acc = lds;                                                   // [row][diagonal][lane of the unary phase]
+  double* s_xw = acc + kSeedRows * kSeedDiags * HD;                    // staged records: exp(lambda_k tsc) [k][record],
+  int* offs = reinterpret_cast<int*>(s_xw + 2 * kSeedCap);             // [row][diagonal + 1]: CSR offsets of the role
+  int* pre = offs + kSeedRows * (kSeedDiags + 1);                     // [row + 1]: records of the rows before
+  int* cmap = pre + kSeedRows + 1;                                    // L column -> lane
+  int* s_row = cmap + kLoopColsMax;                                   // ... the rows of their three operands and the cell's sums [4][record]
+  int* tq = s_row + 4 * kSeedCap;                                     // the column records of the role's tuples
+  for (int t = tid; t < kSeedRows * kSeedDiags * HD; t += kBT) acc[t] = 0.;
+  if (tid < kLoopColsMax) cmap[tid] = -1;
+  __syncthreads();
+  for (int k = tid; k < HD; k += kBT) {
+    const int c = fcol(a.ints[A.fp_out + a.ints[A.f_live_out + k] * kFastW + 2], 2);
+    if (c >= 0 && c < kLoopColsMax) cmap[c] = k;
+  }
+  const int32_t* G = v.m.big;
+  const double* IB = v.in.band;
+  const double* OB = v.out.band;
+  const float rcp_nq = 1.0f / (float)(nq > 0 ? nq : 1);
+  for (int role = 1; role <= 2; ++role) {
+    const int32_t* off = role == 1 ? v.q.by_left_off : v.q.by_right_off;
+    const LoopItem* items = role == 1 ? v.q.items_left : v.q.items_right;
+    __syncthreads();
+    // (no loop sums on the diagonal d = 0, as in k4_out: the records of its cells are left out of the row's run)
+    for (int t = tid; t < nrow * (nd + 1); t += kBT) {
+      const int r = t / (nd + 1), dd = t - r * (nd + 1), d = d0 + dd;
+      offs[r * (kSeedDiags + 1) + dd] = nq > 0 ? off[v.q.cell(i0 + r, d > 0 ? d : 1)] : 0;
+    }
+    for (int t = tid; t < 2 * nq; t += kBT) tq[t] = G[A.fqc_out + role * 2 * nq + t];
+    __syncthreads();
+    if (tid == 0) {
+      int n = 0;
+      for (int r = 0; r < nrow; ++r) { pre[r] = n; n += offs[r * (kSeedDiags + 1) + nd] - offs[r * (kSeedDiags + 1)]; }
+      pre[nrow] = n;
+    }
+    __syncthreads();
+    const int n_rec = pre[nrow];
+    for (int p0 = 0; p0 < n_rec; p0 += kSeedCap) {
+      const int np = (kSeedCap < n_rec - p0) ? kSeedCap : n_rec - p0;
+      // one record per lane: its cell, the rows of its operands, its weights
+      for (int xs = tid; xs < np; xs += kBT) {
+        const int x = p0 + xs;
+        int r = 0;
+        while (r + 1 < nrow && pre[r + 1] <= x) ++r;
+        const int* ro = offs + r * (kSeedDiags + 1);
+        const int n = ro[0] + (x - pre[r]);
+        int dd = 0;
+        while (dd + 1 < nd && ro[dd + 1] <= n) ++dd;   // the cell that owns record n
+        const int i = i0 + r, d = d0 + dd;
+        const bool on = i + d <= L && (v.q.ubits(i, d) & UB_L);
+        const LoopItem it = items[n];
+        s_row[xs] = (int)v.out.cidx(ST_E, it.j - it.i, it.i, 0);
+        s_row[kSeedCap + xs] = (int)v.in.cidx(ST_P, it.l - it.k, it.k, 0);
+        s_row[2 * kSeedCap + xs] = (int)(role == 1 ? v.in.cidx(ST_L, it.j - it.l, it.l, 0) : v.in.cidx(ST_L, it.k - it.i, it.i, 0));
+        s_row[3 * kSeedCap + xs] = on ? (r * kSeedDiags + dd) * HD : -1;
+        s_xw[xs] = lin_weight(v.m.lambda[0], it.tsc);
+        s_xw[kSeedCap + xs] = lin_weight(v.m.lambda[1], it.tsc);
+      }
+      __syncthreads();
+      // lane = (record, tuple): three gathers and one add into the cell's sums
+      for (int w = tid; w < np * nq; w += kBT) {
+        const int xs = div_rcp(w, rcp_nq), t = w - xs * nq;
+        const int cell = s_row[3 * kSeedCap + xs];
+        const int qa = tq[2 * t], qb = tq[2 * t + 1];
+        if (cell < 0 || (qb & (4 << 16))) continue;
+        const double x0 = OB[(uint32_t)s_row[xs] + (qa & 0xff)], x1 = IB[(uint32_t)s_row[kSeedCap + xs] + ((qa >> 8) & 0xff)];
+        const double x2 = IB[(uint32_t)s_row[2 * kSeedCap + xs] + ((qa >> 16) & 0xff)];
+        const double term = loop_outside_seed_term(x0, x1, x2, s_xw[((qb >> 16) & 1) * kSeedCap + xs]);
+        if (term != 0.) atomicAdd(&acc[cell + (qb & 0xffff)], term);
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  const int run = kSeedRows * rs;
+  for (int t = tid; t < nd * run; t += kBT) {
+    const int dd = t / run, e = t - dd * run, r = e / rs, c = e - r * rs, d = d0 + dd;
+    if (i0 + r + d > L) continue;   // (the rows i0 .. of a diagonal: one contiguous run of the table)
+    const int k = c < kLoopColsMax ? cmap[c] : -1;
+    v.out.band[v.out.cidx(ST_L, d, i0, 0) + e] = k >= 0 ? acc[(r * kSeedDiags + dd) * HD + k] : 0.;
+  }
+}
+
+// k4_out_loops, the mirror of k4_in_loops: d from W down to 0 per row.  Lane = (row, L column) -- the lanes of a workgroup are the
+// entries of one contiguous run of every diagonal's L rows, so the seed, the inside L entry and the parent row are read in whole
+// lines; the row of the step above stays in LDS.  out L is not written back: nothing reads it behind this kernel (the seeds stay).
+static size_t loop_chain_lds(const AutomatonLayout& A) {
+  return sizeof(double) * (2 * (size_t)kBT + 5 * (size_t)A.n_wr + 2 * (size_t)A.n_theta + 4) + sizeof(int32_t) * kLoopColsMax * (kLoopProgW + 1);
+}
+__global__ __launch_bounds__(kBT) void k4_out_loops(LinArgs a) {
+  extern __shared__ double lds[];
+  LViews v(a.lay);
+  make_lviews(a, blockIdx.y, v);
+  const LPass pi = lpass(a, v);
+  if (pi.skip) return;
+  const AutomatonLayout& A = a.lay;
+  const int tid = threadIdx.x, L = v.q.L, W = v.q.W, nt = A.n_theta;
+  const int rs = v.out.rs[ST_L], R = kBT / rs;
+  const int i0 = blockIdx.x * R;
+  if (i0 > L) return;
+  double* cur = lds;
+  double* prev = lds + kBT;
+  double* wr = lds + 2 * kBT;
+  double* l_en = wr + 5 * A.n_wr;
+  int32_t* prog = reinterpret_cast<int32_t*>(l_en + 2 * nt + 4);
+  int32_t* pst = prog + kLoopColsMax * kLoopProgW;   // the state that owns the column
+  for (int t = tid; t < kLoopColsMax * (kLoopProgW + 1); t += kBT) prog[t] = 0;
+  for (int t = tid; t < 5 * A.n_wr; t += kBT) wr[t] = a.lin[A.lin_wr + t];
+  for (int t = tid; t < 2 * nt + 4; t += kBT) l_en[t] = 0.;
+  cur[tid] = 0.; prev[tid] = 0.;
+  __syncthreads();
+  for (int k = tid; k < A.n_lane; k += kBT) {
+    const int s = a.ints[A.f_live_out + k];
+    const int32_t* P = a.ints + A.fp_out + s * kFastW;
+    const int c = fcol(P[2], 2);
+    if (c >= 0 && c < kLoopColsMax) {
+      for (int w = 0; w < kLoopProgW; ++w) prog[c * kLoopProgW + w] = P[w];
+      pst[c] = s;
+    }
+  }
+  __syncthreads();
+  const int r = tid / rs, c = tid - r * rs, i = i0 + r;
+  const int32_t* P = prog + (r < R ? c : 0) * kLoopProgW;
+  const int w0 = P[0];
+  const bool have = r < R && i <= L && (w0 & 1);   // (a column without a loop state: zeros)
+  const bool w1 = pi.merged && pst[r < R ? c : 0] == A.shadow;
+  const int kl = (w0 >> 2) & 1, cEo = fcol(P[1], 1), ehs = v.m.lam_same ? 0 : kl;
+  const double invZ = w1 ? pi.invZs : pi.invZ;
+  LinSink sink;
+  sink.world = w1 ? 1 : 0;
+  sink.en_ = l_en + (w1 ? nt : 0);
+  sink.eh0 = sink.eh1 = 0.;
+  const int dmax = (W < L - i0) ? W : L - i0;   // (uniform: the first row of the workgroup is its longest)
+  // (the operands that do not hang on the chain are loaded a step ahead)
+  auto cell_on = [&](int d) { return have && d >= 0 && i + d <= L && (v.q.ubits(i, d) & UB_L); };
+  bool on_n = cell_on(dmax);
+  double inL_n = on_n ? v.in.band[v.in.cidx(ST_L, dmax, i, c)] : 0., HL_n = on_n ? v.out.band[v.out.cidx(ST_L, dmax, i, c)] : 0.;
+  for (int d = dmax; d >= 0; --d) {
+    double oL = 0.;
+    const bool on = on_n;
+    const double inL = inL_n, HL = HL_n;
+    on_n = cell_on(d - 1);
+    inL_n = on_n ? v.in.band[v.in.cidx(ST_L, d - 1, i, c)] : 0.;
+    HL_n = on_n ? v.out.band[v.out.cidx(ST_L, d - 1, i, c)] : 0.;
+    if (on) {
+      if (inL != 0.) {
+        const int j = i + d;
+        const bool eok = v.q.e_ok(i, d), doL = j < L && d + 1 <= W;
+        const int c_up = eok ? v.q.cell(i - 1, d + 2) : v.q.cell(i, d);
+        const double oE = (eok && cEo >= 0) ? v.out.band[v.out.cidx(ST_E, d, i, cEo)] : 0.;
+        const double xhp = eok ? xw_cell(v.q, kl, XT_HP, c_up) : 0.;
+        oL = loop_outside_entry<kFastR>(P, v.m.big, A.fe_r, wr, prev + r * rs, inL, HL, oE, xhp, v.q.e_hp[c_up], doL, j < L ? (int)v.q.seq[j] : 0,
+                                        v.q.ews[j < L ? j : L], invZ, ehs, v.m.no_prf != 0, sink);
+      }
+    }
+    cur[tid] = oL;
+    __syncthreads();   // (one barrier per step, as in k4_in_loops)
+    double* x = cur; cur = prev; prev = x;
+  }
+  lflush(a, v, pi, sink, l_en, kBT, (int)blockIdx.x);
 }
 
 // Final statistics of a sequence from those of its two outside passes (see k3_combine in train_kernels.hip):
@@ -2390,6 +2584,23 @@ static void launch_k4_in(const LinArgs& a, dim3 grid, size_t lds, bool fast, boo
 }
 template <int MODE>
 static void launch_k4_out(const LinArgs& a, dim3 grid, size_t lds, bool fast, bool big, hipStream_t st) {
+  if (MODE == OUT_TRAIN && fast && a.loop_post) {   // the train forms in front of the L kernels, with the plan's (inside) lists or without
+    const bool l = a.p.blocks != nullptr;
+    switch (k4_form(a, lds, 6, fast, big)) {
+      case K4_FP2_WAVES:
+        if (l) hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2, true, true, true>), grid, dim3(kBT), lds, st, a);
+        else hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2, true, false, true>), grid, dim3(kBT), lds, st, a);
+        return;
+      case K4_FP2:
+        if (l) hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2, false, true, true>), grid, dim3(kBT), lds, st, a);
+        else hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2, false, false, true>), grid, dim3(kBT), lds, st, a);
+        return;
+      default:
+        if (l) hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, kFastP, false, true, true>), grid, dim3(kBT), lds, st, a);
+        else hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, kFastP, false, false, true>), grid, dim3(kBT), lds, st, a);
+        return;
+    }
+  }
   if (MODE == OUT_TRAIN && fast && a.p.blocks) {   // the train forms that take the plan's lists
     switch (k4_form(a, lds, 6, fast, big)) {
       case K4_FP2_WAVES: hipLaunchKernelGGL((k4_out<OUT_TRAIN, true, true, 2, true, true>), grid, dim3(kBT), lds, st, a); return;
@@ -2460,6 +2671,31 @@ bool lin_loop_prepass_ok(const AutomatonLayout& A, const int32_t* ints, int min_
   }
   return true;
 }
+// The L kernels behind the outside sweep (k4_out_seed / k4_out_loops) fit this automaton: their LDS, a row of the L plane within a
+// chain workgroup, and -- they map L columns to states through the OUTSIDE programs -- every loop state's L column there unique and
+// the one of its inside program, which lin_loop_prepass_ok has looked at.
+static bool loop_outside_lds_ok(const AutomatonLayout& A) {
+  return A.tab_rs[ST_L] >= 1 && A.tab_rs[ST_L] <= kLoopColsMax && kBT / A.tab_rs[ST_L] >= 1 && loop_seed_lds(A) <= 64 * 1024 && loop_chain_lds(A) <= 64 * 1024;
+}
+bool lin_loop_outside_ok(const AutomatonLayout& A, const int32_t* ints) {
+  const bool say = getenv("ELEMDP_PLAN_DEBUG") != nullptr;
+  if (!A.fp_ok || !loop_outside_lds_ok(A)) {
+    if (say) fprintf(stderr, "L kernels behind the outside sweep: not for this automaton (fp_ok %d, L row of %d columns, LDS %zu / %zu)\n", A.fp_ok, A.tab_rs[ST_L], loop_seed_lds(A), loop_chain_lds(A));
+    return false;
+  }
+  auto col = [](int packed, int byte) { const int c = (packed >> (8 * byte)) & 0xff; return c == 0xff ? -1 : c; };
+  unsigned seen = 0;
+  for (int k = 0; k < A.n_lane; ++k) {
+    const int s = ints[A.f_live_out + k];
+    const int c = col(ints[A.fp_out + s * kFastW + 2], 2), ci = col(ints[A.fp_in + s * kFastW + 2], 2);
+    if (c != ci || (c >= 0 && (c >= A.tab_rs[ST_L] || ((seen >> c) & 1u)))) {
+      if (say) fprintf(stderr, "L kernels behind the outside sweep: not for this automaton (state %d: L column %d outside, %d inside)\n", s, c, ci);
+      return false;
+    }
+    if (c >= 0) seen |= 1u << c;
+  }
+  return true;
+}
 static GroupGeom group_geometry(const LinArgs& full, int G, int Lmax, int Wmax, bool scan) {
   GroupGeom g;
   LinArgs& a = g.a;
@@ -2484,6 +2720,12 @@ static GroupGeom group_geometry(const LinArgs& full, int G, int Lmax, int Wmax, 
   // the loop pre-pass: where the table-driven train form runs with the mask (the deterministic mode included: L enters no heavy sum)
   if (scan || !fast || !a.p.useful) a.loop_pre = 0;
   if (a.loop_pre && a.p.blocks && (!a.p.blocks_in || !a.blk_grid_in)) a.loop_pre = 0;
+  // the outside L plane behind the sweep: the same forms, but not the deterministic mode (its statistics follow the block order)
+  if (scan || !fast || !a.p.useful || a.det) a.loop_post = 0;
+  if (a.loop_post && a.p.blocks && (!a.p.blocks_in || !a.blk_grid_in)) a.loop_post = 0;
+  // (lin_loop_prepass_ok looked at the inside programs and the pre-pass's LDS: the L kernels map the columns of the outside
+  // programs and have LDS needs of their own -- where they do not fit, the sweep computes L itself)
+  if (a.loop_post && !loop_outside_lds_ok(a.lay)) a.loop_post = 0;
   const int sp = a.live_span > a.cpb ? a.live_span : a.cpb;   // cells a workgroup's window spans
   g.win = sp + Wmax + 3;
   g.lds_in = block_lds(2 * a.cpb * g.hd + kRecIn, a.cpb, a.n_lin, g.win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0, sp).total;
@@ -2535,13 +2777,24 @@ template <int MODE>
 static void outside_bands(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t st) {
   LinArgs& a = g.a;
   hipLaunchKernelGGL(k4_r7, dim3(((Lmax + 1) * (Wmax + 1) + kThreads - 1) / kThreads, G), dim3(kThreads), 0, st, a);
-  for (int d = Wmax; d >= 0; --d) {
+  // the L plane behind the sweep (train, table-driven, mask): the diagonals down to the first one that can hold an entry outside
+  // the L plane, each with the inside set of lists and its own choice per diagonal, then the seed and chain kernels of the L plane
+  const bool post = MODE == OUT_TRAIN && g.fast && a.loop_post;
+  LinArgs ao = a;
+  if (!post) ao.loop_post = 0;
+  if (post && a.p.blocks) { ao.p.blocks = a.p.blocks_in; ao.blk_grid = a.blk_grid_in; }
+  for (int d = Wmax; d >= (post ? a.in_d0 : 0); --d) {
     const int ncell = Lmax - d + 1;
     if (ncell <= 0) continue;
-    LinArgs ad = a;
+    LinArgs ad = ao;
     ad.d = d;
     const unsigned gx = band_blocks(ad, ncell, MODE == OUT_TRAIN);
     launch_k4_out<MODE>(ad, dim3(gx, G), g.lds_out, g.fast, g.big, st);
+  }
+  if (post) {
+    hipLaunchKernelGGL(k4_out_seed, dim3((Lmax + kSeedRows) / kSeedRows, G, (Wmax + kSeedDiags) / kSeedDiags), dim3(kBT), loop_seed_lds(a.lay), st, a);
+    const int rows = kBT / a.lay.tab_rs[ST_L];
+    hipLaunchKernelGGL(k4_out_loops, dim3((Lmax + rows) / rows, G), dim3(kBT), loop_chain_lds(a.lay), st, a);
   }
 }
 // an unconstrained or constrained sum pass of the scan: inside sweep, exterior chain outwards, outside band sweep
@@ -2589,6 +2842,7 @@ hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool
     fprintf(stderr, "lin group: G %d cpb %d fast %d n_lin %d staged ints in/out %d/%d lds k4_in %zu k4_out %zu fp_max_p %d forms k4_in %s k4_out %s stage_ext %d ext_nt %d ext_ring %d n_pass %d combine %d\n", G, a.cpb, (int)g.fast, a.n_lin, staged_ints(a.lay, a.n_stage, 0), staged_ints(a.lay, a.n_stage, 1), g.lds_in, g.lds_out, a.lay.fp_max_p,
             a.no_rss ? "none" : kK4FormName[k4_form(a, g.lds_in, 8, g.fast, g.big)], a.no_rss ? "none" : !stats ? "nostat" : kK4FormName[k4_form(a, g.lds_out, 6, g.fast, g.big)],
             (int)g.stage_ext, g.stage_ext ? g.ext_nt : 128, a.ext_ring, n_pass, (int)combine);
+    fprintf(stderr, "lin group: loop_prepass %d loop_outside %d (k4_out_seed lds %zu, k4_out_loops lds %zu)\n", a.loop_pre, a.loop_post, loop_seed_lds(a.lay), loop_chain_lds(a.lay));
   }
   for (int pass = 0; pass < n_pass; ++pass) {
     GroupGeom gp = g;

@@ -17,12 +17,12 @@ def short(n):
     return n.split("<")[0].split("(")[0].strip()
 
 
-def form(n):   # the form of the train kernels: sixth template argument = lists, seventh (k4_in) = behind the loop pre-pass
-    if "<" not in n:
+def form(n):   # the form of the train kernels: sixth template argument = lists, seventh = behind the loop pre-pass (k4_in) / in
+    if "<" not in n:   # front of the L kernels (k4_out)
         return ""
     args = n[n.index("<") + 1:n.rindex(">")].replace(" ", "").split(",")
     on = lambda k: len(args) > k and args[k] in ("true", "1")
-    return ("lists" if on(5) else "consecutive") + (" behind the pre-pass" if on(6) else "")
+    return ("lists" if on(5) else "consecutive") + ((" without L" if "k4_out" in n else " behind the pre-pass") if on(6) else "")
 
 
 def load(d):
