@@ -295,7 +295,7 @@ struct LinArgs {
   // diagonal with an entry outside the L plane (first_inside_diagonal); blk_grid_in = blk_grid of the inside set (p.blocks_in)
   int32_t loop_pre = 0, in_d0 = 0;
   const int32_t* blk_grid_in = nullptr;
-  // the outside L plane behind the sweep (option loop_outside; k4_out_seed / k4_out_loops): 1 = the outside sweep of the table-driven
+  // the outside L plane behind the sweep (option loop_outside; k4_out_lrows): 1 = the outside sweep of the table-driven
   // train form computes and stores no L, takes the inside set of lists and starts no diagonal below in_d0 (the engine sets it where
   // loop_pre could be set and the mode is not the deterministic one)
   int32_t loop_post = 0;

@@ -243,7 +243,7 @@ ELEMDP_HD bool fast_scan_stat(Sink& sink, int sf, int kl, int kr, bool yl, bool 
 // (heavy sums H1, H2, HP, HL of the target at ph[0], ph[CS], ph[2 CS], ph[3 CS] in LDS: read where they are used)
 // MODE: OUT_TRAIN (expected counts + energy statistics), OUT_SCAN (counts + start / inner posteriors), OUT_END (end posteriors
 // under the start constraint: CF_YL / CF_YR / CF_JLAST in fl); FS = the ScanFlag words of the scan modes.
-// LPOST: the L plane of the outside table is made behind the sweep (option loop_outside: k4_out_seed / k4_out_loops with
+// LPOST: the L plane of the outside table is made behind the sweep (option loop_outside: k4_out_lrows with
 // loop_outside_entry below) -- nothing in the sweep reads an outside L entry but the L chain itself, so no inside L and no parent
 // L is loaded here, no L <- L count, no 6b statistic and no HL is taken, and no L is stored
 template <int kFR, int kFP, int kFL, int MODE, bool LPOST = false, class Sink>
@@ -439,6 +439,38 @@ ELEMDP_HD double loop_outside_entry(const int32_t* P, const int32_t* G, int fe_r
   const double t6b = oE * xhp, z = t6b * inLz;
   if (z != 0.) sink.eh(ehs, e_hp * z);
   return t6b + sL + HL;
+}
+
+// The same entry in two parts, for the kernel that keeps the seeds of a tile in LDS (k4_out_lrows): the cell part hangs on the cell
+// alone, the chain part on the row of the step before.  oL = inL != 0 ? (t6b + HL) + sL : 0 where loop_outside_entry (and the sweep)
+// have (t6b + sL) + HL: a last-bit difference in sums whose terms are atomics already.
+// loop_outside_cell: the 6b term of a cell with inL != 0 and its energy statistic; the caller adds the return value to the seed.
+template <class Sink>
+ELEMDP_HD double loop_outside_cell(double inL, double oE, double xhp, double e_hp, double invZ, int ehs, Sink& sink) {
+  const double t6b = oE * xhp, z = t6b * (inL * invZ);
+  if (z != 0.) sink.eh(ehs, e_hp * z);
+  return t6b;
+}
+// loop_outside_chain: sL of an entry with inL != 0 and doL, with the right-emission counts.  P = the state's outside program, enr /
+// fr = the words G[fe_r + 2 id], G[fe_r + 2 id + 1] of its right transitions (they hang on the state alone: loaded once),
+// parent = the outside L row of (i, d + 1) by column.
+template <int kFR, class Sink>
+ELEMDP_HD double loop_outside_chain(const int32_t* P, const int* enr, const int* fr, const double* wr, const double* parent, double inL,
+                                    int br, double ews_r, double invZ, bool no_prf, Sink& sink) {
+  const int nRR = (P[0] >> 8) & 15;
+  const double inLz = inL * invZ;
+  double sL = 0.;
+#pragma unroll
+  for (int u = 0; u < kFR; ++u)
+    if (u < nRR) {
+      const int e = P[4 + u], c = fcol(e, 1), id = (e >> 16) & 0x7fff;
+      const double w = wr[5 * id + br] * ((fr[u] & 1) ? ews_r : 1.);
+      const double tL = (e < 0 && c >= 0) ? parent[c] * w : 0.;   // (sign bit: the parent is a loop state)
+      const double z = tL * inLz;
+      if (!no_prf && z != 0. && br) sink.en(enr[u] + br, z);
+      sL += tL;
+    }
+  return sL;
 }
 
 }  // namespace elemdp

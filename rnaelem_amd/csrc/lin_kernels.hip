@@ -1487,7 +1487,7 @@ __global__ __launch_bounds__(kThreads) void k4_r7(LinArgs a) {
 
 // ---- outside, diagonal d: dynamic LDS = 4 * cpb * S + n_theta + 2 doubles
 // W6: asked for six waves per SIMD (80 registers, a few spilled dwords) -- taken by the launcher where six workgroups fit the LDS
-// LPOST: the train form in front of k4_out_seed / k4_out_loops (option loop_outside), which make the L plane of the outside table
+// LPOST: the train form in front of k4_out_lrows (option loop_outside), which makes the L plane of the outside table
 // and its statistics behind the sweep: no L is computed or stored here, the item phase has role 0 alone, the zeros of dead cells
 // leave the L rows alone, and a cell is live by its bits other than UB_L (LISTS: the plan's second set of lists, as behind LPRE)
 template <int MODE, bool BIG, bool FAST = false, int FP = kFastP, bool W6 = false, bool LISTS = false, bool LPOST = false>
@@ -1997,190 +1997,259 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
 
 // ---- the outside L plane behind the sweep (option loop_outside; the table-driven train form under the mask, not the deterministic
 // mode).  Nothing in the outside sweep reads an outside L entry except the L chain itself, so everything that consumes out L runs
-// behind the sweep, where out E, in P and in L are complete and no diagonal order binds it: k4_out_seed sums the heavy sum HL of
-// rule 6c (roles 1 and 2 of the item records) into the cells' out L rows, k4_out_loops runs the chain L <- L down the rows with the
-// 6b statistic and the right-emission counts (loop_outside_entry, lin_fast.h).
-// k4_out_seed: a workgroup takes kSeedRows rows x kSeedDiags diagonals.  The role records of a row's cells (cell index i * (W + 1)
-// + d) are one run of the CSR arrays.  kSeedCap records at a time are staged in LDS, one lane each (the rows of the three operands,
-// both weights, the slot of the cell's sums); then lane = (record, tuple): three gathers and one LDS add.  Every entry of the tile
-// has this one writer: sums in LDS, then plain stores of every entry of the L rows -- zeros where a cell has no record or no UB_L
-// bit.  The LDS (the tile's sums, n_lane doubles per cell, + the staged records) bounds the residency: 5 workgroups per CU on the
-// bench model.
-constexpr int kSeedRows = 8, kSeedDiags = 17, kSeedCap = 256;   // (kSeedCap: records staged at a time)
-static size_t loop_seed_lds(const AutomatonLayout& A) {
-  return sizeof(double) * ((size_t)kSeedRows * kSeedDiags * A.n_lane + 2 * kSeedCap) +
-         sizeof(int32_t) * (kSeedRows * (kSeedDiags + 1) + kSeedRows + 1 + kLoopColsMax + 4 * kSeedCap + 2 * (size_t)A.n_quad);
+// behind the sweep, where out E, in P and in L are complete and no diagonal order binds it -- in one kernel, k4_out_lrows, which
+// stores no L entry at all (the out L rows keep whatever they held).  A workgroup owns R consecutive rows of a sequence and walks
+// their diagonals in tiles of kRowsT, from min(W, L - i0) down to 0; the tile's entries live in LDS, [row][diagonal + 1][L column].
+// Per tile:
+//   cells   lane = (row, L column), the tile's diagonals unrolled: every operand that does not hang on the chain.  in L stays in the
+//           lane's registers; where the cell is an E cell, t6b = out E * xhp (6b) opens the entry's sum and its energy statistic goes to
+//           the lane's (loop_outside_cell, lin_fast.h).  All loads are selects on the address, none waits for another but through
+//           the mask byte and the pair mask: two round trips per tile.
+//   seeds   the heavy sum HL of rule 6c (roles 1 and 2 of the item records) is added to the entries.  The role records of a row's
+//           cells (cell index i * (W + 1) + d) are one run of the CSR arrays; the runs of both roles form one list, of which kSeedCap
+//           records at a time are staged in LDS, one lane each (the rows of the three operands, both weights, the cell's entries);
+//           then lane = (record, tuple): three gathers and one LDS add, kSeedBatch of them per lane with all loads first (2: 26.9 ms
+//           per evaluation of the bench against 29.4 at 1; 4 costs a resident workgroup in registers: 30.2).  The records of d = 0
+//           are left out, as in k4_out; a cell without UB_L takes none.  What hangs on the tile alone -- the CSR offsets, the
+//           records in front of every run (a scan in wave 0 over the runs' ends), base and weight of j -- is loaded at once.
+//   chain   lane = (row, L column), d downwards in place over the entries (loop_outside_chain): one barrier per step and no global
+//           load.  The parent row is the entry above in the tile; above the tile's top it is the last row of the tile before,
+//           which its lane carries in a register into slot nd.
+// R = kBT / (columns of an L row), so that every lane has a chain entry (at most kRowsMax, which bounds the run tables).  kRowsT = 8:
+// on the bench model (16 columns, R = 16) 18 KB of entries + 8 KB of staged records + 3 KB of tables and statistics, 5 workgroups
+// = 20 of 32 waves per CU, what the two kernels this one replaces kept; 17 diagonals per tile would leave 3.  Block ids go through
+// swizzled_block: the row blocks of a sequence share the L2 that holds its out E / in P / in L rows.
+constexpr int kRowsT = 8, kRowsMax = 32, kSeedCap = 256, kSeedBatch = 2;   // (kSeedCap: records staged at a time)
+static_assert(2 * kRowsMax <= 64, "the runs of a tile are scanned by one wave");
+__host__ __device__ inline int loop_rows_r(int rs) { const int r = kBT / (rs > 0 ? rs : 1); return r < kRowsMax ? r : kRowsMax; }
+static size_t loop_rows_lds(const AutomatonLayout& A) {
+  const size_t rs = A.tab_rs[ST_L], R = loop_rows_r(A.tab_rs[ST_L]);
+  return sizeof(double) * (R * (kRowsT + 1) * rs + 2 * kSeedCap + (R + kRowsT) + 5 * (size_t)A.n_wr + 2 * (size_t)A.n_theta + 4) +
+         sizeof(int32_t) * (2 * R * (kRowsT + 1) + 2 * R + 1 + 4 * kSeedCap + 4 * (size_t)A.n_quad + (size_t)A.n_lane + kLoopColsMax * (kLoopProgW + 1) + (R + kRowsT));
 }
-__global__ __launch_bounds__(kBT) void k4_out_seed(LinArgs a) {
+__global__ __launch_bounds__(kBT) void k4_out_lrows(LinArgs a) {
   extern __shared__ double lds[];
+  unsigned bx, by;
+  swizzled_block(bx, by);
   LViews v(a.lay);
-  make_lviews(a, blockIdx.y, v);
-  if (v.row[4] != 0.) return;   // (a skipped sequence: lpass)
-  const AutomatonLayout& A = a.lay;
-  const int tid = threadIdx.x, L = v.q.L, W = v.q.W;
-  const int i0 = blockIdx.x * kSeedRows, d0 = blockIdx.z * kSeedDiags;
-  if (d0 > W || i0 + d0 > L) return;
-  const int nrow = (kSeedRows < L - i0 + 1) ? kSeedRows : L - i0 + 1, nd = (kSeedDiags < W - d0 + 1) ? kSeedDiags : W - d0 + 1;
-  const int HD = A.n_lane, nq = A.n_quad, rs = v.out.rs[ST_L];
-  double* acc = lds;                                                   // [row][diagonal][lane of the unary phase]
-  double* s_xw = acc + kSeedRows * kSeedDiags * HD;                    // staged records: exp(lambda_k tsc) [k][record],
-  int* offs = reinterpret_cast<int*>(s_xw + 2 * kSeedCap);             // [row][diagonal + 1]: CSR offsets of the role
-  int* pre = offs + kSeedRows * (kSeedDiags + 1);                     // [row + 1]: records of the rows before
-  int* cmap = pre + kSeedRows + 1;                                    // L column -> lane
-  int* s_row = cmap + kLoopColsMax;                                   // ... the rows of their three operands and the cell's sums [4][record]
-  int* tq = s_row + 4 * kSeedCap;                                     // the column records of the role's tuples
-  for (int t = tid; t < kSeedRows * kSeedDiags * HD; t += kBT) acc[t] = 0.;
-  if (tid < kLoopColsMax) cmap[tid] = -1;
-  __syncthreads();
-  for (int k = tid; k < HD; k += kBT) {
-    const int c = fcol(a.ints[A.fp_out + a.ints[A.f_live_out + k] * kFastW + 2], 2);
-    if (c >= 0 && c < kLoopColsMax) cmap[c] = k;
-  }
-  const int32_t* G = v.m.big;
-  const double* IB = v.in.band;
-  const double* OB = v.out.band;
-  const float rcp_nq = 1.0f / (float)(nq > 0 ? nq : 1);
-  for (int role = 1; role <= 2; ++role) {
-    const int32_t* off = role == 1 ? v.q.by_left_off : v.q.by_right_off;
-    const LoopItem* items = role == 1 ? v.q.items_left : v.q.items_right;
-    __syncthreads();
-    // (no loop sums on the diagonal d = 0, as in k4_out: the records of its cells are left out of the row's run)
-    for (int t = tid; t < nrow * (nd + 1); t += kBT) {
-      const int r = t / (nd + 1), dd = t - r * (nd + 1), d = d0 + dd;
-      offs[r * (kSeedDiags + 1) + dd] = nq > 0 ? off[v.q.cell(i0 + r, d > 0 ? d : 1)] : 0;
-    }
-    for (int t = tid; t < 2 * nq; t += kBT) tq[t] = G[A.fqc_out + role * 2 * nq + t];
-    __syncthreads();
-    if (tid == 0) {
-      int n = 0;
-      for (int r = 0; r < nrow; ++r) { pre[r] = n; n += offs[r * (kSeedDiags + 1) + nd] - offs[r * (kSeedDiags + 1)]; }
-      pre[nrow] = n;
-    }
-    __syncthreads();
-    const int n_rec = pre[nrow];
-    for (int p0 = 0; p0 < n_rec; p0 += kSeedCap) {
-      const int np = (kSeedCap < n_rec - p0) ? kSeedCap : n_rec - p0;
-      // one record per lane: its cell, the rows of its operands, its weights
-      for (int xs = tid; xs < np; xs += kBT) {
-        const int x = p0 + xs;
-        int r = 0;
-        while (r + 1 < nrow && pre[r + 1] <= x) ++r;
-        const int* ro = offs + r * (kSeedDiags + 1);
-        const int n = ro[0] + (x - pre[r]);
-        int dd = 0;
-        while (dd + 1 < nd && ro[dd + 1] <= n) ++dd;   // the cell that owns record n
-        const int i = i0 + r, d = d0 + dd;
-        const bool on = i + d <= L && (v.q.ubits(i, d) & UB_L);
-        const LoopItem it = items[n];
-        s_row[xs] = (int)v.out.cidx(ST_E, it.j - it.i, it.i, 0);
-        s_row[kSeedCap + xs] = (int)v.in.cidx(ST_P, it.l - it.k, it.k, 0);
-        s_row[2 * kSeedCap + xs] = (int)(role == 1 ? v.in.cidx(ST_L, it.j - it.l, it.l, 0) : v.in.cidx(ST_L, it.k - it.i, it.i, 0));
-        s_row[3 * kSeedCap + xs] = on ? (r * kSeedDiags + dd) * HD : -1;
-        s_xw[xs] = lin_weight(v.m.lambda[0], it.tsc);
-        s_xw[kSeedCap + xs] = lin_weight(v.m.lambda[1], it.tsc);
-      }
-      __syncthreads();
-      // lane = (record, tuple): three gathers and one add into the cell's sums
-      for (int w = tid; w < np * nq; w += kBT) {
-        const int xs = div_rcp(w, rcp_nq), t = w - xs * nq;
-        const int cell = s_row[3 * kSeedCap + xs];
-        const int qa = tq[2 * t], qb = tq[2 * t + 1];
-        if (cell < 0 || (qb & (4 << 16))) continue;
-        const double x0 = OB[(uint32_t)s_row[xs] + (qa & 0xff)], x1 = IB[(uint32_t)s_row[kSeedCap + xs] + ((qa >> 8) & 0xff)];
-        const double x2 = IB[(uint32_t)s_row[2 * kSeedCap + xs] + ((qa >> 16) & 0xff)];
-        const double term = loop_outside_seed_term(x0, x1, x2, s_xw[((qb >> 16) & 1) * kSeedCap + xs]);
-        if (term != 0.) atomicAdd(&acc[cell + (qb & 0xffff)], term);
-      }
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  const int run = kSeedRows * rs;
-  for (int t = tid; t < nd * run; t += kBT) {
-    const int dd = t / run, e = t - dd * run, r = e / rs, c = e - r * rs, d = d0 + dd;
-    if (i0 + r + d > L) continue;   // (the rows i0 .. of a diagonal: one contiguous run of the table)
-    const int k = c < kLoopColsMax ? cmap[c] : -1;
-    v.out.band[v.out.cidx(ST_L, d, i0, 0) + e] = k >= 0 ? acc[(r * kSeedDiags + dd) * HD + k] : 0.;
-  }
-}
-
-// k4_out_loops, the mirror of k4_in_loops: d from W down to 0 per row.  Lane = (row, L column) -- the lanes of a workgroup are the
-// entries of one contiguous run of every diagonal's L rows, so the seed, the inside L entry and the parent row are read in whole
-// lines; the row of the step above stays in LDS.  out L is not written back: nothing reads it behind this kernel (the seeds stay).
-static size_t loop_chain_lds(const AutomatonLayout& A) {
-  return sizeof(double) * (2 * (size_t)kBT + 5 * (size_t)A.n_wr + 2 * (size_t)A.n_theta + 4) + sizeof(int32_t) * kLoopColsMax * (kLoopProgW + 1);
-}
-__global__ __launch_bounds__(kBT) void k4_out_loops(LinArgs a) {
-  extern __shared__ double lds[];
-  LViews v(a.lay);
-  make_lviews(a, blockIdx.y, v);
+  make_lviews(a, by, v);
   const LPass pi = lpass(a, v);
   if (pi.skip) return;
   const AutomatonLayout& A = a.lay;
-  const int tid = threadIdx.x, L = v.q.L, W = v.q.W, nt = A.n_theta;
-  const int rs = v.out.rs[ST_L], R = kBT / rs;
-  const int i0 = blockIdx.x * R;
+  const int tid = threadIdx.x, L = v.q.L, W = v.q.W, nt = A.n_theta, nq = A.n_quad, HD = A.n_lane;
+  const int rs = v.out.rs[ST_L], R = loop_rows_r(rs), TS = (kRowsT + 1) * rs;   // (TS: the entries of a row)
+  const int i0 = bx * R;
   if (i0 > L) return;
-  double* cur = lds;
-  double* prev = lds + kBT;
-  double* wr = lds + 2 * kBT;
+  const int nrow = (R < L - i0 + 1) ? R : L - i0 + 1, nrr = 2 * nrow;           // (nrr: runs of records, [role][row])
+  double* acc = lds;                                                  // [row][diagonal of the tile, + the parent row][column]
+  double* s_xw = acc + R * TS;                                        // staged records: exp(lambda_k tsc) [k][record],
+  double* s_ew = s_xw + 2 * kSeedCap;                                 // position weight of j = i0 + d0 + . of the tile
+  double* wr = s_ew + R + kRowsT;
   double* l_en = wr + 5 * A.n_wr;
-  int32_t* prog = reinterpret_cast<int32_t*>(l_en + 2 * nt + 4);
-  int32_t* pst = prog + kLoopColsMax * kLoopProgW;   // the state that owns the column
+  int* offs = reinterpret_cast<int*>(l_en + 2 * nt + 4);              // [run][diagonal + 1]: CSR offsets of the role
+  int* pre = offs + 2 * R * (kRowsT + 1);                             // [run + 1]: records of the runs before
+  int* s_row = pre + 2 * R + 1;                                       // ... the rows of their three operands and the cell's entries [4][record]
+  int* tq = s_row + 4 * kSeedCap;                                     // the column records of the tuples [role][2 nq]
+  int* lcol = tq + 4 * nq;                                            // lane of the unary phase -> L column
+  int32_t* prog = lcol + HD;                                          // the outside program of the state that owns the column
+  int32_t* pst = prog + kLoopColsMax * kLoopProgW;                    // ... and that state
+  int* s_b = pst + kLoopColsMax;                                      // base of j = i0 + d0 + . of the tile
+  const int32_t* G = v.m.big;
   for (int t = tid; t < kLoopColsMax * (kLoopProgW + 1); t += kBT) prog[t] = 0;
   for (int t = tid; t < 5 * A.n_wr; t += kBT) wr[t] = a.lin[A.lin_wr + t];
   for (int t = tid; t < 2 * nt + 4; t += kBT) l_en[t] = 0.;
-  cur[tid] = 0.; prev[tid] = 0.;
+  for (int t = tid; t < 4 * nq; t += kBT) tq[t] = G[A.fqc_out + 2 * nq + t];   // (roles 1 and 2)
   __syncthreads();
-  for (int k = tid; k < A.n_lane; k += kBT) {
+  for (int k = tid; k < HD; k += kBT) {
     const int s = a.ints[A.f_live_out + k];
     const int32_t* P = a.ints + A.fp_out + s * kFastW;
     const int c = fcol(P[2], 2);
+    lcol[k] = (c >= 0 && c < rs) ? c : -1;
     if (c >= 0 && c < kLoopColsMax) {
       for (int w = 0; w < kLoopProgW; ++w) prog[c * kLoopProgW + w] = P[w];
       pst[c] = s;
     }
   }
   __syncthreads();
+  // the lane's chain entry: row r, column c
   const int r = tid / rs, c = tid - r * rs, i = i0 + r;
-  const int32_t* P = prog + (r < R ? c : 0) * kLoopProgW;
+  const bool lane = r < R;
+  const int32_t* P = prog + (lane ? c : 0) * kLoopProgW;
   const int w0 = P[0];
-  const bool have = r < R && i <= L && (w0 & 1);   // (a column without a loop state: zeros)
-  const bool w1 = pi.merged && pst[r < R ? c : 0] == A.shadow;
+  const bool have = lane && i <= L && (w0 & 1);   // (a column without a loop state: zeros)
+  const bool w1 = pi.merged && pst[lane ? c : 0] == A.shadow;
   const int kl = (w0 >> 2) & 1, cEo = fcol(P[1], 1), ehs = v.m.lam_same ? 0 : kl;
   const double invZ = w1 ? pi.invZs : pi.invZ;
+  int enr[kFastR], fr[kFastR];   // (the words of the right transitions hang on the state alone)
+#pragma unroll
+  for (int u = 0; u < kFastR; ++u) {
+    const bool on = u < ((w0 >> 8) & 15);
+    const int id = on ? (P[4 + u] >> 16) & 0x7fff : 0;
+    enr[u] = on ? G[A.fe_r + 2 * id] : 0;
+    fr[u] = on ? G[A.fe_r + 2 * id + 1] : 0;
+  }
   LinSink sink;
   sink.world = w1 ? 1 : 0;
   sink.en_ = l_en + (w1 ? nt : 0);
   sink.eh0 = sink.eh1 = 0.;
+  double* const row_e = acc + (lane ? r * TS + c : 0);   // the lane's entries: row_e[dd * rs]
+  const float rcp_nq = 1.0f / (float)(nq > 0 ? nq : 1);
+  const double* IB = v.in.band;
+  const double* OB = v.out.band;
   const int dmax = (W < L - i0) ? W : L - i0;   // (uniform: the first row of the workgroup is its longest)
-  // (the operands that do not hang on the chain are loaded a step ahead)
-  auto cell_on = [&](int d) { return have && d >= 0 && i + d <= L && (v.q.ubits(i, d) & UB_L); };
-  bool on_n = cell_on(dmax);
-  double inL_n = on_n ? v.in.band[v.in.cidx(ST_L, dmax, i, c)] : 0., HL_n = on_n ? v.out.band[v.out.cidx(ST_L, dmax, i, c)] : 0.;
-  for (int d = dmax; d >= 0; --d) {
-    double oL = 0.;
-    const bool on = on_n;
-    const double inL = inL_n, HL = HL_n;
-    on_n = cell_on(d - 1);
-    inL_n = on_n ? v.in.band[v.in.cidx(ST_L, d - 1, i, c)] : 0.;
-    HL_n = on_n ? v.out.band[v.out.cidx(ST_L, d - 1, i, c)] : 0.;
-    if (on) {
-      if (inL != 0.) {
-        const int j = i + d;
-        const bool eok = v.q.e_ok(i, d), doL = j < L && d + 1 <= W;
-        const int c_up = eok ? v.q.cell(i - 1, d + 2) : v.q.cell(i, d);
-        const double oE = (eok && cEo >= 0) ? v.out.band[v.out.cidx(ST_E, d, i, cEo)] : 0.;
-        const double xhp = eok ? xw_cell(v.q, kl, XT_HP, c_up) : 0.;
-        oL = loop_outside_entry<kFastR>(P, v.m.big, A.fe_r, wr, prev + r * rs, inL, HL, oE, xhp, v.q.e_hp[c_up], doL, j < L ? (int)v.q.seq[j] : 0,
-                                        v.q.ews[j < L ? j : L], invZ, ehs, v.m.no_prf != 0, sink);
+  double carry = 0.;
+  for (int dhi = dmax; dhi >= 0; dhi -= kRowsT) {
+    const int d0 = dhi >= kRowsT ? dhi - kRowsT + 1 : 0, nd = dhi - d0 + 1;
+    // ---- cells
+    double inL[kRowsT], t6[kRowsT];
+    {
+      int ub[kRowsT];
+      uint32_t pw[kRowsT];
+#pragma unroll
+      for (int dd = 0; dd < kRowsT; ++dd) {
+        const int d = d0 + dd;
+        const bool in = have && dd < nd && i + d <= L;
+        const bool up = in && i > 0 && d + 2 <= W && i + d + 1 <= L;   // (the bounds of pair_ok(i - 1, d + 2))
+        ub[dd] = v.q.ubits(in ? i : 0, in ? d : 0);
+        ub[dd] = in ? ub[dd] : 0;
+        pw[dd] = v.q.okbits[up ? (uint32_t)v.q.cell(i - 1, d + 2) >> 5 : 0u];
+        pw[dd] = up ? pw[dd] : 0u;
+      }
+#pragma unroll
+      for (int dd = 0; dd < kRowsT; ++dd) {
+        const int d = d0 + dd, c_up = v.q.cell(i - 1, d + 2);
+        const bool on = (ub[dd] & UB_L) != 0, eok = on && ((pw[dd] >> (c_up & 31)) & 1u);
+        inL[dd] = v.in.ldc(ST_L, d, i, c, on);
+        const double oE = v.out.ldc(ST_E, d, i, cEo, eok), xhp = xw_cell(v.q, kl, XT_HP, eok ? c_up : 0), ehp = v.q.e_hp[eok ? c_up : 0];
+        t6[dd] = 0.;
+        if (eok && inL[dd] != 0.) t6[dd] = loop_outside_cell(inL[dd], oE, xhp, ehp, invZ, ehs, sink);
       }
     }
-    cur[tid] = oL;
-    __syncthreads();   // (one barrier per step, as in k4_in_loops)
-    double* x = cur; cur = prev; prev = x;
+    if (lane) {
+#pragma unroll
+      for (int dd = 0; dd < kRowsT; ++dd) row_e[dd * rs] = dd == nd ? carry : t6[dd];
+      row_e[kRowsT * rs] = carry;
+    }
+    // ---- seeds.  The loads that hang on the tile alone, all at once: the CSR offsets of the runs' cells (no loop sums on the
+    // diagonal d = 0, as in k4_out: the records of its cells are left out of the row's run), the two ends of every run for the
+    // records of the runs before it (wave 0), base and position weight of j
+    {
+      constexpr int kOffU = (2 * kRowsMax * (kRowsT + 1) + kBT - 1) / kBT;
+      int ov[kOffU], os[kOffU];
+#pragma unroll
+      for (int u = 0; u < kOffU; ++u) {
+        const int t = tid + u * kBT;
+        const bool ok = t < nrr * (nd + 1) && nq > 0;
+        const int rr = ok ? div_small(t, nd + 1) : 0, dd = ok ? t - rr * (nd + 1) : 0, role = rr >= nrow, d = d0 + dd;
+        const int32_t* off = role ? v.q.by_right_off : v.q.by_left_off;
+        os[u] = t < nrr * (nd + 1) ? rr * (kRowsT + 1) + dd : -1;
+        ov[u] = off[ok ? v.q.cell(i0 + rr - role * nrow, d > 0 ? d : 1) : 0];
+        ov[u] = ok ? ov[u] : 0;
+      }
+      int lo = 0, hi = 0;
+      if (tid < 64) {
+        const bool ok = tid < nrr && nq > 0;
+        const int role = tid >= nrow, ri = i0 + tid - role * nrow;
+        const int32_t* off = role ? v.q.by_right_off : v.q.by_left_off;
+        lo = off[ok ? v.q.cell(ri, d0 > 0 ? d0 : 1) : 0];
+        hi = off[ok ? v.q.cell(ri, d0 + nd) : 0];
+        lo = ok ? lo : 0;
+        hi = ok ? hi : 0;
+      }
+      int jb = 0;
+      double jw = 0.;
+      if (tid < nrow + nd) {
+        const int j = i0 + d0 + tid;
+        jb = j < L ? (int)v.q.seq[j] : 0;
+        jw = v.q.ews[j < L ? j : L];
+      }
+#pragma unroll
+      for (int u = 0; u < kOffU; ++u)
+        if (os[u] >= 0) offs[os[u]] = ov[u];
+      if (tid < 64) {
+        int n = hi - lo;   // (inclusive scan over the wave)
+#pragma unroll
+        for (int sft = 1; sft < 64; sft <<= 1) {
+          const int up = __shfl_up(n, sft);
+          if (tid >= sft) n += up;
+        }
+        if (tid < nrr) pre[tid + 1] = n;
+        if (tid == 0) pre[0] = 0;
+      }
+      if (tid < nrow + nd) { s_b[tid] = jb; s_ew[tid] = jw; }
+    }
+    __syncthreads();
+    const int n_rec = pre[nrr];
+    for (int p0 = 0; p0 < n_rec; p0 += kSeedCap) {
+      const int np = (kSeedCap < n_rec - p0) ? kSeedCap : n_rec - p0;
+      // one record per lane: its cell, the rows of its operands, its weights
+      for (int xs = tid; xs < np; xs += kBT) {
+        const int x = p0 + xs;
+        int rr = 0;
+        while (rr + 1 < nrr && pre[rr + 1] <= x) ++rr;
+        const int* ro = offs + rr * (kRowsT + 1);
+        const int n = ro[0] + (x - pre[rr]);
+        int dd = 0;
+        while (dd + 1 < nd && ro[dd + 1] <= n) ++dd;   // the cell that owns record n
+        const int role = rr >= nrow, rw = rr - role * nrow, ri = i0 + rw, d = d0 + dd;
+        const bool on = ri + d <= L && (v.q.ubits(ri, d) & UB_L);
+        const LoopItem it = (role ? v.q.items_right : v.q.items_left)[n];
+        s_row[xs] = (int)v.out.cidx(ST_E, it.j - it.i, it.i, 0);
+        s_row[kSeedCap + xs] = (int)v.in.cidx(ST_P, it.l - it.k, it.k, 0);
+        s_row[2 * kSeedCap + xs] = (int)(role ? v.in.cidx(ST_L, it.k - it.i, it.i, 0) : v.in.cidx(ST_L, it.j - it.l, it.l, 0));
+        s_row[3 * kSeedCap + xs] = on ? 2 * (rw * TS + dd * rs) + role : -1;
+        s_xw[xs] = lin_weight(v.m.lambda[0], it.tsc);
+        s_xw[kSeedCap + xs] = lin_weight(v.m.lambda[1], it.tsc);
+      }
+      __syncthreads();
+      // lane = (record, tuple): three gathers and one add into the cell's entry -- kSeedBatch of them at a time, all loads first: a
+      // wave that waits for one triple at a time is bound by the round trip, not by bytes
+      for (int wb = tid; wb < np * nq; wb += kSeedBatch * kBT) {
+        double x0[kSeedBatch], x1[kSeedBatch], x2[kSeedBatch], xw[kSeedBatch];
+        int dst[kSeedBatch];
+#pragma unroll
+        for (int u = 0; u < kSeedBatch; ++u) {
+          const int w = wb + u * kBT;
+          const bool in = w < np * nq;
+          const int xs = in ? div_rcp(w, rcp_nq) : 0, t = in ? w - xs * nq : 0;
+          const int cell = s_row[3 * kSeedCap + xs];
+          const int32_t* q2 = tq + (cell & 1) * 2 * nq + 2 * t;
+          const int qa = q2[0], qb = q2[1], col = lcol[qb & 0xffff];
+          const bool ok = in && cell >= 0 && col >= 0 && !(qb & (4 << 16));
+          dst[u] = ok ? (cell >> 1) + col : -1;
+          x0[u] = OB[ok ? (uint32_t)s_row[xs] + (qa & 0xff) : 0u];
+          x1[u] = IB[ok ? (uint32_t)s_row[kSeedCap + xs] + ((qa >> 8) & 0xff) : 0u];
+          x2[u] = IB[ok ? (uint32_t)s_row[2 * kSeedCap + xs] + ((qa >> 16) & 0xff) : 0u];
+          xw[u] = s_xw[((qb >> 16) & 1) * kSeedCap + xs];
+        }
+#pragma unroll
+        for (int u = 0; u < kSeedBatch; ++u)
+          if (dst[u] >= 0) {
+            const double term = loop_outside_seed_term(x0[u], x1[u], x2[u], xw[u]);
+            if (term != 0.) atomicAdd(&acc[dst[u]], term);
+          }
+      }
+      __syncthreads();
+    }
+    // ---- chain
+    double oL = carry;
+#pragma unroll
+    for (int dd = kRowsT - 1; dd >= 0; --dd) {
+      if (dd >= nd) continue;   // (uniform)
+      oL = 0.;
+      if (inL[dd] != 0.) {
+        const int d = d0 + dd, j = i + d;
+        double sL = 0.;
+        if (j < L && d + 1 <= W)   // (the cell's CF_DOL flag)
+          sL = loop_outside_chain<kFastR>(P, enr, fr, wr, row_e + (dd + 1) * rs - c, inL[dd], s_b[r + dd], s_ew[r + dd], invZ, v.m.no_prf != 0, sink);
+        oL = row_e[dd * rs] + sL;
+      }
+      if (lane) row_e[dd * rs] = oL;
+      __syncthreads();   // (one barrier per step, as in k4_in_loops)
+    }
+    carry = oL;
   }
-  lflush(a, v, pi, sink, l_en, kBT, (int)blockIdx.x);
+  lflush(a, v, pi, sink, l_en, kBT, (int)bx);
 }
 
 // Final statistics of a sequence from those of its two outside passes (see k3_combine in train_kernels.hip):
@@ -2671,16 +2740,16 @@ bool lin_loop_prepass_ok(const AutomatonLayout& A, const int32_t* ints, int min_
   }
   return true;
 }
-// The L kernels behind the outside sweep (k4_out_seed / k4_out_loops) fit this automaton: their LDS, a row of the L plane within a
-// chain workgroup, and -- they map L columns to states through the OUTSIDE programs -- every loop state's L column there unique and
-// the one of its inside program, which lin_loop_prepass_ok has looked at.
+// The L kernel behind the outside sweep (k4_out_lrows) fits this automaton: its LDS, a row of the L plane within a workgroup, and
+// -- it maps L columns to states through the OUTSIDE programs -- every loop state's L column there unique and the one of its inside
+// program, which lin_loop_prepass_ok has looked at.
 static bool loop_outside_lds_ok(const AutomatonLayout& A) {
-  return A.tab_rs[ST_L] >= 1 && A.tab_rs[ST_L] <= kLoopColsMax && kBT / A.tab_rs[ST_L] >= 1 && loop_seed_lds(A) <= 64 * 1024 && loop_chain_lds(A) <= 64 * 1024;
+  return A.tab_rs[ST_L] >= 1 && A.tab_rs[ST_L] <= kLoopColsMax && A.tab_rs[ST_L] <= kBT && loop_rows_lds(A) <= 64 * 1024;
 }
 bool lin_loop_outside_ok(const AutomatonLayout& A, const int32_t* ints) {
   const bool say = getenv("ELEMDP_PLAN_DEBUG") != nullptr;
   if (!A.fp_ok || !loop_outside_lds_ok(A)) {
-    if (say) fprintf(stderr, "L kernels behind the outside sweep: not for this automaton (fp_ok %d, L row of %d columns, LDS %zu / %zu)\n", A.fp_ok, A.tab_rs[ST_L], loop_seed_lds(A), loop_chain_lds(A));
+    if (say) fprintf(stderr, "L kernel behind the outside sweep: not for this automaton (fp_ok %d, L row of %d columns, LDS %zu)\n", A.fp_ok, A.tab_rs[ST_L], loop_rows_lds(A));
     return false;
   }
   auto col = [](int packed, int byte) { const int c = (packed >> (8 * byte)) & 0xff; return c == 0xff ? -1 : c; };
@@ -2792,9 +2861,8 @@ static void outside_bands(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t s
     launch_k4_out<MODE>(ad, dim3(gx, G), g.lds_out, g.fast, g.big, st);
   }
   if (post) {
-    hipLaunchKernelGGL(k4_out_seed, dim3((Lmax + kSeedRows) / kSeedRows, G, (Wmax + kSeedDiags) / kSeedDiags), dim3(kBT), loop_seed_lds(a.lay), st, a);
-    const int rows = kBT / a.lay.tab_rs[ST_L];
-    hipLaunchKernelGGL(k4_out_loops, dim3((Lmax + rows) / rows, G), dim3(kBT), loop_chain_lds(a.lay), st, a);
+    const int rows = loop_rows_r(a.lay.tab_rs[ST_L]);
+    hipLaunchKernelGGL(k4_out_lrows, dim3((Lmax + rows) / rows, G), dim3(kBT), loop_rows_lds(a.lay), st, a);
   }
 }
 // an unconstrained or constrained sum pass of the scan: inside sweep, exterior chain outwards, outside band sweep
@@ -2842,7 +2910,7 @@ hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool
     fprintf(stderr, "lin group: G %d cpb %d fast %d n_lin %d staged ints in/out %d/%d lds k4_in %zu k4_out %zu fp_max_p %d forms k4_in %s k4_out %s stage_ext %d ext_nt %d ext_ring %d n_pass %d combine %d\n", G, a.cpb, (int)g.fast, a.n_lin, staged_ints(a.lay, a.n_stage, 0), staged_ints(a.lay, a.n_stage, 1), g.lds_in, g.lds_out, a.lay.fp_max_p,
             a.no_rss ? "none" : kK4FormName[k4_form(a, g.lds_in, 8, g.fast, g.big)], a.no_rss ? "none" : !stats ? "nostat" : kK4FormName[k4_form(a, g.lds_out, 6, g.fast, g.big)],
             (int)g.stage_ext, g.stage_ext ? g.ext_nt : 128, a.ext_ring, n_pass, (int)combine);
-    fprintf(stderr, "lin group: loop_prepass %d loop_outside %d (k4_out_seed lds %zu, k4_out_loops lds %zu)\n", a.loop_pre, a.loop_post, loop_seed_lds(a.lay), loop_chain_lds(a.lay));
+    fprintf(stderr, "lin group: loop_prepass %d loop_outside %d (k4_out_lrows lds %zu, %d rows x %d diagonals)\n", a.loop_pre, a.loop_post, loop_rows_lds(a.lay), loop_rows_r(a.lay.tab_rs[ST_L]), kRowsT);
   }
   for (int pass = 0; pass < n_pass; ++pass) {
     GroupGeom gp = g;
