@@ -271,6 +271,33 @@ int elemdp_sample(elemdp_handle* h, const double* x, int32_t n_param, int32_t n_
 /* Copies the list of the last elemdp_pair_posteriors / elemdp_pair_mea: seq (batch index), i, j (cell, j = i + d), p; any may be NULL.
  * cap < n_pairs is ELEMDP_EINVAL; before any elemdp_pair_posteriors (of the resident batch) ELEMDP_ESTATE. */
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap);
+/* Motif-conditional pair posteriors of the resident batch under the motif model x: the ensemble of
+ * elemdp_pair_posteriors is a mixture of the parses with the motif (terminals ari) and those without it (terminal nasi); this call
+ * gives the fold of each world on its own.  For every kept pair (i, j = i + d) of the BPP filter,
+ *   P_motif(i, j) = sum_s inside(i, j, P, s) * outside_ari (i, j, P, s) / Z(ari)
+ *   P_none (i, j) = sum_s inside(i, j, P, s) * outside_nasi(i, j, P, s) / Z(nasi)
+ * with the outside tables of one outside sweep per world, seeded with that world's terminals alone, over one inside sweep.
+ * Keeps on the device the pairs with max(P_motif, P_none) >= min_prob (min_prob >= 0; 0 = every kept pair; +inf keeps no list)
+ * in (sequence, i, j) order and returns their number in *n_pairs.  exist_prob: one value per sequence, Z(ari) / Z(ari, nasi).
+ * unpaired_motif, unpaired_none: seq_off indexing (L values per sequence), 1 - the world's P of the pairs base p takes part in.
+ * structure_motif, structure_none: seq_off indexing, L bytes '(' ')' '.' per sequence (no terminator), the maximum expected
+ * accuracy structure of elemdp_pair_mea over the world's P and unpaired; gamma is looked at only when one of them is given and
+ * must then be finite and > 0 (else ELEMDP_EINVAL).  shift: one value per sequence, the sum over the kept pairs of
+ * |P_motif - P_none| -- the expected number of base pairs that differ between the two folds, counted on marginals.  A world
+ * without any parse (Z = 0) is empty: P = 0, unpaired = 1, structure all '.', shift NaN, and exist_prob 0 (no parse with the
+ * motif, or none at all) or 1 (none without it).  Under ELEMDP_NO_RSS there are no pairs: empty list, unpaired 1, shift 0.
+ * Sequences for which one of Z(ari, nasi), Z(ari), Z(nasi) is non-zero and leaves the double range of the scaled-linear tables,
+ * and every sequence under option pipeline 3, go through the fused scan kernel in log space.  Any output but n_pairs may be
+ * NULL.  elemdp_last_timing afterwards: [whole call, sweeps + reductions + decodes, sequences handed to the log-space form].
+ * elemdp_scan, the pair, sample and profile calls (the list of the last elemdp_pair_posteriors included) and the train calls
+ * are unaffected. */
+int elemdp_pair_conditional(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double gamma,
+                            int64_t* n_pairs, double* exist_prob, double* unpaired_motif, double* unpaired_none,
+                            char* structure_motif, char* structure_none, double* shift);
+/* Copies the list of the last elemdp_pair_conditional: seq (batch index), i, j (cell, j = i + d), p_motif, p_none; any may be
+ * NULL.  cap < n_pairs is ELEMDP_EINVAL; before any elemdp_pair_conditional (of the resident batch) ELEMDP_ESTATE. */
+int elemdp_pair_conditional_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p_motif, double* p_none,
+                                 int64_t cap);
 /* Structural context profile of every position under the motif model x: profile[7 * (seq_off[n] + p) + c] is the
  * probability that base p (0-based) of sequence n has the rss letter c of "OLRHBIM" -- exterior, left or right base of a pair,
  * unpaired in a hairpin, bulge, interior or multi-branch loop -- over the ensemble of the scan's first sum pass (terminals ari and

@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_node_mea", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -95,6 +95,9 @@ def load_library():
         L.elemdp_node_profile.argtypes = [hp, dp, C.c_int32, dp]
         L.elemdp_node_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_int32, dp, u8, i32, i32, i32, dp, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
+        L.elemdp_pair_conditional.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int64), dp, dp, dp, C.c_char_p,
+                                              C.c_char_p, dp]
+        L.elemdp_pair_conditional_list.argtypes = [hp, i32, i32, i32, dp, dp, C.c_int64]
         L.elemdp_last_timing.argtypes = [hp, dp, C.c_int32]
         L.elemdp_epoch_permutation.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
         L.elemdp_kmer_shuffle.argtypes = [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
@@ -427,6 +430,40 @@ class Engine:
         raw = s.raw.decode("ascii")
         structs = [raw[int(off[k]):int(off[k + 1])] for k in range(self.n_seq)]
         return structs, sc[:self.n_seq].copy(), None if min_prob is None else self._pair_lists(m.value, unp)
+
+    # ---- motif-conditional pair posteriors
+    def conditional_pairs(self, x, min_prob=0.0, gamma=None):
+        """One record per sequence: the fold with the motif and the fold without it.  i, j: the cells (i, j = i + d) with
+        max(p_motif, p_none) >= min_prob in (i, j) order; p_motif, p_none: the probability that bases i and j-1 (0-based) pair
+        given a parse with the motif / without it; unpaired_motif, unpaired_none: per base; exist_prob = Z(ari) / Z(ari, nasi);
+        shift: the sum of |p_motif - p_none| over the kept pairs.  With gamma also structure_motif and structure_none, the
+        maximum expected accuracy structure of each world.  A world without any parse has p = 0, unpaired = 1, an open
+        structure and shift NaN."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        npos, ns = max(int(off[-1]), 1), max(self.n_seq, 1)
+        um, un = np.zeros(npos), np.zeros(npos)
+        ex, sh = np.zeros(ns), np.zeros(ns)
+        sm = C.create_string_buffer(npos) if gamma is not None else None
+        sn = C.create_string_buffer(npos) if gamma is not None else None
+        m = C.c_int64()
+        self._check(self._lib.elemdp_pair_conditional(self._h, _dp(x), self.n_param, float(min_prob), 0.0 if gamma is None else float(gamma),
+                                                      C.byref(m), _dp(ex), _dp(um), _dp(un), sm, sn, _dp(sh)))
+        n = m.value
+        seq, ii, jj = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
+        pm, pn = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        self._check(self._lib.elemdp_pair_conditional_list(self._h, _i32(seq), _i32(ii), _i32(jj), _dp(pm), _dp(pn), max(n, 1)))
+        bounds = np.searchsorted(seq[:n], np.arange(self.n_seq + 1))
+        recs = []
+        for k, (a, b) in enumerate(zip(bounds[:-1], bounds[1:])):
+            lo, hi = int(off[k]), int(off[k + 1])
+            r = dict(i=ii[a:b].copy(), j=jj[a:b].copy(), p_motif=pm[a:b].copy(), p_none=pn[a:b].copy(),
+                     unpaired_motif=um[lo:hi].copy(), unpaired_none=un[lo:hi].copy(), exist_prob=float(ex[k]), shift=float(sh[k]))
+            if gamma is not None:
+                r["structure_motif"] = sm.raw[lo:hi].decode("ascii")
+                r["structure_none"] = sn.raw[lo:hi].decode("ascii")
+            recs.append(r)
+        return recs
 
     # ---- stochastic samples of derivations (DESIGN.md section 14)
     SAMPLED, NO_PARSE, REFUSED = 0, 1, 2

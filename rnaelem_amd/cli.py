@@ -17,6 +17,9 @@
     python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-sites sites.txt
                                     # + maximum expected accuracy motif alignments and site lists decoded from those profiles
                                     #   (--site-gamma 1.0, --max-sites 1; io.site_record)
+    python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-contrast contrast.txt
+                                    # + the fold with the motif against the fold without it: pair posteriors, unpaired and
+                                    #   MEA structure of each (--contrast-min-prob 1e-3, --contrast-gamma 1.0; io.contrast_record)
     python -m rnaelem_amd.cli       --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --out2 scan.raw
                                     # no sub-command = what script/elem spawns: train, write the model, scan (main.cpp:47-84)
     python -m rnaelem_amd.cli eval  --fastq pos.fq --motif-model model.txt --out1 fn.txt --out2 gr.txt     (motif_eval.hpp:23-54)
@@ -82,6 +85,12 @@ def build_parser():
     sub.choices["scan"].add_argument("--site-gamma", type=float, default=1.0,
                                      help="weight of the pattern's nodes: a base on a pattern node scores gamma N, on z or o its N")
     sub.choices["scan"].add_argument("--max-sites", type=int, default=1, help="most sites reported per sequence (1 .. 64)")
+    sub.choices["scan"].add_argument("--out-contrast", default=None,
+                                     help="motif-conditional pair posteriors, the fold with the motif against the fold without it: "
+                                          "one record per sequence (io.contrast_record)")
+    sub.choices["scan"].add_argument("--contrast-min-prob", type=float, default=1e-3,
+                                     help="pairs below this probability in both folds are left out")
+    sub.choices["scan"].add_argument("--contrast-gamma", type=float, default=1.0, help="weight of the pairs in the two structures (as --mea-gamma)")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -249,7 +258,7 @@ def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
 
 def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0,
                   out_samples=None, n_samples=100, sample_seed=0, out_context=None, out_nodes=None, out_sites=None, site_gamma=1.0,
-                  max_sites=1):
+                  max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0):
     from .distributed import assigned_range
     nodes = eng.describe()["node"]
     step = max(1, chunk)
@@ -260,7 +269,8 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             part = mine[c0:c0 + step]
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
-            if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None:
+            if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None \
+                    and out_contrast is None:
                 for (rid, codes, _), r in zip(part, res):
                     yield io.scan_record(rid, codes, r, nodes)
                 continue
@@ -277,6 +287,7 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                 nod = [r["profile"] for r in sit] if out_nodes is not None else None
             else:
                 nod = eng.node_profiles(m["x"]) if out_nodes is not None else None
+            con = eng.conditional_pairs(m["x"], contrast_min_prob, contrast_gamma) if out_contrast is not None else None
             for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
                 texts = [io.scan_record(rid, codes, r, nodes)]
                 if out_pairs is not None:
@@ -293,12 +304,14 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                     texts.append(io.node_record(rid, nod[k], nodes, api.alignment_confidence(nod[k], r["psihat"])))
                 if out_sites is not None:
                     texts.append(io.site_record(rid, sit[k], nodes))
+                if out_contrast is not None:
+                    texts.append(io.contrast_record(rid, con[k]))
                 yield tuple(texts)
 
-    if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None:
+    if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None and out_contrast is None:
         sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
     else:
-        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites) if o is not None]
+        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast) if o is not None]
         sharded_write(recs, outs, rank, world, scan_part, barrier)
 
 
@@ -313,7 +326,8 @@ def cmd_scan(a):
     m = io.read_model(a.motif_model)
     eng = io.engine_from_model(m, a.device if a.device is not None else local_rank)
     _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
-                  a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites)
+                  a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites,
+                  a.out_contrast, a.contrast_min_prob, a.contrast_gamma)
     if world > 1:
         dist.destroy_process_group()
 

@@ -30,6 +30,7 @@
 
 #include "../../include/elemdp.h"
 #include "automaton.h"
+#include "cond_rules.h"
 #include "device_layout.h"
 #include "energy_tables.h"
 #include "host_prep.h"
@@ -204,6 +205,12 @@ class Engine {
   struct MeaOut { double gamma; char* structure; double* score; };
   void pair_posteriors(const double* x, int n_param, double min_prob, int64_t* n_pairs, double* unpaired, const MeaOut* mea = nullptr);
   void pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap);
+  // motif-conditional pair posteriors (cond_rules.h): the fold with the motif and the fold without it; outputs as
+  // elemdp_pair_conditional, any may be null; gamma is read only where a structure is asked for.  The list stays on the device
+  // for cond_list; the list of the last pair_posteriors is left alone.
+  struct CondOut { double gamma; double* exist; double* unpaired[2]; char* structure[2]; double* shift; };
+  void pair_conditional(const double* x, int n_param, double min_prob, int64_t* n_pairs, const CondOut& out);
+  void cond_list(int32_t* seq, int32_t* i, int32_t* j, double* p_motif, double* p_none, int64_t cap);
   // stochastic samples of derivations (sample_rules.h); outputs as elemdp_sample
   struct SampleOut { char* rss; uint8_t* node; double* logp; int32_t* status; };
   void sample_structures(const double* x, int n_param, int n_samples, uint64_t seed, int64_t index_base, const SampleOut& out);
@@ -360,6 +367,7 @@ class Engine {
   void stream_scan(const double* x, int n_param, elemdp_scan_out* out);
   void stream_pairs(const double* x, int n_param, double min_prob, double* unpaired, const MeaOut* mea);
   void stream_samples(const double* x, int n_param, int n_samples, uint64_t seed, int64_t index_base, const SampleOut& out);
+  void stream_cond(const double* x, int n_param, double min_prob, const CondOut& out);
   // pair posteriors: kept pairs per sequence and their prefix (staging ranges), pairs kept by min_prob and their prefix, the
   // P(i, d) scratch of the table slots, the staging list, the final list of the last call (n_pairs_ < 0: none)
   DevBuf d_pr_kept_, d_pr_koff_, d_pr_cnt_, d_pr_off_, d_pr_P_, d_pr_unp_, d_pr_si_, d_pr_sj_, d_pr_sp_;
@@ -368,6 +376,13 @@ class Engine {
   // MEA structures: the M table and choice scratch of the table slots (as d_pr_P_), the structures and the scores of the call
   DevBuf d_mea_M_, d_mea_ch_, d_mea_s_, d_mea_sc_;
   DevBuf d_sm_rss_, d_sm_node_, d_sm_logp_, d_sm_status_, d_sm_stack_;   // sample_structures
+  // conditional pair posteriors, all of the call's own: counts and prefixes as for the pair call, the P(i, d) scratch of both
+  // worlds per table slot, ln Z per slot of the log-space form, unpaired vectors, exist_prob and shift, the staging list and the
+  // final list of the last call (n_cond_ < 0: none), then the MEA scratch, structures and scores of both worlds
+  DevBuf d_cd_kept_, d_cd_koff_, d_cd_cnt_, d_cd_off_, d_cd_P_, d_cd_z_, d_cd_unp_[2], d_cd_exist_, d_cd_shift_, d_cd_si_, d_cd_sj_, d_cd_sp_[2];
+  DevBuf d_cl_seq_, d_cl_i_, d_cl_j_, d_cl_p_[2];
+  int64_t n_cond_ = -1;
+  DevBuf d_cd_M_, d_cd_ch_, d_cd_s_[2], d_cd_sc_;
   // context profiles: P, u, h, b of the table slots (four [i][d] arrays per slot), their exterior columns, the profile of the call
   DevBuf d_cx_cells_, d_cx_o_, d_cx_prof_;
   DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
@@ -912,6 +927,7 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   DeviceGuard dg(device_);
   n_seq_ = 0;
   n_pairs_ = -1;
+  n_cond_ = -1;
   streaming_ = false;
   train_rows_ = false;
   BatchShape shape = check_batch(seq, off, qual, qoff, fix, n);
@@ -2319,6 +2335,202 @@ void Engine::pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t 
 }
 
 
+// ---- motif-conditional pair posteriors (cond_rules.h).  Per group, queued on its stream behind one another on its
+// table slots: the inside sweep (SCAN_PASS_INSIDE, with the train evaluation's range check over all three Z), the outside sweep
+// seeded with the ari terminals and the reduction of the P plane with Z(ari), the outside sweep seeded with the nasi terminal
+// into the same outside slot and the reduction with Z(nasi), the per-sequence pass over both worlds, the two MEA decodes.  The
+// log-space form -- the fused scan kernel up to its inside pass, then one outside pass and one reduction per world -- for the
+// sequences that leave the double range and under pipeline 3.  Then the batch list in (sequence, i, j) order with two probability
+// columns, in buffers of its own: the list of the last pair call is left alone.
+void Engine::pair_conditional(const double* x, int n_param_in, double min_prob, int64_t* n_pairs, const CondOut& out) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (!n_pairs) throw ArgError("pair_conditional: null n_pairs");
+  if (!(min_prob >= 0.)) throw ArgError("pair_conditional: min_prob must be >= 0");
+  const bool mea = out.structure[0] || out.structure[1];
+  if (mea && !(std::isfinite(out.gamma) && out.gamma > 0.)) throw ArgError("pair_conditional: gamma must be finite and > 0");
+  if (streaming_) { stream_cond(x, n_param_in, min_prob, out); *n_pairs = n_cond_; return; }
+  require_resident("pair_conditional", n_param_in);
+  n_cond_ = -1;
+  upload_params(x, lay_, false);
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  const size_t pcells = (size_t)(Lmax_ + 1) * (Wmax_ + 1);   // P(i, d) of one world of one table slot
+  ScanPos pos(n_seqpos, n);
+  d_cd_kept_.alloc(8 * (size_t)n); d_cd_koff_.alloc(8 * ((size_t)n + 1));
+  d_cd_cnt_.alloc(8 * (size_t)n); d_cd_off_.alloc(8 * ((size_t)n + 1));
+  d_cd_unp_[0].alloc(8 * n_seqpos); d_cd_unp_[1].alloc(8 * n_seqpos);
+  d_cd_exist_.alloc(8 * (size_t)n); d_cd_shift_.alloc(8 * (size_t)n);
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  // staging ranges: a sequence's list holds at most its kept pairs
+  HIP_OK(launch_pair_kept(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, d_cd_kept_.as<int64_t>(), st_));
+  HIP_OK(launch_pair_prefix(d_cd_kept_.as<int64_t>(), n, d_cd_koff_.as<int64_t>(), st_));
+  int64_t n_kept = 0;
+  HIP_OK(hipMemcpyAsync(&n_kept, d_cd_koff_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  d_cd_si_.alloc(4 * (size_t)n_kept); d_cd_sj_.alloc(4 * (size_t)n_kept);
+  d_cd_sp_[0].alloc(8 * (size_t)n_kept); d_cd_sp_[1].alloc(8 * (size_t)n_kept);
+  HIP_OK(hipMemsetAsync(d_cd_cnt_.as<void>(), 0, 8 * (size_t)n, st_));
+  CondArgs ca;
+  std::memset(&ca, 0, sizeof(ca));
+  ca.plans = plan_.d_plans.as<SeqPlan>();
+  ca.okbits = d_okbits1_.as<uint32_t>();
+  ca.seq_out = d_seq_out_.as<double>(); ca.out_stride = out_stride_;
+  ca.p_stride = pcells;
+  ca.min_prob = min_prob;
+  ca.unpaired[0] = d_cd_unp_[0].as<double>(); ca.unpaired[1] = d_cd_unp_[1].as<double>();
+  ca.exist = d_cd_exist_.as<double>(); ca.shift = d_cd_shift_.as<double>();
+  ca.koff = d_cd_koff_.as<int64_t>(); ca.cnt = d_cd_cnt_.as<int64_t>();
+  ca.st_i = d_cd_si_.as<int32_t>(); ca.st_j = d_cd_sj_.as<int32_t>();
+  ca.st_p[0] = d_cd_sp_[0].as<double>(); ca.st_p[1] = d_cd_sp_[1].as<double>();
+  // the scratch per slot: P of world 0 of every slot, then P of world 1; MEA: the M table and the choices next to them
+  const size_t mea_ch_stride = pcells + (size_t)Lmax_ + 1;
+  size_t n_slot = 0;
+  auto scratch = [&](size_t slots) {
+    n_slot = slots;
+    d_cd_P_.alloc(8 * 2 * pcells * slots);
+    if (!mea) return;
+    d_cd_M_.alloc(8 * pcells * slots);
+    d_cd_ch_.alloc(4 * mea_ch_stride * slots);
+  };
+  auto at_slot = [&](CondArgs& ck, size_t slot0) {
+    ck.P[0] = d_cd_P_.as<double>() + slot0 * pcells;
+    ck.P[1] = d_cd_P_.as<double>() + (n_slot + slot0) * pcells;
+  };
+  // the MEA decode of both worlds: the pair call's kernel over the world's P and unpaired (the scores are not handed out)
+  PairArgs pm = pair_batch_args();
+  pm.p_stride = pcells;
+  if (mea) {
+    d_cd_s_[0].alloc(n_seqpos); d_cd_s_[1].alloc(n_seqpos); d_cd_sc_.alloc(8 * 2 * (size_t)n);
+    pm.mea_gamma2 = 2. * out.gamma;
+    pm.mea_ch_stride = mea_ch_stride;
+  }
+  auto launch_mea = [&](const CondArgs& ck, int skip_flagged, size_t slot0, int G, hipStream_t st) {
+    if (!mea) return;
+    for (int w = 0; w < 2; ++w) {
+      if (!out.structure[w]) continue;
+      PairArgs pk = pm;
+      pk.idx = ck.idx;
+      pk.skip_flagged = skip_flagged;
+      pk.P = ck.P[w];
+      pk.unpaired = ck.unpaired[w];
+      pk.mea_M = d_cd_M_.as<double>() + slot0 * pcells;
+      pk.mea_ch = d_cd_ch_.as<int32_t>() + slot0 * mea_ch_stride;
+      pk.mea_s = d_cd_s_[w].as<char>(); pk.mea_score = d_cd_sc_.as<double>() + (size_t)w * n;
+      HIP_OK(launch_pair_mea(pk, G, Wmax_, st));
+    }
+  };
+  int n_flagged = 0;
+  const bool sums_on_batch = opt_pipeline_ == 4;
+  if (sums_on_batch)
+    n_flagged = scan_sums(pos, [&](LinArgs& a) {
+      scratch((size_t)slots_.n());
+      a.range_all = 1;
+      PairArgs pp = pair_batch_args();
+      pair_plane_fields(pp, a);
+      ca.p_cs = pp.p_cs; ca.p_rs = pp.p_rs; ca.ncol = pp.ncol; ca.band_stride = pp.band_stride;
+      ca.skip_flagged = 1;
+    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      CondArgs ck = ca;
+      ck.idx = ak.grp;
+      ck.band_in = ak.band_in; ck.band_out = ak.band_out; ck.z = ak.zs; ck.z_log = 0;
+      at_slot(ck, slot0);
+      const int cells = (Lg + 1) * (Wg + 1);
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_INSIDE, st));
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_OUT_ARI, st));
+      HIP_OK(launch_cond_cells(ck, COND_MOTIF, G, cells, st));
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_OUT_NASI, st));   // (into the same outside slot)
+      HIP_OK(launch_cond_cells(ck, COND_NONE, G, cells, st));
+      HIP_OK(launch_cond_seq(ck, G, st));
+      launch_mea(ck, 1, slot0, G, st);
+    });
+  // ---- the log-space form, in chunks of at most as many sequences as the scratch holds
+  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
+    if (!sums_on_batch) scratch((size_t)chunk);
+    d_cd_z_.alloc(8 * 4 * (size_t)chunk);
+    d.cond_p0 = d_cd_P_.as<double>();
+    d.cond_p1 = d_cd_P_.as<double>() + n_slot * pcells;
+    d.cond_z = d_cd_z_.as<double>();
+    d.pair_stride = pcells;
+    return chunk;
+  }, [&](const int32_t* idx, int C) {
+    CondArgs ck = ca;
+    ck.idx = idx;
+    ck.skip_flagged = 0;
+    ck.z = d_cd_z_.as<double>(); ck.z_log = 1;
+    at_slot(ck, 0);
+    HIP_OK(launch_cond_seq(ck, C, st_));
+    launch_mea(ck, 0, 0, C, st_);
+  });
+  HIP_OK(hipEventRecord(ev_[3], st_));
+  // ---- the list in (sequence, i, j) order
+  HIP_OK(launch_pair_prefix(d_cd_cnt_.as<int64_t>(), n, d_cd_off_.as<int64_t>(), st_));
+  int64_t total = 0;
+  HIP_OK(hipMemcpyAsync(&total, d_cd_off_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  d_cl_seq_.alloc(4 * (size_t)total); d_cl_i_.alloc(4 * (size_t)total); d_cl_j_.alloc(4 * (size_t)total);
+  d_cl_p_[0].alloc(8 * (size_t)total); d_cl_p_[1].alloc(8 * (size_t)total);
+  HIP_OK(launch_cond_scatter(d_cd_koff_.as<int64_t>(), d_cd_cnt_.as<int64_t>(), d_cd_off_.as<int64_t>(), d_cd_si_.as<int32_t>(),
+                             d_cd_sj_.as<int32_t>(), d_cd_sp_[0].as<double>(), d_cd_sp_[1].as<double>(), n, d_cl_seq_.as<int32_t>(),
+                             d_cl_i_.as<int32_t>(), d_cl_j_.as<int32_t>(), d_cl_p_[0].as<double>(), d_cl_p_[1].as<double>(), st_));
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms_all = 0, ms_dp = 0;
+  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
+  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
+  last_ms[0] = ms_all;
+  last_ms[1] = ms_dp;
+  last_ms[2] = (double)n_flagged;
+  auto get = [&](void* dst, const DevBuf& src, size_t bytes) { if (dst && bytes) HIP_OK(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost)); };
+  get(out.exist, d_cd_exist_, 8 * (size_t)n);
+  get(out.shift, d_cd_shift_, 8 * (size_t)n);
+  for (int w = 0; w < 2; ++w) {
+    get(out.unpaired[w], d_cd_unp_[w], 8 * n_seqpos);
+    if (mea) get(out.structure[w], d_cd_s_[w], n_seqpos);
+  }
+  n_cond_ = total;
+  *n_pairs = total;
+}
+
+void Engine::stream_cond(const double* x, int n_param_in, double min_prob, const CondOut& out) {
+  std::vector<int32_t> hs, hi, hj;
+  std::vector<double> hp[2];
+  n_cond_ = -1;
+  stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+    int64_t m = 0;
+    const int64_t at = h_seq_off_[c0] - h_seq_off_[0];   // (the chunk's first position)
+    CondOut oc{out.gamma, out.exist ? out.exist + c0 : nullptr,
+               {out.unpaired[0] ? out.unpaired[0] + at : nullptr, out.unpaired[1] ? out.unpaired[1] + at : nullptr},
+               {out.structure[0] ? out.structure[0] + at : nullptr, out.structure[1] ? out.structure[1] + at : nullptr},
+               out.shift ? out.shift + c0 : nullptr};
+    e.pair_conditional(x, n_param_in, min_prob, &m, oc);
+    const size_t b = hs.size();
+    hs.resize(b + m); hi.resize(b + m); hj.resize(b + m); hp[0].resize(b + m); hp[1].resize(b + m);
+    e.cond_list(hs.data() + b, hi.data() + b, hj.data() + b, hp[0].data() + b, hp[1].data() + b, m);
+    for (size_t t = b; t < hs.size(); ++t) hs[t] += c0;   // (batch-global sequence indices)
+  });
+  d_cl_seq_.upload(hs, st_); d_cl_i_.upload(hi, st_); d_cl_j_.upload(hj, st_);
+  d_cl_p_[0].upload(hp[0], st_); d_cl_p_[1].upload(hp[1], st_);
+  HIP_OK(hipStreamSynchronize(st_));
+  n_cond_ = (int64_t)hs.size();
+}
+
+void Engine::cond_list(int32_t* seq, int32_t* i, int32_t* j, double* p_motif, double* p_none, int64_t cap) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (n_cond_ < 0) throw StateError("pair_conditional_list before pair_conditional");
+  if (cap < n_cond_) throw ArgError("pair_conditional_list: buffer too small");
+  const size_t m = (size_t)n_cond_;
+  if (m == 0) return;
+  if (seq) HIP_OK(hipMemcpy(seq, d_cl_seq_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (i) HIP_OK(hipMemcpy(i, d_cl_i_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (j) HIP_OK(hipMemcpy(j, d_cl_j_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (p_motif) HIP_OK(hipMemcpy(p_motif, d_cl_p_[0].as<void>(), 8 * m, hipMemcpyDeviceToHost));
+  if (p_none) HIP_OK(hipMemcpy(p_none, d_cl_p_[1].as<void>(), 8 * m, hipMemcpyDeviceToHost));
+}
+
+
 // ---- structural context profiles under the motif model (ctx_rules.h).  The scan's first sum pass per group, then
 // on the group's table slots, before the next group of the stream reuses them: the pair reduction (k4_pairs), the per-run values
 // and the exterior column (k_ctx_cells), the seven columns per position (k_ctx_seq).  The log-space form -- the fused scan kernel
@@ -2944,6 +3156,21 @@ int elemdp_node_mea(elemdp_handle* h, const double* x, int32_t n_param, double g
   ELEMDP_TRY
   if (!h || !x) throw elemdp::ArgError("elemdp_node_mea: null argument");
   h->e->node_mea(x, n_param, gamma, max_sites, elemdp::Engine::NodeMeaOut{profile, node, n_sites, site_start, site_end, site_score, site_conf});
+  ELEMDP_CATCH
+}
+int elemdp_pair_conditional(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double gamma, int64_t* n_pairs,
+                            double* exist_prob, double* unpaired_motif, double* unpaired_none, char* structure_motif,
+                            char* structure_none, double* shift) {
+  ELEMDP_TRY
+  if (!h || !x || !n_pairs) throw elemdp::ArgError("elemdp_pair_conditional: null argument");
+  const elemdp::Engine::CondOut out{gamma, exist_prob, {unpaired_motif, unpaired_none}, {structure_motif, structure_none}, shift};
+  h->e->pair_conditional(x, n_param, min_prob, n_pairs, out);
+  ELEMDP_CATCH
+}
+int elemdp_pair_conditional_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p_motif, double* p_none, int64_t cap) {
+  ELEMDP_TRY
+  if (!h) throw elemdp::ArgError("elemdp_pair_conditional_list: null handle");
+  h->e->cond_list(seq, i, j, p_motif, p_none, cap);
   ELEMDP_CATCH
 }
 int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {

@@ -165,6 +165,10 @@ struct DpArgs {
   // SCAN, samples (sample_rules.h, log-space form): n_samples > 0 = stop after the inside pass and draw the samples of sequence
   // order[w] on the slot's dense log tables, the workgroup's lanes over the samples
   SampleArgs smp;
+  // SCAN, motif-conditional pair posteriors (cond_rules.h, log-space form): non-null = stop after inside + one outside pass per
+  // world (terminals ari alone, then nasi alone) and write P_motif / P_none of the sequence order[w] to cond_p0 / cond_p1 +
+  // w * pair_stride (as pair_p) and ln Z(ari, nasi), ln Z(ari), ln Z(nasi) to cond_z + 4 w
+  double* cond_p0; double* cond_p1; double* cond_z;
   // SCAN, structural context profiles (ctx_rules.h, log-space form): ctx.u non-null = stop after inside + the first outside pass
   // and write P, u, h, b and o of the sequence order[w] to slot w of ctx (the rows k_ctx_seq reads behind the launch)
   CtxArgs ctx;
@@ -299,6 +303,11 @@ struct LinArgs {
   // train form computes and stores no L, takes the inside set of lists and starts no diagonal below in_d0 (the engine sets it where
   // loop_pre could be set and the mode is not the deterministic one)
   int32_t loop_post = 0;
+  // scan, motif-conditional pair posteriors (cond_rules.h).  scan_terms: the terminals an outside sweep of the scan is seeded with
+  // -- 0 = ari and nasi with Z(ari, nasi), 1 = ari alone with Z(ari), 2 = nasi alone with Z(nasi); a sequence whose world is empty
+  // (Z = 0) is left alone by that sweep.  range_all: 1 = the range check of the inside pass looks at all three Z, as the train
+  // evaluation's does, except that a Z of exactly 0 is an empty world and no range failure
+  int32_t scan_terms = 0, range_all = 0;
 };
 struct LinWeightArgs {
   const LoopItem* items_inner; const LoopItem* items_left; const LoopItem* items_right;   // (may be null)
@@ -316,7 +325,9 @@ hipError_t launch_lin_weights(const LinWeightArgs& a, hipStream_t st);
 // to that start with end posteriors and argmax end (RNAelemScanDP::operator(), motif_scanner.hpp:186-202); SCAN_PASS_INSIDE = the
 // inside sweeps and the exterior chain of SCAN_PASS_START only (Z and the range check, no outside pass: the tables of the sampler,
 // sample_rules.h)
-enum ScanPass { SCAN_PASS_START = 0, SCAN_PASS_END = 1, SCAN_PASS_INSIDE = 2 };
+// SCAN_PASS_OUT_ARI / SCAN_PASS_OUT_NASI = an outside sweep alone, behind SCAN_PASS_INSIDE on the same slots, seeded with the ari
+// terminals / the nasi terminal only (LinArgs::scan_terms): the outside tables of one world of cond_rules.h, no pick
+enum ScanPass { SCAN_PASS_START = 0, SCAN_PASS_END = 1, SCAN_PASS_INSIDE = 2, SCAN_PASS_OUT_ARI = 3, SCAN_PASS_OUT_NASI = 4 };
 hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax, ScanPass pass, hipStream_t st);
 // scan: Viterbi parse (max-plus CYK with trace records, then traceback) of a group; uses band_in / ext_in as the CYK table
 hipError_t launch_cyk_group(const LinArgs& full, int G, int Lmax, int Wmax, hipStream_t st);
@@ -384,6 +395,37 @@ hipError_t launch_pair_cells(const PairArgs& a, int G, int cells_max, hipStream_
 hipError_t launch_pair_seq(const PairArgs& a, int G, hipStream_t st);
 // k_pair_mea, behind launch_pair_seq on the same slots and stream; Wmax >= the W of every sequence of the launch (LDS size)
 hipError_t launch_pair_mea(const PairArgs& a, int G, int Wmax, hipStream_t st);
+
+// ---- motif-conditional pair posteriors (cond_rules.h, cond_kernels.hip).  A launch covers the G sequences idx[0 .. G) of one group
+// or chunk; slot g of the launch owns P[w] + g * p_stride ([i][d], rows of W+1) for the worlds w = 0 (motif) and 1 (none).
+struct CondArgs {
+  const SeqPlan* plans;           // batch plans (batch index)
+  const int32_t* idx;             // idx[g] = batch index of the sequence in slot g
+  const uint32_t* okbits;         // pair mask after the filter (bits_base indexing)
+  // launch_cond_cells: the P plane of the group's compact table slots, as PairArgs
+  const double* band_in; const double* band_out; size_t band_stride;
+  int32_t p_cs, p_rs, ncol;
+  // per slot: Z(ari, nasi), Z(ari), Z(nasi) at z[4 g ..] -- mantissas in the tables' scale (z_log 0), or logarithms (z_log 1)
+  const double* z; int32_t z_log;
+  const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
+  int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)
+  double* P[2]; size_t p_stride;
+  // launch_cond_seq
+  double min_prob;
+  double* unpaired[2];            // seq_base indexing, L values per sequence
+  double* exist; double* shift;   // per batch index
+  const int64_t* koff;            // per batch index: first staging entry (prefix of the kept pairs)
+  int32_t* st_i; int32_t* st_j; double* st_p[2];   // staging list, (i, j) in row order per sequence
+  int64_t* cnt;                   // per batch index: pairs with max(P_motif, P_none) >= min_prob
+};
+// k4_cond behind launch_lin_scan_group (SCAN_PASS_OUT_ARI: world 0, SCAN_PASS_OUT_NASI: world 1) on the same slots and stream
+hipError_t launch_cond_cells(const CondArgs& a, int world, int G, int cells_max, hipStream_t st);
+// k_cond_seq behind both worlds' reductions, or behind the fused scan kernel (DpArgs::cond_p0)
+hipError_t launch_cond_seq(const CondArgs& a, int G, hipStream_t st);
+// the scatter of the staging list into the final list ordered by (sequence, i, j), two probability columns
+hipError_t launch_cond_scatter(const int64_t* koff, const int64_t* cnt, const int64_t* off, const int32_t* st_i, const int32_t* st_j,
+                               const double* st_p0, const double* st_p1, int n, int32_t* seq, int32_t* i, int32_t* j, double* p0,
+                               double* p1, hipStream_t st);
 
 hipError_t launch_sample(const LinArgs& a, const SampleArgs& s, int G, hipStream_t st);
 // k_ctx_cells behind launch_lin_scan_group (SCAN_PASS_START) and launch_pair_cells on the same slots and stream; k_ctx_seq behind

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "cond_rules.h"
 #include "ctx_rules.h"
 #include "dp_rules.h"
 #include "energy_rules.h"
@@ -724,6 +725,32 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
           if (status != SAMPLE_OK) atomicMax(&l_status, status);
           __syncthreads();
           if (tid == 0) a.smp.status[n] = l_status;
+          continue;
+        }
+        if (a.cond_p0) {   // motif-conditional pair posteriors (cond_rules.h): one outside pass per world, each with its own Z
+          if (tid == 0) {
+            l_zs[2] = part_func(m, Tin, true, false);
+            l_zs[3] = part_func(m, Tin, false, true);
+            a.cond_z[4 * (size_t)w] = l_zs[0]; a.cond_z[4 * (size_t)w + 1] = l_zs[2]; a.cond_z[4 * (size_t)w + 2] = l_zs[3];
+          }
+          __syncthreads();
+          sink.post_[0] = Pys; sink.post_[1] = Pyi;   // (the scan form's position sums: scratch here)
+          for (int world = 0; world < 2; ++world) {
+            const double Zw = l_zs[2 + world];
+            const bool live = Zw > ELEMDP_NEG_INF && Zw < HUGE_VAL;   // (an empty world: no sweep, P = 0)
+            if (live) sweep_outside<OUT_SCAN>(m, q, Tin, Tout, Zw, c0, world == COND_MOTIF, world == COND_NONE, sink, l_eh, no_rss, sc, pf);
+            double* P = (world == COND_MOTIF ? a.cond_p0 : a.cond_p1) + (size_t)w * a.pair_stride;
+            const PairLog r{Zw};
+            for (int t = tid; t < ncell; t += kThreads) {
+              const int i = t / (W + 1), d = t - i * (W + 1);
+              double acc = 0.;
+              if (live && i + d <= L && q.pair_ok(i, d))
+                for (int s = 0; s < S; ++s)
+                  if (s != m.lay.shadow) acc += r.term(Tin.at(ST_P, d, i, s), Tout.at(ST_P, d, i, s));
+              P[t] = r.finish(acc);
+            }
+            __syncthreads();   // (the next world's sweep overwrites the outside tables)
+          }
           continue;
         }
         const double ZL = l_zs[0];

@@ -1259,7 +1259,8 @@ __global__ __launch_bounds__(128 * kExtBlock) void k4_in_ext(LinArgs a) {
     v.row[2] = (Zn > 0.) ? log(Zn) - sl * ln2 : ELEMDP_NEG_INF;
     if (CON && v.row[4] != 0.) {
       // (second scan pass of a sequence the first one already flagged: nothing to add)
-    } else if (out_of_range(Zo) || (!a.scan && (out_of_range(Za) || out_of_range(Zn)))) {
+    } else if (a.range_all ? ((Zo != 0. && out_of_range(Zo)) || (Za != 0. && out_of_range(Za)) || (Zn != 0. && out_of_range(Zn)))
+                           : (out_of_range(Zo) || (!a.scan && (out_of_range(Za) || out_of_range(Zn))))) {
       // outside the double range (or a structurally empty component): the log-space pipeline re-evaluates the
       // sequence and applies the reference's skip rule (motif_trainer.hpp:211-215)
       v.row[3] = 0.; v.row[4] = 2.; v.row[5] = 0.;
@@ -1292,8 +1293,13 @@ __device__ __forceinline__ LPass lpass(const LinArgs& a, const LViews& v) {
   pi.skip = v.row[4] != 0.;
   double Z;
   if (a.schedule == 0) {
-    if (a.pass == 0) { Z = v.zs[0]; pi.ari = true; pi.nasi = true; }
-    else {   // (--lik-ratio: the "has motif" terminals for both labels, roles swapped in k4_combine)
+    if (a.pass == 0) {
+      Z = v.zs[0]; pi.ari = true; pi.nasi = true;
+      // (scan, one world of cond_rules.h: its terminals and its Z; a sequence whose world is empty takes no part in the sweep)
+      if (a.scan_terms == 1) { Z = v.zs[1]; pi.nasi = false; }
+      if (a.scan_terms == 2) { Z = v.zs[2]; pi.ari = false; }
+      if (a.scan_terms != 0 && Z == 0.) pi.skip = true;
+    } else {   // (--lik-ratio: the "has motif" terminals for both labels, roles swapped in k4_combine)
       const bool use_ari = positive || a.lik_ratio;
       Z = use_ari ? v.zs[1] : v.zs[2]; pi.ari = use_ari; pi.nasi = !use_ari;
     }
@@ -2865,16 +2871,21 @@ static void outside_bands(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t s
     hipLaunchKernelGGL(k4_out_lrows, dim3((Lmax + rows) / rows, G), dim3(kBT), loop_rows_lds(a.lay), st, a);
   }
 }
-// an unconstrained or constrained sum pass of the scan: inside sweep, exterior chain outwards, outside band sweep
-template <bool CON, int MODE>
-static void scan_sweeps(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t st) {
+// the outside half of a sum pass of the scan: exterior chain outwards, outside band sweep
+template <int MODE>
+static void scan_outside(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t st) {
   const LinArgs& a = g.a;
   const int S = a.lay.S, nt = a.lay.n_theta;
   const size_t lds_ext_out = g.stage_ext ? (size_t)ext_lds(2 * nt + 4 + (a.ext_ring ? ext_ring_doubles(2 * nt + 4, Wmax, S, kLinEth + nt, Lmax, a.nword_max, a.n_stage) : 0), kLinEth + nt, Lmax, a.nword_max, a.n_stage).total : sizeof(double) * (2 * nt + 4);
-  inside_sweeps<CON>(g, G, Lmax, Wmax, true, st);
   if (g.stage_ext) hipLaunchKernelGGL((k4_out_ext<MODE, true>), dim3(G), dim3(g.ext_nt), lds_ext_out, st, a);
   else hipLaunchKernelGGL((k4_out_ext<MODE, false>), dim3(G), dim3(128), lds_ext_out, st, a);
   outside_bands<MODE>(g, G, Lmax, Wmax, st);
+}
+// an unconstrained or constrained sum pass of the scan: inside sweep, then the outside half
+template <bool CON, int MODE>
+static void scan_sweeps(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t st) {
+  inside_sweeps<CON>(g, G, Lmax, Wmax, true, st);
+  scan_outside<MODE>(g, G, Lmax, Wmax, st);
 }
 
 hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax, ScanPass pass, hipStream_t st) {
@@ -2887,6 +2898,11 @@ hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax,
   } else if (pass == SCAN_PASS_START) {   // unconstrained sweeps, the statistics of the scan
     scan_sweeps<false, OUT_SCAN>(g, G, Lmax, Wmax, st);
     hipLaunchKernelGGL(k5_pick<0>, dim3((G + 63) / 64), dim3(64), 0, st, a, G);
+  } else if (pass == SCAN_PASS_OUT_ARI || pass == SCAN_PASS_OUT_NASI) {
+    // one world's outside tables behind SCAN_PASS_INSIDE: the unconstrained scan form seeded with that world's terminals (its
+    // position statistics land in the call's scratch: the band kernel has no tables-only form on the pattern automaton), no pick
+    g.a.scan_terms = pass == SCAN_PASS_OUT_ARI ? 1 : 2;
+    scan_outside<OUT_SCAN>(g, G, Lmax, Wmax, st);
   } else {   // the start constraint at Ys, the end posteriors
     scan_sweeps<true, OUT_END>(g, G, Lmax, Wmax, st);
     hipLaunchKernelGGL(k5_pick<1>, dim3((G + 63) / 64), dim3(64), 0, st, a, G);

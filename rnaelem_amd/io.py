@@ -168,6 +168,44 @@ def read_pair_records(path):
     return out
 
 
+def contrast_record(rid, rec):
+    """Record of one sequence in the `scan --out-contrast` file, from a record of Engine.conditional_pairs with structures: the id
+    line with exist_prob and shift (tab separated, fmt), the maximum expected accuracy structure with the motif and the one
+    without it, the two lines of unpaired probabilities, the number of pairs, then one line `i j p_motif p_none` per pair --
+    1-based base positions i < j (cell (i0, j0) -> i0+1, j0), ordered by i then j, probabilities as %.6g."""
+    lines = ["id: %s\texist prob: %s\tshift: %s" % (rid, fmt(rec["exist_prob"]), fmt(rec["shift"])),
+             "motif: " + rec["structure_motif"], "none: " + rec["structure_none"],
+             "unpaired motif: " + fmt_vec(rec["unpaired_motif"]), "unpaired none: " + fmt_vec(rec["unpaired_none"]),
+             "pairs: %d" % len(rec["i"])]
+    lines += ["%d %d %.6g %.6g" % (int(a) + 1, int(b), float(u), float(v))
+              for a, b, u, v in zip(rec["i"], rec["j"], rec["p_motif"], rec["p_none"])]
+    return "\n".join(lines) + "\n"
+
+
+def read_contrast_records(path):
+    """-> list of dicts (id, exist_prob, shift, structure_motif, structure_none, unpaired_motif, unpaired_none,
+    pairs = [(i, j, p_motif, p_none), ...] with 1-based i < j) from a `scan --out-contrast` file."""
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+
+    def vec(line, head):
+        if not line.startswith(head):
+            raise ValueError("contrast record: line %r where %r was expected" % (line, head))
+        body = line[len(head):].strip("[]")
+        return np.array([float(v) for v in body.split(",")] if body else [])
+
+    while k + 5 < len(lines) and lines[k].startswith("id: "):
+        rid, ex, sh = lines[k][4:].rsplit("\t", 2)
+        n = int(lines[k + 5][len("pairs: "):])
+        prs = [(int(a), int(b), float(u), float(v)) for a, b, u, v in (lines[k + 6 + t].split() for t in range(n))]
+        out.append(dict(id=rid, exist_prob=float(ex[len("exist prob: "):]), shift=float(sh[len("shift: "):]),
+                        structure_motif=lines[k + 1][len("motif: "):], structure_none=lines[k + 2][len("none: "):],
+                        unpaired_motif=vec(lines[k + 3], "unpaired motif: "), unpaired_none=vec(lines[k + 4], "unpaired none: "),
+                        pairs=prs))
+        k += 6 + n
+    return out
+
+
 def mea_record(rid, structure, score):
     """Record of one sequence in the `scan --out-mea` file: its id, the maximum expected accuracy structure under the motif model
     ('(', ')', '.'; one character per base) and its score as %.17g."""
