@@ -338,6 +338,24 @@ int elemdp_context_profile(elemdp_handle* h, const double* x, int32_t n_param, d
  * handed to the log-space form].  elemdp_scan, the pair calls (the list of the last one stays valid), elemdp_sample,
  * elemdp_context_profile and the train calls are unaffected. */
 int elemdp_node_profile(elemdp_handle* h, const double* x, int32_t n_param, double* profile);
+/* Accessibility under the motif model x: with U = max_width, access[U * (seq_off[n] + p) + (w - 1)], p 0-based,
+ * w = 1 .. U, is the probability that the bases p .. p+w-1 of sequence n are all unpaired, over the ensemble of the scan's first sum
+ * pass (terminals ari and nasi, Z(ari, nasi): the ensemble of elemdp_pair_posteriors and elemdp_context_profile), from its inside /
+ * outside tables.  A window of unpaired bases lies in one maximal unpaired stretch, which the grammar makes by one of four chains of
+ * single emissions -- a loop run (L <- L), the exterior (rule 8), the tail behind a multi-loop branch (rule 3a), the leading bases
+ * of a multi-loop (rule 5a) -- and the value is the sum of the four w-step path sums between the tables, clamped to [0, 1]
+ * (access_rules.h).  Width 1 is the unpaired vector of elemdp_pair_posteriors wherever the tables' inside and outside agree (1e-12
+ * with energies at max_iloop 30); where the outside pass enumerates interior loops the inside pass does not -- max_iloop < 30, or a
+ * model without energies on sequences longer than max_iloop -- the two cut the derivations at different items and differ by the
+ * weight of those loops (2.5e-7 seen without energies at L = 40).  A window that runs off the end (p + w > L) is NaN.
+ * A sequence without any parse (Z = 0) has 1 in every valid window, exactly, and so has every sequence under ELEMDP_NO_RSS.
+ * Sequences that leave the double range of the scaled-linear tables, and every sequence under option pipeline 3, go through the
+ * same rule on the log-space tables of the fused scan kernel.  max_width outside 1 .. 64, x NULL or access NULL is ELEMDP_EINVAL,
+ * a call before elemdp_load_batch ELEMDP_ESTATE, a call without a device ELEMDP_ENODEV.  elemdp_last_timing afterwards: [whole call
+ * including the copy to the host, sum passes + accessibility kernels, sequences handed to the log-space form].  Every buffer is
+ * the call's own: elemdp_scan, the pair calls (the list of the last one stays valid), the other scan-family calls and the train
+ * calls are unaffected. */
+int elemdp_accessibility(elemdp_handle* h, const double* x, int32_t n_param, int32_t max_width, double* access);
 /* Maximum expected accuracy motif alignments and site lists under the motif model x, decoded on the device from
  * the profile N of elemdp_node_profile.  A node row (0 = 'z' .. M-1 = 'o') is valid if it is the row of some alignment: all 'z', or
  * z^a n1^r1 .. nk^rk o^c over the pattern's nodes in order, r >= 1 (r >= 0 for a '*' node), the body not empty.  With g = gamma on

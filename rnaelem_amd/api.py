@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -93,6 +93,7 @@ def load_library():
         L.elemdp_sample.argtypes = [hp, dp, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(C.c_uint8), dp, i32]
         L.elemdp_context_profile.argtypes = [hp, dp, C.c_int32, dp]
         L.elemdp_node_profile.argtypes = [hp, dp, C.c_int32, dp]
+        L.elemdp_accessibility.argtypes = [hp, dp, C.c_int32, C.c_int32, dp]
         L.elemdp_node_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_int32, dp, u8, i32, i32, i32, dp, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
         L.elemdp_pair_conditional.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int64), dp, dp, dp, C.c_char_p,
@@ -517,6 +518,22 @@ class Engine:
         prof = np.zeros(max(M * n_pos, 1))
         self._check(self._lib.elemdp_node_profile(self._h, _dp(x), self.n_param, _dp(prof)))
         return [prof[M * int(off[k]):M * int(off[k + 1])].reshape(-1, M).copy() for k in range(self.n_seq)]
+
+    # ---- accessibility
+    def accessibility(self, x, max_width=16):
+        """One (L, U) array per sequence, U = max_width (1 .. 64): column w-1 of row p is the probability that the bases
+        p .. p+w-1 are all unpaired, over the ensemble of pair_posteriors and context_profiles; NaN where the window runs off the
+        end.  Column 0 is the unpaired vector of pair_posteriors (to 1e-12 with energies at max_iloop 30; where the outside pass
+        enumerates interior loops the inside pass does not -- max_iloop < 30, no energies and L > max_iloop -- they differ by the
+        weight of those loops, 2.5e-7 seen).  Engine option access_terms (bits 1 loop runs, 2 exterior, 4 tails behind a
+        multi-loop branch, 8 leading bases of a multi-loop; default 15) leaves terms out of the sum."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        U = int(max_width)
+        n_pos = int(off[-1]) if off is not None else 0
+        acc = np.zeros(max(max(U, 1) * n_pos, 1))
+        self._check(self._lib.elemdp_accessibility(self._h, _dp(x), self.n_param, U, _dp(acc)))
+        return [acc[U * int(off[k]):U * int(off[k + 1])].reshape(-1, U).copy() for k in range(self.n_seq)]
 
     # ---- maximum expected accuracy motif alignments and site lists (DESIGN.md section 17)
     def mea_alignments(self, x, gamma=1.0, max_sites=1, profile=False):

@@ -20,6 +20,9 @@
     python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-contrast contrast.txt
                                     # + the fold with the motif against the fold without it: pair posteriors, unpaired and
                                     #   MEA structure of each (--contrast-min-prob 1e-3, --contrast-gamma 1.0; io.contrast_record)
+    python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-access access.txt
+                                    # + accessibility: the probability that the window of width 1 .. --access-width (16) at
+                                    #   every base is unpaired (io.access_record)
     python -m rnaelem_amd.cli       --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --out2 scan.raw
                                     # no sub-command = what script/elem spawns: train, write the model, scan (main.cpp:47-84)
     python -m rnaelem_amd.cli eval  --fastq pos.fq --motif-model model.txt --out1 fn.txt --out2 gr.txt     (motif_eval.hpp:23-54)
@@ -91,6 +94,10 @@ def build_parser():
     sub.choices["scan"].add_argument("--contrast-min-prob", type=float, default=1e-3,
                                      help="pairs below this probability in both folds are left out")
     sub.choices["scan"].add_argument("--contrast-gamma", type=float, default=1.0, help="weight of the pairs in the two structures (as --mea-gamma)")
+    sub.choices["scan"].add_argument("--out-access", default=None,
+                                     help="accessibility under the motif model, the probability that a window of bases is unpaired: "
+                                          "one record per sequence (io.access_record)")
+    sub.choices["scan"].add_argument("--access-width", type=int, default=16, help="widest window (1 .. 64)")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -258,7 +265,7 @@ def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
 
 def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0,
                   out_samples=None, n_samples=100, sample_seed=0, out_context=None, out_nodes=None, out_sites=None, site_gamma=1.0,
-                  max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0):
+                  max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0, out_access=None, access_width=16):
     from .distributed import assigned_range
     nodes = eng.describe()["node"]
     step = max(1, chunk)
@@ -270,7 +277,7 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
             if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None \
-                    and out_contrast is None:
+                    and out_contrast is None and out_access is None:
                 for (rid, codes, _), r in zip(part, res):
                     yield io.scan_record(rid, codes, r, nodes)
                 continue
@@ -288,6 +295,7 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             else:
                 nod = eng.node_profiles(m["x"]) if out_nodes is not None else None
             con = eng.conditional_pairs(m["x"], contrast_min_prob, contrast_gamma) if out_contrast is not None else None
+            acc = eng.accessibility(m["x"], access_width) if out_access is not None else None
             for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
                 texts = [io.scan_record(rid, codes, r, nodes)]
                 if out_pairs is not None:
@@ -306,12 +314,15 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                     texts.append(io.site_record(rid, sit[k], nodes))
                 if out_contrast is not None:
                     texts.append(io.contrast_record(rid, con[k]))
+                if out_access is not None:
+                    texts.append(io.access_record(rid, acc[k]))
                 yield tuple(texts)
 
-    if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None and out_contrast is None:
+    if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None and out_contrast is None \
+            and out_access is None:
         sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
     else:
-        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast) if o is not None]
+        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast, out_access) if o is not None]
         sharded_write(recs, outs, rank, world, scan_part, barrier)
 
 
@@ -327,7 +338,7 @@ def cmd_scan(a):
     eng = io.engine_from_model(m, a.device if a.device is not None else local_rank)
     _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
                   a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites,
-                  a.out_contrast, a.contrast_min_prob, a.contrast_gamma)
+                  a.out_contrast, a.contrast_min_prob, a.contrast_gamma, a.out_access, a.access_width)
     if world > 1:
         dist.destroy_process_group()
 

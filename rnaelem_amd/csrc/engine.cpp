@@ -29,6 +29,7 @@
 #include <dlfcn.h>
 
 #include "../../include/elemdp.h"
+#include "access_rules.h"
 #include "automaton.h"
 #include "cond_rules.h"
 #include "device_layout.h"
@@ -218,6 +219,8 @@ class Engine {
   void context_profile(const double* x, int n_param, double* profile);
   // posterior motif-node profiles (node_rules.h): n_node doubles per position of the batch
   void node_profile(const double* x, int n_param, double* profile);
+  // accessibility (access_rules.h): max_width doubles per position of the batch, the widths 1 .. max_width
+  void accessibility(const double* x, int n_param, int max_width, double* access);
   // maximum expected accuracy motif alignments and site lists over that profile (node_mea_rules.h); outputs as
   // elemdp_node_mea, any may be null
   struct NodeMeaOut { double* profile; uint8_t* node; int32_t* n_sites; int32_t* start; int32_t* end; double* score; double* conf; };
@@ -385,6 +388,7 @@ class Engine {
   DevBuf d_cd_M_, d_cd_ch_, d_cd_s_[2], d_cd_sc_;
   // context profiles: P, u, h, b of the table slots (four [i][d] arrays per slot), their exterior columns, the profile of the call
   DevBuf d_cx_cells_, d_cx_o_, d_cx_prof_;
+  DevBuf d_ac_T_, d_ac_vec_, d_ac_out_;   // accessibility: the four planes per slot, the log-space form's vectors, the result
   DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
   // node MEA: the chain lists, the backpointer scratch (M bytes per position), the rows, sites per sequence, start / end / score / confidence per slot
   DevBuf d_nm_lists_, d_nm_bp_, d_nm_node_, d_nm_ns_, d_nm_s0_, d_nm_s1_, d_nm_sc_, d_nm_cf_;
@@ -466,6 +470,7 @@ class Engine {
   int opt_schedule_ = 1;   // 1 = linear (ari pass + one-state nasi pass), 0 = the reference's two full passes
   int opt_dbg_ = 0;        // timing experiments (LinArgs::dbg); results are wrong when set
   int opt_group_ = 0;      // sequences swept in lockstep by the batch pipeline (0 = auto)
+  int opt_access_terms_ = 15;     // accessibility: the terms that take part (bit AccessTerm)
   int opt_node_rules_ = NR_ALL;   // node_profile: the emitting rules that take part (NodeRule bits)
   DevBuf d_prof_;
   DevBuf d_okbits_end_, d_nitems_, d_plans_all_;   // scratch of build_planset and of the canonical mask, kept across loads
@@ -639,6 +644,10 @@ void Engine::set_option(const std::string& key, double v) {
   else if (key == "node_rules") {   // (node_profile: the emitting rules that take part, NodeRule bits; a subset gives that part of the profile)
     if (v < 1 || v > NR_ALL) throw ArgError("node_rules: 1 .. 63 (bits: L <- L, rule 3a, rule 5a, left base of rules 1a / 1b, rule 8, right base of rules 1a / 1b)");
     opt_node_rules_ = (int)v;
+  }
+  else if (key == "access_terms") {   // (accessibility: the terms that take part, bit AccessTerm; a subset gives that part of the sum)
+    if (v < 1 || v > 15) throw ArgError("access_terms: 1 .. 15 (bits: loop runs, exterior, tails behind a branch, leading bases of a multi-loop)");
+    opt_access_terms_ = (int)v;
   }
   else if (key == "schedule") opt_schedule_ = (int)v;
   else if (key == "dbg") opt_dbg_ = (int)v;
@@ -2624,6 +2633,87 @@ void Engine::context_profile(const double* x, int n_param_in, double* profile) {
 }
 
 
+// ---- accessibility under the motif model (access_rules.h).  The scan's first sum pass per group, then on the
+// group's table slots, before the next group of the stream reuses them: the chains of the four terms (k_access_chains) and the
+// windows of every position (k_access_seq).  The log-space form -- the fused scan kernel up to its first outside pass, then the
+// same rule on its dense tables -- for the sequences that leave the double range and under pipeline 3, with k_access_seq behind
+// every launch.  Every buffer is the call's own: leaves the list of the last pair call alone.
+void Engine::accessibility(const double* x, int n_param_in, int max_width, double* access) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (!access) throw ArgError("accessibility: null access");
+  if (max_width < 1 || max_width > kAccessMaxWidth) throw ArgError("accessibility: max_width must lie in 1 .. 64");
+  const int U = max_width;
+  if (streaming_) {
+    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+      e.accessibility(x, n_param_in, U, access + (size_t)U * (size_t)(h_seq_off_[c0] - h_seq_off_[0]));
+    });
+    return;
+  }
+  require_resident("accessibility", n_param_in);
+  upload_params(x, lay_, false);
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  const size_t plane = ((size_t)Lmax_ + 1) * U;   // one term of a slot: U sums per position 0 .. L
+  ScanPos pos(n_seqpos, n);
+  d_ac_out_.alloc(8 * (size_t)U * std::max<size_t>(n_seqpos, 1));
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  AccessArgs ca;
+  std::memset(&ca, 0, sizeof(ca));
+  ca.plans = plan_.d_plans.as<SeqPlan>();
+  ca.seq_out = d_seq_out_.as<double>(); ca.out_stride = out_stride_;
+  ca.U = U;
+  ca.terms = opt_access_terms_;
+  ca.plane = plane; ca.t_stride = ACC_TERMS * plane;
+  ca.access = d_ac_out_.as<double>();
+  ca.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
+  auto scratch = [&](size_t slots) { d_ac_T_.alloc(8 * ACC_TERMS * plane * std::max<size_t>(slots, 1)); };
+  auto at_slot = [&](AccessArgs& ck, size_t slot0) { ck.T = d_ac_T_.as<double>() + slot0 * ACC_TERMS * plane; };
+  int n_flagged = 0, n_vec = 0;
+  const bool sums_on_batch = opt_pipeline_ == 4;
+  if (sums_on_batch)
+    n_flagged = scan_sums(pos, [&](LinArgs& a) {
+      scratch((size_t)slots_.n());
+      n_vec = std::max(a.lay.S, a.lay.n_ap);   // (entries of a state vector: the interval states, the pairs of rule 2)
+      ca.skip_flagged = 1;
+    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      AccessArgs ck = ca;
+      ck.idx = ak.grp;
+      at_slot(ck, slot0);
+      if (!ca.no_rss) HIP_OK(launch_access_chains(ak, ck, G, Lg, n_vec, st));
+      HIP_OK(launch_access_seq(ck, G, st));
+    });
+  // ---- the log-space form, in chunks of at most as many sequences as the scratch holds
+  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
+    if (!sums_on_batch) scratch((size_t)chunk);
+    // (a launch has at most n_blocks workgroups, each with 64 lanes on units: 2 S doubles per lane, 22 KB per workgroup at S = 22)
+    d_ac_vec_.alloc(8 * 2 * (size_t)d.lay.S * 64 * (size_t)std::max(n_blocks, 1));
+    d.acc = ca;
+    d.acc.vec = d_ac_vec_.as<double>();
+    at_slot(d.acc, 0);
+    return chunk;
+  }, [&](const int32_t* idx, int C) {
+    AccessArgs ck = ca;
+    ck.idx = idx;
+    ck.skip_flagged = 0;
+    at_slot(ck, 0);
+    HIP_OK(launch_access_seq(ck, C, st_));
+  });
+  HIP_OK(hipEventRecord(ev_[3], st_));
+  if (n_seqpos) HIP_OK(hipMemcpyAsync(access, d_ac_out_.as<void>(), 8 * (size_t)U * n_seqpos, hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms_all = 0, ms_dp = 0;
+  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
+  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
+  last_ms[0] = ms_all;
+  last_ms[1] = ms_dp;
+  last_ms[2] = (double)n_flagged;
+}
+
+
 // ---- posterior motif-node profiles under the motif model (node_rules.h).  The scan's first sum pass per group,
 // then k_node_pos on the group's table slots, before the next group of the stream reuses them; the log-space form -- the fused
 // scan kernel up to its first outside pass, then the same rule on its dense tables -- for the sequences that leave the double
@@ -3143,6 +3233,12 @@ int elemdp_context_profile(elemdp_handle* h, const double* x, int32_t n_param, d
   ELEMDP_TRY
   if (!h || !x || !profile) throw elemdp::ArgError("elemdp_context_profile: null argument");
   h->e->context_profile(x, n_param, profile);
+  ELEMDP_CATCH
+}
+int elemdp_accessibility(elemdp_handle* h, const double* x, int32_t n_param, int32_t max_width, double* access) {
+  ELEMDP_TRY
+  if (!h || !x || !access) throw elemdp::ArgError("elemdp_accessibility: null argument");
+  h->e->accessibility(x, n_param, max_width, access);
   ELEMDP_CATCH
 }
 int elemdp_node_profile(elemdp_handle* h, const double* x, int32_t n_param, double* profile) {

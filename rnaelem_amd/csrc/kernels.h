@@ -113,6 +113,22 @@ struct NodeArgs {
   double* profile;
 };
 
+// ---- accessibility (access_rules.h, access_kernels.hip).  A launch covers the G sequences idx[0 .. G) of one group or chunk; slot g
+// of the launch owns the four planes T + g * t_stride + term * plane (AccessTerm), rows of U doubles per position 0 .. L.  The result
+// of batch index n goes to access + U * seq_base, U doubles per position: the widths 1 .. U.
+struct AccessArgs {
+  const SeqPlan* plans;           // batch plans (batch index)
+  const int32_t* idx;             // idx[g] = batch index of the sequence in slot g (launch_access_seq)
+  const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
+  int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)
+  int32_t U;                      // max_width
+  int32_t terms;                  // bit AccessTerm: the terms that take part (all of them unless option access_terms says otherwise)
+  int32_t no_rss;                 // a model without secondary structure: every valid window is 1
+  double* T; size_t t_stride, plane;
+  double* vec;                    // log-space form: two state vectors per thread of a workgroup of the fused scan kernel
+  double* access;
+};
+
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h, node_mea_kernels.hip) over the profile of the
 // whole batch: batch index n with seq_base b and length L writes the row of slot k at node + max_sites * b + k * L (the sampler's
 // layout), n_sites[n], and start / end / score / conf at [n * max_sites + k]
@@ -175,6 +191,9 @@ struct DpArgs {
   // SCAN, posterior motif-node profiles (node_rules.h, log-space form): node.profile non-null = stop after inside + the first
   // outside pass and write the M columns of every position of the sequence order[w]
   NodeArgs node;
+  // SCAN, accessibility (access_rules.h, log-space form): acc.T non-null = stop after inside + the first outside pass and write the
+  // four planes of the sequence order[w] to slot w of acc (the rows k_access_seq reads behind the launch)
+  AccessArgs acc;
 };
 
 // arguments of the diagonal-synchronous train pipeline (train_kernels.hip)
@@ -432,6 +451,10 @@ hipError_t launch_sample(const LinArgs& a, const SampleArgs& s, int G, hipStream
 // it, or behind the fused scan kernel (DpArgs::ctx)
 hipError_t launch_ctx_cells(const LinArgs& a, const CtxArgs& c, int G, int cells_max, hipStream_t st);
 hipError_t launch_ctx_seq(const CtxArgs& c, int G, hipStream_t st);
+// k_access_chains behind launch_lin_scan_group (SCAN_PASS_START) on the same slots and stream (n_vec: the entries of a state vector,
+// max(S, n_ap); Lmax: the longest sequence of the group); k_access_seq behind it, or behind the fused scan kernel (DpArgs::acc)
+hipError_t launch_access_chains(const LinArgs& a, const AccessArgs& c, int G, int Lmax, int n_vec, hipStream_t st);
+hipError_t launch_access_seq(const AccessArgs& c, int G, hipStream_t st);
 // k_node_pos behind launch_lin_scan_group (SCAN_PASS_START) on the same slots and stream: one wave per (sequence, position)
 hipError_t launch_node_pos(const LinArgs& a, const NodeArgs& c, int G, int Lmax, hipStream_t st);
 // k_node_mea behind the node pass of the whole batch (both forms), on the engine's stream: one wave per sequence

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "access_rules.h"
 #include "cond_rules.h"
 #include "ctx_rules.h"
 #include "dp_rules.h"
@@ -598,6 +599,29 @@ __device__ bool run_trace_back(const ModelView& m, const SeqView& q, const Table
   return trace_back(m, q, T, R, c, L, s0, path, rss, stack, cap);
 }
 
+// accessibility on the dense log tables of one sequence (access_rules.h, DpArgs::acc), slot w of the call's planes.  One unit (term,
+// position) per lane of the workgroup's first wave, the lane's two state vectors in its own slice of acc.vec: 2 S doubles per lane,
+// kAccLogLanes lanes per workgroup.
+constexpr int kAccLogLanes = 64;
+__device__ __forceinline__ void access_log_units(const ModelView& m, const SeqView& q, const TableView& Tin, const TableView& Tout,
+                                              double ZL, const AccessArgs& acc, int w) {
+  const int tid = threadIdx.x;
+  if (tid >= kAccLogLanes) return;
+  const AccLog f(ZL);
+  const OneLane ln;
+  const bool live = ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL;
+  const int U = acc.U, S = m.lay.S, L = q.L;
+  double* T = acc.T + (size_t)w * acc.t_stride;
+  double* v0 = acc.vec + ((size_t)blockIdx.x * kAccLogLanes + tid) * 2 * S;
+  for (int t = tid; t < ACC_TERMS * (L + 1); t += kAccLogLanes) {
+    const int term = t & 3, x = t >> 2;
+    double* dst = T + (size_t)term * acc.plane + (size_t)x * U;
+    if (!((acc.terms >> term) & 1)) for (int u = 0; u < U; ++u) dst[u] = 0.;   // (option access_terms)
+    else if (live) access_unit(f, ln, m, q, Tin, Tout, term, x, U, v0, v0 + S, dst);
+    else access_unit_no_parse(term, U, dst);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // the DP kernel: TRAIN = K2 + 2 x K3 fused, BPP = K1, SCAN = K4 + K5 + K6
 // ---------------------------------------------------------------------------------------------
@@ -802,6 +826,10 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
             const int pos = t / a.node.M, node = t - pos * a.node.M;
             prof[t] = live ? node_value(f, nl, m, q, Tin, Tout, pos, node, !no_rss) : node_no_parse(node);
           }
+          continue;
+        }
+        if (a.acc.T) {   // accessibility (access_rules.h): the units (term, position) of this first pass
+          if (!no_rss) access_log_units(m, q, Tin, Tout, ZL, a.acc, w);   // (without secondary structure k_access_seq reads no plane)
           continue;
         }
         if (tid == 0) l_zs[4] = (double)last_argmax(Pys, L);

@@ -297,6 +297,34 @@ def read_context_records(path):
     return out
 
 
+def access_record(rid, access):
+    """Record of one sequence in the `scan --out-access` file: `id: <id>`, then one line per width `u1: [...]` .. `uU: [...]` with
+    the probability that the window of that width starting at every base is unpaired (6 significant digits; `nan` where the
+    window runs off the end); access: an (L, U) array as Engine.accessibility gives it."""
+    access = np.asarray(access, dtype=np.float64)
+    lines = ["id: " + rid] + ["u%d: %s" % (w + 1, fmt_vec(access[:, w])) for w in range(access.shape[1])]
+    return "\n".join(lines) + "\n"
+
+
+def read_access_records(path):
+    """-> list of (id, (L, U) array) from a `scan --out-access` file."""
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+    while k < len(lines) and lines[k].startswith("id: "):
+        rid = lines[k][4:]
+        k += 1
+        cols = []
+        while k < len(lines) and lines[k] and not lines[k].startswith("id: "):
+            head, body = lines[k].split(": ", 1)
+            if head != "u%d" % (len(cols) + 1):
+                raise ValueError("access record %r: line %r where u%d was expected" % (rid, head, len(cols) + 1))
+            body = body.strip("[]")
+            cols.append([float(v) for v in body.split(",")] if body else [])
+            k += 1
+        out.append((rid, np.array(cols, dtype=np.float64).T.reshape(-1, len(cols))))
+    return out
+
+
 def node_record(rid, profile, names, confidence=None):
     """Record of one sequence in the `scan --out-nodes` file: `id: <id>`, then one line per pattern node `<index><name>: [...]`
     with the probability that the node emits each base (6 significant digits); profile: an (L, M) array as Engine.node_profiles
