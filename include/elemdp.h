@@ -121,6 +121,12 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *                       of elemdp_live_blocks_inside (built for it where "loop_prepass" is 0); active wherever "useful_mask" is,
  *                       except in the deterministic mode, where it is ignored; 0: the sweep computes L itself -- the A/B
  *                       switch and the tests' reference
+ *     "own_slots"       1 (default): an unranged train evaluation of a resident batch gives every sequence a table slot of its
+ *                       own where the batch fits the sizing rules (about twice the table memory of the bench configuration);
+ *                       the zeros of the entries "useful_mask" calls useless then stay in the slots from one evaluation to the
+ *                       next of the same plan and options, and are not stored again (elemdp_last_timing entries 3 and 4 say
+ *                       whether, and how many slots the handle holds); 0: the slots of one group, shared by the groups of a
+ *                       stream.  The sequences swept in lockstep and the streams are the same either way
  *   measurement / tests
  *     "profile"         in-kernel phase clocks for elemdp_debug_profile; "dbg": switch phases off (results invalid);
  *     "poison"          1: every table is filled with NaN before an evaluation (an unmasked read of an entry nobody stored shows) */
@@ -380,7 +386,9 @@ int elemdp_node_mea(elemdp_handle* h, const double* x, int32_t n_param, double g
 
 /* timing of the last train evaluation, measured with HIP events on the engine's stream:
  * ms[0] = whole evaluation, ms[1] = the DP pipeline only (all kernels of the inside/outside sweeps),
- * ms[2] = number of sequences the scaled-linear pipeline handed to the log-space pipeline (range check) */
+ * ms[2] = number of sequences the scaled-linear pipeline handed to the log-space pipeline (range check);
+ * with n > 3 also ms[3] = 1 when the last train evaluation of the scaled-linear pipeline found the zeros of the dead entries kept
+ * in its slots and stored none (option "own_slots"), else 0, and ms[4] = the table slots the handle holds */
 int elemdp_last_timing(elemdp_handle* h, double* ms, int32_t n);
 /* debug: summed shader-clock cycles per phase of the last train evaluation when option "profile" = 1:
  * pipeline 2: [stage, inside band, inside exterior, outside exterior, outside band, queue/other];

@@ -571,6 +571,13 @@ class Engine:
         self._lib.elemdp_last_timing(self._h, _dp(ms), 3)
         return ms
 
+    def slot_status(self):
+        """{"zeros_kept": the last train evaluation found the zeros of the dead entries kept in its table slots and stored none
+        (option own_slots), "slots": table slots the handle holds}"""
+        ms = np.zeros(5)
+        self._lib.elemdp_last_timing(self._h, _dp(ms), 5)
+        return {"zeros_kept": bool(ms[3]), "slots": int(ms[4])}
+
     def profile(self):
         c = np.zeros(16)
         self._lib.elemdp_debug_profile(self._h, _dp(c), 16)

@@ -243,6 +243,10 @@ class Engine {
   void debug_tables(double* inside, double* outside, double* inside_o, double* outside_o, double* ENo, double* ENx, double* EH);
   void batch_pairs(int idx, uint8_t* kept, double* lnbpp, int cap);
   double last_ms[3] = {0, 0, 0};
+  // the last train evaluation ran with the zeros of the dead entries kept in the slots (TableSlots::zeros), and the slots the
+  // handle holds: elemdp_last_timing entries 3 and 4
+  bool last_zeros_kept() const { return last_zeros_kept_; }
+  int slots_held() const { return slots_.n_held(); }
 
  private:
   void upload_params(const double* x, const AutomatonLayout& lay, bool trivial);
@@ -280,7 +284,9 @@ class Engine {
   void run_train_batch();
   void run_lin_batch();
   // group_cap: most sequences swept in lockstep (a scan uses fewer: fresh table memory costs ~20 ms / GB)
-  int prepare_lin(LinArgs& a, bool sched1, bool dense_too = false, int n_eval = 0, int group_cap = 8192);
+  // own: the call may give every sequence a slot of its own (option own_slots; decided here: own_map_)
+  int prepare_lin(LinArgs& a, bool sched1, bool dense_too = false, int n_eval = 0, int group_cap = 8192, bool own = false);
+  ZeroBinding zero_binding(const LinArgs& a, bool sched1, bool ranged) const;
   template <class Work> void sweep_groups(const LinArgs& a, int n, const int32_t* h_ord, const int32_t* d_ord, const SeqPlan* d_sorted,
                                           int gsz, int ns, Work work);
   struct ScanPos {   // what a scan's first sum pass writes besides its tables: per position, then per sequence
@@ -303,7 +309,7 @@ class Engine {
   TrArgs log_pipeline_args();
   void init_device();
   void flatten_automaton();
-  void poison_tables();
+  bool poison_tables();
   void lin_weights(int first = 0, int count = 0);
   void upload_automaton();
   bool opt_prune_ = true;   // transition lists pruned to the transitions of complete parses (Automaton::flatten)
@@ -316,6 +322,13 @@ class Engine {
   int range_key_[2] = {-1, -1};
   bool opt_det_ = false;    // deterministic reductions of the scaled-linear train evaluation (LinArgs::det): bit-identical repeats
   bool opt_fast_ = true;    // table-driven unary phases of the train kernels (lin_fast.h); 0 = the generic rule code
+  bool opt_own_slots_ = true;   // option "own_slots": an unranged train evaluation of a resident batch gives every sequence a slot of
+                                // its own where the batch fits (slot_sizing.h), and the zeros of dead entries stay from one evaluation
+                                // to the next; 0: the slots of one group, shared by the groups of a stream
+  bool own_map_ = false;        // the mapping of the last prepare_lin: a slot per sequence, groups cut for lock_slots_ slots
+  int lock_slots_ = 0;
+  bool last_zeros_kept_ = false;
+  unsigned long long plan_gen_ = 0;   // identity of plan_, its mask and its lists (ZeroBinding::plan)
   bool opt_poison_ = false; // tests: the table slots are filled with NaN before every evaluation of the scaled-linear pipeline, so
                             // that a read of an entry nobody stored shows up in the results (the compact tables hold garbage there)
   void require_device() const;
@@ -653,6 +666,7 @@ void Engine::set_option(const std::string& key, double v) {
   else if (key == "dbg") opt_dbg_ = (int)v;
   else if (key == "bpp_log") opt_bpp_log_ = v != 0;
   else if (key == "poison") opt_poison_ = v != 0;
+  else if (key == "own_slots") opt_own_slots_ = v != 0;
   else if (key == "fast") opt_fast_ = v != 0;
   else if (key == "deterministic") opt_det_ = v != 0;
   else if (key == "sorted_plan") opt_sorted_plan_ = v != 0;
@@ -843,6 +857,7 @@ void Engine::ensure_useful_mask() {
   HIP_OK(launch_useful_mask(plan_.ka, (size_t)plan_.n_cells, (size_t)opt_useful_lds_kb_ * 1024, st_));
   plan_.useful_built = true;
   plan_.blk_cpb = plan_.blk_cap = 0;
+  ++plan_gen_;
 }
 
 // The live-block lists of the resident plan for blocks of `cpb` cells that span at most `cap`, from its mask; the largest block
@@ -881,6 +896,7 @@ bool Engine::ensure_live_blocks(int cpb, int cap, bool inside_too) {
   plan_.blk_all = opt_live_blocks_ >= 2;
   plan_.blk_two = inside_too;
   plan_.blk_cpb = cpb; plan_.blk_cap = cap;
+  ++plan_gen_;
   return true;
 }
 
@@ -890,6 +906,7 @@ void Engine::ensure_sorted_plan() {
   if (plan_.permuted) HIP_OK(launch_permute_items(plan_.ka, st_));
   HIP_OK(hipStreamSynchronize(st_));
   plan_.sorted = true;
+  ++plan_gen_;
 }
 
 SlotRequest Engine::slot_request(int S, int row, bool scan, int n_want, int group, int pair_row) const {
@@ -1261,6 +1278,7 @@ void Engine::resident_plan(const uint32_t* mask) {
   // (a ranged evaluation writes the rows of its range only: the rows of a new batch start as zeros, not as what the memory held)
   HIP_OK(hipMemsetAsync(d_seq_out_.as<void>(), 0, sizeof(double) * (size_t)out_stride_ * n, st_));
   slots_.invalidate();   // (a new batch: new Lmax, Wmax)
+  ++plan_gen_;
   HIP_OK(hipStreamSynchronize(st_));
   dbg_lap("load: weights / output buffers");
 }
@@ -1465,10 +1483,12 @@ void Engine::run_train_batch() {
 // The scaled-linear pipeline (lin_kernels.hip); sequences it flags (partition function outside the double range, or a
 // structurally empty component) are re-evaluated by the log-space pipeline, which applies the reference's skip rule.
 // slots, side buffers and the argument record of the scaled-linear pipeline; returns the balanced group size
-void Engine::poison_tables() {
-  if (!opt_poison_) return;
+bool Engine::poison_tables() {   // true: poisoned (whatever zeros the slots held are gone)
+  if (!opt_poison_) return false;
+  slots_.clear_zeros();
   for (DevBuf* b : {&slots_.band_in, &slots_.band_out, &slots_.a_in, &slots_.a_out})
     if (b->bytes()) HIP_OK(hipMemsetAsync(b->as<void>(), 0xff, b->bytes(), st_));   // (all-ones bytes: NaN)
+  return true;
 }
 
 void Engine::lin_weights(int first, int count) {
@@ -1489,7 +1509,7 @@ void Engine::lin_weights(int first, int count) {
   HIP_OK(launch_lin_weights(w, st_));
 }
 
-int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int group_cap) {
+int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int group_cap, bool own) {
   // schedule 1 sweeps the automaton with the shadow copy of (0,0) (one state more per table row); the scan and schedule 0
   // the plain one.  The slots are sized for the wider row.
   const bool shadow = sched1 && lays_.shadow >= 0;
@@ -1503,9 +1523,17 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int
   const size_t free_b = free_device_bytes();
   const int group = balanced_group(lin_group_bytes(Lmax_, Wmax_, row, Sa, nap), n_need, group_cap, opt_group_, slot_budget_, free_b,
                                    slots_.held_bytes(TableSlots::Held::Group));
-  slots_.ensure(slot_request(Sa, row, false, n_need, group, nap), free_b);
+  SlotRequest rq = slot_request(Sa, row, false, n_need, group, nap);
+  // a slot per sequence where the call may have it and the batch fits: more slots, the same groups (lock_slots_)
+  own_map_ = own && opt_own_slots_ && !inner_ && !dense_too &&
+             own_slots_fit(n_need, lin_group_bytes(Lmax_, Wmax_, row, Sa, nap), rq.per_slot(), opt_group_, opt_slots_, slot_budget_, free_b,
+                           slots_.held_bytes(TableSlots::Held::Group), slots_.held_bytes(TableSlots::Held::Slots));
+  if (own_map_) rq.group = n_need;
+  slots_.ensure(rq, free_b);
+  if (own_map_ && slots_.n() < n_need) own_map_ = false;   // (the allocation had to shrink after all: the shared mapping)
+  lock_slots_ = lockstep_slots(own_map_, group, n_need, slots_.n());
   // (if the allocation had to shrink, rebalance for the slots we got)
-  const int gsz = even_groups(n_need, slots_.n());
+  const int gsz = even_groups(n_need, lock_slots_);
   std::memset(&a, 0, sizeof(a));
   a.lay = L;
   a.layp = shadow ? d_lays_.as<AutomatonLayout>() : d_lay_.as<AutomatonLayout>();
@@ -1559,12 +1587,11 @@ int Engine::prepare_lin(LinArgs& a, bool sched1, bool dense_too, int n_eval, int
 template <class Work>
 void Engine::sweep_groups(const LinArgs& a, int n, const int32_t* h_ord, const int32_t* d_ord, const SeqPlan* d_sorted, int gsz,
                           int ns, Work work) {
-  const int slots_each = slots_.n() / ns;
-  if (ns > 1) {   // every stream the same number of groups
-    int n_groups = (n + slots_each - 1) / slots_each;
-    n_groups = ((n_groups + ns - 1) / ns) * ns;
-    gsz = (n + n_groups - 1) / n_groups;
-  }
+  // (a slot per sequence: the groups are cut as for the slots of the shared mapping, only their slots differ -- slot_sizing.h)
+  const int n_lock = own_map_ ? lock_slots_ : slots_.n();
+  const int slots_each = n_lock / ns;
+  gsz = stream_group(n, gsz, n_lock, ns);   // every stream the same number of groups
+  if (own_map_ && slots_.n() < n) throw StateError("sweep_groups: fewer slots than sequences under the own-slot mapping");
   need_group_streams(ns);
   if (ns > 1) {   // the other streams start behind what st_ has queued so far ...
     HIP_OK(hipEventRecord(gstart_, st_));
@@ -1573,7 +1600,7 @@ void Engine::sweep_groups(const LinArgs& a, int n, const int32_t* h_ord, const i
   int gi = 0;
   for (int g0 = 0; g0 < n; g0 += gsz, ++gi) {
     const int k = gi % ns;
-    const size_t k0 = (size_t)k * slots_each;
+    const size_t k0 = group_slot_base(own_map_, g0, k, slots_each);
     LinArgs ak = a;
     ak.band_in += k0 * a.band_stride; ak.band_out += k0 * a.band_stride;
     ak.ext_in += k0 * a.ext_stride; ak.ext_out += k0 * a.ext_stride;
@@ -1606,6 +1633,23 @@ int Engine::read_flagged(std::vector<int32_t>* list) {
   return n_flagged;
 }
 
+// The binding of the zeros a train evaluation with the arguments `a` leaves in the dead entries of the slots (slot_sizing.h); not
+// valid where it leaves none a later one could build on: a range of the batch, the shared slot mapping, no mask, the generic
+// kernels (which store every entry), a timing experiment.
+ZeroBinding Engine::zero_binding(const LinArgs& a, bool sched1, bool ranged) const {
+  ZeroBinding z;
+  z.valid = own_map_ && !ranged && a.p.useful != nullptr && lin_train_cpb(a) > 0 && !a.no_rss && a.dbg == 0 && !opt_first_pass_only_ &&
+            !opt_profile_;
+  z.plan = plan_gen_;
+  z.slots_gen = slots_.generation(); z.n_slots = slots_.n(); z.band_stride = slots_.band_stride();
+  z.own = own_map_ ? 1 : 0; z.n_seq = n_seq_;
+  z.S = a.lay.S; z.tab_row = a.lay.tab_row; z.ap_rs = a.lay.ap_rs; z.shadow = a.lay.shadow; z.schedule = sched1 ? 1 : 0;
+  // (the options as they are set: what they come to in this evaluation follows from them, the layout and the plan)
+  z.useful_mask = opt_useful_mask_ ? 1 : 0; z.loop_prepass = opt_loop_prepass_ ? 1 : 0; z.loop_outside = opt_loop_outside_ ? 1 : 0;
+  z.live_blocks = opt_live_blocks_; z.live_span = opt_live_span_; z.deterministic = opt_det_ ? 1 : 0; z.fast = a.fast;
+  return z;
+}
+
 void Engine::run_lin_batch() {
   const bool sched1 = opt_schedule_ == 1 && linear_ok_ && !opt_first_pass_only_ && lay_.s00 == 0 && lays_.shadow >= 0;
   LinArgs a;
@@ -1613,7 +1657,10 @@ void Engine::run_lin_batch() {
   const bool ranged = opt_eval_count_ > 0 && !(opt_eval_first_ == 0 && opt_eval_count_ == n_seq_);
   const int r0 = ranged ? opt_eval_first_ : 0, n_ev = ranged ? opt_eval_count_ : n_seq_;
   if (r0 < 0 || n_ev <= 0 || r0 + n_ev > n_seq_) throw ArgError("eval_first / eval_count outside the resident batch");
-  int gsz = prepare_lin(a, sched1, false, n_ev);
+  // (what zeros the slots hold: taken before anything of this evaluation touches them)
+  ZeroBinding had = slots_.take_zeros();
+  last_zeros_kept_ = false;
+  int gsz = prepare_lin(a, sched1, false, n_ev, 8192, !ranged);
   if (opt_useful_mask_) ensure_useful_mask();
   a.p.useful = opt_useful_mask_ ? plan_.useful.as<uint8_t>() : nullptr;   // (the train sweeps only: the scan family sees null)
   // the loop pre-pass goes with the mask (the launcher drops it where the table-driven form does not run)
@@ -1649,7 +1696,7 @@ void Engine::run_lin_batch() {
     h_ord = h_order_r_.data();
     d_ord = d_order_r_.as<int32_t>();
     d_sorted = d_plans_sorted_r_.as<SeqPlan>();
-    gsz = even_groups(n_ev, slots_.n());
+    gsz = even_groups(n_ev, lock_slots_);
   }
   HIP_OK(hipMemsetAsync(d_seq_out_.as<double>() + (size_t)r0 * out_stride_, 0, sizeof(double) * (size_t)out_stride_ * n_ev, st_));
   HIP_OK(hipMemsetAsync(d_flagged_.as<void>(), 0, sizeof(int32_t), st_));
@@ -1663,9 +1710,12 @@ void Engine::run_lin_batch() {
   }
   HIP_OK(hipEventRecord(ev_[1], st_));
   lin_weights(r0, n_ev);
-  poison_tables();
+  if (poison_tables()) had = ZeroBinding();
+  // the dead entries of these slots still hold the zeros of this very binding: the sweeps store none of them
+  const ZeroBinding zb = zero_binding(a, sched1, ranged);
+  a.zeros_kept = zeros_match(had, zb) ? 1 : 0;
   // (concurrent groups: not for a handful of sequences, whose tables debug_tables reads, nor under the phase profile)
-  const int ns = group_streams(n_ev >= 64 && slots_.n() >= 64 && !opt_profile_);
+  const int ns = group_streams(n_ev >= 64 && lock_slots_ >= 64 && !opt_profile_);
   sweep_groups(a, n_ev, h_ord, d_ord, d_sorted, gsz, ns, [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
     HIP_OK(launch_lin_group(ak, G, Lg, Wg, opt_first_pass_only_, st));
   });
@@ -1676,8 +1726,10 @@ void Engine::run_lin_batch() {
     last_prof.assign(16, 0);
     for (size_t k = 0; k < hp.size(); ++k) last_prof[k % 16] += hp[k];
   }
-  if (n_flagged == 0) slots_.set_holds(TableSlots::Holds::Linear, a.lay.S);
+  // (the zeros stand behind an evaluation that stored or kept them, covered every resident sequence and flagged none)
+  if (n_flagged == 0) slots_.set_holds(TableSlots::Holds::Linear, a.lay.S, zb.valid ? &zb : nullptr);
   else slots_.set_holds(TableSlots::Holds::DenseLog);
+  last_zeros_kept_ = a.zeros_kept != 0;
   if (n_flagged > 0) {
     ensure_sorted_plan();   // (the log-space kernels sum the role lists in list order: kernels.h)
     TrArgs t = log_pipeline_args();
@@ -3278,6 +3330,8 @@ int elemdp_pair_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, dou
 int elemdp_last_timing(elemdp_handle* h, double* ms, int32_t n) {
   if (!h || !ms) return ELEMDP_EINVAL;
   for (int k = 0; k < n && k < 3; ++k) ms[k] = h->e->last_ms[k];
+  if (n > 3) ms[3] = h->e->last_zeros_kept() ? 1. : 0.;
+  if (n > 4) ms[4] = (double)h->e->slots_held();
   return ELEMDP_OK;
 }
 int elemdp_debug_profile(elemdp_handle* h, double* cycles, int32_t n) {

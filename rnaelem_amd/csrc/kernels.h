@@ -327,6 +327,10 @@ struct LinArgs {
   // (Z = 0) is left alone by that sweep.  range_all: 1 = the range check of the inside pass looks at all three Z, as the train
   // evaluation's does, except that a Z of exactly 0 is an empty world and no range failure
   int32_t scan_terms = 0, range_all = 0;
+  // train sweeps under the mask: 1 = every entry the mask calls useless already holds its 0 in these slots (an earlier evaluation of
+  // the same plan on the same slots stored it: TableSlots::zeros), so the sweeps store none -- no fill of dead cells or rows, no 0
+  // from the dead branch of the pair phases, dead workgroups return at once
+  int32_t zeros_kept = 0;
 };
 struct LinWeightArgs {
   const LoopItem* items_inner; const LoopItem* items_left; const LoopItem* items_right;   // (may be null)

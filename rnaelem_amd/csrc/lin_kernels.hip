@@ -655,7 +655,7 @@ __device__ __forceinline__ void fill_dead_cells(const TableView& T, unsigned lon
 // The cells of a workgroup of the train sweeps that take lists: block bx of the diagonal's live-block list (plan_rules.h).
 // sweep: false = nothing to sweep (beyond the list; workgroup 0 of a diagonal without a live cell still owns its zeros)
 struct LiveCells { int i0, nc, span, own_lo, own_end; unsigned long long live; bool sweep; };
-__device__ __forceinline__ LiveCells live_cells(const SeqView& q, int d, int bx, int ncell) {
+__device__ __forceinline__ LiveCells live_cells(const SeqView& q, int d, int bx, int ncell, bool kept) {
   LiveCells r;
   // ONE load behind the plan record: the slots behind a diagonal's last block hold zeros (count 0), so the workgroup needs no count
   const int nslot = live_blocks_slots(q.L), slot = bx < nslot ? bx : nslot - 1;
@@ -671,7 +671,7 @@ __device__ __forceinline__ LiveCells live_cells(const SeqView& q, int d, int bx,
   r.live = r.sweep ? b.live : 0ull;
   r.span = r.sweep ? 64 - __builtin_clzll(b.live | 1ull) : 0;
   r.own_lo = r.sweep ? b.own_lo : 0;
-  r.own_end = r.sweep ? b.own_end : (bx == 0 ? ncell : 0);   // (no block 0: the diagonal has no live cell)
+  r.own_end = r.sweep ? b.own_end : ((bx == 0 && !kept) ? ncell : 0);   // (no block 0: the diagonal has no live cell)
   return r;
 }
 
@@ -703,12 +703,14 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
   static_assert(!LPRE || (FAST && !CON), "loop pre-pass: the table-driven train form only");
   constexpr int kDeadL = LPRE ? -1 : (int)ST_L;   // (the L rows of dead cells: the pre-pass has stored them)
   constexpr bool lists = LISTS;
+  // the dead entries of these slots hold their zeros from an earlier evaluation of the same plan (LinArgs::zeros_kept): none is stored
+  const bool kept = MASK && a.zeros_kept != 0;
   int i0 = bx * cpb, nc = 0, span = 0;
   unsigned long long live = 0ull;
   if (lists) {
-    const LiveCells lc = live_cells(v.q, d, (int)bx, ncell);
+    const LiveCells lc = live_cells(v.q, d, (int)bx, ncell, kept);
     // (the zeros of the dead cells the block owns: an entry that is parsable but useless still has readers)
-    if (lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.in, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, kDeadL, ST_2, ST_1, ST_M);
+    if (!kept && lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.in, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, kDeadL, ST_2, ST_1, ST_M);
     if (!lc.sweep) return;
     i0 = lc.i0; nc = lc.nc; span = lc.span; live = lc.live;
   } else {
@@ -722,7 +724,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
     const int ys = a.ys[v.n];
     if (ys < i0 || ys - d + 1 > i0 + nc - 1) return;
   }
-  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid, LPRE ? (UB_ALL & ~UB_L) : UB_ALL)) { fill_dead_rows(v.in, d, i0, nc, tid, kDeadL, ST_2, ST_1, ST_M); return; }
+  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid, LPRE ? (UB_ALL & ~UB_L) : UB_ALL)) { if (!kept) fill_dead_rows(v.in, d, i0, nc, tid, kDeadL, ST_2, ST_1, ST_M); return; }
   const int HD = FAST ? A.n_lane : S;   // stride of the heavy sums per cell: the live states (table-driven: their index among them), or all
   const int CS = cpb * HD;
   constexpr int NW = 1;                      // (one copy of the heavy sums in either mode: see the deterministic mode above)
@@ -816,7 +818,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
         // before this phase)
         const bool dead = MASK && exists && !(v.q.ubits(i, d) & UB_A);
         if (dead) {
-          v.in.a(d, i, p) = 0.;
+          if (!kept) v.in.a(d, i, p) = 0.;
         } else if (exists) {
           BitIter it;
           it.init(v.q.okbits_end, j * W1, 1, d - dmi);
@@ -1518,11 +1520,12 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
   static_assert(!LPOST || (FAST && MODE == OUT_TRAIN), "the L plane behind the sweep: the table-driven train form only");
   constexpr int kDeadL = LPOST ? -1 : ST_L;   // (the L rows belong to the kernels behind the sweep)
   constexpr bool lists = LISTS;   // (as in k4_in: the live cells of block bx)
+  const bool kept = MASK && a.zeros_kept != 0;   // (as in k4_in: no zero of a dead entry is stored)
   int i0 = bx * cpb, nc = 0, span = 0;
   unsigned long long live = 0ull;
   if (lists) {
-    const LiveCells lc = live_cells(v.q, d, (int)bx, ncell);
-    if (lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.out, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, kDeadL, ST_2, ST_M, -1);
+    const LiveCells lc = live_cells(v.q, d, (int)bx, ncell, kept);
+    if (!kept && lc.own_end - lc.own_lo > lc.nc) fill_dead_cells(v.out, lc.live, lc.i0, d, lc.own_lo, lc.own_end, tid, kDeadL, ST_2, ST_M, -1);
     if (!lc.sweep) return;
     i0 = lc.i0; nc = lc.nc; span = lc.span; live = lc.live;
   } else {
@@ -1536,7 +1539,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     // reader.  Workgroups whose cells all satisfy j <= Ys return: on average half of the sweep.
     if (!(a.dbg & 4096) && i0 + nc - 1 + d <= a.ys[v.n]) return;
   }
-  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid, LPOST ? (UB_ALL & ~UB_L) : UB_ALL)) { fill_dead_rows(v.out, d, i0, nc, tid, kDeadL, ST_2, ST_M, -1); return; }
+  if (MASK && !lists && block_is_dead(v.q, d, i0, nc, tid, LPOST ? (UB_ALL & ~UB_L) : UB_ALL)) { if (!kept) fill_dead_rows(v.out, d, i0, nc, tid, kDeadL, ST_2, ST_M, -1); return; }
   const int HD = FAST ? A.n_lane : S;   // (as in k4_in)
   const int CS = cpb * HD;
   // ONE copy of the heavy sums (deterministic mode: each gets its adds from one wave, see the top of the file); the statistics,
@@ -1938,7 +1941,7 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
         const bool exists = dmi > 0 && dmi < d;      // (otherwise the entry does not exist)
         const bool dead = MASK && exists && !((crfl[c] >> CF_USH) & UB_A);
         if (dead) {                    // a useless entry: 0, nothing loaded
-          out.a(d, i, p) = 0.;
+          if (!kept) out.a(d, i, p) = 0.;
         } else if (exists) {
           const bool step = d + 1 <= W && j < L && v.q.unp[j];
           const int nr = step ? (r1 >> 20) & 15 : 0;
@@ -2814,10 +2817,12 @@ static GroupGeom group_geometry(const LinArgs& full, int G, int Lmax, int Wmax, 
 // largest block count of the diagonal in the plan -- at least one: workgroup 0 of a diagonal without a live cell stores its zeros
 // (blk_grid[d] < 0: the plan found that the lists of this diagonal save no workgroups worth their cost -- consecutive cells there:
 // either scheme stores every entry of the diagonal, so the choice is free per launch)
+// 0: no launch -- the zeros are kept in the slots (LinArgs::zeros_kept) and no sequence of the plan has a live block on the diagonal
 static unsigned band_blocks(LinArgs& a, int ncell, bool train) {
   const int n = (ncell + a.cpb - 1) / a.cpb;
   if (!train || !a.blk_grid || !a.p.blocks) return (unsigned)n;
   if (a.blk_grid[a.d] < 0) { a.p.blocks = nullptr; return (unsigned)n; }
+  if (a.zeros_kept && a.blk_grid[a.d] == 0) return 0u;
   return (unsigned)std::max(1, std::min(n, a.blk_grid[a.d]));
 }
 // The inside sweep of a group: the band diagonals 0 .. Wmax (`bands`: the train has none without pairs, no_rss), then the
@@ -2842,6 +2847,7 @@ static void inside_sweeps(GroupGeom& g, int G, int Lmax, int Wmax, bool bands, h
       LinArgs ad = ai;
       ad.d = d;
       const unsigned gx = band_blocks(ad, ncell, !CON);
+      if (!gx) continue;
       launch_k4_in<CON>(ad, dim3(gx, G), g.lds_in, g.fast, g.big, st);
     }
   if (g.stage_ext) hipLaunchKernelGGL((k4_in_ext<true, CON>), dim3(G), dim3(g.ext_nt), g.lds_ext_in, st, a);
@@ -2864,6 +2870,7 @@ static void outside_bands(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t s
     LinArgs ad = ao;
     ad.d = d;
     const unsigned gx = band_blocks(ad, ncell, MODE == OUT_TRAIN);
+    if (!gx) continue;
     launch_k4_out<MODE>(ad, dim3(gx, G), g.lds_out, g.fast, g.big, st);
   }
   if (post) {

@@ -84,4 +84,58 @@ inline size_t lin_group_bytes(int Lmax, int Wmax, int row, int Sa, int nap) {
   return (cells * row + ext * Sa) * 2 * sizeof(double) + ext * Sa * 3 * sizeof(double) + cells * nap * 2 * sizeof(double);
 }
 
+// The group size a sweep over ns streams ends up with: the n_slots slots are shared out evenly, every stream gets the same number
+// of groups (one stream: gsz as it came).
+inline int stream_group(int n, int gsz, int n_slots, int ns) {
+  if (ns <= 1) return gsz;
+  const int slots_each = std::max(1, n_slots / ns);
+  int n_groups = (n + slots_each - 1) / slots_each;
+  n_groups = ((n_groups + ns - 1) / ns) * ns;
+  return (n + n_groups - 1) / n_groups;
+}
+
+// ---- a slot per sequence (option own_slots): an unranged train evaluation of a resident batch gives every sequence the slot of
+// its position in processing order, so that what one evaluation leaves in a slot is still there for the next one of the same plan
+// (the zeros of the dead entries: ZeroBinding).  The sequences swept in lockstep and the streams stay what they are without it.
+//
+// Do n sequences get a slot each?  Only inside both sizing rules -- the 68 % of balanced_group over a group's bytes per sequence
+// and the 72 % of slots_sized over a slot's, each within an inner handle's budget -- and not where option `group` or `slots`
+// asks for fewer slots than sequences.
+inline bool own_slots_fit(int n, size_t group_bytes, size_t per_slot_bytes, int opt_group, int opt_slots, size_t budget_in, size_t free_b,
+                          size_t held_group_b, size_t held_slots_b) {
+  if (n < 1 || (opt_group > 0 && opt_group < n) || (opt_slots > 0 && opt_slots < n)) return false;
+  auto inside = [&](size_t per, size_t reach, double frac) {
+    size_t budget = (size_t)((double)reach * frac);
+    if (budget_in > 0) budget = std::min(budget, budget_in);
+    return per * (size_t)n <= budget;
+  };
+  return inside(group_bytes, free_b + held_group_b, 0.68) && inside(per_slot_bytes, free_b + held_slots_b, 0.72);
+}
+// the slots the groups of a sweep are cut for: with a slot per sequence still the `group` sequences of the shared mapping
+inline int lockstep_slots(bool own, int group, int n, int n_slots) { return own ? std::max(1, std::min(group, n)) : n_slots; }
+// first slot of the group that starts at position g0 of the processing order and runs on stream k (slots_each slots per stream)
+inline size_t group_slot_base(bool own, int g0, int k, int slots_each) { return own ? (size_t)g0 : (size_t)k * slots_each; }
+
+// "The dead entries of these slots hold the zeros of this binding": everything the set of entries the usefulness mask calls useless,
+// and their addresses, depend on.  An evaluation whose binding matches the one the slots hold stores none of those zeros again
+// (LinArgs::zeros_kept).
+struct ZeroBinding {
+  bool valid = false;              // false: the slots hold no such zeros (or the evaluation is none that could leave them)
+  unsigned long long plan = 0;     // identity of the plan: bumped by load_batch and by whatever rebuilds the plan, its mask or its lists
+  unsigned slots_gen = 0;          // the slots: their sizing generation, count, band stride; the mapping (a slot per sequence) and
+  int n_slots = 0;                 // the sequences it covers
+  size_t band_stride = 0;
+  int own = 0, n_seq = 0;
+  int S = 0, tab_row = 0, ap_rs = 0, shadow = 0, schedule = 0;   // the layout that was swept
+  int useful_mask = 0, loop_prepass = 0, loop_outside = 0, live_blocks = 0, live_span = 0, deterministic = 0, fast = 0;   // options
+};
+inline bool zeros_match(const ZeroBinding& held, const ZeroBinding& want) {
+  return held.valid && want.valid && held.plan == want.plan && held.slots_gen == want.slots_gen && held.n_slots == want.n_slots &&
+         held.band_stride == want.band_stride && held.own == want.own && held.n_seq == want.n_seq && held.S == want.S &&
+         held.tab_row == want.tab_row && held.ap_rs == want.ap_rs && held.shadow == want.shadow && held.schedule == want.schedule &&
+         held.useful_mask == want.useful_mask && held.loop_prepass == want.loop_prepass && held.loop_outside == want.loop_outside &&
+         held.live_blocks == want.live_blocks && held.live_span == want.live_span && held.deterministic == want.deterministic &&
+         held.fast == want.fast;
+}
+
 }  // namespace elemdp

@@ -25,7 +25,20 @@ struct TableSlots {
   size_t band_stride() const { return g_.band_stride; }
   Holds holds() const { return holds_; }
   int linear_S() const { return linear_S_; }   // states per row of Holds::Linear tables (one more with the shadow state)
-  void set_holds(Holds h, int linear_S = 0) { holds_ = h; linear_S_ = linear_S; }
+  // zeros: the binding whose dead entries the slots hold as zeros behind this call (a train evaluation's own record; anything
+  // else that says what the slots hold leaves none)
+  void set_holds(Holds h, int linear_S = 0, const ZeroBinding* zeros = nullptr) {
+    holds_ = h; linear_S_ = linear_S;
+    zeros_ = zeros ? *zeros : ZeroBinding();
+  }
+  // The zeros the slots hold (ZeroBinding::valid false: none).  A train evaluation TAKES the record before it touches the slots --
+  // they then hold none until it sets its own --; ensure(), set_holds(), invalidate() and release() all drop it, so a call that
+  // sweeps anything else over the slots cannot leave it standing.
+  const ZeroBinding& zeros() const { return zeros_; }
+  ZeroBinding take_zeros() { const ZeroBinding z = zeros_; zeros_ = ZeroBinding(); return z; }
+  void clear_zeros() { zeros_ = ZeroBinding(); }
+  unsigned generation() const { return gen_; }   // sizings so far: part of a ZeroBinding
+  int n_held() const { return g_.n; }            // slots the buffers are sized for, whatever they hold
 
   size_t held_bytes(Held set) const {
     const size_t band = band_in.bytes() + band_out.bytes(), ext = ext_in.bytes() + ext_out.bytes();
@@ -39,6 +52,7 @@ struct TableSlots {
   // Slots for the request, given the free device memory: what is there is kept if it serves (no reset -- DevBuf::alloc keeps what
   // is large enough), else sized afresh.  The pair tables follow the slot count in the same call.
   void ensure(const SlotRequest& r, size_t free_b) {
+    clear_zeros();
     if (holds_ == Holds::Trace) invalidate();
     Lmax_ = r.Lmax; S_dense_ = r.S_dense;
     if (!slots_keep(g_, r)) {
@@ -67,7 +81,7 @@ struct TableSlots {
     tr_stack.alloc((size_t)g_.n * trace_stack_stride(Lmax_) * sizeof(int32_t));
   }
   // keeps the memory, forgets what it was sized for and what it holds: the next ensure() sizes afresh
-  void invalidate() { g_ = SlotGeometry(); set_holds(Holds::Nothing); }
+  void invalidate() { g_ = SlotGeometry(); ++gen_; set_holds(Holds::Nothing); }
   void release() {
     for (DevBuf* d : {&band_in, &band_out, &ext_in, &ext_out, &tmp, &tr_ext, &tr_stack, &zs, &a_in, &a_out}) d->reset();
     invalidate();
@@ -76,6 +90,8 @@ struct TableSlots {
  private:
   SlotGeometry g_;
   Holds holds_ = Holds::Nothing;
+  ZeroBinding zeros_;
+  unsigned gen_ = 0;
   int linear_S_ = 0, Lmax_ = 0, S_dense_ = 0;
 };
 
