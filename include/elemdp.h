@@ -344,6 +344,25 @@ int elemdp_context_profile(elemdp_handle* h, const double* x, int32_t n_param, d
  * handed to the log-space form].  elemdp_scan, the pair calls (the list of the last one stays valid), elemdp_sample,
  * elemdp_context_profile and the train calls are unaffected. */
 int elemdp_node_profile(elemdp_handle* h, const double* x, int32_t n_param, double* profile);
+/* Joint node-by-context posteriors under the motif model x and the emission counts behind a motif logo.  With
+ * M = elemdp_n_node and the letters c = O L R H B I M (the column order of elemdp_context_profile), J(p, m, c) is the probability
+ * that base p of a sequence is emitted by pattern node m AND carries structure letter c, over the ensemble of the scan's first sum
+ * pass (terminals ari and nasi, Z(ari, nasi): the ensemble of elemdp_context_profile and elemdp_node_profile), from its inside /
+ * outside tables.  O, L, R and M are the rule-8, pair-left, pair-right and 3a + 5a parts of elemdp_node_profile routed by letter;
+ * the L <- L part splits into H, B and I: the outside L entry is linear in its seeds, so the hairpin seeds (rule 6b) and the bulge
+ * seeds (the rule-6c items with one empty run) are carried down every row by the L <- L chain on their own, and
+ * I = max(0, L <- L part - H - B).  Every entry is clamped to [0, 1]; nothing is renormalised.  sum_c J(p, m, c) is the node
+ * profile and sum_m J(p, m, c) the context profile, wherever the tables' inside and outside agree (max_iloop 30).
+ *   counts:  required; counts[((n M + m) 7 + c) 5 + b] = sum_p J(p, m, c) [seq_n[p] = b], b = 0 .. 4 (N A C G U), reduced on
+ *            the device in a fixed order: the logo table of a set of sequences is the sum of their blocks;
+ *   profile: NULL, or 7 M doubles per position at 7 M (seq_off[n] + p) + 7 m + c (then the profile is copied to the host, else it
+ *            stays on the device).
+ * A sequence without any parse (Z = 0) has J(p, 0, O) = 1 and 0 elsewhere, exactly; under ELEMDP_NO_RSS rule 8 alone exists.
+ * Sequences that leave the double range of the scaled-linear tables, and every sequence under option pipeline 3, go through the
+ * same rule on the log-space tables of the fused scan kernel.  counts NULL or more than 255 pattern nodes is ELEMDP_EINVAL, a call
+ * before elemdp_load_batch ELEMDP_ESTATE.  elemdp_last_timing afterwards: [whole call, sum passes + joint kernels, sequences handed
+ * to the log-space form].  The other calls of the handle are unaffected; the list of the last pair call stays valid. */
+int elemdp_joint_profile(elemdp_handle* h, const double* x, int32_t n_param, double* counts, double* profile);
 /* Accessibility under the motif model x: with U = max_width, access[U * (seq_off[n] + p) + (w - 1)], p 0-based,
  * w = 1 .. U, is the probability that the bases p .. p+w-1 of sequence n are all unpaired, over the ensemble of the scan's first sum
  * pass (terminals ari and nasi, Z(ari, nasi): the ensemble of elemdp_pair_posteriors and elemdp_context_profile), from its inside /

@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_joint_profile", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -93,6 +93,7 @@ def load_library():
         L.elemdp_sample.argtypes = [hp, dp, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_char_p, C.POINTER(C.c_uint8), dp, i32]
         L.elemdp_context_profile.argtypes = [hp, dp, C.c_int32, dp]
         L.elemdp_node_profile.argtypes = [hp, dp, C.c_int32, dp]
+        L.elemdp_joint_profile.argtypes = [hp, dp, C.c_int32, dp, dp]
         L.elemdp_accessibility.argtypes = [hp, dp, C.c_int32, C.c_int32, dp]
         L.elemdp_node_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_int32, dp, u8, i32, i32, i32, dp, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
@@ -519,6 +520,25 @@ class Engine:
         self._check(self._lib.elemdp_node_profile(self._h, _dp(x), self.n_param, _dp(prof)))
         return [prof[M * int(off[k]):M * int(off[k + 1])].reshape(-1, M).copy() for k in range(self.n_seq)]
 
+    # ---- joint node-by-context posteriors and emission counts
+    def joint_profiles(self, x, profile=False):
+        """counts, an (n, M, 7, 5) array: the expected number of emissions of each base (N A C G U) by each pattern node (the
+        node order of node_profiles) under each structure letter (the column order of CONTEXT_LETTERS), per sequence, reduced on
+        the device -- the table behind a motif logo (motif_logo).  With profile=True returns (counts, profiles): one (L, M, 7)
+        array per sequence, the probability that a base is emitted by the node and carries the letter; its sum over the letters
+        is node_profiles, its sum over the nodes context_profiles.  Else the profile stays on the device."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        M, n = self.n_node, max(self.n_seq, 0)
+        n_pos = int(off[-1]) if off is not None else 0
+        counts = np.zeros(max(n * M * 35, 1))
+        prof = np.zeros(max(7 * M * n_pos, 1)) if profile else None
+        self._check(self._lib.elemdp_joint_profile(self._h, _dp(x), self.n_param, _dp(counts), _dp(prof)))
+        counts = counts[:n * M * 35].reshape(n, M, 7, 5)
+        if not profile:
+            return counts
+        return counts, [prof[7 * M * int(off[k]):7 * M * int(off[k + 1])].reshape(-1, M, 7).copy() for k in range(self.n_seq)]
+
     # ---- accessibility (DESIGN.md section 19)
     def accessibility(self, x, max_width=16):
         """One (L, U) array per sequence, U = max_width (1 .. 64): column w-1 of row p is the probability that the bases
@@ -597,3 +617,35 @@ def alignment_confidence(profile, psihat):
     if psihat.size and (psihat.min() < 0 or psihat.max() >= profile.shape[1]):
         raise ValueError("alignment_confidence: node index out of range")
     return profile[np.arange(profile.shape[0]), psihat]
+
+
+def motif_logo(counts, weights=None):
+    """The table behind a motif logo from the (n, M, 7, 5) counts of Engine.joint_profiles: the counts are summed over the
+    sequences in input order, each times its weight if weights are given.  Returns a dict of arrays over the M pattern nodes:
+    counts (M, 7, 5), the weighted sum; occurrences (M,), the expected number of bases the node emits; base_freq (M, 4), the
+    frequencies of A C G U among the emissions with a known base; letter_freq (M, 7), the frequencies of the structure letters
+    O L R H B I M; information (M,), 2 - H2 of base_freq in bits.  A node that emits nothing has frequencies and information 0.
+    There is no small-sample correction: the counts are expectations, not a sample."""
+    counts = np.asarray(counts, dtype=np.float64)
+    if counts.ndim != 4 or counts.shape[2:] != (7, 5):
+        raise ValueError("motif_logo: (n, M, 7, 5) counts are expected")
+    n, M = counts.shape[:2]
+    if weights is None:
+        w = np.ones(n)
+    else:
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError("motif_logo: one weight per sequence is expected")
+    total = np.zeros((M, 7, 5))
+    for k in range(n):
+        total += w[k] * counts[k]
+    occ = total.sum(axis=(1, 2))
+    known = total[:, :, 1:].sum(axis=1)
+    ksum = known.sum(axis=1)
+    base = np.divide(known, ksum[:, None], out=np.zeros_like(known), where=ksum[:, None] > 0)
+    letters = total.sum(axis=2)
+    letter = np.divide(letters, occ[:, None], out=np.zeros_like(letters), where=occ[:, None] > 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h2 = -np.where(base > 0, base * np.log2(np.where(base > 0, base, 1.0)), 0.0).sum(axis=1)
+    info = np.where(ksum > 0, 2.0 - h2, 0.0)
+    return dict(counts=total, occurrences=occ, base_freq=base, letter_freq=letter, information=info)

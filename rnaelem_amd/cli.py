@@ -23,6 +23,10 @@
     python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-access access.txt
                                     # + accessibility: the probability that the window of width 1 .. --access-width (16) at
                                     #   every base is unpaired (io.access_record)
+    python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-logo logo.txt
+                                    # + the table behind a motif logo: per pattern node the expected emission counts of each base
+                                    #   under each structure letter, over the sequences with exist_prob >= --logo-min-exist (0)
+                                    #   (io.write_logo)
     python -m rnaelem_amd.cli       --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --out2 scan.raw
                                     # no sub-command = what script/elem spawns: train, write the model, scan (main.cpp:47-84)
     python -m rnaelem_amd.cli eval  --fastq pos.fq --motif-model model.txt --out1 fn.txt --out2 gr.txt     (motif_eval.hpp:23-54)
@@ -98,6 +102,11 @@ def build_parser():
                                      help="accessibility under the motif model, the probability that a window of bases is unpaired: "
                                           "one record per sequence (io.access_record)")
     sub.choices["scan"].add_argument("--access-width", type=int, default=16, help="widest window (1 .. 64)")
+    sub.choices["scan"].add_argument("--out-logo", default=None,
+                                     help="the table behind a motif logo: per pattern node the expected emission counts of each base "
+                                          "under each structure letter, summed over the sequences (io.write_logo)")
+    sub.choices["scan"].add_argument("--logo-min-exist", type=float, default=0.0,
+                                     help="only sequences whose exist_prob is at least this enter the logo table")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -265,8 +274,10 @@ def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
 
 def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0,
                   out_samples=None, n_samples=100, sample_seed=0, out_context=None, out_nodes=None, out_sites=None, site_gamma=1.0,
-                  max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0, out_access=None, access_width=16):
+                  max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0, out_access=None, access_width=16, out_logo=None,
+                  logo_min_exist=0.0):
     from .distributed import assigned_range
+    logo_parts = None if out_logo is None else out_logo + ".seqs"     # (per-sequence counts, joined in input order before the sum)
     nodes = eng.describe()["node"]
     step = max(1, chunk)
     lo = assigned_range(len(recs), world, rank)[0]     # (batch-global sequence index of this rank's first record: the samples' key)
@@ -277,7 +288,7 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
             if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None \
-                    and out_contrast is None and out_access is None:
+                    and out_contrast is None and out_access is None and out_logo is None:
                 for (rid, codes, _), r in zip(part, res):
                     yield io.scan_record(rid, codes, r, nodes)
                 continue
@@ -296,6 +307,7 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                 nod = eng.node_profiles(m["x"]) if out_nodes is not None else None
             con = eng.conditional_pairs(m["x"], contrast_min_prob, contrast_gamma) if out_contrast is not None else None
             acc = eng.accessibility(m["x"], access_width) if out_access is not None else None
+            jnt = eng.joint_profiles(m["x"]) if out_logo is not None else None
             for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
                 texts = [io.scan_record(rid, codes, r, nodes)]
                 if out_pairs is not None:
@@ -316,14 +328,31 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                     texts.append(io.contrast_record(rid, con[k]))
                 if out_access is not None:
                     texts.append(io.access_record(rid, acc[k]))
+                if out_logo is not None:
+                    texts.append(io.logo_counts_record(rid, r["exist_prob"], jnt[k]))
                 yield tuple(texts)
 
     if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None and out_contrast is None \
-            and out_access is None:
+            and out_access is None and out_logo is None:
         sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
     else:
-        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast, out_access) if o is not None]
+        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast, out_access, logo_parts)
+                         if o is not None]
         sharded_write(recs, outs, rank, world, scan_part, barrier)
+    if out_logo is not None:
+        if rank == 0:
+            write_logo_from_parts(logo_parts, out_logo, nodes, logo_min_exist)
+        barrier()
+
+
+def write_logo_from_parts(parts_path, out_logo, nodes, min_exist=0.0):
+    """The `--out-logo` file from the per-sequence count records in input order: the sequences with exist_prob >= min_exist are
+    summed in that order (api.motif_logo with weights 1 / 0); the records file is removed."""
+    parts = io.read_logo_counts(parts_path)
+    use = np.array([1.0 if ex >= min_exist else 0.0 for _, ex, _ in parts])
+    counts = np.stack([c for _, _, c in parts]) if parts else np.zeros((0, len(nodes), 7, 5))
+    io.write_logo(out_logo, nodes, api.motif_logo(counts, use)["counts"], int(use.sum()), len(parts))
+    os.remove(parts_path)
 
 
 def cmd_scan(a):
@@ -338,7 +367,7 @@ def cmd_scan(a):
     eng = io.engine_from_model(m, a.device if a.device is not None else local_rank)
     _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
                   a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites,
-                  a.out_contrast, a.contrast_min_prob, a.contrast_gamma, a.out_access, a.access_width)
+                  a.out_contrast, a.contrast_min_prob, a.contrast_gamma, a.out_access, a.access_width, a.out_logo, a.logo_min_exist)
     if world > 1:
         dist.destroy_process_group()
 

@@ -40,6 +40,7 @@
 #include "live_blocks.h"
 #include "node_mea_rules.h"
 #include "node_rules.h"
+#include "joint_rules.h"
 #include "sample_rules.h"
 #include "table_slots.h"
 
@@ -219,6 +220,9 @@ class Engine {
   void context_profile(const double* x, int n_param, double* profile);
   // posterior motif-node profiles (node_rules.h): n_node doubles per position of the batch
   void node_profile(const double* x, int n_param, double* profile);
+  // joint node-by-context posteriors (joint_rules.h): 35 n_node counts per sequence, and on request 7 n_node
+  // doubles per position of the batch
+  void joint_profile(const double* x, int n_param, double* counts, double* profile);
   // accessibility (access_rules.h): max_width doubles per position of the batch, the widths 1 .. max_width
   void accessibility(const double* x, int n_param, int max_width, double* access);
   // maximum expected accuracy motif alignments and site lists over that profile (node_mea_rules.h); outputs as
@@ -402,6 +406,7 @@ class Engine {
   // context profiles: P, u, h, b of the table slots (four [i][d] arrays per slot), their exterior columns, the profile of the call
   DevBuf d_cx_cells_, d_cx_o_, d_cx_prof_;
   DevBuf d_ac_T_, d_ac_vec_, d_ac_out_;   // accessibility: the four planes per slot, the log-space form's vectors, the result
+  DevBuf d_jn_lists_, d_jn_X_, d_jn_vec_, d_jn_prof_, d_jn_counts_;   // joint profiles: lists and slot map, per-cell scratch per slot, the log-space form's vectors, the results
   DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
   // node MEA: the chain lists, the backpointer scratch (M bytes per position), the rows, sites per sequence, start / end / score / confidence per slot
   DevBuf d_nm_lists_, d_nm_bp_, d_nm_node_, d_nm_ns_, d_nm_s0_, d_nm_s1_, d_nm_sc_, d_nm_cf_;
@@ -2836,6 +2841,95 @@ int Engine::node_profile_device(const char* what, const double* x, int n_param_i
 }
 
 
+// ---- joint node-by-context posteriors and emission counts (joint_rules.h).  The scan's first sum pass per group,
+// then on the group's table slots, before the next group of the stream reuses them: the hairpin and bulge chains of every row
+// (k_joint_rows), the 7 M columns of every position (k_joint_pos), the counts (k_joint_counts).  The log-space form -- the fused
+// scan kernel up to its first outside pass, then the same rule on its dense tables -- for the sequences that leave the double range
+// and under pipeline 3, with k_joint_counts behind the launch.  The profile goes to the host only where the caller gave a buffer.
+// Every buffer is the call's own: leaves the list of the last pair call alone.
+void Engine::joint_profile(const double* x, int n_param_in, double* counts, double* profile) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (!counts) throw ArgError("joint_profile: null counts");
+  const int M = au_.M();
+  if (M > 255) throw ArgError("joint_profile: more than 255 pattern nodes");
+  const size_t row = (size_t)kCtxCols * M, nc = row * kJointBases;
+  if (streaming_) {
+    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+      e.joint_profile(x, n_param_in, counts + nc * (size_t)c0, profile ? profile + row * (size_t)(h_seq_off_[c0] - h_seq_off_[0]) : nullptr);
+    });
+    return;
+  }
+  require_resident("joint_profile", n_param_in);
+  upload_params(x, lay_, false);
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  ScanPos pos(n_seqpos, n);
+  d_jn_prof_.alloc(8 * row * std::max<size_t>(n_seqpos, 1));
+  d_jn_counts_.alloc(8 * nc * (size_t)n);
+  std::vector<int32_t> lists;
+  size_t slot_at = 0;
+  const int n_slots = joint_lists_build(lay_, ints_.data(), &lists, &slot_at);
+  d_jn_lists_.upload(lists, st_);
+  HIP_OK(hipStreamSynchronize(st_));   // (the host vector goes out of use with the copy)
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  JointArgs ja;
+  std::memset(&ja, 0, sizeof(ja));
+  ja.plans = plan_.d_plans.as<SeqPlan>();
+  ja.seq_out = d_seq_out_.as<double>(); ja.out_stride = out_stride_;
+  ja.seq = d_seq_.as<uint8_t>();
+  ja.lists = d_jn_lists_.as<int32_t>();
+  ja.slot_at = (int32_t)slot_at; ja.n_slots = n_slots;
+  ja.M = M;
+  ja.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
+  ja.x_stride = joint_scratch_size(Lmax_, Wmax_, n_slots);
+  ja.profile = d_jn_prof_.as<double>();
+  ja.counts = d_jn_counts_.as<double>();
+  int n_flagged = 0;
+  const bool sums_on_batch = opt_pipeline_ == 4;
+  if (sums_on_batch)
+    n_flagged = scan_sums(pos, [&](LinArgs& a) {
+      if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("joint_profile: the scan sweeps another automaton than the lists name");
+      d_jn_X_.alloc(8 * ja.x_stride * (size_t)std::max(slots_.n(), 1));
+      ja.X = d_jn_X_.as<double>();
+      ja.skip_flagged = 1;
+    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      JointArgs jk = ja;
+      jk.idx = ak.grp;
+      jk.X = ja.X + slot0 * ja.x_stride;
+      if (!ja.no_rss) HIP_OK(launch_joint_rows(ak, jk, G, Lg, st));
+      HIP_OK(launch_joint_pos(ak, jk, G, Lg, st));
+      HIP_OK(launch_joint_counts(jk, G, st));
+    });
+  // ---- the log-space form: one launch, the scratch and the vectors per workgroup
+  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+    const size_t nb = (size_t)std::max(n_blocks, 1);
+    if (!sums_on_batch || d_jn_X_.bytes() < 8 * ja.x_stride * nb) d_jn_X_.alloc(8 * ja.x_stride * nb);
+    d_jn_vec_.alloc(8 * 5 * (size_t)d.lay.S * kThreads * nb);
+    d.jnt = ja;
+    d.jnt.X = d_jn_X_.as<double>();
+    d.jnt.vec = d_jn_vec_.as<double>();
+    return std::max(n_log, 1);
+  }, [&](const int32_t* idx, int C) {
+    JointArgs jk = ja;
+    jk.idx = idx;
+    jk.skip_flagged = 0;
+    HIP_OK(launch_joint_counts(jk, C, st_));
+  });
+  HIP_OK(hipEventRecord(ev_[3], st_));
+  HIP_OK(hipMemcpyAsync(counts, d_jn_counts_.as<void>(), 8 * nc * (size_t)n, hipMemcpyDeviceToHost, st_));
+  if (profile && n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_jn_prof_.as<void>(), 8 * row * n_seqpos, hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms_all = 0, ms_dp = 0;
+  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
+  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
+  last_ms[0] = ms_all;
+  last_ms[1] = ms_dp;
+  last_ms[2] = (double)n_flagged;
+}
+
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h).  The node pass of
 // node_profile, then k_node_mea once over the profile of the whole batch on the engine's stream, behind the last group and the
 // log-space form.  The profile goes to the host only where the caller gave a buffer.  Leaves the list of the last pair call alone.
@@ -3297,6 +3391,12 @@ int elemdp_node_profile(elemdp_handle* h, const double* x, int32_t n_param, doub
   ELEMDP_TRY
   if (!h || !x || !profile) throw elemdp::ArgError("elemdp_node_profile: null argument");
   h->e->node_profile(x, n_param, profile);
+  ELEMDP_CATCH
+}
+int elemdp_joint_profile(elemdp_handle* h, const double* x, int32_t n_param, double* counts, double* profile) {
+  ELEMDP_TRY
+  if (!h || !x || !counts) throw elemdp::ArgError("elemdp_joint_profile: null argument");
+  h->e->joint_profile(x, n_param, counts, profile);
   ELEMDP_CATCH
 }
 int elemdp_node_mea(elemdp_handle* h, const double* x, int32_t n_param, double gamma, int32_t max_sites, double* profile,

@@ -129,6 +129,26 @@ struct AccessArgs {
   double* access;
 };
 
+// ---- joint node-by-context posteriors and emission counts (joint_rules.h, joint_kernels.hip).  Slot g of a launch of the
+// scaled-linear form (workgroup b of the fused scan kernel in the log-space form) owns the per-cell scratch X + g * x_stride:
+// the sums in(L) G_c / Z of every cell by kind and by emitting node (joint_cell_at).  The profile of batch index n goes to
+// profile + 7 M * seq_base, 7 M doubles per position at 7 m + c; its counts to counts + 35 M * n at (7 m + c) 5 + b.
+struct JointArgs {
+  const SeqPlan* plans;           // batch plans (batch index)
+  const int32_t* idx;             // idx[g] = batch index of the sequence in slot g (launch_joint_counts)
+  const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
+  int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)
+  const uint8_t* seq;             // base codes of the batch (BatchArrays::seq)
+  const int32_t* lists;           // the transitions by emitted node (node_lists_build), then the slot map at slot_at
+  int32_t slot_at, n_slots;       // joint_lists_build
+  int32_t M;                      // pattern nodes
+  int32_t no_rss;                 // a model without secondary structure: rule 8 alone, the band tables are not read
+  double* X; size_t x_stride;
+  double* vec;                    // log-space form: 5 S doubles per thread of a workgroup of the fused scan kernel
+  double* profile;
+  double* counts;
+};
+
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h, node_mea_kernels.hip) over the profile of the
 // whole batch: batch index n with seq_base b and length L writes the row of slot k at node + max_sites * b + k * L (the sampler's
 // layout), n_sites[n], and start / end / score / conf at [n * max_sites + k]
@@ -194,6 +214,9 @@ struct DpArgs {
   // SCAN, accessibility (access_rules.h, log-space form): acc.T non-null = stop after inside + the first outside pass and write the
   // four planes of the sequence order[w] to slot w of acc (the rows k_access_seq reads behind the launch)
   AccessArgs acc;
+  // SCAN, joint node-by-context posteriors (joint_rules.h, log-space form): jnt.profile non-null = stop after inside + the first
+  // outside pass and write the 7 M columns of every position of the sequence order[w] (k_joint_counts reads them behind the launch)
+  JointArgs jnt;
 };
 
 // arguments of the diagonal-synchronous train pipeline (train_kernels.hip)
@@ -461,6 +484,12 @@ hipError_t launch_access_chains(const LinArgs& a, const AccessArgs& c, int G, in
 hipError_t launch_access_seq(const AccessArgs& c, int G, hipStream_t st);
 // k_node_pos behind launch_lin_scan_group (SCAN_PASS_START) on the same slots and stream: one wave per (sequence, position)
 hipError_t launch_node_pos(const LinArgs& a, const NodeArgs& c, int G, int Lmax, hipStream_t st);
+// k_joint_rows (one wave per row of a sequence: the hairpin and bulge chains, per-cell sums by node) and k_joint_pos (one wave per
+// (sequence, position): the 7 M columns) behind launch_lin_scan_group (SCAN_PASS_START) on the same slots and stream;
+// k_joint_counts behind them, or behind the fused scan kernel (DpArgs::jnt)
+hipError_t launch_joint_rows(const LinArgs& a, const JointArgs& c, int G, int Lmax, hipStream_t st);
+hipError_t launch_joint_pos(const LinArgs& a, const JointArgs& c, int G, int Lmax, hipStream_t st);
+hipError_t launch_joint_counts(const JointArgs& c, int G, hipStream_t st);
 // k_node_mea behind the node pass of the whole batch (both forms), on the engine's stream: one wave per sequence
 hipError_t launch_node_mea(const NodeMeaArgs& a, int n_seq, hipStream_t st);
 // kept pairs of every sequence of the batch (the staging capacity), off[0..n] = exclusive prefix of cnt[0..n) with off[n] the total,

@@ -24,6 +24,7 @@
 #include "energy_rules.h"
 #include "kernels.h"
 #include "node_rules.h"
+#include "joint_rules.h"
 #include "pair_rules.h"
 #include "plan_rules.h"
 #include "sample_lane.h"
@@ -825,6 +826,25 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
           for (int t = tid; t < L * a.node.M; t += kThreads) {
             const int pos = t / a.node.M, node = t - pos * a.node.M;
             prof[t] = live ? node_value(f, nl, m, q, Tin, Tout, pos, node, !no_rss) : node_no_parse(node);
+          }
+          continue;
+        }
+        if (a.jnt.profile) {   // joint node-by-context posteriors (joint_rules.h): the chains one row per lane, then one (position, node) per lane
+          const JointLog f(ZL);
+          const int M = a.jnt.M;
+          const JointLists jl{NodeLists{a.jnt.lists, M, NR_ALL}, a.jnt.lists + a.jnt.slot_at, a.jnt.n_slots, JP_ALL};
+          const bool live = ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL;
+          double* prof = a.jnt.profile + (size_t)CTX_COLS * M * p.seq_base;
+          double* X = a.jnt.X + (size_t)blockIdx.x * a.jnt.x_stride;
+          if (live && !no_rss) {
+            double* vec = a.jnt.vec + ((size_t)blockIdx.x * kThreads + tid) * 5 * (size_t)S;
+            for (int i = tid; i < L; i += kThreads) joint_row(f, jl, m, q, Tin, Tout, i, vec, X);
+            __syncthreads();
+          }
+          for (int t = tid; t < L * M; t += kThreads) {
+            const int pos = t / M, node = t - pos * M;
+            if (live) joint_value(f, jl, m, q, Tin, Tout, X, pos, node, !no_rss, prof + (size_t)CTX_COLS * t);
+            else joint_no_parse(node, prof + (size_t)CTX_COLS * t);
           }
           continue;
         }

@@ -395,3 +395,67 @@ def read_sites(path):
         out.append((rid, dict(start=np.array(start, dtype=np.int32), end=np.array(end, dtype=np.int32), score=np.array(score),
                               confidence=np.array(conf), rows=rows)))
     return out
+
+
+def logo_counts_record(rid, exist_prob, counts):
+    """Record of one sequence on the way to the `scan --out-logo` file: `id: <id>`, `exist: <exist_prob>` and `counts: [...]`, the
+    sequence's (M, 7, 5) block of Engine.joint_profiles in full precision: the ranks of a sharded run write these, and rank 0
+    joins them in input order before it sums."""
+    counts = np.asarray(counts, dtype=np.float64)
+    return "id: %s\nexist: %.17g\ncounts: [%s]\n" % (rid, exist_prob, ",".join("%.17g" % v for v in counts.ravel()))
+
+
+def read_logo_counts(path):
+    """-> list of (id, exist_prob, (M, 7, 5) array) from the per-sequence records of logo_counts_record."""
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+    while k + 2 < len(lines) and lines[k].startswith("id: "):
+        if not lines[k + 1].startswith("exist: ") or not lines[k + 2].startswith("counts: "):
+            raise ValueError("logo counts record %r: exist and counts lines expected" % lines[k][4:])
+        body = lines[k + 2][8:].strip("[]")
+        v = np.array([float(t) for t in body.split(",")] if body else [], dtype=np.float64)
+        out.append((lines[k][4:], float(lines[k + 1][7:]), v.reshape(-1, 7, 5)))
+        k += 3
+    return out
+
+
+LOGO_BASES = "NACGU"
+
+
+def write_logo(path, names, counts, n_used, n_total=None):
+    """The `scan --out-logo` file: a header `sequences: <used> / <read>` and `columns: N A C G U`, then one record per pattern node:
+    `node: <index><name>`, `occurrences: <expected number of bases the node emits>` and seven lines `O: [...]` .. `M: [...]`, the
+    node's expected emission counts of each base under that structure letter (17 significant digits: the file is a sum that
+    further sums are formed from); counts: an (M, 7, 5) array, the `counts` of api.motif_logo."""
+    counts = np.asarray(counts, dtype=np.float64).reshape(len(names), 7, 5)
+    lines = ["sequences: %d / %d" % (n_used, n_used if n_total is None else n_total), "columns: " + " ".join(LOGO_BASES)]
+    for m, c in enumerate(names):
+        lines += ["node: %d%s" % (m, c), "occurrences: %.17g" % counts[m].sum()]
+        lines += ["%s: [%s]" % (l, ",".join("%.17g" % v for v in counts[m, k])) for k, l in enumerate(CONTEXT_LETTERS)]
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def read_logo(path):
+    """-> dict(n_used, n_total, names, occurrences (M,), counts (M, 7, 5)) from a `scan --out-logo` file."""
+    lines = open(path).read().split("\n")
+    if len(lines) < 2 or not lines[0].startswith("sequences: ") or lines[1] != "columns: " + " ".join(LOGO_BASES):
+        raise ValueError("logo file %r: header expected" % path)
+    used, total = (int(t) for t in lines[0][11:].split(" / "))
+    names, occ, blocks = "", [], []
+    k = 2
+    while k < len(lines) and lines[k].startswith("node: "):
+        head = lines[k][6:]
+        if not head[:-1].isdigit() or int(head[:-1]) != len(blocks) or not lines[k + 1].startswith("occurrences: "):
+            raise ValueError("logo file %r: record of node %d expected at line %d" % (path, len(blocks), k + 1))
+        names += head[-1]
+        occ.append(float(lines[k + 1][13:]))
+        rows = []
+        for t, l in enumerate(CONTEXT_LETTERS):
+            h, body = lines[k + 2 + t].split(": ", 1)
+            if h != l:
+                raise ValueError("logo file %r: line %r where %r was expected" % (path, h, l))
+            rows.append([float(v) for v in body.strip("[]").split(",")])
+        blocks.append(rows)
+        k += 2 + len(CONTEXT_LETTERS)
+    return dict(n_used=used, n_total=total, names=names, occurrences=np.array(occ), counts=np.array(blocks, dtype=np.float64).reshape(-1, 7, 5))
