@@ -110,6 +110,12 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *                       the value takes its cells per block); 0 (default): 32;
  *     "useful_mask"     1 (default): the train sweeps skip the table entries no complete parse reaches (elemdp_useful_mask);
  *                       0: they compute every entry -- kept as the A/B switch and as the tests' reference
+ *     "pair_terms"      1 (default): the pair sums of the outside train sweep (rule 2, factorised) walk the plan's words
+ *                       (elemdp_pair_terms): HA takes its work items from the useful parent rows of its stem cells instead of
+ *                       every row up to the span, H1 walks the useful stems of its cell instead of every kept pair that starts
+ *                       at the cell's end -- the dropped terms are exact zeros that were never added; ignored where the plan
+ *                       has no words (a span above 64, the mask of all ones, "useful_mask" 0) and in the deterministic mode;
+ *                       0: every row and stem -- the A/B switch and the tests' reference
  *     "loop_prepass"    1 (default): a row pre-pass fills the inside L plane before the table-driven train sweep, whose workgroups
  *                       then compute no L, skip the cells that are useful in the L plane alone (lists of their own:
  *                       elemdp_live_blocks_inside) and the diagonals below the first hairpin; active wherever "useful_mask" is,
@@ -177,6 +183,15 @@ int elemdp_live_blocks_inside(elemdp_handle* h, int32_t seq_index, int32_t* coun
 /* Host only: elemdp_live_blocks_host with the bits that make a cell live (1 .. 255; 255 = any non-zero byte, 127 = the inside set). */
 int elemdp_live_blocks_host_bits(const uint8_t* mask, int32_t L, int32_t W, int32_t cpb, int32_t cap, int32_t bits, int32_t* counts,
                                  void* records, int32_t stride);
+/* Debug: the pair-term words of one sequence of the resident plan (built with the mask by the call if no
+ * evaluation has built them), (W+1)*(L+1) words each, index d*(L+1)+i like the mask.  ha_rows: bit b-1 of the word of a kept pair
+ * (i, d) is set where the term outA(i-b, i+d) x 1(i-b, i) of its HA sum can be non-zero; h1_stems: bit sp-1 of the word of cell
+ * (i, d) where the term outA(i, j+sp) x P(j, j+sp), j = i+d, of its H1 sum can.  Both hold the same triples.  Fails where the plan
+ * has no words: a span above 64, or the mask of all ones. */
+int elemdp_pair_terms(elemdp_handle* h, int32_t seq_index, uint64_t* ha_rows, uint64_t* h1_stems, int32_t cap);
+/* Host only: the same words by the same rules on the CPU from a mask[(W+1)*(L+1)] and the kept pairs kept[(L+1)*(W+1)] of one
+ * sequence (as elemdp_useful_mask_host takes them); W <= 64 (else ELEMDP_EINVAL). */
+int elemdp_pair_terms_host(const uint8_t* mask, const uint8_t* kept, int32_t L, int32_t W, uint64_t* ha_rows, uint64_t* h1_stems);
 
 /* == RNAelemTrainer::operator()(x, fn, gr) over the whole resident batch with --no-shuffle
  * (motif_trainer.hpp:595-633 + RNAelemTrainDP::operator() :124-272).  fn/gr are the UNREGULARISED

@@ -22,7 +22,7 @@ DBG_FIX_RSS, DBG_NO_TURN = 1 << 9, 1 << 10
 # every symbol include/elemdp.h declares
 SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "elemdp_create", "elemdp_destroy",
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
-           "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_train_eval",
+           "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_pair_terms", "elemdp_pair_terms_host", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
            "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_joint_profile", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
@@ -80,6 +80,9 @@ def load_library():
         L.elemdp_live_blocks_host.argtypes = [u8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]
         L.elemdp_live_blocks_inside.argtypes = L.elemdp_live_blocks.argtypes
         L.elemdp_live_blocks_host_bits.argtypes = [u8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]
+        u64 = C.POINTER(C.c_uint64)
+        L.elemdp_pair_terms.argtypes = [hp, C.c_int32, u64, u64, C.c_int32]
+        L.elemdp_pair_terms_host.argtypes = [u8, u8, C.c_int32, C.c_int32, u64, u64]
         L.elemdp_train_eval.argtypes = [hp, dp, C.c_int32, dp, dp, dp, i32]
         L.elemdp_train_partial.argtypes = [hp, dp, C.c_int32, C.c_void_p, C.c_int32]
         L.elemdp_train_finish.argtypes = [hp, dp, dp, dp, dp, i32]
@@ -199,6 +202,26 @@ def live_blocks_host(mask, cpb, cap, bits=None):
     return _live_block_lists(counts, recs)
 
 
+def _u64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def pair_terms_host(mask, kept):
+    """Pair-term words of one sequence on the CPU from its mask [(W+1), (L+1)] and kept pairs [(L+1), (W+1)]: (ha_rows,
+    h1_stems), uint64 [(W+1), (L+1)] each (host; elemdp_pair_terms_host).  W > 64 is refused."""
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    kept = np.ascontiguousarray(kept, dtype=np.uint8)
+    W, L = mask.shape[0] - 1, mask.shape[1] - 1
+    if kept.shape != (L + 1, W + 1):
+        raise ValueError("pair_terms_host: kept must be [(L+1), (W+1)]")
+    ha = np.zeros((W + 1, L + 1), dtype=np.uint64)
+    h1 = np.zeros((W + 1, L + 1), dtype=np.uint64)
+    rc = load_library().elemdp_pair_terms_host(_u8(mask), _u8(kept), L, W, _u64(ha), _u64(h1))
+    if rc:
+        raise ElemdpError(rc, "pair_terms_host")
+    return ha, h1
+
+
 class Engine:
     """One model on one GPU (== one `RNAelem` object plus the trainer / scanner workers around it)."""
 
@@ -281,6 +304,15 @@ class Engine:
         out = np.zeros((W + 1, L + 1), dtype=np.uint8)
         self._check(self._lib.elemdp_useful_mask(self._h, index, _u8(out), out.size))
         return out
+
+    def pair_terms(self, index):
+        """(ha_rows, h1_stems), uint64 [(W+1), (L+1)] each: the pair-term words of sequence `index` (elemdp_pair_terms)."""
+        L = int(self._off[index + 1] - self._off[index])
+        W = min(L, self.max_span)
+        ha = np.zeros((W + 1, L + 1), dtype=np.uint64)
+        h1 = np.zeros((W + 1, L + 1), dtype=np.uint64)
+        self._check(self._lib.elemdp_pair_terms(self._h, index, _u64(ha), _u64(h1), ha.size))
+        return ha, h1
 
     def live_blocks(self, index, with_taken=False, inside=False):
         """The live-block lists of sequence `index` for the model's cells per block and the span of the current options:

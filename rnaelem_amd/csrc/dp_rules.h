@@ -169,6 +169,10 @@ struct SeqView {
   ELEMDP_HD int ubits(int i, int d) const { return useful ? (int)useful[d * (L + 1) + i] : 0xff; }
   // live-block lists of the train sweeps (live_blocks.h); null: a workgroup takes consecutive cells
   const LiveBlock* blocks = nullptr;
+  // useful parent rows of the stem cells' HA sums and useful stems of the cells' H1 sums in the outside train sweep
+  // (plan_rules.h: ha_rows / h1_stems, [d][i] like the mask); null, both or neither: every row and stem is walked
+  const unsigned long long* ha_rows = nullptr;
+  const unsigned long long* h1_stems = nullptr;
 
   ELEMDP_HD int cell(int i, int d) const { return i * (W + 1) + d; }
   ELEMDP_HD bool pair_ok(int i, int d) const {  // is_parsable<ST_P>

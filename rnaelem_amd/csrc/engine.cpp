@@ -151,6 +151,10 @@ struct PlanSet {
   // (Engine::ensure_useful_mask): a batch that is only scanned never pays for it
   DevBuf useful;
   bool useful_built = false;
+  // pair terms of the outside train sweep (PlanArrays::ha_rows / h1_stems), built right behind the mask, once per plan; not where
+  // the plan gets no words: W > 64, or the mask of all ones
+  DevBuf pair_words;
+  bool pair_terms_built = false;
   // live-block lists of the train sweeps (PlanArrays::blocks; Engine::ensure_live_blocks) for `blk_cpb` cells per block that span
   // at most `blk_cap` cells, and the largest block count of every diagonal over the set (host copy: the grids)
   DevBuf blocks, blk_max;
@@ -189,6 +193,7 @@ class Engine {
   ~Engine();
 
   void useful_mask(int idx, uint8_t* mask, int cap);
+  void pair_terms(int idx, uint64_t* ha, uint64_t* h1, int cap);
   void live_blocks(int idx, int32_t* counts, void* records, int stride, int32_t* cpb_cap, int32_t* taken, bool inside = false);
   int n_param() const { return au_.n_theta() + 2; }
   int n_state() const { return au_.S(); }
@@ -462,6 +467,7 @@ class Engine {
   // 4 = scaled-linear batch pipeline (lin_kernels.hip), 3 = log-space batch pipeline, 2 = fused one-workgroup-per-sequence kernel
   int opt_pipeline_ = 4;
   bool opt_useful_mask_ = true;    // option "useful_mask": the train sweeps skip the entries no complete parse reaches
+  bool opt_pair_terms_ = true;     // option "pair_terms": the pair sums of the outside train sweep walk the plan's words of useful rows and stems
   int opt_live_blocks_ = 1;        // option "live_blocks": a workgroup of the train sweeps takes cpb LIVE cells of its diagonal;
                                    // 2: on every diagonal, also where the lists save no workgroups
   int opt_live_span_ = 0;          // option "live_span": the cells a block may span (0: kLiveSpanDefault, at least cpb)
@@ -676,6 +682,7 @@ void Engine::set_option(const std::string& key, double v) {
   else if (key == "deterministic") opt_det_ = v != 0;
   else if (key == "sorted_plan") opt_sorted_plan_ = v != 0;
   else if (key == "useful_mask") opt_useful_mask_ = v != 0;
+  else if (key == "pair_terms") opt_pair_terms_ = v != 0;
   else if (key == "live_blocks") {
     if (v < 0 || v > 2) throw ArgError("live_blocks: 0, 1 or 2");
     opt_live_blocks_ = (int)v;
@@ -797,7 +804,7 @@ void Engine::build_planset(PlanSet& ps, int first, int count, const uint32_t* d_
   }
   ps.n_cells = cell_b;
   ps.n_blocks = blk_b;
-  ps.useful_built = false;   // (the mask follows the pair mask: ensure_useful_mask builds it again)
+  ps.useful_built = ps.pair_terms_built = false;   // (the mask follows the pair mask: ensure_useful_mask builds it again, and the pair terms behind it)
   ps.blk_cpb = ps.blk_cap = 0;   // (and the lists follow the mask)
   d_okbits_end_.alloc(sizeof(uint32_t) * (size_t)bits_end);   // the pair mask by (end, span): scratch of the item enumeration
   ps.d_plans.upload(ps.h, st_);
@@ -861,6 +868,17 @@ void Engine::ensure_useful_mask() {
   plan_.ka.m_min = m_min();
   HIP_OK(launch_useful_mask(plan_.ka, (size_t)plan_.n_cells, (size_t)opt_useful_lds_kb_ * 1024, st_));
   plan_.useful_built = true;
+  // the pair terms of the outside sweep: plan work like the mask they are read from (not from the mask of all ones, which drops
+  // nothing, nor for a span that does not fit a word)
+  plan_.pair_terms_built = false;
+  plan_.ka.p.ha_rows = plan_.ka.p.h1_stems = nullptr;
+  if (plan_.ka.wmax1 - 1 <= kPairTermsMaxW && useful_mask_fits(plan_.ka, (size_t)opt_useful_lds_kb_ * 1024)) {
+    plan_.pair_words.alloc(2 * sizeof(unsigned long long) * (size_t)plan_.n_cells);
+    plan_.ka.p.ha_rows = plan_.pair_words.as<unsigned long long>();
+    plan_.ka.p.h1_stems = plan_.ka.p.ha_rows + (size_t)plan_.n_cells;
+    HIP_OK(launch_pair_terms(plan_.ka, st_));
+    plan_.pair_terms_built = true;
+  }
   plan_.blk_cpb = plan_.blk_cap = 0;
   ++plan_gen_;
 }
@@ -1652,6 +1670,8 @@ ZeroBinding Engine::zero_binding(const LinArgs& a, bool sched1, bool ranged) con
   // (the options as they are set: what they come to in this evaluation follows from them, the layout and the plan)
   z.useful_mask = opt_useful_mask_ ? 1 : 0; z.loop_prepass = opt_loop_prepass_ ? 1 : 0; z.loop_outside = opt_loop_outside_ ? 1 : 0;
   z.live_blocks = opt_live_blocks_; z.live_span = opt_live_span_; z.deterministic = opt_det_ ? 1 : 0; z.fast = a.fast;
+  // (option pair_terms has no field: the words drop terms that are exact zeros and were never added -- no stored entry, dead or
+  // live, depends on it, so the zeros of one setting serve the other)
   return z;
 }
 
@@ -1668,6 +1688,11 @@ void Engine::run_lin_batch() {
   int gsz = prepare_lin(a, sched1, false, n_ev, 8192, !ranged);
   if (opt_useful_mask_) ensure_useful_mask();
   a.p.useful = opt_useful_mask_ ? plan_.useful.as<uint8_t>() : nullptr;   // (the train sweeps only: the scan family sees null)
+  // the pair terms go with the mask, where the plan has words (the deterministic mode keeps its walk and with it its order of adds)
+  if (opt_useful_mask_ && opt_pair_terms_ && !opt_det_ && plan_.pair_terms_built) {
+    a.p.ha_rows = plan_.pair_words.as<unsigned long long>();
+    a.p.h1_stems = a.p.ha_rows + (size_t)plan_.n_cells;
+  }
   // the loop pre-pass goes with the mask (the launcher drops it where the table-driven form does not run)
   a.loop_pre = (opt_loop_prepass_ && opt_useful_mask_ && loop_prepass_ok(sched1)) ? 1 : 0;
   a.loop_post = (opt_loop_outside_ && opt_useful_mask_ && !opt_det_ && loop_prepass_ok(sched1) && loop_outside_ok(sched1)) ? 1 : 0;
@@ -2042,6 +2067,23 @@ void Engine::useful_mask(int idx, uint8_t* mask, int cap) {
   ensure_useful_mask();
   HIP_OK(hipStreamSynchronize(st_));
   HIP_OK(hipMemcpy(mask, plan_.useful.as<uint8_t>() + p.cell_base, nc, hipMemcpyDeviceToHost));
+}
+
+// The pair-term words of sequence idx (built with the mask if no evaluation has): (W+1) * (L+1) words each, [d][i].
+void Engine::pair_terms(int idx, uint64_t* ha, uint64_t* h1, int cap) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (streaming_) throw StateError("pair_terms needs a resident batch (the handle streams this one in chunks)");
+  if (idx < 0 || idx >= n_seq_) throw ArgError("pair_terms: bad sequence index");
+  const SeqPlan& p = h_plans_[idx];
+  const int nc = (p.L + 1) * (p.W + 1);
+  if (cap < nc) throw ArgError("pair_terms: buffer too small");
+  ensure_useful_mask();
+  if (!plan_.pair_terms_built) throw StateError("pair_terms: no words for this plan (a span above 64, or the mask of all ones)");
+  HIP_OK(hipStreamSynchronize(st_));
+  const unsigned long long* w = plan_.pair_words.as<unsigned long long>();
+  HIP_OK(hipMemcpy(ha, w + p.cell_base, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(h1, w + (size_t)plan_.n_cells + p.cell_base, sizeof(uint64_t) * nc, hipMemcpyDeviceToHost));
 }
 
 // The scaled-linear sum passes of a scan (and the first one of pair_posteriors): table slots, cleared outputs, weights.  A scan
@@ -3275,6 +3317,18 @@ int elemdp_useful_mask_host(const uint8_t* kept, const uint8_t* unp, int32_t L, 
                             uint8_t* mask) {
   if (!kept || !mask || L < 0 || W < 0 || W > L || max_iloop < 0) return ELEMDP_EINVAL;
   elemdp::useful_mask_host(kept, unp, L, W, max_iloop, (flags & ELEMDP_DBG_NO_TURN) ? 4 : 10, (flags & ELEMDP_NO_ENERGY) != 0, mask);
+  return ELEMDP_OK;
+}
+int elemdp_pair_terms(elemdp_handle* h, int32_t seq_index, uint64_t* ha_rows, uint64_t* h1_stems, int32_t cap) {
+  ELEMDP_TRY
+  if (!h || !ha_rows || !h1_stems) throw elemdp::ArgError("elemdp_pair_terms: null argument");
+  h->e->pair_terms(seq_index, ha_rows, h1_stems, cap);
+  ELEMDP_CATCH
+}
+int elemdp_pair_terms_host(const uint8_t* mask, const uint8_t* kept, int32_t L, int32_t W, uint64_t* ha_rows, uint64_t* h1_stems) {
+  if (!mask || !kept || !ha_rows || !h1_stems || L < 0 || W < 0 || W > L || W > elemdp::kPairTermsMaxW) return ELEMDP_EINVAL;
+  static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the words of the plan");
+  elemdp::pair_terms_host(mask, kept, L, W, reinterpret_cast<unsigned long long*>(ha_rows), reinterpret_cast<unsigned long long*>(h1_stems));
   return ELEMDP_OK;
 }
 

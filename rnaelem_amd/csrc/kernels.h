@@ -13,6 +13,7 @@
 namespace elemdp {
 
 constexpr int kThreads = 256;  // workgroup size of every kernel (4 waves of 64: one per SIMD of a CU)
+constexpr int kPairTermsMaxW = 64;   // the largest span whose pair terms fit a word (PlanArrays::ha_rows)
 
 // device arrays of one plan set (see SeqPlan for the per-sequence bases)
 struct PlanArrays {
@@ -33,6 +34,10 @@ struct PlanArrays {
   LiveBlock* blocks = nullptr;
   // the second set of lists, from the mask bytes without UB_L: the inside sweep behind the loop pre-pass (live_blocks.h)
   LiveBlock* blocks_in = nullptr;
+  // pair terms of the outside train sweep (plan_rules.h: ha_rows / h1_stems), one 64-bit word per cell each, indexed like
+  // `useful`; null: no words for this plan (W > 64, the mask of all ones, no mask) -- the sweep walks every row and stem
+  unsigned long long* ha_rows = nullptr;
+  unsigned long long* h1_stems = nullptr;
 };
 
 // static per-batch arrays
@@ -387,6 +392,11 @@ hipError_t launch_plan_cells(const PlanKernelArgs& a, int32_t* n_items_out, hipS
 hipError_t launch_plan_items(const PlanKernelArgs& a, hipStream_t st);
 hipError_t launch_useful_mask(const PlanKernelArgs& a, size_t n_cells, size_t lds_cap, hipStream_t st);   // needs dmin (launch_plan_cells)
 void useful_mask_host(const uint8_t* kept, const uint8_t* unp, int L, int W, int C, int m_min, bool no_ene, uint8_t* out);
+bool useful_mask_fits(const PlanKernelArgs& a, size_t lds_cap);   // false: launch_useful_mask stores the mask of all ones
+// the pair-term words of every sequence of the set from its finished mask (a.p.useful -> a.p.ha_rows, a.p.h1_stems); wmax1 <= 65
+hipError_t launch_pair_terms(const PlanKernelArgs& a, hipStream_t st);
+// the same words on the host from a mask[(W+1)*(L+1)] and the kept pairs kept[(L+1)*(W+1)] of one sequence, W <= 64
+void pair_terms_host(const uint8_t* mask, const uint8_t* kept, int L, int W, unsigned long long* ha, unsigned long long* h1);
 // the live-block lists of every sequence of the set from its mask (a.p.useful -> a.p.blocks of n_records records, a.blk_max),
 // cells per block a.live_cpb;
 // with a.p.blocks_in non-null also the inside set; a.blk_max holds 6 rows of wmax1 ints either way

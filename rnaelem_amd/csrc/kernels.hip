@@ -1016,6 +1016,20 @@ __global__ __launch_bounds__(kThreads) void k_live_blocks(PlanKernelArgs a) {
   }
 }
 
+// K-plan 7: the pair-term words of the outside train sweep from the finished mask (plan_rules.h: ha_rows / h1_stems), lane =
+// cell [d][i] of sequence blockIdx.y.  Most cells answer from their own byte and pair bit; a kept pair reads two bytes per row.
+__global__ __launch_bounds__(kThreads) void k_pair_terms(PlanKernelArgs a) {
+  const SeqPlan p = a.plans[a.first + blockIdx.y];
+  const int L = p.L, W = p.W, c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= (L + 1) * (W + 1)) return;
+  const int d = c / (L + 1), i = c - d * (L + 1);
+  const uint8_t* m = a.p.useful + p.cell_base;
+  const UsefulCtx q{L, W, p.C, a.m_min, 0, a.okbits + p.bits_base, nullptr, a.p.dmin + p.dmin_base, nullptr};
+  const bool cell = i + d <= L;
+  a.p.ha_rows[p.cell_base + c] = cell ? ha_rows(q, m, i, d) : 0ull;
+  a.p.h1_stems[p.cell_base + c] = cell ? h1_stems(q, m, i, d) : 0ull;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1117,10 +1131,11 @@ hipError_t launch_reduce(const double* seq_out, int out_stride, int n_seq, int n
 }
 // the usefulness mask of every sequence of the set into a.p.useful (cell_base indexing, [d][i]); a set whose largest sequence
 // does not fit lds_cap bytes of a workgroup's LDS gets the mask of all ones (every entry useful: the sweeps then skip nothing)
+bool useful_mask_fits(const PlanKernelArgs& a, size_t lds_cap) { return (size_t)useful_lds(a.lmax, a.wmax1 - 1).total <= lds_cap; }
 hipError_t launch_useful_mask(const PlanKernelArgs& a, size_t n_cells, size_t lds_cap, hipStream_t st) {
   if (a.count <= 0 || !a.p.useful) return hipSuccess;
   const size_t lds = (size_t)useful_lds(a.lmax, a.wmax1 - 1).total;
-  if (lds > lds_cap) return hipMemsetAsync(a.p.useful, UB_ALL, n_cells, st);
+  if (!useful_mask_fits(a, lds_cap)) return hipMemsetAsync(a.p.useful, UB_ALL, n_cells, st);
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_useful_mask), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_useful_mask, dim3(a.count), dim3(kThreads), lds, st, a);
@@ -1139,6 +1154,31 @@ hipError_t launch_live_blocks(const PlanKernelArgs& a, size_t n_records, hipStre
   const long long lanes = (long long)a.count * a.wmax1;
   hipLaunchKernelGGL(k_live_blocks, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a);
   return hipGetLastError();
+}
+hipError_t launch_pair_terms(const PlanKernelArgs& a, hipStream_t st) {
+  if (a.count <= 0 || !a.p.useful || !a.p.ha_rows || !a.p.h1_stems) return hipSuccess;
+  if (a.wmax1 - 1 > kPairTermsMaxW) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pair_terms, dim3((a.ncell_max + kThreads - 1) / kThreads, a.count), dim3(kThreads), 0, st, a);
+  return hipGetLastError();
+}
+void pair_terms_host(const uint8_t* mask, const uint8_t* kept, int L, int W, unsigned long long* ha, unsigned long long* h1) {
+  const int n = (L + 1) * (W + 1);
+  std::vector<uint32_t> bits((n + 31) / 32 + 1, 0u);
+  std::vector<int16_t> dmin(L + 1, 0);
+  for (int i = 0; i <= L; ++i)
+    for (int d = 0; d <= W; ++d)
+      if (i + d <= L && kept[i * (W + 1) + d]) {
+        const int c = i * (W + 1) + d;
+        bits[c >> 5] |= 1u << (c & 31);
+        if (d > 0 && dmin[i] == 0) dmin[i] = (int16_t)d;
+      }
+  const UsefulCtx q{L, W, 0, 0, 0, bits.data(), nullptr, dmin.data(), nullptr};
+  for (int d = 0; d <= W; ++d)
+    for (int i = 0; i <= L; ++i) {
+      const bool cell = i + d <= L;
+      ha[q.at(i, d)] = cell ? ha_rows(q, mask, i, d) : 0ull;
+      h1[q.at(i, d)] = cell ? h1_stems(q, mask, i, d) : 0ull;
+    }
 }
 void live_blocks_host(const uint8_t* mask, int L, int W, int cpb, int cap, int32_t* counts, LiveBlock* records, int stride, int bits) {
   for (int d = 0; d <= W; ++d) {

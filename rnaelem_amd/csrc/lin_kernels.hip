@@ -222,6 +222,16 @@ struct BitIter {
     }
   }
 };
+// The same walk over a word of the plan's pair terms (plan_rules.h: bit n - 1 <=> n).
+struct WordIter {
+  unsigned long long w;
+  __device__ __forceinline__ int next() {
+    if (!w) return -1;
+    const int b = __builtin_ctzll(w);
+    w &= w - 1ull;
+    return b + 1;
+  }
+};
 // crd: doubles per cell record of the table-driven unary phase (lin_fast.h), 0 = none
 // sp: the cells the workgroup's window spans -- cpb (0), or the cap of the live-block lists (train sweeps: the cells of a block
 // lie up to `sp` apart); win = sp + W + 3 positions
@@ -1584,9 +1594,35 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
       }
     }
   }
+  // pair terms (option pair_terms; plan_rules.h: ha_rows, h1_stems): the words of useful parent rows and of useful stems of the
+  // lane's cell -- 0 where the cell is no kept pair / has no H1 sum -- travel with the cell records.  (Not in the deterministic
+  // mode, whose adds keep their lane mapping.)
+  const bool pterms = MASK && v.q.ha_rows != nullptr && !a.det;
+  unsigned long long hw = 0ull, sw = 0ull;
+  if (MASK && pterms && tid < nc) { hw = v.q.ha_rows[d * (L + 1) + ci(tid)]; sw = v.q.h1_stems[d * (L + 1) + ci(tid)]; }
   if (a.dbg & 1024) { if (nc == 12345) lds[tid] = crx[0] + pi.invZ; return; }   // (timing experiments, as in k4_in)
   const BlockCtx cx = stage_context<BIG, 1, FAST>(a, v, reinterpret_cast<unsigned char*>(lds), BL, i0, span, d, cpb, gaps ? ci(tid < nc ? tid : 0) : -1);
   if (pi.skip) return;   // (tested here: the loads behind `pi` travel with those of the context instead of before them)
+  // ... and the first wave expands the words into the list of the HA work: one 16-bit entry (cell << 8 | row b) per set bit, in
+  // cell order, behind its count, in the item-record area (idle until the item sums; the barrier below publishes it).  A list
+  // that does not fit the area is not used (the count says so): the block walks every row.  The words of the stems go there as
+  // they are, one per cell (the H1 lanes of a cell share it).
+  int* ha_cnt = reinterpret_cast<int*>(sOB1);
+  unsigned long long* h1_wd = reinterpret_cast<unsigned long long*>(sOB1) + 1;
+  unsigned short* ha_ent = reinterpret_cast<unsigned short*>(h1_wd + 64);
+  constexpr int kHAcap = kRecOut * 4 - 4 - 4 * 64;
+  static_assert(ELEMDP_CPB_MAX <= 64 && kHAcap > 0, "a word per cell of the block in the item-record area");
+  if (MASK && pterms && tid < 64) {
+    h1_wd[tid] = sw;
+    const int n = __popcll(hw);
+    int off = n;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) { const int t = __shfl_up(off, s); if (tid >= s) off += t; }
+    if (tid == 63) ha_cnt[0] = off;
+    off -= n;
+    for (unsigned long long m = hw; m; m &= m - 1ull, ++off)
+      if (off < kHAcap) ha_ent[off] = (unsigned short)((tid << 8) | (__builtin_ctzll(m) + 1));
+  }
   int* dm = cx.dm; int* cnts = cx.cnts; int* pre = cx.pre; int* base = cx.base;
   const int32_t* G = v.m.big;
   double* crec = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(lds) + BL.crec);
@@ -1665,11 +1701,16 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
     // flat list, four work items' loads in flight per lane.  The loads of the first round are issued here, ahead of the H1
     // sums: both read outA of larger spans only, so one round trip serves both.  (The rule-7 term of the stem cells' P states
     // is already in the table: k4_r7.)
+    // With the plan's words (pterms) the flat list holds the useful rows only: work item = (entry of the list, pair); every
+    // dropped row's product is an exact 0 that the add below would have skipped.
+    const int n_ent = (MASK && pterms) ? __builtin_amdgcn_readfirstlane(ha_cnt[0]) : 0;
+    const bool plist = MASK && pterms && n_ent <= kHAcap && n_ent * nA < (1 << 20);   // (the second: div_rcp's range)
     unsigned long long stems = 0;             // bit c: cell c of the workgroup is a pair (cpb <= 64)
-    for (int c = 0; c < nc; ++c) stems |= v.q.pair_ok(ci(c), d) ? (1ull << c) : 0ull;
-    if ((a.dbg & 1) || (ELEMDP_KO & 1)) stems = 0;
+    if (!plist) for (int c = 0; c < nc; ++c) stems |= v.q.pair_ok(ci(c), d) ? (1ull << c) : 0ull;
+    const bool no_ha = (a.dbg & 1) || (ELEMDP_KO & 1);
+    if (no_ha) stems = 0;
     const int nb = W - d;                     // b = 1 .. nb: parent span d + b <= W
-    const int per = nb * nA, total = __popcll(stems) * per;
+    const int per = nb * nA, total = plist ? (no_ha ? 0 : n_ent * nA) : __popcll(stems) * per;
     constexpr int kHA = 4;
     double ha_oa[kHA], ha_x1[kHA];
     int ha_idx[kHA];
@@ -1688,11 +1729,21 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
         ha_idx[u] = c * HD + pr_t(p);
       }
     };
+    // work item w = entry * nA + p of the list of useful rows into slot u (an entry's row is parsable: no test)
+    auto ha_item = [&](int u, bool valid, int w) {
+      const int e = div_rcp(w, a.rcp_nap), p = w - e * nA;
+      const int ent = valid ? (int)ha_ent[e] : 1;
+      const int c = ent >> 8, b = ent & 0xff, ii = ci(c) - b;
+      ha_oa[u] = out.lda(d + b, ii, p, valid);
+      ha_x1[u] = in.ldc(ST_1, b, ii, pr_c1(p), valid);
+      ha_idx[u] = c * HD + pr_t(p);
+    };
     auto ha_load = [&](int w0) {      // flat list over all stem cells of the block: w = sc * per + r
 #pragma unroll
       for (int u = 0; u < kHA; ++u) {
         const int w = w0 + u * kBT;
         const bool valid = w < total;
+        if (MASK && plist) { ha_item(u, valid, valid ? w : 0); continue; }
         const int sc = valid ? div_small(w, per) : 0;
         ha_slot(u, valid, sc, valid ? w - sc * per : 0);
       }
@@ -1718,12 +1769,11 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
       const int s1 = pr_s1(p);
       const int cP = pr_cP(p);
       const int dmi = dm[c];
-      if (dmi > 0 && dmi <= d && !(MASK && !(v.q.ubits(i, d) & UB_1))) {     // left_ok(i, d)  (a dead child 1(i,j,s1) drops the sum in the unary phase; a useless one is not summed)
-        const int hi = (W - d < L - j) ? W - d : L - j;
+      // the stems (j, j + sp) of the sum: with the plan's words the set bits of the cell's word (plan_rules.h: h1_stems -- 0 where
+      // the cell is not left_ok or has no UB_1, and only stems whose parent entry has UB_A), else the kept pairs of row j
+      auto h1_sum = [&](auto& it) {
         const double* xml = v.q.xwc + (size_t)(pr_kl(p) * 5 + XT_ML) * v.q.xwc_stride;
         double acc = 0.;
-        BitIter it;
-        it.init(v.q.okbits, j * W1, 1, hi);
         if (FAST) {   // (b = X = P * exp(lambda e_ml) from the B plane's rows, see fast_inside_unary; no weight load)
           for (;;) {
             int sp[kStems];
@@ -1761,6 +1811,15 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
           if (sp3 < 0) break;
         }
         if (acc != 0.) atomicAdd(&h1A[c * HD + s1], acc);
+      };
+      if (MASK && pterms) {
+        WordIter it{h1_wd[c]};
+        if (it.w) h1_sum(it);
+      } else if (dmi > 0 && dmi <= d && !(MASK && !(v.q.ubits(i, d) & UB_1))) {     // left_ok(i, d)  (a dead child 1(i,j,s1) drops the sum in the unary phase; a useless one is not summed)
+        const int hi = (W - d < L - j) ? W - d : L - j;
+        BitIter it;
+        it.init(v.q.okbits, j * W1, 1, hi);
+        h1_sum(it);
       }
     }
     if (!a.det) {

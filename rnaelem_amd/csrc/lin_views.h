@@ -89,6 +89,8 @@ __device__ __forceinline__ void make_lviews(const LinArgs& a, int g, LViews& v) 
   q.okbits_end = a.okbits_end ? a.okbits_end + p.bits_base : nullptr;
   q.useful = a.p.useful ? a.p.useful + p.cell_base : nullptr;
   q.blocks = a.p.blocks ? a.p.blocks + p.blk_base : nullptr;
+  q.ha_rows = a.p.ha_rows ? a.p.ha_rows + p.cell_base : nullptr;
+  q.h1_stems = a.p.ha_rows ? a.p.h1_stems + p.cell_base : nullptr;
   v.row = a.seq_out + (size_t)n * a.out_stride;
   v.zs = a.zs + (size_t)g * 4;
 }

@@ -267,4 +267,36 @@ ELEMDP_HOSTDEV void useful_mask_serial(const UsefulCtx& q, uint8_t* m, uint8_t* 
     for (int i = 0; i + d <= L; ++i) m[q.at(i, d)] = (uint8_t)useful_outside_cell(q, m, lm, i, d);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Pair terms: which terms 1(i,k) x stem (k,j) -> A(i,j) of the factorised rule 2 can be non-zero, as the outside
+// sweep walks them -- two 64-bit words per cell from the finished mask `m` ([d][i]), the pair mask and dmin; W <= 64
+// (kPairTermsMaxW, kernels.h).  Both words hold the same set of triples (i, k, j): ha_rows by the stem cell (k, j - k), h1_stems
+// by the left cell (i, k - i).
+// ---------------------------------------------------------------------------------------------
+
+// the parent rows of the stem cell (i, d): bit b - 1, 1 <= b <= W - d, is set where 1(i - b, i) is parsable (the kernel's `ok`),
+// A(i - b, i + d) has UB_A and 1(i - b, i) has UB_1; 0 where (i, d) is no kept pair
+ELEMDP_HOSTDEV unsigned long long ha_rows(const UsefulCtx& q, const uint8_t* m, int i, int d) {
+  if (!q.pair_ok(i, d)) return 0ull;
+  unsigned long long w = 0ull;
+  for (int b = 1; b <= q.W - d && b <= i; ++b) {
+    const int ii = i - b, dm = q.dmin[ii];
+    if (dm > 0 && b >= dm && (m[q.at(ii, d + b)] & UB_A) && (m[q.at(ii, b)] & UB_1)) w |= 1ull << (b - 1);
+  }
+  return w;
+}
+
+// the stems that start at the end j = i + d of the cell (i, d): bit sp - 1, 1 <= sp <= min(W - d, L - j), is set where (j, sp) is
+// a kept pair and A(i, j + sp) has UB_A; 0 where 1(i, j) is not parsable or has no UB_1
+ELEMDP_HOSTDEV unsigned long long h1_stems(const UsefulCtx& q, const uint8_t* m, int i, int d) {
+  if (!q.left_ok(i, d) || !(m[q.at(i, d)] & UB_1)) return 0ull;
+  const int j = i + d, hi = (q.W - d < q.L - j) ? q.W - d : q.L - j;
+  unsigned long long w = 0ull;
+  any_mask_bit(q.okbits, j * (q.W + 1), 1, hi, [&](int sp) {
+    if (m[q.at(i, d + sp)] & UB_A) w |= 1ull << (sp - 1);
+    return false;
+  });
+  return w;
+}
+
 }  // namespace elemdp

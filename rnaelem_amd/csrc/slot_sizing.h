@@ -129,6 +129,8 @@ struct ZeroBinding {
   int S = 0, tab_row = 0, ap_rs = 0, shadow = 0, schedule = 0;   // the layout that was swept
   int useful_mask = 0, loop_prepass = 0, loop_outside = 0, live_blocks = 0, live_span = 0, deterministic = 0, fast = 0;   // options
 };
+// (option pair_terms is not compared: it drops terms of the outside pair sums that are exact zeros and were never added, so it
+// changes no stored entry)
 inline bool zeros_match(const ZeroBinding& held, const ZeroBinding& want) {
   return held.valid && want.valid && held.plan == want.plan && held.slots_gen == want.slots_gen && held.n_slots == want.n_slots &&
          held.band_stride == want.band_stride && held.own == want.own && held.n_seq == want.n_seq && held.S == want.S &&

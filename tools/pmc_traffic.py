@@ -7,7 +7,7 @@ times of a kernel-trace pass of the same command.
 
 The number of evaluations (scans) of a run is READ FROM THE RUN: k4_weights is launched once per evaluation / scan, k_mask once per
 load_batch -- separately for each of the three passes (they may run different commands).  Kernels of the evaluation are divided by the
-evaluations, load-time kernels (k_mask*, k6_*, k_plan_*, k_role_*, k_permute_items, k_useful_mask, k_live_blocks) by the loads.  With --bench the per-kernel
+evaluations, load-time kernels (k_mask*, k6_*, k_plan_*, k_role_*, k_permute_items, k_useful_mask, k_live_blocks, k_pair_terms) by the loads.  With --bench the per-kernel
 times of the train pipeline must add up to at most 1.05 x the ms_per_step of that bench line, or the tool fails: a wrong divisor
 shows up there first (round 3 divided 7 evaluations by 6: 17 %).  (The kernel trace runs the groups on ONE stream so that kernel
 times add up; the bench overlaps the tails of two streams and is 2 - 3 % faster than that sum.)
@@ -64,7 +64,7 @@ def family(k):
     return k.split("<")[0]
 
 
-LOAD_FAMILIES = ("k_mask", "k6_", "k_plan_", "k_role_", "k_permute_items", "k_useful_mask", "k_live_blocks")   # (the last two: once per plan)
+LOAD_FAMILIES = ("k_mask", "k6_", "k_plan_", "k_role_", "k_permute_items", "k_useful_mask", "k_live_blocks", "k_pair_terms")   # (the last three: once per plan)
 
 
 def counts(tab):
