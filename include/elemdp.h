@@ -378,6 +378,33 @@ int elemdp_node_profile(elemdp_handle* h, const double* x, int32_t n_param, doub
  * before elemdp_load_batch ELEMDP_ESTATE.  elemdp_last_timing afterwards: [whole call, sum passes + joint kernels, sequences handed
  * to the log-space form].  The other calls of the handle are unaffected; the list of the last pair call stays valid. */
 int elemdp_joint_profile(elemdp_handle* h, const double* x, int32_t n_param, double* counts, double* profile);
+/* Pair posteriors by motif node pair under the motif model x and the pair counts behind a stem logo.  The model
+ * emits the two bases of a motif pair jointly: a pair transition s -> sp of the automaton emits the left base by node st_l(sp) and
+ * the right base by node st_r(s).  A stem slot is a distinct node pair (left, right) over these transitions, slots in increasing
+ * (left, right) order, K of them; elemdp_stem_slots writes the two node indices of every slot (both arrays NULL: only counts them)
+ * and returns K.  It needs no device; cap < K is ELEMDP_EINVAL.  For a kept cell (i, j) and a slot k, Q(i, j, k) is the
+ * probability that bases i and j-1 pair AND the pair is emitted by a transition of slot k, over the ensemble of the scan's first sum
+ * pass (terminals ari and nasi, Z(ari, nasi): the ensemble of elemdp_pair_posteriors), from its inside / outside tables: the
+ * rule-1a and rule-1b terms of elemdp_node_profile routed to the pair of nodes.  Every entry is clamped to [0, 1]; nothing is
+ * renormalised.  sum_k Q(i, j, k) is the P of elemdp_pair_posteriors; summed over the slots of one left (right) node it is the L (R)
+ * column of elemdp_joint_profile.
+ *   counts:    required; counts[((n K + k) 5 + bl) 5 + br] = sum over the kept cells of Q(i, j, k) [seq_n[i] = bl] [seq_n[j-1] = br],
+ *              base codes 0 .. 4 (N A C G U), reduced on the device in a fixed order: the stem table of a set of sequences is the
+ *              sum of their blocks;
+ *   min_prob:  >= 0, or +inf.  Finite: the entries (sequence, i, j, slot, q) with q = Q(i, j, k) >= min_prob are kept on the device
+ *              in (sequence, i, j, slot) order for elemdp_stem_list, i 0-based and j exclusive as in elemdp_pair_list; at 0 the
+ *              list holds every slot of every kept cell.  +inf: no list, and no staging is allocated;
+ *   n_entries: NULL, or receives the length of the list.
+ * A sequence without any parse (Z = 0) has counts 0 and no entries, exactly; so has every sequence under ELEMDP_NO_RSS, where the
+ * band tables are not read.  Sequences that leave the double range of the scaled-linear tables, and every sequence under option
+ * pipeline 3, go through the same rule on the log-space tables of the fused scan kernel.  counts or x NULL, min_prob negative or NaN,
+ * more than 255 slots or pattern nodes: ELEMDP_EINVAL; a call before elemdp_load_batch: ELEMDP_ESTATE; elemdp_stem_list before any
+ * stem call on the resident batch: ELEMDP_ESTATE, with cap below the length of the list: ELEMDP_EINVAL (its arrays may be NULL).
+ * elemdp_last_timing afterwards: [whole call, sum passes + stem kernels, sequences handed to the log-space form].  The other calls
+ * of the handle are unaffected; the lists of the last pair call and the last conditional call stay valid. */
+int elemdp_stem_slots(const elemdp_handle* h, int32_t* node_left, int32_t* node_right, int32_t cap);
+int elemdp_stem_profile(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double* counts, int64_t* n_entries);
+int elemdp_stem_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q, int64_t cap);
 /* Accessibility under the motif model x: with U = max_width, access[U * (seq_off[n] + p) + (w - 1)], p 0-based,
  * w = 1 .. U, is the probability that the bases p .. p+w-1 of sequence n are all unpaired, over the ensemble of the scan's first sum
  * pass (terminals ari and nasi, Z(ari, nasi): the ensemble of elemdp_pair_posteriors and elemdp_context_profile), from its inside /

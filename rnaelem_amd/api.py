@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_pair_terms", "elemdp_pair_terms_host", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_joint_profile", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_joint_profile", "elemdp_stem_slots", "elemdp_stem_profile", "elemdp_stem_list", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -97,6 +97,9 @@ def load_library():
         L.elemdp_context_profile.argtypes = [hp, dp, C.c_int32, dp]
         L.elemdp_node_profile.argtypes = [hp, dp, C.c_int32, dp]
         L.elemdp_joint_profile.argtypes = [hp, dp, C.c_int32, dp, dp]
+        L.elemdp_stem_slots.argtypes = [hp, i32, i32, C.c_int32]
+        L.elemdp_stem_profile.argtypes = [hp, dp, C.c_int32, C.c_double, dp, C.POINTER(C.c_int64)]
+        L.elemdp_stem_list.argtypes = [hp, i32, i32, i32, i32, dp, C.c_int64]
         L.elemdp_accessibility.argtypes = [hp, dp, C.c_int32, C.c_int32, dp]
         L.elemdp_node_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_int32, dp, u8, i32, i32, i32, dp, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
@@ -571,6 +574,38 @@ class Engine:
             return counts
         return counts, [prof[7 * M * int(off[k]):7 * M * int(off[k + 1])].reshape(-1, M, 7).copy() for k in range(self.n_seq)]
 
+    # ---- pair posteriors by motif node pair and the stem logo table
+    def stem_slots(self):
+        """A (K, 2) int array: the node pair (left, right) of every stem slot -- the distinct pairs of pattern nodes that a pair
+        transition of the model emits jointly, in increasing (left, right) order (node indices as in node_profiles)."""
+        if getattr(self, "_stem_slots", None) is None:      # (the pattern's: built once per engine)
+            K = self._check(self._lib.elemdp_stem_slots(self._h, None, None, 0))
+            left, right = (np.zeros(max(K, 1), dtype=np.int32) for _ in range(2))
+            self._check(self._lib.elemdp_stem_slots(self._h, _i32(left), _i32(right), K))
+            self._stem_slots = np.stack([left[:K], right[:K]], axis=1)
+        return self._stem_slots.copy()
+
+    def stem_profiles(self, x, min_prob=np.inf):
+        """counts, an (n, K, 5, 5) array: per sequence and stem slot (stem_slots) the expected number of pairs the slot emits with
+        each left base and each right base (N A C G U), reduced on the device -- the table behind a stem logo (stem_logo).  With
+        a finite min_prob returns (counts, lists): per sequence (i, j, slot, q), the entries with q >= min_prob in (i, j, slot)
+        order, q the probability that bases i and j-1 (0-based) pair and the pair is emitted by that slot; the sum of q over the
+        slots of a cell is the p of pair_posteriors.  At min_prob 0 the list holds every slot of every kept cell."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        K, n = len(self.stem_slots()), max(self.n_seq, 0)
+        counts = np.zeros(max(n * K * 25, 1))
+        m = C.c_int64()
+        self._check(self._lib.elemdp_stem_profile(self._h, _dp(x), self.n_param, float(min_prob), _dp(counts), C.byref(m)))
+        counts = counts[:n * K * 25].reshape(n, K, 5, 5)
+        if not np.isfinite(min_prob):
+            return counts
+        m = m.value
+        seq, ii, jj, kk = (np.zeros(max(m, 1), dtype=np.int32) for _ in range(4))
+        q = np.zeros(max(m, 1))
+        self._check(self._lib.elemdp_stem_list(self._h, _i32(seq), _i32(ii), _i32(jj), _i32(kk), _dp(q), max(m, 1)))
+        bounds = np.searchsorted(seq[:m], np.arange(self.n_seq + 1))
+        return counts, [(ii[a:b].copy(), jj[a:b].copy(), kk[a:b].copy(), q[a:b].copy()) for a, b in zip(bounds[:-1], bounds[1:])]
+
     # ---- accessibility (DESIGN.md section 19)
     def accessibility(self, x, max_width=16):
         """One (L, U) array per sequence, U = max_width (1 .. 64): column w-1 of row p is the probability that the bases
@@ -681,3 +716,54 @@ def motif_logo(counts, weights=None):
         h2 = -np.where(base > 0, base * np.log2(np.where(base > 0, base, 1.0)), 0.0).sum(axis=1)
     info = np.where(ksum > 0, 2.0 - h2, 0.0)
     return dict(counts=total, occurrences=occ, base_freq=base, letter_freq=letter, information=info)
+
+
+STEM_PAIR_TYPES = ("CG", "GC", "GU", "UG", "AU", "UA")     # the order of a ')' node's theta row
+
+
+def stem_logo(counts, slots, names, weights=None):
+    """The table behind a stem logo from the (n, K, 5, 5) counts of Engine.stem_profiles, the (K, 2) slots of Engine.stem_slots
+    and the node names (Engine.describe()["node"]): the counts are summed over the sequences in input order, each times its
+    weight if weights are given.  Returns a dict of arrays over the K slots: counts (K, 5, 5), the weighted sum; labels, the two
+    node names of each slot as '<left index><name>-<right index><name>'; occurrences (K,), the expected number of pairs the slot
+    emits; pair_freq (K, 7), the frequencies of the six canonical pair types in the order of STEM_PAIR_TYPES, then "other" (any
+    other two bases, N included); information (K,), log2(6) - H2 of the six canonical frequencies renormalised, in bits;
+    mutual_information (K,), that of the left and the right column in bits, from the 4 x 4 block over A C G U.  A slot that
+    emits nothing has frequencies, information and mutual information 0.  There is no small-sample correction: the counts are
+    expectations, not a sample."""
+    counts = np.asarray(counts, dtype=np.float64)
+    slots = np.asarray(slots, dtype=np.int64).reshape(-1, 2)
+    if counts.ndim != 4 or counts.shape[2:] != (5, 5) or counts.shape[1] != len(slots):
+        raise ValueError("stem_logo: (n, K, 5, 5) counts and (K, 2) slots are expected")
+    n, K = counts.shape[:2]
+    if weights is None:
+        w = np.ones(n)
+    else:
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError("stem_logo: one weight per sequence is expected")
+    if len(slots) and (slots.min() < 0 or slots.max() >= len(names)):
+        raise ValueError("stem_logo: node index out of range")
+    total = np.zeros((K, 5, 5))
+    for k in range(n):
+        total += w[k] * counts[k]
+    occ = total.sum(axis=(1, 2))
+    code = {c: b for b, c in enumerate("NACGU")}
+    canon = np.stack([total[:, code[t[0]], code[t[1]]] for t in STEM_PAIR_TYPES], axis=1) if K else np.zeros((0, 6))
+    types = np.concatenate([canon, (occ - canon.sum(axis=1))[:, None]], axis=1)
+    freq = np.divide(types, occ[:, None], out=np.zeros_like(types), where=occ[:, None] > 0)
+    freq = np.maximum(freq, 0.0)          # (the remainder may round below 0)
+    csum = canon.sum(axis=1)
+    f6 = np.divide(canon, csum[:, None], out=np.zeros_like(canon), where=csum[:, None] > 0)
+
+    def entropy(f):
+        return -np.where(f > 0, f * np.log2(np.where(f > 0, f, 1.0)), 0.0)
+
+    info = np.where(csum > 0, np.log2(6.0) - entropy(f6).sum(axis=1), 0.0)
+    known = total[:, 1:, 1:]
+    ksum = known.sum(axis=(1, 2))
+    joint = np.divide(known, ksum[:, None, None], out=np.zeros_like(known), where=ksum[:, None, None] > 0)
+    mi = entropy(joint.sum(axis=2)).sum(axis=1) + entropy(joint.sum(axis=1)).sum(axis=1) - entropy(joint).sum(axis=(1, 2))
+    mi = np.where(ksum > 0, np.maximum(mi, 0.0), 0.0)
+    labels = ["%d%s-%d%s" % (l, names[l], r, names[r]) for l, r in slots]
+    return dict(counts=total, labels=labels, occurrences=occ, pair_freq=freq, information=info, mutual_information=mi)

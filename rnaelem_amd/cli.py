@@ -27,6 +27,11 @@
                                     # + the table behind a motif logo: per pattern node the expected emission counts of each base
                                     #   under each structure letter, over the sequences with exist_prob >= --logo-min-exist (0)
                                     #   (io.write_logo)
+    python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-stems stems.txt --out-stem-pairs sp.txt
+                                    # + the table behind a stem logo: per pair of pattern nodes that emit a base pair jointly the
+                                    #   expected counts of each left and right base, over the sequences with exist_prob >=
+                                    #   --logo-min-exist (io.write_stems); and one line per base pair and node pair with
+                                    #   probability >= --stem-min-prob (0.01) (io.stem_pair_line)
     python -m rnaelem_amd.cli       --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --out2 scan.raw
                                     # no sub-command = what script/elem spawns: train, write the model, scan (main.cpp:47-84)
     python -m rnaelem_amd.cli eval  --fastq pos.fq --motif-model model.txt --out1 fn.txt --out2 gr.txt     (motif_eval.hpp:23-54)
@@ -107,6 +112,14 @@ def build_parser():
                                           "under each structure letter, summed over the sequences (io.write_logo)")
     sub.choices["scan"].add_argument("--logo-min-exist", type=float, default=0.0,
                                      help="only sequences whose exist_prob is at least this enter the logo table")
+    sub.choices["scan"].add_argument("--out-stems", default=None,
+                                     help="the table behind a stem logo: per pair of pattern nodes that emit a base pair jointly the "
+                                          "expected counts of each left and right base, summed over the sequences that pass "
+                                          "--logo-min-exist (io.write_stems)")
+    sub.choices["scan"].add_argument("--out-stem-pairs", default=None,
+                                     help="base pairs labelled by the pair of pattern nodes that emits them: one line per entry with "
+                                          "sequence id, i, j, the two nodes and the probability (io.stem_pair_line)")
+    sub.choices["scan"].add_argument("--stem-min-prob", type=float, default=0.01, help="smallest probability listed in --out-stem-pairs")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -275,8 +288,11 @@ def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
 def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0,
                   out_samples=None, n_samples=100, sample_seed=0, out_context=None, out_nodes=None, out_sites=None, site_gamma=1.0,
                   max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0, out_access=None, access_width=16, out_logo=None,
-                  logo_min_exist=0.0):
+                  logo_min_exist=0.0, out_stems=None, out_stem_pairs=None, stem_min_prob=0.01):
     from .distributed import assigned_range
+    stem_parts = None if out_stems is None else out_stems + ".seqs"   # (as logo_parts)
+    want_stems = out_stems is not None or out_stem_pairs is not None
+    slots = eng.stem_slots() if want_stems else None                  # (the model's: once per run)
     logo_parts = None if out_logo is None else out_logo + ".seqs"     # (per-sequence counts, joined in input order before the sum)
     nodes = eng.describe()["node"]
     step = max(1, chunk)
@@ -288,7 +304,7 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
             if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None \
-                    and out_contrast is None and out_access is None and out_logo is None:
+                    and out_contrast is None and out_access is None and out_logo is None and not want_stems:
                 for (rid, codes, _), r in zip(part, res):
                     yield io.scan_record(rid, codes, r, nodes)
                 continue
@@ -308,6 +324,9 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             con = eng.conditional_pairs(m["x"], contrast_min_prob, contrast_gamma) if out_contrast is not None else None
             acc = eng.accessibility(m["x"], access_width) if out_access is not None else None
             jnt = eng.joint_profiles(m["x"]) if out_logo is not None else None
+            if want_stems:      # (one call gives the counts and the list)
+                stm = eng.stem_profiles(m["x"], stem_min_prob if out_stem_pairs is not None else np.inf)
+                stm_counts, stm_lists = stm if out_stem_pairs is not None else (stm, None)
             for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
                 texts = [io.scan_record(rid, codes, r, nodes)]
                 if out_pairs is not None:
@@ -330,19 +349,38 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                     texts.append(io.access_record(rid, acc[k]))
                 if out_logo is not None:
                     texts.append(io.logo_counts_record(rid, r["exist_prob"], jnt[k]))
+                if out_stem_pairs is not None:
+                    texts.append("".join(io.stem_pair_line(rid, i + 1, j, "%d%s" % (slots[t, 0], nodes[slots[t, 0]]),
+                                                           "%d%s" % (slots[t, 1], nodes[slots[t, 1]]), q) for i, j, t, q in zip(*stm_lists[k])))
+                if out_stems is not None:
+                    texts.append(io.stem_counts_record(rid, r["exist_prob"], stm_counts[k]))
                 yield tuple(texts)
 
     if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None and out_contrast is None \
-            and out_access is None and out_logo is None:
+            and out_access is None and out_logo is None and not want_stems:
         sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
     else:
-        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast, out_access, logo_parts)
-                         if o is not None]
+        outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast, out_access, logo_parts,
+                                   out_stem_pairs, stem_parts) if o is not None]
         sharded_write(recs, outs, rank, world, scan_part, barrier)
     if out_logo is not None:
         if rank == 0:
             write_logo_from_parts(logo_parts, out_logo, nodes, logo_min_exist)
         barrier()
+    if out_stems is not None:
+        if rank == 0:
+            write_stems_from_parts(stem_parts, out_stems, nodes, slots, logo_min_exist)
+        barrier()
+
+
+def write_stems_from_parts(parts_path, out_stems, nodes, slots, min_exist=0.0):
+    """The `--out-stems` file from the per-sequence count records in input order: the sequences with exist_prob >= min_exist are
+    summed in that order (api.stem_logo with weights 1 / 0); the records file is removed."""
+    parts = io.read_stem_counts(parts_path)
+    use = np.array([1.0 if ex >= min_exist else 0.0 for _, ex, _ in parts])
+    counts = np.stack([c for _, _, c in parts]) if parts else np.zeros((0, len(slots), 5, 5))
+    io.write_stems(out_stems, nodes, slots, api.stem_logo(counts, slots, nodes, use)["counts"], int(use.sum()), len(parts))
+    os.remove(parts_path)
 
 
 def write_logo_from_parts(parts_path, out_logo, nodes, min_exist=0.0):
@@ -367,7 +405,8 @@ def cmd_scan(a):
     eng = io.engine_from_model(m, a.device if a.device is not None else local_rank)
     _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
                   a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites,
-                  a.out_contrast, a.contrast_min_prob, a.contrast_gamma, a.out_access, a.access_width, a.out_logo, a.logo_min_exist)
+                  a.out_contrast, a.contrast_min_prob, a.contrast_gamma, a.out_access, a.access_width, a.out_logo, a.logo_min_exist,
+                  a.out_stems, a.out_stem_pairs, a.stem_min_prob)
     if world > 1:
         dist.destroy_process_group()
 

@@ -42,6 +42,7 @@
 #include "node_rules.h"
 #include "joint_rules.h"
 #include "sample_rules.h"
+#include "stem_rules.h"
 #include "table_slots.h"
 
 namespace elemdp {
@@ -228,6 +229,11 @@ class Engine {
   // joint node-by-context posteriors (joint_rules.h): 35 n_node counts per sequence, and on request 7 n_node
   // doubles per position of the batch
   void joint_profile(const double* x, int n_param, double* counts, double* profile);
+  // pair posteriors by motif node pair (stem_rules.h): 25 K counts per sequence; with a finite min_prob the
+  // labelled list stays on the device for stem_list.  stem_slots: the node pair of every slot (host only), returns K.
+  int stem_slots(int32_t* node_left, int32_t* node_right, int cap) const;
+  void stem_profile(const double* x, int n_param, double min_prob, double* counts, int64_t* n_entries);
+  void stem_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q, int64_t cap);
   // accessibility (access_rules.h): max_width doubles per position of the batch, the widths 1 .. max_width
   void accessibility(const double* x, int n_param, int max_width, double* access);
   // maximum expected accuracy motif alignments and site lists over that profile (node_mea_rules.h); outputs as
@@ -412,6 +418,11 @@ class Engine {
   DevBuf d_cx_cells_, d_cx_o_, d_cx_prof_;
   DevBuf d_ac_T_, d_ac_vec_, d_ac_out_;   // accessibility: the four planes per slot, the log-space form's vectors, the result
   DevBuf d_jn_lists_, d_jn_X_, d_jn_vec_, d_jn_prof_, d_jn_counts_;   // joint profiles: lists and slot map, per-cell scratch per slot, the log-space form's vectors, the results
+  // stem profiles: the transitions by slot, Q of the table slots, the parse marks and counts of the call, the staging list, the
+  // final list of the last call (n_stem_ < 0: none)
+  DevBuf d_sp_lists_, d_sp_X_, d_sp_has_, d_sp_counts_, d_sp_kept_, d_sp_koff_, d_sp_cnt_, d_sp_off_, d_sp_si_, d_sp_sj_, d_sp_sk_, d_sp_sq_;
+  DevBuf d_sl_seq_, d_sl_i_, d_sl_j_, d_sl_k_, d_sl_q_;
+  int64_t n_stem_ = -1;
   DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
   // node MEA: the chain lists, the backpointer scratch (M bytes per position), the rows, sites per sequence, start / end / score / confidence per slot
   DevBuf d_nm_lists_, d_nm_bp_, d_nm_node_, d_nm_ns_, d_nm_s0_, d_nm_s1_, d_nm_sc_, d_nm_cf_;
@@ -977,6 +988,7 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   n_seq_ = 0;
   n_pairs_ = -1;
   n_cond_ = -1;
+  n_stem_ = -1;
   streaming_ = false;
   train_rows_ = false;
   BatchShape shape = check_batch(seq, off, qual, qoff, fix, n);
@@ -2972,6 +2984,163 @@ void Engine::joint_profile(const double* x, int n_param_in, double* counts, doub
   last_ms[2] = (double)n_flagged;
 }
 
+// ---- the stem slots of the automaton (stem_rules.h): host only, no device needed
+int Engine::stem_slots(int32_t* node_left, int32_t* node_right, int cap) const {
+  std::vector<int32_t> lists;
+  const int K = stem_lists_build(lay_, ints_.data(), &lists);
+  if (!node_left && !node_right) return K;
+  if (cap < K) throw ArgError("stem_slots: buffer too small");
+  for (int k = 0; k < K; ++k) {   // (the node pairs behind the K + 1 offsets: StemLists::left / right)
+    if (node_left) node_left[k] = lists[K + 1 + 2 * k];
+    if (node_right) node_right[k] = lists[K + 2 + 2 * k];
+  }
+  return K;
+}
+
+// ---- pair posteriors by motif node pair and the pair counts behind a stem logo (stem_rules.h).  The scan's first
+// sum pass per group, then on the group's table slots, before the next group of the stream reuses them: Q of every cell by stem
+// slot (k_stem_cells), the counts (k_stem_counts) and, with a finite min_prob, the list entries into the staging ranges
+// (k_stem_seq).  The log-space form -- the fused scan kernel up to its first outside pass, then the same rule on its dense tables
+// -- for the sequences that leave the double range and under pipeline 3, with the same two kernels behind the launch.  Then the
+// batch list in (sequence, i, j, slot) order.  The staging is sized by the bound kept cells x K.  Every buffer is the call's own:
+// leaves the lists of the last pair call and the last conditional call alone.
+void Engine::stem_profile(const double* x, int n_param_in, double min_prob, double* counts, int64_t* n_entries) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (!counts) throw ArgError("stem_profile: null counts");
+  if (!(min_prob >= 0.)) throw ArgError("stem_profile: min_prob must be >= 0");
+  std::vector<int32_t> lists;
+  const int K = stem_lists_build(lay_, ints_.data(), &lists);
+  if (K > kStemMaxSlots || au_.M() > 255) throw ArgError("stem_profile: more than 255 stem slots or pattern nodes");
+  const size_t nc = (size_t)K * kStemBlock;
+  const bool want_list = min_prob < HUGE_VAL;
+  n_stem_ = -1;
+  if (streaming_) {
+    std::vector<int32_t> hs, hi, hj, hk;
+    std::vector<double> hq;
+    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+      int64_t m = 0;
+      e.stem_profile(x, n_param_in, min_prob, counts + nc * (size_t)c0, &m);
+      const size_t b = hs.size();
+      hs.resize(b + m); hi.resize(b + m); hj.resize(b + m); hk.resize(b + m); hq.resize(b + m);
+      e.stem_list(hs.data() + b, hi.data() + b, hj.data() + b, hk.data() + b, hq.data() + b, m);
+      for (size_t t = b; t < hs.size(); ++t) hs[t] += c0;   // (batch-global sequence indices)
+    });
+    d_sl_seq_.upload(hs, st_); d_sl_i_.upload(hi, st_); d_sl_j_.upload(hj, st_); d_sl_k_.upload(hk, st_); d_sl_q_.upload(hq, st_);
+    HIP_OK(hipStreamSynchronize(st_));
+    n_stem_ = (int64_t)hs.size();
+    if (n_entries) *n_entries = n_stem_;
+    return;
+  }
+  require_resident("stem_profile", n_param_in);
+  upload_params(x, lay_, false);
+  const int n = n_seq_;
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  ScanPos pos(n_seqpos, n);
+  d_sp_counts_.alloc(8 * std::max<size_t>(nc, 1) * (size_t)n);
+  d_sp_has_.alloc(4 * (size_t)n);
+  d_sp_lists_.upload(lists, st_);
+  HIP_OK(hipMemsetAsync(d_sp_has_.as<void>(), 0, 4 * (size_t)n, st_));
+  HIP_OK(hipStreamSynchronize(st_));   // (the host vector goes out of use with the copy; the marks are clear before any group runs)
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  StemArgs sa;
+  std::memset(&sa, 0, sizeof(sa));
+  sa.plans = plan_.d_plans.as<SeqPlan>();
+  sa.seq_out = d_seq_out_.as<double>(); sa.out_stride = out_stride_;
+  sa.seq = d_seq_.as<uint8_t>();
+  sa.okbits = d_okbits1_.as<uint32_t>();
+  sa.lists = d_sp_lists_.as<int32_t>();
+  sa.K = K; sa.n_list = (int32_t)lists.size();
+  sa.x_stride = stem_scratch_size(Lmax_, Wmax_, K);
+  sa.has = d_sp_has_.as<int32_t>();
+  sa.counts = d_sp_counts_.as<double>();
+  sa.min_prob = min_prob;
+  if (want_list) {   // staging ranges: a sequence's list holds at most K entries per kept cell
+    d_sp_kept_.alloc(8 * (size_t)n); d_sp_koff_.alloc(8 * ((size_t)n + 1));
+    d_sp_cnt_.alloc(8 * (size_t)n); d_sp_off_.alloc(8 * ((size_t)n + 1));
+    HIP_OK(launch_pair_kept(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, d_sp_kept_.as<int64_t>(), st_));
+    HIP_OK(launch_pair_prefix(d_sp_kept_.as<int64_t>(), n, d_sp_koff_.as<int64_t>(), st_));
+    int64_t n_kept = 0;
+    HIP_OK(hipMemcpyAsync(&n_kept, d_sp_koff_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipStreamSynchronize(st_));
+    const size_t cap = (size_t)n_kept * (size_t)K;
+    d_sp_si_.alloc(4 * cap); d_sp_sj_.alloc(4 * cap); d_sp_sk_.alloc(cap); d_sp_sq_.alloc(8 * cap);
+    // (cnt needs no clearing: k_stem_seq writes the count of every sequence, in exactly one of the two forms, 0 where it has no Q)
+    sa.koff = d_sp_koff_.as<int64_t>(); sa.cnt = d_sp_cnt_.as<int64_t>();
+    sa.st_i = d_sp_si_.as<int32_t>(); sa.st_j = d_sp_sj_.as<int32_t>(); sa.st_k = d_sp_sk_.as<uint8_t>(); sa.st_q = d_sp_sq_.as<double>();
+  }
+  const bool no_rss = (flags_ & ELEMDP_NO_RSS) != 0;
+  int n_flagged = 0;
+  const bool sums_on_batch = opt_pipeline_ == 4;
+  if (sums_on_batch)
+    n_flagged = scan_sums(pos, [&](LinArgs& a) {
+      if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("stem_profile: the scan sweeps another automaton than the lists name");
+      d_sp_X_.alloc(8 * sa.x_stride * (size_t)std::max(slots_.n(), 1));
+      sa.X = d_sp_X_.as<double>();
+      sa.skip_flagged = 1;
+    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      StemArgs sk = sa;
+      sk.idx = ak.grp;
+      sk.X = sa.X + slot0 * sa.x_stride;
+      if (!no_rss) HIP_OK(launch_stem_cells(ak, sk, G, (Lg + 1) * (Wg + 1), st));   // (else no mark is set: the band tables are not read)
+      HIP_OK(launch_stem_counts(sk, G, Lg, Wg, st));
+      if (want_list) HIP_OK(launch_stem_seq(sk, G, st));
+    });
+  // ---- the log-space form, in chunks of at most as many sequences as the table slots hold (the scratch is bounded by the chunk)
+  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
+    if (!sums_on_batch) d_sp_X_.alloc(8 * sa.x_stride * (size_t)chunk);
+    d.stm = sa;
+    d.stm.X = d_sp_X_.as<double>();
+    return chunk;
+  }, [&](const int32_t* idx, int C) {
+    StemArgs sk = sa;
+    sk.idx = idx;
+    sk.X = d_sp_X_.as<double>();
+    sk.skip_flagged = 0;
+    HIP_OK(launch_stem_counts(sk, C, Lmax_, Wmax_, st_));
+    if (want_list) HIP_OK(launch_stem_seq(sk, C, st_));
+  });
+  HIP_OK(hipEventRecord(ev_[3], st_));
+  // ---- the list in (sequence, i, j, slot) order
+  int64_t total = 0;
+  if (want_list) {
+    HIP_OK(launch_pair_prefix(d_sp_cnt_.as<int64_t>(), n, d_sp_off_.as<int64_t>(), st_));
+    HIP_OK(hipMemcpyAsync(&total, d_sp_off_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipStreamSynchronize(st_));
+    d_sl_seq_.alloc(4 * (size_t)total); d_sl_i_.alloc(4 * (size_t)total); d_sl_j_.alloc(4 * (size_t)total);
+    d_sl_k_.alloc(4 * (size_t)total); d_sl_q_.alloc(8 * (size_t)total);
+    HIP_OK(launch_stem_scatter(sa, d_sp_off_.as<int64_t>(), n, d_sl_seq_.as<int32_t>(), d_sl_i_.as<int32_t>(), d_sl_j_.as<int32_t>(),
+                               d_sl_k_.as<int32_t>(), d_sl_q_.as<double>(), st_));
+  }
+  if (nc) HIP_OK(hipMemcpyAsync(counts, d_sp_counts_.as<void>(), 8 * nc * (size_t)n, hipMemcpyDeviceToHost, st_));
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms_all = 0, ms_dp = 0;
+  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
+  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
+  last_ms[0] = ms_all;
+  last_ms[1] = ms_dp;
+  last_ms[2] = (double)n_flagged;
+  n_stem_ = total;
+  if (n_entries) *n_entries = total;
+}
+
+void Engine::stem_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q, int64_t cap) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (n_stem_ < 0) throw StateError("stem_list before stem_profile");
+  if (cap < n_stem_) throw ArgError("stem_list: buffer too small");
+  const size_t m = (size_t)n_stem_;
+  if (m == 0) return;
+  if (seq) HIP_OK(hipMemcpy(seq, d_sl_seq_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (i) HIP_OK(hipMemcpy(i, d_sl_i_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (j) HIP_OK(hipMemcpy(j, d_sl_j_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (slot) HIP_OK(hipMemcpy(slot, d_sl_k_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
+  if (q) HIP_OK(hipMemcpy(q, d_sl_q_.as<void>(), 8 * m, hipMemcpyDeviceToHost));
+}
+
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h).  The node pass of
 // node_profile, then k_node_mea once over the profile of the whole batch on the engine's stream, behind the last group and the
 // log-space form.  The profile goes to the host only where the caller gave a buffer.  Leaves the list of the last pair call alone.
@@ -3451,6 +3620,26 @@ int elemdp_joint_profile(elemdp_handle* h, const double* x, int32_t n_param, dou
   ELEMDP_TRY
   if (!h || !x || !counts) throw elemdp::ArgError("elemdp_joint_profile: null argument");
   h->e->joint_profile(x, n_param, counts, profile);
+  ELEMDP_CATCH
+}
+int elemdp_stem_slots(const elemdp_handle* h, int32_t* node_left, int32_t* node_right, int32_t cap) {
+  try {
+    if (!h) throw elemdp::ArgError("elemdp_stem_slots: null handle");
+    return h->e->stem_slots(node_left, node_right, cap);
+  } catch (const std::exception& ex) {
+    return fail(ex);
+  }
+}
+int elemdp_stem_profile(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double* counts, int64_t* n_entries) {
+  ELEMDP_TRY
+  if (!h || !x || !counts) throw elemdp::ArgError("elemdp_stem_profile: null argument");
+  h->e->stem_profile(x, n_param, min_prob, counts, n_entries);
+  ELEMDP_CATCH
+}
+int elemdp_stem_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q, int64_t cap) {
+  ELEMDP_TRY
+  if (!h) throw elemdp::ArgError("elemdp_stem_list: null handle");
+  h->e->stem_list(seq, i, j, slot, q, cap);
   ELEMDP_CATCH
 }
 int elemdp_node_mea(elemdp_handle* h, const double* x, int32_t n_param, double gamma, int32_t max_sites, double* profile,

@@ -154,6 +154,27 @@ struct JointArgs {
   double* counts;
 };
 
+// ---- pair posteriors by motif node pair and the pair counts behind a stem logo (stem_rules.h, stem_kernels.hip).  A launch covers
+// the G sequences idx[0 .. G) of one group or chunk; slot g of the launch owns the per-cell scratch X + g * x_stride: Q of every
+// cell by stem slot (stem_at).  has[n] = 1 once batch index n has Q (a parse, and a model with secondary structure).  The counts
+// of batch index n go to counts + 25 K * n at (k 5 + bl) 5 + br; its list entries to the staging range that starts at K * koff[n].
+struct StemArgs {
+  const SeqPlan* plans;           // batch plans (batch index)
+  const int32_t* idx;             // idx[g] = batch index of the sequence in slot g (launch_stem_counts, launch_stem_seq)
+  const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
+  int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)
+  const uint8_t* seq;             // base codes of the batch (BatchArrays::seq)
+  const uint32_t* okbits;         // the pair mask of the batch
+  const int32_t* lists;           // the pair transitions by stem slot (stem_lists_build)
+  int32_t K, n_list;              // stem slots, ints of the lists
+  double* X; size_t x_stride;
+  int32_t* has;
+  double* counts;
+  double min_prob;
+  const int64_t* koff; int64_t* cnt;   // kept cells before batch index n (launch_pair_kept / launch_pair_prefix), entries staged
+  int32_t* st_i; int32_t* st_j; uint8_t* st_k; double* st_q;   // staging (null: no list is kept)
+};
+
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h, node_mea_kernels.hip) over the profile of the
 // whole batch: batch index n with seq_base b and length L writes the row of slot k at node + max_sites * b + k * L (the sampler's
 // layout), n_sites[n], and start / end / score / conf at [n * max_sites + k]
@@ -222,6 +243,9 @@ struct DpArgs {
   // SCAN, joint node-by-context posteriors (joint_rules.h, log-space form): jnt.profile non-null = stop after inside + the first
   // outside pass and write the 7 M columns of every position of the sequence order[w] (k_joint_counts reads them behind the launch)
   JointArgs jnt;
+  // SCAN, pair posteriors by motif node pair (stem_rules.h, log-space form): stm.X non-null = stop after inside + the first outside
+  // pass and write Q of the sequence order[w] to slot w of stm (k_stem_counts and k_stem_seq read it behind the launch)
+  StemArgs stm;
 };
 
 // arguments of the diagonal-synchronous train pipeline (train_kernels.hip)
@@ -500,6 +524,14 @@ hipError_t launch_node_pos(const LinArgs& a, const NodeArgs& c, int G, int Lmax,
 hipError_t launch_joint_rows(const LinArgs& a, const JointArgs& c, int G, int Lmax, hipStream_t st);
 hipError_t launch_joint_pos(const LinArgs& a, const JointArgs& c, int G, int Lmax, hipStream_t st);
 hipError_t launch_joint_counts(const JointArgs& c, int G, hipStream_t st);
+// k_stem_cells (one lane per cell: Q by stem slot) behind launch_lin_scan_group (SCAN_PASS_START) on the same slots and stream;
+// k_stem_counts (one workgroup per sequence: the K 25 counts) and k_stem_seq (its list entries with q >= min_prob into its staging
+// range) behind it, or behind the fused scan kernel (DpArgs::stm); k_stem_scatter: the batch list in (sequence, i, j, slot) order
+hipError_t launch_stem_cells(const LinArgs& a, const StemArgs& c, int G, int cells_max, hipStream_t st);
+hipError_t launch_stem_counts(const StemArgs& c, int G, int Lmax, int Wmax, hipStream_t st);
+hipError_t launch_stem_seq(const StemArgs& c, int G, hipStream_t st);
+hipError_t launch_stem_scatter(const StemArgs& c, const int64_t* off, int n, int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q,
+                               hipStream_t st);
 // k_node_mea behind the node pass of the whole batch (both forms), on the engine's stream: one wave per sequence
 hipError_t launch_node_mea(const NodeMeaArgs& a, int n_seq, hipStream_t st);
 // kept pairs of every sequence of the batch (the staging capacity), off[0..n] = exclusive prefix of cnt[0..n) with off[n] the total,

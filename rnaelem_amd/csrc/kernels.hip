@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "node_rules.h"
 #include "joint_rules.h"
+#include "stem_rules.h"
 #include "pair_rules.h"
 #include "plan_rules.h"
 #include "sample_lane.h"
@@ -846,6 +847,20 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
             if (live) joint_value(f, jl, m, q, Tin, Tout, X, pos, node, !no_rss, prof + (size_t)CTX_COLS * t);
             else joint_no_parse(node, prof + (size_t)CTX_COLS * t);
           }
+          continue;
+        }
+        if (a.stm.X) {   // pair posteriors by motif node pair (stem_rules.h): one cell per lane, slot-major, on this first pass
+          const StemLog f(ZL);
+          const StemLists sl{a.stm.lists, a.stm.K, SP_ALL};
+          const bool live = ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL && !no_rss;   // (else no Q: k_stem_counts and k_stem_seq read none)
+          double* X = a.stm.X + (size_t)w * a.stm.x_stride;
+          if (tid == 0) a.stm.has[n] = live ? 1 : 0;
+          if (live)
+            for (int t = tid; t < ncell; t += kThreads) {
+              const int d = t / (L + 1), i = t - d * (L + 1);
+              if (i + d > L) continue;
+              for (int k = 0; k < a.stm.K; ++k) X[stem_at(L, W, k, i, d)] = stem_value(f, sl, m, q, Tin, Tout, d, i, k);
+            }
           continue;
         }
         if (a.acc.T) {   // accessibility (access_rules.h): the units (term, position) of this first pass

@@ -4,6 +4,7 @@
 // the same tables give the same bits.
 #include <hip/hip_runtime.h>
 
+#include "block_scan.h"
 #include "kernels.h"
 #include "pair_rules.h"
 
@@ -14,22 +15,6 @@ namespace {
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 typedef dbl2 dbl2_a8 __attribute__((aligned(8)));
 
-// exclusive prefix over the workgroup (kThreads lanes); returns the workgroup's total through *total
-__device__ int64_t block_exclusive(int64_t v, int64_t* s, int64_t* total) {
-  const int tid = threadIdx.x;
-  s[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < kThreads; off <<= 1) {
-    const int64_t u = tid >= off ? s[tid - off] : 0;
-    __syncthreads();
-    s[tid] += u;
-    __syncthreads();
-  }
-  const int64_t incl = s[tid];
-  *total = s[kThreads - 1];
-  __syncthreads();
-  return incl - v;
-}
 }  // namespace
 
 // one lane per cell (i fastest, so that neighbouring lanes read neighbouring rows); grid (cells / kThreads, G)

@@ -459,3 +459,74 @@ def read_logo(path):
         blocks.append(rows)
         k += 2 + len(CONTEXT_LETTERS)
     return dict(n_used=used, n_total=total, names=names, occurrences=np.array(occ), counts=np.array(blocks, dtype=np.float64).reshape(-1, 7, 5))
+
+
+def stem_counts_record(rid, exist_prob, counts):
+    """Record of one sequence on the way to the `scan --out-stems` file: `id: <id>`, `exist: <exist_prob>` and `stems: [...]`, the
+    sequence's (K, 5, 5) block of Engine.stem_profiles in full precision: the ranks of a sharded run write these, and rank 0
+    joins them in input order before it sums."""
+    counts = np.asarray(counts, dtype=np.float64)
+    return "id: %s\nexist: %.17g\nstems: [%s]\n" % (rid, exist_prob, ",".join("%.17g" % v for v in counts.ravel()))
+
+
+def read_stem_counts(path):
+    """-> list of (id, exist_prob, (K, 5, 5) array) from the per-sequence records of stem_counts_record."""
+    lines = open(path).read().split("\n")
+    out, k = [], 0
+    while k + 2 < len(lines) and lines[k].startswith("id: "):
+        if not lines[k + 1].startswith("exist: ") or not lines[k + 2].startswith("stems: "):
+            raise ValueError("stem counts record %r: exist and stems lines expected" % lines[k][4:])
+        body = lines[k + 2][7:].strip("[]")
+        v = np.array([float(t) for t in body.split(",")] if body else [], dtype=np.float64)
+        out.append((lines[k][4:], float(lines[k + 1][7:]), v.reshape(-1, 5, 5)))
+        k += 3
+    return out
+
+
+def stem_pair_line(rid, i, j, left, right, q):
+    """One line of the `scan --out-stem-pairs` file: the sequence id, the 1-based positions i < j of the two paired bases
+    (as the `scan --out-pairs` file numbers them: cell (i0, j0) -> i0+1, j0), the two pattern nodes that emit them as `<index><name>` and the probability q of that labelled pair."""
+    return "%s\t%d\t%d\t%s\t%s\t%.6g\n" % (rid, i, j, left, right, q)
+
+
+def write_stems(path, names, slots, counts, n_used, n_total=None):
+    """The `scan --out-stems` file: a header `sequences: <used> / <read>` and `columns: N A C G U`, then one record per stem slot:
+    `stem: <index><name> <index><name>` (the pattern nodes of the left and the right base), `occurrences: <expected number of
+    pairs>` and five lines `N: [...]` .. `U: [...]`, the row of a left base over the right bases (17 significant digits: the
+    file is a sum that further sums are formed from); slots: (K, 2) node indices; counts: a (K, 5, 5) array."""
+    slots = np.asarray(slots, dtype=np.int64).reshape(-1, 2)
+    counts = np.asarray(counts, dtype=np.float64).reshape(len(slots), 5, 5)
+    lines = ["sequences: %d / %d" % (n_used, n_used if n_total is None else n_total), "columns: " + " ".join(LOGO_BASES)]
+    for k, (l, r) in enumerate(slots):
+        lines += ["stem: %d%s %d%s" % (l, names[l], r, names[r]), "occurrences: %.17g" % counts[k].sum()]
+        lines += ["%s: [%s]" % (b, ",".join("%.17g" % v for v in counts[k, t])) for t, b in enumerate(LOGO_BASES)]
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def read_stems(path):
+    """-> dict(n_used, n_total, slots (K, 2), names (K pairs of node names), occurrences (K,), counts (K, 5, 5)) from a
+    `scan --out-stems` file."""
+    lines = open(path).read().split("\n")
+    if len(lines) < 2 or not lines[0].startswith("sequences: ") or lines[1] != "columns: " + " ".join(LOGO_BASES):
+        raise ValueError("stems file %r: header expected" % path)
+    used, total = (int(t) for t in lines[0][11:].split(" / "))
+    slots, names, occ, blocks = [], [], [], []
+    k = 2
+    while k < len(lines) and lines[k].startswith("stem: "):
+        heads = lines[k][6:].split(" ")
+        if len(heads) != 2 or not all(h[:-1].isdigit() for h in heads) or not lines[k + 1].startswith("occurrences: "):
+            raise ValueError("stems file %r: record of slot %d expected at line %d" % (path, len(blocks), k + 1))
+        slots.append([int(h[:-1]) for h in heads])
+        names.append((heads[0][-1], heads[1][-1]))
+        occ.append(float(lines[k + 1][13:]))
+        rows = []
+        for t, b in enumerate(LOGO_BASES):
+            h, body = lines[k + 2 + t].split(": ", 1)
+            if h != b:
+                raise ValueError("stems file %r: line %r where %r was expected" % (path, h, b))
+            rows.append([float(v) for v in body.strip("[]").split(",")])
+        blocks.append(rows)
+        k += 2 + len(LOGO_BASES)
+    return dict(n_used=used, n_total=total, slots=np.array(slots, dtype=np.int64).reshape(-1, 2), names=names, occurrences=np.array(occ),
+                counts=np.array(blocks, dtype=np.float64).reshape(-1, 5, 5))
