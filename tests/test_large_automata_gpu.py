@@ -1,0 +1,309 @@
+"""Patterns of 63 to 128 interval states through every kernel family, against the oracle.  The largest
+automaton of the other files has S = 59, 60 active states with the shadow copy of (0,0): below one wave.  Above 64 the kernels
+map states to lanes, parts, chunks and LDS slices by code nothing else runs.  No checker and no tolerance of its own: the train
+cases go through train_check.check_train_path, the scan and pair cases through pair_check.check_pair_path(scan=True), every
+posterior product through the check_* function of its own GPU file, on the patterns and batches of tests/large_automata.py
+(tests/test_large_automata_cpu.py: their state counts, the host rules and the parse shares of the batches, without a GPU).
+
+What the engine sweeps (Engine::flatten_automaton): the shadow state, and with it the merged train schedule (n_pass 1), for
+S < 127 -- at most 127 active states; S = 127 and 128 sweep the plain automaton under the reference's two outside passes
+(n_pass 2).  So no handle has more than 128 active states, the `S > 128` branches of the exterior-chain kernels are out of
+reach, and the shadow lane of the outside chain (ps == shadow among 128 lanes) always exists: test_train asserts n_pass.
+
+Exterior-chain kernels: group_geometry launches k4_in_ext and the outside chain with 512 threads (the four-fold blocked chain)
+for every group of at most 1024 sequences, whatever the state count; 128 threads for a larger group, for the outside chain of
+the deterministic mode, and under option dbg 8192 (the plain chain without the fetch ahead).  Every batch here is one small group,
+so "default" runs both chains in the blocked form, "deterministic" the outside chain in the plain form and "plain-chain" (dbg
+8192) both in the plain form: nparts = 128 / n_active = 1 from S = 64 (65 active states) in all of them, 2 at S = 63.  The LDS
+ring of the chain's last rows (ext_ring_doubles: 64 rows at W = 50, at most 48 KiB) exists up to 96 active states -- S = 63 to 78
+-- and not for S = 126, 127, 128, which read the chain from the global table.
+
+Band kernels (the forms launch_lin_group names under ELEMDP_LDS_DEBUG): the table-driven programs need lists that fit them
+(every pattern here but S = 127, with the pruned lists) and an automaton blob of at most 4096 ints, which is staged whole: S = 63,
+64 and 65 run them (form fp2), S = 78 to 128 the general kernels that read the blob from global memory (form generic), with 127
+states in one cell of a workgroup's 256 lanes at cpb = 2; option fast 0 at S = 64 gives the general kernels with the staged blob
+(form staged); test_train asserts which.
+
+Log-space pipeline (pipeline 3): wave_gather.h's second state chunk (lane c * 64 + lane, c = 1) from 65 active states."""
+import numpy as np
+import pytest
+
+from rnaelem_amd import api
+from tests import cond_check as cd
+from tests import ctx_check as cc
+from tests import large_automata as la
+from tests import test_access_gpu as t_access
+from tests import test_cond_gpu as t_cond
+from tests import test_ctx_gpu as t_ctx
+from tests import test_joint_gpu as t_joint
+from tests import test_node_gpu as t_node
+from tests import test_node_mea_gpu as t_mea
+from tests import test_stem_gpu as t_stem
+from tests import train_check as tc
+from tests.pair_check import check_pair_path, oracle_refs
+from tests.sample_check import Driver, check_sample_path
+from tests.test_pair_posterior_gpu import perturbed
+from tests.test_pair_shapes_gpu import oracle_maker
+from tests.test_train_shapes_gpu import LINE
+
+pytestmark = pytest.mark.gpu
+
+PAR = "~T2004~"
+W, C = 50, 30
+TABLE_DRIVEN = {"fp2-waves", "fp2", "fast"}
+BLOB_STAGED_WHOLE = 4096        # ints: Engine::prepare_lin stages the whole automaton blob up to this size, else its small part
+
+
+def engine(S, opts=()):
+    eng = api.Engine(la.PATTERN[S], PAR, W, C, 1e-4, 0.1, 0, 0)
+    for k, v in opts:
+        eng.set_option(k, v)
+    return eng
+
+
+_X = {}
+
+
+def params(S):
+    if S not in _X:
+        _X[S] = perturbed(engine(S))
+    return _X[S]
+
+
+def loaded(S, seqs, quals, opts=()):
+    eng = engine(S, opts)
+    eng.load_batch(seqs, quals)
+    return eng, params(S)
+
+
+@pytest.fixture
+def forms(monkeypatch, capfd):
+    """sets ELEMDP_LDS_DEBUG; forms() returns (k4_in, k4_out, stage_ext, ext_nt, ext_ring, n_pass, combine) of every
+    launch_lin_group since the last call"""
+    monkeypatch.setenv("ELEMDP_LDS_DEBUG", "1")
+    return lambda: [m.groups()[1:] for m in map(LINE.search, capfd.readouterr().err.splitlines()) if m]
+
+
+# ---- refusals
+
+@pytest.mark.parametrize("S,pattern", la.REFUSED, ids=[str(S) for S, _ in la.REFUSED])
+def test_patterns_above_128_states_are_refused(S, pattern):
+    with pytest.raises(api.ElemdpError, match="more than 128 interval states") as e:
+        api.Engine(pattern, PAR, W, C, 1e-4, 0.1, 0, 0)
+    assert e.value.code == -1
+
+
+def test_a_pattern_of_128_states_constructs():
+    eng = engine(128)
+    assert eng.describe()["S"] == 128 and eng.describe()["layout"]["S"] == 128
+
+
+# ---- train
+
+TRAIN_OPTS = {
+    "default": (),
+    "deterministic": (("deterministic", 1),),
+    "plain-chain": (("dbg", 8192),),
+    "fast0": (("fast", 0),),
+    "pipeline3": (("pipeline", 3),),
+}
+TRAIN_CASES = [(S, name) for S in la.ACCEPTED for name in ("default", "deterministic")] + \
+              [(S, "plain-chain") for S in (64, 78, 126, 128)] + [(64, "fast0")] + [(S, "pipeline3") for S in la.LOG_SPACE]
+_TRAIN_REFS = {}
+
+
+def train_refs(S, name, make):
+    """the oracle's rows of a batch, computed once for all its option sets"""
+    if (S, name) not in _TRAIN_REFS:
+        seqs, quals = make(S)
+        _TRAIN_REFS[(S, name)] = seqs, quals, tc.oracle_train_refs(oracle_maker(la.PATTERN[S], W, C, params(S)), seqs, quals)
+    return _TRAIN_REFS[(S, name)]
+
+
+def assert_motif_parses(refs, quals):
+    """three quarters of the batch's sequences, under either label, are not skipped by the oracle"""
+    n = len(quals) // 2
+    got = refs.unskipped(quals)
+    assert got[0] >= la.PARSE_SHARE * n and got[1] >= la.PARSE_SHARE * n, got
+
+
+def check_forms(S, name, seen, lay):
+    """lay: describe()["layout"] of the engine, the automaton a train evaluation sweeps"""
+    if name == "pipeline3":
+        assert not seen
+        return
+    shadow = S < la.SHADOW_BELOW
+    assert seen, "no launch_lin_group line"
+    band = {"generic"} if lay["n_ints"] > BLOB_STAGED_WHOLE else TABLE_DRIVEN if lay["fp_ok"] and name != "fast0" else {"staged"}
+    assert (band == {"generic"}) == (S > 65)
+    for k4_in, k4_out, stage_ext, ext_nt, ext_ring, n_pass, combine in seen:
+        assert {k4_in, k4_out} <= band, (k4_in, k4_out, band)
+        assert (stage_ext, ext_ring) == ("1", "1")
+        assert ext_nt == ("128" if name == "plain-chain" else "512"), ext_nt
+        assert n_pass == ("1" if shadow else "2"), n_pass
+        assert combine == ("1" if shadow or name == "deterministic" else "0"), combine
+
+
+@pytest.mark.parametrize("S,name", TRAIN_CASES, ids=["%d-%s" % c for c in TRAIN_CASES])
+def test_train(S, name, forms):
+    """Twelve rows (six sequences of L 40 .. 131 under both labels): seq_stats, the count columns, fn, gr and the partial vector
+    against the oracle, a repeated evaluation.  Which chain form each option set runs, and where nparts is 1 and the ring is
+    gone: the module's docstring; check_forms asserts what the launcher reports (ext_nt of the inside chain, n_pass, the band
+    form)."""
+    seqs, quals, refs = train_refs(S, "train", la.train_batch)
+    assert_motif_parses(refs, quals)
+    eng, x = loaded(S, seqs, quals, TRAIN_OPTS[name])
+    _, res, stats, counts = tc.check_train_path(eng, seqs, quals, x, oracle_maker(la.PATTERN[S], W, C, x), refs=refs)
+    check_forms(S, name, forms(), eng.describe()["layout"])
+    if name == "deterministic":         # bit for bit from one evaluation to the next
+        res2 = eng.train_eval(x)
+        c2 = eng.seq_counts()
+        assert res2[0] == res[0] and np.array_equal(res2[1], res[1])
+        assert np.array_equal(eng.seq_stats(), stats, equal_nan=True)
+        assert all(np.array_equal(c2[key], counts[key]) for key in tc.COUNTS)
+
+
+@pytest.mark.parametrize("S", la.LOG_SPACE)
+def test_train_on_seventy_short_sequences(S, forms):
+    """One group of 70 sequences (L 52 .. 76 under both labels): 70 workgroups per chain launch and per band diagonal, still
+    the blocked chain (a group leaves it above 1024 sequences only: test_one_group_too_large_for_the_exterior_ring of
+    test_train_shapes_gpu.py)."""
+    seqs, quals, refs = train_refs(S, "many", la.many_batch)
+    assert_motif_parses(refs, quals)
+    eng, x = loaded(S, seqs, quals)
+    tc.check_train_path(eng, seqs, quals, x, oracle_maker(la.PATTERN[S], W, C, x), refs=refs)
+    check_forms(S, "default", forms(), eng.describe()["layout"])
+
+
+# ---- scan and pairs
+
+GAMMAS = (0.5, 1.0, 4.0)
+
+
+def pair_run(S, seqs, quals, opts=()):
+    eng, x = loaded(S, seqs, quals, opts)
+    refs, res, mea = check_pair_path(eng, seqs, quals, x, oracle_maker(la.PATTERN[S], W, C, x), gammas=GAMMAS, scan=True)
+    e = [r["scan"]["exist_prob"] for r in refs]
+    return refs, res, mea, e
+
+
+@pytest.mark.parametrize("S", la.SCAN)
+def test_scan_and_pairs(S):
+    """pair list, P and unpaired against the oracle, MEA against the mirror and the optimum, scan records (start, end, inner,
+    exist_prob, Ys, Ye, rss, psihat, E[N]) against the oracle's; one sequence of the four is marked as without the motif"""
+    seqs, quals = la.scan_batch(S)
+    refs, res, mea, e = pair_run(S, seqs, quals)
+    assert sum(v > 0.0 for v in e) >= la.PARSE_SHARE * len(seqs), e
+    assert sum(len(r[2]) for r in res) > 0
+
+
+def test_scan_and_pairs_with_two_slots_reused():
+    """S = 126, option group 2: five unsorted sequences in three groups on two slots"""
+    seqs, quals = la.group2_batch(126)
+    refs, res, mea, e = pair_run(126, seqs, quals, opts=(("group", 2),))
+    assert sum(v > 0.0 for v in e) >= la.PARSE_SHARE * len(seqs), e
+
+
+def test_scan_and_pairs_across_the_row_blocks():
+    """S = 64, L = 257: the second 256-row block of k_pair_seq and k_pair_mea on an automaton of more than 64 active states"""
+    seqs, quals = la.long_batch(64)
+    refs, res, mea, e = pair_run(64, seqs, quals)
+    assert all(v > 0.0 for v in e), e
+    assert refs[0]["P"] is not None and len(res[0][3]) == 257 and len(res[0][2]) > 0
+
+
+# ---- posterior products
+
+@pytest.fixture(scope="module", params=la.WEIGHTED)
+def product(request):
+    """(S, seqs, quals, x, exist_prob per sequence from the oracle's scan)"""
+    S = request.param
+    seqs, quals = la.product_batch(S)
+    x = params(S)
+    refs = oracle_refs(oracle_maker(la.PATTERN[S], W, C, x), seqs, quals)
+    e = [r["scan"]["exist_prob"] for r in refs]
+    assert sum(v > 0.0 for v in e) >= la.PARSE_SHARE * len(seqs), e
+    assert sum(v >= cd.E_MIN for v in e) >= 2, e
+    return S, seqs, quals, x, refs
+
+
+def test_context_profiles(product):
+    S, seqs, quals, x, _ = product
+    eng, _ = loaded(S, seqs, quals)
+
+    def make():
+        o = cc.ctx_oracle(la.PATTERN[S], W, C)
+        o.set_params(x)
+        return o
+    refs = t_ctx.table_refs(make, seqs, quals, x)
+    assert all(r is not None for r in refs)
+    t_ctx.check_profiles(eng, x, seqs, refs, what=S)
+
+
+def test_node_profiles(product):
+    S, seqs, quals, x, _ = product
+    eng, _ = loaded(S, seqs, quals)
+    make = t_node.oracle_with(la.PATTERN[S], x, W, C)
+    refs = t_node.table_refs(make, seqs, quals, x)
+    assert all(r is not None for r in refs)
+    t_node.check_profiles(eng, x, seqs, quals, refs, make=make, what=S)
+
+
+def test_joint_profiles(product):
+    S, seqs, quals, x, _ = product
+    eng, _ = loaded(S, seqs, quals)
+    refs = t_joint.table_refs(t_joint.oracle_with(la.PATTERN[S], x, W, C), seqs, quals, x)
+    assert all(r is not None for r in refs)
+    t_joint.check_joint(eng, x, seqs, refs, what=S)
+
+
+def test_stem_profiles(product):
+    S, seqs, quals, x, _ = product
+    eng, _ = loaded(S, seqs, quals)
+    make = t_stem.oracle_with(la.PATTERN[S], x, W, C)
+    refs = t_stem.table_refs(make, seqs, quals, x)
+    assert all(r is not None for r in refs)
+    counts, _, _ = t_stem.check_stems(eng, x, seqs, refs, what=S)
+    t_stem.check_en(make, seqs, quals, refs, counts, eng.stem_slots(), what=S)
+
+
+@pytest.mark.parametrize("width", [16, 64])
+def test_accessibility(product, width):
+    S, seqs, quals, x, _ = product
+    eng, _ = loaded(S, seqs, quals)
+    refs = t_access.table_refs(t_access.maker(la.PATTERN[S], x, W, C), seqs, quals, x, width)
+    assert all(r is not None for r in refs)
+    t_access.check_access(eng, x, seqs, refs, width, what=(S, width))
+
+
+def test_conditional_pairs(product):
+    S, seqs, quals, x, _ = product
+    eng, _ = loaded(S, seqs, quals)
+    refs = t_cond.table_refs(t_cond.pattern_oracles(la.PATTERN[S], x, W, C), seqs, quals)
+    assert sum(r["e"] >= cd.E_MIN for r in refs) >= 2, [r["e"] for r in refs]
+    t_cond.check_batch(eng, x, seqs, refs, what=S)
+
+
+def test_node_mea(product):
+    S, seqs, quals, x, _ = product
+    eng, _ = loaded(S, seqs, quals)
+    refs = t_node.table_refs(t_node.oracle_with(la.PATTERN[S], x, W, C), seqs, quals, x)
+    found = 0
+    for K, gamma in ((1, 1.0), (4, 4.0)):
+        found += sum(len(g["start"]) for g in t_mea.check_batch(eng, x, refs, gamma, K, what=S))
+    assert found > 0
+
+
+def test_sampler(product):
+    """70 samples per sequence (a full lane round of k_sample and a partial one): status, validity on the kept cells, the draws
+    of the CPU driver, exact log-probabilities against the oracle.  Not the frequencies against the posteriors (check_sample_path
+    without refs): their bound, five standard deviations + 2e-3, is meant for thousands of samples -- at 70 a single draw of one
+    of the many cells below 1e-3 is outside it."""
+    S, seqs, quals, x, _ = product
+    eng, _ = loaded(S, seqs, quals)
+    drv = Driver(la.PATTERN[S], PAR, W, C)
+    drv.set_fast(True)
+    out = check_sample_path(eng, seqs, quals, x, oracle_maker(la.PATTERN[S], W, C, x), 70, seed=S, drv=drv, n_check=6,
+                            what="S %d" % S)
+    assert all(st == eng.SAMPLED for _, _, _, st in out["res"])
+    assert out["total"] >= 70          # (the driver drew at least one sequence's samples in the scaled-linear form)
