@@ -69,6 +69,7 @@
 #include "lin_rules.h"
 #include "lin_fast.h"
 #include "lin_views.h"
+#include "loop_rows_layout.h"
 #include "scan_rules.h"
 #include "wave_gather.h"
 
@@ -1008,8 +1009,7 @@ __global__ __launch_bounds__(kBT, W8 ? ELEMDP_LB_IN_FAST : ELEMDP_LB_IN) void k4
 // [d][i]) and the wave stores every diagonal's rows as whole lines.  Every entry k4_in stores is stored: the chain value where the
 // cell's UB_L bit is on, an exact 0 where it is off (loop_inside_entry: the operations of fast_inside_unary in their order).
 constexpr int kLoopLanes = 64;     // rows per workgroup = one wave
-constexpr int kLoopColsMax = 16;   // most columns of an L row the pre-pass takes (lin_loop_prepass_ok)
-constexpr int kLoopProgW = 8;      // program words staged per column: P[0 .. 4 + kFastR)
+// (kLoopColsMax, the most columns of an L row the pre-pass takes, and kLoopProgW, the program words staged per column: loop_rows_layout.h)
 static_assert(4 + kFastR <= kLoopProgW, "the staged program holds the right transitions");
 static size_t loop_prepass_lds(const AutomatonLayout& A) {
   return sizeof(double) * (2 * (size_t)kLoopLanes * A.tab_rs[ST_L] + 5 * (size_t)A.n_wr) + sizeof(int32_t) * kLoopColsMax * kLoopProgW;
@@ -2068,32 +2068,35 @@ __global__ __launch_bounds__(kBT, W6 ? ELEMDP_LB_OUT6 : ELEMDP_LB_OUT) void k4_o
 // behind the sweep, where out E, in P and in L are complete and no diagonal order binds it -- in one kernel, k4_out_lrows, which
 // stores no L entry at all (the out L rows keep whatever they held).  A workgroup owns R consecutive rows of a sequence and walks
 // their diagonals in tiles of kRowsT, from min(W, L - i0) down to 0; the tile's entries live in LDS, [row][diagonal + 1][L column].
+// Once per workgroup, in one round of loads before the tile loop, the plan data of its rows go to LDS: the mask bytes of its cells,
+// the pair-mask words of the bits cell(i - 1, d + 2), base and weight of the positions i0 .. i0 + R - 1 + dmax, and the runs of
+// records of every tile (none of it hangs on theta, lambda or a table value).
 // Per tile:
 //   cells   lane = (row, L column), the tile's diagonals unrolled: every operand that does not hang on the chain.  in L stays in the
 //           lane's registers; where the cell is an E cell, t6b = out E * xhp (6b) opens the entry's sum and its energy statistic goes to
-//           the lane's (loop_outside_cell, lin_fast.h).  All loads are selects on the address, none waits for another but through
-//           the mask byte and the pair mask: two round trips per tile.
+//           the lane's (loop_outside_cell, lin_fast.h).  All loads are selects on the address; mask byte and pair bit come from LDS,
+//           so none waits for another: one round trip per tile.
 //   seeds   the heavy sum HL of rule 6c (roles 1 and 2 of the item records) is added to the entries.  The role records of a row's
 //           cells (cell index i * (W + 1) + d) are one run of the CSR arrays; the runs of both roles form one list, of which kSeedCap
 //           records at a time are staged in LDS, one lane each (the rows of the three operands, both weights, the cell's entries);
 //           then lane = (record, tuple): three gathers and one LDS add, kSeedBatch of them per lane with all loads first (2: 26.9 ms
 //           per evaluation of the bench against 29.4 at 1; 4 costs a resident workgroup in registers: 30.2).  The records of d = 0
-//           are left out, as in k4_out; a cell without UB_L takes none.  What hangs on the tile alone -- the CSR offsets, the
-//           records in front of every run (a scan in wave 0 over the runs' ends), base and weight of j -- is loaded at once.
+//           are left out, as in k4_out; a cell without UB_L takes none.  A record names its own cell, so a lane needs the run of its
+//           record alone (a binary search over the staged run sums) in front of the record load.
 //   chain   lane = (row, L column), d downwards in place over the entries (loop_outside_chain): one barrier per step and no global
 //           load.  The parent row is the entry above in the tile; above the tile's top it is the last row of the tile before,
 //           which its lane carries in a register into slot nd.
 // R = kBT / (columns of an L row), so that every lane has a chain entry (at most kRowsMax, which bounds the run tables).  kRowsT = 8:
-// on the bench model (16 columns, R = 16) 18 KB of entries + 8 KB of staged records + 3 KB of tables and statistics, 5 workgroups
-// = 20 of 32 waves per CU, what the two kernels this one replaces kept; 17 diagonals per tile would leave 3.  Block ids go through
-// swizzled_block: the row blocks of a sequence share the L2 that holds its out E / in P / in L rows.
-constexpr int kRowsT = 8, kRowsMax = 32, kSeedCap = 256, kSeedBatch = 2;   // (kSeedCap: records staged at a time)
+// on the bench model (13 columns under schedule 1, R = 19) 17 KB of entries + 8 KB of staged records + 3 KB of tables and statistics
+// + 3 KB of plan data = 31 840 bytes, 5 workgroups = 20 of 32 waves per CU, what the two kernels this one replaces kept; 17
+// diagonals per tile would leave 3.  Block ids go through swizzled_block: the row blocks of a sequence share the L2 that holds its
+// out E / in P / in L rows.
+// (kRowsT = 8, kRowsMax = 32, kSeedCap = 256 records staged at a time, kSeedBatch = 2: loop_rows_layout.h, whose loop_rows_layout
+// gives the kernel its regions and the launcher its bytes)
 static_assert(2 * kRowsMax <= 64, "the runs of a tile are scanned by one wave");
-__host__ __device__ inline int loop_rows_r(int rs) { const int r = kBT / (rs > 0 ? rs : 1); return r < kRowsMax ? r : kRowsMax; }
-static size_t loop_rows_lds(const AutomatonLayout& A) {
-  const size_t rs = A.tab_rs[ST_L], R = loop_rows_r(A.tab_rs[ST_L]);
-  return sizeof(double) * (R * (kRowsT + 1) * rs + 2 * kSeedCap + (R + kRowsT) + 5 * (size_t)A.n_wr + 2 * (size_t)A.n_theta + 4) +
-         sizeof(int32_t) * (2 * R * (kRowsT + 1) + 2 * R + 1 + 4 * kSeedCap + 4 * (size_t)A.n_quad + (size_t)A.n_lane + kLoopColsMax * (kLoopProgW + 1) + (R + kRowsT));
+static_assert(kBT == kLoopRowsThreads && kSeedCap <= kBT, "the layout's workgroup; a record per lane");
+static size_t loop_rows_lds(const AutomatonLayout& A, int W) {
+  return (size_t)loop_rows_lds_bytes(A.tab_rs[ST_L], W, A.n_wr, A.n_theta, A.n_quad, A.n_lane);
 }
 __global__ __launch_bounds__(kBT) void k4_out_lrows(LinArgs a) {
   extern __shared__ double lds[];
@@ -2103,30 +2106,79 @@ __global__ __launch_bounds__(kBT) void k4_out_lrows(LinArgs a) {
   make_lviews(a, by, v);
   const LPass pi = lpass(a, v);
   if (pi.skip) return;
+  PhaseClock pc;   // (slots 2, 7, 13, 14, 15: cells, everything in front of the tile loop, record staging, gathers, chain)
+  pc.start(a.prof);
   const AutomatonLayout& A = a.lay;
   const int tid = threadIdx.x, L = v.q.L, W = v.q.W, nt = A.n_theta, nq = A.n_quad, HD = A.n_lane;
   const int rs = v.out.rs[ST_L], R = loop_rows_r(rs), TS = (kRowsT + 1) * rs;   // (TS: the entries of a row)
   const int i0 = bx * R;
   if (i0 > L) return;
   const int nrow = (R < L - i0 + 1) ? R : L - i0 + 1, nrr = 2 * nrow;           // (nrr: runs of records, [role][row])
-  double* acc = lds;                                                  // [row][diagonal of the tile, + the parent row][column]
-  double* s_xw = acc + R * TS;                                        // staged records: exp(lambda_k tsc) [k][record],
-  double* s_ew = s_xw + 2 * kSeedCap;                                 // position weight of j = i0 + d0 + . of the tile
-  double* wr = s_ew + R + kRowsT;
-  double* l_en = wr + 5 * A.n_wr;
-  int* offs = reinterpret_cast<int*>(l_en + 2 * nt + 4);              // [run][diagonal + 1]: CSR offsets of the role
-  int* pre = offs + 2 * R * (kRowsT + 1);                             // [run + 1]: records of the runs before
-  int* s_row = pre + 2 * R + 1;                                       // ... the rows of their three operands and the cell's entries [4][record]
-  int* tq = s_row + 4 * kSeedCap;                                     // the column records of the tuples [role][2 nq]
-  int* lcol = tq + 4 * nq;                                            // lane of the unary phase -> L column
-  int32_t* prog = lcol + HD;                                          // the outside program of the state that owns the column
-  int32_t* pst = prog + kLoopColsMax * kLoopProgW;                    // ... and that state
-  int* s_b = pst + kLoopColsMax;                                      // base of j = i0 + d0 + . of the tile
+  const LoopRowsLds y = loop_rows_layout(rs, a.wmax, A.n_wr, nt, nq, HD);   // (the regions: loop_rows_layout.h)
+  char* const lds8 = reinterpret_cast<char*>(lds);
+  double* acc = reinterpret_cast<double*>(lds8 + y.acc.off);
+  double* s_xw = reinterpret_cast<double*>(lds8 + y.xw.off);
+  double* s_ew = reinterpret_cast<double*>(lds8 + y.ew.off);
+  double* wr = reinterpret_cast<double*>(lds8 + y.wr.off);
+  double* l_en = reinterpret_cast<double*>(lds8 + y.en.off);
+  int* s_lo = reinterpret_cast<int*>(lds8 + y.lo.off);
+  int* s_pre = reinterpret_cast<int*>(lds8 + y.pre.off);
+  int* s_row = reinterpret_cast<int*>(lds8 + y.srow.off);
+  int* tq = reinterpret_cast<int*>(lds8 + y.tq.off);
+  int* lcol = reinterpret_cast<int*>(lds8 + y.lcol.off);
+  int32_t* prog = reinterpret_cast<int32_t*>(lds8 + y.prog.off);
+  int32_t* pst = reinterpret_cast<int32_t*>(lds8 + y.pst.off);   // (behind prog: the two are cleared as one)
+  uint32_t* s_okw = reinterpret_cast<uint32_t*>(lds8 + y.okw.off);
+  uint8_t* s_pb = reinterpret_cast<uint8_t*>(lds8 + y.pb.off);
+  uint8_t* s_ub = reinterpret_cast<uint8_t*>(lds8 + y.ub.off);
   const int32_t* G = v.m.big;
+  const int dmax = (W < L - i0) ? W : L - i0;   // (uniform: the first row of the workgroup is its longest)
+  const int okw0 = (i0 > 0 ? (i0 - 1) * (W + 1) : 0) >> 5;   // the first staged word of the pair mask
   for (int t = tid; t < kLoopColsMax * (kLoopProgW + 1); t += kBT) prog[t] = 0;
   for (int t = tid; t < 5 * A.n_wr; t += kBT) wr[t] = a.lin[A.lin_wr + t];
   for (int t = tid; t < 2 * nt + 4; t += kBT) l_en[t] = 0.;
   for (int t = tid; t < 4 * nq; t += kBT) tq[t] = G[A.fqc_out + 2 * nq + t];   // (roles 1 and 2)
+  // ---- the plan data of the workgroup, once: nothing here hangs on theta, lambda or a table value, and the tiles read it from LDS.
+  // The mask bytes of the cells (row r, d = 0 .. dmax), 0 where the cell lies beyond the sequence
+  for (int t = tid; t < (dmax + 1) * R; t += kBT) {
+    const int d = div_small(t, R), rw = t - d * R;
+    const bool in = i0 + rw + d <= L;
+    const int ub = v.q.ubits(in ? i0 + rw : 0, in ? d : 0);
+    s_ub[t] = (uint8_t)(in ? ub : 0);
+  }
+  // the words of the pair mask that hold the bits cell(i - 1, d + 2) of the workgroup's cells (one run of bits: W + 1 per row)
+  {
+    const int last_bit = (i0 + R - 2) * (W + 1) + W, end_bit = (L + 1) * (W + 1) - 1;
+    const int okw1 = (last_bit < end_bit ? (last_bit > 0 ? last_bit : 0) : end_bit) >> 5;
+    for (int t = tid; t <= okw1 - okw0 && t < y.nokw; t += kBT) s_okw[t] = v.q.okbits[okw0 + t];
+  }
+  // base and position weight of the positions i0 .. i0 + R - 1 + dmax
+  for (int t = tid; t < R + dmax; t += kBT) {
+    const int j = i0 + t;
+    s_pb[t] = j < L ? v.q.seq[j] : (uint8_t)0;
+    s_ew[t] = v.q.ews[j < L ? j : L];
+  }
+  // the runs of records of every tile: the role records of a row's cells (cell index i * (W + 1) + d) are one run of the CSR arrays,
+  // so a tile's run is bounded by the offsets at its two edges (no loop sums on the diagonal d = 0, as in k4_out: its records are
+  // left out of the row's run).  A wave takes a tile, a lane a run: its first record and, by a scan over the wave, the records of
+  // the runs before it
+  for (int tt = tid >> 6; tt <= dmax / kRowsT; tt += kWaves) {
+    const int ln = tid & 63, dhi = dmax - tt * kRowsT, d0 = dhi >= kRowsT ? dhi - kRowsT + 1 : 0;
+    const bool ok = ln < nrr && nq > 0;
+    const int role = ln >= nrow, ri = i0 + ln - role * nrow;
+    const int32_t* off = role ? v.q.by_right_off : v.q.by_left_off;
+    int lo = off[ok ? v.q.cell(ri, d0 > 0 ? d0 : 1) : 0], hi = off[ok ? v.q.cell(ri, dhi + 1) : 0];
+    lo = ok ? lo : 0;
+    hi = ok ? hi : 0;
+    int n = hi - lo;   // (inclusive scan over the wave)
+#pragma unroll
+    for (int sft = 1; sft < 64; sft <<= 1) {
+      const int up = __shfl_up(n, sft);
+      if (ln >= sft) n += up;
+    }
+    if (ln < nrr) { s_lo[tt * 2 * R + ln] = lo; s_pre[tt * (2 * R + 1) + ln + 1] = n; }
+    if (ln == 0) s_pre[tt * (2 * R + 1)] = 0;
+  }
   __syncthreads();
   for (int k = tid; k < HD; k += kBT) {
     const int s = a.ints[A.f_live_out + k];
@@ -2164,104 +2216,52 @@ __global__ __launch_bounds__(kBT) void k4_out_lrows(LinArgs a) {
   const float rcp_nq = 1.0f / (float)(nq > 0 ? nq : 1);
   const double* IB = v.in.band;
   const double* OB = v.out.band;
-  const int dmax = (W < L - i0) ? W : L - i0;   // (uniform: the first row of the workgroup is its longest)
   double carry = 0.;
-  for (int dhi = dmax; dhi >= 0; dhi -= kRowsT) {
+  pc.mark<7>();
+  for (int dhi = dmax, tt = 0; dhi >= 0; dhi -= kRowsT, ++tt) {
     const int d0 = dhi >= kRowsT ? dhi - kRowsT + 1 : 0, nd = dhi - d0 + 1;
+    const int* const pre = s_pre + tt * (2 * R + 1);   // [run + 1]: records of the tile's runs before
+    const int* const rlo = s_lo + tt * 2 * R;          // [run]: its first record
     // ---- cells
     double inL[kRowsT], t6[kRowsT];
-    {
-      int ub[kRowsT];
-      uint32_t pw[kRowsT];
 #pragma unroll
-      for (int dd = 0; dd < kRowsT; ++dd) {
-        const int d = d0 + dd;
-        const bool in = have && dd < nd && i + d <= L;
-        const bool up = in && i > 0 && d + 2 <= W && i + d + 1 <= L;   // (the bounds of pair_ok(i - 1, d + 2))
-        ub[dd] = v.q.ubits(in ? i : 0, in ? d : 0);
-        ub[dd] = in ? ub[dd] : 0;
-        pw[dd] = v.q.okbits[up ? (uint32_t)v.q.cell(i - 1, d + 2) >> 5 : 0u];
-        pw[dd] = up ? pw[dd] : 0u;
-      }
-#pragma unroll
-      for (int dd = 0; dd < kRowsT; ++dd) {
-        const int d = d0 + dd, c_up = v.q.cell(i - 1, d + 2);
-        const bool on = (ub[dd] & UB_L) != 0, eok = on && ((pw[dd] >> (c_up & 31)) & 1u);
-        inL[dd] = v.in.ldc(ST_L, d, i, c, on);
-        const double oE = v.out.ldc(ST_E, d, i, cEo, eok), xhp = xw_cell(v.q, kl, XT_HP, eok ? c_up : 0), ehp = v.q.e_hp[eok ? c_up : 0];
-        t6[dd] = 0.;
-        if (eok && inL[dd] != 0.) t6[dd] = loop_outside_cell(inL[dd], oE, xhp, ehp, invZ, ehs, sink);
-      }
+    for (int dd = 0; dd < kRowsT; ++dd) {
+      const int d = d0 + dd, c_up = v.q.cell(i - 1, d + 2);
+      const bool in = have && dd < nd && i + d <= L;
+      const bool up = in && i > 0 && d + 2 <= W && i + d + 1 <= L;   // (the bounds of pair_ok(i - 1, d + 2))
+      const bool on = (s_ub[in ? d * R + r : 0] & UB_L) != 0 && in;
+      const bool eok = on && up && ((s_okw[up ? (c_up >> 5) - okw0 : 0] >> (c_up & 31)) & 1u);
+      inL[dd] = v.in.ldc(ST_L, d, i, c, on);
+      const double oE = v.out.ldc(ST_E, d, i, cEo, eok), xhp = xw_cell(v.q, kl, XT_HP, eok ? c_up : 0), ehp = v.q.e_hp[eok ? c_up : 0];
+      t6[dd] = 0.;
+      if (eok && inL[dd] != 0.) t6[dd] = loop_outside_cell(inL[dd], oE, xhp, ehp, invZ, ehs, sink);
     }
     if (lane) {
 #pragma unroll
       for (int dd = 0; dd < kRowsT; ++dd) row_e[dd * rs] = dd == nd ? carry : t6[dd];
       row_e[kRowsT * rs] = carry;
     }
-    // ---- seeds.  The loads that hang on the tile alone, all at once: the CSR offsets of the runs' cells (no loop sums on the
-    // diagonal d = 0, as in k4_out: the records of its cells are left out of the row's run), the two ends of every run for the
-    // records of the runs before it (wave 0), base and position weight of j
-    {
-      constexpr int kOffU = (2 * kRowsMax * (kRowsT + 1) + kBT - 1) / kBT;
-      int ov[kOffU], os[kOffU];
-#pragma unroll
-      for (int u = 0; u < kOffU; ++u) {
-        const int t = tid + u * kBT;
-        const bool ok = t < nrr * (nd + 1) && nq > 0;
-        const int rr = ok ? div_small(t, nd + 1) : 0, dd = ok ? t - rr * (nd + 1) : 0, role = rr >= nrow, d = d0 + dd;
-        const int32_t* off = role ? v.q.by_right_off : v.q.by_left_off;
-        os[u] = t < nrr * (nd + 1) ? rr * (kRowsT + 1) + dd : -1;
-        ov[u] = off[ok ? v.q.cell(i0 + rr - role * nrow, d > 0 ? d : 1) : 0];
-        ov[u] = ok ? ov[u] : 0;
-      }
-      int lo = 0, hi = 0;
-      if (tid < 64) {
-        const bool ok = tid < nrr && nq > 0;
-        const int role = tid >= nrow, ri = i0 + tid - role * nrow;
-        const int32_t* off = role ? v.q.by_right_off : v.q.by_left_off;
-        lo = off[ok ? v.q.cell(ri, d0 > 0 ? d0 : 1) : 0];
-        hi = off[ok ? v.q.cell(ri, d0 + nd) : 0];
-        lo = ok ? lo : 0;
-        hi = ok ? hi : 0;
-      }
-      int jb = 0;
-      double jw = 0.;
-      if (tid < nrow + nd) {
-        const int j = i0 + d0 + tid;
-        jb = j < L ? (int)v.q.seq[j] : 0;
-        jw = v.q.ews[j < L ? j : L];
-      }
-#pragma unroll
-      for (int u = 0; u < kOffU; ++u)
-        if (os[u] >= 0) offs[os[u]] = ov[u];
-      if (tid < 64) {
-        int n = hi - lo;   // (inclusive scan over the wave)
-#pragma unroll
-        for (int sft = 1; sft < 64; sft <<= 1) {
-          const int up = __shfl_up(n, sft);
-          if (tid >= sft) n += up;
-        }
-        if (tid < nrr) pre[tid + 1] = n;
-        if (tid == 0) pre[0] = 0;
-      }
-      if (tid < nrow + nd) { s_b[tid] = jb; s_ew[tid] = jw; }
-    }
-    __syncthreads();
+    pc.mark<2>();
+    // ---- seeds.  What hangs on the tile alone -- its runs of records -- was staged before the tile loop; a record names its own
+    // cell (k_role_build keys role 1 by (i, k - i) and role 2 by (l, j - l), and a run holds the records of its row's cells of the
+    // tile's diagonals), so a lane needs the run of its record, by a binary search over at most 64 runs, and nothing more
     const int n_rec = pre[nrr];
+    if (n_rec == 0) __syncthreads();   // (the entries of the tile, for the chain)
     for (int p0 = 0; p0 < n_rec; p0 += kSeedCap) {
       const int np = (kSeedCap < n_rec - p0) ? kSeedCap : n_rec - p0;
       // one record per lane: its cell, the rows of its operands, its weights
       for (int xs = tid; xs < np; xs += kBT) {
         const int x = p0 + xs;
-        int rr = 0;
-        while (rr + 1 < nrr && pre[rr + 1] <= x) ++rr;
-        const int* ro = offs + rr * (kRowsT + 1);
-        const int n = ro[0] + (x - pre[rr]);
-        int dd = 0;
-        while (dd + 1 < nd && ro[dd + 1] <= n) ++dd;   // the cell that owns record n
-        const int role = rr >= nrow, rw = rr - role * nrow, ri = i0 + rw, d = d0 + dd;
-        const bool on = ri + d <= L && (v.q.ubits(ri, d) & UB_L);
+        int rr = 0, rhi = nrr - 1;   // the last run with pre[run] <= x
+        while (rr < rhi) {
+          const int mid = (rr + rhi + 1) >> 1;
+          if (pre[mid] <= x) rr = mid; else rhi = mid - 1;
+        }
+        const int n = rlo[rr] + (x - pre[rr]);
+        const int role = rr >= nrow, rw = rr - role * nrow;
         const LoopItem it = (role ? v.q.items_right : v.q.items_left)[n];
+        const int d = role ? it.j - it.l : it.k - it.i, dd = d - d0;   // the cell that owns the record: (i0 + rw, d)
+        const bool on = dd >= 0 && dd < nd && (s_ub[dd >= 0 && dd < nd ? d * R + rw : 0] & UB_L);
         s_row[xs] = (int)v.out.cidx(ST_E, it.j - it.i, it.i, 0);
         s_row[kSeedCap + xs] = (int)v.in.cidx(ST_P, it.l - it.k, it.k, 0);
         s_row[2 * kSeedCap + xs] = (int)(role ? v.in.cidx(ST_L, it.k - it.i, it.i, 0) : v.in.cidx(ST_L, it.j - it.l, it.l, 0));
@@ -2270,6 +2270,7 @@ __global__ __launch_bounds__(kBT) void k4_out_lrows(LinArgs a) {
         s_xw[kSeedCap + xs] = lin_weight(v.m.lambda[1], it.tsc);
       }
       __syncthreads();
+      pc.mark<13>();
       // lane = (record, tuple): three gathers and one add into the cell's entry -- kSeedBatch of them at a time, all loads first: a
       // wave that waits for one triple at a time is bound by the round trip, not by bytes
       for (int wb = tid; wb < np * nq; wb += kSeedBatch * kBT) {
@@ -2298,6 +2299,7 @@ __global__ __launch_bounds__(kBT) void k4_out_lrows(LinArgs a) {
           }
       }
       __syncthreads();
+      pc.mark<14>();
     }
     // ---- chain
     double oL = carry;
@@ -2309,13 +2311,14 @@ __global__ __launch_bounds__(kBT) void k4_out_lrows(LinArgs a) {
         const int d = d0 + dd, j = i + d;
         double sL = 0.;
         if (j < L && d + 1 <= W)   // (the cell's CF_DOL flag)
-          sL = loop_outside_chain<kFastR>(P, enr, fr, wr, row_e + (dd + 1) * rs - c, inL[dd], s_b[r + dd], s_ew[r + dd], invZ, v.m.no_prf != 0, sink);
+          sL = loop_outside_chain<kFastR>(P, enr, fr, wr, row_e + (dd + 1) * rs - c, inL[dd], (int)s_pb[r + d], s_ew[r + d], invZ, v.m.no_prf != 0, sink);
         oL = row_e[dd * rs] + sL;
       }
       if (lane) row_e[dd * rs] = oL;
       __syncthreads();   // (one barrier per step, as in k4_in_loops)
     }
     carry = oL;
+    pc.mark<15>();
   }
   lflush(a, v, pi, sink, l_en, kBT, (int)bx);
 }
@@ -2811,13 +2814,14 @@ bool lin_loop_prepass_ok(const AutomatonLayout& A, const int32_t* ints, int min_
 // The L kernel behind the outside sweep (k4_out_lrows) fits this automaton: its LDS, a row of the L plane within a workgroup, and
 // -- it maps L columns to states through the OUTSIDE programs -- every loop state's L column there unique and the one of its inside
 // program, which lin_loop_prepass_ok has looked at.
-static bool loop_outside_lds_ok(const AutomatonLayout& A) {
-  return A.tab_rs[ST_L] >= 1 && A.tab_rs[ST_L] <= kLoopColsMax && A.tab_rs[ST_L] <= kBT && loop_rows_lds(A) <= 64 * 1024;
+static bool loop_outside_lds_ok(const AutomatonLayout& A, int W) {
+  return loop_rows_fits(A.tab_rs[ST_L], W, A.n_wr, A.n_theta, A.n_quad, A.n_lane);
 }
 bool lin_loop_outside_ok(const AutomatonLayout& A, const int32_t* ints) {
   const bool say = getenv("ELEMDP_PLAN_DEBUG") != nullptr;
-  if (!A.fp_ok || !loop_outside_lds_ok(A)) {
-    if (say) fprintf(stderr, "L kernel behind the outside sweep: not for this automaton (fp_ok %d, L row of %d columns, LDS %zu)\n", A.fp_ok, A.tab_rs[ST_L], loop_rows_lds(A));
+  // (the automaton's share of the LDS alone: what the band width adds is known per group of a sweep -- group_geometry)
+  if (!A.fp_ok || !loop_outside_lds_ok(A, 0)) {
+    if (say) fprintf(stderr, "L kernel behind the outside sweep: not for this automaton (fp_ok %d, L row of %d columns, LDS %zu)\n", A.fp_ok, A.tab_rs[ST_L], loop_rows_lds(A, 0));
     return false;
   }
   auto col = [](int packed, int byte) { const int c = (packed >> (8 * byte)) & 0xff; return c == 0xff ? -1 : c; };
@@ -2862,7 +2866,7 @@ static GroupGeom group_geometry(const LinArgs& full, int G, int Lmax, int Wmax, 
   if (a.loop_post && a.p.blocks && (!a.p.blocks_in || !a.blk_grid_in)) a.loop_post = 0;
   // (lin_loop_prepass_ok looked at the inside programs and the pre-pass's LDS: the L kernels map the columns of the outside
   // programs and have LDS needs of their own -- where they do not fit, the sweep computes L itself)
-  if (a.loop_post && !loop_outside_lds_ok(a.lay)) a.loop_post = 0;
+  if (a.loop_post && !loop_outside_lds_ok(a.lay, Wmax)) a.loop_post = 0;
   const int sp = a.live_span > a.cpb ? a.live_span : a.cpb;   // cells a workgroup's window spans
   g.win = sp + Wmax + 3;
   g.lds_in = block_lds(2 * a.cpb * g.hd + kRecIn, a.cpb, a.n_lin, g.win, fast ? a.lay.fb_in_n : staged_ints(a.lay, a.n_stage, 0), 0, fast ? kCellInD : 0, sp).total;
@@ -2934,7 +2938,7 @@ static void outside_bands(GroupGeom& g, int G, int Lmax, int Wmax, hipStream_t s
   }
   if (post) {
     const int rows = loop_rows_r(a.lay.tab_rs[ST_L]);
-    hipLaunchKernelGGL(k4_out_lrows, dim3((Lmax + rows) / rows, G), dim3(kBT), loop_rows_lds(a.lay), st, a);
+    hipLaunchKernelGGL(k4_out_lrows, dim3((Lmax + rows) / rows, G), dim3(kBT), loop_rows_lds(a.lay, a.wmax), st, a);
   }
 }
 // the outside half of a sum pass of the scan: exterior chain outwards, outside band sweep
@@ -2992,7 +2996,7 @@ hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool
     fprintf(stderr, "lin group: G %d cpb %d fast %d n_lin %d staged ints in/out %d/%d lds k4_in %zu k4_out %zu fp_max_p %d forms k4_in %s k4_out %s stage_ext %d ext_nt %d ext_ring %d n_pass %d combine %d\n", G, a.cpb, (int)g.fast, a.n_lin, staged_ints(a.lay, a.n_stage, 0), staged_ints(a.lay, a.n_stage, 1), g.lds_in, g.lds_out, a.lay.fp_max_p,
             a.no_rss ? "none" : kK4FormName[k4_form(a, g.lds_in, 8, g.fast, g.big)], a.no_rss ? "none" : !stats ? "nostat" : kK4FormName[k4_form(a, g.lds_out, 6, g.fast, g.big)],
             (int)g.stage_ext, g.stage_ext ? g.ext_nt : 128, a.ext_ring, n_pass, (int)combine);
-    fprintf(stderr, "lin group: loop_prepass %d loop_outside %d (k4_out_lrows lds %zu, %d rows x %d diagonals)\n", a.loop_pre, a.loop_post, loop_rows_lds(a.lay), loop_rows_r(a.lay.tab_rs[ST_L]), kRowsT);
+    fprintf(stderr, "lin group: loop_prepass %d loop_outside %d (k4_out_lrows lds %zu, %d rows x %d diagonals)\n", a.loop_pre, a.loop_post, loop_rows_lds(a.lay, a.wmax), loop_rows_r(a.lay.tab_rs[ST_L]), kRowsT);
   }
   for (int pass = 0; pass < n_pass; ++pass) {
     GroupGeom gp = g;

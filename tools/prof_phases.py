@@ -16,7 +16,15 @@ ms = eng.last_timing()
 c = eng.profile()
 names = ["in setup", "in stage", "in products", "in items", "in unary", "out setup", "out stage", "out products", "out item records",
          "out item terms", "out (unused)", "out unary", "out flush"]
-tot = c[:13].sum()
+# k4_out_lrows (slot 7: everything in front of the tile loop, the set-up and the workgroup's plan data)
+lrows = {7: "lrows plan data", 2: "lrows cells", 13: "lrows staging", 14: "lrows gathers", 15: "lrows chain"}
+band = [k for k in range(13) if k not in lrows]
+tot = c[band].sum()
 print("n=%d L=%d pipeline %.1f ms -> %.0f seq/s ; fn=%.6f" % (n, L, ms[1], n / ms[1] * 1e3, fn))
-for k, nm in enumerate(names):
-    print("  %-16s %6.2f %%  (%.3g cycles)" % (nm, 100 * c[k] / tot, c[k]))
+for k in band:
+    print("  %-16s %6.2f %%  (%.3g cycles)" % (names[k], 100 * c[k] / tot, c[k]))
+tot = sum(c[k] for k in lrows)
+if tot > 0:
+    print("k4_out_lrows (thread 0 of every workgroup)")
+    for k, nm in lrows.items():
+        print("  %-16s %6.2f %%  (%.3g cycles)" % (nm, 100 * c[k] / tot, c[k]))
