@@ -32,7 +32,9 @@ ACCEPTED = [S for S, _, _ in TABLE]
 SHADOW_BELOW = 127       # Engine::flatten_automaton: the shadow copy of (0,0), and with it the merged train schedule, for S < 127
 LOG_SPACE = (64, 127, 128)          # the patterns of the pipeline 3 and the many-sequence train cases
 SCAN = (64, 65, 78, 126, 127, 128)  # the scan and pair cases (65: the other pattern above 64 states that runs table-driven)
+LOG_SCAN = (64, 78, 128)            # the scan and pair cases in the log-space form (78: the first blob not staged whole)
 WEIGHTED = (64, 126, 128)           # the patterns whose motif parses with weight: the posterior-product cases
+MIXED_FORM = (64, 128)              # the cases with both forms of the scan family in one call
 PARSE_SHARE = 0.75
 STEM = 8                 # the deepest stem of the table (S = 127, 128)
 
@@ -117,6 +119,12 @@ def long_batch(S=64):
     return mixed((257, 70), seed=2570 + S, planted_every=2)
 
 
+def mixed_form_batch(S):
+    """planted sequences of L 40 and 70 beside L 131 and 257 for the cases that run both forms of the scan family in one call:
+    under parameters sharp enough the long ones leave the double range of the scaled-linear tables, the short ones do not"""
+    return mixed((40, 257, 70, 131), seed=2600 + S)
+
+
 # ---- posterior products (the motif-conditioned checks need exist_prob >= E_MIN)
 
 PRODUCT_RANDOM = {64: ((70, 3064), (131, 3081)), 126: ((70, 3177), (131, 3143))}     # (L, seed of synth.synth_batch)
@@ -134,4 +142,4 @@ def product_batch(S):
 ALL_BATCHES = (
     [("train", S, train_batch) for S in ACCEPTED] + [("many", S, many_batch) for S in LOG_SPACE] +
     [("scan", S, scan_batch) for S in SCAN] + [("group2", 126, group2_batch), ("long", 64, long_batch)] +
-    [("product", S, product_batch) for S in WEIGHTED])
+    [("product", S, product_batch) for S in WEIGHTED] + [("mixed", S, mixed_form_batch) for S in MIXED_FORM])

@@ -103,19 +103,62 @@ def test_tiny_batch_equals_the_enumeration(opts, tiny_refs):
 RAGGED = (1, 2, 5, 13, 40, 97, 131, 200)
 
 
-@pytest.mark.parametrize("pattern,W,lens,width", [(P1, 50, RAGGED, 16), (P5, 50, RAGGED, 16), (P1, 20, (5, 19, 20, 21, 47), 16),
-                                                  (P1, 50, (257, 300), 16), (P1, 50, (40,), 1), (P1, 50, (40,), 64)],
-                         ids=["P1-W50", "P5-W50", "P1-W20", "P1-W50-long", "U1", "U64"])
+PIPELINE3 = (("pipeline", 3),)
+_REFS = {}
+
+
+def cached(key, compute):
+    """the references of a case, computed once for the scaled-linear and the log-space form (the oracle is the slow part)"""
+    if key not in _REFS:
+        _REFS[key] = compute()
+    return _REFS[key]
+
+
+def engine_with(pattern, W, opts=()):
+    eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    for k, v in opts:
+        eng.set_option(k, v)
+    return eng
+
+
+def shape_case(pattern, W, lens, width):
+    """(seqs, quals, x, table references) of a shape case"""
+    def compute():
+        seqs, quals = batch(lens, seed=1000 * W + len(pattern) + len(lens), n_every=3 if len(lens) > 1 else 0, neg_every=2)
+        x = perturbed(engine_with(pattern, W))
+        return seqs, quals, x, table_refs(maker(pattern, x, W), seqs, quals, x, width)
+    return cached(("shape", pattern, W, lens, width), compute)
+
+
+W20_LENS, W70_LENS, LONG_LENS = (5, 19, 20, 21, 47), (66, 70, 93), (257, 300)
+
+
+@pytest.mark.parametrize("pattern,W,lens,width", [(P1, 50, RAGGED, 16), (P5, 50, RAGGED, 16), (P1, 20, W20_LENS, 16),
+                                                  (P1, 50, LONG_LENS, 16), (P1, 50, (40,), 1), (P1, 50, (40,), 64),
+                                                  (P1, 70, W70_LENS, 16)],
+                         ids=["P1-W50", "P5-W50", "P1-W20", "P1-W50-long", "U1", "U64", "P1-W70"])
 def test_shapes_against_the_table_path_sums(pattern, W, lens, width):
     """(L = 257 and 300: more windows than one tile of k_access_seq, more positions than one row of workgroups of the chain
-    kernel's first 256 units; U = 64 at L = 40: every width a lane of the T_L scan, most windows off the end)"""
-    seqs, quals = batch(lens, seed=1000 * W + len(pattern) + len(lens), n_every=3 if len(lens) > 1 else 0, neg_every=2)
-    eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    kernel's first 256 units; U = 64 at L = 40: every width a lane of the T_L scan, most windows off the end; W = 70: spans
+    above 64)"""
+    seqs, quals, x, refs = shape_case(pattern, W, lens, width)
+    eng = engine_with(pattern, W)
     eng.load_batch(seqs, quals)
-    x = perturbed(eng)
-    refs = table_refs(maker(pattern, x, W), seqs, quals, x, width)
     assert all(r is not None for r in refs)
     check_access(eng, x, seqs, refs, width, what=(pattern, W, width))
+    assert eng.last_timing()[2] == 0
+
+
+@pytest.mark.parametrize("W,lens", [(20, W20_LENS), (70, W70_LENS), (50, LONG_LENS)], ids=["P1-W20", "P1-W70", "P1-W50-long"])
+def test_shapes_in_the_log_space_form(W, lens):
+    """pipeline 3: k_dp<DP_SCAN> and access_log_units (AccLog, the lanes' state vectors in acc.vec) fill the term planes
+    k_access_seq sums, addressed by launch position; the references of the scaled-linear cases at the 1e-10 of
+    test_sequences_out_of_the_double_range_take_the_log_space_form"""
+    seqs, quals, x, refs = shape_case(P1, W, lens, 16)
+    eng = engine_with(P1, W, PIPELINE3)
+    eng.load_batch(seqs, quals)
+    assert all(r is not None for r in refs)
+    check_access(eng, x, seqs, refs, 16, what=(W, "pipeline 3"), atol=1e-10, unp_atol=1e-10)
     assert eng.last_timing()[2] == 0
 
 
@@ -141,16 +184,35 @@ def test_a_model_without_energies_carries_both_multi_loop_terms():
     assert top["2"] >= 1e-3 and top["M"] >= 1e-3, top
 
 
-@pytest.mark.parametrize("model", ["syn_sm.model", "syn_a2007.model", "2.model"])
+MODELS = ["syn_sm.model", "syn_a2007.model", "2.model"]
+
+
+def model_case(model):
+    def compute():
+        m = io.read_model(gpath(model))
+        seqs, quals = batch((3, 13, 40, 97), seed=len(model))
+        return m, seqs, quals, table_refs(lambda: ac.access_oracle_from_model(gpath(model))[0], seqs, quals, m["x"], 16)
+    return cached(("model", model), compute)
+
+
+@pytest.mark.parametrize("model", MODELS)
 def test_models_against_the_table_path_sums(model):
     """softmax theta, the ~A2007~ energy parameters, and a model without secondary structure (2.model: 1 in every valid window)"""
-    m = io.read_model(gpath(model))
-    seqs, quals = batch((3, 13, 40, 97), seed=len(model))
+    m, seqs, quals, refs = model_case(model)
     eng = io.engine_from_model(m)
     eng.load_batch(seqs, quals)
-    x = m["x"]
-    refs = table_refs(lambda: ac.access_oracle_from_model(gpath(model))[0], seqs, quals, x, 16)
-    check_access(eng, x, seqs, refs, 16, what=model, no_rss=m["no_rss"])
+    check_access(eng, m["x"], seqs, refs, 16, what=model, no_rss=m["no_rss"])
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_in_the_log_space_form(model):
+    """pipeline 3 (2.model: the no_rss branches of k_dp, access_log_units skipped)"""
+    m, seqs, quals, refs = model_case(model)
+    eng = io.engine_from_model(m)
+    eng.set_option("pipeline", 3)
+    eng.load_batch(seqs, quals)
+    check_access(eng, m["x"], seqs, refs, 16, what=(model, "pipeline 3"), atol=1e-10, unp_atol=1e-10, no_rss=m["no_rss"])
+    assert eng.last_timing()[2] == 0
 
 
 def test_sequences_out_of_the_double_range_take_the_log_space_form():
@@ -221,6 +283,24 @@ def test_groupings_agree_and_nothing_else_changes():
 
 
 # ---- command line, refusals
+
+def test_a_workgroup_of_the_log_space_form_takes_several_sequences():
+    """pipeline 3 with option slots 3: log_scan_args asks for min(slots, n_seq) table slots and launches as many workgroups, so
+    n_blocks = 3 workgroups take the n_seq = 9 unsorted sequences of L 20 .. 280 of the grouping test off the atomic counter;
+    acc.vec is indexed by blockIdx.x, the term planes by launch position.  Against the table references, not against another
+    grouping."""
+    lens = [int(v) for v in np.linspace(20, 280, 9)][::-1]
+    lens[2], lens[6] = lens[6], lens[2]
+    seqs, quals = batch(lens, seed=5)
+    eng = engine_with(P1, 50, PIPELINE3 + (("slots", 3),))
+    eng.load_batch(seqs, quals)
+    x = perturbed(eng)
+    refs = table_refs(maker(P1, x), seqs, quals, x, 16)
+    assert sum(r is not None for r in refs) >= 8
+    check_access(eng, x, seqs, refs, 16, what="slots 3", atol=1e-10, unp_atol=1e-10)
+    assert (eng.slot_status()["slots"], eng.n_seq) == (3, 9)
+    assert eng.last_timing()[2] == 0
+
 
 def test_command_line_writes_the_access_file(tmp_path):
     fq, model = gpath("positive_head6.fq"), gpath("trna_a.model")

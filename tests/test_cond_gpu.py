@@ -80,15 +80,44 @@ def test_tiny_batch_equals_the_enumeration(opts):
 
 # ---- 2. shapes against the oracle's tables and the engine's own pair call
 
-@pytest.mark.parametrize("pattern,W,lens", [(P1, 50, SHAPE_LENS), (P2, 50, SHAPE_LENS), (P1, 20, (5, 19, 20, 21, 47)),
-                                            (P1, 50, (257, 300))], ids=["P1-W50", "P2-W50", "P1-W20", "P1-W50-long"])
-def test_shapes_against_the_tables_and_the_mixture(pattern, W, lens):
-    """(L = 257 and 300: k_cond_seq walks the rows in tiles of 256 and carries the shift and the list position into the second)"""
-    seqs, quals = shape_batch(lens, seed=1000 * W + len(pattern) + len(lens), with_edge=(lens is SHAPE_LENS))
+PIPELINE3 = (("pipeline", 3),)
+_REFS = {}
+
+
+def cached(key, compute):
+    """the references of a case, computed once for the scaled-linear and the log-space form (the oracle is the slow part)"""
+    if key not in _REFS:
+        _REFS[key] = compute()
+    return _REFS[key]
+
+
+def engine_with(pattern, W, opts=()):
     eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    for k, v in opts:
+        eng.set_option(k, v)
+    return eng
+
+
+def shape_case(pattern, W, lens):
+    """(seqs, quals, x, the tables of both worlds) of a shape case"""
+    def compute():
+        seqs, quals = shape_batch(lens, seed=1000 * W + len(pattern) + len(lens), with_edge=(lens is SHAPE_LENS))
+        x = perturbed(engine_with(pattern, W))
+        return seqs, quals, x, table_refs(pattern_oracles(pattern, x, W), seqs, quals)
+    return cached(("shape", pattern, W, lens), compute)
+
+
+W20_LENS, W70_LENS, LONG_LENS = (5, 19, 20, 21, 47), (66, 70, 93), (257, 300)
+
+
+@pytest.mark.parametrize("pattern,W,lens", [(P1, 50, SHAPE_LENS), (P2, 50, SHAPE_LENS), (P1, 20, W20_LENS), (P1, 50, LONG_LENS),
+                                            (P1, 70, W70_LENS)], ids=["P1-W50", "P2-W50", "P1-W20", "P1-W50-long", "P1-W70"])
+def test_shapes_against_the_tables_and_the_mixture(pattern, W, lens):
+    """(L = 257 and 300: k_cond_seq walks the rows in tiles of 256 and carries the shift and the list position into the second;
+    W = 70: spans above 64)"""
+    seqs, quals, x, refs = shape_case(pattern, W, lens)
+    eng = engine_with(pattern, W)
     eng.load_batch(seqs, quals)
-    x = perturbed(eng)
-    refs = table_refs(pattern_oracles(pattern, x, W), seqs, quals)
     assert_comparable(refs, (pattern, W))
     if pattern == P1 and lens is SHAPE_LENS:
         # (here the world without the motif is a sliver of the mixture, and its P is still checked at full tolerance)
@@ -101,24 +130,59 @@ def test_shapes_against_the_tables_and_the_mixture(pattern, W, lens):
             assert len(recs[k]["i"]) == 0 and np.all(recs[k]["unpaired_none"] == 1.0), k
 
 
+@pytest.mark.parametrize("W,lens", [(20, W20_LENS), (70, W70_LENS), (50, LONG_LENS)], ids=["P1-W20", "P1-W70", "P1-W50-long"])
+def test_shapes_in_the_log_space_form(W, lens):
+    """pipeline 3: k_dp<DP_SCAN> runs the two worlds in its loop over cond_p0 / cond_p1 and k_cond_seq reads their planes by
+    launch position; the references and the checks of the scaled-linear cases"""
+    seqs, quals, x, refs = shape_case(P1, W, lens)
+    eng = engine_with(P1, W, PIPELINE3)
+    eng.load_batch(seqs, quals)
+    assert_comparable(refs, (P1, W))
+    check_batch(eng, x, seqs, refs, what=(W, "pipeline 3"))
+    assert eng.last_timing()[2] == 0
+
+
 # ---- 3. models
 
-@pytest.mark.parametrize("model", ["syn_sm.model", "syn_a2007.model", "2.model"])
-def test_models_against_the_tables(model):
-    """softmax theta, the ~A2007~ energy parameters, and a model without secondary structure (2.model: empty lists, unpaired 1,
-    shift 0)"""
-    m = io.read_model(gpath(model))
-    seqs, quals = batch((3, 13, 40, 97, 131), seed=len(model))
+MODELS = ["syn_sm.model", "syn_a2007.model", "2.model"]
+
+
+def model_case(model):
+    def compute():
+        m = io.read_model(gpath(model))
+        seqs, quals = batch((3, 13, 40, 97, 131), seed=len(model))
+        return m, seqs, quals, table_refs(lambda: cd.model_oracles(gpath(model)), seqs, quals)
+    return cached(("model", model), compute)
+
+
+def check_model(model, opts):
+    m, seqs, quals, refs = model_case(model)
     eng = io.engine_from_model(m)
+    for k, v in opts:
+        eng.set_option(k, v)
     eng.load_batch(seqs, quals)
-    refs = table_refs(lambda: cd.model_oracles(gpath(model)), seqs, quals)
-    recs = check_batch(eng, m["x"], seqs, refs, what=model)
+    recs = check_batch(eng, m["x"], seqs, refs, what=(model, opts))
     if m["no_rss"]:
         for rec, s, ref in zip(recs, seqs, refs):
             assert len(rec["i"]) == 0 and np.all(rec["unpaired_motif"] == 1.0) and np.all(rec["unpaired_none"] == 1.0)
             assert rec["structure_motif"] == rec["structure_none"] == "." * len(s)
             if np.isfinite(ref["Zari"]) and np.isfinite(ref["Znasi"]):
                 assert rec["shift"] == 0.0
+    return eng
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_against_the_tables(model):
+    """softmax theta, the ~A2007~ energy parameters, and a model without secondary structure (2.model: empty lists, unpaired 1,
+    shift 0)"""
+    check_model(model, ())
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_in_the_log_space_form(model):
+    """pipeline 3 (2.model: the no_rss branches of k_dp, both worlds without pairs)"""
+    eng = check_model(model, PIPELINE3)
+    assert eng.last_timing()[2] == 0
 
 
 # ---- 4. the log-space form
@@ -202,6 +266,23 @@ def test_groupings_and_poisoned_slots_give_the_same_records(opts, grouped):
     for r in got:
         assert all(np.all(np.isfinite(r[key])) for key in ("p_motif", "p_none", "unpaired_motif", "unpaired_none"))
     cd.same_records(got, want, rtol=1e-10, atol=1e-14)
+
+
+def test_a_workgroup_of_the_log_space_form_takes_several_sequences():
+    """pipeline 3 with option slots 3: log_scan_args asks for min(slots, n_seq) table slots and launches as many workgroups, so
+    n_blocks = 3 workgroups take the n_seq = 11 unsorted sequences of L 20 .. 280 of the grouping tests off the atomic counter.
+    Against the oracle's tables of both worlds, not against another grouping."""
+    lens = [int(v) for v in np.linspace(20, 280, 11)][::-1]
+    lens[2], lens[7] = lens[7], lens[2]
+    seqs, quals = batch(lens, seed=5)
+    eng = engine_with(P1, 50, PIPELINE3 + (("slots", 3),))
+    eng.load_batch(seqs, quals)
+    x = perturbed(eng)
+    refs = table_refs(pattern_oracles(P1, x), seqs, quals)
+    assert_comparable(refs, "slots 3")
+    check_batch(eng, x, seqs, refs, what="slots 3")
+    assert (eng.slot_status()["slots"], eng.n_seq) == (3, 11)
+    assert eng.last_timing()[2] == 0
 
 
 # ---- 8. the other calls of the handle

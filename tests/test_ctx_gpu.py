@@ -124,21 +124,44 @@ def shape_batch(lens, seed, with_edge):
     return seqs, quals
 
 
-@pytest.mark.parametrize("pattern,W,lens", [(P1, 50, SHAPE_LENS), (P2, 50, SHAPE_LENS), (P1, 20, (5, 19, 20, 21, 47)),
-                                            (P1, 50, (257, 300))], ids=["P1-W50", "P2-W50", "P1-W20", "P1-W50-long"])
-def test_shapes_against_the_table_definitions(pattern, W, lens):
-    """(L = 257 and 300: k_ctx_seq forms its prefix sums per tile of 256 positions and carries them into the second tile)"""
-    seqs, quals = shape_batch(lens, seed=1000 * W + len(pattern) + len(lens), with_edge=(lens is SHAPE_LENS))
+PIPELINE3 = (("pipeline", 3),)
+_REFS = {}
+
+
+def cached(key, compute):
+    """the references of a case, computed once for the scaled-linear and the log-space form (the oracle is the slow part)"""
+    if key not in _REFS:
+        _REFS[key] = compute()
+    return _REFS[key]
+
+
+def engine_with(pattern, W, opts=()):
     eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    for k, v in opts:
+        eng.set_option(k, v)
+    return eng
+
+
+def shape_case(pattern, W, lens):
+    """(seqs, quals, x, table references) of a shape case"""
+    def compute():
+        seqs, quals = shape_batch(lens, seed=1000 * W + len(pattern) + len(lens), with_edge=(lens is SHAPE_LENS))
+        x = perturbed(engine_with(pattern, W))
+        return seqs, quals, x, table_refs(oracle_maker_ctx(pattern, x, W), seqs, quals, x)
+    return cached(("shape", pattern, W, lens), compute)
+
+
+W20_LENS, W70_LENS, LONG_LENS = (5, 19, 20, 21, 47), (66, 70, 93), (257, 300)
+
+
+@pytest.mark.parametrize("pattern,W,lens", [(P1, 50, SHAPE_LENS), (P2, 50, SHAPE_LENS), (P1, 20, W20_LENS), (P1, 50, LONG_LENS),
+                                            (P1, 70, W70_LENS)], ids=["P1-W50", "P2-W50", "P1-W20", "P1-W50-long", "P1-W70"])
+def test_shapes_against_the_table_definitions(pattern, W, lens):
+    """(L = 257 and 300: k_ctx_seq forms its prefix sums per tile of 256 positions and carries them into the second tile; W = 70:
+    spans above 64)"""
+    seqs, quals, x, refs = shape_case(pattern, W, lens)
+    eng = engine_with(pattern, W)
     eng.load_batch(seqs, quals)
-    x = perturbed(eng)
-
-    def make():
-        o = cc.ctx_oracle(pattern, W, 30)
-        o.set_params(x)
-        return o
-
-    refs = table_refs(make, seqs, quals, x)
     prof = check_profiles(eng, x, seqs, refs, what=(pattern, W))
     assert sum(r is not None for r in refs) >= len(lens)
     if lens is SHAPE_LENS:
@@ -148,18 +171,53 @@ def test_shapes_against_the_table_definitions(pattern, W, lens):
         assert max(p[:, 4].max() for p in prof) > 1e-2 and max(p[:, 5].max() for p in prof) > 1e-2
 
 
-@pytest.mark.parametrize("model", ["syn_sm.model", "syn_a2007.model", "2.model"])
+@pytest.mark.parametrize("W,lens", [(20, W20_LENS), (70, W70_LENS), (50, LONG_LENS)], ids=["P1-W20", "P1-W70", "P1-W50-long"])
+def test_shapes_in_the_log_space_form(W, lens):
+    """pipeline 3: k_dp<DP_SCAN> and CtxLog fill the planes of k_ctx_seq, addressed by launch position; the references of the
+    scaled-linear cases, rows within 1e-10 (test_sequences_out_of_the_double_range_take_the_log_space_form)"""
+    seqs, quals, x, refs = shape_case(P1, W, lens)
+    eng = engine_with(P1, W, PIPELINE3)
+    eng.load_batch(seqs, quals)
+    check_profiles(eng, x, seqs, refs, what=(W, "pipeline 3"), row_atol=1e-10)
+    assert sum(r is not None for r in refs) >= len(lens)
+    assert eng.last_timing()[2] == 0
+
+
+MODELS = ["syn_sm.model", "syn_a2007.model", "2.model"]
+
+
+def model_case(model):
+    def compute():
+        m = io.read_model(gpath(model))
+        seqs, quals = batch((3, 13, 40, 97, 131), seed=len(model))
+        return m, seqs, quals, table_refs(lambda: cc.ctx_oracle_from_model(gpath(model))[0], seqs, quals, m["x"])
+    return cached(("model", model), compute)
+
+
+@pytest.mark.parametrize("model", MODELS)
 def test_models_against_the_table_definitions(model):
     """softmax theta, the ~A2007~ energy parameters, and a model without secondary structure (2.model: O = 1 everywhere)"""
-    m = io.read_model(gpath(model))
-    seqs, quals = batch((3, 13, 40, 97, 131), seed=len(model))
+    m, seqs, quals, refs = model_case(model)
     eng = io.engine_from_model(m)
     eng.load_batch(seqs, quals)
     x = m["x"]
-    refs = table_refs(lambda: cc.ctx_oracle_from_model(gpath(model))[0], seqs, quals, x)
     prof = check_profiles(eng, x, seqs, refs, what=model, no_rss=m["no_rss"])
     if m["no_rss"]:
         assert all(np.array_equal(g, cc.exterior_only(len(s))) for g, s in zip(prof, seqs))
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_in_the_log_space_form(model):
+    """pipeline 3 (2.model: the no_rss branches of k_dp, ctx.o = 1)"""
+    m, seqs, quals, refs = model_case(model)
+    eng = io.engine_from_model(m)
+    eng.set_option("pipeline", 3)
+    eng.load_batch(seqs, quals)
+    x = m["x"]
+    prof = check_profiles(eng, x, seqs, refs, what=(model, "pipeline 3"), no_rss=m["no_rss"], row_atol=1e-10)
+    if m["no_rss"]:
+        assert all(np.array_equal(g, cc.exterior_only(len(s))) for g, s in zip(prof, seqs))
+    assert eng.last_timing()[2] == 0
 
 
 def test_sequences_out_of_the_double_range_take_the_log_space_form():
@@ -227,6 +285,26 @@ def test_groupings_agree_and_nothing_else_changes():
         got = eng.context_profiles(x)
         for k, (g, w) in enumerate(zip(got, want)):
             np.testing.assert_allclose(g, w, rtol=1e-10, atol=1e-14, err_msg=str((opts, k)))
+
+
+GROUPED_LENS = [int(v) for v in np.linspace(20, 280, 11)][::-1]
+GROUPED_LENS[2], GROUPED_LENS[7] = GROUPED_LENS[7], GROUPED_LENS[2]      # (the lengths of the grouping test)
+
+
+def test_a_workgroup_of_the_log_space_form_takes_several_sequences():
+    """pipeline 3 with option slots 3: log_scan_args asks for min(slots, n_seq) table slots and launches as many workgroups, so
+    n_blocks = 3 workgroups take the n_seq = 11 unsorted sequences of L 20 .. 280 off the atomic counter; the per-workgroup
+    scratch is indexed by blockIdx.x, the planes of k_ctx_seq by launch position.  Against the table references, not against
+    another grouping."""
+    seqs, quals = batch(GROUPED_LENS, seed=5)
+    eng = engine_with(P1, 50, PIPELINE3 + (("slots", 3),))
+    eng.load_batch(seqs, quals)
+    x = perturbed(eng)
+    refs = table_refs(oracle_maker_ctx(P1, x), seqs, quals, x)
+    check_profiles(eng, x, seqs, refs, what="slots 3", row_atol=1e-10)
+    assert sum(r is not None for r in refs) >= 10
+    assert (eng.slot_status()["slots"], eng.n_seq) == (3, 11)
+    assert eng.last_timing()[2] == 0
 
 
 # ---- 8. the split beyond enumeration

@@ -72,30 +72,88 @@ def test_enumerated_cases(opts):
 
 # ---- shapes against the definitions over the oracle's tables
 
-@pytest.mark.parametrize("pattern,W,lens", [(P1, 20, tuple(range(1, 61))), (P2, 20, tuple(range(1, 61))), (P1, 70, (107,))],
+PIPELINE3 = (("pipeline", 3),)
+_REFS = {}
+
+
+def cached(key, compute):
+    """the references of a case, computed once for the scaled-linear and the log-space form (the oracle is the slow part)"""
+    if key not in _REFS:
+        _REFS[key] = compute()
+    return _REFS[key]
+
+
+def engine_with(pattern, W, opts=()):
+    eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    for k, v in opts:
+        eng.set_option(k, v)
+    return eng
+
+
+def shape_case(pattern, W, lens):
+    """(seqs, quals, x, table references) of a shape case"""
+    def compute():
+        seqs, quals = batch(lens, seed=1000 * W + len(pattern) + len(lens))
+        x = jc.joint_params(engine_with(pattern, W))
+        return seqs, quals, x, table_refs(oracle_with(pattern, x, W), seqs, quals, x)
+    return cached(("shape", pattern, W, lens), compute)
+
+
+def long_case():
+    """L = 257 and 300 at W = 20, the references from the CPU driver of the product rule"""
+    def compute():
+        seqs, quals = batch((257, 300), seed=77, n_every=0)
+        eng = engine_with(P1, 20)
+        x = jc.joint_params(eng)
+        drv = jc.JointDriver(P1, PAR, 20, 30, 1e-4, 0.1, 0, n_node=eng.n_node)
+        return seqs, quals, x, [drv.joint(x, s, q, 0)[0] for s, q in zip(seqs, quals)]
+    return cached("long", compute)
+
+
+W20_LENS, W70_LENS = tuple(range(1, 61)), (107,)
+
+
+@pytest.mark.parametrize("pattern,W,lens", [(P1, 20, W20_LENS), (P2, 20, W20_LENS), (P1, 70, W70_LENS)],
                          ids=["P1-W20", "P2-W20", "P1-W70"])
 def test_shapes_against_the_table_definitions(pattern, W, lens):
     """(L = 1 .. 60: the last workgroup of a sequence, four rows or positions each, is partly empty, rows shorter and longer than
     W; W = 70: a position with cells of span above 64 sums a second round per lane before the wave reduction)"""
-    seqs, quals = batch(lens, seed=1000 * W + len(pattern) + len(lens))
-    eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    seqs, quals, x, refs = shape_case(pattern, W, lens)
+    eng = engine_with(pattern, W)
     eng.load_batch(seqs, quals)
-    x = jc.joint_params(eng)
-    refs = table_refs(oracle_with(pattern, x, W), seqs, quals, x)
     _, prof = check_joint(eng, x, seqs, refs, what=(pattern, W))
     assert sum(r is not None for r in refs) >= len(lens) - 1
     assert max(p[:, 1:-1, 3].sum(axis=1).max() for p in prof) > 0.05
 
 
+@pytest.mark.parametrize("W,lens", [(20, W20_LENS), (70, W70_LENS)], ids=["P1-W20", "P1-W70"])
+def test_shapes_in_the_log_space_form(W, lens):
+    """pipeline 3: k_dp<DP_SCAN> and JointLog on the per-thread vectors of jnt.vec, the X scratch of the workgroup, the counts
+    stage by launch position; the references of the scaled-linear cases, sums within 1e-10 (Rounding)"""
+    seqs, quals, x, refs = shape_case(P1, W, lens)
+    eng = engine_with(P1, W, PIPELINE3)
+    eng.load_batch(seqs, quals)
+    _, prof = check_joint(eng, x, seqs, refs, what=(W, "pipeline 3"), row_atol=1e-10)
+    assert sum(r is not None for r in refs) >= len(lens) - 1
+    assert max(p[:, 1:-1, 3].sum(axis=1).max() for p in prof) > 0.05
+    assert eng.last_timing()[2] == 0
+
+
 def test_long_sequences_against_the_cpu_driver():
     """L = 257 and 300 at W = 20 cross the tiles of 256 of the per-sequence stages"""
-    seqs, quals = batch((257, 300), seed=77, n_every=0)
-    eng = api.Engine(P1, PAR, 20, 30, 1e-4, 0.1, 0, 0)
+    seqs, quals, x, refs = long_case()
+    eng = engine_with(P1, 20)
     eng.load_batch(seqs, quals)
-    x = jc.joint_params(eng)
-    drv = jc.JointDriver(P1, PAR, 20, 30, 1e-4, 0.1, 0, n_node=eng.n_node)
-    refs = [drv.joint(x, s, q, 0)[0] for s, q in zip(seqs, quals)]
     check_joint(eng, x, seqs, refs, what="long")
+
+
+def test_long_sequences_in_the_log_space_form():
+    """the same under pipeline 3"""
+    seqs, quals, x, refs = long_case()
+    eng = engine_with(P1, 20, PIPELINE3)
+    eng.load_batch(seqs, quals)
+    check_joint(eng, x, seqs, refs, what="long, pipeline 3", row_atol=1e-10)
+    assert eng.last_timing()[2] == 0
 
 
 # ---- the two marginal identities against the handle's own calls
@@ -118,16 +176,36 @@ def test_marginals_are_the_node_and_the_context_profiles_of_the_same_handle(opts
     assert max(g[:, 1:-1, 6].max() for g in prof) > 1e-4 and max(g[:, 1:-1, 3].max() for g in prof) > 0.05
 
 
-@pytest.mark.parametrize("model", ["syn_sm.model", "syn_a2007.model", "2.model"])
+MODELS = ["syn_sm.model", "syn_a2007.model", "2.model"]
+
+
+def model_case(model):
+    def compute():
+        m = io.read_model(gpath(model))
+        seqs, quals = batch((3, 13, 40, 97), seed=len(model))
+        refs = table_refs(lambda: jc.joint_oracle_from_model(gpath(model))[0], seqs, quals, m["x"], tau=m["tau"])
+        return m, seqs, quals, refs
+    return cached(("model", model), compute)
+
+
+@pytest.mark.parametrize("model", MODELS)
 def test_models_against_the_table_definitions(model):
     """softmax theta, the ~A2007~ energy parameters, and a model without secondary structure (2.model: rule 8 alone)"""
-    m = io.read_model(gpath(model))
-    seqs, quals = batch((3, 13, 40, 97), seed=len(model))
+    m, seqs, quals, refs = model_case(model)
     eng = io.engine_from_model(m)
     eng.load_batch(seqs, quals)
-    x = m["x"]
-    refs = table_refs(lambda: jc.joint_oracle_from_model(gpath(model))[0], seqs, quals, x, tau=m["tau"])
-    check_joint(eng, x, seqs, refs, what=model)
+    check_joint(eng, m["x"], seqs, refs, what=model)
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_in_the_log_space_form(model):
+    """pipeline 3 (2.model: the no_rss branches of k_dp)"""
+    m, seqs, quals, refs = model_case(model)
+    eng = io.engine_from_model(m)
+    eng.set_option("pipeline", 3)
+    eng.load_batch(seqs, quals)
+    check_joint(eng, m["x"], seqs, refs, what=(model, "pipeline 3"), row_atol=1e-10)
+    assert eng.last_timing()[2] == 0
 
 
 def test_sequences_out_of_the_double_range_take_the_log_space_form():
@@ -199,6 +277,24 @@ def test_groupings_agree_counts_equal_the_scan_and_nothing_else_changes():
         for k, (g, w) in enumerate(zip(got, want)):
             assert g.shape == w.shape
             np.testing.assert_allclose(g, w, rtol=1e-10, atol=1e-14, err_msg=str((opts, k)))
+
+
+def test_a_workgroup_of_the_log_space_form_takes_several_sequences():
+    """pipeline 3 with option slots 3: log_scan_args asks for min(slots, n_seq) table slots and launches as many workgroups, so
+    n_blocks = 3 workgroups take the n_seq = 9 unsorted sequences of L 20 .. 160 of the grouping test off the atomic counter;
+    jnt.X and jnt.vec are indexed by blockIdx.x, the planes of the counts stage by launch position.  Against the table
+    references, not against another grouping."""
+    lens = [int(v) for v in np.linspace(20, 160, 9)][::-1]
+    lens[2], lens[6] = lens[6], lens[2]
+    seqs, quals = batch(lens, seed=5)
+    eng = engine_with(P1, 50, PIPELINE3 + (("slots", 3),))
+    eng.load_batch(seqs, quals)
+    x = jc.joint_params(eng)
+    refs = table_refs(oracle_with(P1, x), seqs, quals, x)
+    check_joint(eng, x, seqs, refs, what="slots 3", row_atol=1e-10)
+    assert sum(r is not None for r in refs) >= 8
+    assert (eng.slot_status()["slots"], eng.n_seq) == (3, 9)
+    assert eng.last_timing()[2] == 0
 
 
 # ---- command line

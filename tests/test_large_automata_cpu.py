@@ -2,7 +2,8 @@
 that a failure of tests/test_large_automata_gpu.py points at a kernel: the state and node counts of the table, the automaton the
 engine flattens (which patterns get the shadow copy of (0,0)), the automaton description against the oracle's, the rule headers
 through the CPU emulation against the oracle (log-space, scaled-linear under the reference schedule and the merged one, pruned
-and unpruned lists), the refusals, and -- from the oracle alone -- that the batches of the GPU file let the motif parse.
+and unpruned lists), the log-space rule headers of the posterior products through their CPU drivers against the table references,
+the refusals, and -- from the oracle alone -- that the batches of the GPU file let the motif parse.
 
 What the table-driven band programs fit (Emul.set_fast, bit 1; bit 4 for the automaton with the shadow state): with the pruned
 lists, the engine's default, every accepted pattern of the table except S = 127; the launcher also wants the whole automaton
@@ -195,3 +196,65 @@ def test_the_motif_parses_in_the_batches_of_the_gpu_file(name, S, make):
     assert np.mean(e > 0.0) >= la.PARSE_SHARE, e
     if name == "product":
         assert np.sum(e >= cd.E_MIN) >= 2, e
+
+
+# ---- the log-space rule headers of the posterior products above 64 states
+
+PRODUCTS = ("context", "node", "joint", "stem", "access", "cond")
+ACCESS_WIDTH = 16
+
+
+@pytest.mark.parametrize("product", PRODUCTS)
+@pytest.mark.parametrize("S", la.WEIGHTED)
+def test_log_space_product_rules_match_the_tables(S, product):
+    """The LOG form of every product's CPU driver -- the rule headers the fused scan kernel runs behind its sweeps, over dense
+    tables -- on la.product_batch(S) against the table reference and with the assert_* function the GPU file uses for that
+    product: a failure here is a rule that is wrong above 64 states, a failure of the GPU file alone is the kernel's mapping of
+    states to lanes, chunks and scratch."""
+    from tests import access_check as ac, ctx_check as cc, joint_check as jc, node_check as nc, stem_check as sc
+    pattern = la.PATTERN[S]
+    seqs, quals = la.product_batch(S)
+    eng = engine(S)
+    x = perturbed(eng)
+    M = eng.n_node
+    args = (pattern, "~T2004~", 50, 30, 1e-4, 0.1, 0)
+    if product == "cond":
+        o, on = cd.world_oracles(lambda: cc.ctx_oracle(pattern, 50, 30), x)
+        drv = cd.CondDriver(*args)
+    else:
+        o = {"context": cc.ctx_oracle, "node": nc.node_oracle, "joint": jc.joint_oracle, "stem": sc.stem_oracle,
+             "access": ac.access_oracle}[product](pattern, 50, 30)
+        o.set_params(x)
+    for k, (s, q) in enumerate(zip(seqs, quals)):
+        L, what = len(s), (S, product, k)
+        if product == "context":
+            ref = cc.table_profile(o, s, q, x, bulge=L <= 97)
+            got, used = cc.CtxDriver(*args).profile(x, s, q, cc.CtxDriver.LOG)
+            full = not np.isnan(ref[:, 4]).any()
+            cc.assert_profile(got, ref, what=what, cols=range(7) if full else (0, 1, 2, 3, 6))
+            np.testing.assert_allclose(got.sum(axis=1), 1.0, rtol=0, atol=1e-10)
+        elif product == "node":
+            ref = nc.table_profile(o, s, q, x)
+            got, used = nc.NodeDriver(*args, n_node=M).profile(x, s, q, nc.NodeDriver.LOG)
+            nc.assert_profile(got, ref, what=what, cols=range(M))
+            np.testing.assert_allclose(got.sum(axis=1), 1.0, rtol=0, atol=1e-10)
+        elif product == "joint":
+            ref = jc.table_joint(o, s, q, x)
+            got, counts, used = jc.JointDriver(*args, n_node=M).joint(x, s, q, jc.JointDriver.LOG)
+            jc.assert_joint(got, ref, what=what)
+            np.testing.assert_allclose(got.sum(axis=(1, 2)), 1.0, rtol=0, atol=1e-10)
+        elif product == "stem":
+            drv = sc.StemDriver(*args)
+            assert np.array_equal(drv.slots, eng.stem_slots())
+            ref = sc.table_stems(o, s, q, x)
+            got, counts, used = drv.stems(x, s, q, sc.StemDriver.LOG)
+            sc.assert_stem(got, sc.by_slot(ref, drv.slots), what=what)
+        elif product == "access":
+            ref, _ = ac.table_access(o, s, q, x, ACCESS_WIDTH)
+            got, _, used = ac.AccessDriver(*args).access(x, s, q, ACCESS_WIDTH, ac.AccessDriver.LOG)
+            ac.assert_access(got, ref, what=what)
+        else:
+            ref = cd.table_worlds(o, on, s, q)
+            rec, used = drv.record(x, s, q, ref["kept"], cd.CondDriver.LOG)
+            cd.check_record(rec, ref, L, min(L, 50), what=what)
+        assert ref is not None and used == 1, what

@@ -24,7 +24,14 @@ Band kernels (the forms launch_lin_group names under ELEMDP_LDS_DEBUG): the tabl
 states in one cell of a workgroup's 256 lanes at cpb = 2; option fast 0 at S = 64 gives the general kernels with the staged blob
 (form staged); test_train asserts which.
 
-Log-space pipeline (pipeline 3): wave_gather.h's second state chunk (lane c * 64 + lane, c = 1) from 65 active states."""
+Log-space pipeline (pipeline 3): wave_gather.h's second state chunk (lane c * 64 + lane, c = 1) from 65 active states.  The
+option names two different pipelines.  Under train_eval it is the batch pipeline of train_kernels.hip (the "pipeline3" cases of
+test_train).  Under a scan-family call it is the log-space form of that call: the fused per-sequence kernel k_dp<DP_SCAN> of
+kernels.hip, one workgroup per sequence on dense tables, which also takes the sequences the range check of the scaled-linear
+form hands over.  Its sweeps merge tuples in both state chunks, and its per-workgroup scratch is sized by the state count
+(tmp: 3 (Lmax + 1) S doubles; jnt.vec: 5 S per thread; acc.vec: 2 S per lane of the first wave).  The tests named
+*_in_the_log_space_form run it on the batches and against the references of the scaled-linear cases, and
+test_both_forms_in_one_call lets the range check split one batch between the two forms."""
 import numpy as np
 import pytest
 
@@ -180,19 +187,49 @@ def test_train_on_seventy_short_sequences(S, forms):
 GAMMAS = (0.5, 1.0, 4.0)
 
 
-def pair_run(S, seqs, quals, opts=()):
+PIPELINE3 = (("pipeline", 3),)
+_REFS = {}
+
+
+def cached(key, compute):
+    """the oracle's references of a batch at params(S), computed once for every option set that runs it (as _TRAIN_REFS)"""
+    if key not in _REFS:
+        _REFS[key] = compute()
+    return _REFS[key]
+
+
+def pair_run(S, seqs, quals, opts=(), refs=None):
     eng, x = loaded(S, seqs, quals, opts)
-    refs, res, mea = check_pair_path(eng, seqs, quals, x, oracle_maker(la.PATTERN[S], W, C, x), gammas=GAMMAS, scan=True)
+    refs, res, mea = check_pair_path(eng, seqs, quals, x, oracle_maker(la.PATTERN[S], W, C, x), gammas=GAMMAS, scan=True, refs=refs)
     e = [r["scan"]["exist_prob"] for r in refs]
+    if ("pipeline", 3) in opts:          # (no sum pass on the batch, so no sequence handed on by the range check)
+        assert eng.last_timing()[2] == 0
     return refs, res, mea, e
+
+
+def scan_refs(S):
+    seqs, quals = la.scan_batch(S)
+    return seqs, quals, cached((S, "scan"), lambda: oracle_refs(oracle_maker(la.PATTERN[S], W, C, params(S)), seqs, quals))
 
 
 @pytest.mark.parametrize("S", la.SCAN)
 def test_scan_and_pairs(S):
     """pair list, P and unpaired against the oracle, MEA against the mirror and the optimum, scan records (start, end, inner,
     exist_prob, Ys, Ye, rss, psihat, E[N]) against the oracle's; one sequence of the four is marked as without the motif"""
-    seqs, quals = la.scan_batch(S)
-    refs, res, mea, e = pair_run(S, seqs, quals)
+    seqs, quals, refs = scan_refs(S)
+    refs, res, mea, e = pair_run(S, seqs, quals, refs=refs)
+    assert sum(v > 0.0 for v in e) >= la.PARSE_SHARE * len(seqs), e
+    assert sum(len(r[2]) for r in res) > 0
+
+
+@pytest.mark.parametrize("S", la.LOG_SCAN)
+def test_scan_and_pairs_in_the_log_space_form(S):
+    """The batch of test_scan_and_pairs under pipeline 3: k_dp<DP_SCAN> runs the whole schedule of every sequence on dense tables
+    -- both chunks of merge_tuples in its sweeps, the constrained second passes, sweep_cyk and the trace-back, PairLog -- on 65
+    active states (S = 64), on a pattern whose blob the band kernels do not stage whole (78) and on the plain automaton of 128
+    states.  The same references and checks as the scaled-linear form."""
+    seqs, quals, refs = scan_refs(S)
+    refs, res, mea, e = pair_run(S, seqs, quals, opts=PIPELINE3, refs=refs)
     assert sum(v > 0.0 for v in e) >= la.PARSE_SHARE * len(seqs), e
     assert sum(len(r[2]) for r in res) > 0
 
@@ -227,71 +264,170 @@ def product(request):
     return S, seqs, quals, x, refs
 
 
-def test_context_profiles(product):
+# Every product below runs twice on the same batch and against the same references (cached: the oracle is the slow part): in the
+# scaled-linear form, and -- the tests named *_in_the_log_space_form, option pipeline 3 -- through k_dp<DP_SCAN> and the product's
+# block behind its sweeps (CtxLog, NodeLog, JointLog, StemLog, AccLog, the two worlds of cond_p0 / cond_p1, the sample stacks),
+# with the per-lane scratch sized by the state count.  The log-space runs take the tolerances the product
+# files give that form in their lambda = 40 tests, and assert that no sequence was handed on by a range check: nothing ran the
+# sum passes.
+
+def product_engine(product, log):
     S, seqs, quals, x, _ = product
-    eng, _ = loaded(S, seqs, quals)
+    eng, _ = loaded(S, seqs, quals, PIPELINE3 if log else ())
+    return eng
+
+
+def assert_log_form(eng, log):
+    if log:
+        assert eng.last_timing()[2] == 0
+
+
+def context(product, log):
+    S, seqs, quals, x, _ = product
+    eng = product_engine(product, log)
 
     def make():
         o = cc.ctx_oracle(la.PATTERN[S], W, C)
         o.set_params(x)
         return o
-    refs = t_ctx.table_refs(make, seqs, quals, x)
+    refs = cached((S, "ctx"), lambda: t_ctx.table_refs(make, seqs, quals, x))
     assert all(r is not None for r in refs)
-    t_ctx.check_profiles(eng, x, seqs, refs, what=S)
+    if log:
+        t_ctx.check_profiles(eng, x, seqs, refs, what=(S, "log"), row_atol=1e-10)
+    else:
+        t_ctx.check_profiles(eng, x, seqs, refs, what=S)
+    assert_log_form(eng, log)
+
+
+def test_context_profiles(product):
+    context(product, False)
+
+
+def test_context_profiles_in_the_log_space_form(product):
+    context(product, True)
+
+
+def node_refs(S, seqs, quals, x):
+    return cached((S, "node"), lambda: t_node.table_refs(t_node.oracle_with(la.PATTERN[S], x, W, C), seqs, quals, x))
+
+
+def node(product, log):
+    S, seqs, quals, x, _ = product
+    eng = product_engine(product, log)
+    make = t_node.oracle_with(la.PATTERN[S], x, W, C)
+    refs = node_refs(S, seqs, quals, x)
+    assert all(r is not None for r in refs)
+    if log:
+        t_node.check_profiles(eng, x, seqs, quals, refs, make=make, what=(S, "log"), row_atol=1e-10)
+    else:
+        t_node.check_profiles(eng, x, seqs, quals, refs, make=make, what=S)
+    assert_log_form(eng, log)
 
 
 def test_node_profiles(product):
+    node(product, False)
+
+
+def test_node_profiles_in_the_log_space_form(product):
+    node(product, True)
+
+
+def joint(product, log):
     S, seqs, quals, x, _ = product
-    eng, _ = loaded(S, seqs, quals)
-    make = t_node.oracle_with(la.PATTERN[S], x, W, C)
-    refs = t_node.table_refs(make, seqs, quals, x)
+    eng = product_engine(product, log)
+    refs = cached((S, "joint"), lambda: t_joint.table_refs(t_joint.oracle_with(la.PATTERN[S], x, W, C), seqs, quals, x))
     assert all(r is not None for r in refs)
-    t_node.check_profiles(eng, x, seqs, quals, refs, make=make, what=S)
+    if log:
+        t_joint.check_joint(eng, x, seqs, refs, what=(S, "log"), row_atol=1e-10)
+    else:
+        t_joint.check_joint(eng, x, seqs, refs, what=S)
+    assert_log_form(eng, log)
 
 
 def test_joint_profiles(product):
+    joint(product, False)
+
+
+def test_joint_profiles_in_the_log_space_form(product):
+    joint(product, True)
+
+
+def stems(product, log):
     S, seqs, quals, x, _ = product
-    eng, _ = loaded(S, seqs, quals)
-    refs = t_joint.table_refs(t_joint.oracle_with(la.PATTERN[S], x, W, C), seqs, quals, x)
+    eng = product_engine(product, log)
+    make = t_stem.oracle_with(la.PATTERN[S], x, W, C)
+    refs = cached((S, "stem"), lambda: t_stem.table_refs(make, seqs, quals, x))
     assert all(r is not None for r in refs)
-    t_joint.check_joint(eng, x, seqs, refs, what=S)
+    counts, _, _ = t_stem.check_stems(eng, x, seqs, refs, what=(S, "log") if log else S)
+    assert_log_form(eng, log)
+    t_stem.check_en(make, seqs, quals, refs, counts, eng.stem_slots(), what=S)
 
 
 def test_stem_profiles(product):
+    stems(product, False)
+
+
+def test_stem_profiles_in_the_log_space_form(product):
+    stems(product, True)
+
+
+def access(product, width, log):
     S, seqs, quals, x, _ = product
-    eng, _ = loaded(S, seqs, quals)
-    make = t_stem.oracle_with(la.PATTERN[S], x, W, C)
-    refs = t_stem.table_refs(make, seqs, quals, x)
+    eng = product_engine(product, log)
+    refs = cached((S, "access", width),
+                  lambda: t_access.table_refs(t_access.maker(la.PATTERN[S], x, W, C), seqs, quals, x, width))
     assert all(r is not None for r in refs)
-    counts, _, _ = t_stem.check_stems(eng, x, seqs, refs, what=S)
-    t_stem.check_en(make, seqs, quals, refs, counts, eng.stem_slots(), what=S)
+    if log:
+        t_access.check_access(eng, x, seqs, refs, width, what=(S, width, "log"), atol=1e-10, unp_atol=1e-10)
+    else:
+        t_access.check_access(eng, x, seqs, refs, width, what=(S, width))
+    assert_log_form(eng, log)
 
 
 @pytest.mark.parametrize("width", [16, 64])
 def test_accessibility(product, width):
+    access(product, width, False)
+
+
+@pytest.mark.parametrize("width", [16, 64])
+def test_accessibility_in_the_log_space_form(product, width):
+    access(product, width, True)
+
+
+def conditional(product, log):
     S, seqs, quals, x, _ = product
-    eng, _ = loaded(S, seqs, quals)
-    refs = t_access.table_refs(t_access.maker(la.PATTERN[S], x, W, C), seqs, quals, x, width)
-    assert all(r is not None for r in refs)
-    t_access.check_access(eng, x, seqs, refs, width, what=(S, width))
+    eng = product_engine(product, log)
+    refs = cached((S, "cond"), lambda: t_cond.table_refs(t_cond.pattern_oracles(la.PATTERN[S], x, W, C), seqs, quals))
+    assert sum(r["e"] >= cd.E_MIN for r in refs) >= 2, [r["e"] for r in refs]
+    t_cond.check_batch(eng, x, seqs, refs, what=(S, "log") if log else S)
+    assert_log_form(eng, log)
 
 
 def test_conditional_pairs(product):
+    conditional(product, False)
+
+
+def test_conditional_pairs_in_the_log_space_form(product):
+    conditional(product, True)
+
+
+def node_mea(product, log):
     S, seqs, quals, x, _ = product
-    eng, _ = loaded(S, seqs, quals)
-    refs = t_cond.table_refs(t_cond.pattern_oracles(la.PATTERN[S], x, W, C), seqs, quals)
-    assert sum(r["e"] >= cd.E_MIN for r in refs) >= 2, [r["e"] for r in refs]
-    t_cond.check_batch(eng, x, seqs, refs, what=S)
+    eng = product_engine(product, log)
+    refs = node_refs(S, seqs, quals, x)
+    found = 0
+    for K, gamma in ((1, 1.0), (4, 4.0)):
+        found += sum(len(g["start"]) for g in t_mea.check_batch(eng, x, refs, gamma, K, what=(S, "log") if log else S))
+    assert found > 0
+    assert_log_form(eng, log)
 
 
 def test_node_mea(product):
-    S, seqs, quals, x, _ = product
-    eng, _ = loaded(S, seqs, quals)
-    refs = t_node.table_refs(t_node.oracle_with(la.PATTERN[S], x, W, C), seqs, quals, x)
-    found = 0
-    for K, gamma in ((1, 1.0), (4, 4.0)):
-        found += sum(len(g["start"]) for g in t_mea.check_batch(eng, x, refs, gamma, K, what=S))
-    assert found > 0
+    node_mea(product, False)
+
+
+def test_node_mea_in_the_log_space_form(product):
+    node_mea(product, True)
 
 
 def test_sampler(product):
@@ -307,3 +443,62 @@ def test_sampler(product):
                             what="S %d" % S)
     assert all(st == eng.SAMPLED for _, _, _, st in out["res"])
     assert out["total"] >= 70          # (the driver drew at least one sequence's samples in the scaled-linear form)
+
+
+def test_sampler_in_the_log_space_form(product):
+    """pipeline 3: every sequence is sampled by k_dp<DP_SCAN> on its dense inside tables, walking the sample stacks of the
+    state-count-sized scratch; that form has no CPU driver (section E of test_sample_shapes_gpu.py), so: status, validity on the
+    kept cells, and the exact log-probability of six drawn derivations per sequence against Oracle.derivation_logz.  70 samples
+    and no frequency check, for the reason test_sampler gives."""
+    S, seqs, quals, x, _ = product
+    eng = product_engine(product, True)
+    out = check_sample_path(eng, seqs, quals, x, oracle_maker(la.PATTERN[S], W, C, x), 70, seed=S, n_check=6, log_all=True,
+                            what="S %d pipeline 3" % S)
+    assert all(st == eng.SAMPLED for _, _, _, st in out["res"])
+    assert eng.last_timing()[2] == 0
+
+
+
+
+# ---- both forms in one call
+
+LAM = {64: 10.0, 128: 10.0}      # lambda of Engine.initial_params, chosen on the GPU: test_both_forms_in_one_call
+MIXED_PRODUCTS = ("pairs", "context", "node", "access")
+
+
+@pytest.mark.parametrize("what", MIXED_PRODUCTS)
+@pytest.mark.parametrize("S", la.MIXED_FORM)
+def test_both_forms_in_one_call(S, what):
+    """Option group 2, parameters Engine.initial_params(lambda) as in the lambda = 40 tests of the product files, planted
+    sequences of L 40, 257, 70 and 131: the range check of the scaled-linear sum passes hands the sequences whose tables leave
+    the double range to k_dp<DP_SCAN>, in chunks of two, and the others keep the planes of the scaled-linear form: both forms
+    fill one call's output, the log-space form addressing it by launch position.  Pair posteriors (and MEA), context and node
+    profiles and accessibility at width 16 against the oracle's references at these same parameters, with the tolerances of the
+    log-space form.  lambda was chosen on an MI355X among 5, 10, 20, 30, 40, 60, 80: at S = 64 and at S = 128 alike, in every
+    one of the four calls and in scan, lambda = 5 flags 1 sequence of the 4, lambda = 10 flags 3 (two chunks), and from
+    lambda = 20 all 4 are flagged; so lambda = 10, flagged count 3, for both patterns."""
+    seqs, quals = la.mixed_form_batch(S)
+    eng = engine(S, (("group", 2),))
+    eng.load_batch(seqs, quals)
+    x = eng.initial_params(LAM[S])
+    pattern = la.PATTERN[S]
+    if what == "pairs":
+        make = oracle_maker(pattern, W, C, x)
+        check_pair_path(eng, seqs, quals, x, make, gammas=GAMMAS, refs=oracle_refs(make, seqs, quals))
+    elif what == "context":
+        def make():
+            o = cc.ctx_oracle(pattern, W, C)
+            o.set_params(x)
+            return o
+        t_ctx.check_profiles(eng, x, seqs, t_ctx.table_refs(make, seqs, quals, x), what=(S, "mixed"), row_atol=1e-10)
+        eng.context_profiles(x)
+    elif what == "node":
+        make = t_node.oracle_with(pattern, x, W, C)
+        t_node.check_profiles(eng, x, seqs, quals, t_node.table_refs(make, seqs, quals, x), what=(S, "mixed"), row_atol=1e-10)
+    else:
+        refs = t_access.table_refs(t_access.maker(pattern, x, W, C), seqs, quals, x, 16)
+        t_access.check_access(eng, x, seqs, refs, 16, what=(S, "mixed"), atol=1e-10, unp_atol=1e-10)
+        eng.accessibility(x, 16)
+    n_flagged = int(eng.last_timing()[2])          # (of the product's own call, the last one)
+    print("both forms, S %d, %s: lambda %g flags %d of %d" % (S, what, LAM[S], n_flagged, len(seqs)))
+    assert 1 <= n_flagged < len(seqs), n_flagged

@@ -93,34 +93,94 @@ def test_tiny_batch_equals_the_enumeration(opts, tiny_refs):
 
 # ---- shapes against the definitions over the oracle's tables and the oracle's scan
 
-@pytest.mark.parametrize("pattern,W,lens", [(P1, 50, SHAPE_LENS), (P2, 50, SHAPE_LENS), (P1, 20, (5, 19, 20, 21, 47)),
-                                            (P1, 70, (66, 70, 93))], ids=["P1-W50", "P2-W50", "P1-W20", "P1-W70"])
+PIPELINE3 = (("pipeline", 3),)
+_REFS = {}
+
+
+def cached(key, compute):
+    """the references of a case, computed once for the scaled-linear and the log-space form (the oracle is the slow part)"""
+    if key not in _REFS:
+        _REFS[key] = compute()
+    return _REFS[key]
+
+
+def engine_with(pattern, W, opts=()):
+    eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    for k, v in opts:
+        eng.set_option(k, v)
+    return eng
+
+
+def shape_case(pattern, W, lens):
+    """(seqs, quals, x, the oracle maker, table references) of a shape case"""
+    def compute():
+        seqs, quals = shape_batch(lens, seed=1000 * W + len(pattern) + len(lens), with_edge=(lens is SHAPE_LENS))
+        x = node_params(engine_with(pattern, W))
+        make = oracle_with(pattern, x, W)
+        return seqs, quals, x, make, table_refs(make, seqs, quals, x)
+    return cached(("shape", pattern, W, lens), compute)
+
+
+W20_LENS, W70_LENS, LONG_LENS = (5, 19, 20, 21, 47), (66, 70, 93), (257, 300)
+
+
+@pytest.mark.parametrize("pattern,W,lens", [(P1, 50, SHAPE_LENS), (P2, 50, SHAPE_LENS), (P1, 20, W20_LENS), (P1, 70, W70_LENS),
+                                            (P1, 20, LONG_LENS)], ids=["P1-W50", "P2-W50", "P1-W20", "P1-W70", "P1-W20-long"])
 def test_shapes_against_the_table_definitions(pattern, W, lens):
     """(W = 70: the lanes of k_node_pos take the spans d = 1 + lane, 65 + lane, .., so a position with cells of span above 64 sums
     a second round per lane before the wave reduction; the lengths 1 .. 200 leave the last workgroup of a sequence, four positions
-    each, partly empty)"""
-    seqs, quals = shape_batch(lens, seed=1000 * W + len(pattern) + len(lens), with_edge=(lens is SHAPE_LENS))
-    eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    each, partly empty; L = 257 and 300 at W = 20: positions beyond 256)"""
+    seqs, quals, x, make, refs = shape_case(pattern, W, lens)
+    eng = engine_with(pattern, W)
     eng.load_batch(seqs, quals)
-    x = node_params(eng)
-    make = oracle_with(pattern, x, W)
-    refs = table_refs(make, seqs, quals, x)
     prof = check_profiles(eng, x, seqs, quals, refs, make, what=(pattern, W))
     assert sum(r is not None for r in refs) >= len(lens)
     assert max(p[:, 1:-1].sum(axis=1).max() for p in prof) > 0.05
 
 
-@pytest.mark.parametrize("model", ["syn_sm.model", "syn_a2007.model", "2.model"])
+@pytest.mark.parametrize("W,lens", [(20, W20_LENS), (70, W70_LENS), (20, LONG_LENS)], ids=["P1-W20", "P1-W70", "P1-W20-long"])
+def test_shapes_in_the_log_space_form(W, lens):
+    """pipeline 3: k_dp<DP_SCAN> and NodeLog fill the planes the position stage reads, addressed by launch position; the
+    references of the scaled-linear cases, rows within 1e-10 (test_sequences_out_of_the_double_range_take_the_log_space_form)"""
+    seqs, quals, x, make, refs = shape_case(P1, W, lens)
+    eng = engine_with(P1, W, PIPELINE3)
+    eng.load_batch(seqs, quals)
+    prof = check_profiles(eng, x, seqs, quals, refs, make, what=(W, "pipeline 3"), row_atol=1e-10)
+    assert sum(r is not None for r in refs) >= len(lens)
+    assert max(p[:, 1:-1].sum(axis=1).max() for p in prof) > 0.05
+    assert eng.last_timing()[2] == 0
+
+
+MODELS = ["syn_sm.model", "syn_a2007.model", "2.model"]
+
+
+def model_case(model):
+    def compute():
+        m = io.read_model(gpath(model))
+        seqs, quals = batch((3, 13, 40, 97, 131), seed=len(model))
+        make = lambda: nc.node_oracle_from_model(gpath(model))[0]
+        return m, seqs, quals, make, table_refs(make, seqs, quals, m["x"], tau=m["tau"])
+    return cached(("model", model), compute)
+
+
+@pytest.mark.parametrize("model", MODELS)
 def test_models_against_the_table_definitions(model):
     """softmax theta, the ~A2007~ energy parameters, and a model without secondary structure (2.model: rule 8 alone)"""
-    m = io.read_model(gpath(model))
-    seqs, quals = batch((3, 13, 40, 97, 131), seed=len(model))
+    m, seqs, quals, make, refs = model_case(model)
     eng = io.engine_from_model(m)
     eng.load_batch(seqs, quals)
-    x = m["x"]
-    make = lambda: nc.node_oracle_from_model(gpath(model))[0]
-    refs = table_refs(make, seqs, quals, x, tau=m["tau"])
-    check_profiles(eng, x, seqs, quals, refs, make, what=model)
+    check_profiles(eng, m["x"], seqs, quals, refs, make, what=model)
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_in_the_log_space_form(model):
+    """pipeline 3 (2.model: the no_rss branches of k_dp, the node profile by rule 8 alone)"""
+    m, seqs, quals, make, refs = model_case(model)
+    eng = io.engine_from_model(m)
+    eng.set_option("pipeline", 3)
+    eng.load_batch(seqs, quals)
+    check_profiles(eng, m["x"], seqs, quals, refs, make, what=(model, "pipeline 3"), row_atol=1e-10)
+    assert eng.last_timing()[2] == 0
 
 
 def test_sequences_out_of_the_double_range_take_the_log_space_form():
@@ -179,6 +239,23 @@ def test_groupings_agree_and_nothing_else_changes():
         for k, (g, w) in enumerate(zip(got, want)):
             assert g.shape == w.shape
             np.testing.assert_allclose(g, w, rtol=1e-10, atol=1e-14, err_msg=str((opts, k)))
+
+
+def test_a_workgroup_of_the_log_space_form_takes_several_sequences():
+    """pipeline 3 with option slots 3: log_scan_args asks for min(slots, n_seq) table slots and launches as many workgroups, so
+    n_blocks = 3 workgroups take the n_seq = 11 unsorted sequences of L 20 .. 280 off the atomic counter.  Against the table
+    references, not against another grouping."""
+    lens = [int(v) for v in np.linspace(20, 280, 11)][::-1]
+    lens[2], lens[7] = lens[7], lens[2]
+    seqs, quals = batch(lens, seed=5)
+    eng = engine_with(P1, 50, PIPELINE3 + (("slots", 3),))
+    eng.load_batch(seqs, quals)
+    x = node_params(eng)
+    refs = table_refs(oracle_with(P1, x), seqs, quals, x)
+    check_profiles(eng, x, seqs, quals, refs, what="slots 3", row_atol=1e-10)
+    assert sum(r is not None for r in refs) >= 10
+    assert (eng.slot_status()["slots"], eng.n_seq) == (3, 11)
+    assert eng.last_timing()[2] == 0
 
 
 # ---- the engine's own context profiles, rule by rule

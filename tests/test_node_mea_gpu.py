@@ -119,14 +119,42 @@ def test_tiny_and_multi_site_cases_equal_the_enumeration(opts, tiny_brute):
 
 # ---- shapes through the checker
 
-@pytest.mark.parametrize("pattern,W,lens", [(P1, 50, SHAPE_LENS), (P2, 50, SHAPE_LENS), (P1, 70, (66, 70, 93))],
-                         ids=["P1-W50", "P2-W50", "P1-W70"])
-def test_shapes_through_the_checker(pattern, W, lens):
-    seqs, quals = shape_batch(lens, seed=1000 * W + len(pattern) + len(lens), with_edge=(lens is SHAPE_LENS))
+PIPELINE3 = (("pipeline", 3),)
+_REFS = {}
+
+
+def cached(key, compute):
+    """the references of a case, computed once for the scaled-linear and the log-space form (the oracle is the slow part)"""
+    if key not in _REFS:
+        _REFS[key] = compute()
+    return _REFS[key]
+
+
+def engine_with(pattern, W, opts=()):
     eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    for k, v in opts:
+        eng.set_option(k, v)
+    return eng
+
+
+def shape_case(pattern, W, lens):
+    """(seqs, quals, x, the table references of the node profile) of a shape case"""
+    def compute():
+        seqs, quals = shape_batch(lens, seed=1000 * W + len(pattern) + len(lens), with_edge=(lens is SHAPE_LENS))
+        x = node_params(engine_with(pattern, W))
+        return seqs, quals, x, table_refs(oracle_with(pattern, x, W), seqs, quals, x)
+    return cached(("shape", pattern, W, lens), compute)
+
+
+W20_LENS, W70_LENS, LONG_LENS = (5, 19, 20, 21, 47), (66, 70, 93), (257, 300)
+
+
+@pytest.mark.parametrize("pattern,W,lens", [(P1, 50, SHAPE_LENS), (P2, 50, SHAPE_LENS), (P1, 70, W70_LENS), (P1, 20, W20_LENS),
+                                            (P1, 20, LONG_LENS)], ids=["P1-W50", "P2-W50", "P1-W70", "P1-W20", "P1-W20-long"])
+def test_shapes_through_the_checker(pattern, W, lens):
+    seqs, quals, x, refs = shape_case(pattern, W, lens)
+    eng = engine_with(pattern, W)
     eng.load_batch(seqs, quals)
-    x = node_params(eng)
-    refs = table_refs(oracle_with(pattern, x, W), seqs, quals, x)
     found = 0
     first = {}
     for K in (1, 4):
@@ -145,17 +173,55 @@ def test_shapes_through_the_checker(pattern, W, lens):
         assert found > 0
 
 
-@pytest.mark.parametrize("model", ["syn_sm.model", "syn_a2007.model", "2.model"])
-def test_models_through_the_checker(model):
-    m = io.read_model(gpath(model))
-    seqs, quals = batch((3, 13, 40, 97, 131), seed=len(model))
-    eng = io.engine_from_model(m)
+@pytest.mark.parametrize("W,lens", [(20, W20_LENS), (70, W70_LENS), (20, LONG_LENS)], ids=["P1-W20", "P1-W70", "P1-W20-long"])
+def test_shapes_in_the_log_space_form(W, lens):
+    """pipeline 3: the node pass runs in k_dp<DP_SCAN> (NodeLog) and k_node_mea reads its profile by launch position; the
+    references of the scaled-linear cases through the same checker, at every gamma for one site and for four"""
+    seqs, quals, x, refs = shape_case(P1, W, lens)
+    eng = engine_with(P1, W, PIPELINE3)
     eng.load_batch(seqs, quals)
-    make = lambda: nc.node_oracle_from_model(gpath(model))[0]
-    refs = table_refs(make, seqs, quals, m["x"], tau=m["tau"])
+    found = 0
     for K in (1, 4):
         for gamma in GAMMAS:
-            check_batch(eng, m["x"], refs, gamma, K, what=model)
+            found += sum(len(g["start"]) for g in check_batch(eng, x, refs, gamma, K, what=(W, "pipeline 3")))
+    assert found > 0
+    assert eng.last_timing()[2] == 0
+
+
+MODELS = ["syn_sm.model", "syn_a2007.model", "2.model"]
+
+
+def model_case(model):
+    def compute():
+        m = io.read_model(gpath(model))
+        seqs, quals = batch((3, 13, 40, 97, 131), seed=len(model))
+        make = lambda: nc.node_oracle_from_model(gpath(model))[0]
+        return m, seqs, quals, table_refs(make, seqs, quals, m["x"], tau=m["tau"])
+    return cached(("model", model), compute)
+
+
+def check_model(model, opts):
+    m, seqs, quals, refs = model_case(model)
+    eng = io.engine_from_model(m)
+    for k, v in opts:
+        eng.set_option(k, v)
+    eng.load_batch(seqs, quals)
+    for K in (1, 4):
+        for gamma in GAMMAS:
+            check_batch(eng, m["x"], refs, gamma, K, what=(model, opts))
+    return eng
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_through_the_checker(model):
+    check_model(model, ())
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_in_the_log_space_form(model):
+    """pipeline 3 (2.model: the no_rss branches of k_dp)"""
+    eng = check_model(model, PIPELINE3)
+    assert eng.last_timing()[2] == 0
 
 
 def test_both_forms_of_the_node_pass_in_one_call():
@@ -210,6 +276,21 @@ def test_groupings_and_a_streamed_batch(opts, grouped):
     want = check_batch(base, x, refs, 4.0, 4, what="default")
     assert [len(g["start"]) for g in got] == [len(w["start"]) for w in want]
     assert sum(len(g["start"]) for g in got) > 0
+
+
+def test_a_workgroup_of_the_log_space_form_takes_several_sequences(grouped):
+    """pipeline 3 with option slots 3: log_scan_args asks for min(slots, n_seq) table slots and launches as many workgroups, so
+    n_blocks = 3 workgroups take the n_seq = 9 unsorted sequences of L 20 .. 200 of the grouping tests off the atomic counter.
+    Through the checker against the table references, not against another grouping."""
+    seqs, quals, base, x, refs = grouped
+    eng = api.Engine(P1, PAR, 50, 30, 1e-4, 0.1, 0, 0)
+    eng.set_option("pipeline", 3)
+    eng.set_option("slots", 3)
+    eng.load_batch(seqs, quals)
+    got = check_batch(eng, x, refs, 4.0, 4, what="slots 3")
+    assert sum(len(g["start"]) for g in got) > 0
+    assert (eng.slot_status()["slots"], eng.n_seq) == (3, 9)
+    assert eng.last_timing()[2] == 0
 
 
 def test_the_profile_flag_and_the_python_call(grouped):

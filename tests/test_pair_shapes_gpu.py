@@ -9,7 +9,7 @@ import pytest
 
 from oracle import pyoracle as po
 from rnaelem_amd import api, io, synth
-from tests.pair_check import GAMMAS, check_pair_path, oracle_refs
+from tests.pair_check import GAMMAS, check_pair_lists, check_pair_path, oracle_refs
 from tests.test_pair_posterior_gpu import perturbed
 from tests.util import gpath
 
@@ -183,6 +183,66 @@ def test_log_space_pipeline_in_two_chunks():
     seqs, quals = batch(lens, seed=3)
     _, _, refs, res, _ = run(P1, seqs, quals, opts=(("pipeline", 3),), gammas=(1.0, 4.0))
     assert sum(r["P"] is not None for r in refs[1024:]) >= 20 and sum(len(r[2]) for r in res[1024:]) > 0
+
+
+LDS_LIMIT = 160 * 1024
+K_THREADS = 256          # kernels.h: kThreads
+
+
+def lds_image_bytes(L, n_theta, n_small, W=50):
+    """Engine::lds_layout(lay, Lmax, nword_max, scan = true), the LDS image of k_dp<DP_SCAN>, every field rounded up to 16 bytes:
+    theta, en_o, en_x (8 (n_theta + 1) each), eh (8 * 4), zs (8 * 8), ws (8 (Lmax + 1)), post (8 * 3 (Lmax + 1)), the small part
+    of the automaton blob (4 n_small), wave_scr (8 * 128 * kThreads / 64), the pair mask (4 nword_max, one bit per cell of
+    (Lmax + 1) (W + 1): Engine::check_batch), dmin (2 (Lmax + 1)), seq and unp (Lmax + 1 each)"""
+    def take(b):
+        return (b + 15) & ~15
+    nword = ((L + 1) * (min(L, W) + 1) + 31) // 32
+    return (3 * take(8 * (n_theta + 1)) + take(8 * 4) + take(8 * 8) + take(8 * (L + 1)) + take(8 * 3 * (L + 1)) + take(4 * n_small) +
+            take(8 * 128 * (K_THREADS // 64)) + take(4 * nword) + take(2 * (L + 1)) + 2 * take(L + 1))
+
+
+def first_refused_length(n_theta, n_small):
+    L = 1
+    while lds_image_bytes(L, n_theta, n_small) <= LDS_LIMIT:
+        L += 1
+    return L
+
+
+def test_a_sequence_beyond_the_lds_staging_is_refused_and_the_handle_lives_on():
+    """The log-space form stages a sequence's rows in LDS and Engine::lds_layout refuses an image above 160 KiB; log_scan_args
+    sizes it by the batch's longest sequence.  For ((.*.)) at W = 50 (n_theta 24, n_small 889 ints) the first refused length is
+    3667 (163 856 bytes; L = 3666 fills the 163 840 exactly).  describe() reports n_ints, the whole blob, not its small part:
+    with 0 <= n_small <= n_ints the limit lies between first_refused_length(n_theta, n_ints) and first_refused_length(n_theta,
+    0) = 3752, and the batch here holds one sequence of the latter length, refused whatever the small part is, behind three
+    short ones.  Under pipeline 3 scan, pair_posteriors and context_profiles throw on the host before any launch.
+    The handle stays usable: under pipeline 4 the same batch gives the oracle's pair posteriors on the three short sequences
+    (the long one needs no reference, it only has to be resident and swept), and a fresh batch of the three short ones under
+    pipeline 3 passes the whole check."""
+    eng = api.Engine(P1, PAR, 50, 30, 1e-4, 0.1, 0, 0)
+    n_theta, n_ints = eng.n_param - 2, eng.describe()["layout"]["n_ints"]
+    lo, L = first_refused_length(n_theta, n_ints), first_refused_length(n_theta, 0)
+    assert (n_theta, L) == (24, 3752) and lo <= first_refused_length(n_theta, 889) == 3667 <= L
+    assert lds_image_bytes(3666, n_theta, 889) == LDS_LIMIT
+    short_s, short_q = batch((40, 71, 97), seed=160)
+    (long_s,), (long_q,) = batch((L,), seed=161, n_every=0, neg_every=0)
+    seqs, quals = short_s + [long_s], short_q + [long_q]
+    x = perturbed(eng)
+    make = oracle_maker(P1, 50, 30, x)
+    refs = oracle_refs(make, short_s, short_q)
+    assert sum(r["P"] is not None for r in refs) == 3
+    eng.set_option("pipeline", 3)
+    eng.load_batch(seqs, quals)
+    for call in (lambda: eng.scan(x), lambda: eng.pair_posteriors(x, 0.0), lambda: eng.context_profiles(x)):
+        with pytest.raises(api.ElemdpError, match="too large for the LDS staging"):
+            call()
+    eng.set_option("pipeline", 4)
+    res = eng.pair_posteriors(x, 0.0)
+    assert eng.last_timing()[2] == 0 and len(res) == 4 and len(res[3][3]) == L
+    check_pair_lists(eng, short_s, res[:3], [r["P"] for r in refs])
+    eng.set_option("pipeline", 3)
+    eng.load_batch(short_s, short_q)
+    check_pair_path(eng, short_s, short_q, x, make, refs=refs)
+    assert eng.last_timing()[2] == 0
 
 
 # ---- F. models

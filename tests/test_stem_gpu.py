@@ -97,33 +97,93 @@ def test_enumerated_cases(opts):
 
 # ---- shapes against the definition over the oracle's tables
 
-@pytest.mark.parametrize("pattern,W,lens", [(P1, 20, tuple(range(1, 61))), (P5, 20, tuple(range(1, 61))), (P1, 70, (107,))],
+PIPELINE3 = (("pipeline", 3),)
+_REFS = {}
+
+
+def cached(key, compute):
+    """the references of a case, computed once for the scaled-linear and the log-space form (the oracle is the slow part)"""
+    if key not in _REFS:
+        _REFS[key] = compute()
+    return _REFS[key]
+
+
+def engine_with(pattern, W, opts=()):
+    eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    for k, v in opts:
+        eng.set_option(k, v)
+    return eng
+
+
+def shape_case(pattern, W, lens):
+    """(seqs, quals, x, table references) of a shape case"""
+    def compute():
+        seqs, quals = batch(lens, seed=1000 * W + len(pattern) + len(lens))
+        x = sc.stem_params(engine_with(pattern, W))
+        return seqs, quals, x, table_refs(oracle_with(pattern, x, W), seqs, quals, x)
+    return cached(("shape", pattern, W, lens), compute)
+
+
+def long_case():
+    """L = 257 and 300 at W = 20, the references from the CPU driver of the product rule"""
+    def compute():
+        seqs, quals = batch((257, 300), seed=77, n_every=0)
+        eng = engine_with(P1, 20)
+        x = sc.stem_params(eng)
+        drv = sc.StemDriver(P1, PAR, 20, 30, 1e-4, 0.1, 0)
+        assert np.array_equal(drv.slots, eng.stem_slots())
+        return seqs, quals, x, [drv.stems(x, s, q, 0)[0] for s, q in zip(seqs, quals)]
+    return cached("long", compute)
+
+
+W20_LENS, W70_LENS = tuple(range(1, 61)), (107,)
+
+
+@pytest.mark.parametrize("pattern,W,lens", [(P1, 20, W20_LENS), (P5, 20, W20_LENS), (P1, 70, W70_LENS)],
                          ids=["P1-W20", "P5-W20", "P1-W70"])
 def test_shapes_against_the_table_definition(pattern, W, lens):
     """(L = 1 .. 60: sequences shorter than a pair, than the motif and than W, cell counts that are no multiple of the workgroup,
     rows shorter and longer than W; L = 107 at W = 70: eight thousand cells, thirty workgroups of k_stem_cells)"""
-    seqs, quals = batch(lens, seed=1000 * W + len(pattern) + len(lens))
-    eng = api.Engine(pattern, PAR, W, 30, 1e-4, 0.1, 0, 0)
+    seqs, quals, x, refs = shape_case(pattern, W, lens)
+    eng = engine_with(pattern, W)
     eng.load_batch(seqs, quals)
-    x = sc.stem_params(eng)
-    refs = table_refs(oracle_with(pattern, x, W), seqs, quals, x)
     counts, _, dense = check_stems(eng, x, seqs, refs, what=(pattern, W))
     check_en(oracle_with(pattern, x, W), seqs, quals, refs, counts, eng.stem_slots(), what=(pattern, W))
     assert sum(r is not None for r in refs) >= len(lens) - 1
     assert max(g.sum() for g in dense) > 1.0
 
 
+@pytest.mark.parametrize("W,lens", [(20, W20_LENS), (70, W70_LENS)], ids=["P1-W20", "P1-W70"])
+def test_shapes_in_the_log_space_form(W, lens):
+    """pipeline 3: k_dp<DP_SCAN> and StemLog fill the cells the list stage compacts, addressed by launch position; the
+    references and the checks of the scaled-linear cases"""
+    seqs, quals, x, refs = shape_case(P1, W, lens)
+    eng = engine_with(P1, W, PIPELINE3)
+    eng.load_batch(seqs, quals)
+    counts, _, dense = check_stems(eng, x, seqs, refs, what=(W, "pipeline 3"))
+    assert eng.last_timing()[2] == 0
+    check_en(oracle_with(P1, x, W), seqs, quals, refs, counts, eng.stem_slots(), what=(W, "pipeline 3"))
+    assert sum(r is not None for r in refs) >= len(lens) - 1
+    assert max(g.sum() for g in dense) > 1.0
+
+
 def test_long_sequences_against_the_cpu_driver():
     """L = 257 and 300 at W = 20 cross the tiles of 256 rows of the list kernel"""
-    seqs, quals = batch((257, 300), seed=77, n_every=0)
-    eng = api.Engine(P1, PAR, 20, 30, 1e-4, 0.1, 0, 0)
+    seqs, quals, x, refs = long_case()
+    eng = engine_with(P1, 20)
     eng.load_batch(seqs, quals)
-    x = sc.stem_params(eng)
-    drv = sc.StemDriver(P1, PAR, 20, 30, 1e-4, 0.1, 0)
-    assert np.array_equal(drv.slots, eng.stem_slots())
-    refs = [drv.stems(x, s, q, 0)[0] for s, q in zip(seqs, quals)]
     o = oracle_with(P1, x, 20)()
     check_stems(eng, x, seqs, refs, what="long", oracle=o, quals=quals)
+
+
+def test_long_sequences_in_the_log_space_form():
+    """the same under pipeline 3"""
+    seqs, quals, x, refs = long_case()
+    eng = engine_with(P1, 20, PIPELINE3)
+    eng.load_batch(seqs, quals)
+    o = oracle_with(P1, x, 20)()
+    check_stems(eng, x, seqs, refs, what="long, pipeline 3", oracle=o, quals=quals)
+    assert eng.last_timing()[2] == 0
 
 
 # ---- the identities against the handle's own calls
@@ -153,22 +213,46 @@ def test_sums_are_the_pair_posteriors_and_the_joint_counts_of_the_same_handle(op
     assert max(q.max() for _, _, _, q in lists) > 0.05
 
 
-@pytest.mark.parametrize("model", ["syn_sm.model", "syn_a2007.model", "2.model"])
-def test_models_against_the_table_definition(model):
-    """softmax theta, the ~A2007~ energy parameters, and a model without secondary structure (2.model: no stems at all)"""
-    m = io.read_model(gpath(model))
-    seqs, quals = batch((3, 13, 40, 97), seed=len(model))
+MODELS = ["syn_sm.model", "syn_a2007.model", "2.model"]
+
+
+def model_case(model):
+    def compute():
+        m = io.read_model(gpath(model))
+        seqs, quals = batch((3, 13, 40, 97), seed=len(model))
+        refs = table_refs(lambda: sc.stem_oracle_from_model(gpath(model))[0], seqs, quals, m["x"], tau=m["tau"])
+        return m, seqs, quals, refs
+    return cached(("model", model), compute)
+
+
+def check_model(model, opts):
+    m, seqs, quals, refs = model_case(model)
     eng = io.engine_from_model(m)
+    for k, v in opts:
+        eng.set_option(k, v)
     eng.load_batch(seqs, quals)
     x = m["x"]
-    refs = table_refs(lambda: sc.stem_oracle_from_model(gpath(model))[0], seqs, quals, x, tau=m["tau"])
     if m["no_rss"]:
         counts, lists = eng.stem_profiles(x, 0.0)
         assert not counts.any() and all(len(l[3]) == 0 for l in lists)
         assert all(r is None or not r.any() for r in refs)
-        return
+        return eng
     o = sc.stem_oracle_from_model(gpath(model))[0]
-    check_stems(eng, x, seqs, refs, what=model, oracle=o, quals=quals)
+    check_stems(eng, x, seqs, refs, what=(model, opts), oracle=o, quals=quals)
+    return eng
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_against_the_table_definition(model):
+    """softmax theta, the ~A2007~ energy parameters, and a model without secondary structure (2.model: no stems at all)"""
+    check_model(model, ())
+
+
+@pytest.mark.parametrize("model", MODELS)
+def test_models_in_the_log_space_form(model):
+    """pipeline 3 (2.model: the no_rss branches of k_dp, stm.has = 0)"""
+    eng = check_model(model, PIPELINE3)
+    assert eng.last_timing()[2] == 0
 
 
 def test_sequences_out_of_the_double_range_take_the_log_space_form():
@@ -202,6 +286,24 @@ def test_a_sequence_without_any_parse_has_no_stems():
     assert refs[0] is None and refs[1] is not None
     counts, lists, _ = check_stems(eng, x, seqs, refs, what="no parse")
     assert not counts[0].any() and len(lists[0][3]) == 0 and len(lists[1][3]) > 0
+
+
+def test_a_workgroup_of_the_log_space_form_takes_several_sequences():
+    """pipeline 3 with option slots 3: log_scan_args asks for min(slots, n_seq) table slots and launches as many workgroups, so
+    n_blocks = 3 workgroups take the n_seq = 9 unsorted sequences of L 20 .. 160 of the grouping test off the atomic counter.
+    Against the table references and the oracle's scan, not against another grouping."""
+    lens = [int(v) for v in np.linspace(20, 160, 9)][::-1]
+    lens[2], lens[6] = lens[6], lens[2]
+    seqs, quals = batch(lens, seed=5)
+    eng = engine_with(P1, 50, PIPELINE3 + (("slots", 3),))
+    eng.load_batch(seqs, quals)
+    x = sc.stem_params(eng)
+    refs = table_refs(oracle_with(P1, x), seqs, quals, x)
+    counts, _, _ = check_stems(eng, x, seqs, refs, what="slots 3")
+    assert (eng.slot_status()["slots"], eng.n_seq) == (3, 9)
+    assert eng.last_timing()[2] == 0
+    check_en(oracle_with(P1, x), seqs, quals, refs, counts, eng.stem_slots(), what="slots 3")
+    assert sum(r is not None for r in refs) >= 8
 
 
 # ---- groupings, streamed batches, thresholds, and what a call leaves alone
