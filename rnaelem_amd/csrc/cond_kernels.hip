@@ -1,8 +1,8 @@
 // cond_kernels.hip -- motif-conditional pair posteriors (rule in cond_rules.h): the pair reduction of one world over
 // the compact tables behind that world's outside sweep (k4_cond), the per-sequence pass over both worlds -- unpaired vectors,
-// exist_prob, shift and the compaction with two probability columns (k_cond_seq) -- and the scatter into the batch list in
-// (sequence, i, j) order (k_cond_scatter; the counts and prefixes are those of pair_kernels.hip).  No atomics: every sum has a
-// fixed order, so repeats over the same tables give the same bits.
+// exist_prob, shift and the compaction with two probability columns (k_cond_seq).  The batch list in (sequence, i, j) order is
+// built by the counts, prefixes and scatter of pair_kernels.hip.  No atomics: every sum has a fixed order, so repeats over the
+// same tables give the same bits.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -122,17 +122,6 @@ __global__ __launch_bounds__(kThreads) void k_cond_seq(CondArgs a) {
   }
 }
 
-__global__ __launch_bounds__(kThreads) void k_cond_scatter(const int64_t* koff, const int64_t* cnt, const int64_t* off, const int32_t* st_i,
-                                                           const int32_t* st_j, const double* st_p0, const double* st_p1, int32_t* seq,
-                                                           int32_t* i, int32_t* j, double* p0, double* p1) {
-  const int n = blockIdx.x;
-  const int64_t c = cnt[n], src = koff[n], dst = off[n];
-  for (int64_t t = threadIdx.x; t < c; t += kThreads) {
-    seq[dst + t] = n; i[dst + t] = st_i[src + t]; j[dst + t] = st_j[src + t];
-    p0[dst + t] = st_p0[src + t]; p1[dst + t] = st_p1[src + t];
-  }
-}
-
 hipError_t launch_cond_cells(const CondArgs& a, int world, int G, int cells_max, hipStream_t st) {
   if (G <= 0) return hipSuccess;
   hipLaunchKernelGGL(k4_cond, dim3((cells_max + kThreads - 1) / kThreads, G), dim3(kThreads), 0, st, a, world);
@@ -141,13 +130,6 @@ hipError_t launch_cond_cells(const CondArgs& a, int world, int G, int cells_max,
 hipError_t launch_cond_seq(const CondArgs& a, int G, hipStream_t st) {
   if (G <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_cond_seq, dim3(G), dim3(kThreads), 0, st, a);
-  return hipGetLastError();
-}
-hipError_t launch_cond_scatter(const int64_t* koff, const int64_t* cnt, const int64_t* off, const int32_t* st_i, const int32_t* st_j,
-                               const double* st_p0, const double* st_p1, int n, int32_t* seq, int32_t* i, int32_t* j, double* p0,
-                               double* p1, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_cond_scatter, dim3(n), dim3(kThreads), 0, st, koff, cnt, off, st_i, st_j, st_p0, st_p1, seq, i, j, p0, p1);
   return hipGetLastError();
 }
 

@@ -43,6 +43,7 @@
 #include "joint_rules.h"
 #include "sample_rules.h"
 #include "stem_rules.h"
+#include "staged_list.h"
 #include "table_slots.h"
 
 namespace elemdp {
@@ -314,12 +315,17 @@ class Engine {
   int prepare_scan(LinArgs& a, const ScanPos& pos);
   int read_flagged(std::vector<int32_t>* list = nullptr);
   DpArgs log_scan_args(bool sums_on_batch, int* n_blocks);
-  int log_chunk(bool sums_on_batch, int n_blocks, int n_log) const;
+  int log_chunk(int n_blocks, int n_log) const;
+  template <class T> T* slot_scratch(DevBuf& b, size_t stride, size_t slot0 = 0);
   PairArgs pair_batch_args() const;
   void pair_plane_fields(PairArgs& pa, const LinArgs& a) const;
   void require_resident(const char* what, int n_param_in);
   template <class Fill, class Group> int scan_sums(const ScanPos& pos, Fill fill, Group group, std::vector<int32_t>* flagged = nullptr);
   template <class Fill, class Behind> void scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind behind);
+  template <class Fill, class Group, class LogFill, class Behind>
+  int scan_both_forms(const ScanPos& pos, Fill fill, Group group, LogFill log_fill, Behind behind);
+  void finish_call(int n_flagged);
+  template <class Copy> void finish_call(int n_flagged, Copy copy_out);
   int node_profile_device(const char* what, const double* x, int n_param_in);
   TrArgs log_pipeline_args();
   void init_device();
@@ -399,30 +405,25 @@ class Engine {
   void stream_pairs(const double* x, int n_param, double min_prob, double* unpaired, const MeaOut* mea);
   void stream_samples(const double* x, int n_param, int n_samples, uint64_t seed, int64_t index_base, const SampleOut& out);
   void stream_cond(const double* x, int n_param, double min_prob, const CondOut& out);
-  // pair posteriors: kept pairs per sequence and their prefix (staging ranges), pairs kept by min_prob and their prefix, the
-  // P(i, d) scratch of the table slots, the staging list, the final list of the last call (n_pairs_ < 0: none)
-  DevBuf d_pr_kept_, d_pr_koff_, d_pr_cnt_, d_pr_off_, d_pr_P_, d_pr_unp_, d_pr_si_, d_pr_sj_, d_pr_sp_;
-  DevBuf d_pl_seq_, d_pl_i_, d_pl_j_, d_pl_p_;
-  int64_t n_pairs_ = -1;
+  // the lists of the last pair, conditional and stem call (staged_list.h), each in buffers of its own
+  StagedList pairs_{"pair_list", "pair_posteriors", 1, false};
+  StagedList conds_{"pair_conditional_list", "pair_conditional", 2, false};
+  StagedList stems_{"stem_list", "stem_profile", 1, true};
+  size_t scratch_slots_ = 0;   // slots the per-slot scratch of the running scan-family call is sized for (slot_scratch)
+  DevBuf d_pr_P_, d_pr_unp_;   // pair posteriors: the P(i, d) scratch of the table slots, the unpaired vector of the call
   // MEA structures: the M table and choice scratch of the table slots (as d_pr_P_), the structures and the scores of the call
   DevBuf d_mea_M_, d_mea_ch_, d_mea_s_, d_mea_sc_;
   DevBuf d_sm_rss_, d_sm_node_, d_sm_logp_, d_sm_status_, d_sm_stack_;   // sample_structures
-  // conditional pair posteriors, all of the call's own: counts and prefixes as for the pair call, the P(i, d) scratch of both
-  // worlds per table slot, ln Z per slot of the log-space form, unpaired vectors, exist_prob and shift, the staging list and the
-  // final list of the last call (n_cond_ < 0: none), then the MEA scratch, structures and scores of both worlds
-  DevBuf d_cd_kept_, d_cd_koff_, d_cd_cnt_, d_cd_off_, d_cd_P_, d_cd_z_, d_cd_unp_[2], d_cd_exist_, d_cd_shift_, d_cd_si_, d_cd_sj_, d_cd_sp_[2];
-  DevBuf d_cl_seq_, d_cl_i_, d_cl_j_, d_cl_p_[2];
-  int64_t n_cond_ = -1;
+  // conditional pair posteriors, all of the call's own: the P(i, d) scratch of both worlds per table slot, ln Z per slot of the
+  // log-space form, unpaired vectors, exist_prob and shift, then the MEA scratch, structures and scores of both worlds
+  DevBuf d_cd_P_[2], d_cd_z_, d_cd_unp_[2], d_cd_exist_, d_cd_shift_;
   DevBuf d_cd_M_, d_cd_ch_, d_cd_s_[2], d_cd_sc_;
   // context profiles: P, u, h, b of the table slots (four [i][d] arrays per slot), their exterior columns, the profile of the call
   DevBuf d_cx_cells_, d_cx_o_, d_cx_prof_;
   DevBuf d_ac_T_, d_ac_vec_, d_ac_out_;   // accessibility: the four planes per slot, the log-space form's vectors, the result
   DevBuf d_jn_lists_, d_jn_X_, d_jn_vec_, d_jn_prof_, d_jn_counts_;   // joint profiles: lists and slot map, per-cell scratch per slot, the log-space form's vectors, the results
-  // stem profiles: the transitions by slot, Q of the table slots, the parse marks and counts of the call, the staging list, the
-  // final list of the last call (n_stem_ < 0: none)
-  DevBuf d_sp_lists_, d_sp_X_, d_sp_has_, d_sp_counts_, d_sp_kept_, d_sp_koff_, d_sp_cnt_, d_sp_off_, d_sp_si_, d_sp_sj_, d_sp_sk_, d_sp_sq_;
-  DevBuf d_sl_seq_, d_sl_i_, d_sl_j_, d_sl_k_, d_sl_q_;
-  int64_t n_stem_ = -1;
+  // stem profiles: the transitions by slot, Q of the table slots, the parse marks and counts of the call
+  DevBuf d_sp_lists_, d_sp_X_, d_sp_has_, d_sp_counts_;
   DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
   // node MEA: the chain lists, the backpointer scratch (M bytes per position), the rows, sites per sequence, start / end / score / confidence per slot
   DevBuf d_nm_lists_, d_nm_bp_, d_nm_node_, d_nm_ns_, d_nm_s0_, d_nm_s1_, d_nm_sc_, d_nm_cf_;
@@ -986,9 +987,9 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   require_device();
   DeviceGuard dg(device_);
   n_seq_ = 0;
-  n_pairs_ = -1;
-  n_cond_ = -1;
-  n_stem_ = -1;
+  pairs_.invalidate();
+  conds_.invalidate();
+  stems_.invalidate();
   streaming_ = false;
   train_rows_ = false;
   BatchShape shape = check_batch(seq, off, qual, qoff, fix, n);
@@ -2145,8 +2146,18 @@ void Engine::require_resident(const char* what, int n_param_in) {
 
 // Sequences per launch of the log-space form of a call with per-slot scratch: what the table slots hold behind the sum passes,
 // else (pipeline 3) what the scratch of the call is sized for.
-int Engine::log_chunk(bool sums_on_batch, int n_blocks, int n_log) const {
-  return std::min(n_log, sums_on_batch ? slots_.n() : std::max(n_blocks, 1024));
+int Engine::log_chunk(int n_blocks, int n_log) const {
+  return std::min(n_log, opt_pipeline_ == 4 ? slots_.n() : std::max(n_blocks, 1024));
+}
+
+// The per-slot scratch of a scan-family call: `stride` elements of T per slot in b, one slot per table slot behind prepare_scan
+// (slots_.n(), known in the fill of scan_sums at the earliest), one per sequence of a log_chunk under pipeline 3 -- the one sizing
+// rule, scratch_slots_, which scan_sums and scan_log_form set.  Returns the scratch of slot slot0.  A call sizes its scratch in its
+// fill, before anything is queued, by pointing its argument record at slot 0; the same request again keeps the buffer
+// (DevBuf::alloc), so a group asks with its own slot0.
+template <class T> T* Engine::slot_scratch(DevBuf& b, size_t stride, size_t slot0) {
+  b.alloc(sizeof(T) * stride * std::max<size_t>(scratch_slots_, 1));
+  return b.as<T>() + slot0 * stride;
 }
 
 // The pair reduction's arguments (pair_posteriors, context_profile).  pair_batch_args: its view of the batch -- plan, mask and rows --
@@ -2186,6 +2197,7 @@ template <class Fill, class Group>
 int Engine::scan_sums(const ScanPos& pos, Fill fill, Group group, std::vector<int32_t>* flagged) {
   LinArgs a;
   const int gsz = prepare_scan(a, pos);
+  scratch_slots_ = (size_t)slots_.n();
   fill(a);
   const int ns = group_streams(n_seq_ >= 128 && slots_.n() >= 128);
   sweep_groups(a, n_seq_, h_order_.data(), d_order_.as<int32_t>(), d_plans_sorted_.as<SeqPlan>(), gsz, ns, group);
@@ -2206,6 +2218,7 @@ void Engine::scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind 
   if (n_log > 0) {
     int n_blocks;
     DpArgs d = log_scan_args(sums_on_batch, &n_blocks);
+    if (!sums_on_batch) scratch_slots_ = (size_t)log_chunk(n_blocks, n_log);
     const int chunk = fill(d, n_blocks, n_log);
     const int32_t* list = sums_on_batch ? d_flagged_.as<int32_t>() + 1 : d_order_.as<int32_t>();
     for (int c0 = 0; c0 < n_log; c0 += chunk) {
@@ -2218,6 +2231,38 @@ void Engine::scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind 
     }
   }
   if (!sums_on_batch) slots_.set_holds(TableSlots::Holds::Trace);   // the slots of log_scan_args are not reused by the train pipelines
+}
+
+// Both forms of a scan-family call, queued behind ev_[1]: the sum passes on the batch under pipeline 4 (scan_sums: fill, group),
+// then the log-space form for what they flagged, or for the whole batch otherwise (scan_log_form: log_fill, behind).  Returns the
+// number of sequences the range check flagged.
+template <class Fill, class Group, class LogFill, class Behind>
+int Engine::scan_both_forms(const ScanPos& pos, Fill fill, Group group, LogFill log_fill, Behind behind) {
+  const bool sums_on_batch = opt_pipeline_ == 4;
+  const int n_flagged = sums_on_batch ? scan_sums(pos, fill, group) : 0;
+  scan_log_form(sums_on_batch, n_flagged, log_fill, behind);
+  return n_flagged;
+}
+
+// The end of a scan-family call and its times (elemdp_last_timing): ev_[1] .. ev_[2] is the whole call, ev_[1] .. ev_[3] its
+// kernels.  copy_out() queues on st_ what the call counts as its way out -- asynchronous copies to the host, the scatter of a list
+// -- between ev_[3] and ev_[2].  Without one (scan, sample_structures) there is no ev_[3] and both times are the same; what such a
+// call hands out it fetches with blocking copies behind this, outside the timed window.
+void Engine::finish_call(int n_flagged) {
+  HIP_OK(hipEventRecord(ev_[2], st_));
+  HIP_OK(hipStreamSynchronize(st_));
+  float ms = 0;
+  HIP_OK(hipEventElapsedTime(&ms, ev_[1], ev_[2]));
+  last_ms[0] = last_ms[1] = ms;
+  last_ms[2] = (double)n_flagged;
+}
+template <class Copy> void Engine::finish_call(int n_flagged, Copy copy_out) {
+  HIP_OK(hipEventRecord(ev_[3], st_));
+  copy_out();
+  finish_call(n_flagged);
+  float ms_dp = 0;
+  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
+  last_ms[1] = ms_dp;
 }
 
 void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
@@ -2277,12 +2322,7 @@ void Engine::scan(const double* x, int n_param_in, elemdp_scan_out* out) {
   // for pipeline != 4
   scan_log_form(sums_on_batch, (int)flagged.size(), [&](DpArgs& d, int, int n_log) { scan_fields(d); return n_log; },
                 [](const int32_t*, int) {});
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, ev_[1], ev_[2]));
-  last_ms[0] = last_ms[1] = ms;
-  last_ms[2] = (double)flagged.size();
+  finish_call((int)flagged.size());
   auto get = [&](void* dst, const DevBuf& src, size_t bytes) { if (dst) HIP_OK(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost)); };
   get(out->start, pos.start, 8 * n_seqpos);
   get(out->inner, pos.inner, 8 * n_seqpos);
@@ -2320,44 +2360,30 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
   if (!n_pairs) throw ArgError("pair_posteriors: null n_pairs");
   if (!(min_prob >= 0.)) throw ArgError("pair_posteriors: min_prob must be >= 0");
   if (mea && !(std::isfinite(mea->gamma) && mea->gamma > 0.)) throw ArgError("pair_mea: gamma must be finite and > 0");
-  n_pairs_ = -1;
-  if (streaming_) { stream_pairs(x, n_param_in, min_prob, unpaired, mea); *n_pairs = n_pairs_; return; }
+  pairs_.invalidate();
+  if (streaming_) { stream_pairs(x, n_param_in, min_prob, unpaired, mea); *n_pairs = pairs_.count(); return; }
   require_resident("pair_posteriors", n_param_in);
   upload_params(x, lay_, false);
   const int n = n_seq_;
   const size_t n_seqpos = (size_t)h_seq_off_[n];
   const size_t pcells = (size_t)(Lmax_ + 1) * (Wmax_ + 1);   // P(i, d) of one table slot
   ScanPos pos(n_seqpos, n);
-  d_pr_kept_.alloc(8 * (size_t)n); d_pr_koff_.alloc(8 * ((size_t)n + 1));
-  d_pr_cnt_.alloc(8 * (size_t)n); d_pr_off_.alloc(8 * ((size_t)n + 1));
   d_pr_unp_.alloc(8 * n_seqpos);
   HIP_OK(hipEventRecord(ev_[1], st_));
-  // staging ranges: a sequence's list holds at most its kept pairs
-  HIP_OK(launch_pair_kept(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, d_pr_kept_.as<int64_t>(), st_));
-  HIP_OK(launch_pair_prefix(d_pr_kept_.as<int64_t>(), n, d_pr_koff_.as<int64_t>(), st_));
-  int64_t n_kept = 0;
-  HIP_OK(hipMemcpyAsync(&n_kept, d_pr_koff_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  d_pr_si_.alloc(4 * (size_t)n_kept); d_pr_sj_.alloc(4 * (size_t)n_kept); d_pr_sp_.alloc(8 * (size_t)n_kept);
-  HIP_OK(hipMemsetAsync(d_pr_cnt_.as<void>(), 0, 8 * (size_t)n, st_));
+  const StagedList::Staging sl = pairs_.begin(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, 1, st_);
   PairArgs pa = pair_batch_args();
   pa.p_stride = pcells;
   pa.min_prob = min_prob;
   pa.unpaired = d_pr_unp_.as<double>();
-  pa.koff = d_pr_koff_.as<int64_t>(); pa.cnt = d_pr_cnt_.as<int64_t>();
-  pa.st_i = d_pr_si_.as<int32_t>(); pa.st_j = d_pr_sj_.as<int32_t>(); pa.st_p = d_pr_sp_.as<double>();
-  // MEA: the M table and the choices of a slot next to its P(i, d); the chain's choices after the table's (L+1)(W+1)
+  pa.koff = sl.koff; pa.cnt = sl.cnt;
+  pa.st_i = sl.st_i; pa.st_j = sl.st_j; pa.st_p = sl.st_v[0];
+  // per slot: P(i, d); MEA: the M table and the choices next to it, the chain's choices after the table's (L+1)(W+1)
   const size_t mea_ch_stride = pcells + (size_t)Lmax_ + 1;
-  auto mea_scratch = [&](size_t slots) {
+  auto at_slot = [&](PairArgs& pk, size_t slot0) {
+    pk.P = slot_scratch<double>(d_pr_P_, pcells, slot0);
     if (!mea) return;
-    d_mea_M_.alloc(8 * pcells * slots);
-    d_mea_ch_.alloc(4 * mea_ch_stride * slots);
-  };
-  auto launch_mea = [&](PairArgs pk, size_t slot0, int G, hipStream_t st) {
-    if (!mea) return;
-    pk.mea_M = d_mea_M_.as<double>() + slot0 * pcells;
-    pk.mea_ch = d_mea_ch_.as<int32_t>() + slot0 * mea_ch_stride;
-    HIP_OK(launch_pair_mea(pk, G, Wmax_, st));
+    pk.mea_M = slot_scratch<double>(d_mea_M_, pcells, slot0);
+    pk.mea_ch = slot_scratch<int32_t>(d_mea_ch_, mea_ch_stride, slot0);
   };
   if (mea) {
     d_mea_s_.alloc(n_seqpos); d_mea_sc_.alloc(8 * (size_t)n);
@@ -2365,93 +2391,55 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
     pa.mea_ch_stride = mea_ch_stride;
     pa.mea_s = d_mea_s_.as<char>(); pa.mea_score = d_mea_sc_.as<double>();
   }
-  int n_flagged = 0;
-  const bool sums_on_batch = opt_pipeline_ == 4;
-  if (sums_on_batch)
-    n_flagged = scan_sums(pos, [&](LinArgs& a) {
-      d_pr_P_.alloc(8 * pcells * (size_t)slots_.n());
-      mea_scratch((size_t)slots_.n());
-      pair_plane_fields(pa, a);
-    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
-      PairArgs pk = pa;
-      pk.idx = ak.grp;
-      pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
-      pk.P = d_pr_P_.as<double>() + slot0 * pcells;
-      HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
-      HIP_OK(launch_pair_seq(pk, G, st));
-      launch_mea(pk, slot0, G, st);
-    });
+  const int n_flagged = scan_both_forms(pos, [&](LinArgs& a) {
+    at_slot(pa, 0);
+    pair_plane_fields(pa, a);
+  }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    PairArgs pk = pa;
+    pk.idx = ak.grp;
+    pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+    at_slot(pk, slot0);
+    HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
+    HIP_OK(launch_pair_seq(pk, G, st));
+    if (mea) HIP_OK(launch_pair_mea(pk, G, Wmax_, st));
+  },
   // ---- the log-space form, in chunks of at most as many sequences as the table slots hold (the P scratch is bounded by the chunk)
-  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
-    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
-    if (!sums_on_batch) { d_pr_P_.alloc(8 * pcells * (size_t)chunk); mea_scratch((size_t)chunk); }
-    d.pair_p = d_pr_P_.as<double>();
+  [&](DpArgs& d, int n_blocks, int n_log) {
+    at_slot(pa, 0);
+    d.pair_p = pa.P;
     d.pair_stride = pcells;
-    return chunk;
+    return log_chunk(n_blocks, n_log);
   }, [&](const int32_t* idx, int C) {
     PairArgs pk = pa;
     pk.idx = idx;
-    pk.P = d_pr_P_.as<double>();
     pk.skip_flagged = 0;
     HIP_OK(launch_pair_seq(pk, C, st_));
-    launch_mea(pk, 0, C, st_);
+    if (mea) HIP_OK(launch_pair_mea(pk, C, Wmax_, st_));
   });
-  HIP_OK(hipEventRecord(ev_[3], st_));
-  // ---- the list in (sequence, i, j) order
-  HIP_OK(launch_pair_prefix(d_pr_cnt_.as<int64_t>(), n, d_pr_off_.as<int64_t>(), st_));
-  int64_t total = 0;
-  HIP_OK(hipMemcpyAsync(&total, d_pr_off_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  d_pl_seq_.alloc(4 * (size_t)total); d_pl_i_.alloc(4 * (size_t)total); d_pl_j_.alloc(4 * (size_t)total); d_pl_p_.alloc(8 * (size_t)total);
-  HIP_OK(launch_pair_scatter(d_pr_koff_.as<int64_t>(), d_pr_cnt_.as<int64_t>(), d_pr_off_.as<int64_t>(), d_pr_si_.as<int32_t>(),
-                             d_pr_sj_.as<int32_t>(), d_pr_sp_.as<double>(), n, d_pl_seq_.as<int32_t>(), d_pl_i_.as<int32_t>(),
-                             d_pl_j_.as<int32_t>(), d_pl_p_.as<double>(), st_));
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  float ms_all = 0, ms_dp = 0;
-  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
-  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
-  last_ms[0] = ms_all;
-  last_ms[1] = ms_dp;
-  last_ms[2] = (double)n_flagged;
+  finish_call(n_flagged, [&] { *n_pairs = pairs_.finish(st_); });   // the list in (sequence, i, j) order
   if (unpaired) HIP_OK(hipMemcpy(unpaired, d_pr_unp_.as<void>(), 8 * n_seqpos, hipMemcpyDeviceToHost));
   if (mea && mea->structure) HIP_OK(hipMemcpy(mea->structure, d_mea_s_.as<void>(), n_seqpos, hipMemcpyDeviceToHost));
   if (mea && mea->score) HIP_OK(hipMemcpy(mea->score, d_mea_sc_.as<void>(), 8 * (size_t)n, hipMemcpyDeviceToHost));
-  n_pairs_ = total;
-  *n_pairs = total;
 }
 
 void Engine::stream_pairs(const double* x, int n_param_in, double min_prob, double* unpaired, const MeaOut* mea) {
-  std::vector<int32_t> hs, hi, hj;
-  std::vector<double> hp;
+  StagedList::Host list;
   stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
     int64_t m = 0;
     const int64_t at = h_seq_off_[c0] - h_seq_off_[0];   // (the chunk's first position)
     MeaOut mc;
     if (mea) mc = MeaOut{mea->gamma, mea->structure ? mea->structure + at : nullptr, mea->score ? mea->score + c0 : nullptr};
     e.pair_posteriors(x, n_param_in, min_prob, &m, unpaired ? unpaired + at : nullptr, mea ? &mc : nullptr);
-    const size_t b = hs.size();
-    hs.resize(b + m); hi.resize(b + m); hj.resize(b + m); hp.resize(b + m);
-    e.pair_list(hs.data() + b, hi.data() + b, hj.data() + b, hp.data() + b, m);
-    for (size_t t = b; t < hs.size(); ++t) hs[t] += c0;   // (batch-global sequence indices)
+    list.append(e.pairs_, c0);
   });
-  d_pl_seq_.upload(hs, st_); d_pl_i_.upload(hi, st_); d_pl_j_.upload(hj, st_); d_pl_p_.upload(hp, st_);
-  HIP_OK(hipStreamSynchronize(st_));
-  n_pairs_ = (int64_t)hs.size();
+  pairs_.adopt(list, st_);
 }
 
 void Engine::pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {
   require_device();
   DeviceGuard dg(device_);
-  if (n_pairs_ < 0) throw StateError("pair_list before pair_posteriors");
-  if (cap < n_pairs_) throw ArgError("pair_list: buffer too small");
-  const size_t m = (size_t)n_pairs_;
-  if (m == 0) return;
-  if (seq) HIP_OK(hipMemcpy(seq, d_pl_seq_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (i) HIP_OK(hipMemcpy(i, d_pl_i_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (j) HIP_OK(hipMemcpy(j, d_pl_j_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (p) HIP_OK(hipMemcpy(p, d_pl_p_.as<void>(), 8 * m, hipMemcpyDeviceToHost));
+  pairs_.fetch(seq, i, j, p, nullptr, nullptr, cap);
 }
 
 
@@ -2469,28 +2457,18 @@ void Engine::pair_conditional(const double* x, int n_param_in, double min_prob, 
   if (!(min_prob >= 0.)) throw ArgError("pair_conditional: min_prob must be >= 0");
   const bool mea = out.structure[0] || out.structure[1];
   if (mea && !(std::isfinite(out.gamma) && out.gamma > 0.)) throw ArgError("pair_conditional: gamma must be finite and > 0");
-  if (streaming_) { stream_cond(x, n_param_in, min_prob, out); *n_pairs = n_cond_; return; }
+  if (streaming_) { stream_cond(x, n_param_in, min_prob, out); *n_pairs = conds_.count(); return; }
   require_resident("pair_conditional", n_param_in);
-  n_cond_ = -1;
+  conds_.invalidate();
   upload_params(x, lay_, false);
   const int n = n_seq_;
   const size_t n_seqpos = (size_t)h_seq_off_[n];
   const size_t pcells = (size_t)(Lmax_ + 1) * (Wmax_ + 1);   // P(i, d) of one world of one table slot
   ScanPos pos(n_seqpos, n);
-  d_cd_kept_.alloc(8 * (size_t)n); d_cd_koff_.alloc(8 * ((size_t)n + 1));
-  d_cd_cnt_.alloc(8 * (size_t)n); d_cd_off_.alloc(8 * ((size_t)n + 1));
   d_cd_unp_[0].alloc(8 * n_seqpos); d_cd_unp_[1].alloc(8 * n_seqpos);
   d_cd_exist_.alloc(8 * (size_t)n); d_cd_shift_.alloc(8 * (size_t)n);
   HIP_OK(hipEventRecord(ev_[1], st_));
-  // staging ranges: a sequence's list holds at most its kept pairs
-  HIP_OK(launch_pair_kept(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, d_cd_kept_.as<int64_t>(), st_));
-  HIP_OK(launch_pair_prefix(d_cd_kept_.as<int64_t>(), n, d_cd_koff_.as<int64_t>(), st_));
-  int64_t n_kept = 0;
-  HIP_OK(hipMemcpyAsync(&n_kept, d_cd_koff_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  d_cd_si_.alloc(4 * (size_t)n_kept); d_cd_sj_.alloc(4 * (size_t)n_kept);
-  d_cd_sp_[0].alloc(8 * (size_t)n_kept); d_cd_sp_[1].alloc(8 * (size_t)n_kept);
-  HIP_OK(hipMemsetAsync(d_cd_cnt_.as<void>(), 0, 8 * (size_t)n, st_));
+  const StagedList::Staging sl = conds_.begin(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, 1, st_);
   CondArgs ca;
   std::memset(&ca, 0, sizeof(ca));
   ca.plans = plan_.d_plans.as<SeqPlan>();
@@ -2500,22 +2478,16 @@ void Engine::pair_conditional(const double* x, int n_param_in, double min_prob, 
   ca.min_prob = min_prob;
   ca.unpaired[0] = d_cd_unp_[0].as<double>(); ca.unpaired[1] = d_cd_unp_[1].as<double>();
   ca.exist = d_cd_exist_.as<double>(); ca.shift = d_cd_shift_.as<double>();
-  ca.koff = d_cd_koff_.as<int64_t>(); ca.cnt = d_cd_cnt_.as<int64_t>();
-  ca.st_i = d_cd_si_.as<int32_t>(); ca.st_j = d_cd_sj_.as<int32_t>();
-  ca.st_p[0] = d_cd_sp_[0].as<double>(); ca.st_p[1] = d_cd_sp_[1].as<double>();
-  // the scratch per slot: P of world 0 of every slot, then P of world 1; MEA: the M table and the choices next to them
+  ca.koff = sl.koff; ca.cnt = sl.cnt;
+  ca.st_i = sl.st_i; ca.st_j = sl.st_j;
+  ca.st_p[0] = sl.st_v[0]; ca.st_p[1] = sl.st_v[1];
+  // the scratch per slot: P of either world; MEA: the M table and the choices, which the two decodes of a slot share
   const size_t mea_ch_stride = pcells + (size_t)Lmax_ + 1;
-  size_t n_slot = 0;
-  auto scratch = [&](size_t slots) {
-    n_slot = slots;
-    d_cd_P_.alloc(8 * 2 * pcells * slots);
+  auto at_slot = [&](CondArgs& ck, PairArgs& pk, size_t slot0) {
+    for (int w = 0; w < 2; ++w) ck.P[w] = slot_scratch<double>(d_cd_P_[w], pcells, slot0);
     if (!mea) return;
-    d_cd_M_.alloc(8 * pcells * slots);
-    d_cd_ch_.alloc(4 * mea_ch_stride * slots);
-  };
-  auto at_slot = [&](CondArgs& ck, size_t slot0) {
-    ck.P[0] = d_cd_P_.as<double>() + slot0 * pcells;
-    ck.P[1] = d_cd_P_.as<double>() + (n_slot + slot0) * pcells;
+    pk.mea_M = slot_scratch<double>(d_cd_M_, pcells, slot0);
+    pk.mea_ch = slot_scratch<int32_t>(d_cd_ch_, mea_ch_stride, slot0);
   };
   // the MEA decode of both worlds: the pair call's kernel over the world's P and unpaired (the scores are not handed out)
   PairArgs pm = pair_batch_args();
@@ -2525,52 +2497,47 @@ void Engine::pair_conditional(const double* x, int n_param_in, double min_prob, 
     pm.mea_gamma2 = 2. * out.gamma;
     pm.mea_ch_stride = mea_ch_stride;
   }
-  auto launch_mea = [&](const CondArgs& ck, int skip_flagged, size_t slot0, int G, hipStream_t st) {
+  auto launch_mea = [&](const CondArgs& ck, PairArgs pk, int G, hipStream_t st) {
     if (!mea) return;
     for (int w = 0; w < 2; ++w) {
       if (!out.structure[w]) continue;
-      PairArgs pk = pm;
       pk.idx = ck.idx;
-      pk.skip_flagged = skip_flagged;
+      pk.skip_flagged = ck.skip_flagged;
       pk.P = ck.P[w];
       pk.unpaired = ck.unpaired[w];
-      pk.mea_M = d_cd_M_.as<double>() + slot0 * pcells;
-      pk.mea_ch = d_cd_ch_.as<int32_t>() + slot0 * mea_ch_stride;
       pk.mea_s = d_cd_s_[w].as<char>(); pk.mea_score = d_cd_sc_.as<double>() + (size_t)w * n;
       HIP_OK(launch_pair_mea(pk, G, Wmax_, st));
     }
   };
-  int n_flagged = 0;
-  const bool sums_on_batch = opt_pipeline_ == 4;
-  if (sums_on_batch)
-    n_flagged = scan_sums(pos, [&](LinArgs& a) {
-      scratch((size_t)slots_.n());
-      a.range_all = 1;
-      PairArgs pp = pair_batch_args();
-      pair_plane_fields(pp, a);
-      ca.p_cs = pp.p_cs; ca.p_rs = pp.p_rs; ca.ncol = pp.ncol; ca.band_stride = pp.band_stride;
-      ca.skip_flagged = 1;
-    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      CondArgs ck = ca;
-      ck.idx = ak.grp;
-      ck.band_in = ak.band_in; ck.band_out = ak.band_out; ck.z = ak.zs; ck.z_log = 0;
-      at_slot(ck, slot0);
-      const int cells = (Lg + 1) * (Wg + 1);
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_INSIDE, st));
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_OUT_ARI, st));
-      HIP_OK(launch_cond_cells(ck, COND_MOTIF, G, cells, st));
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_OUT_NASI, st));   // (into the same outside slot)
-      HIP_OK(launch_cond_cells(ck, COND_NONE, G, cells, st));
-      HIP_OK(launch_cond_seq(ck, G, st));
-      launch_mea(ck, 1, slot0, G, st);
-    });
+  const int n_flagged = scan_both_forms(pos, [&](LinArgs& a) {
+    at_slot(ca, pm, 0);
+    a.range_all = 1;
+    PairArgs pp = pair_batch_args();
+    pair_plane_fields(pp, a);
+    ca.p_cs = pp.p_cs; ca.p_rs = pp.p_rs; ca.ncol = pp.ncol; ca.band_stride = pp.band_stride;
+    ca.skip_flagged = 1;
+  }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+    CondArgs ck = ca;
+    PairArgs pk = pm;
+    ck.idx = ak.grp;
+    ck.band_in = ak.band_in; ck.band_out = ak.band_out; ck.z = ak.zs; ck.z_log = 0;
+    at_slot(ck, pk, slot0);
+    const int cells = (Lg + 1) * (Wg + 1);
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_INSIDE, st));
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_OUT_ARI, st));
+    HIP_OK(launch_cond_cells(ck, COND_MOTIF, G, cells, st));
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_OUT_NASI, st));   // (into the same outside slot)
+    HIP_OK(launch_cond_cells(ck, COND_NONE, G, cells, st));
+    HIP_OK(launch_cond_seq(ck, G, st));
+    launch_mea(ck, pk, G, st);
+  },
   // ---- the log-space form, in chunks of at most as many sequences as the scratch holds
-  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
-    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
-    if (!sums_on_batch) scratch((size_t)chunk);
+  [&](DpArgs& d, int n_blocks, int n_log) {
+    const int chunk = log_chunk(n_blocks, n_log);
+    at_slot(ca, pm, 0);
     d_cd_z_.alloc(8 * 4 * (size_t)chunk);
-    d.cond_p0 = d_cd_P_.as<double>();
-    d.cond_p1 = d_cd_P_.as<double>() + n_slot * pcells;
+    d.cond_p0 = ca.P[0];
+    d.cond_p1 = ca.P[1];
     d.cond_z = d_cd_z_.as<double>();
     d.pair_stride = pcells;
     return chunk;
@@ -2579,29 +2546,10 @@ void Engine::pair_conditional(const double* x, int n_param_in, double min_prob, 
     ck.idx = idx;
     ck.skip_flagged = 0;
     ck.z = d_cd_z_.as<double>(); ck.z_log = 1;
-    at_slot(ck, 0);
     HIP_OK(launch_cond_seq(ck, C, st_));
-    launch_mea(ck, 0, 0, C, st_);
+    launch_mea(ck, pm, C, st_);
   });
-  HIP_OK(hipEventRecord(ev_[3], st_));
-  // ---- the list in (sequence, i, j) order
-  HIP_OK(launch_pair_prefix(d_cd_cnt_.as<int64_t>(), n, d_cd_off_.as<int64_t>(), st_));
-  int64_t total = 0;
-  HIP_OK(hipMemcpyAsync(&total, d_cd_off_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  d_cl_seq_.alloc(4 * (size_t)total); d_cl_i_.alloc(4 * (size_t)total); d_cl_j_.alloc(4 * (size_t)total);
-  d_cl_p_[0].alloc(8 * (size_t)total); d_cl_p_[1].alloc(8 * (size_t)total);
-  HIP_OK(launch_cond_scatter(d_cd_koff_.as<int64_t>(), d_cd_cnt_.as<int64_t>(), d_cd_off_.as<int64_t>(), d_cd_si_.as<int32_t>(),
-                             d_cd_sj_.as<int32_t>(), d_cd_sp_[0].as<double>(), d_cd_sp_[1].as<double>(), n, d_cl_seq_.as<int32_t>(),
-                             d_cl_i_.as<int32_t>(), d_cl_j_.as<int32_t>(), d_cl_p_[0].as<double>(), d_cl_p_[1].as<double>(), st_));
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  float ms_all = 0, ms_dp = 0;
-  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
-  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
-  last_ms[0] = ms_all;
-  last_ms[1] = ms_dp;
-  last_ms[2] = (double)n_flagged;
+  finish_call(n_flagged, [&] { *n_pairs = conds_.finish(st_); });   // the list in (sequence, i, j) order
   auto get = [&](void* dst, const DevBuf& src, size_t bytes) { if (dst && bytes) HIP_OK(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost)); };
   get(out.exist, d_cd_exist_, 8 * (size_t)n);
   get(out.shift, d_cd_shift_, 8 * (size_t)n);
@@ -2609,14 +2557,11 @@ void Engine::pair_conditional(const double* x, int n_param_in, double min_prob, 
     get(out.unpaired[w], d_cd_unp_[w], 8 * n_seqpos);
     if (mea) get(out.structure[w], d_cd_s_[w], n_seqpos);
   }
-  n_cond_ = total;
-  *n_pairs = total;
 }
 
 void Engine::stream_cond(const double* x, int n_param_in, double min_prob, const CondOut& out) {
-  std::vector<int32_t> hs, hi, hj;
-  std::vector<double> hp[2];
-  n_cond_ = -1;
+  StagedList::Host list;
+  conds_.invalidate();
   stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
     int64_t m = 0;
     const int64_t at = h_seq_off_[c0] - h_seq_off_[0];   // (the chunk's first position)
@@ -2625,29 +2570,15 @@ void Engine::stream_cond(const double* x, int n_param_in, double min_prob, const
                {out.structure[0] ? out.structure[0] + at : nullptr, out.structure[1] ? out.structure[1] + at : nullptr},
                out.shift ? out.shift + c0 : nullptr};
     e.pair_conditional(x, n_param_in, min_prob, &m, oc);
-    const size_t b = hs.size();
-    hs.resize(b + m); hi.resize(b + m); hj.resize(b + m); hp[0].resize(b + m); hp[1].resize(b + m);
-    e.cond_list(hs.data() + b, hi.data() + b, hj.data() + b, hp[0].data() + b, hp[1].data() + b, m);
-    for (size_t t = b; t < hs.size(); ++t) hs[t] += c0;   // (batch-global sequence indices)
+    list.append(e.conds_, c0);
   });
-  d_cl_seq_.upload(hs, st_); d_cl_i_.upload(hi, st_); d_cl_j_.upload(hj, st_);
-  d_cl_p_[0].upload(hp[0], st_); d_cl_p_[1].upload(hp[1], st_);
-  HIP_OK(hipStreamSynchronize(st_));
-  n_cond_ = (int64_t)hs.size();
+  conds_.adopt(list, st_);
 }
 
 void Engine::cond_list(int32_t* seq, int32_t* i, int32_t* j, double* p_motif, double* p_none, int64_t cap) {
   require_device();
   DeviceGuard dg(device_);
-  if (n_cond_ < 0) throw StateError("pair_conditional_list before pair_conditional");
-  if (cap < n_cond_) throw ArgError("pair_conditional_list: buffer too small");
-  const size_t m = (size_t)n_cond_;
-  if (m == 0) return;
-  if (seq) HIP_OK(hipMemcpy(seq, d_cl_seq_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (i) HIP_OK(hipMemcpy(i, d_cl_i_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (j) HIP_OK(hipMemcpy(j, d_cl_j_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (p_motif) HIP_OK(hipMemcpy(p_motif, d_cl_p_[0].as<void>(), 8 * m, hipMemcpyDeviceToHost));
-  if (p_none) HIP_OK(hipMemcpy(p_none, d_cl_p_[1].as<void>(), 8 * m, hipMemcpyDeviceToHost));
+  conds_.fetch(seq, i, j, p_motif, p_none, nullptr, cap);
 }
 
 
@@ -2683,64 +2614,47 @@ void Engine::context_profile(const double* x, int n_param_in, double* profile) {
   ca.o_stride = ocol;
   ca.profile = d_cx_prof_.as<double>();
   ca.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
-  auto scratch = [&](size_t slots) {
-    d_cx_cells_.alloc(8 * 4 * pcells * slots);
-    d_cx_o_.alloc(8 * ocol * slots);
-  };
   auto at_slot = [&](CtxArgs& ck, size_t slot0) {
-    ck.P = d_cx_cells_.as<double>() + slot0 * 4 * pcells;
+    ck.P = slot_scratch<double>(d_cx_cells_, 4 * pcells, slot0);
     ck.u = ck.P + pcells; ck.h = ck.P + 2 * pcells; ck.b = ck.P + 3 * pcells;
-    ck.o = d_cx_o_.as<double>() + slot0 * ocol;
+    ck.o = slot_scratch<double>(d_cx_o_, ocol, slot0);
   };
   PairArgs pa = pair_batch_args();
   pa.p_stride = 4 * pcells;
-  int n_flagged = 0;
-  const bool sums_on_batch = opt_pipeline_ == 4;
-  if (sums_on_batch)
-    n_flagged = scan_sums(pos, [&](LinArgs& a) {
-      scratch((size_t)slots_.n());
-      pair_plane_fields(pa, a);
-      ca.skip_flagged = 1;
-    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
-      CtxArgs ck = ca;
-      ck.idx = ak.grp;
-      at_slot(ck, slot0);
-      if (!ca.no_rss) {
-        PairArgs pk = pa;
-        pk.idx = ak.grp;
-        pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
-        pk.P = ck.P;
-        HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
-        HIP_OK(launch_ctx_cells(ak, ck, G, (Lg + 1) * (Wg + 1), st));
-      }
-      HIP_OK(launch_ctx_seq(ck, G, st));
-    });
+  const int n_flagged = scan_both_forms(pos, [&](LinArgs& a) {
+    at_slot(ca, 0);
+    pair_plane_fields(pa, a);
+    ca.skip_flagged = 1;
+  }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    CtxArgs ck = ca;
+    ck.idx = ak.grp;
+    at_slot(ck, slot0);
+    if (!ca.no_rss) {
+      PairArgs pk = pa;
+      pk.idx = ak.grp;
+      pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+      pk.P = ck.P;
+      HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
+      HIP_OK(launch_ctx_cells(ak, ck, G, (Lg + 1) * (Wg + 1), st));
+    }
+    HIP_OK(launch_ctx_seq(ck, G, st));
+  },
   // ---- the log-space form, in chunks of at most as many sequences as the scratch holds
-  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
-    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
-    if (!sums_on_batch) scratch((size_t)chunk);
+  [&](DpArgs& d, int n_blocks, int n_log) {
+    at_slot(ca, 0);
     d.ctx = ca;
-    at_slot(d.ctx, 0);
-    return chunk;
+    return log_chunk(n_blocks, n_log);
   }, [&](const int32_t* idx, int C) {
     CtxArgs ck = ca;
     ck.idx = idx;
     ck.skip_flagged = 0;
-    at_slot(ck, 0);
     HIP_OK(launch_ctx_seq(ck, C, st_));
   });
-  HIP_OK(hipEventRecord(ev_[3], st_));
   // (the whole call includes the profile's way to the host: 7 doubles per position, 112 MB for 10 000 sequences of L = 200)
-  if (n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_cx_prof_.as<void>(), 8 * kCtxCols * n_seqpos, hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  float ms_all = 0, ms_dp = 0;
-  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
-  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
-  last_ms[0] = ms_all;
-  last_ms[1] = ms_dp;
-  last_ms[2] = (double)n_flagged;
+  finish_call(n_flagged, [&] {
+    if (n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_cx_prof_.as<void>(), 8 * kCtxCols * n_seqpos, hipMemcpyDeviceToHost, st_));
+  });
 }
 
 
@@ -2778,50 +2692,37 @@ void Engine::accessibility(const double* x, int n_param_in, int max_width, doubl
   ca.plane = plane; ca.t_stride = ACC_TERMS * plane;
   ca.access = d_ac_out_.as<double>();
   ca.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
-  auto scratch = [&](size_t slots) { d_ac_T_.alloc(8 * ACC_TERMS * plane * std::max<size_t>(slots, 1)); };
-  auto at_slot = [&](AccessArgs& ck, size_t slot0) { ck.T = d_ac_T_.as<double>() + slot0 * ACC_TERMS * plane; };
-  int n_flagged = 0, n_vec = 0;
-  const bool sums_on_batch = opt_pipeline_ == 4;
-  if (sums_on_batch)
-    n_flagged = scan_sums(pos, [&](LinArgs& a) {
-      scratch((size_t)slots_.n());
-      n_vec = std::max(a.lay.S, a.lay.n_ap);   // (entries of a state vector: the interval states, the pairs of rule 2)
-      ca.skip_flagged = 1;
-    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
-      AccessArgs ck = ca;
-      ck.idx = ak.grp;
-      at_slot(ck, slot0);
-      if (!ca.no_rss) HIP_OK(launch_access_chains(ak, ck, G, Lg, n_vec, st));
-      HIP_OK(launch_access_seq(ck, G, st));
-    });
+  auto at_slot = [&](AccessArgs& ck, size_t slot0) { ck.T = slot_scratch<double>(d_ac_T_, ACC_TERMS * plane, slot0); };
+  int n_vec = 0;
+  const int n_flagged = scan_both_forms(pos, [&](LinArgs& a) {
+    at_slot(ca, 0);
+    n_vec = std::max(a.lay.S, a.lay.n_ap);   // (entries of a state vector: the interval states, the pairs of rule 2)
+    ca.skip_flagged = 1;
+  }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    AccessArgs ck = ca;
+    ck.idx = ak.grp;
+    at_slot(ck, slot0);
+    if (!ca.no_rss) HIP_OK(launch_access_chains(ak, ck, G, Lg, n_vec, st));
+    HIP_OK(launch_access_seq(ck, G, st));
+  },
   // ---- the log-space form, in chunks of at most as many sequences as the scratch holds
-  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
-    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
-    if (!sums_on_batch) scratch((size_t)chunk);
+  [&](DpArgs& d, int n_blocks, int n_log) {
+    at_slot(ca, 0);
     // (a launch has at most n_blocks workgroups, each with 64 lanes on units: 2 S doubles per lane, 22 KB per workgroup at S = 22)
     d_ac_vec_.alloc(8 * 2 * (size_t)d.lay.S * 64 * (size_t)std::max(n_blocks, 1));
     d.acc = ca;
     d.acc.vec = d_ac_vec_.as<double>();
-    at_slot(d.acc, 0);
-    return chunk;
+    return log_chunk(n_blocks, n_log);
   }, [&](const int32_t* idx, int C) {
     AccessArgs ck = ca;
     ck.idx = idx;
     ck.skip_flagged = 0;
-    at_slot(ck, 0);
     HIP_OK(launch_access_seq(ck, C, st_));
   });
-  HIP_OK(hipEventRecord(ev_[3], st_));
-  if (n_seqpos) HIP_OK(hipMemcpyAsync(access, d_ac_out_.as<void>(), 8 * (size_t)U * n_seqpos, hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  float ms_all = 0, ms_dp = 0;
-  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
-  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
-  last_ms[0] = ms_all;
-  last_ms[1] = ms_dp;
-  last_ms[2] = (double)n_flagged;
+  finish_call(n_flagged, [&] {
+    if (n_seqpos) HIP_OK(hipMemcpyAsync(access, d_ac_out_.as<void>(), 8 * (size_t)U * n_seqpos, hipMemcpyDeviceToHost, st_));
+  });
 }
 
 
@@ -2844,16 +2745,9 @@ void Engine::node_profile(const double* x, int n_param_in, double* profile) {
   }
   const int n_flagged = node_profile_device("node_profile", x, n_param_in);
   const size_t n_seqpos = (size_t)h_seq_off_[n_seq_];
-  HIP_OK(hipEventRecord(ev_[3], st_));
-  if (n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_nd_prof_.as<void>(), 8 * (size_t)M * n_seqpos, hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  float ms_all = 0, ms_dp = 0;
-  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
-  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
-  last_ms[0] = ms_all;
-  last_ms[1] = ms_dp;
-  last_ms[2] = (double)n_flagged;
+  finish_call(n_flagged, [&] {
+    if (n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_nd_prof_.as<void>(), 8 * (size_t)M * n_seqpos, hipMemcpyDeviceToHost, st_));
+  });
 }
 
 // The profile of the resident batch on the device (d_nd_prof_), both forms, queued on the engine's stream behind ev_[1]; returns
@@ -2878,20 +2772,15 @@ int Engine::node_profile_device(const char* what, const double* x, int n_param_i
   na.rules = opt_node_rules_;
   na.no_rss = (flags_ & ELEMDP_NO_RSS) ? 1 : 0;
   na.profile = d_nd_prof_.as<double>();
-  int n_flagged = 0;
-  const bool sums_on_batch = opt_pipeline_ == 4;
-  if (sums_on_batch)
-    n_flagged = scan_sums(pos, [&](LinArgs& a) {
-      if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("node_profile: the scan sweeps another automaton than the lists name");
-    }, [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
-      HIP_OK(launch_node_pos(ak, na, G, Lg, st));
-    });
-  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+  return scan_both_forms(pos, [&](LinArgs& a) {
+    if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("node_profile: the scan sweeps another automaton than the lists name");
+  }, [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    HIP_OK(launch_node_pos(ak, na, G, Lg, st));
+  }, [&](DpArgs& d, int, int n_log) {
     d.node = na;
     return std::max(n_log, 1);
   }, [&](const int32_t*, int) {});
-  return n_flagged;
 }
 
 
@@ -2939,27 +2828,24 @@ void Engine::joint_profile(const double* x, int n_param_in, double* counts, doub
   ja.x_stride = joint_scratch_size(Lmax_, Wmax_, n_slots);
   ja.profile = d_jn_prof_.as<double>();
   ja.counts = d_jn_counts_.as<double>();
-  int n_flagged = 0;
-  const bool sums_on_batch = opt_pipeline_ == 4;
-  if (sums_on_batch)
-    n_flagged = scan_sums(pos, [&](LinArgs& a) {
-      if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("joint_profile: the scan sweeps another automaton than the lists name");
-      d_jn_X_.alloc(8 * ja.x_stride * (size_t)std::max(slots_.n(), 1));
-      ja.X = d_jn_X_.as<double>();
-      ja.skip_flagged = 1;
-    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
-      JointArgs jk = ja;
-      jk.idx = ak.grp;
-      jk.X = ja.X + slot0 * ja.x_stride;
-      if (!ja.no_rss) HIP_OK(launch_joint_rows(ak, jk, G, Lg, st));
-      HIP_OK(launch_joint_pos(ak, jk, G, Lg, st));
-      HIP_OK(launch_joint_counts(jk, G, st));
-    });
-  // ---- the log-space form: one launch, the scratch and the vectors per workgroup
-  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+  const int n_flagged = scan_both_forms(pos, [&](LinArgs& a) {
+    if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("joint_profile: the scan sweeps another automaton than the lists name");
+    ja.X = slot_scratch<double>(d_jn_X_, ja.x_stride);
+    ja.skip_flagged = 1;
+  }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    JointArgs jk = ja;
+    jk.idx = ak.grp;
+    jk.X = slot_scratch<double>(d_jn_X_, ja.x_stride, slot0);
+    if (!ja.no_rss) HIP_OK(launch_joint_rows(ak, jk, G, Lg, st));
+    HIP_OK(launch_joint_pos(ak, jk, G, Lg, st));
+    HIP_OK(launch_joint_counts(jk, G, st));
+  },
+  // ---- the log-space form: one launch, the scratch and the vectors per workgroup (not per sequence: what the sum passes left
+  // serves where it is large enough)
+  [&](DpArgs& d, int n_blocks, int n_log) {
     const size_t nb = (size_t)std::max(n_blocks, 1);
-    if (!sums_on_batch || d_jn_X_.bytes() < 8 * ja.x_stride * nb) d_jn_X_.alloc(8 * ja.x_stride * nb);
+    if (opt_pipeline_ != 4 || d_jn_X_.bytes() < 8 * ja.x_stride * nb) d_jn_X_.alloc(8 * ja.x_stride * nb);
     d_jn_vec_.alloc(8 * 5 * (size_t)d.lay.S * kThreads * nb);
     d.jnt = ja;
     d.jnt.X = d_jn_X_.as<double>();
@@ -2971,17 +2857,10 @@ void Engine::joint_profile(const double* x, int n_param_in, double* counts, doub
     jk.skip_flagged = 0;
     HIP_OK(launch_joint_counts(jk, C, st_));
   });
-  HIP_OK(hipEventRecord(ev_[3], st_));
-  HIP_OK(hipMemcpyAsync(counts, d_jn_counts_.as<void>(), 8 * nc * (size_t)n, hipMemcpyDeviceToHost, st_));
-  if (profile && n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_jn_prof_.as<void>(), 8 * row * n_seqpos, hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  float ms_all = 0, ms_dp = 0;
-  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
-  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
-  last_ms[0] = ms_all;
-  last_ms[1] = ms_dp;
-  last_ms[2] = (double)n_flagged;
+  finish_call(n_flagged, [&] {
+    HIP_OK(hipMemcpyAsync(counts, d_jn_counts_.as<void>(), 8 * nc * (size_t)n, hipMemcpyDeviceToHost, st_));
+    if (profile && n_seqpos) HIP_OK(hipMemcpyAsync(profile, d_jn_prof_.as<void>(), 8 * row * n_seqpos, hipMemcpyDeviceToHost, st_));
+  });
 }
 
 // ---- the stem slots of the automaton (stem_rules.h): host only, no device needed
@@ -3014,22 +2893,15 @@ void Engine::stem_profile(const double* x, int n_param_in, double min_prob, doub
   if (K > kStemMaxSlots || au_.M() > 255) throw ArgError("stem_profile: more than 255 stem slots or pattern nodes");
   const size_t nc = (size_t)K * kStemBlock;
   const bool want_list = min_prob < HUGE_VAL;
-  n_stem_ = -1;
+  stems_.invalidate();
   if (streaming_) {
-    std::vector<int32_t> hs, hi, hj, hk;
-    std::vector<double> hq;
+    StagedList::Host list;
     stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
-      int64_t m = 0;
-      e.stem_profile(x, n_param_in, min_prob, counts + nc * (size_t)c0, &m);
-      const size_t b = hs.size();
-      hs.resize(b + m); hi.resize(b + m); hj.resize(b + m); hk.resize(b + m); hq.resize(b + m);
-      e.stem_list(hs.data() + b, hi.data() + b, hj.data() + b, hk.data() + b, hq.data() + b, m);
-      for (size_t t = b; t < hs.size(); ++t) hs[t] += c0;   // (batch-global sequence indices)
+      e.stem_profile(x, n_param_in, min_prob, counts + nc * (size_t)c0, nullptr);
+      list.append(e.stems_, c0);
     });
-    d_sl_seq_.upload(hs, st_); d_sl_i_.upload(hi, st_); d_sl_j_.upload(hj, st_); d_sl_k_.upload(hk, st_); d_sl_q_.upload(hq, st_);
-    HIP_OK(hipStreamSynchronize(st_));
-    n_stem_ = (int64_t)hs.size();
-    if (n_entries) *n_entries = n_stem_;
+    stems_.adopt(list, st_);
+    if (n_entries) *n_entries = stems_.count();
     return;
   }
   require_resident("stem_profile", n_param_in);
@@ -3056,89 +2928,47 @@ void Engine::stem_profile(const double* x, int n_param_in, double min_prob, doub
   sa.counts = d_sp_counts_.as<double>();
   sa.min_prob = min_prob;
   if (want_list) {   // staging ranges: a sequence's list holds at most K entries per kept cell
-    d_sp_kept_.alloc(8 * (size_t)n); d_sp_koff_.alloc(8 * ((size_t)n + 1));
-    d_sp_cnt_.alloc(8 * (size_t)n); d_sp_off_.alloc(8 * ((size_t)n + 1));
-    HIP_OK(launch_pair_kept(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, d_sp_kept_.as<int64_t>(), st_));
-    HIP_OK(launch_pair_prefix(d_sp_kept_.as<int64_t>(), n, d_sp_koff_.as<int64_t>(), st_));
-    int64_t n_kept = 0;
-    HIP_OK(hipMemcpyAsync(&n_kept, d_sp_koff_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
-    HIP_OK(hipStreamSynchronize(st_));
-    const size_t cap = (size_t)n_kept * (size_t)K;
-    d_sp_si_.alloc(4 * cap); d_sp_sj_.alloc(4 * cap); d_sp_sk_.alloc(cap); d_sp_sq_.alloc(8 * cap);
-    // (cnt needs no clearing: k_stem_seq writes the count of every sequence, in exactly one of the two forms, 0 where it has no Q)
-    sa.koff = d_sp_koff_.as<int64_t>(); sa.cnt = d_sp_cnt_.as<int64_t>();
-    sa.st_i = d_sp_si_.as<int32_t>(); sa.st_j = d_sp_sj_.as<int32_t>(); sa.st_k = d_sp_sk_.as<uint8_t>(); sa.st_q = d_sp_sq_.as<double>();
+    const StagedList::Staging sl = stems_.begin(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, K, st_);
+    sa.koff = sl.koff; sa.cnt = sl.cnt;
+    sa.st_i = sl.st_i; sa.st_j = sl.st_j; sa.st_k = sl.st_k; sa.st_q = sl.st_v[0];
   }
   const bool no_rss = (flags_ & ELEMDP_NO_RSS) != 0;
-  int n_flagged = 0;
-  const bool sums_on_batch = opt_pipeline_ == 4;
-  if (sums_on_batch)
-    n_flagged = scan_sums(pos, [&](LinArgs& a) {
-      if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("stem_profile: the scan sweeps another automaton than the lists name");
-      d_sp_X_.alloc(8 * sa.x_stride * (size_t)std::max(slots_.n(), 1));
-      sa.X = d_sp_X_.as<double>();
-      sa.skip_flagged = 1;
-    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
-      StemArgs sk = sa;
-      sk.idx = ak.grp;
-      sk.X = sa.X + slot0 * sa.x_stride;
-      if (!no_rss) HIP_OK(launch_stem_cells(ak, sk, G, (Lg + 1) * (Wg + 1), st));   // (else no mark is set: the band tables are not read)
-      HIP_OK(launch_stem_counts(sk, G, Lg, Wg, st));
-      if (want_list) HIP_OK(launch_stem_seq(sk, G, st));
-    });
+  const int n_flagged = scan_both_forms(pos, [&](LinArgs& a) {
+    if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("stem_profile: the scan sweeps another automaton than the lists name");
+    sa.X = slot_scratch<double>(d_sp_X_, sa.x_stride);
+    sa.skip_flagged = 1;
+  }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    StemArgs sk = sa;
+    sk.idx = ak.grp;
+    sk.X = slot_scratch<double>(d_sp_X_, sa.x_stride, slot0);
+    if (!no_rss) HIP_OK(launch_stem_cells(ak, sk, G, (Lg + 1) * (Wg + 1), st));   // (else no mark is set: the band tables are not read)
+    HIP_OK(launch_stem_counts(sk, G, Lg, Wg, st));
+    if (want_list) HIP_OK(launch_stem_seq(sk, G, st));
+  },
   // ---- the log-space form, in chunks of at most as many sequences as the table slots hold (the scratch is bounded by the chunk)
-  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
-    const int chunk = log_chunk(sums_on_batch, n_blocks, n_log);
-    if (!sums_on_batch) d_sp_X_.alloc(8 * sa.x_stride * (size_t)chunk);
+  [&](DpArgs& d, int n_blocks, int n_log) {
+    sa.X = slot_scratch<double>(d_sp_X_, sa.x_stride);
     d.stm = sa;
-    d.stm.X = d_sp_X_.as<double>();
-    return chunk;
+    return log_chunk(n_blocks, n_log);
   }, [&](const int32_t* idx, int C) {
     StemArgs sk = sa;
     sk.idx = idx;
-    sk.X = d_sp_X_.as<double>();
     sk.skip_flagged = 0;
     HIP_OK(launch_stem_counts(sk, C, Lmax_, Wmax_, st_));
     if (want_list) HIP_OK(launch_stem_seq(sk, C, st_));
   });
-  HIP_OK(hipEventRecord(ev_[3], st_));
-  // ---- the list in (sequence, i, j, slot) order
-  int64_t total = 0;
-  if (want_list) {
-    HIP_OK(launch_pair_prefix(d_sp_cnt_.as<int64_t>(), n, d_sp_off_.as<int64_t>(), st_));
-    HIP_OK(hipMemcpyAsync(&total, d_sp_off_.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
-    HIP_OK(hipStreamSynchronize(st_));
-    d_sl_seq_.alloc(4 * (size_t)total); d_sl_i_.alloc(4 * (size_t)total); d_sl_j_.alloc(4 * (size_t)total);
-    d_sl_k_.alloc(4 * (size_t)total); d_sl_q_.alloc(8 * (size_t)total);
-    HIP_OK(launch_stem_scatter(sa, d_sp_off_.as<int64_t>(), n, d_sl_seq_.as<int32_t>(), d_sl_i_.as<int32_t>(), d_sl_j_.as<int32_t>(),
-                               d_sl_k_.as<int32_t>(), d_sl_q_.as<double>(), st_));
-  }
-  if (nc) HIP_OK(hipMemcpyAsync(counts, d_sp_counts_.as<void>(), 8 * nc * (size_t)n, hipMemcpyDeviceToHost, st_));
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  float ms_all = 0, ms_dp = 0;
-  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
-  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
-  last_ms[0] = ms_all;
-  last_ms[1] = ms_dp;
-  last_ms[2] = (double)n_flagged;
-  n_stem_ = total;
-  if (n_entries) *n_entries = total;
+  finish_call(n_flagged, [&] {
+    if (want_list) stems_.finish(st_); else stems_.set_empty();   // the list in (sequence, i, j, slot) order
+    if (nc) HIP_OK(hipMemcpyAsync(counts, d_sp_counts_.as<void>(), 8 * nc * (size_t)n, hipMemcpyDeviceToHost, st_));
+  });
+  if (n_entries) *n_entries = stems_.count();
 }
 
 void Engine::stem_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q, int64_t cap) {
   require_device();
   DeviceGuard dg(device_);
-  if (n_stem_ < 0) throw StateError("stem_list before stem_profile");
-  if (cap < n_stem_) throw ArgError("stem_list: buffer too small");
-  const size_t m = (size_t)n_stem_;
-  if (m == 0) return;
-  if (seq) HIP_OK(hipMemcpy(seq, d_sl_seq_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (i) HIP_OK(hipMemcpy(i, d_sl_i_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (j) HIP_OK(hipMemcpy(j, d_sl_j_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (slot) HIP_OK(hipMemcpy(slot, d_sl_k_.as<void>(), 4 * m, hipMemcpyDeviceToHost));
-  if (q) HIP_OK(hipMemcpy(q, d_sl_q_.as<void>(), 8 * m, hipMemcpyDeviceToHost));
+  stems_.fetch(seq, i, j, q, nullptr, slot, cap);
 }
 
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h).  The node pass of
@@ -3187,23 +3017,16 @@ void Engine::node_mea(const double* x, int n_param_in, double gamma, int max_sit
   ma.start = d_nm_s0_.as<int32_t>(); ma.end = d_nm_s1_.as<int32_t>();
   ma.score = d_nm_sc_.as<double>(); ma.conf = d_nm_cf_.as<double>();
   HIP_OK(launch_node_mea(ma, n, st_));
-  HIP_OK(hipEventRecord(ev_[3], st_));
   auto fetch = [&](void* dst, const DevBuf& src, size_t bytes) {
     if (dst && bytes) HIP_OK(hipMemcpyAsync(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost, st_));
   };
-  fetch(out.profile, d_nd_prof_, 8 * (size_t)M * n_seqpos);
-  fetch(out.node, d_nm_node_, (size_t)K * n_seqpos);
-  fetch(out.n_sites, d_nm_ns_, 4 * (size_t)n);
-  fetch(out.start, d_nm_s0_, 4 * n_slots); fetch(out.end, d_nm_s1_, 4 * n_slots);
-  fetch(out.score, d_nm_sc_, 8 * n_slots); fetch(out.conf, d_nm_cf_, 8 * n_slots);
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));   // (the host vector of the lists goes out of use here at the latest)
-  float ms_all = 0, ms_dp = 0;
-  HIP_OK(hipEventElapsedTime(&ms_all, ev_[1], ev_[2]));
-  HIP_OK(hipEventElapsedTime(&ms_dp, ev_[1], ev_[3]));
-  last_ms[0] = ms_all;
-  last_ms[1] = ms_dp;
-  last_ms[2] = (double)n_flagged;
+  finish_call(n_flagged, [&] {   // (its wait: the host vector of the lists goes out of use there at the latest)
+    fetch(out.profile, d_nd_prof_, 8 * (size_t)M * n_seqpos);
+    fetch(out.node, d_nm_node_, (size_t)K * n_seqpos);
+    fetch(out.n_sites, d_nm_ns_, 4 * (size_t)n);
+    fetch(out.start, d_nm_s0_, 4 * n_slots); fetch(out.end, d_nm_s1_, 4 * n_slots);
+    fetch(out.score, d_nm_sc_, 8 * n_slots); fetch(out.conf, d_nm_cf_, 8 * n_slots);
+  });
 }
 
 
@@ -3232,23 +3055,19 @@ void Engine::sample_structures(const double* x, int n_param_in, int n_samples, u
   sa.rss = d_sm_rss_.as<char>(); sa.node = d_sm_node_.as<uint8_t>(); sa.logp = d_sm_logp_.as<double>();
   sa.status = d_sm_status_.as<int32_t>();
   sa.stack_cap = cap;
-  int n_flagged = 0;
-  const bool sums_on_batch = opt_pipeline_ == 4;
-  if (sums_on_batch) {
-    ScanPos pos(n_seqpos, n);
-    n_flagged = scan_sums(pos, [&](LinArgs&) {
-      sa.stack_lanes = std::min(n_samples, kSampleLanes);
-      d_sm_stack_.alloc(sizeof(TraceFrame) * (size_t)slots_.n() * sa.stack_lanes * cap);
-    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_INSIDE, st));
-      SampleArgs sk = sa;
-      sk.stack = d_sm_stack_.as<TraceFrame>() + slot0 * sa.stack_lanes * (size_t)cap;
-      HIP_OK(launch_sample(ak, sk, G, st));
-    });
-  }
+  const ScanPos pos(n_seqpos, n);
+  const int n_flagged = scan_both_forms(pos, [&](LinArgs&) {
+    sa.stack_lanes = std::min(n_samples, kSampleLanes);
+    sa.stack = slot_scratch<TraceFrame>(d_sm_stack_, (size_t)sa.stack_lanes * cap);
+  }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_INSIDE, st));
+    SampleArgs sk = sa;
+    sk.stack = slot_scratch<TraceFrame>(d_sm_stack_, (size_t)sa.stack_lanes * cap, slot0);
+    HIP_OK(launch_sample(ak, sk, G, st));
+  },
   // ---- the log-space form: the fused scan kernel stops after its inside pass and draws the samples on its own slot before it
-  // takes the next sequence
-  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+  // takes the next sequence (stacks per workgroup, not per sequence)
+  [&](DpArgs& d, int n_blocks, int n_log) {
     const int lanes = std::min(n_samples, kThreads);
     d_sm_stack_.alloc(sizeof(TraceFrame) * (size_t)n_blocks * lanes * cap);
     d.smp = sa;
@@ -3256,12 +3075,7 @@ void Engine::sample_structures(const double* x, int n_param_in, int n_samples, u
     d.smp.stack_lanes = lanes;
     return n_log;
   }, [](const int32_t*, int) {});
-  HIP_OK(hipEventRecord(ev_[2], st_));
-  HIP_OK(hipStreamSynchronize(st_));
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, ev_[1], ev_[2]));
-  last_ms[0] = last_ms[1] = ms;
-  last_ms[2] = (double)n_flagged;
+  finish_call(n_flagged);
   if (out.rss && n_bytes) HIP_OK(hipMemcpy(out.rss, d_sm_rss_.as<void>(), n_bytes, hipMemcpyDeviceToHost));
   if (out.node && n_bytes) HIP_OK(hipMemcpy(out.node, d_sm_node_.as<void>(), n_bytes, hipMemcpyDeviceToHost));
   if (out.logp) HIP_OK(hipMemcpy(out.logp, d_sm_logp_.as<void>(), 8 * (size_t)n * n_samples, hipMemcpyDeviceToHost));

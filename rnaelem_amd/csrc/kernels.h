@@ -502,10 +502,7 @@ struct CondArgs {
 hipError_t launch_cond_cells(const CondArgs& a, int world, int G, int cells_max, hipStream_t st);
 // k_cond_seq behind both worlds' reductions, or behind the fused scan kernel (DpArgs::cond_p0)
 hipError_t launch_cond_seq(const CondArgs& a, int G, hipStream_t st);
-// the scatter of the staging list into the final list ordered by (sequence, i, j), two probability columns
-hipError_t launch_cond_scatter(const int64_t* koff, const int64_t* cnt, const int64_t* off, const int32_t* st_i, const int32_t* st_j,
-                               const double* st_p0, const double* st_p1, int n, int32_t* seq, int32_t* i, int32_t* j, double* p0,
-                               double* p1, hipStream_t st);
+// (the final list, ordered by (sequence, i, j) with two probability columns: launch_list_scatter)
 
 hipError_t launch_sample(const LinArgs& a, const SampleArgs& s, int G, hipStream_t st);
 // k_ctx_cells behind launch_lin_scan_group (SCAN_PASS_START) and launch_pair_cells on the same slots and stream; k_ctx_seq behind
@@ -526,19 +523,25 @@ hipError_t launch_joint_pos(const LinArgs& a, const JointArgs& c, int G, int Lma
 hipError_t launch_joint_counts(const JointArgs& c, int G, hipStream_t st);
 // k_stem_cells (one lane per cell: Q by stem slot) behind launch_lin_scan_group (SCAN_PASS_START) on the same slots and stream;
 // k_stem_counts (one workgroup per sequence: the K 25 counts) and k_stem_seq (its list entries with q >= min_prob into its staging
-// range) behind it, or behind the fused scan kernel (DpArgs::stm); k_stem_scatter: the batch list in (sequence, i, j, slot) order
+// range) behind it, or behind the fused scan kernel (DpArgs::stm); launch_list_scatter: the batch list in (sequence, i, j, slot) order
 hipError_t launch_stem_cells(const LinArgs& a, const StemArgs& c, int G, int cells_max, hipStream_t st);
 hipError_t launch_stem_counts(const StemArgs& c, int G, int Lmax, int Wmax, hipStream_t st);
 hipError_t launch_stem_seq(const StemArgs& c, int G, hipStream_t st);
-hipError_t launch_stem_scatter(const StemArgs& c, const int64_t* off, int n, int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q,
-                               hipStream_t st);
 // k_node_mea behind the node pass of the whole batch (both forms), on the engine's stream: one wave per sequence
 hipError_t launch_node_mea(const NodeMeaArgs& a, int n_seq, hipStream_t st);
+// ---- the staged lists of the pair, conditional and stem calls (staged_list.h, pair_kernels.hip).  The columns of one list, as
+// k_list_scatter takes them: batch index n has cnt[n] entries in staging from mult * koff[n] on, and its entries of the final list
+// start at off[n].  A null st_v[1] or st_k: the list has no second value column, or no label column.
+struct ListCols {
+  const int64_t* koff; const int64_t* cnt; const int64_t* off;
+  int64_t mult;                   // staging entries per kept cell (1; the stem slots K of the stem list)
+  const int32_t* st_i; const int32_t* st_j; const double* st_v[2]; const uint8_t* st_k;
+  int32_t* seq; int32_t* i; int32_t* j; double* v[2]; int32_t* k;   // final list: seq = n, the label widened to int32
+};
 // kept pairs of every sequence of the batch (the staging capacity), off[0..n] = exclusive prefix of cnt[0..n) with off[n] the total,
-// and the scatter of the staging list into the final list ordered by (sequence, i, j)
+// and the scatter of the staging list into the final list ordered by (sequence, i, j[, label])
 hipError_t launch_pair_kept(const SeqPlan* plans, const uint32_t* okbits, int n, int64_t* kept, hipStream_t st);
 hipError_t launch_pair_prefix(const int64_t* cnt, int n, int64_t* off, hipStream_t st);
-hipError_t launch_pair_scatter(const int64_t* koff, const int64_t* cnt, const int64_t* off, const int32_t* st_i, const int32_t* st_j,
-                               const double* st_p, int n, int32_t* seq, int32_t* i, int32_t* j, double* p, hipStream_t st);
+hipError_t launch_list_scatter(const ListCols& c, int n, hipStream_t st);
 
 }  // namespace elemdp

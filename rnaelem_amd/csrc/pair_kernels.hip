@@ -1,7 +1,7 @@
 // pair_kernels.hip -- base-pair posteriors under the motif model: the reduction over the compact tables of the
 // scan's first sum pass (k4_pairs), the per-sequence unpaired sums and compaction (k_pair_seq), and the batch list in
-// (sequence, i, j) order (k_pair_kept, k_pair_prefix, k_pair_scatter).  No atomics: every sum has a fixed order, so repeats over
-// the same tables give the same bits.
+// (sequence, i, j) order (k_pair_kept, k_pair_prefix, k_list_scatter; the conditional and the stem call build their lists with the
+// same three).  No atomics: every sum has a fixed order, so repeats over the same tables give the same bits.
 #include <hip/hip_runtime.h>
 
 #include "block_scan.h"
@@ -105,12 +105,16 @@ __global__ __launch_bounds__(kThreads) void k_pair_prefix(const int64_t* cnt, in
   if (threadIdx.x == 0) off[n] = total;
 }
 
-__global__ __launch_bounds__(kThreads) void k_pair_scatter(const int64_t* koff, const int64_t* cnt, const int64_t* off, const int32_t* st_i,
-                                                           const int32_t* st_j, const double* st_p, int32_t* seq, int32_t* i, int32_t* j, double* p) {
+// grid (n): the staging range of batch index blockIdx.x into its place in the batch list (the lists of the pair, conditional and
+// stem calls: which columns a list has is uniform over the launch)
+__global__ __launch_bounds__(kThreads) void k_list_scatter(ListCols c) {
   const int n = blockIdx.x;
-  const int64_t c = cnt[n], src = koff[n], dst = off[n];
-  for (int64_t t = threadIdx.x; t < c; t += kThreads) {
-    seq[dst + t] = n; i[dst + t] = st_i[src + t]; j[dst + t] = st_j[src + t]; p[dst + t] = st_p[src + t];
+  const int64_t m = c.cnt[n], src = c.koff[n] * c.mult, dst = c.off[n];
+  for (int64_t t = threadIdx.x; t < m; t += kThreads) {
+    c.seq[dst + t] = n; c.i[dst + t] = c.st_i[src + t]; c.j[dst + t] = c.st_j[src + t];
+    c.v[0][dst + t] = c.st_v[0][src + t];
+    if (c.st_v[1]) c.v[1][dst + t] = c.st_v[1][src + t];
+    if (c.st_k) c.k[dst + t] = c.st_k[src + t];
   }
 }
 
@@ -133,10 +137,9 @@ hipError_t launch_pair_prefix(const int64_t* cnt, int n, int64_t* off, hipStream
   hipLaunchKernelGGL(k_pair_prefix, dim3(1), dim3(kThreads), 0, st, cnt, n, off);
   return hipGetLastError();
 }
-hipError_t launch_pair_scatter(const int64_t* koff, const int64_t* cnt, const int64_t* off, const int32_t* st_i, const int32_t* st_j,
-                               const double* st_p, int n, int32_t* seq, int32_t* i, int32_t* j, double* p, hipStream_t st) {
+hipError_t launch_list_scatter(const ListCols& c, int n, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pair_scatter, dim3(n), dim3(kThreads), 0, st, koff, cnt, off, st_i, st_j, st_p, seq, i, j, p);
+  hipLaunchKernelGGL(k_list_scatter, dim3(n), dim3(kThreads), 0, st, c);
   return hipGetLastError();
 }
 

@@ -10,7 +10,8 @@
 //                  only adds where the two bases are its own.  It serves the log-space form too, whose Q the fused scan kernel
 //                  writes (DpArgs::stm).
 //   k_stem_seq     one workgroup per sequence: the entries with q >= min_prob in (i, j, slot) order into the sequence's staging
-//                  range (the scheme of k_pair_seq); k_stem_scatter: the batch list behind the prefix over the counts.
+//                  range (the scheme of k_pair_seq); the batch list behind the prefix over the counts is k_list_scatter's
+//                  (pair_kernels.hip).
 // No atomics: every sum has a fixed order, so repeats over the same tables give the same bits.  A sequence the range check flagged
 // is left to the log-space form.
 #include <hip/hip_runtime.h>
@@ -141,15 +142,6 @@ __global__ __launch_bounds__(kThreads) void k_stem_seq(StemArgs c) {
   if (tid == 0) c.cnt[n] = base;
 }
 
-__global__ __launch_bounds__(kThreads) void k_stem_scatter(StemArgs c, const int64_t* off, int32_t* seq, int32_t* i, int32_t* j, int32_t* slot,
-                                                           double* q) {
-  const int n = blockIdx.x;
-  const int64_t m = c.cnt[n], src = c.koff[n] * c.K, dst = off[n];
-  for (int64_t t = threadIdx.x; t < m; t += kThreads) {
-    seq[dst + t] = n; i[dst + t] = c.st_i[src + t]; j[dst + t] = c.st_j[src + t]; slot[dst + t] = c.st_k[src + t]; q[dst + t] = c.st_q[src + t];
-  }
-}
-
 hipError_t launch_stem_cells(const LinArgs& a, const StemArgs& c, int G, int cells_max, hipStream_t st) {
   if (G <= 0 || cells_max <= 0) return hipSuccess;
   constexpr size_t kLdsMax = 60 * 1024;   // (with the static part below the 64 KiB a workgroup may ask for)
@@ -172,12 +164,6 @@ hipError_t launch_stem_counts(const StemArgs& c, int G, int Lmax, int Wmax, hipS
 hipError_t launch_stem_seq(const StemArgs& c, int G, hipStream_t st) {
   if (G <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_stem_seq, dim3(G), dim3(kThreads), 0, st, c);
-  return hipGetLastError();
-}
-hipError_t launch_stem_scatter(const StemArgs& c, const int64_t* off, int n, int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q,
-                               hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_stem_scatter, dim3(n), dim3(kThreads), 0, st, c, off, seq, i, j, slot, q);
   return hipGetLastError();
 }
 

@@ -347,6 +347,18 @@ def test_groupings_thresholds_and_what_a_call_leaves_alone():
         assert (a["structure_motif"], a["structure_none"]) == (b["structure_motif"], b["structure_none"]), k
         for f in ("p_motif", "p_none", "unpaired_motif", "unpaired_none", "exist_prob", "shift"):
             np.testing.assert_allclose(b[f], a[f], rtol=1e-10, atol=1e-14, equal_nan=True, err_msg="%s %d" % (f, k))
+    # the list of the last stem call is still that call's, bit for bit, behind pair and conditional calls (the third direction:
+    # the three lists share no buffer)
+    n_stem = sum(len(r[3]) for r in want)
+    assert n_stem > 0
+    ss, si, sj, sk = (np.full(n_stem, -1, dtype=np.int32) for _ in range(4))
+    sq = np.full(n_stem, np.nan)
+    assert api.load_library().elemdp_stem_list(base._h, ss.ctypes.data_as(i32), si.ctypes.data_as(i32), sj.ctypes.data_as(i32),
+                                               sk.ctypes.data_as(i32), sq.ctypes.data_as(dp), n_stem) == 0
+    assert api.load_library().elemdp_stem_list(base._h, None, None, None, None, None, n_stem - 1) == -1     # (its length too)
+    assert np.array_equal(ss, np.concatenate([np.full(len(r[3]), k, dtype=np.int32) for k, r in enumerate(want)]))
+    for col, got in enumerate((si, sj, sk, sq)):
+        assert np.array_equal(got, np.concatenate([r[col] for r in want])), col
     # a second call on the loaded batch agrees to the last bits (the sum passes add with LDS atomics: DESIGN.md section 12)
     c2, l2 = base.stem_profiles(x, 0.0)
     np.testing.assert_allclose(c2, want_c, rtol=1e-10, atol=1e-14)

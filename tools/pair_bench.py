@@ -10,7 +10,7 @@ same batch, from the engine's HIP events (last_timing).  Prints one JSON line pe
 comes from the kernel trace of a run with option group_streams 1 (PAIR_BENCH_GROUP_STREAMS=1).
 
 The pair kernels' share of the call comes from a separate `rocprofv3 --kernel-trace --stats` run of this script: k4_pairs,
-k_pair_seq, k_pair_kept, k_pair_prefix and k_pair_scatter against the sum passes (k4_in / k4_in_ext / k4_out_ext / k4_r7 /
+k_pair_seq, k_pair_kept, k_pair_prefix and k_list_scatter against the sum passes (k4_in / k4_in_ext / k4_out_ext / k4_r7 /
 k4_out / k5_pick)."""
 import json
 import os

@@ -7,7 +7,7 @@ three.  The pair call is the yardstick: the same sum passes, one reduction per c
     python tools/stem_bench.py [n] [L ...]       (default: 10000 sequences of L = 200 and of L = 300, pattern ((.*.)))
 
 The share of each kernel comes from a separate `rocprofv3 --kernel-trace --stats` run of this script: k_stem_cells, k_stem_counts,
-k_stem_seq and k_stem_scatter against k4_pairs / k_pair_seq and the sum passes (k4_in / k4_in_ext / k4_out_ext / k4_r7 / k4_out /
+k_stem_seq and k_list_scatter against k4_pairs / k_pair_seq and the sum passes (k4_in / k4_in_ext / k4_out_ext / k4_r7 / k4_out /
 k5_pick)."""
 import json
 import os
