@@ -405,6 +405,37 @@ int elemdp_joint_profile(elemdp_handle* h, const double* x, int32_t n_param, dou
 int elemdp_stem_slots(const elemdp_handle* h, int32_t* node_left, int32_t* node_right, int32_t cap);
 int elemdp_stem_profile(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double* counts, int64_t* n_entries);
 int elemdp_stem_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q, int64_t cap);
+/* Helix posteriors under the motif model x.  Cells as in elemdp_pair_list: cell (i, j) pairs the 0-based bases i and
+ * j-1.  The helix (i, j, len), len >= 1, is the event that the cells (i + t, j - t), t = 0 .. len-1, are all pairs: a run of len
+ * directly stacked pairs whose outermost pair is (i, j).  H(i, j, len) is its probability over the ensemble of the scan's first sum
+ * pass (terminals ari and nasi, Z(ari, nasi): the ensemble of elemdp_pair_posteriors), exact from its inside / outside tables: a
+ * len-step path sum along the stacking rule (helix_rules.h), clamped to [0, 1], nothing renormalised.  H(i, j, 1) is the P of
+ * elemdp_pair_posteriors, H is non-increasing in len, and H(i, j, len) <= H(i+1, j-1, len-1), wherever the tables' inside and outside
+ * agree.  The pair marginals only bound it from above.
+ *   max_len:   1 .. ELEMDP_HELIX_MAX_LEN; min_len: 1 .. max_len;
+ *   min_prob:  >= 0, or +inf.  Finite: the entries (sequence, i, j, len, H) with min_len <= len <= max_len and H >= min_prob are kept
+ *              on the device in (sequence, i, j, len) order for elemdp_helix_list; at 0 the list holds every (kept cell, len) whose
+ *              len cells are all kept.  +inf: no list, and no staging is allocated;
+ *   n_entries: NULL, or receives the length of the list;
+ *   structure: NULL, or dot-bracket strings in seq_off indexing (L bytes per sequence, ( ) . only).  A stem is a maximal run of
+ *              directly nested pairs of that structure.  stem_len and stem_prob (seq_off indexing; one of them may be NULL) receive,
+ *              at the position of the 5' base of a stem's outermost pair, the stem's length -- not bounded by max_len -- and the joint
+ *              probability of the whole stem; elsewhere 0 and NaN.  A stem that holds a pair that is not a kept cell, or a span above
+ *              max_span, has probability 0 exactly.
+ * A sequence without any parse (Z = 0) has no entries and stem probabilities 0, exactly; so has every sequence under ELEMDP_NO_RSS,
+ * where the band tables are not read.  Sequences that leave the double range of the scaled-linear tables, and every sequence under
+ * option pipeline 3, go through the same rule on the log-space tables of the fused scan kernel.  x NULL, max_len outside
+ * 1 .. ELEMDP_HELIX_MAX_LEN, min_len outside 1 .. max_len, min_prob negative or NaN, an unbalanced structure or one with other
+ * characters, a structure with both outputs NULL: ELEMDP_EINVAL; a call before elemdp_load_batch: ELEMDP_ESTATE; elemdp_helix_list
+ * before any helix call on the resident batch: ELEMDP_ESTATE, with cap below the length of the list: ELEMDP_EINVAL (its arrays may
+ * be NULL); no device: ELEMDP_ENODEV.  elemdp_last_timing afterwards: [whole call, sum passes + helix kernels, sequences handed to
+ * the log-space form].  The other calls of the handle are unaffected; the lists of the last pair, conditional and stem call stay
+ * valid, and a pair, conditional or stem call leaves the helix list alone. */
+#define ELEMDP_HELIX_MAX_LEN 32
+int elemdp_helix_posteriors(elemdp_handle* h, const double* x, int32_t n_param, int32_t max_len, int32_t min_len,
+                            double min_prob, int64_t* n_entries,
+                            const char* structure, int32_t* stem_len, double* stem_prob);
+int elemdp_helix_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, int32_t* len, double* p, int64_t cap);
 /* Accessibility under the motif model x: with U = max_width, access[U * (seq_off[n] + p) + (w - 1)], p 0-based,
  * w = 1 .. U, is the probability that the bases p .. p+w-1 of sequence n are all unpaired, over the ensemble of the scan's first sum
  * pass (terminals ari and nasi, Z(ari, nasi): the ensemble of elemdp_pair_posteriors and elemdp_context_profile), from its inside /

@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_pair_terms", "elemdp_pair_terms_host", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_joint_profile", "elemdp_stem_slots", "elemdp_stem_profile", "elemdp_stem_list", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_joint_profile", "elemdp_stem_slots", "elemdp_stem_profile", "elemdp_stem_list", "elemdp_helix_posteriors", "elemdp_helix_list", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -100,6 +100,8 @@ def load_library():
         L.elemdp_stem_slots.argtypes = [hp, i32, i32, C.c_int32]
         L.elemdp_stem_profile.argtypes = [hp, dp, C.c_int32, C.c_double, dp, C.POINTER(C.c_int64)]
         L.elemdp_stem_list.argtypes = [hp, i32, i32, i32, i32, dp, C.c_int64]
+        L.elemdp_helix_posteriors.argtypes = [hp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int64), C.c_char_p, i32, dp]
+        L.elemdp_helix_list.argtypes = [hp, i32, i32, i32, i32, dp, C.c_int64]
         L.elemdp_accessibility.argtypes = [hp, dp, C.c_int32, C.c_int32, dp]
         L.elemdp_node_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_int32, dp, u8, i32, i32, i32, dp, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
@@ -223,6 +225,44 @@ def pair_terms_host(mask, kept):
     if rc:
         raise ElemdpError(rc, "pair_terms_host")
     return ha, h1
+
+
+HELIX_MAX_LEN = 32   # ELEMDP_HELIX_MAX_LEN
+
+
+def structure_helices(db):
+    """The stems of a dot-bracket string, host only: (i, j, len) per maximal run of directly nested pairs (i, j-1), (i+1, j-2), ..,
+    i 0-based and j exclusive as in pair_posteriors, by increasing i.  Raises ValueError for an unbalanced string or one with
+    characters other than ( ) ."""
+    mate, stack = [-1] * len(db), []
+    for p, c in enumerate(db):
+        if c == "(":
+            stack.append(p)
+        elif c == ")":
+            if not stack:
+                raise ValueError("unbalanced structure")
+            mate[p] = stack.pop()
+            mate[mate[p]] = p
+        elif c != ".":
+            raise ValueError("a structure holds ( ) . only")
+    if stack:
+        raise ValueError("unbalanced structure")
+    out = []
+    for p, r in enumerate(mate):
+        if r < p or (p > 0 and r + 1 < len(db) and mate[p - 1] == r + 1):
+            continue
+        n = 1
+        while p + n < r - n and mate[p + n] == r - n:
+            n += 1
+        out.append((p, r + 1, n))
+    return out
+
+
+def stem_min_posterior(pairs, i, j, n):
+    """The smallest pair posterior of the stem (i, j, n) in a pair list (i, j, p, ..) of its sequence; 0 where a pair is not listed."""
+    ii, jj, pp = pairs[0], pairs[1], pairs[2]
+    have = {(int(a), int(b)): float(v) for a, b, v in zip(ii, jj, pp)}
+    return min(have.get((i + t, j - t), 0.0) for t in range(n))
 
 
 class Engine:
@@ -605,6 +645,47 @@ class Engine:
         self._check(self._lib.elemdp_stem_list(self._h, _i32(seq), _i32(ii), _i32(jj), _i32(kk), _dp(q), max(m, 1)))
         bounds = np.searchsorted(seq[:m], np.arange(self.n_seq + 1))
         return counts, [(ii[a:b].copy(), jj[a:b].copy(), kk[a:b].copy(), q[a:b].copy()) for a, b in zip(bounds[:-1], bounds[1:])]
+
+    # ---- helix posteriors
+    def helix_posteriors(self, x, min_prob=0.01, min_len=2, max_len=16, structures=None):
+        """Per sequence (i, j, len, p): the helices -- runs of len directly stacked pairs (i, j), (i+1, j-1), .., cells as in
+        pair_posteriors -- with min_len <= len <= max_len (at most HELIX_MAX_LEN) whose joint probability p reaches min_prob, in
+        (i, j, len) order, over the ensemble of pair_posteriors; len 1 is its p.  At min_prob 0 every (kept cell, len) whose cells
+        are all kept; at +inf no list (empty arrays).  With structures (one dot-bracket string per sequence) returns
+        (lists, stems): per sequence (i, j, len, p) of every stem of its structure (structure_helices), p the joint probability of
+        the whole stem, whatever its length; 0 where a pair of the stem is not a kept cell."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        n_pos = int(off[-1]) if off is not None else 0
+        db = slen = sprob = None
+        if structures is not None:
+            structures = [s if isinstance(s, str) else bytes(s).decode() for s in structures]
+            if off is None or len(structures) != self.n_seq or any(len(s) != int(off[k + 1] - off[k]) for k, s in enumerate(structures)):
+                raise ValueError("helix_posteriors: one structure per sequence, of its length")
+            db = "".join(structures).encode()
+            slen = np.zeros(max(n_pos, 1), dtype=np.int32)
+            sprob = np.zeros(max(n_pos, 1))
+        m = C.c_int64()
+        self._check(self._lib.elemdp_helix_posteriors(self._h, _dp(x), self.n_param, int(max_len), int(min_len), float(min_prob), C.byref(m),
+                                                      db, _i32(slen) if slen is not None else None, _dp(sprob)))
+        m = m.value
+        seq, ii, jj, kk = (np.zeros(max(m, 1), dtype=np.int32) for _ in range(4))
+        p = np.zeros(max(m, 1))
+        if np.isfinite(min_prob):
+            self._check(self._lib.elemdp_helix_list(self._h, _i32(seq), _i32(ii), _i32(jj), _i32(kk), _dp(p), max(m, 1)))
+        bounds = np.searchsorted(seq[:m], np.arange(self.n_seq + 1))
+        lists = [(ii[a:b].copy(), jj[a:b].copy(), kk[a:b].copy(), p[a:b].copy()) for a, b in zip(bounds[:-1], bounds[1:])]
+        if structures is None:
+            return lists
+        stems = []
+        for k in range(self.n_seq):
+            a, b = int(off[k]), int(off[k + 1])
+            at = np.nonzero(slen[a:b])[0]
+            ln = slen[a:b][at]
+            # (the 3' end of the outermost pair, exclusive: the partner of base i in the caller's own string)
+            jj_k = np.array([j for _, j, _ in structure_helices(structures[k])], dtype=np.int32).reshape(-1)
+            stems.append((at.astype(np.int32), jj_k, ln.copy(), sprob[a:b][at].copy()))
+        return lists, stems
 
     # ---- accessibility (DESIGN.md section 19)
     def accessibility(self, x, max_width=16):

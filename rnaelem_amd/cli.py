@@ -120,6 +120,18 @@ def build_parser():
                                      help="base pairs labelled by the pair of pattern nodes that emits them: one line per entry with "
                                           "sequence id, i, j, the two nodes and the probability (io.stem_pair_line)")
     sub.choices["scan"].add_argument("--stem-min-prob", type=float, default=0.01, help="smallest probability listed in --out-stem-pairs")
+    sub.choices["scan"].add_argument("--out-helices", default=None,
+                                     help="helix posteriors, the joint probability that a run of directly stacked pairs forms: one line "
+                                          "per entry with sequence id, i, j of the outermost pair (as --out-stem-pairs), the number of "
+                                          "pairs and the probability (io.helix_line)")
+    sub.choices["scan"].add_argument("--helix-min-prob", type=float, default=0.01, help="smallest probability listed in --out-helices")
+    sub.choices["scan"].add_argument("--helix-min-len", type=int, default=2, help="shortest helix listed in --out-helices")
+    sub.choices["scan"].add_argument("--helix-max-len", type=int, default=16, help="longest helix listed in --out-helices (1 .. 32)")
+    sub.choices["scan"].add_argument("--out-mea-helices", default=None,
+                                     help="the stems of the maximum expected accuracy structure at --mea-gamma: one line per stem with "
+                                          "sequence id, i, j, length, the joint probability of the whole stem and the smallest pair "
+                                          "posterior in it (io.mea_helix_line); costs one MEA call (shared with --out-mea) and one "
+                                          "helix call (shared with --out-helices)")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -288,10 +300,12 @@ def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
 def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0,
                   out_samples=None, n_samples=100, sample_seed=0, out_context=None, out_nodes=None, out_sites=None, site_gamma=1.0,
                   max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0, out_access=None, access_width=16, out_logo=None,
-                  logo_min_exist=0.0, out_stems=None, out_stem_pairs=None, stem_min_prob=0.01):
+                  logo_min_exist=0.0, out_stems=None, out_stem_pairs=None, stem_min_prob=0.01, out_helices=None, helix_min_prob=0.01,
+                  helix_min_len=2, helix_max_len=16, out_mea_helices=None):
     from .distributed import assigned_range
     stem_parts = None if out_stems is None else out_stems + ".seqs"   # (as logo_parts)
     want_stems = out_stems is not None or out_stem_pairs is not None
+    want_helices = out_helices is not None or out_mea_helices is not None
     slots = eng.stem_slots() if want_stems else None                  # (the model's: once per run)
     logo_parts = None if out_logo is None else out_logo + ".seqs"     # (per-sequence counts, joined in input order before the sum)
     nodes = eng.describe()["node"]
@@ -304,15 +318,18 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
             if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None \
-                    and out_contrast is None and out_access is None and out_logo is None and not want_stems:
+                    and out_contrast is None and out_access is None and out_logo is None and not want_stems and not want_helices:
                 for (rid, codes, _), r in zip(part, res):
                     yield io.scan_record(rid, codes, r, nodes)
                 continue
             # (the same loaded batch; with both files one device call gives the pairs and the structures)
-            if out_mea is None:
+            if out_mea is None and out_mea_helices is None:
                 prs = eng.pair_posteriors(m["x"], pair_min_prob) if out_pairs is not None else None
-            else:
+            elif out_mea_helices is None:
                 structs, scores, prs = eng.mea_structures(m["x"], mea_gamma, pair_min_prob if out_pairs is not None else None)
+            else:   # (the stems' smallest pair posterior comes from this call's own list: every pair, cut to --pair-min-prob for the pairs file)
+                structs, scores, every = eng.mea_structures(m["x"], mea_gamma, 0.0)
+                prs = [(ii[pp >= pair_min_prob], jj[pp >= pair_min_prob], pp[pp >= pair_min_prob], unp) for ii, jj, pp, unp in every]
             smp = eng.sample_structures(m["x"], n_samples, sample_seed, lo + c0) if out_samples is not None else None
             ctx = eng.context_profiles(m["x"]) if out_context is not None else None
             # (with both files one node pass gives the profiles and the sites)
@@ -327,6 +344,10 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             if want_stems:      # (one call gives the counts and the list)
                 stm = eng.stem_profiles(m["x"], stem_min_prob if out_stem_pairs is not None else np.inf)
                 stm_counts, stm_lists = stm if out_stem_pairs is not None else (stm, None)
+            if want_helices:    # (one call gives the list and the stems of the MEA structures)
+                hlx = eng.helix_posteriors(m["x"], helix_min_prob if out_helices is not None else np.inf, helix_min_len, helix_max_len,
+                                           structs if out_mea_helices is not None else None)
+                hlx_lists, hlx_stems = hlx if out_mea_helices is not None else (hlx, None)
             for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
                 texts = [io.scan_record(rid, codes, r, nodes)]
                 if out_pairs is not None:
@@ -354,14 +375,19 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                                                            "%d%s" % (slots[t, 1], nodes[slots[t, 1]]), q) for i, j, t, q in zip(*stm_lists[k])))
                 if out_stems is not None:
                     texts.append(io.stem_counts_record(rid, r["exist_prob"], stm_counts[k]))
+                if out_helices is not None:
+                    texts.append("".join(io.helix_line(rid, i + 1, j, n, p) for i, j, n, p in zip(*hlx_lists[k])))
+                if out_mea_helices is not None:
+                    texts.append("".join(io.mea_helix_line(rid, i + 1, j, n, p, api.stem_min_posterior(every[k], i, j, n))
+                                         for i, j, n, p in zip(*hlx_stems[k])))
                 yield tuple(texts)
 
     if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None and out_contrast is None \
-            and out_access is None and out_logo is None and not want_stems:
+            and out_access is None and out_logo is None and not want_stems and not want_helices:
         sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
     else:
         outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast, out_access, logo_parts,
-                                   out_stem_pairs, stem_parts) if o is not None]
+                                   out_stem_pairs, stem_parts, out_helices, out_mea_helices) if o is not None]
         sharded_write(recs, outs, rank, world, scan_part, barrier)
     if out_logo is not None:
         if rank == 0:
@@ -406,7 +432,8 @@ def cmd_scan(a):
     _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
                   a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites,
                   a.out_contrast, a.contrast_min_prob, a.contrast_gamma, a.out_access, a.access_width, a.out_logo, a.logo_min_exist,
-                  a.out_stems, a.out_stem_pairs, a.stem_min_prob)
+                  a.out_stems, a.out_stem_pairs, a.stem_min_prob, a.out_helices, a.helix_min_prob, a.helix_min_len, a.helix_max_len,
+                  a.out_mea_helices)
     if world > 1:
         dist.destroy_process_group()
 

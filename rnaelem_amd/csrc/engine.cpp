@@ -43,6 +43,7 @@
 #include "joint_rules.h"
 #include "sample_rules.h"
 #include "stem_rules.h"
+#include "helix_rules.h"
 #include "staged_list.h"
 #include "table_slots.h"
 
@@ -235,6 +236,13 @@ class Engine {
   int stem_slots(int32_t* node_left, int32_t* node_right, int cap) const;
   void stem_profile(const double* x, int n_param, double min_prob, double* counts, int64_t* n_entries);
   void stem_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, double* q, int64_t cap);
+  // helix posteriors (helix_rules.h): the joint probability of every run of min_len .. max_len stacked pairs that
+  // reaches min_prob; with a finite min_prob the list stays on the device for helix_list.  structure: dot-bracket strings in seq_off
+  // indexing or null; stem_len / stem_prob (seq_off indexing, either may be null): at the 5' base of the outermost pair of every
+  // stem of the structure its length and the joint probability of the whole stem, 0 / NaN elsewhere.
+  void helix_posteriors(const double* x, int n_param, int max_len, int min_len, double min_prob, int64_t* n_entries,
+                        const char* structure, int32_t* stem_len, double* stem_prob);
+  void helix_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* len, double* p, int64_t cap);
   // accessibility (access_rules.h): max_width doubles per position of the batch, the widths 1 .. max_width
   void accessibility(const double* x, int n_param, int max_width, double* access);
   // maximum expected accuracy motif alignments and site lists over that profile (node_mea_rules.h); outputs as
@@ -405,10 +413,11 @@ class Engine {
   void stream_pairs(const double* x, int n_param, double min_prob, double* unpaired, const MeaOut* mea);
   void stream_samples(const double* x, int n_param, int n_samples, uint64_t seed, int64_t index_base, const SampleOut& out);
   void stream_cond(const double* x, int n_param, double min_prob, const CondOut& out);
-  // the lists of the last pair, conditional and stem call (staged_list.h), each in buffers of its own
+  // the lists of the last pair, conditional, stem and helix call (staged_list.h), each in buffers of its own
   StagedList pairs_{"pair_list", "pair_posteriors", 1, false};
   StagedList conds_{"pair_conditional_list", "pair_conditional", 2, false};
   StagedList stems_{"stem_list", "stem_profile", 1, true};
+  StagedList helices_{"helix_list", "helix_posteriors", 1, true};
   size_t scratch_slots_ = 0;   // slots the per-slot scratch of the running scan-family call is sized for (slot_scratch)
   DevBuf d_pr_P_, d_pr_unp_;   // pair posteriors: the P(i, d) scratch of the table slots, the unpaired vector of the call
   // MEA structures: the M table and choice scratch of the table slots (as d_pr_P_), the structures and the scores of the call
@@ -424,6 +433,10 @@ class Engine {
   DevBuf d_jn_lists_, d_jn_X_, d_jn_vec_, d_jn_prof_, d_jn_counts_;   // joint profiles: lists and slot map, per-cell scratch per slot, the log-space form's vectors, the results
   // stem profiles: the transitions by slot, Q of the table slots, the parse marks and counts of the call
   DevBuf d_sp_lists_, d_sp_X_, d_sp_has_, d_sp_counts_;
+  // helix posteriors: P, the units (count, i, d, reached length) and their values per table slot, the log-space form's vectors, the
+  // stems of the caller's structures (offsets per sequence, i, d, length) and their probabilities
+  DevBuf d_hx_P_, d_hx_nu_, d_hx_ui_, d_hx_ud_, d_hx_nlen_, d_hx_X_, d_hx_vec_;
+  DevBuf d_hx_soff_, d_hx_si_, d_hx_sd_, d_hx_slen_, d_hx_sp_;
   DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
   // node MEA: the chain lists, the backpointer scratch (M bytes per position), the rows, sites per sequence, start / end / score / confidence per slot
   DevBuf d_nm_lists_, d_nm_bp_, d_nm_node_, d_nm_ns_, d_nm_s0_, d_nm_s1_, d_nm_sc_, d_nm_cf_;
@@ -990,6 +1003,7 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   pairs_.invalidate();
   conds_.invalidate();
   stems_.invalidate();
+  helices_.invalidate();
   streaming_ = false;
   train_rows_ = false;
   BatchShape shape = check_batch(seq, off, qual, qoff, fix, n);
@@ -2971,6 +2985,177 @@ void Engine::stem_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, doub
   stems_.fetch(seq, i, j, q, nullptr, slot, cap);
 }
 
+// ---- helix posteriors (helix_rules.h).  The host parses the stems of the caller's structures.  The scan's first sum
+// pass per group, then on the group's table slots, before the next group of the stream reuses them: P of every cell (k4_pairs), the
+// units -- the kept cells whose P reaches min_prob -- (k_helix_units), the chains of the units and of the stems (k_helix_chains) and
+// the list entries into the staging ranges (k_helix_seq).  The log-space form -- the fused scan kernel up to its first outside pass,
+// then the same chain on its dense tables -- for the sequences that leave the double range and under pipeline 3, with k_helix_seq
+// behind the launch.  Then the batch list in (sequence, i, j, len) order.  The staging is sized by the bound kept cells x
+// (max_len - min_len + 1).  Every buffer is the call's own: leaves the lists of the last pair, conditional and stem call alone.
+void Engine::helix_posteriors(const double* x, int n_param_in, int max_len, int min_len, double min_prob, int64_t* n_entries,
+                              const char* structure, int32_t* stem_len, double* stem_prob) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (max_len < 1 || max_len > kHelixMaxLen) throw ArgError("helix_posteriors: max_len must lie in 1 .. 32");
+  if (min_len < 1 || min_len > max_len) throw ArgError("helix_posteriors: min_len must lie in 1 .. max_len");
+  if (!(min_prob >= 0.)) throw ArgError("helix_posteriors: min_prob must be >= 0");
+  if (structure && !stem_len && !stem_prob) throw ArgError("helix_posteriors: a structure needs stem_len or stem_prob");
+  if (n_seq_ <= 0) throw StateError("helix_posteriors before load_batch");
+  const int n = n_seq_;
+  const bool want_list = min_prob < HUGE_VAL;
+  // the stems of every sequence: (i, d, len) of the outermost pair, sequences and 5' ends in increasing order
+  std::vector<int64_t> soff;
+  std::vector<int32_t> s_i, s_d, s_len;
+  if (structure) {
+    soff.assign((size_t)n + 1, 0);
+    std::vector<int32_t> mate, open;
+    for (int t = 0; t < n; ++t) {
+      const char* db = structure + (h_seq_off_[t] - h_seq_off_[0]);
+      const int L = h_seq_off_[t + 1] - h_seq_off_[t];
+      mate.assign((size_t)L, -1);
+      open.clear();
+      for (int p = 0; p < L; ++p) {
+        if (db[p] == '(') open.push_back(p);
+        else if (db[p] == ')') {
+          if (open.empty()) throw ArgError("helix_posteriors: unbalanced structure");
+          mate[p] = open.back(); mate[open.back()] = p;
+          open.pop_back();
+        } else if (db[p] != '.') throw ArgError("helix_posteriors: a structure holds ( ) . only");
+      }
+      if (!open.empty()) throw ArgError("helix_posteriors: unbalanced structure");
+      for (int p = 0; p < L; ++p) {
+        const int r = mate[p];
+        if (r < p || (p > 0 && r + 1 < L && mate[p - 1] == r + 1)) continue;   // (no 5' base, or not the outermost pair of its stem)
+        int len = 1;
+        while (p + len < r - len && mate[p + len] == r - len) ++len;
+        s_i.push_back(p); s_d.push_back(r - p + 1); s_len.push_back(len);
+      }
+      soff[(size_t)t + 1] = (int64_t)s_i.size();
+    }
+  }
+  const size_t n_stems = s_i.size();
+  std::vector<double> s_p(n_stems, 0.);
+  auto stems_out = [&] {   // the stems' columns of the caller, from s_p
+    if (!structure) return;
+    const size_t n_seqpos = (size_t)(h_seq_off_[n] - h_seq_off_[0]);
+    if (stem_len) std::fill(stem_len, stem_len + n_seqpos, 0);
+    if (stem_prob) std::fill(stem_prob, stem_prob + n_seqpos, std::nan(""));
+    for (int t = 0; t < n; ++t)
+      for (int64_t k = soff[t]; k < soff[(size_t)t + 1]; ++k) {
+        const size_t at = (size_t)(h_seq_off_[t] - h_seq_off_[0]) + (size_t)s_i[(size_t)k];
+        if (stem_len) stem_len[at] = s_len[(size_t)k];
+        if (stem_prob) stem_prob[at] = s_p[(size_t)k];
+      }
+  };
+  helices_.invalidate();
+  if (streaming_) {
+    StagedList::Host list;
+    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+      const size_t at = (size_t)(h_seq_off_[c0] - h_seq_off_[0]);
+      e.helix_posteriors(x, n_param_in, max_len, min_len, min_prob, nullptr, structure ? structure + at : nullptr,
+                         stem_len ? stem_len + at : nullptr, stem_prob ? stem_prob + at : nullptr);
+      list.append(e.helices_, c0);
+    });
+    helices_.adopt(list, st_);
+    if (n_entries) *n_entries = helices_.count();
+    return;
+  }
+  require_resident("helix_posteriors", n_param_in);
+  upload_params(x, lay_, false);
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  ScanPos pos(n_seqpos, n);
+  const bool no_rss = (flags_ & ELEMDP_NO_RSS) != 0;
+  HelixArgs ha;
+  std::memset(&ha, 0, sizeof(ha));
+  if (structure) {
+    d_hx_soff_.upload(soff, st_); d_hx_si_.upload(s_i, st_); d_hx_sd_.upload(s_d, st_); d_hx_slen_.upload(s_len, st_);
+    d_hx_sp_.alloc(8 * std::max<size_t>(n_stems, 1));
+    HIP_OK(hipMemsetAsync(d_hx_sp_.as<void>(), 0, 8 * std::max<size_t>(n_stems, 1), st_));
+    HIP_OK(hipStreamSynchronize(st_));   // (the host vectors go out of use with the copies; the probabilities are clear before any group runs)
+    ha.soff = d_hx_soff_.as<int64_t>();
+    ha.s_i = d_hx_si_.as<int32_t>(); ha.s_d = d_hx_sd_.as<int32_t>(); ha.s_len = d_hx_slen_.as<int32_t>();
+    ha.s_p = d_hx_sp_.as<double>();
+  }
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  ha.plans = plan_.d_plans.as<SeqPlan>();
+  ha.seq_out = d_seq_out_.as<double>(); ha.out_stride = out_stride_;
+  ha.okbits = d_okbits1_.as<uint32_t>();
+  ha.max_len = max_len; ha.min_len = min_len;
+  ha.no_rss = no_rss ? 1 : 0;
+  ha.min_prob = min_prob;
+  const size_t pcells = helix_units_cap(Lmax_, Wmax_);
+  ha.p_stride = pcells; ha.u_stride = pcells;
+  if (want_list) {   // staging ranges: a sequence's list holds at most max_len - min_len + 1 entries per kept cell
+    const StagedList::Staging sl = helices_.begin(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, max_len - min_len + 1, st_);
+    ha.koff = sl.koff; ha.cnt = sl.cnt;
+    ha.st_i = sl.st_i; ha.st_j = sl.st_j; ha.st_k = sl.st_k; ha.st_h = sl.st_v[0];
+  }
+  const bool work = want_list || structure;   // (else: nothing to compute, no sweep)
+  auto at_slot = [&](HelixArgs& hk, size_t slot0) {
+    hk.n_units = slot_scratch<int32_t>(d_hx_nu_, 1, slot0);
+    hk.ui = slot_scratch<int32_t>(d_hx_ui_, pcells, slot0);
+    hk.ud = slot_scratch<int32_t>(d_hx_ud_, pcells, slot0);
+    hk.nlen = slot_scratch<int32_t>(d_hx_nlen_, pcells, slot0);
+    hk.X = slot_scratch<double>(d_hx_X_, pcells * (size_t)max_len, slot0);
+  };
+  int n_flagged = 0;
+  if (work) {
+    PairArgs pa = pair_batch_args();
+    pa.p_stride = pcells;
+    n_flagged = scan_both_forms(pos, [&](LinArgs& a) {
+      if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("helix_posteriors: the scan sweeps another automaton than the engine's");
+      at_slot(ha, 0);
+      ha.P = slot_scratch<double>(d_hx_P_, pcells);
+      pair_plane_fields(pa, a);
+      ha.skip_flagged = 1;
+    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      HelixArgs hk = ha;
+      hk.idx = ak.grp;
+      at_slot(hk, slot0);
+      if (!no_rss) {   // (else the band tables are not read: no units, the stems keep their 0)
+        if (want_list) {
+          PairArgs pk = pa;
+          pk.idx = ak.grp;
+          pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+          pk.P = slot_scratch<double>(d_hx_P_, pcells, slot0);
+          hk.P = pk.P;
+          HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
+          HIP_OK(launch_helix_units(hk, G, st));
+        }
+        HIP_OK(launch_helix_chains(ak, hk, G, (Lg + 1) * (Wg + 1), st));
+      }
+      if (want_list) HIP_OK(launch_helix_seq(hk, G, st));
+    },
+    // ---- the log-space form, in chunks of at most as many sequences as the table slots hold (the scratch is bounded by the chunk)
+    [&](DpArgs& d, int n_blocks, int n_log) {
+      at_slot(ha, 0);
+      d_hx_vec_.alloc(8 * 2 * (size_t)d.lay.S * kThreads * (size_t)std::max(n_blocks, 1));
+      d.hlx = ha;
+      d.hlx.vec = d_hx_vec_.as<double>();
+      return log_chunk(n_blocks, n_log);
+    }, [&](const int32_t* idx, int C) {
+      HelixArgs hk = ha;
+      hk.idx = idx;
+      hk.skip_flagged = 0;
+      hk.no_rss = 0;   // (the fused kernel wrote the number of units of every sequence of the launch: 0 without secondary structure)
+      if (want_list) HIP_OK(launch_helix_seq(hk, C, st_));
+    });
+  }
+  finish_call(n_flagged, [&] {
+    if (want_list) helices_.finish(st_); else helices_.set_empty();   // the list in (sequence, i, j, len) order
+    if (n_stems) HIP_OK(hipMemcpyAsync(s_p.data(), d_hx_sp_.as<void>(), 8 * n_stems, hipMemcpyDeviceToHost, st_));
+  });
+  stems_out();
+  if (n_entries) *n_entries = helices_.count();
+}
+
+void Engine::helix_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* len, double* p, int64_t cap) {
+  require_device();
+  DeviceGuard dg(device_);
+  helices_.fetch(seq, i, j, p, nullptr, len, cap);
+}
+
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h).  The node pass of
 // node_profile, then k_node_mea once over the profile of the whole batch on the engine's stream, behind the last group and the
 // log-space form.  The profile goes to the host only where the caller gave a buffer.  Leaves the list of the last pair call alone.
@@ -3454,6 +3639,19 @@ int elemdp_stem_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, int
   ELEMDP_TRY
   if (!h) throw elemdp::ArgError("elemdp_stem_list: null handle");
   h->e->stem_list(seq, i, j, slot, q, cap);
+  ELEMDP_CATCH
+}
+int elemdp_helix_posteriors(elemdp_handle* h, const double* x, int32_t n_param, int32_t max_len, int32_t min_len, double min_prob,
+                            int64_t* n_entries, const char* structure, int32_t* stem_len, double* stem_prob) {
+  ELEMDP_TRY
+  if (!h || !x) throw elemdp::ArgError("elemdp_helix_posteriors: null argument");
+  h->e->helix_posteriors(x, n_param, max_len, min_len, min_prob, n_entries, structure, stem_len, stem_prob);
+  ELEMDP_CATCH
+}
+int elemdp_helix_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, int32_t* len, double* p, int64_t cap) {
+  ELEMDP_TRY
+  if (!h) throw elemdp::ArgError("elemdp_helix_list: null handle");
+  h->e->helix_list(seq, i, j, len, p, cap);
   ELEMDP_CATCH
 }
 int elemdp_node_mea(elemdp_handle* h, const double* x, int32_t n_param, double gamma, int32_t max_sites, double* profile,

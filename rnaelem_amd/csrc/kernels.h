@@ -175,6 +175,29 @@ struct StemArgs {
   int32_t* st_i; int32_t* st_j; uint8_t* st_k; double* st_q;   // staging (null: no list is kept)
 };
 
+// ---- helix posteriors (helix_rules.h, helix_kernels.hip).  A launch covers the G sequences idx[0 .. G) of one group or chunk; slot g
+// of the launch owns one int of n_units, u_stride ints each of ui, ud and nlen, and max_len u_stride doubles of X: its units -- outer
+// kept cells (ui, ud) in (i, d) order --, the lengths 1 .. nlen[r] unit r reached and their values (helix_at, rows of max_len).  The
+// list entries of batch index n go to the staging range that starts at (max_len - min_len + 1) koff[n]; the stems of its caller-given
+// structure are s_i / s_d / s_len[soff[n] .. soff[n + 1]) and their joint probabilities go to s_p.
+struct HelixArgs {
+  const SeqPlan* plans;           // batch plans (batch index)
+  const int32_t* idx;             // idx[g] = batch index of the sequence in slot g (launch_helix_units, launch_helix_seq)
+  const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
+  int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)
+  const uint32_t* okbits;         // the pair mask of the batch
+  int32_t max_len, min_len;
+  int32_t no_rss;                 // a model without secondary structure: no units, the band tables are not read
+  double min_prob;
+  const double* P; size_t p_stride;   // scaled-linear form: P(i, d) of the slot ([i][d], rows of W+1; launch_pair_cells) picks the units
+  int32_t* n_units; int32_t* ui; int32_t* ud; int32_t* nlen; size_t u_stride;
+  double* X;
+  double* vec;                    // log-space form: two state vectors per thread of a workgroup of the fused scan kernel
+  const int64_t* koff; int64_t* cnt;   // kept cells before batch index n (launch_pair_kept / launch_pair_prefix), entries staged
+  int32_t* st_i; int32_t* st_j; uint8_t* st_k; double* st_h;   // staging (null: no list is kept)
+  const int64_t* soff; const int32_t* s_i; const int32_t* s_d; const int32_t* s_len; double* s_p;   // stems (soff null: none)
+};
+
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h, node_mea_kernels.hip) over the profile of the
 // whole batch: batch index n with seq_base b and length L writes the row of slot k at node + max_sites * b + k * L (the sampler's
 // layout), n_sites[n], and start / end / score / conf at [n * max_sites + k]
@@ -246,6 +269,10 @@ struct DpArgs {
   // SCAN, pair posteriors by motif node pair (stem_rules.h, log-space form): stm.X non-null = stop after inside + the first outside
   // pass and write Q of the sequence order[w] to slot w of stm (k_stem_counts and k_stem_seq read it behind the launch)
   StemArgs stm;
+  // SCAN, helix posteriors (helix_rules.h, log-space form): hlx.X non-null = stop after inside + the first outside pass and write the
+  // units of the sequence order[w] -- every cell of its band, in (i, d) order -- to slot w of hlx (k_helix_seq reads them behind the
+  // launch) and the probabilities of its stems to hlx.s_p
+  HelixArgs hlx;
 };
 
 // arguments of the diagonal-synchronous train pipeline (train_kernels.hip)
@@ -527,14 +554,22 @@ hipError_t launch_joint_counts(const JointArgs& c, int G, hipStream_t st);
 hipError_t launch_stem_cells(const LinArgs& a, const StemArgs& c, int G, int cells_max, hipStream_t st);
 hipError_t launch_stem_counts(const StemArgs& c, int G, int Lmax, int Wmax, hipStream_t st);
 hipError_t launch_stem_seq(const StemArgs& c, int G, hipStream_t st);
+
+// ---- helix posteriors (helix_kernels.hip), behind launch_lin_scan_group (SCAN_PASS_START) and launch_pair_cells on the same slots
+// and stream: k_helix_units (one workgroup per sequence: the kept cells whose P reaches min_prob, in (i, d) order), k_helix_chains
+// (one wave per unit or stem: the chain of helix_rules.h); k_helix_seq (one workgroup per sequence: its list entries in (i, j, len)
+// order into its staging range) behind them, or behind the fused scan kernel (DpArgs::hlx); launch_list_scatter: the batch list
+hipError_t launch_helix_units(const HelixArgs& c, int G, hipStream_t st);
+hipError_t launch_helix_chains(const LinArgs& a, const HelixArgs& c, int G, int cells_max, hipStream_t st);
+hipError_t launch_helix_seq(const HelixArgs& c, int G, hipStream_t st);
 // k_node_mea behind the node pass of the whole batch (both forms), on the engine's stream: one wave per sequence
 hipError_t launch_node_mea(const NodeMeaArgs& a, int n_seq, hipStream_t st);
-// ---- the staged lists of the pair, conditional and stem calls (staged_list.h, pair_kernels.hip).  The columns of one list, as
+// ---- the staged lists of the pair, conditional, stem and helix calls (staged_list.h, pair_kernels.hip).  The columns of one list, as
 // k_list_scatter takes them: batch index n has cnt[n] entries in staging from mult * koff[n] on, and its entries of the final list
 // start at off[n].  A null st_v[1] or st_k: the list has no second value column, or no label column.
 struct ListCols {
   const int64_t* koff; const int64_t* cnt; const int64_t* off;
-  int64_t mult;                   // staging entries per kept cell (1; the stem slots K of the stem list)
+  int64_t mult;                   // staging entries per kept cell (1; the stem slots K; the lengths of the helix list)
   const int32_t* st_i; const int32_t* st_j; const double* st_v[2]; const uint8_t* st_k;
   int32_t* seq; int32_t* i; int32_t* j; double* v[2]; int32_t* k;   // final list: seq = n, the label widened to int32
 };

@@ -26,6 +26,7 @@
 #include "node_rules.h"
 #include "joint_rules.h"
 #include "stem_rules.h"
+#include "helix_rules.h"
 #include "pair_rules.h"
 #include "plan_rules.h"
 #include "sample_lane.h"
@@ -624,6 +625,37 @@ __device__ __forceinline__ void access_log_units(const ModelView& m, const SeqVi
   }
 }
 
+// helix posteriors (helix_rules.h) on the dense log-space tables of sequence n in slot w: one thread per unit, every cell of the band
+// a unit in (i, d) order (a cell that is not kept reaches no length and is not read), then one thread per stem of the caller-given
+// structure; two state vectors per thread in global scratch.  live false: no parse, or no secondary structure in the model -- no
+// units, and the stem probabilities keep the 0 the call cleared them to.
+__device__ __forceinline__ void helix_log_units(const ModelView& m, const SeqView& q, const TableView& Tin, const TableView& Tout,
+                                             double ZL, const HelixArgs& c, int w, int n, bool live) {
+  const int tid = threadIdx.x;
+  const int L = q.L, W = q.W, S = m.lay.S, ncell = (L + 1) * (W + 1);
+  const bool list = c.st_i != nullptr;
+  if (tid == 0) c.n_units[w] = live && list ? ncell : 0;
+  if (!live) return;
+  const HelixLog f(ZL);
+  const OneLane ln;
+  double* v0 = c.vec + ((size_t)blockIdx.x * kThreads + tid) * 2 * S;
+  int32_t* ui = c.ui + (size_t)w * c.u_stride;
+  int32_t* ud = c.ud + (size_t)w * c.u_stride;
+  int32_t* nlen = c.nlen + (size_t)w * c.u_stride;
+  double* X = c.X + (size_t)w * c.u_stride * (size_t)c.max_len;
+  if (list)
+    for (int t = tid; t < ncell; t += kThreads) {
+      const int i = t / (W + 1), d = t - i * (W + 1);
+      int top = 0;
+      if (d >= 2 && q.pair_ok(i, d))
+        top = helix_chain(f, ln, m, q, Tin, Tout, i, d, c.max_len, c.min_prob, v0, v0 + S, X + helix_at(c.max_len, t, 1)).n;
+      ui[t] = i; ud[t] = d; nlen[t] = top;
+    }
+  if (c.soff)
+    for (int64_t t = c.soff[n] + tid; t < c.soff[n + 1]; t += kThreads)
+      c.s_p[t] = helix_stem(f, ln, m, q, Tin, Tout, c.s_i[t], c.s_d[t], c.s_len[t], v0, v0 + S);
+}
+
 // ---------------------------------------------------------------------------------------------
 // the DP kernel: TRAIN = K2 + 2 x K3 fused, BPP = K1, SCAN = K4 + K5 + K6
 // ---------------------------------------------------------------------------------------------
@@ -861,6 +893,10 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
               if (i + d > L) continue;
               for (int k = 0; k < a.stm.K; ++k) X[stem_at(L, W, k, i, d)] = stem_value(f, sl, m, q, Tin, Tout, d, i, k);
             }
+          continue;
+        }
+        if (a.hlx.X) {   // helix posteriors (helix_rules.h): the chains of this first pass, one unit or stem per lane
+          helix_log_units(m, q, Tin, Tout, ZL, a.hlx, w, n, ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL && !no_rss);
           continue;
         }
         if (a.acc.T) {   // accessibility (access_rules.h): the units (term, position) of this first pass

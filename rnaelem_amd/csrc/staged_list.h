@@ -1,4 +1,4 @@
-// staged_list.h -- the batch lists of the pair, conditional and stem calls of an Engine (engine.cpp): their buffers and their format.
+// staged_list.h -- the batch lists of the pair, conditional, stem and helix calls of an Engine (engine.cpp): their buffers and their format.
 #pragma once
 #include <cstdint>
 

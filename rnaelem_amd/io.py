@@ -489,6 +489,41 @@ def stem_pair_line(rid, i, j, left, right, q):
     return "%s\t%d\t%d\t%s\t%s\t%.6g\n" % (rid, i, j, left, right, q)
 
 
+def helix_line(rid, i, j, n, p):
+    """One line of the `scan --out-helices` file: the sequence id, the 1-based positions i < j of the two bases of the outermost
+    pair (as the `scan --out-stem-pairs` file numbers them: cell (i0, j0) -> i0+1, j0), the number n of directly stacked pairs
+    (i, j), (i+1, j-1), .. and the probability p that all of them form."""
+    return "%s\t%d\t%d\t%d\t%.6g\n" % (rid, i, j, n, p)
+
+
+def read_helices(path):
+    """-> list of dict(id, i, j, len, p) from a `scan --out-helices` file, i 0-based and j exclusive (the engine's cells)."""
+    out = []
+    for line in open(path).read().split("\n")[:-1]:
+        f = line.split("\t")
+        if len(f) != 5:
+            raise ValueError("helices file %r: five fields expected in %r" % (path, line))
+        out.append(dict(id=f[0], i=int(f[1]) - 1, j=int(f[2]), len=int(f[3]), p=float(f[4])))
+    return out
+
+
+def mea_helix_line(rid, i, j, n, p_joint, p_min):
+    """One line of the `scan --out-mea-helices` file, a stem of the sequence's maximum expected accuracy structure: the fields of
+    helix_line with the joint probability of the whole stem, then the smallest pair posterior in it."""
+    return "%s\t%d\t%d\t%d\t%.6g\t%.6g\n" % (rid, i, j, n, p_joint, p_min)
+
+
+def read_mea_helices(path):
+    """-> list of dict(id, i, j, len, p, p_min) from a `scan --out-mea-helices` file, i 0-based and j exclusive."""
+    out = []
+    for line in open(path).read().split("\n")[:-1]:
+        f = line.split("\t")
+        if len(f) != 6:
+            raise ValueError("MEA helices file %r: six fields expected in %r" % (path, line))
+        out.append(dict(id=f[0], i=int(f[1]) - 1, j=int(f[2]), len=int(f[3]), p=float(f[4]), p_min=float(f[5])))
+    return out
+
+
 def write_stems(path, names, slots, counts, n_used, n_total=None):
     """The `scan --out-stems` file: a header `sequences: <used> / <read>` and `columns: N A C G U`, then one record per stem slot:
     `stem: <index><name> <index><name>` (the pattern nodes of the left and the right base), `occurrences: <expected number of
