@@ -436,6 +436,57 @@ int elemdp_helix_posteriors(elemdp_handle* h, const double* x, int32_t n_param, 
                             double min_prob, int64_t* n_entries,
                             const char* structure, int32_t* stem_len, double* stem_prob);
 int elemdp_helix_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, int32_t* len, double* p, int64_t cap);
+/* Loop posteriors under the motif model x: what every pair closes, and the two-loops.  Cells as in elemdp_pair_list:
+ * cell (i, j) pairs the 0-based bases i and j-1.  Over the ensemble of the scan's first sum pass (terminals ari and nasi,
+ * Z(ari, nasi): the ensemble of elemdp_pair_posteriors), exact from its inside / outside tables (loop_rules.h), every value clamped to
+ * [0, 1], nothing renormalised.  For a kept cell the five columns, in the order of ELEMDP_LOOP_H .. ELEMDP_LOOP_M: the probability
+ * that the pair closes a hairpin (H), stacks on the pair (i+1, j-1) (S), closes a bulge (B: one inner pair, one empty side), an
+ * interior loop (I: one inner pair, bases on both sides) or a multi-branch loop (M).  M is the probability of the closing event
+ * alone, whatever the shape of the loop: the joint probability of one particular multi-loop with all its branches is not formed.  The
+ * two-loop (i, j, k, l) is the event that the pair (i, j) lies directly around the pair (k, l) with at least one unpaired base
+ * between them; T is its probability; B and I are the sums of T over the two-loops of the cell.  H + S + B + I + M is the P of
+ * elemdp_pair_posteriors and T <= P wherever the tables' inside and outside agree.
+ *   min_prob:  >= 0, or +inf.  Finite: two lists are kept on the device.  The closing list (elemdp_loop_closing_list) holds the kept
+ *              cells whose P reaches min_prob, in (sequence, i, j) order, with p = P and the five columns (cols: 5 doubles per
+ *              entry): the membership rule and the order of elemdp_pair_list, applied to the P plane this call computes with the
+ *              pair call's own reduction.  A call sweeps the tables anew and two sweeps agree to rounding, not bit for bit (two
+ *              elemdp_pair_posteriors calls on one handle differ by a few 1e-16): against the list of a separate pair call at the
+ *              same min_prob the cells and their order are the same and p agrees to rounding, except that a cell whose P lies
+ *              within rounding of min_prob may be in one list only.  The two-loop list
+ *              (elemdp_loop_two_list) holds every two-loop with T >= min_prob, ordered by its outer cell in (sequence, i, j) order
+ *              and within an outer cell in the order of the plan's interior-loop items of that cell; at 0 it holds every two-loop
+ *              of the inside enumeration whose two cells are kept.  An outer cell whose P lies in the rounding margin below
+ *              min_prob (see counts) may have a two-loop listed without a closing entry.  +inf: no lists, and no staging is
+ *              allocated;
+ *   counts:    NULL, or 5 doubles per sequence: the expected number of loops of each type, the column sums over every kept cell
+ *              whatever min_prob is, reduced on the device in a fixed order.  Their total is the expected number of pairs.  With
+ *              counts every kept cell is walked; without, an outer cell whose P is below min_prob (less a relative margin of 2^-30
+ *              for rounding) is not: T <= P, so no entry is lost;
+ *   n_closing, n_two: NULL, or receive the lengths of the two lists;
+ *   structure: NULL, or dot-bracket strings in seq_off indexing (L bytes per sequence, ( ) . only).  loop_type and loop_prob
+ *              (seq_off indexing; one of them may be NULL) receive, at the position of the 5' base of every pair of the structure,
+ *              the type of the loop that pair closes there (ELEMDP_LOOP_H .. ELEMDP_LOOP_M) and the probability of that loop --
+ *              the column of the closing cell for H, S and M, the T of the two-loop for B and I --, with no threshold; elsewhere 0
+ *              and NaN.  A pair that is not a kept cell (a span above max_span among them) gives 0 exactly, and so does a two-loop
+ *              that is no item of the inside enumeration.  A B or I value is bit-equal to the entry of the two-loop list of the
+ *              same call.
+ * A sequence without any parse (Z = 0) has empty lists, counts 0 and loop probabilities 0, exactly; so has every sequence under
+ * ELEMDP_NO_RSS, where the band tables are not read.  Sequences that leave the double range of the scaled-linear tables, and every
+ * sequence under option pipeline 3, go through the same rule on the log-space tables of the fused scan kernel.  x NULL, min_prob
+ * negative or NaN, an unbalanced structure or one with other characters, a structure with both outputs NULL: ELEMDP_EINVAL; a call
+ * before elemdp_load_batch: ELEMDP_ESTATE; a list before any loop call on the resident batch: ELEMDP_ESTATE, with cap below the
+ * length of the list: ELEMDP_EINVAL (its arrays may be NULL); no device: ELEMDP_ENODEV.  elemdp_last_timing afterwards: [whole
+ * call, sum passes + loop kernels, sequences handed to the log-space form].  The other calls of the handle are unaffected; the lists
+ * of the last pair, conditional, stem and helix call stay valid, and those calls leave the loop lists alone. */
+#define ELEMDP_LOOP_H 1
+#define ELEMDP_LOOP_S 2
+#define ELEMDP_LOOP_B 3
+#define ELEMDP_LOOP_I 4
+#define ELEMDP_LOOP_M 5
+int elemdp_loop_posteriors(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double* counts, int64_t* n_closing,
+                           int64_t* n_two, const char* structure, int32_t* loop_type, double* loop_prob);
+int elemdp_loop_closing_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, double* cols, int64_t cap);
+int elemdp_loop_two_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, int32_t* k, int32_t* l, double* p, int64_t cap);
 /* Accessibility under the motif model x: with U = max_width, access[U * (seq_off[n] + p) + (w - 1)], p 0-based,
  * w = 1 .. U, is the probability that the bases p .. p+w-1 of sequence n are all unpaired, over the ensemble of the scan's first sum
  * pass (terminals ari and nasi, Z(ari, nasi): the ensemble of elemdp_pair_posteriors and elemdp_context_profile), from its inside /

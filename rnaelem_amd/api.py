@@ -24,7 +24,7 @@ SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "el
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
            "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_pair_terms", "elemdp_pair_terms_host", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
-           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_joint_profile", "elemdp_stem_slots", "elemdp_stem_profile", "elemdp_stem_list", "elemdp_helix_posteriors", "elemdp_helix_list", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
+           "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_joint_profile", "elemdp_stem_slots", "elemdp_stem_profile", "elemdp_stem_list", "elemdp_helix_posteriors", "elemdp_helix_list", "elemdp_loop_posteriors", "elemdp_loop_closing_list", "elemdp_loop_two_list", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
 
 
@@ -102,6 +102,9 @@ def load_library():
         L.elemdp_stem_list.argtypes = [hp, i32, i32, i32, i32, dp, C.c_int64]
         L.elemdp_helix_posteriors.argtypes = [hp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int64), C.c_char_p, i32, dp]
         L.elemdp_helix_list.argtypes = [hp, i32, i32, i32, i32, dp, C.c_int64]
+        L.elemdp_loop_posteriors.argtypes = [hp, dp, C.c_int32, C.c_double, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, i32, dp]
+        L.elemdp_loop_closing_list.argtypes = [hp, i32, i32, i32, dp, dp, C.c_int64]
+        L.elemdp_loop_two_list.argtypes = [hp, i32, i32, i32, i32, i32, dp, C.c_int64]
         L.elemdp_accessibility.argtypes = [hp, dp, C.c_int32, C.c_int32, dp]
         L.elemdp_node_mea.argtypes = [hp, dp, C.c_int32, C.c_double, C.c_int32, dp, u8, i32, i32, i32, dp, dp]
         L.elemdp_pair_list.argtypes = [hp, i32, i32, i32, dp, C.c_int64]
@@ -263,6 +266,51 @@ def stem_min_posterior(pairs, i, j, n):
     ii, jj, pp = pairs[0], pairs[1], pairs[2]
     have = {(int(a), int(b)): float(v) for a, b, v in zip(ii, jj, pp)}
     return min(have.get((i + t, j - t), 0.0) for t in range(n))
+
+
+LOOP_TYPES = " HSBIM"   # ELEMDP_LOOP_H .. ELEMDP_LOOP_M: the letter of loop type t is LOOP_TYPES[t]
+
+
+def structure_loops(db):
+    """The loops of a dot-bracket string, host only: (type, i, j, k, l) per pair, by increasing i.  The pair of the bases i and j-1
+    (i 0-based and j exclusive as in pair_posteriors) closes a loop of type 1 .. 5 for H S B I M (LOOP_TYPES): a hairpin without an
+    inner pair, a stack on the pair (i+1, j-1), a bulge with one inner pair and one empty side, an interior loop with one inner pair
+    and bases on both sides, a multi-branch loop with two or more inner pairs.  (k, l) is the cell of the inner pair of a bulge or an
+    interior loop, (-1, -1) otherwise.  Raises ValueError for an unbalanced string or one with characters other than ( ) ."""
+    mate, stack = [-1] * len(db), []
+    for p, c in enumerate(db):
+        if c == "(":
+            stack.append(p)
+        elif c == ")":
+            if not stack:
+                raise ValueError("unbalanced structure")
+            mate[p] = stack.pop()
+            mate[mate[p]] = p
+        elif c != ".":
+            raise ValueError("a structure holds ( ) . only")
+    if stack:
+        raise ValueError("unbalanced structure")
+    out = []
+    for p, r in enumerate(mate):
+        if r < p:
+            continue
+        inner, u = [], p + 1
+        while u < r:
+            if mate[u] > u:
+                inner.append((u, mate[u]))
+                u = mate[u] + 1
+            else:
+                u += 1
+        if not inner:
+            out.append((1, p, r + 1, -1, -1))
+        elif len(inner) > 1:
+            out.append((5, p, r + 1, -1, -1))
+        elif inner[0] == (p + 1, r - 1):
+            out.append((2, p, r + 1, -1, -1))
+        else:
+            k, l = inner[0]
+            out.append((3 if (k == p + 1) != (l == r - 1) else 4, p, r + 1, k, l + 1))
+    return out
 
 
 class Engine:
@@ -686,6 +734,60 @@ class Engine:
             jj_k = np.array([j for _, j, _ in structure_helices(structures[k])], dtype=np.int32).reshape(-1)
             stems.append((at.astype(np.int32), jj_k, ln.copy(), sprob[a:b][at].copy()))
         return lists, stems
+
+    # ---- loop posteriors
+    def loop_posteriors(self, x, min_prob=0.01, structures=None, counts=True):
+        """(closing, two, counts): what every pair closes and the two-loops, over the ensemble of pair_posteriors.  closing: per
+        sequence (i, j, p, cols) -- the cells of the pair list of pair_posteriors(x, min_prob) with its p and an (n, 5) array of the
+        probabilities that the pair closes a hairpin, stacks on (i+1, j-1), closes a bulge, an interior loop or a multi-branch loop
+        (H S B I M), in (i, j) order.  two: per sequence (i, j, k, l, p) -- the pair (i, j) directly around the pair (k, l) with
+        unpaired bases between them -- for every two-loop whose probability reaches min_prob, by outer cell in closing order.
+        counts: (n_seq, 5) expected numbers of loops of each type over every kept cell.  At min_prob 0 every kept cell and every
+        two-loop; at +inf no lists (empty arrays).  With structures (one dot-bracket string per sequence) returns
+        (closing, two, counts, loops): per sequence (type, i, j, k, l, p) of every loop of its structure (structure_loops), p the
+        probability of that loop with no threshold; 0 where its pair is not a kept cell.  counts False: no counts (None in
+        their place), and only the outer cells whose pair posterior reaches min_prob are walked."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        off = self._off
+        n_pos = int(off[-1]) if off is not None else 0
+        db = ltype = lprob = None
+        if structures is not None:
+            structures = [s if isinstance(s, str) else bytes(s).decode() for s in structures]
+            if off is None or len(structures) != self.n_seq or any(len(s) != int(off[k + 1] - off[k]) for k, s in enumerate(structures)):
+                raise ValueError("loop_posteriors: one structure per sequence, of its length")
+            db = "".join(structures).encode()
+            ltype = np.zeros(max(n_pos, 1), dtype=np.int32)
+            lprob = np.zeros(max(n_pos, 1))
+        counts = np.zeros((max(self.n_seq, 1), 5)) if counts else None
+        mc, mt = C.c_int64(), C.c_int64()
+        self._check(self._lib.elemdp_loop_posteriors(self._h, _dp(x), self.n_param, float(min_prob),
+                                                     _dp(counts) if counts is not None else None, C.byref(mc), C.byref(mt),
+                                                     db, _i32(ltype) if ltype is not None else None, _dp(lprob)))
+        mc, mt = mc.value, mt.value
+        seq, ii, jj = (np.zeros(max(mc, 1), dtype=np.int32) for _ in range(3))
+        p, cols = np.zeros(max(mc, 1)), np.zeros((max(mc, 1), 5))
+        tseq, ti, tj, tk, tl = (np.zeros(max(mt, 1), dtype=np.int32) for _ in range(5))
+        tp = np.zeros(max(mt, 1))
+        if np.isfinite(min_prob):
+            self._check(self._lib.elemdp_loop_closing_list(self._h, _i32(seq), _i32(ii), _i32(jj), _dp(p), _dp(cols), max(mc, 1)))
+            self._check(self._lib.elemdp_loop_two_list(self._h, _i32(tseq), _i32(ti), _i32(tj), _i32(tk), _i32(tl), _dp(tp), max(mt, 1)))
+        bounds = np.searchsorted(seq[:mc], np.arange(self.n_seq + 1))
+        closing = [(ii[a:b].copy(), jj[a:b].copy(), p[a:b].copy(), cols[a:b].copy()) for a, b in zip(bounds[:-1], bounds[1:])]
+        bounds = np.searchsorted(tseq[:mt], np.arange(self.n_seq + 1))
+        two = [(ti[a:b].copy(), tj[a:b].copy(), tk[a:b].copy(), tl[a:b].copy(), tp[a:b].copy()) for a, b in zip(bounds[:-1], bounds[1:])]
+        counts = counts[:self.n_seq] if counts is not None else None
+        if structures is None:
+            return closing, two, counts
+        loops = []
+        for k in range(self.n_seq):
+            a = int(off[k])
+            ls = structure_loops(structures[k])
+            cols5 = [np.array([l[c] for l in ls], dtype=np.int32).reshape(-1) for c in range(5)]
+            at = cols5[1]
+            if not np.array_equal(ltype[a + at], cols5[0]):
+                raise RuntimeError("loop_posteriors: the library and structure_loops parse sequence %d differently" % k)
+            loops.append(tuple(cols5) + (lprob[a + at].copy(),))
+        return closing, two, counts, loops
 
     # ---- accessibility (DESIGN.md section 19)
     def accessibility(self, x, max_width=16):

@@ -132,6 +132,16 @@ def build_parser():
                                           "sequence id, i, j, length, the joint probability of the whole stem and the smallest pair "
                                           "posterior in it (io.mea_helix_line); costs one MEA call (shared with --out-mea) and one "
                                           "helix call (shared with --out-helices)")
+    sub.choices["scan"].add_argument("--out-loops", default=None,
+                                     help="loop posteriors, what every listed pair closes: one line per entry with sequence id, type "
+                                          "letter (H S B I M), i, j of the closing pair (as --out-helices), k, l of the inner pair of "
+                                          "a bulge or an interior loop (- - otherwise) and the probability (io.loop_line)")
+    sub.choices["scan"].add_argument("--loop-min-prob", type=float, default=0.01, help="smallest pair posterior and two-loop probability listed in --out-loops")
+    sub.choices["scan"].add_argument("--out-mea-loops", default=None,
+                                     help="the loops of the maximum expected accuracy structure at --mea-gamma: one line per pair with "
+                                          "the fields of --out-loops for the loop it closes, then the pair posterior of the closing pair "
+                                          "(io.mea_loop_line); costs one MEA call (shared with --out-mea) and one loop call (shared "
+                                          "with --out-loops)")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -301,11 +311,13 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                   out_samples=None, n_samples=100, sample_seed=0, out_context=None, out_nodes=None, out_sites=None, site_gamma=1.0,
                   max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0, out_access=None, access_width=16, out_logo=None,
                   logo_min_exist=0.0, out_stems=None, out_stem_pairs=None, stem_min_prob=0.01, out_helices=None, helix_min_prob=0.01,
-                  helix_min_len=2, helix_max_len=16, out_mea_helices=None):
+                  helix_min_len=2, helix_max_len=16, out_mea_helices=None, out_loops=None, loop_min_prob=0.01, out_mea_loops=None):
     from .distributed import assigned_range
     stem_parts = None if out_stems is None else out_stems + ".seqs"   # (as logo_parts)
     want_stems = out_stems is not None or out_stem_pairs is not None
     want_helices = out_helices is not None or out_mea_helices is not None
+    want_loops = out_loops is not None or out_mea_loops is not None
+    want_every = out_mea_helices is not None or out_mea_loops is not None   # (the MEA call lists every pair)
     slots = eng.stem_slots() if want_stems else None                  # (the model's: once per run)
     logo_parts = None if out_logo is None else out_logo + ".seqs"     # (per-sequence counts, joined in input order before the sum)
     nodes = eng.describe()["node"]
@@ -318,14 +330,15 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
             eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
             res, en = eng.scan(m["x"])
             if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None \
-                    and out_contrast is None and out_access is None and out_logo is None and not want_stems and not want_helices:
+                    and out_contrast is None and out_access is None and out_logo is None and not want_stems and not want_helices \
+                    and not want_loops:
                 for (rid, codes, _), r in zip(part, res):
                     yield io.scan_record(rid, codes, r, nodes)
                 continue
             # (the same loaded batch; with both files one device call gives the pairs and the structures)
-            if out_mea is None and out_mea_helices is None:
+            if out_mea is None and not want_every:
                 prs = eng.pair_posteriors(m["x"], pair_min_prob) if out_pairs is not None else None
-            elif out_mea_helices is None:
+            elif not want_every:
                 structs, scores, prs = eng.mea_structures(m["x"], mea_gamma, pair_min_prob if out_pairs is not None else None)
             else:   # (the stems' smallest pair posterior comes from this call's own list: every pair, cut to --pair-min-prob for the pairs file)
                 structs, scores, every = eng.mea_structures(m["x"], mea_gamma, 0.0)
@@ -348,6 +361,11 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                 hlx = eng.helix_posteriors(m["x"], helix_min_prob if out_helices is not None else np.inf, helix_min_len, helix_max_len,
                                            structs if out_mea_helices is not None else None)
                 hlx_lists, hlx_stems = hlx if out_mea_helices is not None else (hlx, None)
+            if want_loops:      # (one call gives the lists and the loops of the MEA structures)
+                lps = eng.loop_posteriors(m["x"], loop_min_prob if out_loops is not None else np.inf,
+                                          structs if out_mea_loops is not None else None, counts=False)
+                lp_closing, lp_two = lps[0], lps[1]
+                lp_mea = lps[3] if out_mea_loops is not None else None
             for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
                 texts = [io.scan_record(rid, codes, r, nodes)]
                 if out_pairs is not None:
@@ -380,14 +398,20 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                 if out_mea_helices is not None:
                     texts.append("".join(io.mea_helix_line(rid, i + 1, j, n, p, api.stem_min_posterior(every[k], i, j, n))
                                          for i, j, n, p in zip(*hlx_stems[k])))
+                if out_loops is not None:
+                    texts.append(io.loop_lines(rid, lp_closing[k], lp_two[k]))
+                if out_mea_loops is not None:
+                    have = {(int(a), int(b)): float(v) for a, b, v in zip(every[k][0], every[k][1], every[k][2])}
+                    texts.append("".join(io.mea_loop_line(rid, api.LOOP_TYPES[t], i + 1, j, kk + 1 if kk >= 0 else None, ll, p,
+                                                          have.get((int(i), int(j)), 0.0)) for t, i, j, kk, ll, p in zip(*lp_mea[k])))
                 yield tuple(texts)
 
     if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None and out_contrast is None \
-            and out_access is None and out_logo is None and not want_stems and not want_helices:
+            and out_access is None and out_logo is None and not want_stems and not want_helices and not want_loops:
         sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
     else:
         outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast, out_access, logo_parts,
-                                   out_stem_pairs, stem_parts, out_helices, out_mea_helices) if o is not None]
+                                   out_stem_pairs, stem_parts, out_helices, out_mea_helices, out_loops, out_mea_loops) if o is not None]
         sharded_write(recs, outs, rank, world, scan_part, barrier)
     if out_logo is not None:
         if rank == 0:
@@ -433,7 +457,7 @@ def cmd_scan(a):
                   a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites,
                   a.out_contrast, a.contrast_min_prob, a.contrast_gamma, a.out_access, a.access_width, a.out_logo, a.logo_min_exist,
                   a.out_stems, a.out_stem_pairs, a.stem_min_prob, a.out_helices, a.helix_min_prob, a.helix_min_len, a.helix_max_len,
-                  a.out_mea_helices)
+                  a.out_mea_helices, a.out_loops, a.loop_min_prob, a.out_mea_loops)
     if world > 1:
         dist.destroy_process_group()
 

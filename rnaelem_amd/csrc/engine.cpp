@@ -44,6 +44,7 @@
 #include "sample_rules.h"
 #include "stem_rules.h"
 #include "helix_rules.h"
+#include "loop_rules.h"
 #include "staged_list.h"
 #include "table_slots.h"
 
@@ -243,6 +244,14 @@ class Engine {
   void helix_posteriors(const double* x, int n_param, int max_len, int min_len, double min_prob, int64_t* n_entries,
                         const char* structure, int32_t* stem_len, double* stem_prob);
   void helix_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* len, double* p, int64_t cap);
+  // loop posteriors (loop_rules.h): what every pair closes (H S B I M) and the two-loops; with a finite min_prob the
+  // two lists stay on the device for loop_closing_list / loop_two_list.  counts (5 per sequence) may be null.  structure: dot-bracket
+  // strings in seq_off indexing or null; loop_type / loop_prob (seq_off indexing, either may be null): at the 5' base of every pair
+  // of the structure the type of the loop it closes and the loop's probability, 0 / NaN elsewhere.
+  void loop_posteriors(const double* x, int n_param, double min_prob, double* counts, int64_t* n_closing, int64_t* n_two,
+                       const char* structure, int32_t* loop_type, double* loop_prob);
+  void loop_closing_list(int32_t* seq, int32_t* i, int32_t* j, double* p, double* cols, int64_t cap);
+  void loop_two_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* k, int32_t* l, double* p, int64_t cap);
   // accessibility (access_rules.h): max_width doubles per position of the batch, the widths 1 .. max_width
   void accessibility(const double* x, int n_param, int max_width, double* access);
   // maximum expected accuracy motif alignments and site lists over that profile (node_mea_rules.h); outputs as
@@ -437,6 +446,15 @@ class Engine {
   // stems of the caller's structures (offsets per sequence, i, d, length) and their probabilities
   DevBuf d_hx_P_, d_hx_nu_, d_hx_ui_, d_hx_ud_, d_hx_nlen_, d_hx_X_, d_hx_vec_;
   DevBuf d_hx_soff_, d_hx_si_, d_hx_sd_, d_hx_slen_, d_hx_sp_;
+  // loop posteriors: P, the units (count, i, d), their columns and the two-loop values per table slot; the counts of the call; the
+  // loops of the caller's structures (offsets per sequence, type, i, d, k, l) and their probabilities; kept cells, their prefix, the
+  // entries staged and their prefixes per batch index; the staging of both lists; the lists (count < 0: none)
+  DevBuf d_lp_P_, d_lp_nu_, d_lp_ui_, d_lp_ud_, d_lp_cols_, d_lp_T_, d_lp_counts_;
+  DevBuf d_lp_soff_, d_lp_st_, d_lp_si_, d_lp_sd_, d_lp_sk_, d_lp_sl_, d_lp_sp_;
+  DevBuf d_lp_kept_, d_lp_koff_, d_lp_cnt_, d_lp_cnt2_, d_lp_off_, d_lp_off2_;
+  DevBuf d_lp_sti_, d_lp_stj_, d_lp_stv_, d_lp_st2i_, d_lp_st2t_;
+  DevBuf d_lc_seq_, d_lc_i_, d_lc_j_, d_lc_v_, d_lt_seq_, d_lt_i_, d_lt_j_, d_lt_k_, d_lt_l_, d_lt_p_;
+  int64_t n_closing_ = -1, n_two_ = -1;
   DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
   // node MEA: the chain lists, the backpointer scratch (M bytes per position), the rows, sites per sequence, start / end / score / confidence per slot
   DevBuf d_nm_lists_, d_nm_bp_, d_nm_node_, d_nm_ns_, d_nm_s0_, d_nm_s1_, d_nm_sc_, d_nm_cf_;
@@ -1004,6 +1022,7 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   conds_.invalidate();
   stems_.invalidate();
   helices_.invalidate();
+  n_closing_ = n_two_ = -1;
   streaming_ = false;
   train_rows_ = false;
   BatchShape shape = check_batch(seq, off, qual, qoff, fix, n);
@@ -3156,6 +3175,279 @@ void Engine::helix_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* len, doub
   helices_.fetch(seq, i, j, p, nullptr, len, cap);
 }
 
+// ---- loop posteriors (loop_rules.h).  The host parses the loops of the caller's structures.  The scan's first sum
+// pass per group, then on the group's table slots, before the next group of the stream reuses them: P of every cell (k4_pairs), the
+// units -- the kept cells whose P reaches the bound -- (k_helix_units: one compaction for both calls), their columns H, S, M
+// (k_loop_unary), the two-loop values of their items and B, I (k_loop_items), the loops of the structures (k_loop_struct), and the
+// counts and the entries of both lists into the staging ranges (k_loop_seq).  The log-space form -- the fused scan kernel up to its
+// first outside pass, then the same rule on its dense tables -- for the sequences that leave the double range and under pipeline 3,
+// with k_loop_seq behind the launch.  Then the batch lists.  A closing entry is staged at the kept-cell prefix of its sequence, a
+// two-loop entry (item index, T) at the sequence's item_base: a sequence lists at most its items.  The bound is
+// loop_pick_bound(min_prob); where the counts are asked for it is 0, since they cover every kept cell.  Every buffer is the call's
+// own: leaves the lists of the last pair, conditional, stem and helix call alone.
+void Engine::loop_posteriors(const double* x, int n_param_in, double min_prob, double* counts, int64_t* n_closing, int64_t* n_two,
+                             const char* structure, int32_t* loop_type, double* loop_prob) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (!(min_prob >= 0.)) throw ArgError("loop_posteriors: min_prob must be >= 0");
+  if (structure && !loop_type && !loop_prob) throw ArgError("loop_posteriors: a structure needs loop_type or loop_prob");
+  if (n_seq_ <= 0) throw StateError("loop_posteriors before load_batch");
+  const int n = n_seq_;
+  const bool want_list = min_prob < HUGE_VAL;
+  // the loops of every sequence: (type, i, d, k, l) of every pair, sequences and 5' ends in increasing order
+  std::vector<int64_t> soff;
+  std::vector<int32_t> s_t, s_i, s_d, s_k, s_l;
+  if (structure) {
+    soff.assign((size_t)n + 1, 0);
+    std::vector<int32_t> mate, open;
+    for (int t = 0; t < n; ++t) {
+      const char* db = structure + (h_seq_off_[t] - h_seq_off_[0]);
+      const int L = h_seq_off_[t + 1] - h_seq_off_[t];
+      mate.assign((size_t)L, -1);
+      open.clear();
+      for (int p = 0; p < L; ++p) {
+        if (db[p] == '(') open.push_back(p);
+        else if (db[p] == ')') {
+          if (open.empty()) throw ArgError("loop_posteriors: unbalanced structure");
+          mate[p] = open.back(); mate[open.back()] = p;
+          open.pop_back();
+        } else if (db[p] != '.') throw ArgError("loop_posteriors: a structure holds ( ) . only");
+      }
+      if (!open.empty()) throw ArgError("loop_posteriors: unbalanced structure");
+      for (int p = 0; p < L; ++p) {
+        const int r = mate[p];
+        if (r < p) continue;
+        int inner = 0, k = -1, l = -1;
+        for (int u = p + 1; u < r;) {
+          if (mate[u] > u) { if (inner++ == 0) { k = u; l = mate[u]; } u = mate[u] + 1; }
+          else ++u;
+        }
+        int type = LOOP_H;
+        if (inner > 1) type = LOOP_M;
+        else if (inner == 1) type = (k == p + 1 && l == r - 1) ? LOOP_S : ((k == p + 1) != (l == r - 1)) ? LOOP_B : LOOP_I;
+        const bool twol = type == LOOP_B || type == LOOP_I;
+        s_t.push_back(type); s_i.push_back(p); s_d.push_back(r - p + 1);
+        s_k.push_back(twol ? k : -1); s_l.push_back(twol ? l + 1 : -1);
+      }
+      soff[(size_t)t + 1] = (int64_t)s_i.size();
+    }
+  }
+  const size_t n_loops = s_i.size();
+  std::vector<double> s_p(n_loops, 0.);
+  auto loops_out = [&] {   // the loops' columns of the caller, from s_p
+    if (!structure) return;
+    const size_t n_seqpos = (size_t)(h_seq_off_[n] - h_seq_off_[0]);
+    if (loop_type) std::fill(loop_type, loop_type + n_seqpos, 0);
+    if (loop_prob) std::fill(loop_prob, loop_prob + n_seqpos, std::nan(""));
+    for (int t = 0; t < n; ++t)
+      for (int64_t k = soff[t]; k < soff[(size_t)t + 1]; ++k) {
+        const size_t at = (size_t)(h_seq_off_[t] - h_seq_off_[0]) + (size_t)s_i[(size_t)k];
+        if (loop_type) loop_type[at] = s_t[(size_t)k];
+        if (loop_prob) loop_prob[at] = s_p[(size_t)k];
+      }
+  };
+  n_closing_ = n_two_ = -1;
+  if (streaming_) {
+    std::vector<int32_t> c_seq, c_i, c_j, t_seq, t_i, t_j, t_k, t_l;
+    std::vector<double> c_v, t_p;
+    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+      const size_t at = (size_t)(h_seq_off_[c0] - h_seq_off_[0]);
+      int64_t mc = 0, mt = 0;
+      e.loop_posteriors(x, n_param_in, min_prob, counts ? counts + (size_t)LOOP_COLS * c0 : nullptr, &mc, &mt,
+                        structure ? structure + at : nullptr, loop_type ? loop_type + at : nullptr, loop_prob ? loop_prob + at : nullptr);
+      const size_t b = c_seq.size(), b2 = t_seq.size();
+      c_seq.resize(b + mc); c_i.resize(b + mc); c_j.resize(b + mc); c_v.resize(6 * (b + mc));
+      t_seq.resize(b2 + mt); t_i.resize(b2 + mt); t_j.resize(b2 + mt); t_k.resize(b2 + mt); t_l.resize(b2 + mt); t_p.resize(b2 + mt);
+      std::vector<double> p((size_t)mc), cols((size_t)LOOP_COLS * mc);
+      e.loop_closing_list(c_seq.data() + b, c_i.data() + b, c_j.data() + b, p.data(), cols.data(), mc);
+      for (size_t r = 0; r < (size_t)mc; ++r) {
+        c_v[6 * (b + r)] = p[r];
+        for (int k = 0; k < LOOP_COLS; ++k) c_v[6 * (b + r) + 1 + k] = cols[LOOP_COLS * r + k];
+        c_seq[b + r] += c0;
+      }
+      e.loop_two_list(t_seq.data() + b2, t_i.data() + b2, t_j.data() + b2, t_k.data() + b2, t_l.data() + b2, t_p.data() + b2, mt);
+      for (size_t r = b2; r < t_seq.size(); ++r) t_seq[r] += c0;
+    });
+    d_lc_seq_.upload(c_seq, st_); d_lc_i_.upload(c_i, st_); d_lc_j_.upload(c_j, st_); d_lc_v_.upload(c_v, st_);
+    d_lt_seq_.upload(t_seq, st_); d_lt_i_.upload(t_i, st_); d_lt_j_.upload(t_j, st_); d_lt_k_.upload(t_k, st_);
+    d_lt_l_.upload(t_l, st_); d_lt_p_.upload(t_p, st_);
+    HIP_OK(hipStreamSynchronize(st_));   // (the host columns go out of use with the copies)
+    n_closing_ = (int64_t)c_seq.size(); n_two_ = (int64_t)t_seq.size();
+    if (n_closing) *n_closing = n_closing_;
+    if (n_two) *n_two = n_two_;
+    return;
+  }
+  require_resident("loop_posteriors", n_param_in);
+  upload_params(x, lay_, false);
+  const size_t n_seqpos = (size_t)h_seq_off_[n];
+  ScanPos pos(n_seqpos, n);
+  const bool no_rss = (flags_ & ELEMDP_NO_RSS) != 0;
+  LoopArgs la;
+  std::memset(&la, 0, sizeof(la));
+  if (structure) {
+    d_lp_soff_.upload(soff, st_); d_lp_st_.upload(s_t, st_); d_lp_si_.upload(s_i, st_); d_lp_sd_.upload(s_d, st_);
+    d_lp_sk_.upload(s_k, st_); d_lp_sl_.upload(s_l, st_);
+    d_lp_sp_.alloc(8 * std::max<size_t>(n_loops, 1));
+    HIP_OK(hipMemsetAsync(d_lp_sp_.as<void>(), 0, 8 * std::max<size_t>(n_loops, 1), st_));
+    HIP_OK(hipStreamSynchronize(st_));   // (the host vectors go out of use with the copies; the probabilities are clear before any group runs)
+    la.soff = d_lp_soff_.as<int64_t>();
+    la.s_type = d_lp_st_.as<int32_t>(); la.s_i = d_lp_si_.as<int32_t>(); la.s_d = d_lp_sd_.as<int32_t>();
+    la.s_k = d_lp_sk_.as<int32_t>(); la.s_l = d_lp_sl_.as<int32_t>();
+    la.s_p = d_lp_sp_.as<double>();
+  }
+  HIP_OK(hipEventRecord(ev_[1], st_));
+  const PlanArrays pa_ = plan_.arrays();
+  la.plans = plan_.d_plans.as<SeqPlan>();
+  la.seq_out = d_seq_out_.as<double>(); la.out_stride = out_stride_;
+  la.okbits = d_okbits1_.as<uint32_t>();
+  la.no_rss = no_rss ? 1 : 0;
+  la.want_units = want_list || counts ? 1 : 0;
+  la.min_prob = min_prob;
+  la.bound = counts ? 0. : loop_pick_bound(min_prob);
+  la.items = pa_.items; la.by_outer_off = pa_.by_outer_off; la.item_in = pa_.item_in;
+  const size_t pcells = loop_units_cap(Lmax_, Wmax_);
+  size_t items_max = 1;
+  for (const SeqPlan& p : plan_.h) items_max = std::max(items_max, (size_t)p.n_items);
+  la.p_stride = pcells; la.u_stride = pcells; la.t_stride = items_max;
+  if (counts) {
+    d_lp_counts_.alloc(8 * (size_t)LOOP_COLS * n);
+    HIP_OK(hipMemsetAsync(d_lp_counts_.as<void>(), 0, 8 * (size_t)LOOP_COLS * n, st_));
+    la.counts = d_lp_counts_.as<double>();
+  }
+  auto prefix_total = [&](const DevBuf& cnt, DevBuf& off) {   // off[0 .. n] = exclusive prefix of cnt[0 .. n) on st_; waits, returns the total
+    HIP_OK(launch_pair_prefix(cnt.as<int64_t>(), n, off.as<int64_t>(), st_));
+    int64_t total = 0;
+    HIP_OK(hipMemcpyAsync(&total, off.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
+    HIP_OK(hipStreamSynchronize(st_));
+    return total;
+  };
+  if (want_list) {   // staging ranges: a closing entry per kept cell, a two-loop entry per item at the most
+    d_lp_kept_.alloc(8 * (size_t)n); d_lp_koff_.alloc(8 * ((size_t)n + 1));
+    d_lp_cnt_.alloc(8 * (size_t)n); d_lp_cnt2_.alloc(8 * (size_t)n);
+    d_lp_off_.alloc(8 * ((size_t)n + 1)); d_lp_off2_.alloc(8 * ((size_t)n + 1));
+    HIP_OK(launch_pair_kept(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, d_lp_kept_.as<int64_t>(), st_));
+    const size_t cap = (size_t)prefix_total(d_lp_kept_, d_lp_koff_), cap2 = (size_t)std::max<int64_t>(plan_.n_items, 0);
+    d_lp_sti_.alloc(4 * cap); d_lp_stj_.alloc(4 * cap); d_lp_stv_.alloc(8 * 6 * cap);
+    d_lp_st2i_.alloc(4 * cap2); d_lp_st2t_.alloc(8 * cap2);
+    HIP_OK(hipMemsetAsync(d_lp_cnt_.as<void>(), 0, 8 * (size_t)n, st_));
+    HIP_OK(hipMemsetAsync(d_lp_cnt2_.as<void>(), 0, 8 * (size_t)n, st_));
+    la.koff = d_lp_koff_.as<int64_t>(); la.cnt = d_lp_cnt_.as<int64_t>(); la.cnt2 = d_lp_cnt2_.as<int64_t>();
+    la.st_i = d_lp_sti_.as<int32_t>(); la.st_j = d_lp_stj_.as<int32_t>(); la.st_v = d_lp_stv_.as<double>();
+    la.st2_it = d_lp_st2i_.as<int32_t>(); la.st2_t = d_lp_st2t_.as<double>();
+  }
+  const bool work = la.want_units || structure;   // (else: nothing to compute, no sweep)
+  auto at_slot = [&](LoopArgs& lk, size_t slot0) {
+    lk.P = slot_scratch<double>(d_lp_P_, pcells, slot0);
+    lk.n_units = slot_scratch<int32_t>(d_lp_nu_, 1, slot0);
+    lk.ui = slot_scratch<int32_t>(d_lp_ui_, pcells, slot0);
+    lk.ud = slot_scratch<int32_t>(d_lp_ud_, pcells, slot0);
+    lk.cols = slot_scratch<double>(d_lp_cols_, pcells * (size_t)LOOP_COLS, slot0);
+    lk.T = slot_scratch<double>(d_lp_T_, items_max, slot0);
+  };
+  int n_flagged = 0;
+  if (work) {
+    PairArgs pa = pair_batch_args();
+    pa.p_stride = pcells;
+    n_flagged = scan_both_forms(pos, [&](LinArgs& a) {
+      if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("loop_posteriors: the scan sweeps another automaton than the engine's");
+      at_slot(la, 0);
+      pair_plane_fields(pa, a);
+      la.skip_flagged = 1;
+    }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
+      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      LoopArgs lk = la;
+      lk.idx = ak.grp;
+      at_slot(lk, slot0);
+      if (!no_rss) {   // (else the band tables are not read: no units, the loops keep their 0)
+        if (la.want_units) {
+          PairArgs pk = pa;
+          pk.idx = ak.grp;
+          pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+          pk.P = lk.P;
+          HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
+          HelixArgs hk;   // (the compaction of the helix call: the kept cells whose P reaches helix_pick_bound(min_prob) = the bound)
+          std::memset(&hk, 0, sizeof(hk));
+          hk.plans = lk.plans; hk.idx = lk.idx; hk.seq_out = lk.seq_out; hk.out_stride = lk.out_stride; hk.skip_flagged = 1;
+          hk.okbits = lk.okbits; hk.min_prob = counts ? 0. : min_prob;
+          hk.P = lk.P; hk.p_stride = pcells;
+          hk.n_units = lk.n_units; hk.ui = lk.ui; hk.ud = lk.ud; hk.u_stride = pcells;
+          HIP_OK(launch_helix_units(hk, G, st));
+          HIP_OK(launch_loop_unary(ak, lk, G, (Lg + 1) * (Wg + 1), st));
+          HIP_OK(launch_loop_items(ak, lk, G, (Lg + 1) * (Wg + 1), st));
+        }
+        if (structure) HIP_OK(launch_loop_struct(ak, lk, G, Lg, st));
+      }
+      if (la.want_units) HIP_OK(launch_loop_seq(lk, G, st));
+    },
+    // ---- the log-space form, in chunks of at most as many sequences as the table slots hold (the scratch is bounded by the chunk)
+    [&](DpArgs& d, int n_blocks, int n_log) {
+      at_slot(la, 0);
+      d.lop = la;
+      return log_chunk(n_blocks, n_log);
+    }, [&](const int32_t* idx, int C) {
+      LoopArgs lk = la;
+      lk.idx = idx;
+      lk.skip_flagged = 0;
+      lk.no_rss = 0;   // (the fused kernel wrote the number of units of every sequence of the launch: 0 without secondary structure)
+      if (la.want_units) HIP_OK(launch_loop_seq(lk, C, st_));
+    });
+  }
+  finish_call(n_flagged, [&] {
+    if (want_list) {   // the lists: by (sequence, i, j), and by outer cell in that order, then in the plan's by-outer order
+      const size_t mc = (size_t)prefix_total(d_lp_cnt_, d_lp_off_), mt = (size_t)prefix_total(d_lp_cnt2_, d_lp_off2_);
+      d_lc_seq_.alloc(4 * mc); d_lc_i_.alloc(4 * mc); d_lc_j_.alloc(4 * mc); d_lc_v_.alloc(8 * 6 * mc);
+      d_lt_seq_.alloc(4 * mt); d_lt_i_.alloc(4 * mt); d_lt_j_.alloc(4 * mt); d_lt_k_.alloc(4 * mt); d_lt_l_.alloc(4 * mt);
+      d_lt_p_.alloc(8 * mt);
+      LoopListCols lc{plan_.d_plans.as<SeqPlan>(), pa_.items, d_lp_koff_.as<int64_t>(), d_lp_cnt_.as<int64_t>(), d_lp_off_.as<int64_t>(),
+                      d_lp_cnt2_.as<int64_t>(), d_lp_off2_.as<int64_t>(), d_lp_sti_.as<int32_t>(), d_lp_stj_.as<int32_t>(),
+                      d_lp_stv_.as<double>(), d_lp_st2i_.as<int32_t>(), d_lp_st2t_.as<double>(),
+                      d_lc_seq_.as<int32_t>(), d_lc_i_.as<int32_t>(), d_lc_j_.as<int32_t>(), d_lc_v_.as<double>(),
+                      d_lt_seq_.as<int32_t>(), d_lt_i_.as<int32_t>(), d_lt_j_.as<int32_t>(), d_lt_k_.as<int32_t>(), d_lt_l_.as<int32_t>(),
+                      d_lt_p_.as<double>()};
+      HIP_OK(launch_loop_scatter(lc, n, st_));
+      n_closing_ = (int64_t)mc; n_two_ = (int64_t)mt;
+    } else {
+      n_closing_ = n_two_ = 0;
+    }
+    if (n_loops) HIP_OK(hipMemcpyAsync(s_p.data(), d_lp_sp_.as<void>(), 8 * n_loops, hipMemcpyDeviceToHost, st_));
+    if (counts) HIP_OK(hipMemcpyAsync(counts, d_lp_counts_.as<void>(), 8 * (size_t)LOOP_COLS * n, hipMemcpyDeviceToHost, st_));
+  });
+  loops_out();
+  if (n_closing) *n_closing = n_closing_;
+  if (n_two) *n_two = n_two_;
+}
+
+void Engine::loop_closing_list(int32_t* seq, int32_t* i, int32_t* j, double* p, double* cols, int64_t cap) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (n_closing_ < 0) throw StateError("loop_closing_list before loop_posteriors");
+  if (cap < n_closing_) throw ArgError("loop_closing_list: buffer too small");
+  const size_t m = (size_t)n_closing_;
+  if (m == 0) return;
+  auto get = [&](void* dst, const DevBuf& src, size_t bytes) { if (dst) HIP_OK(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost)); };
+  get(seq, d_lc_seq_, 4 * m); get(i, d_lc_i_, 4 * m); get(j, d_lc_j_, 4 * m);
+  if (p || cols) {
+    std::vector<double> v(6 * m);
+    get(v.data(), d_lc_v_, 8 * 6 * m);
+    for (size_t r = 0; r < m; ++r) {
+      if (p) p[r] = v[6 * r];
+      if (cols) for (int k = 0; k < LOOP_COLS; ++k) cols[LOOP_COLS * r + k] = v[6 * r + 1 + k];
+    }
+  }
+}
+
+void Engine::loop_two_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* k, int32_t* l, double* p, int64_t cap) {
+  require_device();
+  DeviceGuard dg(device_);
+  if (n_two_ < 0) throw StateError("loop_two_list before loop_posteriors");
+  if (cap < n_two_) throw ArgError("loop_two_list: buffer too small");
+  const size_t m = (size_t)n_two_;
+  if (m == 0) return;
+  auto get = [&](void* dst, const DevBuf& src, size_t bytes) { if (dst) HIP_OK(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost)); };
+  get(seq, d_lt_seq_, 4 * m); get(i, d_lt_i_, 4 * m); get(j, d_lt_j_, 4 * m); get(k, d_lt_k_, 4 * m); get(l, d_lt_l_, 4 * m);
+  get(p, d_lt_p_, 8 * m);
+}
+
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h).  The node pass of
 // node_profile, then k_node_mea once over the profile of the whole batch on the engine's stream, behind the last group and the
 // log-space form.  The profile goes to the host only where the caller gave a buffer.  Leaves the list of the last pair call alone.
@@ -3652,6 +3944,25 @@ int elemdp_helix_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, in
   ELEMDP_TRY
   if (!h) throw elemdp::ArgError("elemdp_helix_list: null handle");
   h->e->helix_list(seq, i, j, len, p, cap);
+  ELEMDP_CATCH
+}
+int elemdp_loop_posteriors(elemdp_handle* h, const double* x, int32_t n_param, double min_prob, double* counts, int64_t* n_closing,
+                           int64_t* n_two, const char* structure, int32_t* loop_type, double* loop_prob) {
+  ELEMDP_TRY
+  if (!h || !x) throw elemdp::ArgError("elemdp_loop_posteriors: null argument");
+  h->e->loop_posteriors(x, n_param, min_prob, counts, n_closing, n_two, structure, loop_type, loop_prob);
+  ELEMDP_CATCH
+}
+int elemdp_loop_closing_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, double* p, double* cols, int64_t cap) {
+  ELEMDP_TRY
+  if (!h) throw elemdp::ArgError("elemdp_loop_closing_list: null handle");
+  h->e->loop_closing_list(seq, i, j, p, cols, cap);
+  ELEMDP_CATCH
+}
+int elemdp_loop_two_list(elemdp_handle* h, int32_t* seq, int32_t* i, int32_t* j, int32_t* k, int32_t* l, double* p, int64_t cap) {
+  ELEMDP_TRY
+  if (!h) throw elemdp::ArgError("elemdp_loop_two_list: null handle");
+  h->e->loop_two_list(seq, i, j, k, l, p, cap);
   ELEMDP_CATCH
 }
 int elemdp_node_mea(elemdp_handle* h, const double* x, int32_t n_param, double gamma, int32_t max_sites, double* profile,

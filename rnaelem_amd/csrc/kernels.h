@@ -198,6 +198,46 @@ struct HelixArgs {
   const int64_t* soff; const int32_t* s_i; const int32_t* s_d; const int32_t* s_len; double* s_p;   // stems (soff null: none)
 };
 
+// ---- loop posteriors (loop_rules.h, loop_kernels.hip).  A launch covers the G sequences idx[0 .. G) of one group or chunk; slot g of
+// the launch owns one int of n_units, u_stride ints each of ui and ud, 5 u_stride doubles of cols and t_stride doubles of T: its
+// units -- outer kept cells (ui, ud) in (i, d) order, picked by k_helix_units from P --, the columns H S B I M of unit r at
+// cols[5 r ..] and the two-loop values of the unit's items at their by-outer positions (the item's index in the plan of the
+// sequence).  A closing entry of batch index n goes to the staging range that starts at koff[n] (6 doubles: p and the columns), a
+// two-loop entry to the range that starts at the sequence's item_base (the item's index and T); counts + 5 n receives the column
+// sums over the units; the loops of its caller-given structure are s_type / s_i / s_d / s_k / s_l[soff[n] .. soff[n + 1]) and their
+// probabilities go to s_p.
+struct LoopArgs {
+  const SeqPlan* plans;           // batch plans (batch index)
+  const int32_t* idx;             // idx[g] = batch index of the sequence in slot g (launch_loop_seq)
+  const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
+  int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)
+  const uint32_t* okbits;         // the pair mask of the batch
+  int32_t no_rss;                 // a model without secondary structure: no units, the band tables are not read
+  int32_t want_units;             // the lists or the counts are asked for: units are picked and walked
+  double min_prob;                // the lists' threshold (+inf: no lists)
+  double bound;                   // the units' threshold on P: loop_pick_bound(min_prob), 0 where the counts are asked for
+  double* P; size_t p_stride;     // P(i, d) of the slot ([i][d], rows of W+1): launch_pair_cells, or the fused scan kernel
+  int32_t* n_units; int32_t* ui; int32_t* ud; size_t u_stride;
+  double* cols;
+  double* T; size_t t_stride;
+  const LoopItem* items; const int32_t* by_outer_off; const uint8_t* item_in;   // the plan's arrays (k_loop_seq, k_loop_scatter)
+  double* counts;                 // null: not asked for
+  const int64_t* koff; int64_t* cnt; int64_t* cnt2;   // kept cells before batch index n, closing / two-loop entries staged
+  int32_t* st_i; int32_t* st_j; double* st_v;          // closing staging (null: no lists are kept)
+  int32_t* st2_it; double* st2_t;                      // two-loop staging
+  const int64_t* soff; const int32_t* s_type; const int32_t* s_i; const int32_t* s_d; const int32_t* s_k; const int32_t* s_l;
+  double* s_p;                    // loops of the structures (soff null: none)
+};
+// the final lists of a loop call, as k_loop_scatter fills them: batch index n has cnt[n] closing entries from staging koff[n] on that
+// go to off[n] .., and cnt2[n] two-loop entries from staging item_base on that go to off2[n] ..
+struct LoopListCols {
+  const SeqPlan* plans; const LoopItem* items;
+  const int64_t* koff; const int64_t* cnt; const int64_t* off; const int64_t* cnt2; const int64_t* off2;
+  const int32_t* st_i; const int32_t* st_j; const double* st_v; const int32_t* st2_it; const double* st2_t;
+  int32_t* c_seq; int32_t* c_i; int32_t* c_j; double* c_v;                              // closing list, 6 doubles per entry
+  int32_t* t_seq; int32_t* t_i; int32_t* t_j; int32_t* t_k; int32_t* t_l; double* t_p;  // two-loop list
+};
+
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h, node_mea_kernels.hip) over the profile of the
 // whole batch: batch index n with seq_base b and length L writes the row of slot k at node + max_sites * b + k * L (the sampler's
 // layout), n_sites[n], and start / end / score / conf at [n * max_sites + k]
@@ -273,6 +313,11 @@ struct DpArgs {
   // units of the sequence order[w] -- every cell of its band, in (i, d) order -- to slot w of hlx (k_helix_seq reads them behind the
   // launch) and the probabilities of its stems to hlx.s_p
   HelixArgs hlx;
+  // SCAN, loop posteriors (loop_rules.h, log-space form): lop.cols non-null = stop after inside + the first outside pass and write P,
+  // the units of the sequence order[w] -- every cell of its band, in (i, d) order, the columns of a cell that is no unit 0 --, their
+  // columns and two-loop values to slot w of lop (k_loop_seq reads them behind the launch) and the probabilities of the loops of its
+  // structure to lop.s_p
+  LoopArgs lop;
 };
 
 // arguments of the diagonal-synchronous train pipeline (train_kernels.hip)
@@ -562,6 +607,17 @@ hipError_t launch_stem_seq(const StemArgs& c, int G, hipStream_t st);
 hipError_t launch_helix_units(const HelixArgs& c, int G, hipStream_t st);
 hipError_t launch_helix_chains(const LinArgs& a, const HelixArgs& c, int G, int cells_max, hipStream_t st);
 hipError_t launch_helix_seq(const HelixArgs& c, int G, hipStream_t st);
+
+// ---- loop posteriors (loop_kernels.hip), behind launch_lin_scan_group (SCAN_PASS_START), launch_pair_cells and launch_helix_units
+// (the units: the compaction scheme is shared) on the same slots and stream: k_loop_unary (one lane per unit: H, S, M), k_loop_items
+// (one wave per unit: the two-loop values of its items, B and I), k_loop_struct (one lane per loop of the caller-given structure);
+// k_loop_seq (one workgroup per sequence: the counts, and its entries of both lists into its staging ranges) behind them, or behind
+// the fused scan kernel (DpArgs::lop); launch_loop_scatter: the batch lists
+hipError_t launch_loop_unary(const LinArgs& a, const LoopArgs& c, int G, int cells_max, hipStream_t st);
+hipError_t launch_loop_items(const LinArgs& a, const LoopArgs& c, int G, int cells_max, hipStream_t st);
+hipError_t launch_loop_struct(const LinArgs& a, const LoopArgs& c, int G, int Lmax, hipStream_t st);
+hipError_t launch_loop_seq(const LoopArgs& c, int G, hipStream_t st);
+hipError_t launch_loop_scatter(const LoopListCols& c, int n, hipStream_t st);
 // k_node_mea behind the node pass of the whole batch (both forms), on the engine's stream: one wave per sequence
 hipError_t launch_node_mea(const NodeMeaArgs& a, int n_seq, hipStream_t st);
 // ---- the staged lists of the pair, conditional, stem and helix calls (staged_list.h, pair_kernels.hip).  The columns of one list, as

@@ -27,6 +27,7 @@
 #include "joint_rules.h"
 #include "stem_rules.h"
 #include "helix_rules.h"
+#include "loop_rules.h"
 #include "pair_rules.h"
 #include "plan_rules.h"
 #include "sample_lane.h"
@@ -656,6 +657,44 @@ __device__ __forceinline__ void helix_log_units(const ModelView& m, const SeqVie
       c.s_p[t] = helix_stem(f, ln, m, q, Tin, Tout, c.s_i[t], c.s_d[t], c.s_len[t], v0, v0 + S);
 }
 
+// loop posteriors (loop_rules.h) on the dense log-space tables of sequence n in slot w: one thread per cell of the band, every cell a
+// unit in (i, d) order -- P as the pair call's log-space form sums it, then the columns and the two-loop values of a kept cell whose P
+// reaches the bound, zeros for any other cell --, then one thread per loop of the caller-given structure.  live false: no parse, or no
+// secondary structure in the model -- no units, and the loop probabilities keep the 0 the call cleared them to.
+__device__ __forceinline__ void loop_log_units(const ModelView& m, const SeqView& q, const TableView& Tin, const TableView& Tout,
+                                            double ZL, const LoopArgs& c, int w, int n, bool live) {
+  const int tid = threadIdx.x;
+  const int L = q.L, W = q.W, S = m.lay.S, ncell = (L + 1) * (W + 1);
+  if (tid == 0) c.n_units[w] = live && c.want_units ? ncell : 0;
+  if (!live) return;
+  const LoopLog f(ZL);
+  const PairLog r{ZL};
+  if (c.want_units) {
+    double* P = c.P + (size_t)w * c.p_stride;
+    int32_t* ui = c.ui + (size_t)w * c.u_stride;
+    int32_t* ud = c.ud + (size_t)w * c.u_stride;
+    double* cols = c.cols + (size_t)w * c.u_stride * LOOP_COLS;
+    double* T = c.T + (size_t)w * c.t_stride;
+    for (int t = tid; t < ncell; t += kThreads) {
+      const int i = t / (W + 1), d = t - i * (W + 1);
+      const bool kept = i + d <= L && q.pair_ok(i, d);
+      double acc = 0.;
+      if (kept)
+        for (int s = 0; s < S; ++s)
+          if (s != m.lay.shadow) acc += r.term(Tin.at(ST_P, d, i, s), Tout.at(ST_P, d, i, s));
+      const double pv = r.finish(acc);
+      P[t] = pv;
+      ui[t] = i; ud[t] = d;
+      double* row = cols + (size_t)LOOP_COLS * t;
+      for (int k = 0; k < LOOP_COLS; ++k) row[k] = 0.;
+      if (kept && d >= 2 && pv >= c.bound) loop_cell(f, m, q, Tin, Tout, i, d, row, T);
+    }
+  }
+  if (c.soff)
+    for (int64_t t = c.soff[n] + tid; t < c.soff[n + 1]; t += kThreads)
+      c.s_p[t] = loop_of_structure(f, m, q, Tin, Tout, c.s_type[t], c.s_i[t], c.s_d[t], c.s_k[t], c.s_l[t]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // the DP kernel: TRAIN = K2 + 2 x K3 fused, BPP = K1, SCAN = K4 + K5 + K6
 // ---------------------------------------------------------------------------------------------
@@ -897,6 +936,10 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
         }
         if (a.hlx.X) {   // helix posteriors (helix_rules.h): the chains of this first pass, one unit or stem per lane
           helix_log_units(m, q, Tin, Tout, ZL, a.hlx, w, n, ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL && !no_rss);
+          continue;
+        }
+        if (a.lop.cols) {   // loop posteriors (loop_rules.h): the columns and two-loops of this first pass, one cell or loop per lane
+          loop_log_units(m, q, Tin, Tout, ZL, a.lop, w, n, ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL && !no_rss);
           continue;
         }
         if (a.acc.T) {   // accessibility (access_rules.h): the units (term, position) of this first pass

@@ -524,6 +524,73 @@ def read_mea_helices(path):
     return out
 
 
+LOOP_LETTERS = "HSBIM"
+
+
+def loop_line(rid, letter, i, j, k, l, p):
+    """One line of the `scan --out-loops` file: the sequence id, the type letter of the loop (H hairpin, S stack, B bulge, I interior
+    loop, M multi-branch loop), the 1-based positions i < j of the two bases of the closing pair (as the `scan --out-helices` file
+    numbers them: cell (i0, j0) -> i0+1, j0), the 1-based positions k < l of the two bases of the inner pair of a two-loop (None:
+    `-`, the closing rows of the types H, S and M), and the probability."""
+    kl = "-\t-" if k is None else "%d\t%d" % (k, l)
+    return "%s\t%s\t%d\t%d\t%s\t%.6g\n" % (rid, letter, i, j, kl, p)
+
+
+def loop_lines(rid, closing, two):
+    """The lines of one sequence in the `scan --out-loops` file from its closing list (i, j, p, cols) and its two-loop list
+    (i, j, k, l, p) of Engine.loop_posteriors: per closing cell the rows H, S and M of the columns that are not 0, then the cell's
+    two-loops as rows B or I.  Both lists are in (i, j) order of the outer cell; a two-loop whose outer cell has no closing
+    row (its pair posterior within rounding below the threshold) is written in its place in that order."""
+    ii, jj, _, cols = closing
+    ti, tj, tk, tl, tp = two
+    out, t = [], 0
+
+    def two_rows(upto):   # the two-loops whose outer cell is at or before `upto` in (i, j) order (None: all that are left)
+        nonlocal t
+        while t < len(ti) and (upto is None or (ti[t], tj[t]) <= upto):
+            bulge = (tk[t] == ti[t] + 1) != (tl[t] == tj[t] - 1)
+            out.append(loop_line(rid, "B" if bulge else "I", ti[t] + 1, tj[t], tk[t] + 1, tl[t], tp[t]))
+            t += 1
+
+    for i, j, c in zip(ii, jj, cols):
+        two_rows((i, j - 1))      # (an outer cell within rounding below the threshold has two-loops but no closing row)
+        out += [loop_line(rid, LOOP_LETTERS[w], i + 1, j, None, None, c[w]) for w in (0, 1, 4) if c[w] > 0.0]
+        two_rows((i, j))
+    two_rows(None)
+    return "".join(out)
+
+
+def _read_loop_fields(path, line, n):
+    f = line.split("\t")
+    if len(f) != n or f[1] not in LOOP_LETTERS or (f[4] == "-") != (f[5] == "-") or (f[4] == "-") != (f[1] in "HSM"):
+        raise ValueError("loops file %r: %d fields with a type letter expected in %r" % (path, n, line))
+    two = f[4] != "-"
+    return dict(id=f[0], type=f[1], i=int(f[2]) - 1, j=int(f[3]), k=int(f[4]) - 1 if two else None, l=int(f[5]) if two else None,
+                p=float(f[6]))
+
+
+def read_loops(path):
+    """-> list of dict(id, type, i, j, k, l, p) from a `scan --out-loops` file, i and k 0-based, j and l exclusive (the engine's
+    cells); k and l are None on the rows of the types H, S and M."""
+    return [_read_loop_fields(path, line, 7) for line in open(path).read().split("\n")[:-1]]
+
+
+def mea_loop_line(rid, letter, i, j, k, l, p_loop, p_pair):
+    """One line of the `scan --out-mea-loops` file, a loop of the sequence's maximum expected accuracy structure: the fields of
+    loop_line with the probability of the loop, then the pair posterior of its closing pair."""
+    return loop_line(rid, letter, i, j, k, l, p_loop)[:-1] + "\t%.6g\n" % p_pair
+
+
+def read_mea_loops(path):
+    """-> list of dict(id, type, i, j, k, l, p, p_pair) from a `scan --out-mea-loops` file, cells as read_loops."""
+    out = []
+    for line in open(path).read().split("\n")[:-1]:
+        r = _read_loop_fields(path, line, 8)
+        r["p_pair"] = float(line.split("\t")[7])
+        out.append(r)
+    return out
+
+
 def write_stems(path, names, slots, counts, n_used, n_total=None):
     """The `scan --out-stems` file: a header `sequences: <used> / <read>` and `columns: N A C G U`, then one record per stem slot:
     `stem: <index><name> <index><name>` (the pattern nodes of the left and the right base), `occurrences: <expected number of
