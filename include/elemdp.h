@@ -133,6 +133,27 @@ int elemdp_describe(const elemdp_handle* h, char* buf, int32_t cap);
  *                       next of the same plan and options, and are not stored again (elemdp_last_timing entries 3 and 4 say
  *                       whether, and how many slots the handle holds); 0: the slots of one group, shared by the groups of a
  *                       stream.  The sequences swept in lockstep and the streams are the same either way
+ *   the ensemble of the posterior products
+ *     "world"           0 (default): the mixture every scan-family call describes, terminals ari and nasi, Z(ari, nasi) -- the
+ *                       parses with the motif and those without it in the proportion exist_prob : 1 - exist_prob; 1: the parses
+ *                       with the motif alone (terminals ari, Z(ari)); 2: the parses without it alone (terminal nasi, Z(nasi)); any
+ *                       other value is ELEMDP_EINVAL.  In world w every product is its own rule on the inside tables of the first
+ *                       sum pass, which the worlds share, and the outside tables of a sweep seeded with world w's terminals alone,
+ *                       normalised with Z_w: elemdp_pair_posteriors in world 1 / 2 is the P_motif / P_none of
+ *                       elemdp_pair_conditional.  Honoured by elemdp_pair_posteriors and elemdp_pair_mea (with elemdp_pair_list),
+ *                       elemdp_sample (the terminal is drawn among the world's terminals alone, draw 0 is consumed as ever, logp is
+ *                       relative to Z_w), elemdp_context_profile, elemdp_node_profile, elemdp_node_mea, elemdp_joint_profile,
+ *                       elemdp_stem_profile (with elemdp_stem_list), elemdp_helix_posteriors (with elemdp_helix_list),
+ *                       elemdp_loop_posteriors (with its two lists and the loops and stems of caller-given structures) and
+ *                       elemdp_accessibility.  Ignored by elemdp_scan (its record is the reference's), by
+ *                       elemdp_pair_conditional (both worlds by definition) and by the train calls.  A world with Z_w = 0
+ *                       exactly is empty: the call returns for that sequence what it returns for a sequence without any parse --
+ *                       P = 0 and unpaired 1, no list entries, structure all '.', context O = 1, profile 1 at node 0 (J(p, 0, O)
+ *                       = 1), counts 0, no sites, accessibility 1, sample status 1 (no parse) -- through the same path, the
+ *                       log-space form (elemdp_last_timing entry 2 counts the sequence); no outside sweep runs for it.  Setting
+ *                       the option keeps the cached masks of a streamed batch and, set again, replaces its entry in the record
+ *                       of options the inner engines of a streamed batch replay (elemdp_last_timing entry 5: the number of
+ *                       entries)
  *   measurement / tests
  *     "profile"         in-kernel phase clocks for elemdp_debug_profile; "dbg": switch phases off (results invalid);
  *     "poison"          1: every table is filled with NaN before an evaluation (an unmasked read of an entry nobody stored shows) */
@@ -531,7 +552,9 @@ int elemdp_node_mea(elemdp_handle* h, const double* x, int32_t n_param, double g
  * ms[0] = whole evaluation, ms[1] = the DP pipeline only (all kernels of the inside/outside sweeps),
  * ms[2] = number of sequences the scaled-linear pipeline handed to the log-space pipeline (range check);
  * with n > 3 also ms[3] = 1 when the last train evaluation of the scaled-linear pipeline found the zeros of the dead entries kept
- * in its slots and stored none (option "own_slots"), else 0, and ms[4] = the table slots the handle holds */
+ * in its slots and stored none (option "own_slots"), else 0, and ms[4] = the table slots the handle holds; with n > 5 also ms[5] =
+ * the number of entries in the record of options that the inner engines of a streamed batch replay (a state of the handle like
+ * entries 3 and 4, no timing; for the tests: setting "world" again replaces its entry) */
 int elemdp_last_timing(elemdp_handle* h, double* ms, int32_t n);
 /* debug: summed shader-clock cycles per phase of the last train evaluation when option "profile" = 1:
  * pipeline 2: [stage, inside band, inside exterior, outside exterior, outside band, queue/other];

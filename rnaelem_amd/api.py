@@ -8,6 +8,7 @@ all-reduce.  There is no CPU fallback: if the library cannot be loaded or no GPU
 calls raise.
 """
 import ctypes as C
+import functools
 import json
 import os
 
@@ -313,6 +314,37 @@ def structure_loops(db):
     return out
 
 
+WORLDS = ("mixed", "motif", "none")     # option "world": 0, 1, 2
+
+
+def world_index(world):
+    """0, 1, 2 for "mixed", "motif", "none" (or for the number itself); ValueError for anything else."""
+    if isinstance(world, str) and world in WORLDS:
+        return WORLDS.index(world)
+    if not isinstance(world, (str, bool)) and world in (0, 1, 2):
+        return int(world)
+    raise ValueError("world: one of %s" % ", ".join(repr(w) for w in WORLDS))
+
+
+def _in_world(method):
+    """A posterior call that takes world="mixed" | "motif" | "none": the ensemble it describes -- the mixture of the parses with
+    the motif and those without it (every call's default), the parses with the motif alone, or those without it alone (option
+    "world").  The option is set for the call and put back afterwards, also when the call raises.  Without
+    world= the call is the mixture's, whatever set_option("world", ..) left on the handle."""
+    @functools.wraps(method)
+    def call(self, *args, world="mixed", **kw):
+        w = world_index(world)
+        before = self._world
+        if w == before:
+            return method(self, *args, **kw)
+        self.set_option("world", w)
+        try:
+            return method(self, *args, **kw)
+        finally:
+            self.set_option("world", before)
+    return call
+
+
 class Engine:
     """One model on one GPU (== one `RNAelem` object plus the trainer / scanner workers around it)."""
 
@@ -329,6 +361,13 @@ class Engine:
         self.n_node = self._lib.elemdp_n_node(self._h)
         self.n_seq = 0
         self._off = self._qoff = None
+        self._world = 0
+
+    @property
+    def world(self):
+        """The handle's option "world" as last set: the world a raw library call runs in.  The posterior methods of this class do
+        not follow it -- each runs in its own world= argument, "mixed" when none is given, and puts this value back afterwards."""
+        return WORLDS[self._world]
 
     def _check(self, rc):
         if rc < 0:
@@ -359,6 +398,8 @@ class Engine:
 
     def set_option(self, key, value):
         self._check(self._lib.elemdp_set_option(self._h, key.encode(), float(value)))
+        if key == "world":
+            self._world = int(value)
 
     # ---- batch
     def load_batch(self, seqs, quals, fix_rss=None):
@@ -520,6 +561,7 @@ class Engine:
         return recs, en
 
     # ---- base-pair posteriors under the motif model
+    @_in_world
     def pair_posteriors(self, x, min_prob=0.0):
         """One entry per sequence: (i, j, p, unpaired) -- the cells (i, j = i + d) whose bases i and j-1 (0-based) pair with
         probability p >= min_prob, in (i, j) order, and the probability that each base is unpaired."""
@@ -540,6 +582,7 @@ class Engine:
                 for k, (a, b) in enumerate(zip(bounds[:-1], bounds[1:]))]
 
     # ---- maximum expected accuracy structures under the motif model
+    @_in_world
     def mea_structures(self, x, gamma=1.0, min_prob=None):
         """(structures, scores, pairs): per sequence the nested structure of kept pairs ('(', ')', '.') that maximises the sum of
         2 gamma P over its pairs plus the sum of the unpaired probabilities over its unpaired bases, and that sum.  pairs: what
@@ -593,6 +636,7 @@ class Engine:
     # ---- stochastic samples of derivations
     SAMPLED, NO_PARSE, REFUSED = 0, 1, 2
 
+    @_in_world
     def sample_structures(self, x, n_samples, seed=0, index_base=0):
         """One entry per sequence: (rss, nodes, logp, status) -- n_samples derivations drawn with their probabilities under the
         model: rss the structure letters (O L R H B I M) of each sample, nodes an (n_samples, L) uint8 array of motif nodes
@@ -619,6 +663,7 @@ class Engine:
     # ---- structural context profiles
     CONTEXT_LETTERS = "OLRHBIM"
 
+    @_in_world
     def context_profiles(self, x):
         """One (L, 7) array per sequence: the probability that each base is exterior (O), the left (L) or right (R) base of a
         pair, or unpaired in a hairpin (H), bulge (B), interior (I) or multi-branch (M) loop -- the marginals of the rss letters,
@@ -631,6 +676,7 @@ class Engine:
         return [prof[7 * int(off[k]):7 * int(off[k + 1])].reshape(-1, 7).copy() for k in range(self.n_seq)]
 
     # ---- posterior motif-node profiles
+    @_in_world
     def node_profiles(self, x):
         """One (L, M) array per sequence, M = n_node: the probability that each base is emitted by each pattern node, in the node
         order of describe()["node"] (0 = 'z', M-1 = 'o': the numbering of psihat and of the sampler's node rows), over the
@@ -644,6 +690,7 @@ class Engine:
         return [prof[M * int(off[k]):M * int(off[k + 1])].reshape(-1, M).copy() for k in range(self.n_seq)]
 
     # ---- joint node-by-context posteriors and emission counts
+    @_in_world
     def joint_profiles(self, x, profile=False):
         """counts, an (n, M, 7, 5) array: the expected number of emissions of each base (N A C G U) by each pattern node (the
         node order of node_profiles) under each structure letter (the column order of CONTEXT_LETTERS), per sequence, reduced on
@@ -673,6 +720,7 @@ class Engine:
             self._stem_slots = np.stack([left[:K], right[:K]], axis=1)
         return self._stem_slots.copy()
 
+    @_in_world
     def stem_profiles(self, x, min_prob=np.inf):
         """counts, an (n, K, 5, 5) array: per sequence and stem slot (stem_slots) the expected number of pairs the slot emits with
         each left base and each right base (N A C G U), reduced on the device -- the table behind a stem logo (stem_logo).  With
@@ -695,6 +743,7 @@ class Engine:
         return counts, [(ii[a:b].copy(), jj[a:b].copy(), kk[a:b].copy(), q[a:b].copy()) for a, b in zip(bounds[:-1], bounds[1:])]
 
     # ---- helix posteriors
+    @_in_world
     def helix_posteriors(self, x, min_prob=0.01, min_len=2, max_len=16, structures=None):
         """Per sequence (i, j, len, p): the helices -- runs of len directly stacked pairs (i, j), (i+1, j-1), .., cells as in
         pair_posteriors -- with min_len <= len <= max_len (at most HELIX_MAX_LEN) whose joint probability p reaches min_prob, in
@@ -736,6 +785,7 @@ class Engine:
         return lists, stems
 
     # ---- loop posteriors
+    @_in_world
     def loop_posteriors(self, x, min_prob=0.01, structures=None, counts=True):
         """(closing, two, counts): what every pair closes and the two-loops, over the ensemble of pair_posteriors.  closing: per
         sequence (i, j, p, cols) -- the cells of the pair list of pair_posteriors(x, min_prob) with its p and an (n, 5) array of the
@@ -790,6 +840,7 @@ class Engine:
         return closing, two, counts, loops
 
     # ---- accessibility
+    @_in_world
     def accessibility(self, x, max_width=16):
         """One (L, U) array per sequence, U = max_width (1 .. 64): column w-1 of row p is the probability that the bases
         p .. p+w-1 are all unpaired, over the ensemble of pair_posteriors and context_profiles; NaN where the window runs off the
@@ -806,6 +857,7 @@ class Engine:
         return [acc[U * int(off[k]):U * int(off[k + 1])].reshape(-1, U).copy() for k in range(self.n_seq)]
 
     # ---- maximum expected accuracy motif alignments and site lists
+    @_in_world
     def mea_alignments(self, x, gamma=1.0, max_sites=1, profile=False):
         """One dict per sequence, decoded on the device from the node profile: rows (n_sites, L) uint8 -- row k is the valid node
         row of greatest score sum_p g N(p, row[p]), g = gamma on the pattern's nodes and 1 on 'z' and 'o', that puts no pattern
@@ -847,6 +899,12 @@ class Engine:
         ms = np.zeros(5)
         self._lib.elemdp_last_timing(self._h, _dp(ms), 5)
         return {"zeros_kept": bool(ms[3]), "slots": int(ms[4])}
+
+    def options_logged(self):
+        """entries in the record of options the inner engines of a streamed batch replay (elemdp_last_timing entry 5)"""
+        ms = np.zeros(6)
+        self._lib.elemdp_last_timing(self._h, _dp(ms), 6)
+        return int(ms[5])
 
     def profile(self):
         c = np.zeros(16)

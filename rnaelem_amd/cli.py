@@ -142,6 +142,11 @@ def build_parser():
                                           "the fields of --out-loops for the loop it closes, then the pair posterior of the closing pair "
                                           "(io.mea_loop_line); costs one MEA call (shared with --out-mea) and one loop call (shared "
                                           "with --out-loops)")
+    sub.choices["scan"].add_argument("--world", choices=list(api.WORLDS), default="mixed",
+                                     help="the ensemble every --out-* product but --out-contrast describes: the mixture of the parses "
+                                          "with the motif and those without it (mixed), the parses with the motif alone (motif) or "
+                                          "those without it alone (none); --out1 is the same in every world.  A product file of a "
+                                          "world other than mixed starts with the line '# world: <world>'")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -265,15 +270,24 @@ def cmd_train(a):
         dist.destroy_process_group()
 
 
-def sharded_write(recs, outs, rank, world, part, barrier):
+def world_header(scan_world):
+    """The first line of a product file written in a world other than the mixture ('' for the mixture)."""
+    return "" if scan_world == "mixed" else "# world: %s\n" % scan_world
+
+
+def sharded_write(recs, outs, rank, world, part, barrier, headers=None):
     """Rank k handles the contiguous range assigned_range(n, world, k): `part(records)` yields one tuple of texts per record, one
     text per file of `outs`, written to `<out>.<k>`; after a barrier rank 0 joins the parts of every file in rank order = input
-    order."""
+    order.  headers: one text per file of `outs` that the joined file starts with (none by default)."""
     from .distributed import assigned_range
     lo, hi = assigned_range(len(recs), world, rank)
     names = list(outs) if world == 1 else ["%s.%d" % (o, rank) for o in outs]
+    headers = list(headers) if headers is not None else [""] * len(outs)
     files = [open(nm, "w") for nm in names]
     try:
+        if world == 1:
+            for f, h in zip(files, headers):
+                f.write(h)
         for texts in part(recs[lo:hi]):
             for f, t in zip(files, texts):
                 f.write(t)
@@ -284,8 +298,9 @@ def sharded_write(recs, outs, rank, world, part, barrier):
         return
     barrier()
     if rank == 0:
-        for o in outs:
+        for o, h in zip(outs, headers):
             with open(o, "w") as f:
+                f.write(h)
                 for k in range(world):
                     name = "%s.%d" % (o, k)
                     with open(name) as g:
@@ -295,7 +310,7 @@ def sharded_write(recs, outs, rank, world, part, barrier):
     barrier()
 
 
-def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
+def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None, pairs_header=""):
     """Scan needs no collective: rank k scans the contiguous range assigned_range(n, world, k) and writes
     `<out1>.<k>`; after a barrier rank 0 joins the parts in rank order = input order into `out1` (the reference's writer
     emits records as its threads finish, motif_scanner.hpp:237-252; here the order is the input's).  `scan_part(records)`
@@ -304,15 +319,21 @@ def sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs=None):
     if out_pairs is None:
         sharded_write(recs, [out1], rank, world, lambda mine: ((t,) for t in scan_part(mine)), barrier)
     else:
-        sharded_write(recs, [out1, out_pairs], rank, world, scan_part, barrier)
+        sharded_write(recs, [out1, out_pairs], rank, world, scan_part, barrier, ["", pairs_header])
 
 
 def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=None, pair_min_prob=1e-3, out_mea=None, mea_gamma=1.0,
                   out_samples=None, n_samples=100, sample_seed=0, out_context=None, out_nodes=None, out_sites=None, site_gamma=1.0,
                   max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0, out_access=None, access_width=16, out_logo=None,
                   logo_min_exist=0.0, out_stems=None, out_stem_pairs=None, stem_min_prob=0.01, out_helices=None, helix_min_prob=0.01,
-                  helix_min_len=2, helix_max_len=16, out_mea_helices=None, out_loops=None, loop_min_prob=0.01, out_mea_loops=None):
+                  helix_min_len=2, helix_max_len=16, out_mea_helices=None, out_loops=None, loop_min_prob=0.01, out_mea_loops=None,
+                  scan_world="mixed"):
+    """scan_world: the world ("mixed", "motif", "none"; Engine option world) of every product but the contrast file, which holds
+    both worlds; the scan records are the same in every world.  A product file of a world other than mixed starts with
+    world_header(scan_world)."""
     from .distributed import assigned_range
+    sw = dict(world=scan_world)
+    head = world_header(scan_world)
     stem_parts = None if out_stems is None else out_stems + ".seqs"   # (as logo_parts)
     want_stems = out_stems is not None or out_stem_pairs is not None
     want_helices = out_helices is not None or out_mea_helices is not None
@@ -337,33 +358,33 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                 continue
             # (the same loaded batch; with both files one device call gives the pairs and the structures)
             if out_mea is None and not want_every:
-                prs = eng.pair_posteriors(m["x"], pair_min_prob) if out_pairs is not None else None
+                prs = eng.pair_posteriors(m["x"], pair_min_prob, **sw) if out_pairs is not None else None
             elif not want_every:
-                structs, scores, prs = eng.mea_structures(m["x"], mea_gamma, pair_min_prob if out_pairs is not None else None)
+                structs, scores, prs = eng.mea_structures(m["x"], mea_gamma, pair_min_prob if out_pairs is not None else None, **sw)
             else:   # (the stems' smallest pair posterior comes from this call's own list: every pair, cut to --pair-min-prob for the pairs file)
-                structs, scores, every = eng.mea_structures(m["x"], mea_gamma, 0.0)
+                structs, scores, every = eng.mea_structures(m["x"], mea_gamma, 0.0, **sw)
                 prs = [(ii[pp >= pair_min_prob], jj[pp >= pair_min_prob], pp[pp >= pair_min_prob], unp) for ii, jj, pp, unp in every]
-            smp = eng.sample_structures(m["x"], n_samples, sample_seed, lo + c0) if out_samples is not None else None
-            ctx = eng.context_profiles(m["x"]) if out_context is not None else None
+            smp = eng.sample_structures(m["x"], n_samples, sample_seed, lo + c0, **sw) if out_samples is not None else None
+            ctx = eng.context_profiles(m["x"], **sw) if out_context is not None else None
             # (with both files one node pass gives the profiles and the sites)
             if out_sites is not None:
-                sit = eng.mea_alignments(m["x"], site_gamma, max_sites, profile=out_nodes is not None)
+                sit = eng.mea_alignments(m["x"], site_gamma, max_sites, profile=out_nodes is not None, **sw)
                 nod = [r["profile"] for r in sit] if out_nodes is not None else None
             else:
-                nod = eng.node_profiles(m["x"]) if out_nodes is not None else None
+                nod = eng.node_profiles(m["x"], **sw) if out_nodes is not None else None
             con = eng.conditional_pairs(m["x"], contrast_min_prob, contrast_gamma) if out_contrast is not None else None
-            acc = eng.accessibility(m["x"], access_width) if out_access is not None else None
-            jnt = eng.joint_profiles(m["x"]) if out_logo is not None else None
+            acc = eng.accessibility(m["x"], access_width, **sw) if out_access is not None else None
+            jnt = eng.joint_profiles(m["x"], **sw) if out_logo is not None else None
             if want_stems:      # (one call gives the counts and the list)
-                stm = eng.stem_profiles(m["x"], stem_min_prob if out_stem_pairs is not None else np.inf)
+                stm = eng.stem_profiles(m["x"], stem_min_prob if out_stem_pairs is not None else np.inf, **sw)
                 stm_counts, stm_lists = stm if out_stem_pairs is not None else (stm, None)
             if want_helices:    # (one call gives the list and the stems of the MEA structures)
                 hlx = eng.helix_posteriors(m["x"], helix_min_prob if out_helices is not None else np.inf, helix_min_len, helix_max_len,
-                                           structs if out_mea_helices is not None else None)
+                                           structs if out_mea_helices is not None else None, **sw)
                 hlx_lists, hlx_stems = hlx if out_mea_helices is not None else (hlx, None)
             if want_loops:      # (one call gives the lists and the loops of the MEA structures)
                 lps = eng.loop_posteriors(m["x"], loop_min_prob if out_loops is not None else np.inf,
-                                          structs if out_mea_loops is not None else None, counts=False)
+                                          structs if out_mea_loops is not None else None, counts=False, **sw)
                 lp_closing, lp_two = lps[0], lps[1]
                 lp_mea = lps[3] if out_mea_loops is not None else None
             for k, ((rid, codes, _), r) in enumerate(zip(part, res)):
@@ -408,19 +429,33 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
 
     if out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None and out_contrast is None \
             and out_access is None and out_logo is None and not want_stems and not want_helices and not want_loops:
-        sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs)
+        sharded_scan(recs, out1, rank, world, scan_part, barrier, out_pairs, head)
     else:
         outs = [out1] + [o for o in (out_pairs, out_mea, out_samples, out_context, out_nodes, out_sites, out_contrast, out_access, logo_parts,
                                    out_stem_pairs, stem_parts, out_helices, out_mea_helices, out_loops, out_mea_loops) if o is not None]
-        sharded_write(recs, outs, rank, world, scan_part, barrier)
+        # (no header on the scan records, the contrast file and the per-sequence records the two tables are summed from)
+        plain = (out1, out_contrast, logo_parts, stem_parts)
+        sharded_write(recs, outs, rank, world, scan_part, barrier, ["" if o in plain else head for o in outs])
     if out_logo is not None:
         if rank == 0:
             write_logo_from_parts(logo_parts, out_logo, nodes, logo_min_exist)
+            _prepend(out_logo, head)
         barrier()
     if out_stems is not None:
         if rank == 0:
             write_stems_from_parts(stem_parts, out_stems, nodes, slots, logo_min_exist)
+            _prepend(out_stems, head)
         barrier()
+
+
+def _prepend(path, head):
+    """Put `head` in front of a (small) finished file; nothing to do for an empty head."""
+    if not head:
+        return
+    with open(path) as f:
+        body = f.read()
+    with open(path, "w") as f:
+        f.write(head + body)
 
 
 def write_stems_from_parts(parts_path, out_stems, nodes, slots, min_exist=0.0):
@@ -457,7 +492,7 @@ def cmd_scan(a):
                   a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites,
                   a.out_contrast, a.contrast_min_prob, a.contrast_gamma, a.out_access, a.access_width, a.out_logo, a.logo_min_exist,
                   a.out_stems, a.out_stem_pairs, a.stem_min_prob, a.out_helices, a.helix_min_prob, a.helix_min_len, a.helix_max_len,
-                  a.out_mea_helices, a.out_loops, a.loop_min_prob, a.out_mea_loops)
+                  a.out_mea_helices, a.out_loops, a.loop_min_prob, a.out_mea_loops, a.world)
     if world > 1:
         dist.destroy_process_group()
 

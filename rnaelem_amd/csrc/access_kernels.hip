@@ -145,7 +145,7 @@ hipError_t launch_access_chains(const LinArgs& a, const AccessArgs& c, int G, in
   const size_t lds = acc_lds_bytes(n_lin, n_vec, c.U, n_ints);
   if (lds > kLdsMax) return hipErrorInvalidValue;   // (some thousand interval states: no such pattern is accepted)
   const int nb = (Lmax + 1 + kAccWaves - 1) / kAccWaves;
-  hipLaunchKernelGGL(k_access_chains, dim3(ACC_TERMS * nb, G), dim3(kThreads), lds, st, a, c, n_vec, n_ints, n_lin);
+  hipLaunchKernelGGL(k_access_chains, dim3(ACC_TERMS * nb, G), dim3(kThreads), lds, st, lin_in_world(a), c, n_vec, n_ints, n_lin);
   return hipGetLastError();
 }
 hipError_t launch_access_seq(const AccessArgs& c, int G, hipStream_t st) {

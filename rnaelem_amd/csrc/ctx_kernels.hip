@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kThreads) void k_ctx_seq(CtxArgs c) {
 
 hipError_t launch_ctx_cells(const LinArgs& a, const CtxArgs& c, int G, int cells_max, hipStream_t st) {
   if (G <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_ctx_cells, dim3((cells_max + kThreads - 1) / kThreads, G), dim3(kThreads), 0, st, a, c);
+  hipLaunchKernelGGL(k_ctx_cells, dim3((cells_max + kThreads - 1) / kThreads, G), dim3(kThreads), 0, st, lin_in_world(a), c);
   return hipGetLastError();
 }
 hipError_t launch_ctx_seq(const CtxArgs& c, int G, hipStream_t st) {

@@ -280,6 +280,8 @@ class Engine {
   // handle holds: elemdp_last_timing entries 3 and 4
   bool last_zeros_kept() const { return last_zeros_kept_; }
   int slots_held() const { return slots_.n_held(); }
+  // options recorded for the inner engines of a streamed batch (elemdp_last_timing entry 5: setting "world" around every call adds none)
+  int options_logged() const { return (int)opt_log_.size(); }
 
  private:
   void upload_params(const double* x, const AutomatonLayout& lay, bool trivial);
@@ -340,7 +342,7 @@ class Engine {
   template <class Fill, class Group> int scan_sums(const ScanPos& pos, Fill fill, Group group, std::vector<int32_t>* flagged = nullptr);
   template <class Fill, class Behind> void scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind behind);
   template <class Fill, class Group, class LogFill, class Behind>
-  int scan_both_forms(const ScanPos& pos, Fill fill, Group group, LogFill log_fill, Behind behind);
+  int scan_both_forms(const ScanPos& pos, Fill fill, Group group, LogFill log_fill, Behind behind, bool in_world = true);
   void finish_call(int n_flagged);
   template <class Copy> void finish_call(int n_flagged, Copy copy_out);
   int node_profile_device(const char* what, const double* x, int n_param_in);
@@ -367,6 +369,7 @@ class Engine {
   int lock_slots_ = 0;
   bool last_zeros_kept_ = false;
   unsigned long long plan_gen_ = 0;   // identity of plan_, its mask and its lists (ZeroBinding::plan)
+  int opt_world_ = 0;       // 0 mixture, 1 motif, 2 none: the world of the scan family's posterior products
   bool opt_poison_ = false; // tests: the table slots are filled with NaN before every evaluation of the scaled-linear pipeline, so
                             // that a read of an entry nobody stored shows up in the results (the compact tables hold garbage there)
   void require_device() const;
@@ -720,6 +723,10 @@ void Engine::set_option(const std::string& key, double v) {
   else if (key == "dbg") opt_dbg_ = (int)v;
   else if (key == "bpp_log") opt_bpp_log_ = v != 0;
   else if (key == "poison") opt_poison_ = v != 0;
+  else if (key == "world") {   // (the scan family's posterior products: the mixture, the parses with the motif, those without it)
+    if (v != 0 && v != 1 && v != 2) throw ArgError("world: 0 (mixture, default), 1 (motif) or 2 (none)");
+    opt_world_ = (int)v;
+  }
   else if (key == "own_slots") opt_own_slots_ = v != 0;
   else if (key == "fast") opt_fast_ = v != 0;
   else if (key == "deterministic") opt_det_ = v != 0;
@@ -749,8 +756,12 @@ void Engine::set_option(const std::string& key, double v) {
     if (has_device_) { DeviceGuard dg(device_); HIP_OK(hipStreamSynchronize(st_)); upload_automaton(); }
   }
   else throw ArgError("unknown option: " + key);
-  for (auto& m : st_mask_) m.clear();                  // (an option may change the filter: cached masks of a streamed batch go)
-  opt_log_.emplace_back(key, v);                       // (replayed on the inner engines of a streamed batch)
+  if (key != "world") for (auto& m : st_mask_) m.clear();   // (an option may change the filter: cached masks of a streamed batch go)
+  // (replayed on the inner engines of a streamed batch; world, set around every call, takes one entry however often it is set)
+  auto at = key == "world" ? std::find_if(opt_log_.begin(), opt_log_.end(), [&](const std::pair<std::string, double>& kv) { return kv.first == key; })
+                           : opt_log_.end();
+  if (at != opt_log_.end()) at->second = v;
+  else opt_log_.emplace_back(key, v);
   for (auto& e : sub_) if (e) e->set_option(key, v);
 }
 
@@ -2269,11 +2280,22 @@ void Engine::scan_log_form(bool sums_on_batch, int n_flagged, Fill fill, Behind 
 // Both forms of a scan-family call, queued behind ev_[1]: the sum passes on the batch under pipeline 4 (scan_sums: fill, group),
 // then the log-space form for what they flagged, or for the whole batch otherwise (scan_log_form: log_fill, behind).  Returns the
 // number of sequences the range check flagged.
+// in_world: the call honours option world -- both argument records carry the world, the group work starts with
+// launch_lin_world_group, and a world other than the mixture takes the range check over all three Z (LinArgs::range_all).
 template <class Fill, class Group, class LogFill, class Behind>
-int Engine::scan_both_forms(const ScanPos& pos, Fill fill, Group group, LogFill log_fill, Behind behind) {
+int Engine::scan_both_forms(const ScanPos& pos, Fill fill, Group group, LogFill log_fill, Behind behind, bool in_world) {
   const bool sums_on_batch = opt_pipeline_ == 4;
-  const int n_flagged = sums_on_batch ? scan_sums(pos, fill, group) : 0;
-  scan_log_form(sums_on_batch, n_flagged, log_fill, behind);
+  const int world = in_world ? opt_world_ : 0;
+  const int n_flagged = sums_on_batch ? scan_sums(pos, [&](LinArgs& a) {
+    fill(a);
+    a.world = world;
+    if (world != 0) a.range_all = 1;
+  }, group) : 0;
+  scan_log_form(sums_on_batch, n_flagged, [&](DpArgs& d, int n_blocks, int n_log) {
+    const int chunk = log_fill(d, n_blocks, n_log);
+    d.smp.world = world;      // (behind the fill: the sampler's fill copies its whole record)
+    return chunk;
+  }, behind);
   return n_flagged;
 }
 
@@ -2428,10 +2450,10 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
     at_slot(pa, 0);
     pair_plane_fields(pa, a);
   }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    HIP_OK(launch_lin_world_group(ak, G, Lg, Wg, st));
     PairArgs pk = pa;
     pk.idx = ak.grp;
-    pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+    pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs + ak.world;
     at_slot(pk, slot0);
     HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
     HIP_OK(launch_pair_seq(pk, G, st));
@@ -2581,7 +2603,7 @@ void Engine::pair_conditional(const double* x, int n_param_in, double min_prob, 
     ck.z = d_cd_z_.as<double>(); ck.z_log = 1;
     HIP_OK(launch_cond_seq(ck, C, st_));
     launch_mea(ck, pm, C, st_);
-  });
+  }, false);   // (both worlds by definition: option world does not apply)
   finish_call(n_flagged, [&] { *n_pairs = conds_.finish(st_); });   // the list in (sequence, i, j) order
   auto get = [&](void* dst, const DevBuf& src, size_t bytes) { if (dst && bytes) HIP_OK(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost)); };
   get(out.exist, d_cd_exist_, 8 * (size_t)n);
@@ -2659,14 +2681,14 @@ void Engine::context_profile(const double* x, int n_param_in, double* profile) {
     pair_plane_fields(pa, a);
     ca.skip_flagged = 1;
   }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    HIP_OK(launch_lin_world_group(ak, G, Lg, Wg, st));
     CtxArgs ck = ca;
     ck.idx = ak.grp;
     at_slot(ck, slot0);
     if (!ca.no_rss) {
       PairArgs pk = pa;
       pk.idx = ak.grp;
-      pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+      pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs + ak.world;
       pk.P = ck.P;
       HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
       HIP_OK(launch_ctx_cells(ak, ck, G, (Lg + 1) * (Wg + 1), st));
@@ -2732,7 +2754,7 @@ void Engine::accessibility(const double* x, int n_param_in, int max_width, doubl
     n_vec = std::max(a.lay.S, a.lay.n_ap);   // (entries of a state vector: the interval states, the pairs of rule 2)
     ca.skip_flagged = 1;
   }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    HIP_OK(launch_lin_world_group(ak, G, Lg, Wg, st));
     AccessArgs ck = ca;
     ck.idx = ak.grp;
     at_slot(ck, slot0);
@@ -2808,7 +2830,7 @@ int Engine::node_profile_device(const char* what, const double* x, int n_param_i
   return scan_both_forms(pos, [&](LinArgs& a) {
     if (a.lay.shadow >= 0 || a.lay.S != lay_.S) throw std::logic_error("node_profile: the scan sweeps another automaton than the lists name");
   }, [&](const LinArgs& ak, size_t, int G, int Lg, int Wg, hipStream_t st) {
-    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    HIP_OK(launch_lin_world_group(ak, G, Lg, Wg, st));
     HIP_OK(launch_node_pos(ak, na, G, Lg, st));
   }, [&](DpArgs& d, int, int n_log) {
     d.node = na;
@@ -2866,7 +2888,7 @@ void Engine::joint_profile(const double* x, int n_param_in, double* counts, doub
     ja.X = slot_scratch<double>(d_jn_X_, ja.x_stride);
     ja.skip_flagged = 1;
   }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    HIP_OK(launch_lin_world_group(ak, G, Lg, Wg, st));
     JointArgs jk = ja;
     jk.idx = ak.grp;
     jk.X = slot_scratch<double>(d_jn_X_, ja.x_stride, slot0);
@@ -2971,7 +2993,7 @@ void Engine::stem_profile(const double* x, int n_param_in, double min_prob, doub
     sa.X = slot_scratch<double>(d_sp_X_, sa.x_stride);
     sa.skip_flagged = 1;
   }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-    HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+    HIP_OK(launch_lin_world_group(ak, G, Lg, Wg, st));
     StemArgs sk = sa;
     sk.idx = ak.grp;
     sk.X = slot_scratch<double>(d_sp_X_, sa.x_stride, slot0);
@@ -3128,7 +3150,7 @@ void Engine::helix_posteriors(const double* x, int n_param_in, int max_len, int 
       pair_plane_fields(pa, a);
       ha.skip_flagged = 1;
     }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      HIP_OK(launch_lin_world_group(ak, G, Lg, Wg, st));
       HelixArgs hk = ha;
       hk.idx = ak.grp;
       at_slot(hk, slot0);
@@ -3136,7 +3158,7 @@ void Engine::helix_posteriors(const double* x, int n_param_in, int max_len, int 
         if (want_list) {
           PairArgs pk = pa;
           pk.idx = ak.grp;
-          pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+          pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs + ak.world;
           pk.P = slot_scratch<double>(d_hx_P_, pcells, slot0);
           hk.P = pk.P;
           HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
@@ -3354,7 +3376,7 @@ void Engine::loop_posteriors(const double* x, int n_param_in, double min_prob, d
       pair_plane_fields(pa, a);
       la.skip_flagged = 1;
     }, [&](const LinArgs& ak, size_t slot0, int G, int Lg, int Wg, hipStream_t st) {
-      HIP_OK(launch_lin_scan_group(ak, G, Lg, Wg, SCAN_PASS_START, st));
+      HIP_OK(launch_lin_world_group(ak, G, Lg, Wg, st));
       LoopArgs lk = la;
       lk.idx = ak.grp;
       at_slot(lk, slot0);
@@ -3362,7 +3384,7 @@ void Engine::loop_posteriors(const double* x, int n_param_in, double min_prob, d
         if (la.want_units) {
           PairArgs pk = pa;
           pk.idx = ak.grp;
-          pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs;
+          pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs + ak.world;
           pk.P = lk.P;
           HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
           HelixArgs hk;   // (the compaction of the helix call: the kept cells whose P reaches helix_pick_bound(min_prob) = the bound)
@@ -3532,6 +3554,7 @@ void Engine::sample_structures(const double* x, int n_param_in, int n_samples, u
   sa.rss = d_sm_rss_.as<char>(); sa.node = d_sm_node_.as<uint8_t>(); sa.logp = d_sm_logp_.as<double>();
   sa.status = d_sm_status_.as<int32_t>();
   sa.stack_cap = cap;
+  sa.world = opt_world_;   // (the terminal draw of sample_rules.h)
   const ScanPos pos(n_seqpos, n);
   const int n_flagged = scan_both_forms(pos, [&](LinArgs&) {
     sa.stack_lanes = std::min(n_samples, kSampleLanes);
@@ -3998,6 +4021,7 @@ int elemdp_last_timing(elemdp_handle* h, double* ms, int32_t n) {
   for (int k = 0; k < n && k < 3; ++k) ms[k] = h->e->last_ms[k];
   if (n > 3) ms[3] = h->e->last_zeros_kept() ? 1. : 0.;
   if (n > 4) ms[4] = (double)h->e->slots_held();
+  if (n > 5) ms[5] = (double)h->e->options_logged();
   return ELEMDP_OK;
 }
 int elemdp_debug_profile(elemdp_handle* h, double* cycles, int32_t n) {

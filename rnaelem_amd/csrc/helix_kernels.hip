@@ -179,7 +179,7 @@ hipError_t launch_helix_chains(const LinArgs& a, const HelixArgs& c, int G, int 
   if (lds > kLdsMax) return hipErrorInvalidValue;
   // (the units of a sequence are a small part of its cells; a sequence's workgroups stride over them)
   const int nb = std::max(1, std::min(16, (cells_max + 64 * kHelixWaves - 1) / (64 * kHelixWaves)));
-  hipLaunchKernelGGL(k_helix_chains, dim3(nb, G), dim3(kThreads), lds, st, a, c, n_ints, n_lin);
+  hipLaunchKernelGGL(k_helix_chains, dim3(nb, G), dim3(kThreads), lds, st, lin_in_world(a), c, n_ints, n_lin);
   return hipGetLastError();
 }
 hipError_t launch_helix_seq(const HelixArgs& c, int G, hipStream_t st) {

@@ -158,12 +158,12 @@ hipError_t launch_joint_rows(const LinArgs& a, const JointArgs& c, int G, int Lm
   if (joint_lds_bytes(n_lin, a.lay.S, n_ints) > kLdsMax) n_ints = 0;   // (a large automaton: its blob stays in global memory)
   const size_t lds = joint_lds_bytes(n_lin, a.lay.S, n_ints);
   if (lds > kLdsMax) return hipErrorInvalidValue;   // (more than a thousand interval states: no such pattern is accepted)
-  hipLaunchKernelGGL(k_joint_rows, dim3((Lmax + kJointWaves - 1) / kJointWaves, G), dim3(kThreads), lds, st, a, c, n_ints, n_lin);
+  hipLaunchKernelGGL(k_joint_rows, dim3((Lmax + kJointWaves - 1) / kJointWaves, G), dim3(kThreads), lds, st, lin_in_world(a), c, n_ints, n_lin);
   return hipGetLastError();
 }
 hipError_t launch_joint_pos(const LinArgs& a, const JointArgs& c, int G, int Lmax, hipStream_t st) {
   if (G <= 0 || Lmax <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_joint_pos, dim3((Lmax + kJointWaves - 1) / kJointWaves, G), dim3(kThreads), 0, st, a, c);
+  hipLaunchKernelGGL(k_joint_pos, dim3((Lmax + kJointWaves - 1) / kJointWaves, G), dim3(kThreads), 0, st, lin_in_world(a), c);
   return hipGetLastError();
 }
 hipError_t launch_joint_counts(const JointArgs& c, int G, hipStream_t st) {

@@ -84,6 +84,11 @@ enum DpKind : int { DP_TRAIN = 0, DP_BPP = 1, DP_SCAN = 2 };
 struct TraceFrame;   // (scan_rules.h)
 struct SampleArgs {
   int32_t n_samples;
+  // option world, in the padding in front of seed: 0 = the mixture, 1 = the terminal is drawn among s0m2, s0m1
+  // alone, 2 = s00 alone.  As DpArgs::smp it is also the world of the fused scan kernel's product branches (1 / 2: the first outside
+  // pass is seeded with the ari terminals / the nasi terminal alone and normalised with that world's ln Z; no sweep for an empty
+  // world, ln Z = -inf: the product's no-parse path)
+  int32_t world;
   uint64_t seed;
   int64_t index_base;        // added to the batch index in the generator key
   char* rss; uint8_t* node; double* logp; int32_t* status;
@@ -451,6 +456,9 @@ struct LinArgs {
   // (Z = 0) is left alone by that sweep.  range_all: 1 = the range check of the inside pass looks at all three Z, as the train
   // evaluation's does, except that a Z of exactly 0 is an empty world and no range failure
   int32_t scan_terms = 0, range_all = 0;
+  // scan family, option world: the world whose Z normalises the products behind launch_lin_world_group -- the index
+  // into the slot's zs: 0 = Z(ari, nasi), 1 = Z(ari), 2 = Z(nasi)
+  int32_t world = 0;
   // train sweeps under the mask: 1 = every entry the mask calls useless already holds its 0 in these slots (an earlier evaluation of
   // the same plan on the same slots stored it: TableSlots::zeros), so the sweeps store none -- no fill of dead cells or rows, no 0
   // from the dead branch of the pair phases, dead workgroups return at once
@@ -476,6 +484,17 @@ hipError_t launch_lin_weights(const LinWeightArgs& a, hipStream_t st);
 // terminals / the nasi terminal only (LinArgs::scan_terms): the outside tables of one world of cond_rules.h, no pick
 enum ScanPass { SCAN_PASS_START = 0, SCAN_PASS_END = 1, SCAN_PASS_INSIDE = 2, SCAN_PASS_OUT_ARI = 3, SCAN_PASS_OUT_NASI = 4 };
 hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax, ScanPass pass, hipStream_t st);
+// the tables a product of the scan family reads, in the world full.world: 0 = SCAN_PASS_START as it stands; 1 / 2 =
+// SCAN_PASS_INSIDE, then k_world_empty (a sequence whose world is empty, Z_w = 0 exactly, is handed to the log-space form as a
+// sequence without a parse is, so that no product kernel meets an outside row the sweep skipped), then SCAN_PASS_OUT_ARI / _NASI
+hipError_t launch_lin_world_group(const LinArgs& full, int G, int Lmax, int Wmax, hipStream_t st);
+// the argument record a product kernel of the scan family is launched with: zs moved to the world's Z, so that the kernel's
+// zs[4 g] (LViews::zs[0]) is Z_w -- the product kernels are the same code in every world
+inline LinArgs lin_in_world(const LinArgs& a) {
+  LinArgs b = a;
+  b.zs += a.world;
+  return b;
+}
 // scan: Viterbi parse (max-plus CYK with trace records, then traceback) of a group; uses band_in / ext_in as the CYK table
 hipError_t launch_cyk_group(const LinArgs& full, int G, int Lmax, int Wmax, hipStream_t st);
 hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool first_pass_only, hipStream_t st);
@@ -527,7 +546,7 @@ struct PairArgs {
   // tab_cs[P] * cells + (d * (L+1) + i) * p_rs; the real states' columns are 0 .. ncol-1
   const double* band_in; const double* band_out; size_t band_stride;
   int32_t p_cs, p_rs, ncol;
-  const double* zs;               // per slot: Z(ari, nasi) mantissa at zs[4 g]
+  const double* zs;               // per slot: the Z mantissa that normalises P at zs[4 g] (LinArgs::zs + LinArgs::world)
   const double* seq_out; int32_t out_stride;   // row[4] != 0: the sequence left the double range (the log-space form covers it)
   int32_t skip_flagged;           // 1: leave the sequences flagged in seq_out alone (scaled-linear form)
   double* P; size_t p_stride;

@@ -736,6 +736,7 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
   m.no_prf = a.no_prf;
   m.m_min = a.m_min;
   const bool no_rss = a.no_rss != 0;
+  const bool w_ari = a.smp.world != 2, w_nasi = a.smp.world != 1;   // (option world: the terminals of the product branches)
   __shared__ int l_cell_counter;
   SweepScratch sc;
   sc.cell_counter = &l_cell_counter;
@@ -808,7 +809,8 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
       } else {
         double* Pys = l_post; double* Pyi = l_post + (L + 1); double* Pye = l_post + 2 * (L + 1);
         sweep_inside<false>(m, q, Tin, c0, no_rss, sc, pf);
-        if (tid == 0) { l_zs[0] = part_func(m, Tin, true, true); l_zs[1] = Tin.o(L, m.lay.s00); }
+        // (option world: Z of the world's terminals alone -- the mixture's with world 0; the conditional branch below runs under world 0)
+        if (tid == 0) { l_zs[0] = part_func(m, Tin, w_ari, w_nasi); l_zs[1] = Tin.o(L, m.lay.s00); }
         __syncthreads();
         if (a.smp.n_samples > 0) {   // samples (sample_rules.h): the inside tables are all they need
           __shared__ int l_status;
@@ -850,9 +852,12 @@ __global__ __launch_bounds__(kThreads, ELEMDP_MIN_WAVES) void k_dp(DpArgs a) {
           }
           continue;
         }
+        // (option world: the products below in one world -- its terminals alone and its ln Z, as the conditional branch above runs
+        // them; an empty world runs no sweep, and every branch below takes its no-parse path on ln Z = -inf)
         const double ZL = l_zs[0];
         sink.post_[0] = Pys; sink.post_[1] = Pyi;
-        sweep_outside<OUT_SCAN>(m, q, Tin, Tout, ZL, c0, true, true, sink, l_eh, no_rss, sc, pf);
+        if (a.smp.world == 0 || (ZL > ELEMDP_NEG_INF && ZL < HUGE_VAL))
+          sweep_outside<OUT_SCAN>(m, q, Tin, Tout, ZL, c0, w_ari, w_nasi, sink, l_eh, no_rss, sc, pf);
         if (a.pair_p) {   // base-pair posteriors (pair_rules.h): the tables of this first pass are all they need
           double* P = a.pair_p + (size_t)w * a.pair_stride;
           const PairLog r{ZL};

@@ -2980,6 +2980,29 @@ hipError_t launch_lin_scan_group(const LinArgs& full, int G, int Lmax, int Wmax,
   return hipGetLastError();
 }
 
+// option world, behind SCAN_PASS_INSIDE: one lane per sequence of the group.  A sequence whose world is empty
+// (Z_w = 0 exactly) and that the range check kept is flagged as a sequence without a parse is (row[4], the flagged list): the
+// outside sweep and every product kernel leave it alone, and the log-space form gives it the product's no-parse values.
+__global__ __launch_bounds__(64) void k_world_empty(LinArgs a, int G) {
+  const int g = blockIdx.x * 64 + threadIdx.x;
+  if (g >= G) return;
+  const int n = a.grp[g];
+  double* row = a.seq_out + (size_t)n * a.out_stride;
+  if (row[4] != 0. || a.zs[4 * (size_t)g + a.world] != 0.) return;
+  row[3] = 0.; row[4] = 2.; row[5] = 0.;
+  const int k = atomicAdd(&a.flagged[0], 1);
+  a.flagged[1 + k] = n;
+}
+
+hipError_t launch_lin_world_group(const LinArgs& full, int G, int Lmax, int Wmax, hipStream_t st) {
+  if (full.world == 0) return launch_lin_scan_group(full, G, Lmax, Wmax, SCAN_PASS_START, st);
+  if (G <= 0) return hipSuccess;
+  hipError_t e = launch_lin_scan_group(full, G, Lmax, Wmax, SCAN_PASS_INSIDE, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_world_empty, dim3((G + 63) / 64), dim3(64), 0, st, full, G);
+  return launch_lin_scan_group(full, G, Lmax, Wmax, full.world == 1 ? SCAN_PASS_OUT_ARI : SCAN_PASS_OUT_NASI, st);
+}
+
 hipError_t launch_lin_group(const LinArgs& full, int G, int Lmax, int Wmax, bool first_pass_only, hipStream_t st) {
   if (G <= 0) return hipSuccess;
   GroupGeom g = group_geometry(full, G, Lmax, Wmax, false);

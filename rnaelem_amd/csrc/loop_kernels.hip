@@ -259,7 +259,7 @@ hipError_t launch_loop_unary(const LinArgs& a, const LoopArgs& c, int G, int cel
   if (!loop_lds(a, 0, &n_lin, &n_ints, &lds)) return hipErrorInvalidValue;
   // (the units of a sequence are a part of its cells; a sequence's workgroups stride over them)
   const int nb = std::max(1, std::min(8, (cells_max + 4 * kThreads - 1) / (4 * kThreads)));
-  hipLaunchKernelGGL(k_loop_unary, dim3(nb, G), dim3(kThreads), lds, st, a, c, n_ints, n_lin);
+  hipLaunchKernelGGL(k_loop_unary, dim3(nb, G), dim3(kThreads), lds, st, lin_in_world(a), c, n_ints, n_lin);
   return hipGetLastError();
 }
 hipError_t launch_loop_items(const LinArgs& a, const LoopArgs& c, int G, int cells_max, hipStream_t st) {
@@ -267,7 +267,7 @@ hipError_t launch_loop_items(const LinArgs& a, const LoopArgs& c, int G, int cel
   int n_lin, n_ints; size_t lds;
   if (!loop_lds(a, kLoopWaves, &n_lin, &n_ints, &lds)) return hipErrorInvalidValue;
   const int nb = std::max(1, std::min(16, (cells_max + 64 * kLoopWaves - 1) / (64 * kLoopWaves)));
-  hipLaunchKernelGGL(k_loop_items, dim3(nb, G), dim3(kThreads), lds, st, a, c, n_ints, n_lin);
+  hipLaunchKernelGGL(k_loop_items, dim3(nb, G), dim3(kThreads), lds, st, lin_in_world(a), c, n_ints, n_lin);
   return hipGetLastError();
 }
 hipError_t launch_loop_struct(const LinArgs& a, const LoopArgs& c, int G, int Lmax, hipStream_t st) {
@@ -275,7 +275,7 @@ hipError_t launch_loop_struct(const LinArgs& a, const LoopArgs& c, int G, int Lm
   int n_lin, n_ints; size_t lds;
   if (!loop_lds(a, 0, &n_lin, &n_ints, &lds)) return hipErrorInvalidValue;
   const int nb = std::max(1, (Lmax / 2 + kThreads - 1) / kThreads);   // (a structure of L bases holds at most L / 2 pairs)
-  hipLaunchKernelGGL(k_loop_struct, dim3(nb, G), dim3(kThreads), lds, st, a, c, n_ints, n_lin);
+  hipLaunchKernelGGL(k_loop_struct, dim3(nb, G), dim3(kThreads), lds, st, lin_in_world(a), c, n_ints, n_lin);
   return hipGetLastError();
 }
 hipError_t launch_loop_seq(const LoopArgs& c, int G, hipStream_t st) {

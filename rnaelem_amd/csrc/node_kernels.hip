@@ -44,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void k_node_pos(LinArgs a, NodeArgs c) {
 
 hipError_t launch_node_pos(const LinArgs& a, const NodeArgs& c, int G, int Lmax, hipStream_t st) {
   if (G <= 0 || Lmax <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_node_pos, dim3((Lmax + kNodeWaves - 1) / kNodeWaves, G), dim3(kThreads), 0, st, a, c);
+  hipLaunchKernelGGL(k_node_pos, dim3((Lmax + kNodeWaves - 1) / kNodeWaves, G), dim3(kThreads), 0, st, lin_in_world(a), c);
   return hipGetLastError();
 }
 

@@ -14,7 +14,7 @@ __device__ __forceinline__ int sample_one(const ModelView& m, const SeqView& q, 
   uint8_t* node = sa.node + base + (int64_t)k * L;
   for (int p = 0; p < L; ++p) { rss[p] = ' '; node[p] = 0; }
   double lp = NAN;
-  const int r = sample_walk(m, q, T, sa.seed, (uint64_t)(sa.index_base + n), (uint64_t)k, node, rss, &lp, stack, sa.stack_cap);
+  const int r = sample_walk(m, q, T, sa.seed, (uint64_t)(sa.index_base + n), (uint64_t)k, node, rss, &lp, stack, sa.stack_cap, sa.world);
   if (r != SAMPLE_OK) {
     lp = NAN;
     for (int p = 0; p < L; ++p) { rss[p] = ' '; node[p] = 0; }

@@ -282,17 +282,22 @@ constexpr int sample_stack_cap(int L) { return L + 4; }
 // One sample: the terminal state among s00, s0m2, s0m1 by O(L, .) (draw 0), then the walk from O(L, s0) with frame handling and
 // writes as in trace_back: the motif node per position (node), the structure letters O L R H B I M (rss), and the log of the
 // derivation's probability (*logp).  Returns SAMPLE_OK, SAMPLE_NO_PARSE (Z = 0), or SAMPLE_REFUSED (no candidate with w > 0 at a
-// visited target, or more than cap frames).
+// visited target, or more than cap frames).  world (option world): 1 = the terminal is drawn among s0m2 and s0m1
+// alone (the parses with the motif), 2 = it is s00 (the parses without it); Z, the draw and *logp are that world's, draw 0 is
+// consumed either way, an empty world is SAMPLE_NO_PARSE.
 template <class Tab>
 ELEMDP_HD int sample_walk(const ModelView& m, const SeqView& q, const Tab& T, uint64_t seed, uint64_t index, uint64_t sample,
-                          uint8_t* node, char* rss, double* logp, TraceFrame* stack, int cap) {
+                          uint8_t* node, char* rss, double* logp, TraceFrame* stack, int cap, int world = 0) {
   const AutomatonLayout& A = m.lay;
   const int32_t* I = m.ints;
   const int L = q.L;
   *logp = 0.;
   const int term[3] = {A.s00, A.s0m2, A.s0m1};
   double v[3], Z = T.zero();
-  for (int k = 0; k < 3; ++k) { v[k] = T.o(L, term[k]); Z = T.add(Z, v[k]); }
+  for (int k = 0; k < 3; ++k) {
+    v[k] = (world == 1 && k == 0) || (world == 2 && k != 0) ? T.zero() : T.o(L, term[k]);
+    Z = T.add(Z, v[k]);
+  }
   if (!T.pos(Z)) return SAMPLE_NO_PARSE;
   uint64_t draw = 0;
   int s0 = -1;

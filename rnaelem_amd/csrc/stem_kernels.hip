@@ -151,7 +151,7 @@ hipError_t launch_stem_cells(const LinArgs& a, const StemArgs& c, int G, int cel
   if (stem_lds_bytes(n_lin, n_ints, n_list) > kLdsMax) n_list = 0;   //  then the lists)
   const size_t lds = stem_lds_bytes(n_lin, n_ints, n_list);
   if (lds > kLdsMax) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_stem_cells, dim3((cells_max + kThreads - 1) / kThreads, G), dim3(kThreads), lds, st, a, c, n_ints, n_lin, n_list);
+  hipLaunchKernelGGL(k_stem_cells, dim3((cells_max + kThreads - 1) / kThreads, G), dim3(kThreads), lds, st, lin_in_world(a), c, n_ints, n_lin, n_list);
   return hipGetLastError();
 }
 hipError_t launch_stem_counts(const StemArgs& c, int G, int Lmax, int Wmax, hipStream_t st) {
