@@ -132,6 +132,7 @@ def model_oracles(path):
         flags = (po.NO_RSS if md["no_rss"] else 0) | (po.NO_PRF if md["no_prf"] else 0) | (po.NO_ENE if md["no_ene"] else 0)
         on = po.make_oracle(md["pattern"], md["max_span"], md["max_iloop"], min_bpp=md["min_bpp"], tau=md["tau"], flags=flags,
                             par_text=po.energy_param_text(md["ene_param"]))
+        on.max_iloop_ = md["max_iloop"]          # (as ctx_check.ctx_oracle_from_model: the table references of the loop products read it)
     else:
         on = cc.ctx_oracle_from_model(path)[0]
     on.set_params(none_params(x, o.hmm(), softmax=md["softmax"]))

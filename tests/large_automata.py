@@ -139,6 +139,18 @@ def product_batch(S):
     return [s for s, _ in pairs], [q for _, q in pairs]
 
 
+# ---- one world
+
+# The shift of the pattern rows (test_cond_cpu.motif_heavy(x, hmm, by=shift) on perturbed(engine(S))) at which option world runs on
+# product_batch(S): at the plain parameters every sequence of these batches has exist_prob between 0.997 and 1, and where e is about
+# 1 the world with the motif is the mixture.  At these shifts every sequence keeps e >= cond_check.E_MIN (reference 2
+# holds) and at least one has 0.05 <= e <= 0.95, so that the worlds and the mixture are three different things
+# (tests/test_large_automata_cpu.py: test_the_world_shifts_put_exist_prob_in_mid_range).  e per sequence, from the oracle:
+#   S = 64, shift -0.6: 0.114, 0.531;   S = 126, shift -0.3: 0.822, 1.000;   S = 128, shift -1.0: 0.030, 0.116, 0.933
+WORLD_SHIFT = {64: -0.6, 126: -0.3, 128: -1.0}
+E_MID = (0.05, 0.95)
+
+
 ALL_BATCHES = (
     [("train", S, train_batch) for S in ACCEPTED] + [("many", S, many_batch) for S in LOG_SPACE] +
     [("scan", S, scan_batch) for S in SCAN] + [("group2", 126, group2_batch), ("long", 64, long_batch)] +

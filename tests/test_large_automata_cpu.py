@@ -198,9 +198,33 @@ def test_the_motif_parses_in_the_batches_of_the_gpu_file(name, S, make):
         assert np.sum(e >= cd.E_MIN) >= 2, e
 
 
+@pytest.mark.parametrize("S", la.WEIGHTED)
+def test_the_world_shifts_put_exist_prob_in_mid_range(S):
+    """la.WORLD_SHIFT on la.product_batch(S), from the oracle alone: every sequence has e >= cond_check.E_MIN or no parse with the
+    motif at all (reference 2 of tests/world_check.py holds for the whole batch), and at least one has 0.05 <= e <= 0.95.  For
+    such a sequence the motif world's context reference differs from the mixture's by more than 0.01: the mixture returned in place
+    of the world (Z(ari, nasi) for Z(ari), or the mixture's terminals as the seed of the outside sweep) cannot pass the GPU file's
+    motif-world checks, which it does wherever e is about 1."""
+    from tests import ctx_check as cc, world_check as wc
+    from tests.test_cond_cpu import motif_heavy
+    pattern = la.PATTERN[S]
+    seqs, quals = la.product_batch(S)
+    o, on = cc.ctx_oracle(pattern, 50, 30), cc.ctx_oracle(pattern, 50, 30)
+    x = motif_heavy(perturbed(engine(S)), o.hmm(), by=la.WORLD_SHIFT[S])
+    xn = cd.none_params(x, o.hmm())
+    refs = [wc.table_worlds(o, on, x, xn, s, q, ("context",)) for s, q in zip(seqs, quals)]
+    es = [r["e"] for r in refs]
+    assert all(r["e"] >= cd.E_MIN or not np.isfinite(r["Zari"]) for r in refs), es
+    mid = [r for r in refs if la.E_MID[0] <= r["e"] <= la.E_MID[1]]
+    assert mid, es
+    differ = [np.abs(r["motif"]["context"] - r["mixed"]["context"]).max() for r in mid]
+    print("S %d, shift %g: e %s, |motif - mixed| of the mid-range sequences %s" % (S, la.WORLD_SHIFT[S], es, differ))
+    assert max(differ) > 0.01, (es, differ)
+
+
 # ---- the log-space rule headers of the posterior products above 64 states
 
-PRODUCTS = ("context", "node", "joint", "stem", "access", "cond")
+PRODUCTS = ("context", "node", "joint", "stem", "access", "cond", "helix", "loop")
 ACCESS_WIDTH = 16
 
 
@@ -211,11 +235,13 @@ def test_log_space_product_rules_match_the_tables(S, product):
     tables -- on la.product_batch(S) against the table reference and with the assert_* function the GPU file uses for that
     product: a failure here is a rule that is wrong above 64 states, a failure of the GPU file alone is the kernel's mapping of
     states to lanes, chunks and scratch."""
-    from tests import access_check as ac, ctx_check as cc, joint_check as jc, node_check as nc, stem_check as sc
+    from tests import access_check as ac, ctx_check as cc, helix_check as hc, joint_check as jc, loop_check as lc, node_check as nc
+    from tests import stem_check as sc
     pattern = la.PATTERN[S]
     seqs, quals = la.product_batch(S)
     eng = engine(S)
-    x = perturbed(eng)
+    # (helices and loops at the parameters of their own files, as the GPU file runs them)
+    x = hc.helix_params(eng) if product == "helix" else lc.loop_params(eng) if product == "loop" else perturbed(eng)
     M = eng.n_node
     args = (pattern, "~T2004~", 50, 30, 1e-4, 0.1, 0)
     if product == "cond":
@@ -223,7 +249,7 @@ def test_log_space_product_rules_match_the_tables(S, product):
         drv = cd.CondDriver(*args)
     else:
         o = {"context": cc.ctx_oracle, "node": nc.node_oracle, "joint": jc.joint_oracle, "stem": sc.stem_oracle,
-             "access": ac.access_oracle}[product](pattern, 50, 30)
+             "access": ac.access_oracle, "helix": hc.helix_oracle, "loop": lc.loop_oracle}[product](pattern, 50, 30)
         o.set_params(x)
     for k, (s, q) in enumerate(zip(seqs, quals)):
         L, what = len(s), (S, product, k)
@@ -253,6 +279,18 @@ def test_log_space_product_rules_match_the_tables(S, product):
             ref, _ = ac.table_access(o, s, q, x, ACCESS_WIDTH)
             got, _, used = ac.AccessDriver(*args).access(x, s, q, ACCESS_WIDTH, ac.AccessDriver.LOG)
             ac.assert_access(got, ref, what=what)
+        elif product == "helix":
+            ref = hc.table_helices(o, s, q, x, kmax=hc.KMAX)
+            got, _, used = hc.HelixDriver(*args).helices(x, s, q, hc.HelixDriver.LOG, kmax=hc.KMAX)
+            hc.assert_helix(got, ref, what=what)
+            hc.assert_properties(got, 1e-10, what=what)
+        elif product == "loop":
+            ref = lc.table_loops(o, s, q, x)
+            r = lc.LoopDriver(*args).loops(x, s, q, lc.LoopDriver.LOG)
+            used = r["form"]
+            lc.assert_loop(r["cols"], ref[0], what=what)
+            lc.assert_two(r["two"], ref[1], what=what)
+            lc.assert_loop(r["P"], ref[2], what=(what, "P"))
         else:
             ref = cd.table_worlds(o, on, s, q)
             rec, used = drv.record(x, s, q, ref["kept"], cd.CondDriver.LOG)

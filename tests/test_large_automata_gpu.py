@@ -29,7 +29,8 @@ option names two different pipelines.  Under train_eval it is the batch pipeline
 test_train).  Under a scan-family call it is the log-space form of that call: the fused per-sequence kernel k_dp<DP_SCAN> of
 kernels.hip, one workgroup per sequence on dense tables, which also takes the sequences the range check of the scaled-linear
 form hands over.  Its sweeps merge tuples in both state chunks, and its per-workgroup scratch is sized by the state count
-(tmp: 3 (Lmax + 1) S doubles; jnt.vec: 5 S per thread; acc.vec: 2 S per lane of the first wave).  The tests named
+(tmp: 3 (Lmax + 1) S doubles; jnt.vec: 5 S per thread; acc.vec: 2 S per lane of the first wave; hlx.vec: 2 S per thread).  The
+tests named
 *_in_the_log_space_form run it on the batches and against the references of the scaled-linear cases, and
 test_both_forms_in_one_call lets the range check split one batch between the two forms."""
 import numpy as np
@@ -38,17 +39,25 @@ import pytest
 from rnaelem_amd import api
 from tests import cond_check as cd
 from tests import ctx_check as cc
+from tests import helix_check as hc
 from tests import large_automata as la
+from tests import loop_check as lc
 from tests import test_access_gpu as t_access
 from tests import test_cond_gpu as t_cond
 from tests import test_ctx_gpu as t_ctx
+from tests import test_helix_gpu as t_helix
 from tests import test_joint_gpu as t_joint
+from tests import test_loop_gpu as t_loop
 from tests import test_node_gpu as t_node
 from tests import test_node_mea_gpu as t_mea
 from tests import test_stem_gpu as t_stem
+from tests import test_world_gpu as t_world
 from tests import train_check as tc
+from tests import world_check as wc
+from tests.mea_mirror import pair_matrix
 from tests.pair_check import check_pair_path, oracle_refs
 from tests.sample_check import Driver, check_sample_path
+from tests.test_cond_cpu import motif_heavy
 from tests.test_pair_posterior_gpu import perturbed
 from tests.test_pair_shapes_gpu import oracle_maker
 from tests.test_train_shapes_gpu import LINE
@@ -458,12 +467,120 @@ def test_sampler_in_the_log_space_form(product):
     assert eng.last_timing()[2] == 0
 
 
+# ---- helices and loops (DESIGN.md sections 23 and 24)
+#
+# Their own files stop at S = 65, one state on the second pass of the strided state loops (`for (s = lane; s < S; s += 64)` of
+# k_loop_items, the HelixWave policy of k_helix_chains).  Here: a full second pass (S = 126 with the shadow state, 128 without it
+# and under n_pass 2), the general band kernels and the chains without the LDS ring under them, and in the log-space form the
+# S-sized per-thread vectors of HelixLog and LoopLog.  At the parameters of their own files (helix_check.helix_params,
+# loop_check.loop_params) and against the table references: the CPU drivers take a quarter of a minute per sequence here, and
+# tests/test_large_automata_cpu.py holds their LOG form to these same references.
+
+def helix_case(S, seqs, quals):
+    x = hc.helix_params(engine(S))
+    make = t_helix.oracle_with(la.PATTERN[S], x, W, C)
+    return x, cached((S, "helix"), lambda: t_helix.table_refs(make, seqs, quals, x, kmax=t_helix.KMAX))
+
+
+def loop_case(S, seqs, quals):
+    x = lc.loop_params(engine(S))
+    return x, cached((S, "loop"), lambda: t_loop.table_refs(t_loop.oracle_with(la.PATTERN[S], x, W, C), seqs, quals, x))
+
+
+def helices(S, seqs, quals, log, opts=()):
+    x, refs = helix_case(S, seqs, quals)
+    assert all(r is not None for r in refs)
+    eng, _ = loaded(S, seqs, quals, (PIPELINE3 if log else ()) + opts)
+    _, dense = t_helix.check_helices(eng, x, seqs, refs, kmax=t_helix.KMAX, what=(S, "log", opts) if log else S, log=log)
+    assert_log_form(eng, log)
+    if S == 128:
+        assert max(g[:, :, 4:].max() for g in dense) > 0.05          # (the planted stems: helices of five pairs and more)
+    return eng
+
+
+def loops(S, seqs, quals, log, opts=()):
+    x, refs = loop_case(S, seqs, quals)
+    assert all(r is not None for r in refs)
+    eng, _ = loaded(S, seqs, quals, (PIPELINE3 if log else ()) + opts)
+    closing, _, _ = t_loop.check_loops(eng, x, seqs, refs, what=(S, "log", opts) if log else S, log=log)
+    assert_log_form(eng, log)
+    assert sum(len(c[2]) for c in closing) > 0
+    return eng
+
+
+def test_helix_posteriors(product):
+    helices(*product[:3], False)
+
+
+def test_helix_posteriors_in_the_log_space_form(product):
+    helices(*product[:3], True)
+
+
+def test_loop_posteriors(product):
+    loops(*product[:3], False)
+
+
+def test_loop_posteriors_in_the_log_space_form(product):
+    loops(*product[:3], True)
+
+
+@pytest.mark.parametrize("run", [helices, loops], ids=["helix", "loop"])
+def test_a_workgroup_of_the_log_space_form_takes_two_sequences_of_128_states(run):
+    """pipeline 3 with option slots 2 on the three planted sequences of S = 128: one workgroup takes two sequences on the same
+    S-sized scratch (d_hx_vec_: 2 S doubles per thread at (blockIdx.x kThreads + tid) 2 S, addressed by the workgroup and not by
+    the sequence); the references of the cases above"""
+    seqs, quals = la.product_batch(128)
+    eng = run(128, seqs, quals, True, opts=(("slots", 2),))
+    assert (eng.slot_status()["slots"], eng.n_seq) == (2, 3)
+
+
+# ---- one world (DESIGN.md section 25)
+
+def world_case(S, seqs, quals):
+    """(x: params(S) with the pattern rows shifted by la.WORLD_SHIFT[S], table references of both worlds, all eight products)"""
+    x = motif_heavy(params(S), cc.ctx_oracle(la.PATTERN[S], W, C).hmm(), by=la.WORLD_SHIFT[S])
+    return x, cached((S, "world"), lambda: t_world.table_refs(la.PATTERN[S], W, x, seqs, quals))
+
+
+def worlds(product, log):
+    """Option world on more than 64 states: the launchers' move of zs to zs[4g + world], the outside sweep seeded with one
+    world's terminals and k_world_empty under the general band kernels, the chains without the LDS ring and a handle without the
+    shadow state; in the log-space form the two worlds of k_dp<DP_SCAN>.  Every sequence has e >= E_MIN and one lies in mid-range
+    (tests/test_large_automata_cpu.py), so the world with the motif is neither the mixture nor the other world."""
+    S, seqs, quals, _, _ = product
+    x, refs = world_case(S, seqs, quals)
+    es = [r["e"] for r in refs]
+    assert all(r["e"] >= wc.E_MIN or not np.isfinite(r["Zari"]) for r in refs), es
+    assert any(la.E_MID[0] <= e <= la.E_MID[1] for e in es), es
+    eng, _ = loaded(S, seqs, quals, PIPELINE3 if log else ())
+    got = t_world.check_worlds(eng, x, seqs, refs, what=(S, "log") if log else S)
+    return eng, x, seqs, refs, got
+
+
+def test_worlds(product):
+    eng, x, seqs, refs, got = worlds(product, False)
+    # a sequence whose world is empty is handed to the log-space form (k_world_empty): none here, in either world
+    n_empty = {w: sum(not np.isfinite(r["Zari" if w == "motif" else "Znasi"]) for r in refs) for w in wc.WORLDS}
+    assert n_empty == dict(motif=0, none=0)
+    assert eng.last_timing()[2] == n_empty["none"]          # (of the last call of check_worlds: the world without the motif)
+    eng.pair_posteriors(x, 0.0, world="motif")
+    assert eng.last_timing()[2] == n_empty["motif"]
+    # e X_motif + (1 - e) X_none = X_mixed on the engine's own outputs, at the oracle's e
+    mixed = wc.engine_products(eng, x, "mixed", seqs)
+    assert eng.world == "mixed"
+    for k, r in enumerate(refs):
+        wc.assert_mixture(mixed[k], got["motif"][k], got["none"][k], r["e"], what=(product[0], k, r["e"]))
+
+
+def test_worlds_in_the_log_space_form(product):
+    eng, _, _, _, _ = worlds(product, True)
+    assert eng.last_timing()[2] == 0
 
 
 # ---- both forms in one call
 
 LAM = {64: 10.0, 128: 10.0}      # lambda of Engine.initial_params, chosen on the GPU: test_both_forms_in_one_call
-MIXED_PRODUCTS = ("pairs", "context", "node", "access")
+MIXED_PRODUCTS = ("pairs", "context", "node", "access", "helix", "loop", "world")
 
 
 @pytest.mark.parametrize("what", MIXED_PRODUCTS)
@@ -474,9 +591,11 @@ def test_both_forms_in_one_call(S, what):
     the double range to k_dp<DP_SCAN>, in chunks of two, and the others keep the planes of the scaled-linear form: both forms
     fill one call's output, the log-space form addressing it by launch position.  Pair posteriors (and MEA), context and node
     profiles and accessibility at width 16 against the oracle's references at these same parameters, with the tolerances of the
-    log-space form.  lambda was chosen on an MI355X among 5, 10, 20, 30, 40, 60, 80: at S = 64 and at S = 128 alike, in every
-    one of the four calls and in scan, lambda = 5 flags 1 sequence of the 4, lambda = 10 flags 3 (two chunks), and from
-    lambda = 20 all 4 are flagged; so lambda = 10, flagged count 3, for both patterns."""
+    log-space form; helix and loop posteriors against their table references likewise; "world": pairs and context in both worlds
+    (the last call counted is context_profiles in the world with the motif).  lambda was chosen on an MI355X among 5, 10, 20,
+    30, 40, 60, 80: at S = 64 and at S = 128 alike, in every one of the first four calls and in scan, lambda = 5 flags 1 sequence
+    of the 4, lambda = 10 flags 3 (two chunks), and from lambda = 20 all 4 are flagged; so lambda = 10, flagged count 3, for
+    both patterns."""
     seqs, quals = la.mixed_form_batch(S)
     eng = engine(S, (("group", 2),))
     eng.load_batch(seqs, quals)
@@ -495,10 +614,38 @@ def test_both_forms_in_one_call(S, what):
     elif what == "node":
         make = t_node.oracle_with(pattern, x, W, C)
         t_node.check_profiles(eng, x, seqs, quals, t_node.table_refs(make, seqs, quals, x), what=(S, "mixed"), row_atol=1e-10)
-    else:
+    elif what == "access":
         refs = t_access.table_refs(t_access.maker(pattern, x, W, C), seqs, quals, x, 16)
         t_access.check_access(eng, x, seqs, refs, 16, what=(S, "mixed"), atol=1e-10, unp_atol=1e-10)
         eng.accessibility(x, 16)
+    elif what == "helix":
+        refs = t_helix.table_refs(t_helix.oracle_with(pattern, x, W, C), seqs, quals, x, kmax=t_helix.KMAX)
+        t_helix.check_helices(eng, x, seqs, refs, kmax=t_helix.KMAX, what=(S, "mixed"), log=True)
+        eng.helix_posteriors(x, 0.0, 1, t_helix.KMAX)
+    elif what == "loop":
+        refs = t_loop.table_refs(t_loop.oracle_with(pattern, x, W, C), seqs, quals, x)
+        t_loop.check_loops(eng, x, seqs, refs, what=(S, "mixed"), log=True)
+        eng.loop_posteriors(x, 0.0)
+    else:
+        # pairs and context in both worlds, with the checks and the tolerances of test_world_gpu's
+        # test_sequences_out_of_the_double_range_take_the_log_space_form: the mixture identity at the conditional call's e, the
+        # world without the motif against reference 1, P of both worlds against the conditional call
+        prods = ("pairs", "context")
+        refs = t_world.table_refs(pattern, W, x, seqs, quals, prods)
+        got = {}
+        for w in ("mixed",) + wc.WORLDS:
+            got[w] = wc.engine_products(eng, x, w, seqs, prods)
+            assert 1 <= eng.last_timing()[2] < len(seqs), (w, eng.last_timing()[2])
+        con = eng.conditional_pairs(x, 0.0)
+        for k in range(len(seqs)):
+            L, Wk = len(seqs[k]), min(len(seqs[k]), W)
+            wc.assert_mixture(got["mixed"][k], got["motif"][k], got["none"][k], con[k]["exist_prob"], what=(S, k), count_rtol=1e-12)
+            for w in wc.WORLDS:
+                np.testing.assert_allclose(got[w][k]["pairs"], pair_matrix(L, Wk, con[k]["i"], con[k]["j"], con[k]["p_" + w])[0],
+                                           rtol=0, atol=1e-12, err_msg=str((S, w, k)))
+            if np.isfinite(refs[k]["Znasi"]):
+                wc.assert_world(got["none"][k], refs[k], "none", ("pairs", "unpaired", "context"), what=(S, k))
+        eng.context_profiles(x, world="motif")
     n_flagged = int(eng.last_timing()[2])          # (of the product's own call, the last one)
     print("both forms, S %d, %s: lambda %g flags %d of %d" % (S, what, LAM[S], n_flagged, len(seqs)))
     assert 1 <= n_flagged < len(seqs), n_flagged

@@ -1,8 +1,10 @@
 """Scan posteriors in one world on the GPU: every call that honours option world against the references of
-tests/world_check.py -- the enumeration on the tiny cases, the oracle's tables at the lengths around W = 20 and on a batch at W = 50
---, the mixture identity on the engine's own outputs, the agreement with conditional_pairs, empty worlds under poisoned table
-slots, both forms in one call, groupings and a streamed batch, the mixture after a world call, the sampler, the sites, the command
-line and the refusals."""
+tests/world_check.py -- the enumeration on the tiny cases, the oracle's tables at the lengths around W = 20 and on a batch at W = 50,
+with exist_prob near 1 and in mid-range, at W = 70 and at L = 257 and 300, on the softmax, ~A2007~ and no-structure models --, the
+mixture identity on the engine's own outputs, the agreement with conditional_pairs, empty worlds under poisoned table slots, both
+forms in one call, groupings and a streamed batch (one grouping against another, then slot reuse, two group streams with groups
+of more than 64 sequences and several sequences per workgroup of the log-space form against the references), the mixture after a
+world call, the sampler, the sites, the command line and the refusals."""
 import ctypes as C
 
 import numpy as np
@@ -18,6 +20,7 @@ from tests.mea_mirror import mea_fold, pair_matrix
 from tests.test_cond_cpu import motif_heavy
 from tests.test_ctx_cpu import CASES
 from tests.test_ctx_gpu import pool_map
+from tests.test_loop_gpu import nine
 from tests.test_pair_posterior_gpu import perturbed
 from tests.test_pair_shapes_gpu import P1, PAR, batch
 from tests.test_world_cpu import WORLD_METHODS, references
@@ -117,14 +120,35 @@ W20_LENS = (1, 5, 19, 20, 21, 47)
 W50_LENS = (107, 3, 50, 51, 64, 88, 12, 33, 100)
 
 
-def shape_case(pattern, W, lens):
-    """(seqs, quals, x with the pattern rows raised by 3, table references of both worlds)"""
+W70_LENS = (66, 70, 93, 107)
+LONG_LENS = (257, 300)
+HEAVY = 3.0
+
+# Two parameter sets.  With the pattern rows raised by HEAVY every sequence that has a parse with the motif has e = exist_prob >= 0.999:
+# reference 2 is as well conditioned as it gets, but the world with the motif coincides with the mixture there, so its checks
+# cannot tell a launcher that handed the product kernels Z(ari, nasi) in place of Z(ari), or seeded the outside sweep with the
+# mixture's terminals, from a right one.  With the rows shifted by MID_SHIFT, chosen per case from the oracle, e lies in mid-range:
+# the two worlds and the mixture are three different things, and reference 2 still holds at motif_atol(p, e) = atol (2 - e) / e.
+# e of the sequences that have a parse with the motif, in batch order:
+#   P1-W20       -1: 0.206, 0.687, 0.714, 0.844
+#   P3-W20       -2: 0.0584, 0.467, 0.227, 0.549
+#   P1-W50       -2: 0.472, 0.237, 0.427, 0.376, 0.547, 0.0828, 0.0745, 0.448
+#   P3-W50       -3: 0.543, 0.266, 0.658, 0.472, 0.619, 0.209, 0.0969, 0.501
+#   P1-W70       -2: 0.428, 0.211, 0.299, 0.612
+#   P1-W20-long  -2: 0.684, 0.895
+# (shift 0 leaves `((.*.))` at e >= 0.94 at W = 20 and e >= 0.999 from L = 66.)
+MID_SHIFT = {"P1-W20": -1.0, "P3-W20": -2.0, "P1-W50": -2.0, "P3-W50": -3.0, "P1-W70": -2.0, "P1-W20-long": -2.0}
+E_MID = (0.05, 0.95)
+
+
+def shape_case(pattern, W, lens, shift=HEAVY, products=wc.ALL_PRODUCTS):
+    """(seqs, quals, x with the pattern rows shifted -- raised by 3 unless told otherwise --, table references of both worlds)"""
     def compute():
         seqs, quals = batch(lens, seed=31 + W, neg_every=0)
         o = cc.ctx_oracle(pattern, W, 30)
-        x = motif_heavy(perturbed(engine_with(pattern, W)), o.hmm())
-        return seqs, quals, x, table_refs(pattern, W, x, seqs, quals)
-    return cached(("shape", pattern, W, lens), compute)
+        x = motif_heavy(perturbed(engine_with(pattern, W)), o.hmm(), by=shift)
+        return seqs, quals, x, table_refs(pattern, W, x, seqs, quals, products)
+    return cached(("shape", pattern, W, lens) if shift == HEAVY else ("shape", pattern, W, lens, shift), compute)
 
 
 @pytest.mark.parametrize("pattern,W,lens", [(P1, 20, W20_LENS), (P3, 20, W20_LENS), (P1, 50, W50_LENS), (P3, 50, W50_LENS)],
@@ -139,6 +163,33 @@ def test_shapes_against_the_tables_of_both_worlds(pattern, W, lens, opts):
     eng = engine_with(pattern, W, opts)
     eng.load_batch(seqs, quals)
     check_worlds(eng, x, seqs, refs, what=(pattern, W, opts))
+
+
+MID_SHAPES = [("P1-W20", P1, 20, W20_LENS), ("P3-W20", P3, 20, W20_LENS), ("P1-W50", P1, 50, W50_LENS), ("P3-W50", P3, 50, W50_LENS),
+              ("P1-W70", P1, 70, W70_LENS), ("P1-W20-long", P1, 20, LONG_LENS)]
+
+
+@pytest.mark.parametrize("name,pattern,W,lens", MID_SHAPES, ids=[c[0] for c in MID_SHAPES])
+@pytest.mark.parametrize("opts", [(), (("pipeline", 3),)], ids=["lin", "log"])
+def test_shapes_with_exist_prob_in_mid_range(name, pattern, W, lens, opts):
+    """The shapes above at the parameters of MID_SHIFT, where the world with the motif is not the mixture, and two more: W = 70, a
+    band wider than a wave, at L = 66 .. 107, and L = 257 and 300 at W = 20, the second tile of 256 rows of the per-sequence
+    kernels.  All eight products everywhere: at W = 20 the table references of accessibility, of the stem profile and of the joint
+    profile take under a second per sequence at L = 300 too."""
+    products = wc.ALL_PRODUCTS
+    seqs, quals, x, refs = shape_case(pattern, W, lens, MID_SHIFT[name], products)
+    es = [r["e"] for r in refs if np.isfinite(r["Zari"])]
+    print("%s, shift %g: e %s" % (name, MID_SHIFT[name], ["%.3g" % e for e in es]))
+    assert all(e >= wc.E_MIN for e in es), es
+    assert all(np.isfinite(r["Znasi"]) for r in refs) and len(es) >= len(refs) - 2
+    assert 3 * sum(E_MID[0] <= e <= E_MID[1] for e in es) >= len(es) > 0, es
+    eng = engine_with(pattern, W, opts)
+    eng.load_batch(seqs, quals)
+    got = check_worlds(eng, x, seqs, refs, products, what=(name, opts))
+    if any(k == "pipeline" for k, _ in opts):
+        assert eng.last_timing()[2] == 0
+    # (the worlds differ: the mixture in place of the world with the motif cannot pass)
+    assert max(np.abs(g["context"] - r["mixed"]["context"]).max() for g, r in zip(got["motif"], refs) if np.isfinite(r["Zari"])) > 0.01
 
 
 # ---- 3. the mixture identity on the engine's own outputs, 4. the agreement with conditional_pairs
@@ -325,6 +376,168 @@ def test_groupings_and_a_streamed_batch_give_the_same_products(opts, grouped):
     for w in WORLDS:
         same_products(wc.engine_products(eng, x, w, seqs), want[w], dict(rtol=1e-10, atol=1e-14))
     assert eng.options_logged() == n0 + 1 and eng.world == "mixed"
+
+
+def processing_groups(seqs, gsz):
+    """group index of every sequence: the engine sweeps the batch longest first (a stable sort) in groups of gsz"""
+    order = sorted(range(len(seqs)), key=lambda k: -len(seqs[k]))
+    out = [0] * len(seqs)
+    for pos, k in enumerate(order):
+        out[k] = pos // gsz
+    return out
+
+
+def test_three_slots_reused_by_seven_groups_against_the_references():
+    """Option group 3 on 20 unsorted sequences of L 5 .. 200: seven groups reuse three slots, and with them the call's scratch
+    and the world's column of zs.  Against the table references, where test_groupings_and_a_streamed_batch_give_the_same_products
+    holds one grouping to another (both could be wrong the same way).  Two sequences have an empty motif world, in different
+    groups: L = 5, shorter than the pattern, and poly-A of L = 97, which keeps no pair -- k_world_empty flags each behind the
+    inside sweep of its own group."""
+    lens = [int(v) for v in np.linspace(5, 200, 20)][::-1]
+    lens[3], lens[11] = lens[11], lens[3]
+    prods = ("pairs", "context", "nodes", "loops", "helices")
+
+    def compute():
+        seqs, quals = batch(lens, seed=53, neg_every=0)
+        seqs[lens.index(97)] = np.ones(97, dtype=np.uint8)          # (poly-A: no kept pair, so no parse with `((.*.))`)
+        x = perturbed(engine_with(P1, 50))
+        return seqs, quals, x, table_refs(P1, 50, x, seqs, quals, prods)
+    seqs, quals, x, refs = cached("group3", compute)
+    empty = [k for k, r in enumerate(refs) if not np.isfinite(r["Zari"])]
+    groups = processing_groups(seqs, 3)
+    assert sorted(len(seqs[k]) for k in empty) == [5, 97] and groups[empty[0]] != groups[empty[1]] and max(groups) == 6
+    assert all(r["e"] >= wc.E_MIN or not np.isfinite(r["Zari"]) for r in refs), [r["e"] for r in refs]
+    eng = engine_with(P1, 50, (("group", 3),))
+    eng.load_batch(seqs, quals)
+    check_worlds(eng, x, seqs, refs, prods, what="group 3")
+    eng.pair_posteriors(x, 0.0, world="motif")
+    assert eng.last_timing()[2] == len(empty)
+
+
+@pytest.mark.parametrize("group,gsz", [(128, 54), (256, 80)])
+def test_two_group_streams_and_groups_of_more_than_a_wave(group, gsz, monkeypatch, capfd):
+    """320 sequences of L 3 .. 60, 100 of them shorter than the pattern (L < 7: an empty motif world), as
+    test_two_group_streams_with_three_groups_each of tests/test_pair_shapes_gpu.py: from 128 sequences and 128 slots on, two group
+    streams with half the slots each.  Option group 128: six groups of 54 (the last 50), three per stream; option group 256:
+    four groups of 80, two per stream, so that k_world_empty runs two workgroups per group, (G + 63) / 64.  The engine sweeps the
+    batch longest first, whatever its order, so the short sequences fill the last two groups of the sweep, one on each stream,
+    and the batch order cannot put them into every group: both streams append their empty worlds to the one flagged list with
+    atomics (under option group 256, lanes of both workgroups of k_world_empty).  From the oracle: 112 empty motif worlds (12
+    longer sequences have no parse with the motif either), e >= E_MIN for the other 208.  Pairs and context in the scaled-linear form: the world without the
+    motif of every sequence against reference 1, the world with it against reference 2 where e >= E_MIN and against the
+    conventions of an empty world, exactly, where it is empty; the flagged counts; a scan afterwards, whose launcher reports the
+    groups."""
+    prods = ("pairs", "context")
+
+    def compute():
+        rng = np.random.default_rng(320)
+        lens = np.concatenate([rng.integers(3, 7, size=100), rng.integers(7, 61, size=220)])
+        rng.shuffle(lens)
+        seqs, quals = batch([int(v) for v in lens], seed=320, neg_every=0)
+        x = perturbed(engine_with(P1, 50))
+        return seqs, quals, x, table_refs(P1, 50, x, seqs, quals, prods)
+    seqs, quals, x, refs = cached("streams", compute)
+    n = len(seqs)
+    empty = {k for k, r in enumerate(refs) if not np.isfinite(r["Zari"])}
+    groups = processing_groups(seqs, gsz)
+    assert sum(len(s) < 7 for s in seqs) == 100 and all(k in empty for k in range(n) if len(seqs[k]) < 7)
+    assert {groups[k] % 2 for k in empty} == {0, 1}          # (groups are dealt to the two streams in turn)
+    assert all(np.isfinite(r["Znasi"]) for r in refs)
+    eng = engine_with(P1, 50, (("group", group),))
+    eng.load_batch(seqs, quals)
+    got, flagged = {}, {}
+    for w in WORLDS:
+        got[w] = wc.engine_products(eng, x, w, seqs, prods)
+        flagged[w] = eng.last_timing()[2]
+    assert flagged == dict(motif=len(empty), none=0), (flagged, len(empty))
+    M, K = eng.n_node, len(eng.stem_slots())
+    compared = 0
+    for k, ref in enumerate(refs):
+        L = len(seqs[k])
+        wc.assert_world(got["none"][k], ref, "none", what=(group, k, L))
+        if not np.isfinite(ref["Zari"]):
+            check_empty(got["motif"][k], L, min(L, 50), M, K, what=(group, k, L))
+        elif ref["e"] >= wc.E_MIN:
+            wc.assert_world(got["motif"][k], ref, "motif", what=(group, k, L))
+            compared += 1
+    print("two group streams, group %d: %d empty motif worlds, %d compared with reference 2" % (group, len(empty), compared))
+    assert compared >= 100, compared
+    monkeypatch.setenv("ELEMDP_LDS_DEBUG", "1")
+    capfd.readouterr()
+    recs, _ = eng.scan(x)
+    assert len(recs) == n and eng.world == "mixed"
+    sizes = [int(line.split()[3]) for line in capfd.readouterr().err.splitlines() if line.startswith("scan group: G ")]
+    assert sizes == [gsz] * (n // gsz) + ([n % gsz] if n % gsz else []), sizes
+
+
+def test_a_workgroup_of_the_log_space_form_takes_several_sequences():
+    """pipeline 3 with option slots 3: three workgroups take the nine unsorted sequences of L 20 .. 160 off the atomic counter, in
+    both worlds.  Pairs, context and loops against the table references, not against another grouping."""
+    prods = ("pairs", "context", "loops")
+    seqs, quals = nine()
+    x = perturbed(engine_with(P1, 50))
+    refs = cached("nine", lambda: table_refs(P1, 50, x, seqs, quals, prods))
+    assert all(r["e"] >= wc.E_MIN or not np.isfinite(r["Zari"]) for r in refs), [r["e"] for r in refs]
+    assert sum(np.isfinite(r["Zari"]) for r in refs) >= 4
+    eng = engine_with(P1, 50, (("pipeline", 3), ("slots", 3)))
+    eng.load_batch(seqs, quals)
+    check_worlds(eng, x, seqs, refs, prods, what="slots 3")
+    assert (eng.slot_status()["slots"], eng.n_seq) == (3, 9)
+    assert eng.last_timing()[2] == 0
+
+
+# ---- 7b. models
+
+MODELS = ["syn_sm.model", "syn_a2007.model", "2.model"]
+MODEL_PRODUCTS = ("pairs", "context", "nodes", "loops", "helices")
+
+
+def model_case(model):
+    """(model, seqs, quals, table references of both worlds): reference 1 on cond_check.none_params of the model's x (a softmax
+    model's second oracle takes the log-probabilities as plain theta: cond_check.model_oracles)"""
+    def compute():
+        path = gpath(model)
+        m = io.read_model(path)
+        # (the seed: reference 2 needs e >= E_MIN.  At seed 3 the sequence of L = 13 has e = 0.605 under syn_sm.model, 0.495 under
+        # syn_a2007.model and 0.977 under 2.model, L = 40 and 97 have e >= 0.979; the seed of the other files, len(model), leaves
+        # L = 13 at e = 3e-4 under syn_sm.model)
+        seqs, quals = batch((3, 13, 40, 97), seed=3, neg_every=0)
+        xn = cd.none_params(m["x"], cd.model_oracles(path)[0].hmm(), softmax=m["softmax"])
+        order = sorted(range(len(seqs)), key=lambda k: -len(seqs[k]))
+        # (without secondary structure the oracle's P plane means nothing -- cond_check.table_worlds has zeros for it too: the
+        # test holds the pair call to the empty list instead)
+        prods = MODEL_PRODUCTS[1:] if m["no_rss"] else MODEL_PRODUCTS
+        got = pool_map(lambda: cd.model_oracles(path),
+                       lambda oo, k: wc.table_worlds(oo[0], oo[1], m["x"], xn, seqs[k], quals[k], prods), order)
+        refs = [None] * len(seqs)
+        for k, v in zip(order, got):
+            refs[k] = v
+        return m, seqs, quals, refs
+    return cached(("model", model), compute)
+
+
+@pytest.mark.parametrize("opts", [(), (("pipeline", 3),)], ids=["lin", "log"])
+@pytest.mark.parametrize("model", MODELS)
+def test_models_against_the_tables_of_both_worlds(model, opts):
+    """softmax theta, the ~A2007~ energy parameters, and a model without secondary structure (2.model, pattern `..*..`: no pair,
+    loop or helix in either world, the lists empty and the counts 0; context and node profiles still against the references).
+    L = 3 is shorter than either pattern: an empty motif world."""
+    m, seqs, quals, refs = model_case(model)
+    assert all(r["e"] >= wc.E_MIN or not np.isfinite(r["Zari"]) for r in refs), [r["e"] for r in refs]
+    assert not np.isfinite(refs[0]["Zari"]) and sum(np.isfinite(r["Zari"]) for r in refs) >= 2 and all(np.isfinite(r["Znasi"]) for r in refs)
+    eng = io.engine_from_model(m)
+    for k, v in opts:
+        eng.set_option(k, v)
+    eng.load_batch(seqs, quals)
+    got = check_worlds(eng, m["x"], seqs, refs, MODEL_PRODUCTS[1:] if m["no_rss"] else MODEL_PRODUCTS, what=(model, opts))
+    if m["no_rss"]:
+        for w in WORLDS:
+            for g, h in zip(got[w], wc.engine_products(eng, m["x"], w, seqs, ("pairs",))):
+                assert not h["pairs"].any() and np.all(h["unpaired"] == 1.0) and not g["loops"].any() and not g["helices"].any(), w
+                assert not g["loop_counts"].any() and g["two"] == {}, w
+        assert max(np.abs(a["nodes"] - b["nodes"]).max() for a, b in zip(got["motif"], got["none"])) > 0.5
+    if opts:
+        assert eng.last_timing()[2] == 0
 
 
 # ---- 8. the mixture after a world call; scan and the conditional call ignore the option
