@@ -168,6 +168,22 @@ int elemdp_set_option(elemdp_handle* h, const char* key, double value);
  * structural energy terms of every admissible rule (energy_param.hpp:686-795). */
 int elemdp_load_batch(elemdp_handle* h, const uint8_t* seq_codes, const int32_t* seq_off, const uint8_t* qual,
                       const int32_t* qual_off, const char* fix_rss, int32_t n_seq);
+/* elemdp_load_batch with a hard structure constraint per sequence:
+ *   constraint : NULL (then the call is elemdp_load_batch(..., NULL, ...)), or the concatenated constraint strings in seq_off
+ *                indexing, one character per base:  . free   x unpaired   | paired   < paired, 5' base   > paired, 3' base
+ *                ( ) these two bases pair with each other (balanced, nested; a canonical pair within the span limits)
+ * The BPP filter runs unconstrained (elemdp_batch_bpp_eff is the filter's); behind it the pair mask keeps the filter's pairs the
+ * strings allow plus the forced pairs, and every later call -- train, scan, every posterior -- describes the constrained
+ * ensemble.  A string no structure satisfies is no error: the sequence has no parse.  ELEMDP_EINVAL: an unknown character, an
+ * unbalanced string, a forced pair that is not canonical (the message names sequence and bases), or a handle made with
+ * ELEMDP_DBG_FIX_RSS or ELEMDP_NO_RSS. */
+int elemdp_load_batch_constrained(elemdp_handle* h, const uint8_t* seq_codes, const int32_t* seq_off, const uint8_t* qual,
+                                  const int32_t* qual_off, const char* constraint, int32_t n_seq);
+/* Host only: the same mask rule on the CPU for one sequence of L bases (codes in seq), W = min(L, max_span), from the filter's
+ * pairs kept[(L+1)*(W+1)] (as elemdp_batch_pairs gives them) and a 0-terminated string of L characters: kept_out (same shape)
+ * and unp_out[L+1], "position may be emitted unpaired".  flags: ELEMDP_DBG_NO_TURN is looked at. */
+int elemdp_constraint_mask_host(const uint8_t* kept, const uint8_t* seq, const char* constraint, int32_t L, int32_t W,
+                                int32_t flags, uint8_t* kept_out, uint8_t* unp_out);
 /* per-sequence results of the BPP filter: bpp_eff[n_seq] (energy_model.hpp:265) */
 int elemdp_batch_bpp_eff(elemdp_handle* h, double* bpp_eff, int32_t n_seq);
 /* kept[(L+1)*(W+1)] (index i*(W+1)+d) of one sequence after the filter; lnbpp may be NULL */

@@ -23,7 +23,7 @@ DBG_FIX_RSS, DBG_NO_TURN = 1 << 9, 1 << 10
 # every symbol include/elemdp.h declares
 SYMBOLS = ["elemdp_last_error", "elemdp_abi_version", "elemdp_set_data_dir", "elemdp_create", "elemdp_destroy",
            "elemdp_n_param", "elemdp_n_state", "elemdp_n_node", "elemdp_initial_params", "elemdp_describe",
-           "elemdp_set_option", "elemdp_load_batch", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_pair_terms", "elemdp_pair_terms_host", "elemdp_train_eval",
+           "elemdp_set_option", "elemdp_load_batch", "elemdp_load_batch_constrained", "elemdp_constraint_mask_host", "elemdp_batch_bpp_eff", "elemdp_batch_pairs", "elemdp_useful_mask", "elemdp_useful_mask_host", "elemdp_live_blocks", "elemdp_live_blocks_host", "elemdp_live_blocks_inside", "elemdp_live_blocks_host_bits", "elemdp_pair_terms", "elemdp_pair_terms_host", "elemdp_train_eval",
            "elemdp_partial_len", "elemdp_train_partial", "elemdp_train_finish", "elemdp_set_finish_params", "elemdp_train_seq_stats", "elemdp_train_seq_counts",
            "elemdp_debug_tables", "elemdp_scan", "elemdp_pair_posteriors", "elemdp_pair_mea", "elemdp_sample", "elemdp_context_profile", "elemdp_node_profile", "elemdp_joint_profile", "elemdp_stem_slots", "elemdp_stem_profile", "elemdp_stem_list", "elemdp_helix_posteriors", "elemdp_helix_list", "elemdp_loop_posteriors", "elemdp_loop_closing_list", "elemdp_loop_two_list", "elemdp_accessibility", "elemdp_node_mea", "elemdp_pair_conditional", "elemdp_pair_conditional_list", "elemdp_pair_list", "elemdp_last_timing", "elemdp_debug_profile", "elemdp_kernel_name", "elemdp_kmer_shuffle", "elemdp_epoch_permutation",
            "elemdp_comm_unique_id", "elemdp_comm_init", "elemdp_comm_destroy"]
@@ -73,6 +73,8 @@ def load_library():
         L.elemdp_describe.argtypes = [hp, C.c_char_p, C.c_int32]
         L.elemdp_set_option.argtypes = [hp, C.c_char_p, C.c_double]
         L.elemdp_load_batch.argtypes = [hp, u8, i32, u8, i32, C.c_char_p, C.c_int32]
+        L.elemdp_load_batch_constrained.argtypes = [hp, u8, i32, u8, i32, C.c_char_p, C.c_int32]
+        L.elemdp_constraint_mask_host.argtypes = [u8, u8, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, u8, u8]
         L.elemdp_batch_bpp_eff.argtypes = [hp, dp, C.c_int32]
         L.elemdp_batch_pairs.argtypes = [hp, C.c_int32, u8, dp, C.c_int32]
         L.elemdp_useful_mask.argtypes = [hp, C.c_int32, u8, C.c_int32]
@@ -152,6 +154,42 @@ def kmer_shuffle(codes, k, iter_cnt):
     if rc:
         raise ElemdpError(rc, "kmer_shuffle")
     return out
+
+
+CONSTRAINT_ALPHABET = ".x|<>()"
+
+
+def check_constraints(constraints, lengths):
+    """The constraint strings of a batch as one list of str, None entries made free ('.' per base).  ValueError: another count of
+    strings than sequences, or a string of another length than its sequence (the concatenated form the library takes cannot show
+    either; the library checks the characters, the balance and the forced pairs)."""
+    if len(constraints) != len(lengths):
+        raise ValueError("%d constraint strings for %d sequences" % (len(constraints), len(lengths)))
+    out = []
+    for k, (c, n) in enumerate(zip(constraints, lengths)):
+        if c is None:
+            c = "." * n
+        if len(c) != n:
+            raise ValueError("constraint of sequence %d: %d characters for a sequence of %d" % (k, len(c), n))
+        out.append(c)
+    return out
+
+
+def constraint_mask_host(kept, seq, constraint, flags=0):
+    """The pair mask and the "may be unpaired" flags of one sequence under a constraint string, on the CPU: kept[(L+1), (W+1)]
+    (the filter's pairs, as Engine.pairs gives them), seq (base codes) -> (kept_out, unp[L+1])  (host; elemdp_constraint_mask_host)."""
+    kept = np.ascontiguousarray(kept, dtype=np.uint8)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    L, W = kept.shape[0] - 1, kept.shape[1] - 1
+    if len(seq) != L:
+        raise ValueError("constraint_mask_host: %d bases for a mask of %d" % (len(seq), L))
+    out = np.zeros_like(kept)
+    unp = np.zeros(L + 1, dtype=np.uint8)
+    lib = load_library()
+    rc = lib.elemdp_constraint_mask_host(_u8(kept), _u8(seq), constraint.encode(), L, W, int(flags), _u8(out), _u8(unp))
+    if rc:
+        raise ElemdpError(rc, lib.elemdp_last_error().decode())
+    return out, unp
 
 
 # planes of the usefulness mask (elemdp_useful_mask): bit of each plane
@@ -402,8 +440,9 @@ class Engine:
             self._world = int(value)
 
     # ---- batch
-    def load_batch(self, seqs, quals, fix_rss=None):
-        """seqs: list of uint8 code arrays; quals: list of uint8 arrays with len(seq)+1 entries."""
+    def load_batch(self, seqs, quals, fix_rss=None, constraints=None):
+        """seqs: list of uint8 code arrays; quals: list of uint8 arrays with len(seq)+1 entries.  constraints: a hard structure
+        constraint per sequence (a str over CONSTRAINT_ALPHABET, one character per base; None: free), or None for a plain load."""
         n = len(seqs)
         off = np.zeros(n + 1, dtype=np.int32)
         qoff = np.zeros(n + 1, dtype=np.int32)
@@ -413,7 +452,13 @@ class Engine:
         sc = np.ascontiguousarray(np.concatenate(seqs) if n else np.zeros(1), dtype=np.uint8)
         qc = np.ascontiguousarray(np.concatenate(quals) if n else np.zeros(1), dtype=np.uint8)
         fx = None if fix_rss is None else "".join(fix_rss).encode()
-        self._check(self._lib.elemdp_load_batch(self._h, _u8(sc), _i32(off), _u8(qc), _i32(qoff), fx, n))
+        if constraints is not None:
+            if fix_rss is not None:
+                raise ValueError("load_batch: constraints or fix_rss, not both")
+            cs = "".join(check_constraints(constraints, [len(s) for s in seqs])).encode()
+            self._check(self._lib.elemdp_load_batch_constrained(self._h, _u8(sc), _i32(off), _u8(qc), _i32(qoff), cs, n))
+        else:
+            self._check(self._lib.elemdp_load_batch(self._h, _u8(sc), _i32(off), _u8(qc), _i32(qoff), fx, n))
         self.n_seq, self._off, self._qoff = n, off, qoff
 
     def bpp_eff(self):

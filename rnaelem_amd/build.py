@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libelemdp.so")
-SOURCES = ["kernels.hip", "train_kernels.hip", "lin_kernels.hip", "bpp_kernels.hip", "pair_kernels.hip", "mea_kernels.hip", "sample_kernels.hip", "ctx_kernels.hip", "node_kernels.hip", "joint_kernels.hip", "stem_kernels.hip", "helix_kernels.hip", "loop_kernels.hip", "access_kernels.hip", "node_mea_kernels.hip", "cond_kernels.hip", "engine.cpp", "automaton.cpp", "energy_tables.cpp"]
+SOURCES = ["kernels.hip", "train_kernels.hip", "lin_kernels.hip", "bpp_kernels.hip", "pair_kernels.hip", "mea_kernels.hip", "sample_kernels.hip", "ctx_kernels.hip", "node_kernels.hip", "joint_kernels.hip", "stem_kernels.hip", "helix_kernels.hip", "loop_kernels.hip", "access_kernels.hip", "node_mea_kernels.hip", "cond_kernels.hip", "constraint_kernels.hip", "engine.cpp", "automaton.cpp", "energy_tables.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function", "-Wno-unused-variable"]

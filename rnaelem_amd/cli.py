@@ -32,6 +32,9 @@
                                     #   expected counts of each left and right base, over the sequences with exist_prob >=
                                     #   --logo-min-exist (io.write_stems); and one line per base pair and node pair with
                                     #   probability >= --stem-min-prob (0.01) (io.stem_pair_line)
+    python -m rnaelem_amd.cli scan  --fastq seqs.fq --motif-model model.txt --out1 scan.raw --out-pairs pairs.txt --constraints cons.txt
+                                    # every result under hard structure constraints per sequence: '>id', then one character
+                                    #   per base, . x | < > ( ) (also `eval --constraints`; io.read_constraints)
     python -m rnaelem_amd.cli       --fastq pos.fq --motif-pattern '((.*.))' --out1 model.txt --out2 scan.raw
                                     # no sub-command = what script/elem spawns: train, write the model, scan (main.cpp:47-84)
     python -m rnaelem_amd.cli eval  --fastq pos.fq --motif-model model.txt --out1 fn.txt --out2 gr.txt     (motif_eval.hpp:23-54)
@@ -147,6 +150,15 @@ def build_parser():
                                           "with the motif and those without it (mixed), the parses with the motif alone (motif) or "
                                           "those without it alone (none); --out1 is the same in every world.  A product file of a "
                                           "world other than mixed starts with the line '# world: <world>'")
+    for name in ("scan", "eval"):
+        sub.choices[name].add_argument("--constraints", default=None, metavar="FILE",
+                                       help="hard structure constraints (DESIGN.md section 26): a FASTA-like file, '>id' of a FASTQ "
+                                            "record, then one character per base: . free, x unpaired, | paired, < > paired as the 5' / 3' "
+                                            "base, ( ) these two bases pair.  Records the file does not name are free; an id the FASTQ "
+                                            "lacks or a string of another length than its sequence ends the run.  Every result then "
+                                            "describes the constrained ensemble, and a product file starts with the line "
+                                            "'# constraints: <file>'.  (train takes no constraints: its shuffled negatives and "
+                                            "look-ahead loads would need a policy of their own.)")
     sub.choices["eval"].add_argument("--out2", required=True, help="'gr:' line")
     a = sub.choices["array-eval"]
     a.add_argument("-a", "--array", type=int, required=True, help="number of parts")
@@ -275,6 +287,22 @@ def world_header(scan_world):
     return "" if scan_world == "mixed" else "# world: %s\n" % scan_world
 
 
+def constraints_header(path):
+    """The line a product file written under --constraints starts with ('' without)."""
+    return "" if path is None else "# constraints: %s\n" % path
+
+
+def read_constraints_for(recs, path):
+    """The constraint of every record (io.constraints_for) from the file of --constraints, None without one; a file the records do
+    not fit ends the run with the message."""
+    if path is None:
+        return None
+    try:
+        return io.constraints_for(recs, io.read_constraints(path), path)
+    except ValueError as e:
+        raise SystemExit("--constraints: %s" % e)
+
+
 def sharded_write(recs, outs, rank, world, part, barrier, headers=None):
     """Rank k handles the contiguous range assigned_range(n, world, k): `part(records)` yields one tuple of texts per record, one
     text per file of `outs`, written to `<out>.<k>`; after a barrier rank 0 joins the parts of every file in rank order = input
@@ -327,13 +355,14 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
                   max_sites=1, out_contrast=None, contrast_min_prob=1e-3, contrast_gamma=1.0, out_access=None, access_width=16, out_logo=None,
                   logo_min_exist=0.0, out_stems=None, out_stem_pairs=None, stem_min_prob=0.01, out_helices=None, helix_min_prob=0.01,
                   helix_min_len=2, helix_max_len=16, out_mea_helices=None, out_loops=None, loop_min_prob=0.01, out_mea_loops=None,
-                  scan_world="mixed"):
-    """scan_world: the world ("mixed", "motif", "none"; Engine option world) of every product but the contrast file, which holds
+                  scan_world="mixed", constraints=None, constraints_path=None):
+    """constraints: a hard structure constraint per record of `recs` (None entries free), or None; a product file then starts
+    with constraints_header(constraints_path).  scan_world: the world ("mixed", "motif", "none"; Engine option world) of every product but the contrast file, which holds
     both worlds; the scan records are the same in every world.  A product file of a world other than mixed starts with
     world_header(scan_world)."""
     from .distributed import assigned_range
     sw = dict(world=scan_world)
-    head = world_header(scan_world)
+    head = constraints_header(constraints_path if constraints is not None else None) + world_header(scan_world)
     stem_parts = None if out_stems is None else out_stems + ".seqs"   # (as logo_parts)
     want_stems = out_stems is not None or out_stem_pairs is not None
     want_helices = out_helices is not None or out_mea_helices is not None
@@ -348,7 +377,10 @@ def _scan_records(eng, m, recs, out1, chunk, rank, world, barrier, out_pairs=Non
     def scan_part(mine):
         for c0 in range(0, len(mine), step):        # records are independent: chunks in input order
             part = mine[c0:c0 + step]
-            eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
+            if constraints is None:
+                eng.load_batch([s for _, s, _ in part], [q for _, _, q in part])
+            else:   # (the strings of this rank's records, chunk by chunk)
+                eng.load_batch([s for _, s, _ in part], [q for _, _, q in part], constraints=constraints[lo + c0:lo + c0 + len(part)])
             res, en = eng.scan(m["x"])
             if out_pairs is None and out_mea is None and out_samples is None and out_context is None and out_nodes is None and out_sites is None \
                     and out_contrast is None and out_access is None and out_logo is None and not want_stems and not want_helices \
@@ -488,11 +520,13 @@ def cmd_scan(a):
         barrier = dist.barrier
     m = io.read_model(a.motif_model)
     eng = io.engine_from_model(m, a.device if a.device is not None else local_rank)
-    _scan_records(eng, m, io.read_fastq(a.fastq), a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
+    recs = io.read_fastq(a.fastq)
+    _scan_records(eng, m, recs, a.out1, a.chunk, rank, world, barrier, a.out_pairs, a.pair_min_prob, a.out_mea,
                   a.mea_gamma, a.out_samples, a.n_samples, a.sample_seed, a.out_context, a.out_nodes, a.out_sites, a.site_gamma, a.max_sites,
                   a.out_contrast, a.contrast_min_prob, a.contrast_gamma, a.out_access, a.access_width, a.out_logo, a.logo_min_exist,
                   a.out_stems, a.out_stem_pairs, a.stem_min_prob, a.out_helices, a.helix_min_prob, a.helix_min_len, a.helix_max_len,
-                  a.out_mea_helices, a.out_loops, a.loop_min_prob, a.out_mea_loops, a.world)
+                  a.out_mea_helices, a.out_loops, a.loop_min_prob, a.out_mea_loops, a.world,
+                  read_constraints_for(recs, a.constraints), a.constraints)
     if world > 1:
         dist.destroy_process_group()
 
@@ -532,7 +566,8 @@ def cmd_eval(a):
         torch.cuda.set_device(local_rank)
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world)
-    ev = ShardedTrainer(eng, [s for _, s, _ in recs], [q for _, _, q in recs], rank, world)
+    ev = ShardedTrainer(eng, [s for _, s, _ in recs], [q for _, _, q in recs], rank, world,
+                        constraints=read_constraints_for(recs, getattr(a, "constraints", None)))
     fn, gr, eff, _ = ev(m["x"])
     if rank == 0:
         l1, l2 = eval_text(fn, gr)

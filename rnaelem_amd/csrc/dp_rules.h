@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "device_layout.h"
+#include "live_blocks.h"
 
 // Under hipcc (the product build) the rules exist as DEVICE code only: the shipped library has no
 // host instantiation of the recurrences, hence no CPU path.  Plain g++ (tests/emul) sees inline functions.
@@ -287,8 +288,8 @@ ELEMDP_HD bool m_ok(const ModelView& m, const SeqView& q, int i, int d) {  // is
   return 0 < i && i + d < q.L && d <= q.W && m.m_min <= d;
 }
 
-// base-pair type (bio_sequence.hpp:20-26): CG=1 GC=2 GU=3 UG=4 AU=5 UA=6
-ELEMDP_HD int bp_type(int a, int b) {
+// base-pair type (bio_sequence.hpp:20-26): CG=1 GC=2 GU=3 UG=4 AU=5 UA=6   (host too: the check of a forced pair)
+ELEMDP_HOSTDEV int bp_type(int a, int b) {
   // rows N,A,C,G,U
   const int t = a * 5 + b;
   return t == 9 ? 5 : t == 13 ? 1 : t == 17 ? 2 : t == 19 ? 3 : t == 21 ? 6 : t == 23 ? 4 : 0;

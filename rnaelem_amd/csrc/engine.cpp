@@ -32,6 +32,7 @@
 #include "access_rules.h"
 #include "automaton.h"
 #include "cond_rules.h"
+#include "constraint_rules.h"
 #include "device_layout.h"
 #include "energy_tables.h"
 #include "host_prep.h"
@@ -40,6 +41,7 @@
 #include "live_blocks.h"
 #include "node_mea_rules.h"
 #include "node_rules.h"
+#include "plan_rules.h"
 #include "joint_rules.h"
 #include "sample_rules.h"
 #include "stem_rules.h"
@@ -206,7 +208,8 @@ class Engine {
   const AutomatonLayout& layout() const { return lays_.shadow >= 0 ? lays_ : lay_; }   // (what a train evaluation sweeps)
   bool softmax() const { return flags_ & ELEMDP_THETA_SOFTMAX; }
 
-  void load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix, int n);
+  void load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix, int n,
+                  const char* cons = nullptr);
   // reduce: all-reduce the vector over the communicator of elemdp_comm_init (if any) before it is handed out
   void train_partial(const double* x, int n_param, void* partial, bool device_ptr, bool reduce = false);
   void train_finish(const double* reduced, double* fn, double* gr, double* sum_eff, int32_t* n_skipped);
@@ -298,6 +301,10 @@ class Engine {
   void stage_batch(BatchShape&& b, const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix,
                    std::vector<uint8_t>& h_seq, std::vector<uint32_t>& fix_bits);
   const uint32_t* bpp_filter(const std::vector<uint32_t>& fix_bits);
+  // hard constraints: the rows of the strings, checked on the host; the mask, unp and ndot of the constrained batch
+  struct ConsRows { std::vector<uint8_t> cls, unp; std::vector<int32_t> partner, enc, ndot; };
+  ConsRows constraint_rows(const BatchShape& b, const uint8_t* seq, const int32_t* off, const char* cons, bool check_only) const;
+  const uint32_t* constrain(const uint32_t* mask, const ConsRows& rows);
   void bpp_chunks(bool lin);
   void bpp_lin_chunk(int first, int count, int64_t cells, double* lnbpp);
   void bpp_log_chunk(int first, int count, int64_t cells, double* lnbpp);
@@ -389,7 +396,7 @@ class Engine {
   bool inner_ = false;
   size_t slot_budget_ = 0, st_slot_budget_ = 0;
   std::vector<uint8_t> st_seq_, st_qual_;
-  std::vector<char> st_fix_;
+  std::vector<char> st_fix_, st_cons_;
   std::vector<double> st_rows_;                             // [Z(ari,nasi), Z(ari), Z(nasi), f, skipped] per sequence
   std::unique_ptr<Engine> sub_[2];
   std::vector<std::pair<std::string, double>> opt_log_;     // options to replay on the inner engines
@@ -413,7 +420,9 @@ class Engine {
   void set_filter_preset(const uint32_t* bits, size_t words, const double* eff) { preset_bits_ = bits; preset_words_ = words; preset_eff_ = eff; }
   void filter_result(std::vector<uint32_t>& bits, std::vector<double>& eff) {
     bits.resize(bits_words_);
-    HIP_OK(hipMemcpyAsync(bits.data(), d_okbits1_.as<void>(), sizeof(uint32_t) * bits_words_, hipMemcpyDeviceToHost, st_));
+    // (of a constrained batch the mask from before k_constrain: the cache holds the filter's result)
+    HIP_OK(hipMemcpyAsync(bits.data(), (constrained_ && d_okbits_f_.bytes()) ? d_okbits_f_.as<void>() : d_okbits1_.as<void>(), sizeof(uint32_t) * bits_words_,
+                          hipMemcpyDeviceToHost, st_));
     HIP_OK(hipStreamSynchronize(st_));
     eff.resize(h_plans_.size());
     for (size_t k = 0; k < h_plans_.size(); ++k) eff[k] = h_plans_[k].bpp_eff;
@@ -499,6 +508,10 @@ class Engine {
   std::vector<SeqPlan> h_plans_;
   std::vector<int32_t> h_order_, h_seq_off_, h_qual_off_;
   DevBuf d_seq_, d_ws_, d_unp_, d_ndot_, d_okbits0_, d_okbits1_, d_order_, d_ncanon_;
+  // a constrained batch (elemdp_load_batch_constrained): set behind the BPP filter, which sees no constraint.  The rows of the
+  // strings, and the filter's mask from before k_constrain (a streamed batch caches that one)
+  bool constrained_ = false;
+  DevBuf d_cons_cls_, d_cons_partner_, d_cons_enc_, d_okbits_f_;
   std::vector<double> h_lnbpp_;          // optional (keep_lnbpp)
   std::vector<int64_t> h_lnbpp_base_;
   PlanSet plan_;
@@ -870,7 +883,7 @@ void Engine::build_planset(PlanSet& ps, int first, int count, const uint32_t* d_
   PlanKernelArgs a;
   a.et = d_et_.as<EnergyTables>();
   a.b.seq = d_seq_.as<uint8_t>(); a.b.ws = d_ws_.as<double>(); a.b.unp = d_unp_.as<uint8_t>();
-  a.b.ndot = (flags_ & ELEMDP_DBG_FIX_RSS) ? d_ndot_.as<int32_t>() : nullptr;
+  a.b.ndot = ((flags_ & ELEMDP_DBG_FIX_RSS) || constrained_) ? d_ndot_.as<int32_t>() : nullptr;
   a.okbits = d_okbits;
   a.okbits_end = d_okbits_end_.as<uint32_t>();
   a.ncell_max = (int32_t)ncell_max;
@@ -883,7 +896,7 @@ void Engine::build_planset(PlanSet& ps, int first, int count, const uint32_t* d_
   a.p = ps.arrays();
   a.no_ene = (flags_ & ELEMDP_NO_ENERGY) ? 1 : 0;
   a.min_span = min_span();
-  a.fix_rss = (flags_ & ELEMDP_DBG_FIX_RSS) ? 1 : 0;
+  a.fix_rss = ((flags_ & ELEMDP_DBG_FIX_RSS) || constrained_) ? 1 : 0;   // (the plan builder reads ndot)
   a.count_fast = (loops_finite_ && !a.fix_rss && !getenv("ELEMDP_PLAN_ENUM_COUNT")) ? 1 : 0;
   HIP_OK(launch_plan_cells(a, d_nitems_.as<int32_t>(), st_));
   std::vector<int32_t> n_items(count);
@@ -1025,7 +1038,7 @@ DpArgs Engine::base_args(const AutomatonLayout& lay, const int32_t* d_ints, cons
 // load_batch: check; stream, or stage and upload; canonical mask; BPP filter; resident plan; commit.  A rejected batch leaves the
 // handle without a batch (ELEMDP_ESTATE for what follows) instead of the new sizes over the old device buffers.
 void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* qual, const int32_t* qoff, const char* fix,
-                        int n) {
+                        int n, const char* cons) {
   require_device();
   DeviceGuard dg(device_);
   n_seq_ = 0;
@@ -1036,10 +1049,23 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   n_closing_ = n_two_ = -1;
   streaming_ = false;
   train_rows_ = false;
+  constrained_ = false;   // (until the filter is through: it and the plan of its unfiltered mask see no constraint)
+  if (cons && (flags_ & (ELEMDP_DBG_FIX_RSS | ELEMDP_NO_RSS)))
+    throw ArgError("load_batch: constraints go with neither ELEMDP_DBG_FIX_RSS nor ELEMDP_NO_RSS");
   BatchShape shape = check_batch(seq, off, qual, qoff, fix, n);
+  // strings that constrain nothing (every character '.'): a plain load, with its popcount count pass and no extra buffer
+  if (cons && std::all_of(cons + off[0], cons + off[n], [](char c) { return c == '.'; })) cons = nullptr;
+  if (!cons) { d_cons_cls_.reset(); d_cons_partner_.reset(); d_cons_enc_.reset(); d_okbits_f_.reset(); }
+  ConsRows rows;
+  // (a streamed batch derives the rows chunk by chunk on its inner handles: the outer handle only checks the strings, so that a
+  // refusal comes at the load and names the sequence by its index in the whole batch)
+  const bool stream = should_stream(shape);
+  if (cons) rows = constraint_rows(shape, seq, off, cons, stream);
   h_seq_off_.assign(off, off + n + 1);
   h_qual_off_.assign(qoff, qoff + n + 1);
-  if (should_stream(shape)) { stream_setup(seq, off, qual, qoff, fix, std::move(shape)); return; }
+  if (cons) st_cons_.assign(cons + off[0], cons + off[n]); else st_cons_.clear();
+  if (stream) { stream_setup(seq, off, qual, qoff, fix, std::move(shape)); return; }
+  st_cons_.clear();
   std::vector<uint8_t> h_seq;      // (becomes h_seq_ at the commit)
   std::vector<uint32_t> fix_bits;  // (ELEMDP_DBG_FIX_RSS: the pairs of the fixed structures)
   stage_batch(std::move(shape), seq, off, qual, qoff, fix, h_seq, fix_bits);
@@ -1055,7 +1081,8 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   HIP_OK(hipStreamSynchronize(st_));
   for (int k = 0; k < n; ++k) h_plans_[k].n_canonical = ncanon[k];
   dbg_lap("load: uploads + canonical mask");
-  resident_plan(bpp_filter(fix_bits));
+  const uint32_t* mask = bpp_filter(fix_bits);
+  resident_plan(cons ? constrain(mask, rows) : mask);
   h_seq_.swap(h_seq);
   n_seq_ = n;   // committed: everything above succeeded
   opt_eval_first_ = opt_eval_count_ = 0;   // (an evaluation range belongs to the batch it was set for)
@@ -1091,6 +1118,45 @@ Engine::BatchShape Engine::check_batch(const uint8_t* seq, const int32_t* off, c
   if ((double)kNumBandStates * (b.Wmax + 1) * (b.Lmax + 1) * au_.S() >= 2147483648.0)
     throw ArgError("load_batch: sequence too long for this pattern (band table exceeds 2^31 entries)");
   return b;
+}
+
+// the rows of the constraint strings (concatenated, indexed as the sequences); throws on a string §26 refuses.  check_only: the
+// strings are checked and no rows are kept (every sequence writes the same scratch of the longest one)
+Engine::ConsRows Engine::constraint_rows(const BatchShape& b, const uint8_t* seq, const int32_t* off, const char* cons,
+                                         bool check_only) const {
+  ConsRows r;
+  const size_t pos_b = check_only ? (size_t)b.Lmax + 1 : (size_t)b.n_pos;
+  r.cls.assign(pos_b, 0); r.unp.assign(pos_b, 1); r.partner.assign(pos_b, -1); r.enc.assign(pos_b, -1); r.ndot.assign(pos_b, 0);
+  for (size_t k = 0; k < b.plans.size(); ++k) {
+    const SeqPlan& p = b.plans[k];
+    const uint8_t* s = seq + off[k];
+    const size_t at = check_only ? 0 : (size_t)p.pos_base;
+    const auto pair_ok = [&](int i, int j) { return canonical_pair(s, p.L, p.W, min_span(), i, j - i + 1); };
+    const std::string err = constraint_derive(cons + off[k], p.L, (int)k, pair_ok, &r.cls[at], &r.partner[at], &r.enc[at], &r.unp[at],
+                                              &r.ndot[at]);
+    if (!err.empty()) throw ArgError(err);
+  }
+  if (check_only) r = ConsRows();
+  return r;
+}
+
+// Behind the BPP filter: the constrained mask in d_okbits1_ (k_constrain, from the filter's mask wherever it lies), and the unp /
+// ndot rows of the constraint in place of the all-ones row the filter read.  The inner handle of a streamed batch keeps the
+// filter's own mask in d_okbits_f_ for the cache (filter_result); a resident batch needs no copy of it.
+const uint32_t* Engine::constrain(const uint32_t* mask, const ConsRows& rows) {
+  if (inner_ && mask == d_okbits1_.as<uint32_t>()) {
+    d_okbits_f_.alloc(sizeof(uint32_t) * bits_words_);
+    HIP_OK(hipMemcpyAsync(d_okbits_f_.as<void>(), mask, sizeof(uint32_t) * bits_words_, hipMemcpyDeviceToDevice, st_));
+    mask = d_okbits_f_.as<uint32_t>();
+  }
+  d_cons_cls_.upload(rows.cls, st_); d_cons_partner_.upload(rows.partner, st_); d_cons_enc_.upload(rows.enc, st_);
+  d_unp_.upload(rows.unp, st_); d_ndot_.upload(rows.ndot, st_);
+  HIP_OK(launch_constrain(d_plans_all_.as<SeqPlan>(), (int)h_plans_.size(), nword_max_, d_cons_cls_.as<uint8_t>(),
+                          d_cons_partner_.as<int32_t>(), d_cons_enc_.as<int32_t>(), mask, d_okbits1_.as<uint32_t>(), st_));
+  HIP_OK(hipStreamSynchronize(st_));   // (the rows are host vectors of the caller's)
+  constrained_ = true;
+  dbg_lap("load: constraint mask");
+  return d_okbits1_.as<uint32_t>();
 }
 
 // the batch arrays on the host (base codes into h_seq, the rest through the pinned staging) and their uploads on st_
@@ -1426,7 +1492,8 @@ void Engine::stream_load_chunk(int k, Engine& e) {
   const size_t s0 = (size_t)(h_seq_off_[c0] - h_seq_off_[0]), q0 = (size_t)(h_qual_off_[c0] - h_qual_off_[0]);
   const bool cached = k < (int)st_mask_.size() && !st_mask_[k].empty();
   if (cached) e.set_filter_preset(st_mask_[k].data(), st_mask_[k].size(), st_eff_[k].data());
-  e.load_batch(st_seq_.data() + s0, off.data(), st_qual_.data() + q0, qoff.data(), st_fix_.empty() ? nullptr : st_fix_.data() + s0, c1 - c0);
+  e.load_batch(st_seq_.data() + s0, off.data(), st_qual_.data() + q0, qoff.data(), st_fix_.empty() ? nullptr : st_fix_.data() + s0, c1 - c0,
+               st_cons_.empty() ? nullptr : st_cons_.data() + s0);
   if (!cached && k < (int)st_mask_.size() && st_fix_.empty() && !(flags_ & ELEMDP_NO_RSS) && min_bpp_ > 0) e.filter_result(st_mask_[k], st_eff_[k]);
   // the filter's result of the chunk, for elemdp_batch_bpp_eff (chunks write disjoint ranges)
   for (int t = c0; t < c1; ++t) h_plans_[t].bpp_eff = e.h_plans_[t - c0].bpp_eff;
@@ -3744,6 +3811,37 @@ int elemdp_load_batch(elemdp_handle* h, const uint8_t* seq_codes, const int32_t*
   ELEMDP_TRY
   if (!h) throw elemdp::ArgError("null handle");
   h->e->load_batch(seq_codes, seq_off, qual, qual_off, fix_rss, n_seq);
+  ELEMDP_CATCH
+}
+int elemdp_load_batch_constrained(elemdp_handle* h, const uint8_t* seq_codes, const int32_t* seq_off, const uint8_t* qual,
+                                  const int32_t* qual_off, const char* constraint, int32_t n_seq) {
+  ELEMDP_TRY
+  if (!h) throw elemdp::ArgError("null handle");
+  h->e->load_batch(seq_codes, seq_off, qual, qual_off, nullptr, n_seq, constraint);
+  ELEMDP_CATCH
+}
+int elemdp_constraint_mask_host(const uint8_t* kept, const uint8_t* seq, const char* constraint, int32_t L, int32_t W, int32_t flags,
+                                uint8_t* kept_out, uint8_t* unp_out) {
+  ELEMDP_TRY
+  if (!kept || !seq || !constraint || !kept_out || !unp_out || L < 1 || W < 0 || W > L)
+    throw elemdp::ArgError("elemdp_constraint_mask_host: bad argument");
+  if ((int64_t)std::strlen(constraint) != L)
+    throw elemdp::ArgError("constraint of sequence 0: " + std::to_string(std::strlen(constraint)) + " characters for a sequence of " + std::to_string(L));
+  const int min_span = (flags & ELEMDP_DBG_NO_TURN) ? 1 : 5;
+  std::vector<uint8_t> cls(L);
+  std::vector<int32_t> partner(L), enc(L);
+  const auto pair_ok = [&](int i, int j) { return elemdp::canonical_pair(seq, L, W, min_span, i, j - i + 1); };
+  const std::string err = elemdp::constraint_derive(constraint, L, 0, pair_ok, cls.data(), partner.data(), enc.data(), unp_out, nullptr);
+  if (!err.empty()) throw elemdp::ArgError(err);
+  const int64_t nc = (int64_t)(L + 1) * (W + 1);
+  const int nword = (int)((nc + 31) / 32);
+  const elemdp::ConsView c{cls.data(), partner.data(), enc.data()};
+  for (int w = 0; w < nword; ++w) {
+    uint32_t in = 0;
+    for (int k = 0; k < 32 && (int64_t)w * 32 + k < nc; ++k) in |= (kept[(size_t)w * 32 + k] ? 1u : 0u) << k;
+    const uint32_t out = elemdp::cons_word(c, L, W, w, in);
+    for (int k = 0; k < 32 && (int64_t)w * 32 + k < nc; ++k) kept_out[(size_t)w * 32 + k] = (out >> k) & 1u;
+  }
   ELEMDP_CATCH
 }
 int elemdp_batch_bpp_eff(elemdp_handle* h, double* bpp_eff, int32_t n_seq) {

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdint>
 #include <limits>
+#include <string>
 #include <vector>
 
 namespace elemdp {
@@ -48,6 +49,47 @@ inline void position_weights(const uint8_t* qual, int n_qual, double* ws, double
 inline void nondot_prefix(const char* fix, int L, int32_t* ndot) {
   ndot[0] = 0;
   for (int p = 0; p < L; ++p) ndot[p + 1] = ndot[p] + (fix[p] != '.');
+}
+
+// The per-position rows of a constraint string of L characters (constraint_rules.h: the alphabet and what the rows mean):
+// cls, partner, enc with L entries; unp ("may be emitted unpaired") and ndot (prefix counts of the positions that must pair,
+// as nondot_prefix) with L + 1 entries, either may be null.  pair_ok(i, j): may bases i < j be forced to pair (a canonical
+// pair within the span limits)?  Returns "" or what is wrong with the string, for sequence `index` of the batch.
+template <class PairOk>
+inline std::string constraint_derive(const char* cons, int L, int index, const PairOk& pair_ok, uint8_t* cls, int32_t* partner,
+                                     int32_t* enc, uint8_t* unp, int32_t* ndot) {
+  const std::string who = "constraint of sequence " + std::to_string(index) + ": ";
+  std::vector<int> open;
+  for (int p = 0; p < L; ++p) {
+    int c;
+    switch (cons[p]) {   // (cons_class of constraint_rules.h, which this header does not depend on)
+      case '.': c = 0; break;
+      case 'x': c = 1; break;
+      case '|': c = 2; break;
+      case '<': c = 3; break;
+      case '>': c = 4; break;
+      case '(': c = 5; break;
+      case ')': c = 6; break;
+      default:
+        if (cons[p] == '\0') return who + "shorter than the sequence (" + std::to_string(p) + " of " + std::to_string(L) + " characters)";
+        return who + "unknown character '" + std::string(1, cons[p]) + "' at position " + std::to_string(p);
+    }
+    cls[p] = (uint8_t)c;
+    partner[p] = -1;
+    if (c == 6) {
+      if (open.empty()) return who + "unbalanced, ')' at position " + std::to_string(p) + " closes nothing";
+      const int o = open.back();
+      open.pop_back();
+      if (!pair_ok(o, p)) return who + "bases " + std::to_string(o) + " and " + std::to_string(p) + " cannot be forced to pair (not a canonical pair within the span limits)";
+      partner[o] = p; partner[p] = o;
+    }
+    enc[p] = open.empty() ? -1 : open.back();
+    if (c == 5) open.push_back(p);
+  }
+  if (!open.empty()) return who + "unbalanced, '(' at position " + std::to_string(open.back()) + " is not closed";
+  if (unp) { for (int p = 0; p < L; ++p) unp[p] = cls[p] <= 1; unp[L] = 1; }
+  if (ndot) { ndot[0] = 0; for (int p = 0; p < L; ++p) ndot[p + 1] = ndot[p] + (cls[p] > 1); }
+  return std::string();
 }
 
 }  // namespace elemdp

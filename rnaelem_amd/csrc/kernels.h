@@ -503,6 +503,10 @@ hipError_t launch_train_group(const TrArgs& base, int G, int Lmax, int Wmax, hip
 
 hipError_t launch_mask(const BatchArrays& b, const SeqPlan* plans, int n_seq, int min_span, bool write_bits, uint32_t* okbits,
                        int32_t* n_canonical, hipStream_t st);
+// constraint_kernels.hip: the pair mask of a constrained batch from the filter's mask `in` (it may be `okbits` itself: in place)
+// and the per-position rows of constraint_derive (indexed like BatchArrays::unp, SeqPlan::pos_base)
+hipError_t launch_constrain(const SeqPlan* plans, int n_seq, int nword_max, const uint8_t* cls, const int32_t* partner,
+                            const int32_t* enc, const uint32_t* in, uint32_t* okbits, hipStream_t st);
 hipError_t launch_plan_cells(const PlanKernelArgs& a, int32_t* n_items_out, hipStream_t st);
 hipError_t launch_plan_items(const PlanKernelArgs& a, hipStream_t st);
 hipError_t launch_useful_mask(const PlanKernelArgs& a, size_t n_cells, size_t lds_cap, hipStream_t st);   // needs dmin (launch_plan_cells)

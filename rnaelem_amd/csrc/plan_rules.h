@@ -22,8 +22,8 @@ struct PlanCfg {
 // ndot[p] = number of non-'.' characters in fix[0..p); segment [a,b) is all dots iff equal counts
 ELEMDP_HD bool all_dots(const int32_t* ndot, int a, int b) { return ndot == nullptr || ndot[b] == ndot[a]; }
 
-// canonical candidate: cell (i,d) may pair by sequence alone (energy_model.hpp:216-219)
-ELEMDP_HD bool canonical_pair(const uint8_t* seq, int L, int W, int min_span, int i, int d) {
+// canonical candidate: cell (i,d) may pair by sequence alone (energy_model.hpp:216-219)   (host too: the check of a forced pair)
+ELEMDP_HOSTDEV bool canonical_pair(const uint8_t* seq, int L, int W, int min_span, int i, int d) {
   return d >= min_span && d <= W && i + d <= L && bp_type(seq[i], seq[i + d - 1]) > 0;
 }
 

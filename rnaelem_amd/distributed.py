@@ -21,13 +21,17 @@ def assigned_range(total, n, k):
 class ShardedTrainer:
     """== RNAelemTrainer::operator() (motif_trainer.hpp:595-633) over a batch sharded across ranks."""
 
-    def __init__(self, engine, seqs, quals, rank=0, world=1, use_device_buffer=True):
+    def __init__(self, engine, seqs, quals, rank=0, world=1, use_device_buffer=True, constraints=None):
+        """constraints: a hard structure constraint per sequence (Engine.load_batch), sliced with the records of the rank."""
         self.engine, self.rank, self.world = engine, rank, world
         self.total = len(seqs)
         a, b = assigned_range(self.total, world, rank)
         self.range = (a, b)
         if b > a:      # (more ranks than records: this rank contributes an all-zero partial vector)
-            engine.load_batch(seqs[a:b], quals[a:b])
+            if constraints is None:
+                engine.load_batch(seqs[a:b], quals[a:b])
+            else:
+                engine.load_batch(seqs[a:b], quals[a:b], constraints=constraints[a:b])
         self._buf = None
         self._device = use_device_buffer
         if world > 1:

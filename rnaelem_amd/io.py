@@ -42,6 +42,53 @@ def read_fastq(path, base=33):
     return recs
 
 
+def record_name(rid):
+    """The name of a FASTQ record or of a constraint record: the id line without its '@' / '>' up to the first blank."""
+    f = rid[1:].split()
+    return f[0] if f else ""
+
+
+def read_constraints(path):
+    """A FASTA-like file of hard structure constraints, '>id' then the string over api.CONSTRAINT_ALPHABET (it may run over several
+    lines) -> {name: string}.  ValueError: text before the first '>', a record without a name, a name given twice."""
+    out = {}
+    name = None
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            line = line.strip()
+            if not line:
+                continue
+            if line.startswith(">"):
+                name = record_name(line)
+                if not name:
+                    raise ValueError("%s:%d: a constraint record without a name" % (path, ln))
+                if name in out:
+                    raise ValueError("%s:%d: constraint record %r given twice" % (path, ln, name))
+                out[name] = ""
+            elif name is None:
+                raise ValueError("%s:%d: text before the first '>' line" % (path, ln))
+            else:
+                out[name] += line
+    return out
+
+
+def constraints_for(recs, cons, path="constraints"):
+    """The constraint of every record of read_fastq's list, in its order: the string `cons` (read_constraints) has under the
+    record's name, None (free) for a record it does not name.  ValueError: a name no record has, or a string of another length
+    than its sequence."""
+    names = [record_name(rid) for rid, _, _ in recs]
+    unknown = sorted(set(cons) - set(names))
+    if unknown:
+        raise ValueError("%s: no FASTQ record is named %r" % (path, unknown[0]))
+    out = []
+    for nm, (_, codes, _) in zip(names, recs):
+        c = cons.get(nm)
+        if c is not None and len(c) != len(codes):
+            raise ValueError("%s: the constraint of %r has %d characters, the sequence %d bases" % (path, nm, len(c), len(codes)))
+        out.append(c)
+    return out
+
+
 REQUIRED = ["pattern", "theta|s", "ene-param", "max-span", "rho", "rho-lambda", "tau", "lambda", "min-bpp",
             "max-internal-loop", "theta-softmax"]
 
