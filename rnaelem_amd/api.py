@@ -272,10 +272,8 @@ def pair_terms_host(mask, kept):
 HELIX_MAX_LEN = 32   # ELEMDP_HELIX_MAX_LEN
 
 
-def structure_helices(db):
-    """The stems of a dot-bracket string, host only: (i, j, len) per maximal run of directly nested pairs (i, j-1), (i+1, j-2), ..,
-    i 0-based and j exclusive as in pair_posteriors, by increasing i.  Raises ValueError for an unbalanced string or one with
-    characters other than ( ) ."""
+def _structure_mates(db):
+    """mate[p] of every position of a dot-bracket string, -1 where unpaired (structure_mates of csrc/structure_rules.h)."""
     mate, stack = [-1] * len(db), []
     for p, c in enumerate(db):
         if c == "(":
@@ -289,6 +287,14 @@ def structure_helices(db):
             raise ValueError("a structure holds ( ) . only")
     if stack:
         raise ValueError("unbalanced structure")
+    return mate
+
+
+def structure_helices(db):
+    """The stems of a dot-bracket string, host only: (i, j, len) per maximal run of directly nested pairs (i, j-1), (i+1, j-2), ..,
+    i 0-based and j exclusive as in pair_posteriors, by increasing i.  Raises ValueError for an unbalanced string or one with
+    characters other than ( ) ."""
+    mate = _structure_mates(db)
     out = []
     for p, r in enumerate(mate):
         if r < p or (p > 0 and r + 1 < len(db) and mate[p - 1] == r + 1):
@@ -316,19 +322,7 @@ def structure_loops(db):
     inner pair, a stack on the pair (i+1, j-1), a bulge with one inner pair and one empty side, an interior loop with one inner pair
     and bases on both sides, a multi-branch loop with two or more inner pairs.  (k, l) is the cell of the inner pair of a bulge or an
     interior loop, (-1, -1) otherwise.  Raises ValueError for an unbalanced string or one with characters other than ( ) ."""
-    mate, stack = [-1] * len(db), []
-    for p, c in enumerate(db):
-        if c == "(":
-            stack.append(p)
-        elif c == ")":
-            if not stack:
-                raise ValueError("unbalanced structure")
-            mate[p] = stack.pop()
-            mate[mate[p]] = p
-        elif c != ".":
-            raise ValueError("a structure holds ( ) . only")
-    if stack:
-        raise ValueError("unbalanced structure")
+    mate = _structure_mates(db)
     out = []
     for p, r in enumerate(mate):
         if r < p:

@@ -48,6 +48,7 @@
 #include "helix_rules.h"
 #include "loop_rules.h"
 #include "staged_list.h"
+#include "structure_rules.h"
 #include "table_slots.h"
 
 namespace elemdp {
@@ -434,11 +435,13 @@ class Engine {
   void stream_pairs(const double* x, int n_param, double min_prob, double* unpaired, const MeaOut* mea);
   void stream_samples(const double* x, int n_param, int n_samples, uint64_t seed, int64_t index_base, const SampleOut& out);
   void stream_cond(const double* x, int n_param, double min_prob, const CondOut& out);
-  // the lists of the last pair, conditional, stem and helix call (staged_list.h), each in buffers of its own
+  template <class List, class ChunkCall> void stream_listed(List Engine::*list, int n_param_in, ChunkCall call);
+  // the lists of the last pair, conditional, stem, helix and loop call (staged_list.h), each in buffers of its own
   StagedList pairs_{"pair_list", "pair_posteriors", 1, false};
   StagedList conds_{"pair_conditional_list", "pair_conditional", 2, false};
   StagedList stems_{"stem_list", "stem_profile", 1, true};
   StagedList helices_{"helix_list", "helix_posteriors", 1, true};
+  LoopLists loops_;
   size_t scratch_slots_ = 0;   // slots the per-slot scratch of the running scan-family call is sized for (slot_scratch)
   DevBuf d_pr_P_, d_pr_unp_;   // pair posteriors: the P(i, d) scratch of the table slots, the unpaired vector of the call
   // MEA structures: the M table and choice scratch of the table slots (as d_pr_P_), the structures and the scores of the call
@@ -459,14 +462,9 @@ class Engine {
   DevBuf d_hx_P_, d_hx_nu_, d_hx_ui_, d_hx_ud_, d_hx_nlen_, d_hx_X_, d_hx_vec_;
   DevBuf d_hx_soff_, d_hx_si_, d_hx_sd_, d_hx_slen_, d_hx_sp_;
   // loop posteriors: P, the units (count, i, d), their columns and the two-loop values per table slot; the counts of the call; the
-  // loops of the caller's structures (offsets per sequence, type, i, d, k, l) and their probabilities; kept cells, their prefix, the
-  // entries staged and their prefixes per batch index; the staging of both lists; the lists (count < 0: none)
+  // loops of the caller's structures (offsets per sequence, type, i, d, k, l) and their probabilities.  (The lists: loops_.)
   DevBuf d_lp_P_, d_lp_nu_, d_lp_ui_, d_lp_ud_, d_lp_cols_, d_lp_T_, d_lp_counts_;
   DevBuf d_lp_soff_, d_lp_st_, d_lp_si_, d_lp_sd_, d_lp_sk_, d_lp_sl_, d_lp_sp_;
-  DevBuf d_lp_kept_, d_lp_koff_, d_lp_cnt_, d_lp_cnt2_, d_lp_off_, d_lp_off2_;
-  DevBuf d_lp_sti_, d_lp_stj_, d_lp_stv_, d_lp_st2i_, d_lp_st2t_;
-  DevBuf d_lc_seq_, d_lc_i_, d_lc_j_, d_lc_v_, d_lt_seq_, d_lt_i_, d_lt_j_, d_lt_k_, d_lt_l_, d_lt_p_;
-  int64_t n_closing_ = -1, n_two_ = -1;
   DevBuf d_nd_lists_, d_nd_prof_;   // node profiles: the transitions by emitted node, the profile of the call
   // node MEA: the chain lists, the backpointer scratch (M bytes per position), the rows, sites per sequence, start / end / score / confidence per slot
   DevBuf d_nm_lists_, d_nm_bp_, d_nm_node_, d_nm_ns_, d_nm_s0_, d_nm_s1_, d_nm_sc_, d_nm_cf_;
@@ -1046,7 +1044,7 @@ void Engine::load_batch(const uint8_t* seq, const int32_t* off, const uint8_t* q
   conds_.invalidate();
   stems_.invalidate();
   helices_.invalidate();
-  n_closing_ = n_two_ = -1;
+  loops_.invalidate();
   streaming_ = false;
   train_rows_ = false;
   constrained_ = false;   // (until the filter is through: it and the plan of its unfiltered mask see no constraint)
@@ -1528,6 +1526,17 @@ template <class Checked, class Work> void Engine::stream_call(int n_param_in, Ch
     if (th.joinable()) th.join();
     if (err) std::rethrow_exception(err);
   }
+}
+
+// The streamed form of a call that keeps a list (a StagedList or the LoopLists): call(c0, at, engine) is the call on the chunk whose
+// first sequence is c0 and whose first position is at; the chunks' lists, one behind the other on the host, become this handle's.
+template <class List, class ChunkCall> void Engine::stream_listed(List Engine::*list, int n_param_in, ChunkCall call) {
+  typename List::Host host;
+  stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+    call(c0, (size_t)(h_seq_off_[c0] - h_seq_off_[0]), e);
+    host.append(e.*list, c0);
+  });
+  (this->*list).adopt(host, st_);
 }
 
 void Engine::stream_train(const double* x, int n_param_in, void* partial, bool device_ptr, bool reduce) {
@@ -2546,16 +2555,12 @@ void Engine::pair_posteriors(const double* x, int n_param_in, double min_prob, i
 }
 
 void Engine::stream_pairs(const double* x, int n_param_in, double min_prob, double* unpaired, const MeaOut* mea) {
-  StagedList::Host list;
-  stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+  stream_listed(&Engine::pairs_, n_param_in, [&](int c0, size_t at, Engine& e) {
     int64_t m = 0;
-    const int64_t at = h_seq_off_[c0] - h_seq_off_[0];   // (the chunk's first position)
     MeaOut mc;
     if (mea) mc = MeaOut{mea->gamma, mea->structure ? mea->structure + at : nullptr, mea->score ? mea->score + c0 : nullptr};
     e.pair_posteriors(x, n_param_in, min_prob, &m, unpaired ? unpaired + at : nullptr, mea ? &mc : nullptr);
-    list.append(e.pairs_, c0);
   });
-  pairs_.adopt(list, st_);
 }
 
 void Engine::pair_list(int32_t* seq, int32_t* i, int32_t* j, double* p, int64_t cap) {
@@ -2682,19 +2687,15 @@ void Engine::pair_conditional(const double* x, int n_param_in, double min_prob, 
 }
 
 void Engine::stream_cond(const double* x, int n_param_in, double min_prob, const CondOut& out) {
-  StagedList::Host list;
   conds_.invalidate();
-  stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
+  stream_listed(&Engine::conds_, n_param_in, [&](int c0, size_t at, Engine& e) {
     int64_t m = 0;
-    const int64_t at = h_seq_off_[c0] - h_seq_off_[0];   // (the chunk's first position)
     CondOut oc{out.gamma, out.exist ? out.exist + c0 : nullptr,
                {out.unpaired[0] ? out.unpaired[0] + at : nullptr, out.unpaired[1] ? out.unpaired[1] + at : nullptr},
                {out.structure[0] ? out.structure[0] + at : nullptr, out.structure[1] ? out.structure[1] + at : nullptr},
                out.shift ? out.shift + c0 : nullptr};
     e.pair_conditional(x, n_param_in, min_prob, &m, oc);
-    list.append(e.conds_, c0);
   });
-  conds_.adopt(list, st_);
 }
 
 void Engine::cond_list(int32_t* seq, int32_t* i, int32_t* j, double* p_motif, double* p_none, int64_t cap) {
@@ -3017,12 +3018,7 @@ void Engine::stem_profile(const double* x, int n_param_in, double min_prob, doub
   const bool want_list = min_prob < HUGE_VAL;
   stems_.invalidate();
   if (streaming_) {
-    StagedList::Host list;
-    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
-      e.stem_profile(x, n_param_in, min_prob, counts + nc * (size_t)c0, nullptr);
-      list.append(e.stems_, c0);
-    });
-    stems_.adopt(list, st_);
+    stream_listed(&Engine::stems_, n_param_in, [&](int c0, size_t, Engine& e) { e.stem_profile(x, n_param_in, min_prob, counts + nc * (size_t)c0, nullptr); });
     if (n_entries) *n_entries = stems_.count();
     return;
   }
@@ -3093,6 +3089,62 @@ void Engine::stem_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* slot, doub
   stems_.fetch(seq, i, j, q, nullptr, slot, cap);
 }
 
+// ---- the items -- stems or loops -- of the structures a caller hands to helix_posteriors or loop_posteriors (structure_rules.h):
+// per sequence the range off[t] .. off[t + 1] of items, of an item its 5' position i, a label (the stem's length, the loop's type)
+// and, behind the call, its probability p.  The further columns of an item are the call's own.
+static_assert(LOOP_H == 1 && LOOP_S == 2 && LOOP_B == 3 && LOOP_I == 4 && LOOP_M == 5, "structure_loops writes the types as numbers");
+struct StructItems {
+  std::vector<int64_t> off; std::vector<int32_t> i, label; std::vector<double> p;
+  // One sequence after the other: the mates of its structure, or the refusal "<call>: what is wrong"; add(mate, L) appends its items.
+  template <class Add> void parse(const char* call, const char* structure, const std::vector<int32_t>& seq_off, int n, Add add) {
+    off.assign((size_t)n + 1, 0);
+    std::vector<int32_t> mate;
+    for (int t = 0; t < n; ++t) {
+      const int L = seq_off[t + 1] - seq_off[t];
+      mate.resize((size_t)L);
+      const char* err = structure_mates(structure + (seq_off[t] - seq_off[0]), L, mate.data());
+      if (*err) throw ArgError(std::string(call) + ": " + err);
+      add(mate.data(), L);
+      off[(size_t)t + 1] = (int64_t)i.size();
+    }
+    p.assign(i.size(), 0.);
+  }
+  // Offsets, then the columns given, to the device on st; clears p there; waits (the host vectors go out of use, p is clear before any group runs).
+  using Col = std::pair<DevBuf*, const std::vector<int32_t>*>;
+  void upload_cleared(DevBuf& d_off, std::initializer_list<Col> cols, DevBuf& d_p, hipStream_t st) const {
+    d_off.upload(off, st);
+    for (const Col& c : cols) c.first->upload(*c.second, st);
+    d_p.alloc(8 * std::max<size_t>(p.size(), 1));
+    HIP_OK(hipMemsetAsync(d_p.as<void>(), 0, 8 * std::max<size_t>(p.size(), 1), st));
+    HIP_OK(hipStreamSynchronize(st));
+  }
+  void download(const DevBuf& d_p, hipStream_t st) {   // (queued: p holds the probabilities once st has been waited for)
+    if (!p.empty()) HIP_OK(hipMemcpyAsync(p.data(), d_p.as<void>(), 8 * p.size(), hipMemcpyDeviceToHost, st));
+  }
+  // The caller's columns per position (either may be null): label and p at the position of every item, 0 and NaN elsewhere.
+  void write(const std::vector<int32_t>& seq_off, int n, int32_t* label_out, double* prob_out) const {
+    const size_t n_seqpos = (size_t)(seq_off[n] - seq_off[0]);
+    if (label_out) std::fill(label_out, label_out + n_seqpos, 0);
+    if (prob_out) std::fill(prob_out, prob_out + n_seqpos, std::nan(""));
+    for (int t = 0; t < n; ++t)
+      for (int64_t k = off[t]; k < off[(size_t)t + 1]; ++k) {
+        const size_t at = (size_t)(seq_off[t] - seq_off[0]) + (size_t)i[(size_t)k];
+        if (label_out) label_out[at] = label[(size_t)k];
+        if (prob_out) prob_out[at] = p[(size_t)k];
+      }
+  }
+};
+
+// The loop call's launch_helix_units: the compaction of the helix call, the kept cells whose P reaches helix_pick_bound(min_prob) = the bound
+static HelixArgs loop_unit_pick(const LoopArgs& lk, double min_prob) {
+  HelixArgs hk;
+  std::memset(&hk, 0, sizeof(hk));
+  hk.plans = lk.plans; hk.idx = lk.idx; hk.seq_out = lk.seq_out; hk.out_stride = lk.out_stride; hk.skip_flagged = 1;
+  hk.okbits = lk.okbits; hk.min_prob = min_prob; hk.P = lk.P; hk.p_stride = lk.p_stride;
+  hk.n_units = lk.n_units; hk.ui = lk.ui; hk.ud = lk.ud; hk.u_stride = lk.u_stride;
+  return hk;
+}
+
 // ---- helix posteriors (helix_rules.h).  The host parses the stems of the caller's structures.  The scan's first sum
 // pass per group, then on the group's table slots, before the next group of the stream reuses them: P of every cell (k4_pairs), the
 // units -- the kept cells whose P reaches min_prob -- (k_helix_units), the chains of the units and of the stems (k_helix_chains) and
@@ -3111,60 +3163,17 @@ void Engine::helix_posteriors(const double* x, int n_param_in, int max_len, int 
   if (n_seq_ <= 0) throw StateError("helix_posteriors before load_batch");
   const int n = n_seq_;
   const bool want_list = min_prob < HUGE_VAL;
-  // the stems of every sequence: (i, d, len) of the outermost pair, sequences and 5' ends in increasing order
-  std::vector<int64_t> soff;
-  std::vector<int32_t> s_i, s_d, s_len;
-  if (structure) {
-    soff.assign((size_t)n + 1, 0);
-    std::vector<int32_t> mate, open;
-    for (int t = 0; t < n; ++t) {
-      const char* db = structure + (h_seq_off_[t] - h_seq_off_[0]);
-      const int L = h_seq_off_[t + 1] - h_seq_off_[t];
-      mate.assign((size_t)L, -1);
-      open.clear();
-      for (int p = 0; p < L; ++p) {
-        if (db[p] == '(') open.push_back(p);
-        else if (db[p] == ')') {
-          if (open.empty()) throw ArgError("helix_posteriors: unbalanced structure");
-          mate[p] = open.back(); mate[open.back()] = p;
-          open.pop_back();
-        } else if (db[p] != '.') throw ArgError("helix_posteriors: a structure holds ( ) . only");
-      }
-      if (!open.empty()) throw ArgError("helix_posteriors: unbalanced structure");
-      for (int p = 0; p < L; ++p) {
-        const int r = mate[p];
-        if (r < p || (p > 0 && r + 1 < L && mate[p - 1] == r + 1)) continue;   // (no 5' base, or not the outermost pair of its stem)
-        int len = 1;
-        while (p + len < r - len && mate[p + len] == r - len) ++len;
-        s_i.push_back(p); s_d.push_back(r - p + 1); s_len.push_back(len);
-      }
-      soff[(size_t)t + 1] = (int64_t)s_i.size();
-    }
-  }
-  const size_t n_stems = s_i.size();
-  std::vector<double> s_p(n_stems, 0.);
-  auto stems_out = [&] {   // the stems' columns of the caller, from s_p
-    if (!structure) return;
-    const size_t n_seqpos = (size_t)(h_seq_off_[n] - h_seq_off_[0]);
-    if (stem_len) std::fill(stem_len, stem_len + n_seqpos, 0);
-    if (stem_prob) std::fill(stem_prob, stem_prob + n_seqpos, std::nan(""));
-    for (int t = 0; t < n; ++t)
-      for (int64_t k = soff[t]; k < soff[(size_t)t + 1]; ++k) {
-        const size_t at = (size_t)(h_seq_off_[t] - h_seq_off_[0]) + (size_t)s_i[(size_t)k];
-        if (stem_len) stem_len[at] = s_len[(size_t)k];
-        if (stem_prob) stem_prob[at] = s_p[(size_t)k];
-      }
-  };
+  // the stems of every sequence: (i, d, len) of the outermost pair, sequences and 5' ends in increasing order; the label is len
+  StructItems stems;
+  std::vector<int32_t> s_d;
+  if (structure)
+    stems.parse("helix_posteriors", structure, h_seq_off_, n, [&](const int32_t* mate, int L) { structure_stems(mate, L, &stems.i, &s_d, &stems.label); });
   helices_.invalidate();
   if (streaming_) {
-    StagedList::Host list;
-    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
-      const size_t at = (size_t)(h_seq_off_[c0] - h_seq_off_[0]);
+    stream_listed(&Engine::helices_, n_param_in, [&](int, size_t at, Engine& e) {
       e.helix_posteriors(x, n_param_in, max_len, min_len, min_prob, nullptr, structure ? structure + at : nullptr,
                          stem_len ? stem_len + at : nullptr, stem_prob ? stem_prob + at : nullptr);
-      list.append(e.helices_, c0);
     });
-    helices_.adopt(list, st_);
     if (n_entries) *n_entries = helices_.count();
     return;
   }
@@ -3176,13 +3185,9 @@ void Engine::helix_posteriors(const double* x, int n_param_in, int max_len, int 
   HelixArgs ha;
   std::memset(&ha, 0, sizeof(ha));
   if (structure) {
-    d_hx_soff_.upload(soff, st_); d_hx_si_.upload(s_i, st_); d_hx_sd_.upload(s_d, st_); d_hx_slen_.upload(s_len, st_);
-    d_hx_sp_.alloc(8 * std::max<size_t>(n_stems, 1));
-    HIP_OK(hipMemsetAsync(d_hx_sp_.as<void>(), 0, 8 * std::max<size_t>(n_stems, 1), st_));
-    HIP_OK(hipStreamSynchronize(st_));   // (the host vectors go out of use with the copies; the probabilities are clear before any group runs)
-    ha.soff = d_hx_soff_.as<int64_t>();
+    stems.upload_cleared(d_hx_soff_, {{&d_hx_si_, &stems.i}, {&d_hx_sd_, &s_d}, {&d_hx_slen_, &stems.label}}, d_hx_sp_, st_);
+    ha.soff = d_hx_soff_.as<int64_t>(); ha.s_p = d_hx_sp_.as<double>();
     ha.s_i = d_hx_si_.as<int32_t>(); ha.s_d = d_hx_sd_.as<int32_t>(); ha.s_len = d_hx_slen_.as<int32_t>();
-    ha.s_p = d_hx_sp_.as<double>();
   }
   HIP_OK(hipEventRecord(ev_[1], st_));
   ha.plans = plan_.d_plans.as<SeqPlan>();
@@ -3252,9 +3257,9 @@ void Engine::helix_posteriors(const double* x, int n_param_in, int max_len, int 
   }
   finish_call(n_flagged, [&] {
     if (want_list) helices_.finish(st_); else helices_.set_empty();   // the list in (sequence, i, j, len) order
-    if (n_stems) HIP_OK(hipMemcpyAsync(s_p.data(), d_hx_sp_.as<void>(), 8 * n_stems, hipMemcpyDeviceToHost, st_));
+    stems.download(d_hx_sp_, st_);
   });
-  stems_out();
+  if (structure) stems.write(h_seq_off_, n, stem_len, stem_prob);
   if (n_entries) *n_entries = helices_.count();
 }
 
@@ -3270,10 +3275,9 @@ void Engine::helix_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* len, doub
 // (k_loop_unary), the two-loop values of their items and B, I (k_loop_items), the loops of the structures (k_loop_struct), and the
 // counts and the entries of both lists into the staging ranges (k_loop_seq).  The log-space form -- the fused scan kernel up to its
 // first outside pass, then the same rule on its dense tables -- for the sequences that leave the double range and under pipeline 3,
-// with k_loop_seq behind the launch.  Then the batch lists.  A closing entry is staged at the kept-cell prefix of its sequence, a
-// two-loop entry (item index, T) at the sequence's item_base: a sequence lists at most its items.  The bound is
-// loop_pick_bound(min_prob); where the counts are asked for it is 0, since they cover every kept cell.  Every buffer is the call's
-// own: leaves the lists of the last pair, conditional, stem and helix call alone.
+// with k_loop_seq behind the launch.  Then the batch lists (LoopLists, staged_list.h).  The bound is loop_pick_bound(min_prob); where
+// the counts are asked for it is 0, since they cover every kept cell.  Every buffer is the call's own: leaves the lists of the last
+// pair, conditional, stem and helix call alone.
 void Engine::loop_posteriors(const double* x, int n_param_in, double min_prob, double* counts, int64_t* n_closing, int64_t* n_two,
                              const char* structure, int32_t* loop_type, double* loop_prob) {
   require_device();
@@ -3283,87 +3287,19 @@ void Engine::loop_posteriors(const double* x, int n_param_in, double min_prob, d
   if (n_seq_ <= 0) throw StateError("loop_posteriors before load_batch");
   const int n = n_seq_;
   const bool want_list = min_prob < HUGE_VAL;
-  // the loops of every sequence: (type, i, d, k, l) of every pair, sequences and 5' ends in increasing order
-  std::vector<int64_t> soff;
-  std::vector<int32_t> s_t, s_i, s_d, s_k, s_l;
-  if (structure) {
-    soff.assign((size_t)n + 1, 0);
-    std::vector<int32_t> mate, open;
-    for (int t = 0; t < n; ++t) {
-      const char* db = structure + (h_seq_off_[t] - h_seq_off_[0]);
-      const int L = h_seq_off_[t + 1] - h_seq_off_[t];
-      mate.assign((size_t)L, -1);
-      open.clear();
-      for (int p = 0; p < L; ++p) {
-        if (db[p] == '(') open.push_back(p);
-        else if (db[p] == ')') {
-          if (open.empty()) throw ArgError("loop_posteriors: unbalanced structure");
-          mate[p] = open.back(); mate[open.back()] = p;
-          open.pop_back();
-        } else if (db[p] != '.') throw ArgError("loop_posteriors: a structure holds ( ) . only");
-      }
-      if (!open.empty()) throw ArgError("loop_posteriors: unbalanced structure");
-      for (int p = 0; p < L; ++p) {
-        const int r = mate[p];
-        if (r < p) continue;
-        int inner = 0, k = -1, l = -1;
-        for (int u = p + 1; u < r;) {
-          if (mate[u] > u) { if (inner++ == 0) { k = u; l = mate[u]; } u = mate[u] + 1; }
-          else ++u;
-        }
-        int type = LOOP_H;
-        if (inner > 1) type = LOOP_M;
-        else if (inner == 1) type = (k == p + 1 && l == r - 1) ? LOOP_S : ((k == p + 1) != (l == r - 1)) ? LOOP_B : LOOP_I;
-        const bool twol = type == LOOP_B || type == LOOP_I;
-        s_t.push_back(type); s_i.push_back(p); s_d.push_back(r - p + 1);
-        s_k.push_back(twol ? k : -1); s_l.push_back(twol ? l + 1 : -1);
-      }
-      soff[(size_t)t + 1] = (int64_t)s_i.size();
-    }
-  }
-  const size_t n_loops = s_i.size();
-  std::vector<double> s_p(n_loops, 0.);
-  auto loops_out = [&] {   // the loops' columns of the caller, from s_p
-    if (!structure) return;
-    const size_t n_seqpos = (size_t)(h_seq_off_[n] - h_seq_off_[0]);
-    if (loop_type) std::fill(loop_type, loop_type + n_seqpos, 0);
-    if (loop_prob) std::fill(loop_prob, loop_prob + n_seqpos, std::nan(""));
-    for (int t = 0; t < n; ++t)
-      for (int64_t k = soff[t]; k < soff[(size_t)t + 1]; ++k) {
-        const size_t at = (size_t)(h_seq_off_[t] - h_seq_off_[0]) + (size_t)s_i[(size_t)k];
-        if (loop_type) loop_type[at] = s_t[(size_t)k];
-        if (loop_prob) loop_prob[at] = s_p[(size_t)k];
-      }
-  };
-  n_closing_ = n_two_ = -1;
+  // the loops of every sequence: (type, i, d, k, l) of every pair, sequences and 5' ends in increasing order; the label is the type
+  StructItems loops;
+  std::vector<int32_t> s_d, s_k, s_l;
+  if (structure)
+    loops.parse("loop_posteriors", structure, h_seq_off_, n, [&](const int32_t* mate, int L) { structure_loops(mate, L, &loops.label, &loops.i, &s_d, &s_k, &s_l); });
+  loops_.invalidate();
   if (streaming_) {
-    std::vector<int32_t> c_seq, c_i, c_j, t_seq, t_i, t_j, t_k, t_l;
-    std::vector<double> c_v, t_p;
-    stream_call(n_param_in, [] {}, [&](int c0, int, Engine& e) {
-      const size_t at = (size_t)(h_seq_off_[c0] - h_seq_off_[0]);
-      int64_t mc = 0, mt = 0;
-      e.loop_posteriors(x, n_param_in, min_prob, counts ? counts + (size_t)LOOP_COLS * c0 : nullptr, &mc, &mt,
+    stream_listed(&Engine::loops_, n_param_in, [&](int c0, size_t at, Engine& e) {
+      e.loop_posteriors(x, n_param_in, min_prob, counts ? counts + (size_t)LOOP_COLS * c0 : nullptr, nullptr, nullptr,
                         structure ? structure + at : nullptr, loop_type ? loop_type + at : nullptr, loop_prob ? loop_prob + at : nullptr);
-      const size_t b = c_seq.size(), b2 = t_seq.size();
-      c_seq.resize(b + mc); c_i.resize(b + mc); c_j.resize(b + mc); c_v.resize(6 * (b + mc));
-      t_seq.resize(b2 + mt); t_i.resize(b2 + mt); t_j.resize(b2 + mt); t_k.resize(b2 + mt); t_l.resize(b2 + mt); t_p.resize(b2 + mt);
-      std::vector<double> p((size_t)mc), cols((size_t)LOOP_COLS * mc);
-      e.loop_closing_list(c_seq.data() + b, c_i.data() + b, c_j.data() + b, p.data(), cols.data(), mc);
-      for (size_t r = 0; r < (size_t)mc; ++r) {
-        c_v[6 * (b + r)] = p[r];
-        for (int k = 0; k < LOOP_COLS; ++k) c_v[6 * (b + r) + 1 + k] = cols[LOOP_COLS * r + k];
-        c_seq[b + r] += c0;
-      }
-      e.loop_two_list(t_seq.data() + b2, t_i.data() + b2, t_j.data() + b2, t_k.data() + b2, t_l.data() + b2, t_p.data() + b2, mt);
-      for (size_t r = b2; r < t_seq.size(); ++r) t_seq[r] += c0;
     });
-    d_lc_seq_.upload(c_seq, st_); d_lc_i_.upload(c_i, st_); d_lc_j_.upload(c_j, st_); d_lc_v_.upload(c_v, st_);
-    d_lt_seq_.upload(t_seq, st_); d_lt_i_.upload(t_i, st_); d_lt_j_.upload(t_j, st_); d_lt_k_.upload(t_k, st_);
-    d_lt_l_.upload(t_l, st_); d_lt_p_.upload(t_p, st_);
-    HIP_OK(hipStreamSynchronize(st_));   // (the host columns go out of use with the copies)
-    n_closing_ = (int64_t)c_seq.size(); n_two_ = (int64_t)t_seq.size();
-    if (n_closing) *n_closing = n_closing_;
-    if (n_two) *n_two = n_two_;
+    if (n_closing) *n_closing = loops_.n_closing();
+    if (n_two) *n_two = loops_.n_two();
     return;
   }
   require_resident("loop_posteriors", n_param_in);
@@ -3374,15 +3310,11 @@ void Engine::loop_posteriors(const double* x, int n_param_in, double min_prob, d
   LoopArgs la;
   std::memset(&la, 0, sizeof(la));
   if (structure) {
-    d_lp_soff_.upload(soff, st_); d_lp_st_.upload(s_t, st_); d_lp_si_.upload(s_i, st_); d_lp_sd_.upload(s_d, st_);
-    d_lp_sk_.upload(s_k, st_); d_lp_sl_.upload(s_l, st_);
-    d_lp_sp_.alloc(8 * std::max<size_t>(n_loops, 1));
-    HIP_OK(hipMemsetAsync(d_lp_sp_.as<void>(), 0, 8 * std::max<size_t>(n_loops, 1), st_));
-    HIP_OK(hipStreamSynchronize(st_));   // (the host vectors go out of use with the copies; the probabilities are clear before any group runs)
-    la.soff = d_lp_soff_.as<int64_t>();
+    loops.upload_cleared(d_lp_soff_, {{&d_lp_st_, &loops.label}, {&d_lp_si_, &loops.i}, {&d_lp_sd_, &s_d}, {&d_lp_sk_, &s_k}, {&d_lp_sl_, &s_l}},
+                         d_lp_sp_, st_);
+    la.soff = d_lp_soff_.as<int64_t>(); la.s_p = d_lp_sp_.as<double>();
     la.s_type = d_lp_st_.as<int32_t>(); la.s_i = d_lp_si_.as<int32_t>(); la.s_d = d_lp_sd_.as<int32_t>();
     la.s_k = d_lp_sk_.as<int32_t>(); la.s_l = d_lp_sl_.as<int32_t>();
-    la.s_p = d_lp_sp_.as<double>();
   }
   HIP_OK(hipEventRecord(ev_[1], st_));
   const PlanArrays pa_ = plan_.arrays();
@@ -3403,27 +3335,8 @@ void Engine::loop_posteriors(const double* x, int n_param_in, double min_prob, d
     HIP_OK(hipMemsetAsync(d_lp_counts_.as<void>(), 0, 8 * (size_t)LOOP_COLS * n, st_));
     la.counts = d_lp_counts_.as<double>();
   }
-  auto prefix_total = [&](const DevBuf& cnt, DevBuf& off) {   // off[0 .. n] = exclusive prefix of cnt[0 .. n) on st_; waits, returns the total
-    HIP_OK(launch_pair_prefix(cnt.as<int64_t>(), n, off.as<int64_t>(), st_));
-    int64_t total = 0;
-    HIP_OK(hipMemcpyAsync(&total, off.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st_));
-    HIP_OK(hipStreamSynchronize(st_));
-    return total;
-  };
-  if (want_list) {   // staging ranges: a closing entry per kept cell, a two-loop entry per item at the most
-    d_lp_kept_.alloc(8 * (size_t)n); d_lp_koff_.alloc(8 * ((size_t)n + 1));
-    d_lp_cnt_.alloc(8 * (size_t)n); d_lp_cnt2_.alloc(8 * (size_t)n);
-    d_lp_off_.alloc(8 * ((size_t)n + 1)); d_lp_off2_.alloc(8 * ((size_t)n + 1));
-    HIP_OK(launch_pair_kept(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, d_lp_kept_.as<int64_t>(), st_));
-    const size_t cap = (size_t)prefix_total(d_lp_kept_, d_lp_koff_), cap2 = (size_t)std::max<int64_t>(plan_.n_items, 0);
-    d_lp_sti_.alloc(4 * cap); d_lp_stj_.alloc(4 * cap); d_lp_stv_.alloc(8 * 6 * cap);
-    d_lp_st2i_.alloc(4 * cap2); d_lp_st2t_.alloc(8 * cap2);
-    HIP_OK(hipMemsetAsync(d_lp_cnt_.as<void>(), 0, 8 * (size_t)n, st_));
-    HIP_OK(hipMemsetAsync(d_lp_cnt2_.as<void>(), 0, 8 * (size_t)n, st_));
-    la.koff = d_lp_koff_.as<int64_t>(); la.cnt = d_lp_cnt_.as<int64_t>(); la.cnt2 = d_lp_cnt2_.as<int64_t>();
-    la.st_i = d_lp_sti_.as<int32_t>(); la.st_j = d_lp_stj_.as<int32_t>(); la.st_v = d_lp_stv_.as<double>();
-    la.st2_it = d_lp_st2i_.as<int32_t>(); la.st2_t = d_lp_st2t_.as<double>();
-  }
+  // staging ranges: a closing entry per kept cell, a two-loop entry per item at the most
+  if (want_list) loops_.begin(plan_.d_plans.as<SeqPlan>(), d_okbits1_.as<uint32_t>(), n, plan_.n_items, &la, st_);
   const bool work = la.want_units || structure;   // (else: nothing to compute, no sweep)
   auto at_slot = [&](LoopArgs& lk, size_t slot0) {
     lk.P = slot_scratch<double>(d_lp_P_, pcells, slot0);
@@ -3454,13 +3367,7 @@ void Engine::loop_posteriors(const double* x, int n_param_in, double min_prob, d
           pk.band_in = ak.band_in; pk.band_out = ak.band_out; pk.zs = ak.zs + ak.world;
           pk.P = lk.P;
           HIP_OK(launch_pair_cells(pk, G, (Lg + 1) * (Wg + 1), st));
-          HelixArgs hk;   // (the compaction of the helix call: the kept cells whose P reaches helix_pick_bound(min_prob) = the bound)
-          std::memset(&hk, 0, sizeof(hk));
-          hk.plans = lk.plans; hk.idx = lk.idx; hk.seq_out = lk.seq_out; hk.out_stride = lk.out_stride; hk.skip_flagged = 1;
-          hk.okbits = lk.okbits; hk.min_prob = counts ? 0. : min_prob;
-          hk.P = lk.P; hk.p_stride = pcells;
-          hk.n_units = lk.n_units; hk.ui = lk.ui; hk.ud = lk.ud; hk.u_stride = pcells;
-          HIP_OK(launch_helix_units(hk, G, st));
+          HIP_OK(launch_helix_units(loop_unit_pick(lk, counts ? 0. : min_prob), G, st));
           HIP_OK(launch_loop_unary(ak, lk, G, (Lg + 1) * (Wg + 1), st));
           HIP_OK(launch_loop_items(ak, lk, G, (Lg + 1) * (Wg + 1), st));
         }
@@ -3482,59 +3389,25 @@ void Engine::loop_posteriors(const double* x, int n_param_in, double min_prob, d
     });
   }
   finish_call(n_flagged, [&] {
-    if (want_list) {   // the lists: by (sequence, i, j), and by outer cell in that order, then in the plan's by-outer order
-      const size_t mc = (size_t)prefix_total(d_lp_cnt_, d_lp_off_), mt = (size_t)prefix_total(d_lp_cnt2_, d_lp_off2_);
-      d_lc_seq_.alloc(4 * mc); d_lc_i_.alloc(4 * mc); d_lc_j_.alloc(4 * mc); d_lc_v_.alloc(8 * 6 * mc);
-      d_lt_seq_.alloc(4 * mt); d_lt_i_.alloc(4 * mt); d_lt_j_.alloc(4 * mt); d_lt_k_.alloc(4 * mt); d_lt_l_.alloc(4 * mt);
-      d_lt_p_.alloc(8 * mt);
-      LoopListCols lc{plan_.d_plans.as<SeqPlan>(), pa_.items, d_lp_koff_.as<int64_t>(), d_lp_cnt_.as<int64_t>(), d_lp_off_.as<int64_t>(),
-                      d_lp_cnt2_.as<int64_t>(), d_lp_off2_.as<int64_t>(), d_lp_sti_.as<int32_t>(), d_lp_stj_.as<int32_t>(),
-                      d_lp_stv_.as<double>(), d_lp_st2i_.as<int32_t>(), d_lp_st2t_.as<double>(),
-                      d_lc_seq_.as<int32_t>(), d_lc_i_.as<int32_t>(), d_lc_j_.as<int32_t>(), d_lc_v_.as<double>(),
-                      d_lt_seq_.as<int32_t>(), d_lt_i_.as<int32_t>(), d_lt_j_.as<int32_t>(), d_lt_k_.as<int32_t>(), d_lt_l_.as<int32_t>(),
-                      d_lt_p_.as<double>()};
-      HIP_OK(launch_loop_scatter(lc, n, st_));
-      n_closing_ = (int64_t)mc; n_two_ = (int64_t)mt;
-    } else {
-      n_closing_ = n_two_ = 0;
-    }
-    if (n_loops) HIP_OK(hipMemcpyAsync(s_p.data(), d_lp_sp_.as<void>(), 8 * n_loops, hipMemcpyDeviceToHost, st_));
+    if (want_list) loops_.finish(plan_.d_plans.as<SeqPlan>(), pa_.items, st_); else loops_.set_empty();
+    loops.download(d_lp_sp_, st_);
     if (counts) HIP_OK(hipMemcpyAsync(counts, d_lp_counts_.as<void>(), 8 * (size_t)LOOP_COLS * n, hipMemcpyDeviceToHost, st_));
   });
-  loops_out();
-  if (n_closing) *n_closing = n_closing_;
-  if (n_two) *n_two = n_two_;
+  if (structure) loops.write(h_seq_off_, n, loop_type, loop_prob);
+  if (n_closing) *n_closing = loops_.n_closing();
+  if (n_two) *n_two = loops_.n_two();
 }
 
 void Engine::loop_closing_list(int32_t* seq, int32_t* i, int32_t* j, double* p, double* cols, int64_t cap) {
   require_device();
   DeviceGuard dg(device_);
-  if (n_closing_ < 0) throw StateError("loop_closing_list before loop_posteriors");
-  if (cap < n_closing_) throw ArgError("loop_closing_list: buffer too small");
-  const size_t m = (size_t)n_closing_;
-  if (m == 0) return;
-  auto get = [&](void* dst, const DevBuf& src, size_t bytes) { if (dst) HIP_OK(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost)); };
-  get(seq, d_lc_seq_, 4 * m); get(i, d_lc_i_, 4 * m); get(j, d_lc_j_, 4 * m);
-  if (p || cols) {
-    std::vector<double> v(6 * m);
-    get(v.data(), d_lc_v_, 8 * 6 * m);
-    for (size_t r = 0; r < m; ++r) {
-      if (p) p[r] = v[6 * r];
-      if (cols) for (int k = 0; k < LOOP_COLS; ++k) cols[LOOP_COLS * r + k] = v[6 * r + 1 + k];
-    }
-  }
+  loops_.fetch_closing(seq, i, j, p, cols, cap);
 }
 
 void Engine::loop_two_list(int32_t* seq, int32_t* i, int32_t* j, int32_t* k, int32_t* l, double* p, int64_t cap) {
   require_device();
   DeviceGuard dg(device_);
-  if (n_two_ < 0) throw StateError("loop_two_list before loop_posteriors");
-  if (cap < n_two_) throw ArgError("loop_two_list: buffer too small");
-  const size_t m = (size_t)n_two_;
-  if (m == 0) return;
-  auto get = [&](void* dst, const DevBuf& src, size_t bytes) { if (dst) HIP_OK(hipMemcpy(dst, src.as<void>(), bytes, hipMemcpyDeviceToHost)); };
-  get(seq, d_lt_seq_, 4 * m); get(i, d_lt_i_, 4 * m); get(j, d_lt_j_, 4 * m); get(k, d_lt_k_, 4 * m); get(l, d_lt_l_, 4 * m);
-  get(p, d_lt_p_, 8 * m);
+  loops_.fetch_two(seq, i, j, k, l, p, cap);
 }
 
 // ---- maximum expected accuracy motif alignments and site lists (node_mea_rules.h).  The node pass of

@@ -502,6 +502,48 @@ def test_groupings_thresholds_and_what_a_call_leaves_alone():
         np.testing.assert_allclose(got_n, want_n, rtol=1e-10, atol=1e-14)
 
 
+def test_a_streamed_call_without_lists_leaves_two_empty_lists():
+    """Two sequences that stream as two chunks (max_resident 1), min_prob +inf after a call with min_prob 0: the chunks keep no
+    lists, and the handle's lists are empty, with count 0 and not the -1 of 'no list'; the loops of the structures are those of the
+    first call.  Bit for bit in the log-space form (pipeline 3), whose sums have a fixed order.  The sum passes of the scaled-linear
+    form add with floating-point atomics, so two calls of it agree to rounding only, as with the thresholds and groupings above
+    (seen here: 5 of 6 probabilities of one sequence 2.2e-16 apart between two identical calls, none of the other's); there the
+    probabilities are held to that test's rtol 1e-10."""
+    lib = api.load_library()
+    dp = C.POINTER(C.c_double)
+    seqs, quals = batch((40, 37), seed=5, n_every=0, neg_every=0)
+    off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])])
+    for opts in (PIPELINE3, ()):
+        eng = engine_with(P1, 50, opts + (("max_resident", 1),))
+        eng.load_batch(seqs, quals)
+        x = lc.loop_params(eng)
+        structs = eng.mea_structures(x, 1.0)[0]
+        first = eng.loop_posteriors(x, 0.0, structures=structs)
+        assert sum(len(r[2]) for r in first[0]) > 0 and sum(len(r[4]) for r in first[1]) > 0 and sum(len(r[5]) for r in first[3]) > 2
+        got = eng.loop_posteriors(x, np.inf, structures=structs)
+        assert all(len(c[2]) == 0 for c in got[0]) and all(len(t[4]) == 0 for t in got[1])
+        # the counts of the lists and their fetches, past the wrapper: 0 entries, not "no list"
+        ltype, lprob, counts = np.full(off[-1], -1, dtype=np.int32), np.full(off[-1], -1.0), np.zeros((2, 5))
+        mc, mt = C.c_int64(-7), C.c_int64(-7)
+        assert lib.elemdp_loop_posteriors(eng._h, np.ascontiguousarray(x).ctypes.data_as(dp), eng.n_param, np.inf, counts.ctypes.data_as(dp),
+                                          C.byref(mc), C.byref(mt), "".join(structs).encode(), ltype.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          lprob.ctypes.data_as(dp)) == 0
+        assert (mc.value, mt.value) == (0, 0)
+        assert lib.elemdp_loop_closing_list(eng._h, None, None, None, None, None, 0) == 0       # (-4, ELEMDP_ESTATE, without lists)
+        assert lib.elemdp_loop_two_list(eng._h, None, None, None, None, None, None, 0) == 0
+        for k, (a, b) in enumerate(zip(got[3], first[3])):
+            p = b[5]
+            for what, q in (("wrapper", a[5]), ("library", lprob[off[k] + b[1]])):
+                print("%s, sequence %d, %s: loop_prob differs from the first call's in %d of %d, by at most %.3g"
+                      % (opts, k, what, (q != p).sum(), len(p), np.abs(q - p).max()))
+            assert np.array_equal(ltype[off[k] + b[1]], b[0]) and all(np.array_equal(u, v) for u, v in zip(a[:5], b[:5]))
+            if opts == PIPELINE3:
+                assert np.array_equal(a[5], p) and np.array_equal(lprob[off[k] + b[1]], p)
+            else:
+                np.testing.assert_allclose(a[5], p, rtol=1e-10, atol=1e-14)
+                np.testing.assert_allclose(lprob[off[k] + b[1]], p, rtol=1e-10, atol=1e-14)
+
+
 def test_refusals():
     lib = api.load_library()
     dp = C.POINTER(C.c_double)
